@@ -2,7 +2,7 @@
 """bench.py — stitched output megapixels / second on MI355X, with the HBM roofline of the resample+blit kernel and the
 CPU oracle timed beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` with N > 1 ALWAYS runs N ranks, one per GPU: under torchrun the ranks exist already (WORLD_SIZE is set); invoked
@@ -271,6 +271,24 @@ def canvas_pitch_leg(st, dev, torch):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20       # float32 rows of the sample; the row sums add H x 4 float64 (0.9 MB for the headline canvas)
+
+
+def dump_canvas(out_dir, canvas, np):
+    """--dump-outputs: what the last timed step handed its caller, the H x W x 4 RGBA8 canvas, as .npy files that two builds can
+    be compared with.  The whole canvas (439 MB as uint8) is over budget, so: a fixed, seeded sample of whole rows (float32,
+    canvas_rows.npy, with their indices in canvas_row_index.npy) and every row's per-channel sum (float64, exact;
+    canvas_row_sums.npy), which every byte of the canvas enters."""
+    a = canvas.cpu().numpy()
+    h, w = a.shape[:2]
+    n = max(1, min(h, DUMP_BUDGET_BYTES // (w * 4 * 4)))
+    rows = np.sort(np.random.default_rng(20261015).choice(h, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "canvas_rows.npy"), a[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "canvas_row_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "canvas_row_sums.npy"), a.sum(axis=1, dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------- N = 1
 def run_single(args):
     import numpy as np
@@ -295,6 +313,8 @@ def run_single(args):
         flat0 = L.lib.ist_debug_flat_launches()
         wall, ev_ms = time_job(job, sets, outs, steps, args.warmup, torch)
         flat = L.lib.ist_debug_flat_launches() - flat0 == PREROLL_LAUNCHES + args.warmup + steps
+        if args.dump_outputs and name == "uniform_vertical":
+            dump_canvas(args.dump_outputs, outs[(steps - 1) % nsets], np)      # time_job's last timed launch wrote this set
         mp = p.canvas_w * p.canvas_h / 1e6
         k_us = ev_ms * 1e3 / steps
         results[name] = {"canvas": [p.canvas_w, p.canvas_h], "out_MP": round(mp, 3), "steps": steps,
@@ -1300,6 +1320,7 @@ def main():
     ap.add_argument("--no-config5-host", action="store_true", help="configs[4]: skip the one-GPU host_in_host_out comparator (24.6 GB of pinned host memory on rank 0)")
     ap.add_argument("--launch-timeout", type=int, default=1500, help="seconds the self-started ranks may take")
     ap.add_argument("--group-timeout", type=int, default=300, help="seconds each single-process device-group leg may take")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step computed to DIR/*.npy (N = 1 only)")
     ap.add_argument("--group-leg", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--group-part", default="all", choices=["all", "host", "resident"], help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -1308,6 +1329,11 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.group_leg or args.dry_launch or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                              or os.environ.get("IST_BENCH_FORCE_SHARDED")):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the one-GPU line (run_single) only")
     args.out = StdoutGuard()
     have_ranks = "WORLD_SIZE" in os.environ
     if args.group_leg:

@@ -15,7 +15,6 @@ from tests import util as U
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODE = shutil.which("node")
 ADDON = os.path.join(ROOT, "node", "imagestitch.node")
-REF = "/root/reference"
 needs_node = pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the built addon is missing")
 
 
@@ -67,25 +66,53 @@ def test_node_host_rejects_like_the_reference_without_a_gpu(tmp_path):
     assert rc == 3 and out["code"] == "-5" and out["error"].startswith("拼图失败：")
 
 
+# Replays a Canvas call trace of the reference page (tests/golden/plan_goldens.json "calls": every call its onStitch made, in
+# order, with exact arguments) into node/canvas_shim.js in record-only mode and prints the shim's recorded launches.
+REPLAY_JS = r"""
+const shim = require(process.argv[1]);
+const calls = JSON.parse(require('fs').readFileSync(0, 'utf8'));
+(async () => {
+  const files = {};
+  for (const c of calls) if (c.op === 'drawImage') files['img' + c.img] = { width: c.bmp[0], height: c.bmp[1], data: new Uint8Array(4) };
+  const env = shim.makeEnvironment({ files, recordOnly: true });
+  const canvases = [], images = {};
+  for (const c of calls) {
+    if (c.op === 'createOffscreenCanvas') { canvases.push(env.wx.createOffscreenCanvas({ type: '2d', width: c.a[0], height: c.a[1] })); continue; }
+    const canvas = canvases[Number(c.canvas.slice(3))], ctx = canvas.getContext('2d');
+    if (c.op === 'fillStyle') ctx.fillStyle = c.v;
+    else if (c.op === 'drawImage') {
+      if (!images[c.img]) {
+        const bmp = images[c.img] = canvas.createImage();
+        await new Promise((res, rej) => { bmp.onload = res; bmp.onerror = rej; bmp.src = 'img' + c.img; });
+      }
+      ctx.drawImage(images[c.img], ...c.a);
+    } else if (c.op === 'export') {
+      await env.wx.canvasToTempFilePath({ canvas, x: c.a[0], y: c.a[1], width: c.a[2], height: c.a[3], destWidth: c.a[4], destHeight: c.a[5],
+                                          fileType: c.fileType, quality: c.quality });
+    } else if (typeof ctx[c.op] === 'function') ctx[c.op](...(c.a || []));
+    else throw new Error('trace op outside the stitch path: ' + c.op);
+  }
+  console.log(JSON.stringify(env.recorded));
+})().catch((e) => { console.error(String(e && e.stack || e)); process.exit(3); });
+"""
+
+
 @needs_node
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the authoring container")
 @pytest.mark.parametrize("name", ["G1_3x640x480_v_min_ios", "G2_9x12MP_v_lifted", "G3_9x12MP_h_devtools", "G5_mixed4_h_original_gap10_lifted",
                                   "G7_mixed7_v_min_gap10_android", "G8_orient5_v_lifted", "G8_orient6_v_lifted", "G8_orient7_v_lifted",
                                   "G8_orient8_v_lifted", "G9_gap20_h_original_ios"])
-def test_unmodified_reference_page_drives_the_shim_to_the_same_ops(name, goldens, tmp_path):
-    """Run the reference's own onStitch (read in place, nothing copied) against node/canvas_shim.js in record-only mode:
-    the op list it records must be exactly what ist_plan_ops produces for the same inputs (surface S2 == surface S1)."""
+def test_unmodified_reference_page_drives_the_shim_to_the_same_ops(name, goldens):
+    """Replay the Canvas calls the reference's own onStitch made (captured from the unmodified page, committed in
+    tests/golden/plan_goldens.json) into node/canvas_shim.js in record-only mode: the op list it records must be exactly
+    what ist_plan_ops produces for the same inputs (surface S2 == surface S1)."""
     case = goldens[name]
     inp, lim, _ = G.case_inputs(case)
-    job = {"mode": "reference", "recordOnly": True, "direction": inp["direction"], "gap": inp.get("gap", 0),
-           "stitchMode": inp.get("mode"), "platform": inp.get("platform", "devtools"), "out": str(tmp_path / "o.rgba"),
-           "images": [{"width": im["w"], "height": im["h"], "orientation": im.get("orientation", 1), "fileSize": im.get("fileSize", 0)} for im in inp["images"]]}
-    if inp.get("canvasLimit"):
-        job["canvasLimit"] = inp["canvasLimit"]
-    rc, out, err = _cli(job, tmp_path)
-    assert rc == 0, err
-    assert out["progress"] == 100
-    export = out["recorded"][-1]                    # the export launch (earlier entries are the 1x1 flushes)
+    assert case["error"] is None and case["calls"][-1]["op"] == "export"       # the page ran to its export
+    r = subprocess.run([NODE, "-e", REPLAY_JS, os.path.join(ROOT, "node", "canvas_shim.js")], input=json.dumps(case["calls"]),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    recorded = json.loads(r.stdout.strip().splitlines()[-1])
+    export = recorded[-1]                           # the export launch (earlier entries are the 1x1 flushes)
     opts = {"mode": inp.get("mode", "min"), "gap": inp.get("gap", 0), "platform": inp.get("platform", "devtools"),
             "maxSide": lim["deviceMaxCanvasSize"], "maxPixels": lim["deviceMaxCanvasPixels"]}
     p = ist.plan([{"width": im["w"], "height": im["h"], "orientation": im.get("orientation", 1), "fileSize": im.get("fileSize", 0)} for im in inp["images"]],
@@ -101,8 +128,8 @@ def test_unmodified_reference_page_drives_the_shim_to_the_same_ops(name, goldens
         if o["kind"] == "draw":
             assert q[8:12] == o["s"]
     if p.big_task:                                  # bigTask flushes after every image (index.js:1559-1566)
-        assert len(out["recorded"]) == len(inp["images"]) + 1
-        assert all(r["region"] == {"x": 0, "y": 0, "w": 1, "h": 1} for r in out["recorded"][:-1])
+        assert len(recorded) == len(inp["images"]) + 1
+        assert all(r["region"] == {"x": 0, "y": 0, "w": 1, "h": 1} for r in recorded[:-1])
 
 
 @needs_node
