@@ -69,6 +69,12 @@ class FlatCell(C.Structure):
                 ("src_offset", C.c_int64), ("bg", C.c_uint32), ("opaque", C.c_int32)]
 
 
+class StitchRequest(C.Structure):
+    _fields_ = [("images", C.POINTER(ImageDesc)), ("src", C.POINTER(C.c_void_p)), ("src_pitch", C.POINTER(C.c_size_t)),
+                ("n_images", C.c_int32), ("direction", C.c_int32), ("mode", C.c_int32), ("gap", C.c_double),
+                ("limits", C.POINTER(Limits)), ("filter", C.c_int32), ("reserved", C.c_int32)]
+
+
 class JobInfo(C.Structure):
     _fields_ = [("canvas_w", C.c_int64), ("canvas_h", C.c_int64), ("n_ops", C.c_int32), ("n_cells", C.c_int32),
                 ("n_tiles", C.c_int64), ("out_pixels", C.c_int64), ("src_pixels_touched", C.c_int64),
@@ -87,6 +93,7 @@ SYMBOLS = [
     ("ist_debug_host_sink_stitches", C.c_int64, []),
     ("ist_debug_flat_launches", C.c_int64, []),
     ("ist_debug_duplex_stitches", C.c_int64, []),
+    ("ist_debug_batch_launches", C.c_int64, []),
     ("ist_limits_default", None, [C.c_int, C.POINTER(Limits)]),
     ("ist_limits_unlimited", None, [C.POINTER(Limits)]),
     ("ist_plan_compute", C.c_int, [C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.POINTER(Plan)]),
@@ -108,6 +115,8 @@ SYMBOLS = [
     ("ist_job_info_get", C.c_int, [C.c_void_p, C.POINTER(JobInfo)]),
     ("ist_job_preferred_dst_pitch", C.c_size_t, [C.c_void_p]),
     ("ist_job_launch", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("ist_jobs_launch", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     ("ist_job_destroy", None, [C.c_void_p]),
     ("ist_group_create", C.c_void_p, [C.POINTER(C.c_int), C.c_int]),
     ("ist_group_destroy", None, [C.c_void_p]),
@@ -128,6 +137,7 @@ SYMBOLS = [
     ("ist_stitch_rgba8", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
                                    C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int, C.POINTER(Plan),
                                    C.POINTER(C.POINTER(C.c_uint8))]),
+    ("ist_stitch_rgba8_batch", C.c_int, [C.c_void_p, C.POINTER(StitchRequest), C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8))]),
     ("ist_render_rgba8", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int,
                                    C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                    C.POINTER(Region), C.c_void_p, C.c_size_t]),

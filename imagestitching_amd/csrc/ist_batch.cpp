@@ -1,0 +1,384 @@
+// ist_batch.cpp — many independent stitches per kernel launch (ist_jobs_launch, ist_stitch_rgba8_batch).
+//
+// Reference anchor: each entry of a batch is one unchanged Page.onStitch (miniprogram-stitch/miniprogram/pages/index/index.js:
+// 1186-1633; a request is capped at 9 images by index.js:311).  A service that renders many small requests pays, per request
+// and call, a blocking table upload (ist_job_create), a dependent kernel boundary (ist_job_launch) and - on the host path - its
+// own uploads, stream synchronisation and readback.  Here N jobs share one table copy and one launch per kernel form.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ist_ctx.h"
+#include "ist_internal.h"
+#include "ist_launch.h"
+
+using namespace ist;
+
+namespace {
+
+std::atomic<int64_t> g_batch_launches{0};
+
+constexpr int kKinds = 5;                               // launch_stitch's kernel forms (Compiled::kernel_kind)
+constexpr size_t kAlign = 256;
+size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+
+// The host path splits a batch so that sources + canvases of one sub-batch stay under this many device bytes (a larger
+// request runs alone, with the memory its single stitch would take).  Two sub-batches are in flight (Pipeline below), so the
+// context keeps at most twice this much device scratch for batches.
+constexpr size_t kSubBatchBytes = size_t(512) << 20;
+
+// A ring slot large enough for `bytes`, free to be overwritten: the kernels that read it last time have completed.
+int take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
+  ist_ctx::BatchSlot& s = ctx->batch_ring[ctx->batch_next];
+  ctx->batch_next = (ctx->batch_next + 1) % ist_ctx::kBatchRing;
+  if (s.pending) {
+    if (hipEventSynchronize(s.done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier batch failed"); }
+    s.pending = false;
+  }
+  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError(); s.done = nullptr;
+    return fail(IST_E_HIP, "hipEventCreate failed");
+  }
+  if (s.bytes < bytes) {
+    if (s.host) (void)hipHostFree(s.host);
+    dev_free(s.dev);
+    s.host = nullptr; s.dev = nullptr; s.bytes = 0;
+    size_t want = size_t(64) << 10;
+    while (want < bytes) want <<= 1;
+    if (hipHostMalloc(&s.host, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.host = nullptr; return fail(IST_E_NOMEM, "out of pinned host memory for the batch table"); }
+    if (dev_malloc(&s.dev, want) != 0) {
+      (void)hipGetLastError(); (void)hipHostFree(s.host); s.host = nullptr; s.dev = nullptr;
+      return fail(IST_E_NOMEM, "out of device memory for the batch table");
+    }
+    s.bytes = want;
+  }
+  *out = &s;
+  return IST_OK;
+}
+
+// bitmap bytes of one image of a request (the planner's rule: the decoded size when given, else the natural size)
+size_t image_bytes(const ist_image_desc& d) {
+  const size_t w = static_cast<size_t>(std::max(0, d.bmp_width > 0 ? d.bmp_width : d.width));
+  const size_t h = static_cast<size_t>(std::max(0, d.bmp_height > 0 ? d.bmp_height : d.height));
+  return w * 4 * h;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ist_debug_batch_launches(void) { return g_batch_launches.load(std::memory_order_relaxed); }
+
+int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, const size_t* src_pitch, const int* n_images,
+                    void* const* dst, const size_t* dst_pitch, void* stream) {
+  if (n_jobs <= 0) return fail(IST_E_INVALID, "ist_jobs_launch: no jobs");
+  if (n_jobs > kMaxBatchJobs) return fail(IST_E_UNSUPPORTED, "more than 4096 jobs in one batch");
+  if (!jobs || !n_images || !dst || !dst_pitch) return fail(IST_E_INVALID, "ist_jobs_launch: NULL argument");
+  ist_ctx* ctx = jobs[0] ? jobs[0]->ctx : nullptr;
+  for (int k = 0; k < n_jobs; ++k) {
+    if (!jobs[k]) return fail(IST_E_INVALID, "job " + std::to_string(k) + ": NULL job");
+    if (jobs[k]->ctx != ctx) return fail(IST_E_INVALID, "job " + std::to_string(k) + " belongs to another context than job 0");
+  }
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+    else if (cs != hipStreamCaptureStatusNone) return fail(IST_E_UNSUPPORTED, "ist_jobs_launch: graph capture of a batch is not supported");
+  }
+  // every job is checked (and its arguments built) before anything is enqueued
+  std::vector<LaunchArgs> args(static_cast<size_t>(n_jobs));
+  std::vector<const Compiled*> run(static_cast<size_t>(n_jobs), nullptr);
+  std::vector<char> flat_of(static_cast<size_t>(n_jobs), 0);
+  size_t first = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    if (n_images[k] < 0) return fail(IST_E_INVALID, "job " + std::to_string(k) + ": negative image count");
+    bool flat = false;
+    const int rc = job_launch_args(jobs[k], src ? src + first : nullptr, src_pitch ? src_pitch + first : nullptr, n_images[k], dst[k],
+                                   dst_pitch[k], &args[static_cast<size_t>(k)], &run[static_cast<size_t>(k)], &flat);
+    if (rc) { const std::string why = g_last_error; return fail(rc, "job " + std::to_string(k) + ": " + why); }
+    flat_of[static_cast<size_t>(k)] = flat ? 1 : 0;
+    first += static_cast<size_t>(n_images[k]);
+  }
+  // one group per kernel form; jobs without tiles (an empty clip) launch nothing
+  struct Group { std::vector<int> jobs; int64_t n_tiles = 0; unsigned lds = 0; size_t at_args = 0, at_begin = 0, at_chunk = 0; int64_t n_chunks = 0; };
+  Group grp[kKinds];
+  for (int k = 0; k < n_jobs; ++k) {
+    const Compiled& r = *run[static_cast<size_t>(k)];
+    if (r.info.n_tiles <= 0) continue;
+    const int kind = std::min(std::max(r.kernel_kind, 0), kKinds - 1);
+    Group& G = grp[kind];
+    G.jobs.push_back(k);
+    G.n_tiles += r.info.n_tiles;
+    G.lds = std::max(G.lds, static_cast<unsigned>(args[static_cast<size_t>(k)].lds_words) * 4u);
+  }
+  size_t total = 0;
+  for (Group& G : grp) {
+    if (G.jobs.empty()) continue;
+    if (G.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles of one kernel form");
+    const size_t m = G.jobs.size();
+    G.n_chunks = (G.n_tiles + (int64_t(1) << kBatchChunkLg) - 1) >> kBatchChunkLg;
+    G.at_args = total;  total = align_up(total + m * sizeof(LaunchArgs));
+    G.at_begin = total; total = align_up(total + (m + 1) * sizeof(int64_t));
+    G.at_chunk = total; total = align_up(total + static_cast<size_t>(G.n_chunks + 1) * sizeof(int32_t));
+  }
+  if (total == 0) return IST_OK;
+  std::lock_guard<std::mutex> lk(ctx->batch_mu);
+  ist_ctx::BatchSlot* slot = nullptr;
+  int rc = take_slot(ctx, total, &slot);
+  if (rc) return rc;
+  uint8_t* h = static_cast<uint8_t*>(slot->host);
+  for (const Group& G : grp) {
+    if (G.jobs.empty()) continue;
+    const size_t m = G.jobs.size();
+    LaunchArgs* ja = reinterpret_cast<LaunchArgs*>(h + G.at_args);
+    int64_t* tb = reinterpret_cast<int64_t*>(h + G.at_begin);
+    int32_t* cj = reinterpret_cast<int32_t*>(h + G.at_chunk);
+    int64_t t = 0;
+    for (size_t j = 0; j < m; ++j) {
+      const int k = G.jobs[j];
+      std::memcpy(&ja[j], &args[static_cast<size_t>(k)], sizeof(LaunchArgs));
+      tb[j] = t;
+      t += run[static_cast<size_t>(k)]->info.n_tiles;
+    }
+    tb[m] = t;
+    size_t j = 0;
+    for (int64_t c = 0; c < G.n_chunks; ++c) {            // the job that holds the chunk's first tile
+      const int64_t first_tile = c << kBatchChunkLg;
+      while (j + 1 < m && tb[j + 1] <= first_tile) ++j;
+      cj[c] = static_cast<int32_t>(j);
+    }
+    cj[G.n_chunks] = static_cast<int32_t>(m - 1);
+  }
+  uint8_t* d = static_cast<uint8_t*>(slot->dev);
+  if (hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "uploading the batch table failed"); }
+  int launches = 0;
+  for (int kind = 0; kind < kKinds && rc == IST_OK; ++kind) {
+    const Group& G = grp[kind];
+    if (G.jobs.empty()) continue;
+    BatchArgs b;
+    b.jobs = reinterpret_cast<const LaunchArgs*>(d + G.at_args);
+    b.tile_begin = reinterpret_cast<const int64_t*>(d + G.at_begin);
+    b.chunk_job = reinterpret_cast<const int32_t*>(d + G.at_chunk);
+    b.n_tiles = G.n_tiles;
+    rc = launch_stitch_batch(b, kind, G.lds, stream);
+    if (rc != IST_OK) break;
+    ++launches;
+    int64_t flats = 0;                                    // (bookkeeping only for what was launched)
+    for (const int k : G.jobs) { note_launch_stream(jobs[k], stream); flats += flat_of[static_cast<size_t>(k)]; }
+    count_flat_launches(flats);
+  }
+  // (recorded whatever happened: the copy is in flight and the slot must not be refilled before it is done)
+  if (hipEventRecord(slot->done, st) == hipSuccess) slot->pending = true;
+  else { (void)hipGetLastError(); (void)hipStreamSynchronize(st); }
+  g_batch_launches.fetch_add(launches, std::memory_order_relaxed);
+  return rc;
+}
+
+}  // extern "C"
+
+namespace {
+
+// jobs of a sub-batch whose kernel has completed (its half's kernel_done event): they are dropped without the stream wait of
+// ist_job_destroy, which would also wait for the launch of the NEXT sub-batch queued behind it on the same stream
+void drop_jobs(std::vector<ist_job*>* jobs) {
+  for (ist_job* j : *jobs) {
+    if (!j) continue;
+    j->launched = false; j->n_launched_on = 0; j->launched_many = false;
+    ist_job_destroy(j);
+  }
+  jobs->clear();
+}
+
+// The host path, sub-batch after sub-batch through the two halves of ctx->batch_half: sub-batch i is compiled, its tables and
+// sources go up on the staging stream while sub-batch i - 1's canvases come down on the aux stream, then one ist_jobs_launch on
+// ctx->stream renders it into half i % 2, and its canvases follow on the aux stream into pooled pinned blocks (the batch class of
+// the pool: a batch's caller holds all its results at once).  (What the single-stitch path does band by band, done sub-batch by
+// sub-batch: both directions of PCIe busy at once.)
+struct Pipeline {
+  ist_ctx* ctx;
+  const ist_stitch_request* reqs;
+  const std::vector<std::vector<ist_op>>& ops;
+  const std::vector<int>& n_ops;
+  const ist_plan* plans;
+  uint8_t** out_pixels;
+  std::vector<ist_job*> jobs[2];          // the jobs whose tables live in half 0 / 1
+  bool used[2] = {false, false};
+  int next = 0;
+
+  Pipeline(ist_ctx* c, const ist_stitch_request* r, const std::vector<std::vector<ist_op>>& o, const std::vector<int>& no, const ist_plan* p, uint8_t** out)
+      : ctx(c), reqs(r), ops(o), n_ops(no), plans(p), out_pixels(out) {}
+
+  // everything queued is done; jobs dropped.  Returns rc.
+  int finish(int rc) {
+    const bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess && (!ctx->aux || hipStreamSynchronize(ctx->aux) == hipSuccess);
+    if (!ok) { (void)hipGetLastError(); if (rc == IST_OK) rc = fail(IST_E_HIP, "result readback failed"); }
+    if (ctx->stager) (void)ctx->stager->sync();
+    drop_jobs(&jobs[0]); drop_jobs(&jobs[1]);
+    return rc;
+  }
+
+  int run(const std::vector<int>& idx) {
+    static const uint8_t transparent[4] = {0, 0, 0, 0};
+    const size_t n = idx.size();
+    const int hi = next; next ^= 1;
+    ist_ctx::BatchHalf& H = ctx->batch_half[hi];
+    std::vector<ist_job*> js(n, nullptr);
+    struct Guard { std::vector<ist_job*>* v; ~Guard() { if (v) for (ist_job* j : *v) if (j) ist_job_destroy(j); } } guard{&js};
+    std::vector<TableLayout> lay(n);
+    std::vector<size_t> tab_at(n, 0), dst_at(n, 0), canvas_bytes(n, 0);
+    std::vector<std::vector<size_t>> src_at(n);
+    size_t tab_total = 0, src_total = 0, dst_total = 0;
+    for (size_t q = 0; q < n; ++q) {
+      const int k = idx[q];
+      const ist_stitch_request& r = reqs[k];
+      const ist_plan& p = plans[k];
+      js[q] = job_compile(ctx, p.canvas_w, p.canvas_h, transparent, ops[static_cast<size_t>(k)].data(), n_ops[static_cast<size_t>(k)],
+                          r.images, r.n_images, r.filter, nullptr);
+      if (!js[q]) { const std::string why = g_last_error; return fail(g_last_code ? g_last_code : IST_E_INVALID, "request " + std::to_string(k) + ": " + why); }
+      lay[q] = table_layout(*js[q]);
+      tab_at[q] = tab_total; tab_total += align_up(lay[q].total);
+      src_at[q].assign(static_cast<size_t>(r.n_images), SIZE_MAX);      // the sources the job samples
+      for (const DevOp& o : js[q]->host.ops) {
+        if (o.image < 0 || src_at[q][static_cast<size_t>(o.image)] != SIZE_MAX) continue;
+        const int i = o.image;
+        if (!r.src || !r.src[i]) return fail(IST_E_DECODE, "request " + std::to_string(k) + ": 图片" + std::to_string(i) + "解码异常");
+        const size_t row = static_cast<size_t>(js[q]->host.img_w[i]) * 4;
+        if (r.src_pitch && r.src_pitch[i] < row) return fail(IST_E_INVALID, "request " + std::to_string(k) + ": src_pitch too small");
+        src_at[q][static_cast<size_t>(i)] = src_total;
+        src_total += align_up(row * static_cast<size_t>(js[q]->host.img_h[i]));
+      }
+      canvas_bytes[q] = static_cast<size_t>(p.canvas_w) * 4 * static_cast<size_t>(p.canvas_h);
+      dst_at[q] = dst_total; dst_total += align_up(canvas_bytes[q]);
+    }
+    // the half is free once the launch that read it (two sub-batches ago) is done; its canvases must also be down before they
+    // are re-allocated (a growth) or overwritten (ordered on the device below)
+    if (used[hi]) {
+      if (hipEventSynchronize(H.kernel_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
+      drop_jobs(&jobs[hi]);
+      if (H.dst_bytes < dst_total && hipEventSynchronize(H.read_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
+    }
+    if (!H.kernel_done && hipEventCreateWithFlags(&H.kernel_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.kernel_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
+    if (!H.read_done && hipEventCreateWithFlags(&H.read_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.read_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
+    int rc = grow_device(&H.tab, &H.tab_bytes, tab_total ? tab_total : kAlign);
+    if (!rc) rc = grow_device(&H.src, &H.src_bytes, src_total ? src_total : kAlign);
+    if (!rc) rc = grow_device(&H.dst, &H.dst_bytes, dst_total ? dst_total : kAlign);
+    if (rc) return rc;
+    uint8_t* dtab = static_cast<uint8_t*>(H.tab);
+    uint8_t* dsrc = static_cast<uint8_t*>(H.src);
+    uint8_t* ddst = static_cast<uint8_t*>(H.dst);
+    // every job's tables in one host block: one item of the staged upload
+    std::vector<uint8_t> blob(tab_total, 0);
+    std::vector<RowsCopy> up;
+    for (size_t q = 0; q < n; ++q) {
+      pack_tables(lay[q], blob.data() + tab_at[q]);
+      point_tables(js[q], lay[q], dtab + tab_at[q]);
+    }
+    if (tab_total) up.push_back(RowsCopy{dtab, blob.data(), nullptr, tab_total, tab_total, 1});
+    std::vector<const void*> lsrc;
+    std::vector<size_t> lpitch;
+    std::vector<int> lcount(n, 0);
+    std::vector<void*> ldst(n, nullptr);
+    std::vector<size_t> ldst_pitch(n, 0);
+    for (size_t q = 0; q < n; ++q) {
+      const ist_stitch_request& r = reqs[idx[q]];
+      const Compiled& h = js[q]->host;
+      for (int i = 0; i < r.n_images; ++i) {
+        const size_t at = src_at[q][static_cast<size_t>(i)];
+        if (at == SIZE_MAX) { lsrc.push_back(nullptr); lpitch.push_back(0); continue; }
+        const size_t row = static_cast<size_t>(h.img_w[i]) * 4;
+        up.push_back(RowsCopy{dsrc + at, r.src[i], nullptr, r.src_pitch ? r.src_pitch[i] : row, row, static_cast<size_t>(h.img_h[i])});
+        lsrc.push_back(dsrc + at);
+        lpitch.push_back(row);
+      }
+      lcount[q] = r.n_images;
+      ldst[q] = ddst + dst_at[q];
+      ldst_pitch[q] = static_cast<size_t>(plans[idx[q]].canvas_w) * 4;
+    }
+    if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device));
+    if (!ctx->workers) ctx->workers.reset(new WorkerPool());
+    rc = ctx->stager->upload_big(up, ctx->stream, ctx->workers.get());      // (one stream, big pieces: it shares PCIe with the downloads)
+    if (rc) return rc;
+    if (used[hi] && hipStreamWaitEvent(ctx->stream, H.read_done, 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering a sub-batch failed"); }
+    rc = ist_jobs_launch(js.data(), static_cast<int>(n), lsrc.data(), lpitch.data(), lcount.data(), ldst.data(), ldst_pitch.data(), ctx->stream);
+    if (rc) return rc;
+    if (hipEventRecord(H.kernel_done, ctx->stream) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
+    used[hi] = true;
+    jobs[hi] = js;
+    guard.v = nullptr;                                     // (the pipeline drops them once their launch is done)
+    // every canvas into a pinned block of its own, on the aux stream behind the launch
+    if (hipStreamWaitEvent(ctx->aux, H.kernel_done, 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering a readback failed"); }
+    for (size_t q = 0; q < n; ++q) {
+      uint8_t* host = static_cast<uint8_t*>(pool_take_batch(canvas_bytes[q]));
+      if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the results");
+      out_pixels[idx[q]] = host;                           // (the caller's release() gives it back, after finish())
+      if (hipMemcpyAsync(host, ddst + dst_at[q], canvas_bytes[q], hipMemcpyDeviceToHost, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "queueing a readback failed"); }
+    }
+    if (hipEventRecord(H.read_done, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
+    return IST_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_pixels))) return fail(IST_E_INVALID, "ist_stitch_rgba8_batch: NULL argument");
+  const size_t n = static_cast<size_t>(n_reqs);
+  for (size_t k = 0; k < n; ++k) { out_pixels[k] = nullptr; std::memset(&out_plans[k], 0, sizeof(ist_plan)); }
+  auto release = [&]() {
+    for (size_t k = 0; k < n; ++k) {
+      ist_plan_free(&out_plans[k]);
+      std::memset(&out_plans[k], 0, sizeof(ist_plan));
+      if (out_pixels[k]) { ist_free(out_pixels[k]); out_pixels[k] = nullptr; }
+    }
+  };
+  // plan every request (pure CPU): the op list of each, and what it will hold on the device
+  std::vector<std::vector<ist_op>> ops(n);
+  std::vector<int> n_ops(n, 0);
+  std::vector<size_t> bytes(n, 0);
+  for (size_t k = 0; k < n; ++k) {
+    const ist_stitch_request& r = reqs[k];
+    if (r.n_images <= 0) continue;                        // index.js:1189: nothing to do for this entry
+    ist_limits lim;
+    if (r.limits) lim = *r.limits; else ist_limits_unlimited(&lim);
+    int rc = ist_plan_compute(r.images, r.n_images, r.direction, r.mode, r.gap, &lim, &out_plans[k]);
+    if (rc == IST_NOTHING_TO_DO) { std::memset(&out_plans[k], 0, sizeof(ist_plan)); continue; }
+    if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
+    ops[k].resize(static_cast<size_t>(out_plans[k].n_rects) + 1);
+    rc = ist_plan_ops(&out_plans[k], r.images, r.n_images, ops[k].data(), &n_ops[k]);
+    if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
+    bytes[k] = static_cast<size_t>(out_plans[k].canvas_w) * 4 * static_cast<size_t>(out_plans[k].canvas_h);
+    for (int i = 0; i < r.n_images; ++i) bytes[k] += image_bytes(r.images[i]);
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) { release(); return fail(IST_E_NO_DEVICE, "hipSetDevice failed"); }
+  int rc = ctx_aux_stream(ctx);
+  if (rc) { release(); return rc; }
+  // sub-batches: consecutive requests while their device bytes fit the budget, and at most kMaxBatchJobs of them
+  Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels);
+  std::vector<int> idx;
+  size_t held = 0;
+  for (size_t k = 0; k <= n && rc == IST_OK; ++k) {
+    const bool live = k < n && n_ops[k] > 0;
+    const bool flush = !idx.empty() && (k == n || (live && (held + bytes[k] > kSubBatchBytes || idx.size() >= static_cast<size_t>(kMaxBatchJobs))));
+    if (flush) { rc = pipe.run(idx); idx.clear(); held = 0; }
+    if (live) { idx.push_back(static_cast<int>(k)); held += bytes[k]; }
+  }
+  rc = pipe.finish(rc);
+  if (rc) { const std::string why = g_last_error; const int code = g_last_code; release(); g_last_error = why; g_last_code = code; return rc; }
+  return IST_OK;
+}
+
+}  // extern "C"

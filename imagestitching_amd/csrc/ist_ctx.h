@@ -14,6 +14,7 @@
 
 #include "ist_host.h"
 #include "ist_internal.h"
+#include "ist_launch.h"
 
 struct ist_ctx {
   int device = 0;
@@ -50,6 +51,23 @@ struct ist_ctx {
   std::unique_ptr<ist::Stager> stager;   // pinned staging ring, built on first use
   bool timing_on = false;                // ist_ctx_set_timing: the file pipeline records its phase times (adds a sync per phase)
   double last_ms[IST_PHASE_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // ist_jobs_launch: the per-launch job table goes up through a small ring of (pinned block, device block, event).  The event is
+  // recorded behind the kernels that read the slot's device block; the slot is filled again only after it has completed.
+  static constexpr int kBatchRing = 4;
+  struct BatchSlot { void* host = nullptr; void* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool pending = false; };
+  BatchSlot batch_ring[kBatchRing];
+  int batch_next = 0;
+  std::mutex batch_mu;
+  // ist_stitch_rgba8_batch: two halves of device scratch (op tables, sources, canvases of one sub-batch each), so that one sub-batch's
+  // sources go up while the previous one's canvases come down; grow-only, each bounded by the sub-batch budget (ist_batch.cpp)
+  struct BatchHalf {
+    void* tab = nullptr; size_t tab_bytes = 0;
+    void* src = nullptr; size_t src_bytes = 0;
+    void* dst = nullptr; size_t dst_bytes = 0;
+    hipEvent_t kernel_done = nullptr;    // behind the launch that reads tab / src
+    hipEvent_t read_done = nullptr;      // behind the downloads that read dst
+  };
+  BatchHalf batch_half[2];
 };
 
 namespace ist {
@@ -96,6 +114,23 @@ struct DeviceGuard {
 
 // grow-only device scratch
 int grow_device(void** p, size_t* have, size_t need);
+
+// ---- pieces of ist_job_create / ist_job_launch shared with the batch entry points (ist_batch.cpp) ----
+// compile an op list into a job whose tables are NOT uploaded yet (d_tables stays NULL: ist_job_destroy then frees no table block)
+ist_job* job_compile(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+                     const ist_image_desc* images, int n_images, int filter, const ist_region* clip);
+// where the job's tables (and its flat twin's) sit in one block: 256-byte aligned sections, `total` bytes
+struct TableLayout { size_t bytes[2][5] = {}; size_t at[2][5] = {}; const void* from[2][5] = {}; size_t total = 0; };
+TableLayout table_layout(const ist_job& job);
+void pack_tables(const TableLayout& L, uint8_t* blob);             // host image of the block
+void point_tables(ist_job* job, const TableLayout& L, uint8_t* base);   // the job's table pointers into a device block at base
+// every rule of one launch and the kernel arguments it would pass (the flat form when the caller's rows are dense); no side effects
+int job_launch_args(const ist_job* job, const void* const* src, const size_t* src_pitch, int n_images, void* dst, size_t dst_pitch,
+                    LaunchArgs* out, const Compiled** out_run, bool* out_flat);
+// the job was launched on `stream` (ist_job_destroy waits for it)
+void note_launch_stream(ist_job* job, void* stream);
+void count_flat_launches(int64_t n);
+int ctx_aux_stream(ist_ctx* ctx);        // the context's second stream (made on first use)
 
 
 }  // namespace ist

@@ -28,6 +28,9 @@ namespace ist {
 
 // ---- pool of pinned result buffers (process-wide) -----------------------------------------------------------------
 void* pool_take(size_t bytes);          // pinned, portable (any device may DMA into it); nullptr on failure
+// the same for the results of batch calls: a class of blocks of its own, of which up to 8 GiB / 256 blocks are kept idle for the next
+// batch (a batch's caller holds all of its results at once); ist_pool_trim releases them like the others
+void* pool_take_batch(size_t bytes);
 bool pool_give(void* p);                // true when p came from pool_take (the block is kept for reuse or released)
 void pool_trim();                       // release every cached block
 

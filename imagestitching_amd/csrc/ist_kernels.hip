@@ -1065,6 +1065,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WA
   }
 }
 
+// ------------------------------------------------------------------------------------------------ batch
+// Many independent jobs in one launch (ist_jobs_launch): the tiles of all jobs are numbered job-major, workgroup t finds its job
+// and runs that job's tile through the same run_tile as the single-job kernels.  The job lookup is wave-uniform and costs two
+// dependent scalar loads in the common case: chunk_job[c] is the job holding tile 64c, and a chunk that holds no job boundary
+// (chunk_job[c] == chunk_job[c + 1]) needs no search.  Otherwise a binary search over the at most 64 jobs that start inside it.
+// The job's LaunchArgs are read from the per-launch table through the constant address space, so that they stay scalar loads
+// (s_load_*) after inlining exactly as a kernarg LaunchArgs does.
+typedef const __attribute__((address_space(4))) LaunchArgs ConstLaunchArgs;
+typedef const __attribute__((address_space(4))) int64_t ConstI64;
+typedef const __attribute__((address_space(4))) int32_t ConstI32;
+
+IST_DEV int batch_job_of(const BatchArgs& B, int64_t tile) {
+  ConstI32* cj = (ConstI32*)B.chunk_job;
+  ConstI64* tb = (ConstI64*)B.tile_begin;
+  const int64_t c = tile >> kBatchChunkLg;
+  int lo = cj[c], hi = cj[c + 1];
+  while (lo < hi) {                                   // the last job whose first tile is <= tile
+    const int mid = (lo + hi + 1) >> 1;
+    if (tb[mid] <= tile) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+
+template <int PATHS, int V>
+__global__ __launch_bounds__(256) void ist_stitch_batch_kernel(const BatchArgs B) {
+  const int64_t tile = static_cast<int64_t>(blockIdx.x);
+  const int j = batch_job_of(B, tile);
+  const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
+  run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
+}
+
+template <int PATHS, int V>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_batch_area_kernel(const BatchArgs B) {
+  const int64_t tile = static_cast<int64_t>(blockIdx.x);
+  const int j = batch_job_of(B, tile);
+  const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
+  run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
+}
+
+int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream) {
+  if (args.n_tiles <= 0) return IST_OK;
+  if (args.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>(args.n_tiles)), block(256);
+  // the same instantiations by kind as launch_stitch (shipped copy variant 0, one workgroup per tile)
+  if (kind == 0) hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY, 0>), grid, block, dyn_lds_bytes, s, args);
+  else if (kind == 1) hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE, 0>), grid, block, dyn_lds_bytes, s, args);
+  else if (kind == 3) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
+  else if (kind == 4) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
+  else hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL, 0>), grid, block, dyn_lds_bytes, s, args);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(IST_E_HIP, std::string("batch kernel launch failed: ") + hipGetErrorString(e));
+  return IST_OK;
+}
+
 template <int PATHS, int V, bool PERSIST>
 static void launch_one(const LaunchArgs& args, int64_t n_tiles, hipStream_t stream, int persist_blocks, unsigned dyn_lds) {
   const unsigned grid = PERSIST ? static_cast<unsigned>(std::min<int64_t>(n_tiles, persist_blocks)) : static_cast<unsigned>(n_tiles);

@@ -34,6 +34,20 @@ struct LaunchArgs {
 // with just those paths is launched
 int launch_stitch(const LaunchArgs& args, int64_t n_tiles, int kind, void* stream);
 
+// Several jobs of one kind in ONE launch (ist_jobs_launch).  Three device tables, uploaded per launch:
+//   jobs[n_jobs]            each job's LaunchArgs, as ist_job_launch would pass them by value
+//   tile_begin[n_jobs + 1]  first tile of every job (tiles are numbered job-major); tile_begin[n_jobs] = n_tiles
+//   chunk_job[n_chunks + 1] the job holding tile c << kBatchChunkLg (the last entry: n_jobs - 1)
+constexpr int kBatchChunkLg = 6;             // chunks of 64 tiles
+constexpr int kMaxBatchJobs = 4096;
+struct BatchArgs {
+  const LaunchArgs* jobs;
+  const int64_t* tile_begin;
+  const int32_t* chunk_job;
+  int64_t n_tiles;
+};
+int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream);
+
 }  // namespace ist
 
 #endif  // IST_LAUNCH_H_

@@ -128,6 +128,8 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
 
 }  // namespace
 
+int ist::ctx_aux_stream(ist_ctx* ctx) { return ensure_aux(ctx); }
+
 extern "C" {
 
 int64_t ist_debug_device_allocs(void) { return g_dev_allocs.load(std::memory_order_relaxed); }
@@ -195,6 +197,16 @@ void ist_ctx_destroy(ist_ctx* ctx) {
   if (ctx->png2) { (void)hipStreamSynchronize(ctx->png2); (void)hipStreamDestroy(ctx->png2); }
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (const ist_ctx::TableBlock& b : ctx->table_pool) dev_free(b.p);
+  for (ist_ctx::BatchSlot& s : ctx->batch_ring) {
+    if (s.done) { (void)hipEventSynchronize(s.done); (void)hipEventDestroy(s.done); }
+    if (s.host) (void)hipHostFree(s.host);
+    dev_free(s.dev);
+  }
+  for (ist_ctx::BatchHalf& h : ctx->batch_half) {
+    dev_free(h.tab); dev_free(h.src); dev_free(h.dst);
+    if (h.kernel_done) (void)hipEventDestroy(h.kernel_done);
+    if (h.read_done) (void)hipEventDestroy(h.read_done);
+  }
   ctx->workers.reset();
   ctx->stager.reset();
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -206,9 +218,13 @@ static std::atomic<int64_t> g_duplex_stitches{0};
 
 int64_t ist_debug_flat_launches(void) { return g_flat_launches.load(); }
 
-ist_job* ist_job_create(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
-                        const ist_op* ops, int n_ops, const ist_image_desc* images, int n_images,
-                        int filter, const ist_region* clip) {
+}  // extern "C"
+
+namespace ist {
+void count_flat_launches(int64_t n) { g_flat_launches.fetch_add(n, std::memory_order_relaxed); }
+
+ist_job* job_compile(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+                     const ist_image_desc* images, int n_images, int filter, const ist_region* clip) {
   if (!ctx) { fail(IST_E_NO_CONTEXT, "无法获取绘图上下文"); return nullptr; }
   if (n_images > kMaxImages) { fail(IST_E_UNSUPPORTED, "more than 128 images in one launch"); return nullptr; }
   static const uint8_t transparent[4] = {0, 0, 0, 0};
@@ -219,67 +235,42 @@ ist_job* ist_job_create(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const 
     return nullptr;
   for (const DevOp& o : job->host.ops) job->max_image = std::max(job->max_image, o.image);
   job->flat = compile_flat_twin(canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, n_images, filter, job->host);
-  DeviceGuard g(ctx->device);
-  // the tables (the job's five and, when it has one, its flat twin's five) travel as ONE allocation and ONE copy (256-byte aligned sections)
-  const Compiled* hs[2] = {&job->host, job->flat ? &job->flat->host : nullptr};
-  DevTables* dts[2] = {&job->dt, job->flat ? &job->flat_dt : nullptr};
-  size_t bytes[2][5], at[2][5], total = 0;
-  const void* from[2][5];
+  return job.release();
+}
+
+TableLayout table_layout(const ist_job& job) {
+  TableLayout L;
+  const Compiled* hs[2] = {&job.host, job.flat ? &job.flat->host : nullptr};
   for (int t = 0; t < 2; ++t) {
     if (!hs[t]) continue;
     const Compiled& h = *hs[t];
     const size_t b[5] = {h.ops.size() * sizeof(DevOp), h.cells.size() * sizeof(DevCell), h.bands.size() * sizeof(DevBand),
                          h.stacks.size() * sizeof(int32_t), h.tiles.size() * sizeof(DevTile)};
     const void* f[5] = {h.ops.data(), h.cells.data(), h.bands.data(), h.stacks.data(), h.tiles.data()};
-    for (int k = 0; k < 5; ++k) { bytes[t][k] = b[k]; from[t][k] = f[k]; at[t][k] = total; total += (b[k] + 255) & ~static_cast<size_t>(255); }
+    for (int k = 0; k < 5; ++k) { L.bytes[t][k] = b[k]; L.from[t][k] = f[k]; L.at[t][k] = L.total; L.total += (b[k] + 255) & ~static_cast<size_t>(255); }
   }
-  if (total) {
-    std::vector<uint8_t> blob(total, 0);
-    for (int t = 0; t < 2; ++t)
-      for (int k = 0; k < 5 && hs[t]; ++k) if (bytes[t][k]) std::memcpy(blob.data() + at[t][k], from[t][k], bytes[t][k]);
-    {                                       // a block of an earlier job of this context, if one is large enough
-      std::lock_guard<std::mutex> lk(ctx->table_mu);
-      for (size_t k = 0; k < ctx->table_pool.size(); ++k)
-        if (ctx->table_pool[k].bytes >= total && ctx->table_pool[k].bytes <= 4 * total + (1u << 20)) {
-          job->d_tables = ctx->table_pool[k].p; job->d_tables_bytes = ctx->table_pool[k].bytes;
-          ctx->table_pool.erase(ctx->table_pool.begin() + static_cast<std::ptrdiff_t>(k));
-          break;
-        }
-    }
-    if (!job->d_tables && dev_malloc(reinterpret_cast<void**>(&job->d_tables), total) == hipSuccess) job->d_tables_bytes = total;
-    if (!job->d_tables ||
-        hipMemcpy(job->d_tables, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {      // blocking: the tables are in place when this returns
-      (void)hipGetLastError();
-      fail(IST_E_HIP, "uploading the op tables failed");
-      ist_job_destroy(job.release());
-      return nullptr;
-    }
-    for (int t = 0; t < 2; ++t) {
-      if (!hs[t]) continue;
-      dts[t]->ops = bytes[t][0] ? reinterpret_cast<DevOp*>(job->d_tables + at[t][0]) : nullptr;
-      dts[t]->cells = bytes[t][1] ? reinterpret_cast<DevCell*>(job->d_tables + at[t][1]) : nullptr;
-      dts[t]->bands = bytes[t][2] ? reinterpret_cast<DevBand*>(job->d_tables + at[t][2]) : nullptr;
-      dts[t]->stacks = bytes[t][3] ? reinterpret_cast<int32_t*>(job->d_tables + at[t][3]) : nullptr;
-      dts[t]->tiles = bytes[t][4] ? reinterpret_cast<DevTile*>(job->d_tables + at[t][4]) : nullptr;
-    }
+  return L;
+}
+
+void pack_tables(const TableLayout& L, uint8_t* blob) {
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 5; ++k) if (L.bytes[t][k]) std::memcpy(blob + L.at[t][k], L.from[t][k], L.bytes[t][k]);
+}
+
+void point_tables(ist_job* job, const TableLayout& L, uint8_t* base) {
+  DevTables* dts[2] = {&job->dt, job->flat ? &job->flat_dt : nullptr};
+  for (int t = 0; t < 2; ++t) {
+    if (!dts[t]) continue;
+    dts[t]->ops = L.bytes[t][0] ? reinterpret_cast<DevOp*>(base + L.at[t][0]) : nullptr;
+    dts[t]->cells = L.bytes[t][1] ? reinterpret_cast<DevCell*>(base + L.at[t][1]) : nullptr;
+    dts[t]->bands = L.bytes[t][2] ? reinterpret_cast<DevBand*>(base + L.at[t][2]) : nullptr;
+    dts[t]->stacks = L.bytes[t][3] ? reinterpret_cast<int32_t*>(base + L.at[t][3]) : nullptr;
+    dts[t]->tiles = L.bytes[t][4] ? reinterpret_cast<DevTile*>(base + L.at[t][4]) : nullptr;
   }
-  return job.release();
 }
 
-int ist_job_info_get(const ist_job* job, ist_job_info* out) {
-  if (!job || !out) return fail(IST_E_INVALID, "ist_job_info_get: NULL argument");
-  *out = job->host.info;
-  return IST_OK;
-}
-
-size_t ist_job_preferred_dst_pitch(const ist_job* job) {
-  if (!job) return 0;
-  const size_t row = static_cast<size_t>(job->host.rx1 - job->host.rx0) * 4;      // (a clipped job renders into a buffer as wide as its region)
-  return job->flat ? row : (row + 4095) & ~static_cast<size_t>(4095);
-}
-
-int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch, int n_images, void* dst,
-                   size_t dst_pitch, void* stream) {
+int job_launch_args(const ist_job* job, const void* const* src, const size_t* src_pitch, int n_images, void* dst, size_t dst_pitch,
+                    LaunchArgs* out, const Compiled** out_run, bool* out_flat) {
   if (!job || !dst) return fail(IST_E_INVALID, "ist_job_launch: NULL argument");
   if (n_images <= job->max_image) return fail(IST_E_DECODE, "图片" + std::to_string(job->max_image) + "解码异常: source table too short");
   if (n_images > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one launch");
@@ -287,7 +278,7 @@ int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch
   // only the rendered region is ever addressed, so a compact band buffer (pitch = region width) is legal when the
   // caller biases dst by -(ry0*pitch + rx0*4)
   if (dst_pitch < static_cast<size_t>(h.rx1 - h.rx0) * 4 || (dst_pitch & 3)) return fail(IST_E_INVALID, "dst_pitch too small or not a multiple of 4");
-  LaunchArgs a;
+  LaunchArgs& a = *out;
   std::memset(&a, 0, sizeof(a));
   a.dst = static_cast<uint8_t*>(dst);
   a.dst_pitch = dst_pitch;
@@ -317,7 +308,6 @@ int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch
       f.pitch[k] = kFlatPitch;
     }
     a = f;
-    g_flat_launches.fetch_add(1, std::memory_order_relaxed);
   }
   a.ops = dt.ops; a.cells = dt.cells; a.bands = dt.bands; a.stacks = dt.stacks;
   a.tiles = run.tiles.empty() ? nullptr : dt.tiles;
@@ -327,20 +317,84 @@ int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch
   a.lds_words = run.lds_words;
   a.lds_half = run.lds_half;
   a.pad_ = 0;
+  *out_run = &run;
+  *out_flat = dense;
+  return IST_OK;
+}
+
+void note_launch_stream(ist_job* job, void* stream) {
+  std::lock_guard<std::mutex> lk(job->launch_mu);
+  job->launched = true;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int k = 0;
+  while (k < job->n_launched_on && job->launched_on[k] != st) ++k;
+  if (k == job->n_launched_on) {
+    if (k < ist_job::kStreams) job->launched_on[job->n_launched_on++] = st;
+    else job->launched_many = true;
+  }
+}
+}  // namespace ist
+
+extern "C" {
+
+ist_job* ist_job_create(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
+                        const ist_op* ops, int n_ops, const ist_image_desc* images, int n_images,
+                        int filter, const ist_region* clip) {
+  std::unique_ptr<ist_job> job(job_compile(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, n_images, filter, clip));
+  if (!job) return nullptr;
+  DeviceGuard g(ctx->device);
+  // the tables (the job's five and, when it has one, its flat twin's five) travel as ONE allocation and ONE copy (256-byte aligned sections)
+  const TableLayout lay = table_layout(*job);
+  const size_t total = lay.total;
+  if (total) {
+    std::vector<uint8_t> blob(total, 0);
+    pack_tables(lay, blob.data());
+    {                                       // a block of an earlier job of this context, if one is large enough
+      std::lock_guard<std::mutex> lk(ctx->table_mu);
+      for (size_t k = 0; k < ctx->table_pool.size(); ++k)
+        if (ctx->table_pool[k].bytes >= total && ctx->table_pool[k].bytes <= 4 * total + (1u << 20)) {
+          job->d_tables = ctx->table_pool[k].p; job->d_tables_bytes = ctx->table_pool[k].bytes;
+          ctx->table_pool.erase(ctx->table_pool.begin() + static_cast<std::ptrdiff_t>(k));
+          break;
+        }
+    }
+    if (!job->d_tables && dev_malloc(reinterpret_cast<void**>(&job->d_tables), total) == hipSuccess) job->d_tables_bytes = total;
+    if (!job->d_tables ||
+        hipMemcpy(job->d_tables, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {      // blocking: the tables are in place when this returns
+      (void)hipGetLastError();
+      fail(IST_E_HIP, "uploading the op tables failed");
+      ist_job_destroy(job.release());
+      return nullptr;
+    }
+    point_tables(job.get(), lay, job->d_tables);
+  }
+  return job.release();
+}
+
+int ist_job_info_get(const ist_job* job, ist_job_info* out) {
+  if (!job || !out) return fail(IST_E_INVALID, "ist_job_info_get: NULL argument");
+  *out = job->host.info;
+  return IST_OK;
+}
+
+size_t ist_job_preferred_dst_pitch(const ist_job* job) {
+  if (!job) return 0;
+  const size_t row = static_cast<size_t>(job->host.rx1 - job->host.rx0) * 4;      // (a clipped job renders into a buffer as wide as its region)
+  return job->flat ? row : (row + 4095) & ~static_cast<size_t>(4095);
+}
+
+int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch, int n_images, void* dst,
+                   size_t dst_pitch, void* stream) {
+  LaunchArgs a;
+  const Compiled* run = nullptr;
+  bool flat = false;
+  const int rc = job_launch_args(job, src, src_pitch, n_images, dst, dst_pitch, &a, &run, &flat);
+  if (rc) return rc;
+  if (flat) g_flat_launches.fetch_add(1, std::memory_order_relaxed);
   DeviceGuard g(job->ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
-  {
-    std::lock_guard<std::mutex> lk(job->launch_mu);
-    job->launched = true;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int k = 0;
-    while (k < job->n_launched_on && job->launched_on[k] != st) ++k;
-    if (k == job->n_launched_on) {
-      if (k < ist_job::kStreams) job->launched_on[job->n_launched_on++] = st;
-      else job->launched_many = true;
-    }
-  }
-  return launch_stitch(a, run.info.n_tiles, run.kernel_kind, stream);
+  note_launch_stream(job, stream);
+  return launch_stitch(a, run->info.n_tiles, run->kernel_kind, stream);
 }
 
 void ist_job_destroy(ist_job* job) {

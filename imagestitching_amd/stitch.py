@@ -7,6 +7,7 @@ this.data.{images, direction, gap, verticalStitchMode, horizontalStitchMode}; he
 Two ways in:
   stitch(images, direction, opts)      host RGBA8 arrays in, host RGBA8 array out   (ist_stitch_rgba8)
   Stitcher(device).compile(...)        device-resident: torch CUDA tensors in/out, one fused launch per call
+and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch) and launch_jobs(jobs, srcs, outs) (ist_jobs_launch).
 """
 import ctypes as C
 import os
@@ -229,6 +230,94 @@ def stitch(images, direction, opts=None, device=0):
     w, h = int(cplan.canvas_w), int(cplan.canvas_h)
     L.lib.ist_plan_free(C.byref(cplan))
     return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
+
+
+_BATCH_REFUSED = ("devices", "split", "pngLevel")      # a batch runs on one GPU and returns pixels, not PNG files
+
+
+def stitch_batch(requests, device=0):
+    """Many independent stitch() calls in one go (ist_stitch_rgba8_batch): the requests' tables go up in one copy, their
+    canvases are rendered by one launch per kernel form, and each comes back into a pinned block of its own.
+
+    requests[k] = (images, direction) or (images, direction, opts), each exactly as stitch() takes them.  Returns a list of
+    HxWx4 uint8 arrays, byte-identical to stitch(*requests[k])['data'], with None for a request without images."""
+    reqs = list(requests)
+    if not reqs:
+        return []
+    n = len(reqs)
+    creqs = (L.StitchRequest * n)()
+    keep = []
+    for k, r in enumerate(reqs):
+        if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
+            raise TypeError("request %d: expected (images, direction) or (images, direction, opts)" % k)
+        images, direction = r[0], r[1]
+        opts = r[2] if len(r) == 3 else None
+        bad = sorted(x for x in (opts or {}) if x in _BATCH_REFUSED)
+        if bad:
+            raise TypeError("request %d: option(s) %s do not apply to a batch (one GPU, pixels out)" % (k, bad))
+        o = _merge(opts)
+        if direction not in _DIRECTIONS:
+            raise ValueError("request %d: direction must be 'vertical' or 'horizontal'" % k)
+        m = len(images)
+        descs = _descs(images)
+        ptrs, pitches = (C.c_void_p * max(1, m))(), (C.c_size_t * max(1, m))()
+        arrays = []
+        for i, im in enumerate(images):
+            a = im["data"] if isinstance(im, dict) else im
+            if a is None:
+                raise L.StitchError(-6, "request %d: 图片%d解码异常" % (k, i))
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+                raise TypeError("request %d, image %d: expected an HxWx4 uint8 RGBA array" % (k, i))
+            if a.strides[2] != 1 or a.strides[1] != 4:
+                a = np.ascontiguousarray(a)
+            arrays.append(a)
+            ptrs[i] = a.ctypes.data
+            pitches[i] = a.strides[0]
+        lim = _limits(o)
+        keep.append((descs, ptrs, pitches, arrays, lim))
+        creqs[k] = L.StitchRequest(descs, ptrs, pitches, m, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
+                                   C.pointer(lim), _filter_of(o), 0)
+    ctx = _ctx(device)
+    plans = (L.Plan * n)()
+    outs = (C.POINTER(C.c_uint8) * n)()
+    L.check(L.lib.ist_stitch_rgba8_batch(ctx, creqs, n, plans, outs))
+    res = []
+    for k in range(n):
+        if not outs[k]:
+            res.append(None)
+            continue
+        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
+        L.lib.ist_plan_free(C.byref(plans[k]))
+        res.append(_take_pixels(outs[k], w, h))
+    return res
+
+
+def launch_jobs(jobs, srcs, outs, stream=None):
+    """Run compiled StitchJobs (Stitcher.compile) as ONE batch (ist_jobs_launch): one launch per kernel form on `stream`.
+    srcs[k]: job k's source tensors (None for images it does not sample); outs[k]: its canvas tensor.  Asynchronous."""
+    import torch
+    n = len(jobs)
+    if len(srcs) != n or len(outs) != n:
+        raise ValueError("launch_jobs: jobs, srcs and outs must have the same length")
+    if n == 0:
+        return
+    st = stream if stream is not None else torch.cuda.current_stream(outs[0].device)
+    handles = (C.c_void_p * n)(*[j._h for j in jobs])
+    counts = (C.c_int * n)(*[j.n_images for j in jobs])
+    total = max(1, sum(j.n_images for j in jobs))
+    ptrs, pitches = (C.c_void_p * total)(), (C.c_size_t * total)()
+    at = 0
+    for j, ss in zip(jobs, srcs):
+        if len(ss) > j.n_images:
+            raise ValueError("launch_jobs: more sources than the job has images")
+        for i, t in enumerate(ss):
+            ptrs[at + i] = 0 if t is None else t.data_ptr()
+            pitches[at + i] = 0 if t is None else t.stride(0)
+        at += j.n_images
+    dst = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    dpitch = (C.c_size_t * n)(*[o.stride(0) for o in outs])
+    L.check(L.lib.ist_jobs_launch(handles, n, ptrs, pitches, counts, dst, dpitch, C.c_void_p(st.cuda_stream)))
 
 
 def _take_pixels(out, w, h):

@@ -140,12 +140,14 @@ IST_API int64_t ist_debug_direct_images(void);
 /* diagnostics: ist_group_stitch_rgba8 / ist_stitch_rgba8_multi calls of this process whose result was delivered by the HOST
  * SINK (every device DMAs its bands into the pinned result; no gather, no root readback) */
 IST_API int64_t ist_debug_host_sink_stitches(void);
-/* launches (ist_job_launch, any caller) that took a job's flat form: every op covers whole canvas rows at unit scale and the caller's
+/* launches (ist_job_launch, any caller; every entry of an ist_jobs_launch batch counts as one) that took a job's flat form: every op covers whole canvas rows at unit scale and the caller's
  * rows were dense on both sides, so the same bytes were moved as rows of 32 KiB */
 IST_API int64_t ist_debug_flat_launches(void);
 /* ist_stitch_rgba8 calls delivered band by band with uploads and downloads overlapped (a strip of disjoint row bands >= 32 MB; DESIGN.md
  * section 4 "Host <-> device"); the others took upload-all, launch, download-all */
 IST_API int64_t ist_debug_duplex_stitches(void);
+/* kernel launches made by ist_jobs_launch (and so by ist_stitch_rgba8_batch) in this process: one per kernel form present in a batch */
+IST_API int64_t ist_debug_batch_launches(void);
 
 /* ---- planner: pure CPU, bit-exact to index.js:1211-1216, 1251-1386, 1432-1433, 1522-1554 -------------------- */
 IST_API void ist_limits_default(int platform, ist_limits* out);        /* index.js:126-156 fallback branch */
@@ -241,6 +243,17 @@ IST_API size_t ist_job_preferred_dst_pitch(const ist_job* job);
  * stream = hipStream_t (NULL = default stream).  Asynchronous: returns after enqueueing. */
 IST_API int ist_job_launch(ist_job* job, const void* const* src, const size_t* src_pitch, int n_images,
                            void* dst, size_t dst_pitch, void* stream);
+/* N x the raster flush of Page.onStitch (index.js:1186-1633, utils/canvas.js:205-242) for N independent jobs of ONE context, in as
+ * few kernel launches as possible: the jobs are grouped by the kernel form they need (a copy-only job never runs in the heavier
+ * resampling form) and every group is ONE launch, all on `stream`.  Job k reads the source slots [first_k, first_k + n_images[k])
+ * of the concatenated src / src_pitch tables (first_k = n_images[0] + ... + n_images[k-1]) and writes dst[k] with pitch
+ * dst_pitch[k].  Every rule of ist_job_launch holds per job (the flat form included); every job is checked before anything is
+ * enqueued, and a bad job k fails the whole call with a message that names k.  Jobs may share sources; destinations must not
+ * overlap (not checked).  IST_E_INVALID: n_jobs <= 0 or jobs of different contexts; IST_E_UNSUPPORTED: n_jobs > 4096 or a
+ * stream that is being captured into a graph.  The per-launch job table (2120 bytes per job + 4 bytes per 64 tiles) is
+ * copied to the device on `stream` ahead of the kernels; asynchronous otherwise, like ist_job_launch. */
+IST_API int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, const size_t* src_pitch, const int* n_images,
+                            void* const* dst, const size_t* dst_pitch, void* stream);
 /* waits for the streams the job was launched on (not for the device: other streams keep running), then recycles its tables.
  * A job launched on the legacy default stream (NULL) inherits that stream's own implicit synchronisation rules. */
 IST_API void ist_job_destroy(ist_job* job);
@@ -255,6 +268,26 @@ IST_API void ist_job_destroy(ist_job* job);
 IST_API int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src,
                              const size_t* src_pitch, int n_images, int direction, int mode, double gap,
                              const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_pixels);
+/* one request of ist_stitch_rgba8_batch: the arguments of one ist_stitch_rgba8 call (limits NULL = ist_limits_unlimited) */
+typedef struct ist_stitch_request {
+  const ist_image_desc* images;
+  const uint8_t* const* src;
+  const size_t* src_pitch;      /* NULL: dense rows */
+  int32_t n_images;
+  int32_t direction, mode;
+  double gap;
+  const ist_limits* limits;
+  int32_t filter;
+  int32_t reserved;
+} ist_stitch_request;
+/* N x Page.onStitch (index.js:1186-1633) minus decode and PNG encode: ist_stitch_rgba8 for every request, with the requests' op
+ * tables uploaded in one copy per sub-batch and their canvases rendered by one ist_jobs_launch per sub-batch.  Sub-batches hold
+ * at most 512 MiB of sources + canvases and two are in flight (one uploads while the previous one's canvases come down), which
+ * bounds the device memory the context keeps.  out_plans[k] / out_pixels[k] are what ist_stitch_rgba8 would return for request k
+ * (release with ist_plan_free / ist_free): every canvas is a pinned block of its own, from a class of the result pool that keeps
+ * up to 8 GiB idle for the next batch (ist_pool_trim releases it).  A request without images gets out_pixels[k] = NULL and a
+ * zeroed plan (its IST_NOTHING_TO_DO).  Any failing request fails the whole call (the message names it) and nothing is returned. */
+IST_API int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels);
 /* render a recorded Canvas op list into a caller buffer (the Canvas-2D shim's export / getImageData) */
 IST_API int ist_render_rgba8(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
                              const ist_op* ops, int n_ops, const ist_image_desc* images,

@@ -10,6 +10,8 @@
  *       devices: number[] (devices[0] = root) shards the stitch over several GPUs from this process (ist_stitch_rgba8_multi:
  *       RCCL gather over xGMI); split 0 = by image (round robin), 1 = by band (equal output rows, draw by draw), 2 = by rows (across all draws), 3 = auto
  *   stitchSync(...same...)                                             -> {width,height,data}
+ *   stitchBatch(requests) / stitchBatchSync(requests): requests[k] = [images, direction, mode, gap, limits, filter]
+ *       -> Promise<({width,height,data,plan} | null)[]> / the array itself  (ist_stitch_rgba8_batch: one GPU, many stitches)
  *   render(canvasW, canvasH, clearRGBA, ops, images, filter, region, asPng?) -> Buffer (region pixels, or the PNG file)
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
  *   deviceCount(), lastError(), abiVersion()
@@ -403,6 +405,142 @@ static napi_value js_stitch_sync(napi_env env, napi_callback_info info) {
 }
 
 /* render(canvasW, canvasH, clearRGBA(Uint8Array 4), ops(Float64Array 18/op), images, filter, region|null) -> Buffer */
+/* stitchBatch(requests) / stitchBatchSync(requests): requests[k] = [images, direction, mode, gap, limits, filter] (what stitch takes, minus
+ * the device-group arguments: a batch runs on one GPU).  N x Page.onStitch (index.js:1186-1633) through ist_stitch_rgba8_batch.
+ * Result: an array with {width,height,data,plan} per request, null for a request without images. */
+typedef struct {
+  int n;
+  images_t* im;
+  ist_limits* lim;
+  ist_stitch_request* reqs;
+  ist_plan* plans;
+  uint8_t** pixels;
+  int rc; char err[256];
+  napi_deferred deferred; napi_async_work work;
+} batch_job;
+
+static void batch_free(napi_env env, batch_job* j) {
+  if (!j) return;
+  for (int k = 0; k < j->n; k++) {
+    if (j->im) images_free(env, &j->im[k]);
+    if (j->plans) ist_plan_free(&j->plans[k]);
+    if (j->pixels && j->pixels[k]) ist_free(j->pixels[k]);
+  }
+  free(j->im); free(j->lim); free(j->reqs); free(j->plans); free(j->pixels); free(j);
+}
+
+static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_refs) {
+  size_t argc = 1; napi_value argv[1];
+  bool is_arr = false; uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "stitchBatch([[images, direction, mode, gap, limits, filter], ...])");
+    return NULL;
+  }
+  napi_get_array_length(env, argv[0], &n);
+  batch_job* j = (batch_job*)calloc(1, sizeof *j);
+  j->n = (int)n;
+  j->im = (images_t*)calloc(n ? n : 1, sizeof(images_t));
+  j->lim = (ist_limits*)calloc(n ? n : 1, sizeof(ist_limits));
+  j->reqs = (ist_stitch_request*)calloc(n ? n : 1, sizeof(ist_stitch_request));
+  j->plans = (ist_plan*)calloc(n ? n : 1, sizeof(ist_plan));
+  j->pixels = (uint8_t**)calloc(n ? n : 1, sizeof(uint8_t*));
+  for (uint32_t k = 0; k < n; k++) {
+    napi_value r, a[6]; bool ra = false; uint32_t m = 0;
+    napi_get_element(env, argv[0], k, &r);
+    if (napi_is_array(env, r, &ra) != napi_ok || !ra || napi_get_array_length(env, r, &m) != napi_ok || m < 6) {
+      napi_throw_type_error(env, NULL, "stitchBatch: requests[k] must be [images, direction, mode, gap, limits, filter]");
+      batch_free(env, j); return NULL;
+    }
+    for (uint32_t i = 0; i < 6; i++) napi_get_element(env, r, i, &a[i]);
+    if (!images_parse(env, a[0], &j->im[k], want_refs)) { batch_free(env, j); return NULL; }
+    ist_stitch_request* q = &j->reqs[k];
+    int32_t v = 0;
+    napi_get_value_int32(env, a[1], &v); q->direction = v;
+    napi_get_value_int32(env, a[2], &v); q->mode = v;
+    napi_get_value_double(env, a[3], &q->gap);
+    limits_parse(env, a[4], &j->lim[k]);
+    napi_get_value_int32(env, a[5], &v); q->filter = v;
+    q->images = j->im[k].descs; q->src = j->im[k].data; q->src_pitch = j->im[k].pitch; q->n_images = j->im[k].n; q->limits = &j->lim[k];
+  }
+  return j;
+}
+
+static void batch_execute(napi_env env, void* data) {
+  (void)env;
+  batch_job* j = (batch_job*)data;
+  if (j->n == 0) { j->rc = IST_OK; return; }
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
+  for (int k = 0; k < j->n; k++)
+    for (int i = 0; i < j->im[k].n; i++)
+      if (!j->im[k].data[i]) {
+        j->rc = IST_E_DECODE;
+        snprintf(j->err, sizeof j->err, "request %d: \xe5\x9b\xbe\xe7\x89\x87%d\xe8\xa7\xa3\xe7\xa0\x81\xe5\xbc\x82\xe5\xb8\xb8", k, i);
+        return;
+      }
+  j->rc = ist_stitch_rgba8_batch(ctx, j->reqs, j->n, j->plans, j->pixels);
+  if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
+}
+
+/* the results array; the pixel blocks move into external Buffers (freed by ist_free when they are collected) */
+static napi_value batch_result(napi_env env, batch_job* j) {
+  napi_value arr;
+  if (napi_create_array_with_length(env, (size_t)j->n, &arr) != napi_ok) return NULL;
+  for (int k = 0; k < j->n; k++) {
+    napi_value e;
+    if (!j->pixels[k]) { napi_get_null(env, &e); napi_set_element(env, arr, (uint32_t)k, e); continue; }
+    const ist_plan* p = &j->plans[k];
+    napi_value buf;
+    if (napi_create_external_buffer(env, (size_t)p->canvas_w * (size_t)p->canvas_h * 4, j->pixels[k], free_pixels, NULL, &buf) != napi_ok) return NULL;
+    j->pixels[k] = NULL;                                  /* the Buffer owns it now */
+    napi_create_object(env, &e);
+    set_num(env, e, "width", (double)p->canvas_w);
+    set_num(env, e, "height", (double)p->canvas_h);
+    napi_set_named_property(env, e, "data", buf);
+    napi_set_named_property(env, e, "plan", plan_to_js(env, p));
+    napi_set_element(env, arr, (uint32_t)k, e);
+  }
+  return arr;
+}
+
+static void batch_complete(napi_env env, napi_status status, void* data) {
+  batch_job* j = (batch_job*)data;
+  (void)status;
+  if (j->rc < 0) napi_reject_deferred(env, j->deferred, make_error(env, j->rc, j->err));
+  else {
+    napi_value r = batch_result(env, j);
+    if (r) napi_resolve_deferred(env, j->deferred, r);
+    else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the output buffers"));
+  }
+  napi_delete_async_work(env, j->work);
+  batch_free(env, j);
+}
+
+static napi_value js_stitch_batch(napi_env env, napi_callback_info info) {
+  batch_job* j = batch_parse(env, info, 1);
+  if (!j) return NULL;
+  napi_value promise, name;
+  CHECK(napi_create_promise(env, &j->deferred, &promise));
+  napi_create_string_utf8(env, "imagestitch.stitchBatch", NAPI_AUTO_LENGTH, &name);
+  CHECK(napi_create_async_work(env, NULL, name, batch_execute, batch_complete, j, &j->work));
+  CHECK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
+static napi_value js_stitch_batch_sync(napi_env env, napi_callback_info info) {
+  batch_job* j = batch_parse(env, info, 0);
+  if (!j) return NULL;
+  batch_execute(env, j);
+  napi_value out = NULL;
+  if (j->rc < 0) napi_throw(env, make_error(env, j->rc, j->err));
+  else {
+    out = batch_result(env, j);
+    if (!out) napi_throw(env, make_error(env, IST_E_NOMEM, "could not wrap the output buffers"));
+  }
+  batch_free(env, j);
+  return out;
+}
+
 static napi_value js_render(napi_env env, napi_callback_info info) {
   size_t argc = 8; napi_value argv[8];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -586,6 +724,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"plan", NULL, js_plan, NULL, NULL, NULL, napi_default, NULL},
       {"stitch", NULL, js_stitch, NULL, NULL, NULL, napi_default, NULL},
       {"stitchSync", NULL, js_stitch_sync, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchBatch", NULL, js_stitch_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchBatchSync", NULL, js_stitch_batch_sync, NULL, NULL, NULL, napi_default, NULL},
       {"stitchFiles", NULL, js_stitch_files, NULL, NULL, NULL, napi_default, NULL},
       {"render", NULL, js_render, NULL, NULL, NULL, napi_default, NULL},
       {"encodePng", NULL, js_encode_png, NULL, NULL, NULL, napi_default, NULL},

@@ -30,6 +30,10 @@ export interface StitchResult { width: number; height: number; data: Buffer; pla
 export function stitch(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchResult | null>;
 export function stitchSync(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchResult | null;
 export function plan(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchPlan | null;
+// one request of a batch: a stitch on the batch's GPU (devices / split / pngLevel are refused with a TypeError)
+export interface StitchRequest { images: StitchImage[]; direction: Direction; opts?: Omit<StitchOptions, 'devices' | 'split' | 'pngLevel' | 'onProgress'>; }
+export function stitchBatch(requests: StitchRequest[]): Promise<(StitchResult | null)[]>;
+export function stitchBatchSync(requests: StitchRequest[]): (StitchResult | null)[];
 export interface StitchPngResult { width: number; height: number; png: Buffer; plan: StitchPlan; }
 export function stitchPng(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchPngResult | null>;
 export function encodePng(data: Uint8Array, width: number, height: number, opts?: { pngLevel?: 0 | 1 }): Buffer;

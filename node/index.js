@@ -6,6 +6,7 @@
  * this.data.{images, direction, gap, verticalStitchMode, horizontalStitchMode}.  Here:
  *
  *   stitch(images, direction, opts?) -> Promise<{width, height, data: Buffer, plan}>
+ *   stitchBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, data, plan} | null)[]>   (one GPU, many stitches)
  *
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
@@ -92,6 +93,27 @@ function stitch(images, direction, opts) {
   return withProgress(opts, () => native.stitch(...a));
 }
 function stitchSync(images, direction, opts) { const a = args(images, direction, opts).concat(groupArgs(opts)); return a[0].length ? native.stitchSync(...a) : null; }
+// A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel'];
+function batchArgs(requests) {
+  if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
+  return requests.map((r, k) => {
+    if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
+    const o = r.opts || {};
+    for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
+    return args(r.images, r.direction, o);
+  });
+}
+/** Many independent stitches in one call (one GPU): resolves an array with one {width, height, data, plan} per request
+ *  - the same bytes stitchSync returns for it - and null for a request without images.  Each request is one onStitch
+ *  (index.js:1186-1633); their canvases are rendered by one kernel launch per kernel form. */
+function stitchBatch(requests) {
+  let a;
+  try { a = batchArgs(requests); } catch (e) { return Promise.reject(e); }
+  if (!a.length) return Promise.resolve([]);
+  return native.stitchBatch(a);
+}
+function stitchBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchBatchSync(a) : []; }
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
@@ -130,4 +152,4 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
