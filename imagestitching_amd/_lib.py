@@ -94,6 +94,7 @@ SYMBOLS = [
     ("ist_debug_flat_launches", C.c_int64, []),
     ("ist_debug_duplex_stitches", C.c_int64, []),
     ("ist_debug_batch_launches", C.c_int64, []),
+    ("ist_debug_png_batch_launches", C.c_int64, []),
     ("ist_limits_default", None, [C.c_int, C.POINTER(Limits)]),
     ("ist_limits_unlimited", None, [C.POINTER(Limits)]),
     ("ist_plan_compute", C.c_int, [C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.POINTER(Plan)]),
@@ -138,6 +139,8 @@ SYMBOLS = [
                                    C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int, C.POINTER(Plan),
                                    C.POINTER(C.POINTER(C.c_uint8))]),
     ("ist_stitch_rgba8_batch", C.c_int, [C.c_void_p, C.POINTER(StitchRequest), C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8))]),
+    ("ist_stitch_png_batch", C.c_int, [C.c_void_p, C.POINTER(StitchRequest), C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)),
+                                       C.POINTER(C.c_int64)]),
     ("ist_render_rgba8", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int,
                                    C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                    C.POINTER(Region), C.c_void_p, C.c_size_t]),
@@ -160,6 +163,8 @@ SYMBOLS = [
     ("ist_png_bound", C.c_int64, [C.c_int64, C.c_int64]),
     ("ist_png_encode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                         C.POINTER(C.c_int64), C.c_void_p]),
+    ("ist_png_encode_batch_device", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                              C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
     ("ist_png_encode_rgba8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
                                        C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
     ("ist_render_png", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int,

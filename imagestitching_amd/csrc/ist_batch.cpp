@@ -1,4 +1,4 @@
-// ist_batch.cpp — many independent stitches per kernel launch (ist_jobs_launch, ist_stitch_rgba8_batch).
+// ist_batch.cpp — many independent stitches per kernel launch (ist_jobs_launch, ist_stitch_rgba8_batch, ist_stitch_png_batch).
 //
 // Reference anchor: each entry of a batch is one unchanged Page.onStitch (miniprogram-stitch/miniprogram/pages/index/index.js:
 // 1186-1633; a request is capped at 9 images by index.js:311).  A service that renders many small requests pays, per request
@@ -203,6 +203,10 @@ void drop_jobs(std::vector<ist_job*>* jobs) {
 // ctx->stream renders it into half i % 2, and its canvases follow on the aux stream into pooled pinned blocks (the batch class of
 // the pool: a batch's caller holds all its results at once).  (What the single-stitch path does band by band, done sub-batch by
 // sub-batch: both directions of PCIe busy at once.)
+// With out_len (ist_stitch_png_batch) every result is a PNG file instead: the sub-batch's canvases are encoded straight from the
+// half's canvas area into its file area by one compression launch (+ one gather launch) on ctx->stream, and the files come down on
+// the aux stream, each exactly as long as it is; the few header / trailer bytes no kernel writes are patched into the host copies
+// once the downloads are done (apply_patches).
 struct Pipeline {
   ist_ctx* ctx;
   const ist_stitch_request* reqs;
@@ -210,12 +214,20 @@ struct Pipeline {
   const std::vector<int>& n_ops;
   const ist_plan* plans;
   uint8_t** out_pixels;
+  int64_t* out_len;                       // PNG files out (NULL: canvases)
   std::vector<ist_job*> jobs[2];          // the jobs whose tables live in half 0 / 1
   bool used[2] = {false, false};
   int next = 0;
+  std::vector<std::pair<int, std::vector<PngPatch>>> patches;   // (request, its file's patches), applied after finish()
 
-  Pipeline(ist_ctx* c, const ist_stitch_request* r, const std::vector<std::vector<ist_op>>& o, const std::vector<int>& no, const ist_plan* p, uint8_t** out)
-      : ctx(c), reqs(r), ops(o), n_ops(no), plans(p), out_pixels(out) {}
+  Pipeline(ist_ctx* c, const ist_stitch_request* r, const std::vector<std::vector<ist_op>>& o, const std::vector<int>& no, const ist_plan* p, uint8_t** out,
+           int64_t* len = nullptr)
+      : ctx(c), reqs(r), ops(o), n_ops(no), plans(p), out_pixels(out), out_len(len) {}
+
+  void apply_patches() {
+    for (const auto& fp : patches)
+      for (const PngPatch& pt : fp.second) std::memcpy(out_pixels[fp.first] + pt.at, pt.b, static_cast<size_t>(pt.n));
+  }
 
   // everything queued is done; jobs dropped.  Returns rc.
   int finish(int rc) {
@@ -234,9 +246,9 @@ struct Pipeline {
     std::vector<ist_job*> js(n, nullptr);
     struct Guard { std::vector<ist_job*>* v; ~Guard() { if (v) for (ist_job* j : *v) if (j) ist_job_destroy(j); } } guard{&js};
     std::vector<TableLayout> lay(n);
-    std::vector<size_t> tab_at(n, 0), dst_at(n, 0), canvas_bytes(n, 0);
+    std::vector<size_t> tab_at(n, 0), dst_at(n, 0), canvas_bytes(n, 0), file_at(n, 0), file_cap(n, 0);
     std::vector<std::vector<size_t>> src_at(n);
-    size_t tab_total = 0, src_total = 0, dst_total = 0;
+    size_t tab_total = 0, src_total = 0, dst_total = 0, file_total = 0;
     for (size_t q = 0; q < n; ++q) {
       const int k = idx[q];
       const ist_stitch_request& r = reqs[k];
@@ -258,19 +270,24 @@ struct Pipeline {
       }
       canvas_bytes[q] = static_cast<size_t>(p.canvas_w) * 4 * static_cast<size_t>(p.canvas_h);
       dst_at[q] = dst_total; dst_total += align_up(canvas_bytes[q]);
+      if (out_len) {
+        file_cap[q] = static_cast<size_t>(ist_png_bound(p.canvas_w, p.canvas_h));
+        file_at[q] = file_total; file_total += align_up(file_cap[q]);
+      }
     }
     // the half is free once the launch that read it (two sub-batches ago) is done; its canvases must also be down before they
     // are re-allocated (a growth) or overwritten (ordered on the device below)
     if (used[hi]) {
       if (hipEventSynchronize(H.kernel_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
       drop_jobs(&jobs[hi]);
-      if (H.dst_bytes < dst_total && hipEventSynchronize(H.read_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
+      if ((H.dst_bytes < dst_total || H.file_bytes < file_total) && hipEventSynchronize(H.read_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
     }
     if (!H.kernel_done && hipEventCreateWithFlags(&H.kernel_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.kernel_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
     if (!H.read_done && hipEventCreateWithFlags(&H.read_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.read_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
     int rc = grow_device(&H.tab, &H.tab_bytes, tab_total ? tab_total : kAlign);
     if (!rc) rc = grow_device(&H.src, &H.src_bytes, src_total ? src_total : kAlign);
     if (!rc) rc = grow_device(&H.dst, &H.dst_bytes, dst_total ? dst_total : kAlign);
+    if (!rc && out_len) rc = grow_device(&H.file, &H.file_bytes, file_total ? file_total : kAlign);
     if (rc) return rc;
     uint8_t* dtab = static_cast<uint8_t*>(H.tab);
     uint8_t* dsrc = static_cast<uint8_t*>(H.src);
@@ -314,6 +331,7 @@ struct Pipeline {
     used[hi] = true;
     jobs[hi] = js;
     guard.v = nullptr;                                     // (the pipeline drops them once their launch is done)
+    if (out_len) return encode_and_read(idx, H, ddst, dst_at, file_at, file_cap);
     // every canvas into a pinned block of its own, on the aux stream behind the launch
     if (hipStreamWaitEvent(ctx->aux, H.kernel_done, 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering a readback failed"); }
     for (size_t q = 0; q < n; ++q) {
@@ -325,22 +343,55 @@ struct Pipeline {
     if (hipEventRecord(H.read_done, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
     return IST_OK;
   }
+
+  // the sub-batch's canvases (rendered on ctx->stream) -> PNG files in the half's file area, ONE compression launch for all of them
+  // (the encoder returns with ctx->stream idle); then every file into a pinned block of its real length, on the aux stream
+  int encode_and_read(const std::vector<int>& idx, ist_ctx::BatchHalf& H, uint8_t* ddst, const std::vector<size_t>& dst_at,
+                      const std::vector<size_t>& file_at, const std::vector<size_t>& file_cap) {
+    const size_t n = idx.size();
+    uint8_t* dfile = static_cast<uint8_t*>(H.file);
+    std::vector<PngBatchFile> files(n);
+    for (size_t q = 0; q < n; ++q) {
+      const ist_plan& p = plans[idx[q]];
+      files[q] = PngBatchFile{ddst + dst_at[q], static_cast<size_t>(p.canvas_w) * 4, p.canvas_w, p.canvas_h, dfile + file_at[q],
+                              static_cast<int64_t>(file_cap[q]), 0, {}};
+      const int rc = png_batch_check(files[q], idx[q]);
+      if (rc) { const std::string why = g_last_error; return fail(rc, "request " + std::to_string(idx[q]) + ": " + why); }
+    }
+    int rc = ctx->png_level > 0 ? png_encode_batch_deflate(ctx, files, ctx->stream, true) : png_encode_batch_stored(ctx, files, ctx->stream, true);
+    if (rc) return rc;
+    for (size_t q = 0; q < n; ++q) {
+      const size_t len = static_cast<size_t>(files[q].len);
+      uint8_t* host = static_cast<uint8_t*>(pool_take_batch(len));
+      if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the results");
+      out_pixels[idx[q]] = host;                           // (the caller's release() gives it back, after finish())
+      out_len[idx[q]] = files[q].len;
+      if (hipMemcpyAsync(host, dfile + file_at[q], len, hipMemcpyDeviceToHost, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "queueing a readback failed"); }
+      patches.emplace_back(idx[q], std::move(files[q].patches));
+    }
+    if (hipEventRecord(H.read_done, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
+    return IST_OK;
+  }
 };
 
 }  // namespace
 
 extern "C" {
 
-int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_pixels))) return fail(IST_E_INVALID, "ist_stitch_rgba8_batch: NULL argument");
+}  // extern "C"
+
+namespace {
+
+// ist_stitch_rgba8_batch (out_len NULL) and ist_stitch_png_batch
+int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels, int64_t* out_len) {
   const size_t n = static_cast<size_t>(n_reqs);
-  for (size_t k = 0; k < n; ++k) { out_pixels[k] = nullptr; std::memset(&out_plans[k], 0, sizeof(ist_plan)); }
+  for (size_t k = 0; k < n; ++k) { out_pixels[k] = nullptr; std::memset(&out_plans[k], 0, sizeof(ist_plan)); if (out_len) out_len[k] = 0; }
   auto release = [&]() {
     for (size_t k = 0; k < n; ++k) {
       ist_plan_free(&out_plans[k]);
       std::memset(&out_plans[k], 0, sizeof(ist_plan));
       if (out_pixels[k]) { ist_free(out_pixels[k]); out_pixels[k] = nullptr; }
+      if (out_len) out_len[k] = 0;
     }
   };
   // plan every request (pure CPU): the op list of each, and what it will hold on the device
@@ -360,6 +411,11 @@ int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_r
     if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
     bytes[k] = static_cast<size_t>(out_plans[k].canvas_w) * 4 * static_cast<size_t>(out_plans[k].canvas_h);
     for (int i = 0; i < r.n_images; ++i) bytes[k] += image_bytes(r.images[i]);
+    if (out_len) {                                        // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
+      const int64_t cw = out_plans[k].canvas_w, ch = out_plans[k].canvas_h;
+      bytes[k] += static_cast<size_t>(ist_png_bound(cw, ch));
+      if (ctx->png_level > 0) bytes[k] += static_cast<size_t>(png_deflate_chunks(cw, ch) * png_deflate_slot_bytes());
+    }
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
@@ -367,7 +423,7 @@ int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_r
   int rc = ctx_aux_stream(ctx);
   if (rc) { release(); return rc; }
   // sub-batches: consecutive requests while their device bytes fit the budget, and at most kMaxBatchJobs of them
-  Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels);
+  Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels, out_len);
   std::vector<int> idx;
   size_t held = 0;
   for (size_t k = 0; k <= n && rc == IST_OK; ++k) {
@@ -378,7 +434,24 @@ int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_r
   }
   rc = pipe.finish(rc);
   if (rc) { const std::string why = g_last_error; const int code = g_last_code; release(); g_last_error = why; g_last_code = code; return rc; }
+  pipe.apply_patches();
   return IST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_pixels))) return fail(IST_E_INVALID, "ist_stitch_rgba8_batch: NULL argument");
+  return stitch_batch(ctx, reqs, n_reqs, out_plans, out_pixels, nullptr);
+}
+
+int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_png, int64_t* out_len) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_png || !out_len))) return fail(IST_E_INVALID, "ist_stitch_png_batch: NULL argument");
+  return stitch_batch(ctx, reqs, n_reqs, out_plans, out_png, out_len);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// ist_crc.h — CRC-32 (PNG / zlib, reflected 0xEDB88320) helpers shared by the two PNG encoders
+// ist_crc.h — CRC-32 (PNG / zlib, reflected 0xEDB88320) helpers shared by the two PNG encoders (+ their batch twins' file lookup)
 #ifndef IST_CRC_H_
 #define IST_CRC_H_
 
@@ -35,6 +35,22 @@ inline uint32_t gf_mul(uint32_t a, uint32_t b) {
   }
   return p;
 }
+
+#if defined(__HIPCC__)
+// The batch twins of the PNG kernels (one launch, many files): the file holding work item g is the last f with begin[f] <= g
+// (begin[0] = 0, strictly increasing).  g is wave-uniform and the table is read through the constant address space, so the
+// search is scalar loads and scalar branches, and the per-file table below it is too (ist_png.hip, ist_png_deflate.hip).
+template <typename T> using ConstPtr = const __attribute__((address_space(4))) T*;
+__device__ __forceinline__ int batch_file_of(const int64_t* begin_, int n, int64_t g) {
+  ConstPtr<int64_t> begin = (ConstPtr<int64_t>)begin_;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (begin[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+#endif
 
 }  // namespace ist
 

@@ -64,8 +64,9 @@ struct ist_ctx {
     void* tab = nullptr; size_t tab_bytes = 0;
     void* src = nullptr; size_t src_bytes = 0;
     void* dst = nullptr; size_t dst_bytes = 0;
+    void* file = nullptr; size_t file_bytes = 0;   // ist_stitch_png_batch: the sub-batch's PNG files (ist_png_bound each)
     hipEvent_t kernel_done = nullptr;    // behind the launch that reads tab / src
-    hipEvent_t read_done = nullptr;      // behind the downloads that read dst
+    hipEvent_t read_done = nullptr;      // behind the downloads that read dst (or file)
   };
   BatchHalf batch_half[2];
 };

@@ -154,6 +154,21 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
 int ctx_png_level(const ist_ctx* ctx);
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p);   // the context's grow-only PNG scratch (kept across calls)
 
+// ---- batch PNG export (ist_png_encode_batch_device, ist_stitch_png_batch) ----
+struct PngPatch { int64_t at; uint8_t b[64]; int n; };      // bytes of a file no kernel writes (signature, chunk headers, checksums)
+// one file of a batch: a canvas in device memory -> its PNG in a 16-byte aligned device buffer of `cap` >= ist_png_bound bytes
+struct PngBatchFile { const void* canvas; size_t pitch; int64_t w, h; uint8_t* out; int64_t cap; int64_t len; std::vector<PngPatch> patches; };
+// Every file in ONE compression launch (+ one gather launch at level 1) on `stream`; file k is byte for byte what
+// ist_png_encode_device writes for canvas k at the same level.  Returns with `stream` idle (the checksums are combined on the
+// host).  host_patches: the patches are left in files[k].patches for a caller that writes them into its host copy of the file;
+// otherwise they are copied to the device.  The arguments are checked by the caller (png_batch_check).
+int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
+int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
+int png_batch_check(const PngBatchFile& f, int k);          // the rules of ist_png_encode_device for file k (message names it)
+int64_t png_deflate_chunks(int64_t w, int64_t h);           // chunks (= slots of SLOT bytes) of the compressing form
+int64_t png_deflate_slot_bytes();
+void count_png_batch_launch();
+
 }  // namespace ist
 
 #endif  // IST_INTERNAL_H_

@@ -21,9 +21,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "ist_crc.h"
+#include "ist_host.h"
 #include "ist_internal.h"
 
 namespace ist {
@@ -54,14 +56,11 @@ struct PngArgs {
   uint32_t segs;                 // 16-KiB segments per row
 };
 
-__global__ __launch_bounds__(256) void ist_png_rows_kernel(const PngArgs P) {
-  __shared__ uint32_t T[4][256];
+// segment `seg` of row `r` of the canvas P describes (the body of both stored-form kernels below)
+__device__ __forceinline__ void rows_segment(const PngArgs P, const int r, const int seg, uint32_t (*T)[256]) {
   const int tid = threadIdx.x, lane = tid & 63;
   for (int i = tid; i < 1024; i += 256) T[i >> 8][i & 255] = P.tables[i];
   __syncthreads();
-  // one workgroup per 16-KiB row segment, numbered along the row first (contiguous file bytes for neighbouring workgroups)
-  const int r = static_cast<int>(blockIdx.x / P.segs);
-  const int seg = static_cast<int>(blockIdx.x - static_cast<unsigned>(r) * P.segs);
   const int64_t tab = P.row_tab[r];
   const int64_t pix_off = tab & ~15ll;
   const int k = static_cast<int>(tab & 15);
@@ -158,6 +157,36 @@ __global__ __launch_bounds__(256) void ist_png_rows_kernel(const PngArgs P) {
   }
 }
 
+// one workgroup per 16-KiB row segment, numbered along the row first (contiguous file bytes for neighbouring workgroups)
+__global__ __launch_bounds__(256) void ist_png_rows_kernel(const PngArgs P) {
+  __shared__ uint32_t T[4][256];
+  const int r = static_cast<int>(blockIdx.x / P.segs);
+  rows_segment(P, r, static_cast<int>(blockIdx.x - static_cast<unsigned>(r) * P.segs), T);
+}
+
+// ---- batch twin: the rows of many canvases in ONE launch (png_encode_batch_stored).  Workgroups are numbered file-major;
+// wg_begin[f] is file f's first.  Each file has its own row table, partial sums and output (pointers in its RowsJob), so the
+// body above runs unchanged on the file's own workgroup numbers, and no row of one canvas is read for another.
+struct RowsJob {
+  const uint8_t* canvas; size_t pitch; uint8_t* out;
+  const int64_t* row_tab; unsigned long long* s1; unsigned long long* s2; uint32_t* crc;
+  int64_t row_bytes; int32_t h; int32_t nb; uint32_t segs; int32_t pad_;
+};
+struct RowsBatchArgs { const RowsJob* jobs; const int64_t* wg_begin; int32_t n_files; const uint32_t* xpow4; const uint32_t* tables; };
+
+__global__ __launch_bounds__(256) void ist_png_rows_batch_kernel(const RowsBatchArgs B) {
+  __shared__ uint32_t T[4][256];
+  const int64_t g = blockIdx.x;
+  const int f = batch_file_of(B.wg_begin, B.n_files, g);
+  const RowsJob J = *(const RowsJob*)((ConstPtr<RowsJob>)B.jobs + f);
+  PngArgs P;
+  P.canvas = J.canvas; P.pitch = J.pitch; P.out = J.out; P.row_tab = J.row_tab; P.xpow4 = B.xpow4; P.tables = B.tables;
+  P.s1 = J.s1; P.s2 = J.s2; P.crc = J.crc; P.row_bytes = J.row_bytes; P.h = J.h; P.nb = J.nb; P.segs = J.segs;
+  const unsigned q = static_cast<unsigned>(g - ((ConstPtr<int64_t>)B.wg_begin)[f]);
+  const int r = static_cast<int>(q / J.segs);
+  rows_segment(P, r, static_cast<int>(q - static_cast<unsigned>(r) * J.segs), T);
+}
+
 struct Layout {
   int64_t w = 0, h = 0, row_bytes = 0; int nb = 1;
   std::vector<int64_t> row_tab;          // pix_off | k
@@ -191,7 +220,211 @@ void make_layout(int64_t w, int64_t h, Layout* L) {
 
 void put32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = (v >> 16) & 0xFF; p[2] = (v >> 8) & 0xFF; p[3] = v & 0xFF; }
 
+// CRC slicing tables + x^(32 i) (the register after 4 i zero bytes, from the polynomial "1"), built once
+struct StoredTables { CrcTables T; std::vector<uint32_t> xpow; };
+const StoredTables& stored_tables() {
+  static StoredTables S;
+  static std::once_flag once;
+  std::call_once(once, []() {
+    make_crc_tables(&S.T);
+    const int64_t n_pow = kBlockData / 4 + 1;
+    S.xpow.resize(static_cast<size_t>(n_pow));
+    uint32_t reg = 0x80000000u;
+    for (int64_t i = 0; i < n_pow; ++i) {
+      S.xpow[static_cast<size_t>(i)] = reg;
+      for (int z = 0; z < 4; ++z) reg = crc_byte(S.T, reg, 0);
+    }
+  });
+  return S;
+}
+
+// The host side of one file (both paths): the per-row partials combined into the Adler-32 and the CRC of every IDAT, and the
+// ~60 bytes no kernel writes (signature, IHDR, chunk headers and lengths, checksums, IEND) as patches
+void stored_patches(const Layout& L, const unsigned long long* s1, const unsigned long long* s2, const uint32_t* crc,
+                    std::vector<PngPatch>* patches) {
+  const CrcTables& T = stored_tables().T;
+  const std::vector<uint32_t>& xpow = stored_tables().xpow;
+  const int64_t w = L.w, h = L.h;
+  const uint64_t M = 65521;
+  uint64_t ad_a = 1, ad_b = 0;
+  const uint64_t Lrow = static_cast<uint64_t>(L.row_bytes) + 1;
+  for (int64_t r = 0; r < h; ++r) {
+    ad_b = (ad_b + (Lrow % M) * ad_a + s2[static_cast<size_t>(r)] % M) % M;
+    ad_a = (ad_a + s1[static_cast<size_t>(r)] % M) % M;
+  }
+  const uint32_t adler = static_cast<uint32_t>((ad_b << 16) | ad_a);
+
+  // shift operators for the block lengths in use (full block, last block of a row)
+  const int64_t last_bl = L.row_bytes - (L.nb - 1) * kBlockData;
+  const uint32_t sh_full = xpow[static_cast<size_t>(kBlockData / 4)];
+  const uint32_t sh_last = xpow[static_cast<size_t>(last_bl / 4)];
+  typedef PngPatch Patch;
+  uint32_t reg = 0xFFFFFFFFu;
+  auto feed = [&](const uint8_t* p, int n) { for (int i = 0; i < n; ++i) reg = crc_byte(T, reg, p[i]); };
+  size_t next_chunk = 0;
+  int64_t chunk_len_at = 0, chunk_data_start = 0;
+  int64_t pos = 0;
+  for (int64_t r = 0; r < h; ++r) {
+    const int64_t tab = L.row_tab[static_cast<size_t>(r)];
+    const int64_t pix = tab & ~15ll; const int k = static_cast<int>(tab & 15);
+    const int lead = 5 * k + 6;
+    if (next_chunk < L.chunk_first_row.size() && L.chunk_first_row[next_chunk] == r) {
+      Patch pt; std::memset(&pt, 0, sizeof pt);
+      int n = 0;
+      if (r == 0) {
+        static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+        std::memcpy(pt.b, sig, 8); n = 8;
+        put32(pt.b + n, 13); std::memcpy(pt.b + n + 4, "IHDR", 4);
+        put32(pt.b + n + 8, static_cast<uint32_t>(w)); put32(pt.b + n + 12, static_cast<uint32_t>(h));
+        pt.b[n + 16] = 8; pt.b[n + 17] = 6; pt.b[n + 18] = 0; pt.b[n + 19] = 0; pt.b[n + 20] = 0;
+        uint32_t c = 0xFFFFFFFFu;
+        for (int i = 4; i < 21; ++i) c = crc_byte(T, c, pt.b[n + i]);
+        put32(pt.b + n + 21, c ^ 0xFFFFFFFFu);
+        n += 25;
+      } else {                      // close the previous IDAT: its CRC, and its length field
+        put32(pt.b, reg ^ 0xFFFFFFFFu); n = 4;
+        Patch lp; std::memset(&lp, 0, sizeof lp);
+        lp.at = chunk_len_at; lp.n = 4; put32(lp.b, static_cast<uint32_t>(pos - chunk_data_start));
+        patches->push_back(lp);
+      }
+      pt.at = pos;
+      chunk_len_at = pos + n;                       // length is patched when the chunk closes
+      std::memcpy(pt.b + n + 4, "IDAT", 4);
+      reg = 0xFFFFFFFFu;
+      feed(pt.b + n + 4, 4);
+      n += 8;
+      chunk_data_start = pos + n;
+      if (r == 0) { pt.b[n] = 0x78; pt.b[n + 1] = 0x01; feed(pt.b + n, 2); n += 2; }      // zlib header: deflate, 32 K window, no dict
+      pt.n = n;
+      patches->push_back(pt);
+      ++next_chunk;
+    }
+    // framing bytes of the row (the kernel wrote the same bytes into the file)
+    uint8_t lead_b[96];
+    for (int i = 0; i < 5 * k; ++i) lead_b[i] = (i % 5 >= 3) ? 0xFF : 0x00;
+    {
+      const int64_t bl = std::min(L.row_bytes, kBlockData);
+      const uint32_t len = static_cast<uint32_t>(bl + 1);
+      uint8_t* q = lead_b + 5 * k;
+      q[0] = (r == h - 1 && L.nb == 1) ? 1 : 0; q[1] = len & 0xFF; q[2] = (len >> 8) & 0xFF; q[3] = (~len) & 0xFF; q[4] = ((~len) >> 8) & 0xFF; q[5] = 0;
+    }
+    feed(lead_b, lead);
+    for (int b = 0; b < L.nb; ++b) {
+      if (b > 0) {
+        uint8_t mid[80];
+        for (int i = 0; i < 75; ++i) mid[i] = (i % 5 >= 3) ? 0xFF : 0x00;
+        const int64_t left = L.row_bytes - b * kBlockData;
+        const uint32_t len = static_cast<uint32_t>(std::min(left, kBlockData));
+        mid[75] = (r == h - 1 && b == L.nb - 1) ? 1 : 0; mid[76] = len & 0xFF; mid[77] = (len >> 8) & 0xFF; mid[78] = (~len) & 0xFF; mid[79] = ((~len) >> 8) & 0xFF;
+        feed(mid, 80);
+      }
+      reg = gf_mul(b == L.nb - 1 ? sh_last : sh_full, reg) ^ crc[static_cast<size_t>(r) * L.nb + b];
+    }
+    pos = pix + L.row_bytes + 80ll * (L.nb - 1);
+  }
+  // trailer: adler32, close the last IDAT, IEND
+  {
+    Patch pt; std::memset(&pt, 0, sizeof pt);
+    pt.at = pos;
+    put32(pt.b, adler); feed(pt.b, 4);
+    put32(pt.b + 4, reg ^ 0xFFFFFFFFu);
+    put32(pt.b + 8, 0); std::memcpy(pt.b + 12, "IEND", 4);
+    uint32_t c = 0xFFFFFFFFu;
+    for (int i = 12; i < 16; ++i) c = crc_byte(T, c, pt.b[i]);
+    put32(pt.b + 16, c ^ 0xFFFFFFFFu);
+    pt.n = 20;
+    patches->push_back(pt);
+    Patch lp; std::memset(&lp, 0, sizeof lp);
+    lp.at = chunk_len_at; lp.n = 4; put32(lp.b, static_cast<uint32_t>(pos + 4 - chunk_data_start));
+    patches->push_back(lp);
+  }
+}
+
 }  // namespace
+
+// The stored form of a batch: every row segment of every file in ONE ist_png_rows_batch_kernel launch; the partials come back in
+// one copy each and every file is finished on the host (stored_patches, as for one file).
+int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
+  const size_t nf = files.size();
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const std::vector<uint32_t>& xpow = stored_tables().xpow;
+  const CrcTables& T = stored_tables().T;
+  std::vector<Layout> lay(nf);
+  std::vector<int64_t> wg(nf + 1, 0), row_at(nf + 1, 0), acc_at(nf + 1, 0);
+  std::vector<uint32_t> segs(nf);
+  for (size_t k = 0; k < nf; ++k) {
+    const PngBatchFile& f = files[k];
+    make_layout(f.w, f.h, &lay[k]);
+    if (lay[k].total > f.cap) return fail(IST_E_INVALID, "file " + std::to_string(k) + ": PNG output buffer too small (see ist_png_bound)");
+    segs[k] = static_cast<uint32_t>((lay[k].row_bytes + 4096 * kChunks - 1) / (4096 * kChunks));
+    wg[k + 1] = wg[k] + static_cast<int64_t>(segs[k]) * f.h;
+    row_at[k + 1] = row_at[k] + f.h;
+    acc_at[k + 1] = acc_at[k] + f.h * lay[k].nb;
+  }
+  if (wg[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
+  const size_t rows = static_cast<size_t>(row_at[nf]), n_acc = static_cast<size_t>(acc_at[nf]);
+  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  // device (the context's PNG scratch): row tables | jobs | wg_begin | xpow | tables | s1 | s2 | crc.  The first three go up from
+  // one pinned block; the partial sums come back into one
+  const size_t o_tab = 0, o_jobs = o_tab + up(8 * rows), o_begin = o_jobs + up(sizeof(RowsJob) * nf), o_pow = o_begin + up(8 * (nf + 1)),
+               o_T = o_pow + up(4 * xpow.size()), o_s1 = o_T + up(sizeof T), o_s2 = o_s1 + up(8 * rows), o_crc = o_s2 + up(8 * rows),
+               total = o_crc + up(4 * n_acc);
+  uint8_t* d = nullptr;
+  {
+    void* p = nullptr;
+    const int rc = ctx_png_scratch(ctx, total, &p);
+    if (rc) return rc;
+    d = static_cast<uint8_t*>(p);
+  }
+  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(std::max(o_pow, total - o_s1)))};
+  if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
+#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
+  RowsJob* hj = reinterpret_cast<RowsJob*>(pin.p + o_jobs);
+  for (size_t k = 0; k < nf; ++k) {
+    const PngBatchFile& f = files[k];
+    std::memcpy(pin.p + o_tab + 8 * row_at[k], lay[k].row_tab.data(), 8 * static_cast<size_t>(f.h));
+    RowsJob& J = hj[k];
+    J.canvas = static_cast<const uint8_t*>(f.canvas); J.pitch = f.pitch; J.out = f.out;
+    J.row_tab = reinterpret_cast<const int64_t*>(d + o_tab) + row_at[k];
+    J.s1 = reinterpret_cast<unsigned long long*>(d + o_s1) + row_at[k];
+    J.s2 = reinterpret_cast<unsigned long long*>(d + o_s2) + row_at[k];
+    J.crc = reinterpret_cast<uint32_t*>(d + o_crc) + acc_at[k];
+    J.row_bytes = lay[k].row_bytes; J.h = static_cast<int32_t>(f.h); J.nb = lay[k].nb; J.segs = segs[k]; J.pad_ = 0;
+  }
+  std::memcpy(pin.p + o_begin, wg.data(), 8 * (nf + 1));
+  PNG_HIP(hipMemcpyAsync(d, pin.p, o_pow, hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemcpyAsync(d + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemcpyAsync(d + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemsetAsync(d + o_s1, 0, total - o_s1, stream));
+  RowsBatchArgs B;
+  B.jobs = reinterpret_cast<const RowsJob*>(d + o_jobs);
+  B.wg_begin = reinterpret_cast<const int64_t*>(d + o_begin);
+  B.n_files = static_cast<int32_t>(nf);
+  B.xpow4 = reinterpret_cast<const uint32_t*>(d + o_pow);
+  B.tables = reinterpret_cast<const uint32_t*>(d + o_T);
+  hipLaunchKernelGGL(ist_png_rows_batch_kernel, dim3(static_cast<unsigned>(wg[nf])), dim3(256), 0, stream, B);
+  PNG_HIP(hipGetLastError());
+  count_png_batch_launch();
+  // the partials into the same pinned block (its upload has been consumed by the time the kernel runs: same stream)
+  PNG_HIP(hipMemcpyAsync(pin.p, d + o_s1, total - o_s1, hipMemcpyDeviceToHost, stream));
+  PNG_HIP(hipStreamSynchronize(stream));
+  const unsigned long long* s1 = reinterpret_cast<const unsigned long long*>(pin.p);
+  const unsigned long long* s2 = reinterpret_cast<const unsigned long long*>(pin.p + (o_s2 - o_s1));
+  const uint32_t* crc = reinterpret_cast<const uint32_t*>(pin.p + (o_crc - o_s1));
+  for (size_t k = 0; k < nf; ++k) {
+    PngBatchFile& f = files[k];
+    f.patches.clear();
+    stored_patches(lay[k], s1 + row_at[k], s2 + row_at[k], crc + acc_at[k], &f.patches);
+    f.len = lay[k].total;
+    if (!host_patches)
+      for (const PngPatch& pt : f.patches) PNG_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
+  }
+  PNG_HIP(hipStreamSynchronize(stream));
+  drain.armed = false;
+#undef PNG_HIP
+  return IST_OK;
+}
 
 }  // namespace ist
 
@@ -221,19 +454,8 @@ int ist_png_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_
   int dev = 0;
   (void)hipGetDevice(&dev);
 
-  static CrcTables T;
-  static std::once_flag tables_once;
-  std::call_once(tables_once, []() { make_crc_tables(&T); });
-  // x^(32 i): the register after 4 i zero bytes, starting from the polynomial "1"
-  const int64_t n_pow = kBlockData / 4 + 1;
-  std::vector<uint32_t> xpow(static_cast<size_t>(n_pow));
-  {
-    uint32_t reg = 0x80000000u;
-    for (int64_t i = 0; i < n_pow; ++i) {
-      xpow[static_cast<size_t>(i)] = reg;
-      for (int z = 0; z < 4; ++z) reg = crc_byte(T, reg, 0);
-    }
-  }
+  const CrcTables& T = stored_tables().T;
+  const std::vector<uint32_t>& xpow = stored_tables().xpow;
   // device scratch: row table, xpow, tables, partial sums
   const size_t n_acc = static_cast<size_t>(h) * L.nb;
   const size_t bytes_tab = sizeof(int64_t) * static_cast<size_t>(h), bytes_pow = 4 * xpow.size(), bytes_T = sizeof(T);
@@ -271,101 +493,9 @@ int ist_png_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_
   PNG_HIP(hipMemcpyAsync(crc.data(), scratch + o_crc, bytes_crc, hipMemcpyDeviceToHost, stream));
   PNG_HIP(hipStreamSynchronize(stream));
 
-  const uint64_t M = 65521;
-  uint64_t ad_a = 1, ad_b = 0;
-  const uint64_t Lrow = static_cast<uint64_t>(L.row_bytes) + 1;
-  for (int64_t r = 0; r < h; ++r) {
-    ad_b = (ad_b + (Lrow % M) * ad_a + s2[static_cast<size_t>(r)] % M) % M;
-    ad_a = (ad_a + s1[static_cast<size_t>(r)] % M) % M;
-  }
-  const uint32_t adler = static_cast<uint32_t>((ad_b << 16) | ad_a);
-
-  // shift operators for the block lengths in use (full block, last block of a row)
-  const int64_t last_bl = L.row_bytes - (L.nb - 1) * kBlockData;
-  const uint32_t sh_full = xpow[static_cast<size_t>(kBlockData / 4)];
-  const uint32_t sh_last = xpow[static_cast<size_t>(last_bl / 4)];
-  struct Patch { int64_t at; uint8_t b[48]; int n; };
-  std::vector<Patch> patches;
-  uint32_t reg = 0xFFFFFFFFu;
-  auto feed = [&](const uint8_t* p, int n) { for (int i = 0; i < n; ++i) reg = crc_byte(T, reg, p[i]); };
-  size_t next_chunk = 0;
-  int64_t chunk_len_at = 0, chunk_data_start = 0;
-  int64_t pos = 0;
-  for (int64_t r = 0; r < h; ++r) {
-    const int64_t tab = L.row_tab[static_cast<size_t>(r)];
-    const int64_t pix = tab & ~15ll; const int k = static_cast<int>(tab & 15);
-    const int lead = 5 * k + 6;
-    if (next_chunk < L.chunk_first_row.size() && L.chunk_first_row[next_chunk] == r) {
-      Patch pt; std::memset(&pt, 0, sizeof pt);
-      int n = 0;
-      if (r == 0) {
-        static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-        std::memcpy(pt.b, sig, 8); n = 8;
-        put32(pt.b + n, 13); std::memcpy(pt.b + n + 4, "IHDR", 4);
-        put32(pt.b + n + 8, static_cast<uint32_t>(w)); put32(pt.b + n + 12, static_cast<uint32_t>(h));
-        pt.b[n + 16] = 8; pt.b[n + 17] = 6; pt.b[n + 18] = 0; pt.b[n + 19] = 0; pt.b[n + 20] = 0;
-        uint32_t c = 0xFFFFFFFFu;
-        for (int i = 4; i < 21; ++i) c = crc_byte(T, c, pt.b[n + i]);
-        put32(pt.b + n + 21, c ^ 0xFFFFFFFFu);
-        n += 25;
-      } else {                      // close the previous IDAT: its CRC, and its length field
-        put32(pt.b, reg ^ 0xFFFFFFFFu); n = 4;
-        Patch lp; std::memset(&lp, 0, sizeof lp);
-        lp.at = chunk_len_at; lp.n = 4; put32(lp.b, static_cast<uint32_t>(pos - chunk_data_start));
-        patches.push_back(lp);
-      }
-      pt.at = pos;
-      chunk_len_at = pos + n;                       // length is patched when the chunk closes
-      std::memcpy(pt.b + n + 4, "IDAT", 4);
-      reg = 0xFFFFFFFFu;
-      feed(pt.b + n + 4, 4);
-      n += 8;
-      chunk_data_start = pos + n;
-      if (r == 0) { pt.b[n] = 0x78; pt.b[n + 1] = 0x01; feed(pt.b + n, 2); n += 2; }      // zlib header: deflate, 32 K window, no dict
-      pt.n = n;
-      patches.push_back(pt);
-      ++next_chunk;
-    }
-    // framing bytes of the row (the kernel wrote the same bytes into the file)
-    uint8_t lead_b[96];
-    for (int i = 0; i < 5 * k; ++i) lead_b[i] = (i % 5 >= 3) ? 0xFF : 0x00;
-    {
-      const int64_t bl = std::min(L.row_bytes, kBlockData);
-      const uint32_t len = static_cast<uint32_t>(bl + 1);
-      uint8_t* q = lead_b + 5 * k;
-      q[0] = (r == h - 1 && L.nb == 1) ? 1 : 0; q[1] = len & 0xFF; q[2] = (len >> 8) & 0xFF; q[3] = (~len) & 0xFF; q[4] = ((~len) >> 8) & 0xFF; q[5] = 0;
-    }
-    feed(lead_b, lead);
-    for (int b = 0; b < L.nb; ++b) {
-      if (b > 0) {
-        uint8_t mid[80];
-        for (int i = 0; i < 75; ++i) mid[i] = (i % 5 >= 3) ? 0xFF : 0x00;
-        const int64_t left = L.row_bytes - b * kBlockData;
-        const uint32_t len = static_cast<uint32_t>(std::min(left, kBlockData));
-        mid[75] = (r == h - 1 && b == L.nb - 1) ? 1 : 0; mid[76] = len & 0xFF; mid[77] = (len >> 8) & 0xFF; mid[78] = (~len) & 0xFF; mid[79] = ((~len) >> 8) & 0xFF;
-        feed(mid, 80);
-      }
-      reg = gf_mul(b == L.nb - 1 ? sh_last : sh_full, reg) ^ crc[static_cast<size_t>(r) * L.nb + b];
-    }
-    pos = pix + L.row_bytes + 80ll * (L.nb - 1);
-  }
-  // trailer: adler32, close the last IDAT, IEND
-  {
-    Patch pt; std::memset(&pt, 0, sizeof pt);
-    pt.at = pos;
-    put32(pt.b, adler); feed(pt.b, 4);
-    put32(pt.b + 4, reg ^ 0xFFFFFFFFu);
-    put32(pt.b + 8, 0); std::memcpy(pt.b + 12, "IEND", 4);
-    uint32_t c = 0xFFFFFFFFu;
-    for (int i = 12; i < 16; ++i) c = crc_byte(T, c, pt.b[i]);
-    put32(pt.b + 16, c ^ 0xFFFFFFFFu);
-    pt.n = 20;
-    patches.push_back(pt);
-    Patch lp; std::memset(&lp, 0, sizeof lp);
-    lp.at = chunk_len_at; lp.n = 4; put32(lp.b, static_cast<uint32_t>(pos + 4 - chunk_data_start));
-    patches.push_back(lp);
-  }
-  for (const Patch& pt : patches)
+  std::vector<PngPatch> patches;
+  stored_patches(L, s1.data(), s2.data(), crc.data(), &patches);
+  for (const PngPatch& pt : patches)
     PNG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
   PNG_HIP(hipStreamSynchronize(stream));
 #undef PNG_HIP

@@ -221,7 +221,8 @@ __device__ __forceinline__ int walk_span(const uint32_t (&sp)[16], int n, const 
   return bits;
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_kernel(const DeflArgs P) {
+// One workgroup compresses chunk `chunk` of the canvas P describes (the body of both compressing kernels below).
+__device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t chunk) {
   // ONE buffer, two lives: the filtered chunk (padded layout) until every thread has taken its span into registers, then the
   // Huffman scratch and the output bit stream
   static_assert(PADDED >= SLOT, "the output buffer aliases the filtered chunk");
@@ -235,7 +236,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void i
   __shared__ uint32_t wsum[8];
   __shared__ int s_out_len, s_skip;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t chunk = P.chunk0 + blockIdx.x;
 
   // ---- which pixels: rows [y0, y0 + nrows) x columns [x0, x0 + npr); the filter byte belongs to the piece with x0 == 0
   int64_t y0; int nrows, x0, npr;
@@ -514,16 +514,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void i
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 6] = wall_clock64();
 }
 
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_kernel(const DeflArgs P) {
+  deflate_chunk(P, P.chunk0 + blockIdx.x);
+}
+
+// ---- batch twins: the chunks of many canvases in ONE launch (png_encode_batch_deflate).  Chunks are numbered file-major;
+// chunk_begin[f] is file f's first, chunk_begin[n_files] the total.  A file's per-chunk results and slots are the arrays'
+// entries [chunk_begin[f], chunk_begin[f + 1]), so the body above runs unchanged on the file's own chunk numbers.
+struct DeflJob { const uint8_t* canvas; size_t pitch; int64_t w, h; int32_t rows_per_chunk, pieces_per_row, piece_px, pad_; };
+struct DeflBatchArgs {
+  const DeflJob* jobs;           // per file (device memory)
+  const int64_t* chunk_begin;    // n_files + 1 (device memory)
+  int32_t n_files;
+  uint8_t* slots;
+  uint32_t* len16; uint32_t* crc; uint32_t* ad_a; uint32_t* ad_b; uint32_t* ad_n;
+  const uint32_t* tables; const uint32_t* xpow16;
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_batch_kernel(const DeflBatchArgs B) {
+  const int64_t g = blockIdx.x;
+  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
+  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
+  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
+  DeflArgs P;
+  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
+  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
+  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
+  P.tables = B.tables; P.xpow16 = B.xpow16;
+  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
+  P.chunk0 = 0; P.dbg = nullptr;
+  deflate_chunk(P, g - base);
+}
+
 struct GatherArgs { const uint8_t* slots; uint8_t* out; const int64_t* dst; const uint32_t* len16; int64_t chunk0; };
+
+__device__ __forceinline__ void gather_chunk(const uint8_t* s, uint8_t* d, const int units) {
+  for (int u = threadIdx.x; u < units; u += 256)
+    *reinterpret_cast<u32x4_a4*>(d + 16 * static_cast<size_t>(u)) = *reinterpret_cast<const u32x4*>(s + 16 * static_cast<size_t>(u));
+}
 
 // chunk j: len16[j] 16-byte units from its slot to file offset dst[j] (4-byte aligned)
 __global__ __launch_bounds__(256) void ist_png_gather_kernel(const GatherArgs G) {
   const int64_t j = G.chunk0 + blockIdx.x;
-  const uint8_t* s = G.slots + static_cast<size_t>(j) * SLOT;
-  uint8_t* d = G.out + G.dst[j];
-  const int units = static_cast<int>(G.len16[j]);
-  for (int u = threadIdx.x; u < units; u += 256)
-    *reinterpret_cast<u32x4_a4*>(d + 16 * static_cast<size_t>(u)) = *reinterpret_cast<const u32x4*>(s + 16 * static_cast<size_t>(u));
+  gather_chunk(G.slots + static_cast<size_t>(j) * SLOT, G.out + G.dst[j], static_cast<int>(G.len16[j]));
+}
+
+// batch twin: every chunk of every file of a batch; dst[j] is the chunk's ADDRESS in its file's buffer (files live in separate buffers)
+struct GatherBatchArgs { const uint8_t* slots; const uint64_t* dst; const uint32_t* len16; };
+__global__ __launch_bounds__(256) void ist_png_gather_batch_kernel(const GatherBatchArgs G) {
+  const int64_t j = blockIdx.x;
+  gather_chunk(G.slots + static_cast<size_t>(j) * SLOT, reinterpret_cast<uint8_t*>(G.dst[j]), static_cast<int>(G.len16[j]));
 }
 
 // device -> pinned host, 16-byte units, a FIXED small grid striding over the range: the slab's trip over PCIe as a kernel that
@@ -555,6 +595,103 @@ int64_t idat_limit() {
 
 constexpr int kDataStart = 64;     // signature 8 + IHDR 25 + tEXt 23 + IDAT length/type 8: the stream starts 16-byte aligned
 
+// CRC slicing tables + x^(128 i): what the kernels and the host layout share, built once
+struct DeflTables { CrcTables T; std::vector<uint32_t> xpow; };
+const DeflTables& defl_tables() {
+  static DeflTables D;
+  static std::once_flag once;
+  std::call_once(once, []() {
+    make_crc_tables(&D.T);
+    D.xpow.resize(SLOT / 16 + 2);
+    uint32_t reg = 0x80000000u;                      // the polynomial "1"
+    for (size_t i = 0; i < D.xpow.size(); ++i) { D.xpow[i] = reg; for (int z = 0; z < 16; ++z) reg = crc_byte(D.T, reg, 0); }
+  });
+  return D;
+}
+
+// The host side of ONE file, called slab by slab (the whole file is one slab in a batch): Adler-32 of the filtered stream from
+// the chunks' partials, each chunk's place in the file (a new IDAT chunk per slab, and wherever the IDAT limit is reached), the
+// CRC of every IDAT, and the ~100 bytes no kernel writes - signature, IHDR, chunk headers, trailer - as patches.
+struct FileLayout {
+  const CrcTables& T; const std::vector<uint32_t>& xpow; const int64_t limit;
+  uint64_t a = 1, b = 0;
+  uint32_t reg = 0xFFFFFFFFu;
+  int64_t pos = 56, idat_len_at = 0, idat_data = 0;
+  std::vector<PngPatch>* patches = nullptr;
+  FileLayout() : T(defl_tables().T), xpow(defl_tables().xpow), limit(idat_limit()) {}
+  void feed(const uint8_t* p, int k) { for (int i = 0; i < k; ++i) reg = crc_byte(T, reg, p[i]); }
+  void header(int64_t w, int64_t h, std::vector<PngPatch>* out) {
+    PngPatch pt; std::memset(&pt, 0, sizeof pt);
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    std::memcpy(pt.b, sig, 8);
+    put32(pt.b + 8, 13); std::memcpy(pt.b + 12, "IHDR", 4);
+    put32(pt.b + 16, static_cast<uint32_t>(w)); put32(pt.b + 20, static_cast<uint32_t>(h));
+    pt.b[24] = 8; pt.b[25] = 6; pt.b[26] = 0; pt.b[27] = 0; pt.b[28] = 0;
+    uint32_t c = 0xFFFFFFFFu;
+    for (int i = 12; i < 29; ++i) c = crc_byte(T, c, pt.b[i]);
+    put32(pt.b + 29, c ^ 0xFFFFFFFFu);
+    // an 11-byte tEXt chunk: its only job is to start the IDAT data at file offset 64
+    put32(pt.b + 33, 11); std::memcpy(pt.b + 37, "tEXtSoftware\0is", 15);
+    c = 0xFFFFFFFFu;
+    for (int i = 37; i < 52; ++i) c = crc_byte(T, c, pt.b[i]);
+    put32(pt.b + 52, c ^ 0xFFFFFFFFu);
+    pt.at = 0; pt.n = 56;
+    out->push_back(pt);
+  }
+  void open_idat() {
+    PngPatch pt; std::memset(&pt, 0, sizeof pt);
+    pt.at = pos; idat_len_at = pos;
+    std::memcpy(pt.b + 4, "IDAT", 4);
+    pt.n = 8; patches->push_back(pt);
+    reg = 0xFFFFFFFFu; feed(pt.b + 4, 4);
+    pos += 8; idat_data = 0;
+  }
+  void close_idat() {
+    PngPatch pt; std::memset(&pt, 0, sizeof pt);
+    pt.at = pos; put32(pt.b, reg ^ 0xFFFFFFFFu); pt.n = 4; patches->push_back(pt);
+    PngPatch lp; std::memset(&lp, 0, sizeof lp);
+    lp.at = idat_len_at; put32(lp.b, static_cast<uint32_t>(idat_data)); lp.n = 4; patches->push_back(lp);
+    pos += 4;
+  }
+  // chunks [0, cn) of the slab with the kernel's per-chunk results; dst[k] = base + the chunk's offset in the file.  last: the
+  // file ends with this slab (trailer, IEND)
+  int slab(const uint32_t* len16, const uint32_t* crc, const uint32_t* ada, const uint32_t* adb, const uint32_t* adn, size_t cn,
+           int64_t* dst, int64_t base, bool last, std::vector<PngPatch>* out) {
+    const uint64_t M = 65521;
+    patches = out;
+    open_idat();                                       // a slab starts its own IDAT
+    for (size_t k = 0; k < cn; ++k) {
+      b = (b + (adn[k] % M) * a + adb[k]) % M;
+      a = (a + ada[k]) % M;
+      const int64_t bytes = static_cast<int64_t>(len16[k]) * 16;
+      if (bytes <= 0 || bytes > SLOT) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length");
+      if (idat_data > 0 && idat_data + bytes + 9 > limit) { close_idat(); open_idat(); }
+      dst[k] = base + pos;
+      reg = gf_mul(xpow[static_cast<size_t>(len16[k])], reg) ^ crc[k];
+      pos += bytes; idat_data += bytes;
+    }
+    if (last) {
+      static const uint8_t trailer_block[5] = {0x01, 0x00, 0x00, 0xFF, 0xFF};          // final, empty stored block
+      const uint32_t adler = static_cast<uint32_t>((b << 16) | a);
+      PngPatch pt; std::memset(&pt, 0, sizeof pt);
+      pt.at = pos;
+      std::memcpy(pt.b, trailer_block, 5); put32(pt.b + 5, adler);
+      feed(pt.b, 9);
+      pt.n = 9; patches->push_back(pt);
+      pos += 9; idat_data += 9;
+      close_idat();
+      PngPatch ie; std::memset(&ie, 0, sizeof ie);
+      ie.at = pos; put32(ie.b, 0); std::memcpy(ie.b + 4, "IEND", 4);
+      uint32_t c = 0xFFFFFFFFu;
+      for (int i = 4; i < 8; ++i) c = crc_byte(T, c, ie.b[i]);
+      put32(ie.b + 8, c ^ 0xFFFFFFFFu);
+      ie.n = 12; patches->push_back(ie);
+      pos += 12;
+    } else close_idat();
+    return IST_OK;
+  }
+};
+
 }  // namespace
 
 // upper bound of the compressed form: every chunk stored
@@ -579,15 +716,8 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   // so every slab paid its own tail - the last, partly filled round of workgroups - with the rest of the chip idle; on two
   // streams slab s+1 fills in as slab s drains (a slab is ~3 rounds of workgroups: measured 0.59 ms per 3024-chunk slab alone)
   hipStream_t stream2 = (host_out && stream2_) ? static_cast<hipStream_t>(stream2_) : stream;
-  static CrcTables T;
-  static std::vector<uint32_t> xpow;
-  static std::once_flag once;
-  std::call_once(once, []() {
-    make_crc_tables(&T);
-    xpow.resize(SLOT / 16 + 2);
-    uint32_t reg = 0x80000000u;                      // the polynomial "1"
-    for (size_t i = 0; i < xpow.size(); ++i) { xpow[i] = reg; for (int z = 0; z < 16; ++z) reg = crc_byte(T, reg, 0); }
-  });
+  const CrcTables& T = defl_tables().T;
+  const std::vector<uint32_t>& xpow = defl_tables().xpow;
   const size_t n = static_cast<size_t>(g.n_chunks);
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // per-chunk results, five arrays interleaved per SLAB so that a slab's results are one contiguous copy:
@@ -691,51 +821,10 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
 
   // ---- host, slab by slab: Adler-32 of the filtered stream, the layout of the chunks in the file, the CRC of every
   // IDAT; then the slab's gather (and its trip to the host) on the aux stream
-  const uint64_t M = 65521;
-  uint64_t a = 1, b = 0;
-  struct Patch { int64_t at; uint8_t b[64]; int n; };
+  FileLayout lay;
   int64_t* const dst = dstp.p;
-  const int64_t limit = idat_limit();
-  static const uint8_t trailer_block[5] = {0x01, 0x00, 0x00, 0xFF, 0xFF};          // final, empty stored block
-  uint32_t reg = 0xFFFFFFFFu;
-  auto feed = [&](const uint8_t* p, int k) { for (int i = 0; i < k; ++i) reg = crc_byte(T, reg, p[i]); };
-  std::vector<std::vector<Patch>> slab_patches(n_slabs);     // (all of them live until the final synchronisation)
-  std::vector<Patch>* cur = &slab_patches[0];
-#define patches (*cur)
-  {
-    Patch pt; std::memset(&pt, 0, sizeof pt);
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-    std::memcpy(pt.b, sig, 8);
-    put32(pt.b + 8, 13); std::memcpy(pt.b + 12, "IHDR", 4);
-    put32(pt.b + 16, static_cast<uint32_t>(w)); put32(pt.b + 20, static_cast<uint32_t>(h));
-    pt.b[24] = 8; pt.b[25] = 6; pt.b[26] = 0; pt.b[27] = 0; pt.b[28] = 0;
-    uint32_t c = 0xFFFFFFFFu;
-    for (int i = 12; i < 29; ++i) c = crc_byte(T, c, pt.b[i]);
-    put32(pt.b + 29, c ^ 0xFFFFFFFFu);
-    // an 11-byte tEXt chunk: its only job is to start the IDAT data at file offset 64
-    put32(pt.b + 33, 11); std::memcpy(pt.b + 37, "tEXtSoftware\0is", 15);
-    c = 0xFFFFFFFFu;
-    for (int i = 37; i < 52; ++i) c = crc_byte(T, c, pt.b[i]);
-    put32(pt.b + 52, c ^ 0xFFFFFFFFu);
-    pt.at = 0; pt.n = 56;
-    patches.push_back(pt);
-  }
-  int64_t pos = 56, idat_len_at = 0, idat_data = 0;
-  auto open_idat = [&]() {
-    Patch pt; std::memset(&pt, 0, sizeof pt);
-    pt.at = pos; idat_len_at = pos;
-    std::memcpy(pt.b + 4, "IDAT", 4);
-    pt.n = 8; patches.push_back(pt);
-    reg = 0xFFFFFFFFu; feed(pt.b + 4, 4);
-    pos += 8; idat_data = 0;
-  };
-  auto close_idat = [&]() {
-    Patch pt; std::memset(&pt, 0, sizeof pt);
-    pt.at = pos; put32(pt.b, reg ^ 0xFFFFFFFFu); pt.n = 4; patches.push_back(pt);
-    Patch lp; std::memset(&lp, 0, sizeof lp);
-    lp.at = idat_len_at; put32(lp.b, static_cast<uint32_t>(idat_data)); lp.n = 4; patches.push_back(lp);
-    pos += 4;
-  };
+  std::vector<std::vector<PngPatch>> slab_patches(n_slabs);     // (all of them live until the final synchronisation)
+  lay.header(w, h, &slab_patches[0]);
   for (size_t s = 0; s < n_slabs; ++s) {
     const size_t c0 = slab_at[s], cn = slab_at[s + 1] - c0;
     if (s + 1 < n_slabs) { const int rc = compress(s + 1); if (rc) return rc; tl_mark("png: submitted the compression of slab", static_cast<long>(s + 1)); }
@@ -743,42 +832,15 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     tl_mark("png: compressed (event passed), slab", static_cast<long>(s));
     if (fail_at >= 0 && static_cast<size_t>(fail_at) == s) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length (forced: IST_PNG_FAIL_AT)");
     const uint8_t* r = res.p + 20 * per_slab * s;
-    const uint32_t* len16 = reinterpret_cast<const uint32_t*>(r);
-    const uint32_t* crc = reinterpret_cast<const uint32_t*>(r + 4 * per_slab);
-    const uint32_t* ada = reinterpret_cast<const uint32_t*>(r + 8 * per_slab);
-    const uint32_t* adb = reinterpret_cast<const uint32_t*>(r + 12 * per_slab);
-    const uint32_t* adn = reinterpret_cast<const uint32_t*>(r + 16 * per_slab);
-    const int64_t slab_begin = s == 0 ? 0 : pos;       // file bytes [slab_begin, pos) are final once this slab is laid out
-    cur = &slab_patches[s];
-    open_idat();                                       // a slab starts its own IDAT
-    for (size_t k = 0; k < cn; ++k) {
-      const size_t j = c0 + k;
-      b = (b + (adn[k] % M) * a + adb[k]) % M;
-      a = (a + ada[k]) % M;
-      const int64_t bytes = static_cast<int64_t>(len16[k]) * 16;
-      if (bytes <= 0 || bytes > SLOT) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length");
-      if (idat_data > 0 && idat_data + bytes + 9 > limit) { close_idat(); open_idat(); }
-      dst[j] = pos;
-      reg = gf_mul(xpow[static_cast<size_t>(len16[k])], reg) ^ crc[k];
-      pos += bytes; idat_data += bytes;
+    const int64_t slab_begin = s == 0 ? 0 : lay.pos;   // file bytes [slab_begin, pos) are final once this slab is laid out
+    {
+      const int rc = lay.slab(reinterpret_cast<const uint32_t*>(r), reinterpret_cast<const uint32_t*>(r + 4 * per_slab),
+                              reinterpret_cast<const uint32_t*>(r + 8 * per_slab), reinterpret_cast<const uint32_t*>(r + 12 * per_slab),
+                              reinterpret_cast<const uint32_t*>(r + 16 * per_slab), cn, dst + c0, 0, s + 1 == n_slabs, &slab_patches[s]);
+      if (rc) return rc;
     }
-    if (s + 1 == n_slabs) {
-      const uint32_t adler = static_cast<uint32_t>((b << 16) | a);
-      Patch pt; std::memset(&pt, 0, sizeof pt);
-      pt.at = pos;
-      std::memcpy(pt.b, trailer_block, 5); put32(pt.b + 5, adler);
-      feed(pt.b, 9);
-      pt.n = 9; patches.push_back(pt);
-      pos += 9; idat_data += 9;
-      close_idat();
-      Patch ie; std::memset(&ie, 0, sizeof ie);
-      ie.at = pos; put32(ie.b, 0); std::memcpy(ie.b + 4, "IEND", 4);
-      uint32_t c = 0xFFFFFFFFu;
-      for (int i = 4; i < 8; ++i) c = crc_byte(T, c, ie.b[i]);
-      put32(ie.b + 8, c ^ 0xFFFFFFFFu);
-      ie.n = 12; patches.push_back(ie);
-      pos += 12;
-    } else close_idat();
+    const int64_t pos = lay.pos;
+    const std::vector<PngPatch>& patches = slab_patches[s];
     if (pos > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
     // The gather rides on the stream that compressed the slab (its slots and results are complete: the event above has passed;
     // the next slab is already compressing on the other stream), and the aux stream carries NOTHING but the slabs' trips over
@@ -800,7 +862,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
       tl_mark("png:   event created + recorded + aux ordered behind it, slab", static_cast<long>(s));
     }
     if (!host_out)                                     // (with a host sink the headers are written there, below)
-      for (const Patch& pt : patches)
+      for (const PngPatch& pt : patches)
         PNG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, aux));
     if (host_out) {
       // 256-byte aligned ends.  The bytes past `pos` in the last 256 are the next slab's: its own copy, ordered behind
@@ -839,11 +901,94 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     for (int k = 0; k < 6; ++k) std::fprintf(stderr, "[png phases] %-18s %8.2f us per chunk (100 MHz clock)\n", names[k], sum[k] / static_cast<double>(n) / 100.0);
   }
 #undef PNG_HIP
-#undef patches
   if (host_out)                                        // signature, chunk headers, lengths, CRCs, trailer: ~30 bytes per slab
-    for (const std::vector<Patch>& v : slab_patches)
-      for (const Patch& pt : v) std::memcpy(host_out + pt.at, pt.b, static_cast<size_t>(pt.n));
-  *out_len = pos;
+    for (const std::vector<PngPatch>& v : slab_patches)
+      for (const PngPatch& pt : v) std::memcpy(host_out + pt.at, pt.b, static_cast<size_t>(pt.n));
+  *out_len = lay.pos;
+  return IST_OK;
+}
+
+int64_t png_deflate_chunks(int64_t w, int64_t h) { return make_grid(w, h).n_chunks; }
+int64_t png_deflate_slot_bytes() { return SLOT; }
+
+// The compressing form of a batch: every chunk of every file in ONE ist_png_deflate_batch_kernel launch, the host layout of
+// each file (FileLayout, as for one file), then every chunk of every file in ONE ist_png_gather_batch_kernel launch.
+int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
+  const size_t nf = files.size();
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  std::vector<ChunkGrid> grid(nf);
+  std::vector<int64_t> begin(nf + 1, 0);
+  for (size_t k = 0; k < nf; ++k) {
+    grid[k] = make_grid(files[k].w, files[k].h);
+    begin[k + 1] = begin[k] + grid[k].n_chunks;
+  }
+  if (begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
+  const size_t n = static_cast<size_t>(begin[nf]);
+  const CrcTables& T = defl_tables().T;
+  const std::vector<uint32_t>& xpow = defl_tables().xpow;
+  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  // device: tables | per-file jobs | chunk_begin | slots;  pinned host: per-chunk results [len16 | crc | ad_a | ad_b | ad_n] |
+  // per-chunk destination addresses (read in place by the gather) | the jobs + chunk_begin image that goes up
+  const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_jobs = o_pow + up(4 * xpow.size()), o_begin = o_jobs + up(sizeof(DeflJob) * nf),
+               o_slots = o_begin + up(8 * (nf + 1)), total_scratch = o_slots + n * SLOT;
+  const size_t h_res = 0, h_dst = up(20 * n), h_jobs = h_dst + up(8 * n), h_total = h_jobs + (o_slots - o_jobs);
+  uint8_t* scratch = nullptr;
+  {
+    void* p = nullptr;
+    const int rc = ctx_png_scratch(ctx, total_scratch, &p);
+    if (rc) return rc;
+    scratch = static_cast<uint8_t*>(p);
+  }
+  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(h_total))};
+  if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  // every way out below waits for the stream first: the kernels write `pin` and read it in place (declared after it: runs first)
+  struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
+#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
+  DeflJob* hj = reinterpret_cast<DeflJob*>(pin.p + h_jobs);
+  int64_t* hb = reinterpret_cast<int64_t*>(pin.p + h_jobs + (o_begin - o_jobs));
+  for (size_t k = 0; k < nf; ++k) {
+    const PngBatchFile& f = files[k];
+    hj[k] = DeflJob{static_cast<const uint8_t*>(f.canvas), f.pitch, f.w, f.h, grid[k].rows_per_chunk, grid[k].pieces_per_row, grid[k].piece_px, 0};
+  }
+  std::memcpy(hb, begin.data(), 8 * (nf + 1));
+  PNG_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_slots - o_jobs, hipMemcpyHostToDevice, stream));
+  uint32_t* res = reinterpret_cast<uint32_t*>(pin.p + h_res);
+  DeflBatchArgs B;
+  B.jobs = reinterpret_cast<const DeflJob*>(scratch + o_jobs);
+  B.chunk_begin = reinterpret_cast<const int64_t*>(scratch + o_begin);
+  B.n_files = static_cast<int32_t>(nf);
+  B.slots = scratch + o_slots;
+  B.len16 = res; B.crc = res + n; B.ad_a = res + 2 * n; B.ad_b = res + 3 * n; B.ad_n = res + 4 * n;
+  B.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); B.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
+  hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
+  PNG_HIP(hipGetLastError());
+  count_png_batch_launch();
+  PNG_HIP(hipStreamSynchronize(stream));
+  // ---- host: each file laid out as one slab
+  int64_t* dst = reinterpret_cast<int64_t*>(pin.p + h_dst);
+  for (size_t k = 0; k < nf; ++k) {
+    PngBatchFile& f = files[k];
+    const size_t c0 = static_cast<size_t>(begin[k]), cn = static_cast<size_t>(begin[k + 1] - begin[k]);
+    FileLayout lay;
+    f.patches.clear();
+    lay.header(f.w, f.h, &f.patches);
+    const int rc = lay.slab(res + c0, res + n + c0, res + 2 * n + c0, res + 3 * n + c0, res + 4 * n + c0, cn, dst + c0,
+                            static_cast<int64_t>(reinterpret_cast<uintptr_t>(f.out)), true, &f.patches);
+    if (rc) { const std::string why = g_last_error; return fail(rc, "file " + std::to_string(k) + ": " + why); }
+    if (lay.pos > f.cap) return fail(IST_E_INVALID, "file " + std::to_string(k) + ": PNG output buffer too small (see ist_png_bound)");
+    f.len = lay.pos;
+  }
+  GatherBatchArgs G{scratch + o_slots, reinterpret_cast<const uint64_t*>(dst), res};
+  hipLaunchKernelGGL(ist_png_gather_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, G);
+  PNG_HIP(hipGetLastError());
+  if (!host_patches)
+    for (const PngBatchFile& f : files)
+      for (const PngPatch& pt : f.patches) PNG_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipStreamSynchronize(stream));
+  drain.armed = false;
+#undef PNG_HIP
   return IST_OK;
 }
 

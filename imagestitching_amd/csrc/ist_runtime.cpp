@@ -203,7 +203,7 @@ void ist_ctx_destroy(ist_ctx* ctx) {
     dev_free(s.dev);
   }
   for (ist_ctx::BatchHalf& h : ctx->batch_half) {
-    dev_free(h.tab); dev_free(h.src); dev_free(h.dst);
+    dev_free(h.tab); dev_free(h.src); dev_free(h.dst); dev_free(h.file);
     if (h.kernel_done) (void)hipEventDestroy(h.kernel_done);
     if (h.read_done) (void)hipEventDestroy(h.read_done);
   }

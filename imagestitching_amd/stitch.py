@@ -7,7 +7,8 @@ this.data.{images, direction, gap, verticalStitchMode, horizontalStitchMode}; he
 Two ways in:
   stitch(images, direction, opts)      host RGBA8 arrays in, host RGBA8 array out   (ist_stitch_rgba8)
   Stitcher(device).compile(...)        device-resident: torch CUDA tensors in/out, one fused launch per call
-and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch) and launch_jobs(jobs, srcs, outs) (ist_jobs_launch).
+and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch), stitch_png_batch(requests) (ist_stitch_png_batch),
+launch_jobs(jobs, srcs, outs) (ist_jobs_launch) and encode_png_batch_device(canvases) (ist_png_encode_batch_device).
 """
 import ctypes as C
 import os
@@ -232,18 +233,11 @@ def stitch(images, direction, opts=None, device=0):
     return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
 
 
-_BATCH_REFUSED = ("devices", "split", "pngLevel")      # a batch runs on one GPU and returns pixels, not PNG files
+_BATCH_REFUSED = ("devices", "split", "pngLevel")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files
 
 
-def stitch_batch(requests, device=0):
-    """Many independent stitch() calls in one go (ist_stitch_rgba8_batch): the requests' tables go up in one copy, their
-    canvases are rendered by one launch per kernel form, and each comes back into a pinned block of its own.
-
-    requests[k] = (images, direction) or (images, direction, opts), each exactly as stitch() takes them.  Returns a list of
-    HxWx4 uint8 arrays, byte-identical to stitch(*requests[k])['data'], with None for a request without images."""
-    reqs = list(requests)
-    if not reqs:
-        return []
+def _batch_requests(reqs, why):
+    """ctypes StitchRequest array of stitch_batch / stitch_png_batch requests (+ what must stay alive during the call)"""
     n = len(reqs)
     creqs = (L.StitchRequest * n)()
     keep = []
@@ -254,7 +248,7 @@ def stitch_batch(requests, device=0):
         opts = r[2] if len(r) == 3 else None
         bad = sorted(x for x in (opts or {}) if x in _BATCH_REFUSED)
         if bad:
-            raise TypeError("request %d: option(s) %s do not apply to a batch (one GPU, pixels out)" % (k, bad))
+            raise TypeError("request %d: option(s) %s do not apply to a batch (%s)" % (k, bad, why))
         o = _merge(opts)
         if direction not in _DIRECTIONS:
             raise ValueError("request %d: direction must be 'vertical' or 'horizontal'" % k)
@@ -278,6 +272,20 @@ def stitch_batch(requests, device=0):
         keep.append((descs, ptrs, pitches, arrays, lim))
         creqs[k] = L.StitchRequest(descs, ptrs, pitches, m, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
                                    C.pointer(lim), _filter_of(o), 0)
+    return creqs, keep
+
+
+def stitch_batch(requests, device=0):
+    """Many independent stitch() calls in one go (ist_stitch_rgba8_batch): the requests' tables go up in one copy, their
+    canvases are rendered by one launch per kernel form, and each comes back into a pinned block of its own.
+
+    requests[k] = (images, direction) or (images, direction, opts), each exactly as stitch() takes them.  Returns a list of
+    HxWx4 uint8 arrays, byte-identical to stitch(*requests[k])['data'], with None for a request without images."""
+    reqs = list(requests)
+    if not reqs:
+        return []
+    n = len(reqs)
+    creqs, keep = _batch_requests(reqs, "one GPU, pixels out")
     ctx = _ctx(device)
     plans = (L.Plan * n)()
     outs = (C.POINTER(C.c_uint8) * n)()
@@ -290,6 +298,33 @@ def stitch_batch(requests, device=0):
         w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
         L.lib.ist_plan_free(C.byref(plans[k]))
         res.append(_take_pixels(outs[k], w, h))
+    return res
+
+
+def stitch_png_batch(requests, device=0, level=None):
+    """Many independent stitch_png() calls in one go (ist_stitch_png_batch): stitch_batch with a PNG file in place of each
+    canvas.  Every sub-batch is rendered by one launch per kernel form and encoded by ONE compression launch; only the files
+    cross PCIe.  requests as for stitch_batch (no per-request pngLevel: `level` chooses the form for the whole batch, 0 stored,
+    1 compressed, None = DEFAULT_PNG_LEVEL).  Returns a list of {'width', 'height', 'png': bytes}, with None for a request
+    without images; each file's zlib stream is stitch_png(*requests[k])['png']'s, byte for byte."""
+    reqs = list(requests)
+    if not reqs:
+        return []
+    n = len(reqs)
+    creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=")
+    ctx = _ctx_png(device, level)
+    plans = (L.Plan * n)()
+    outs = (C.POINTER(C.c_uint8) * n)()
+    lens = (C.c_int64 * n)()
+    L.check(L.lib.ist_stitch_png_batch(ctx, creqs, n, plans, outs, lens))
+    res = []
+    for k in range(n):
+        if not outs[k]:
+            res.append(None)
+            continue
+        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
+        L.lib.ist_plan_free(C.byref(plans[k]))
+        res.append({"width": w, "height": h, "png": _take_png(outs[k], C.c_int64(lens[k]))})
     return res
 
 
@@ -531,6 +566,36 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
                                         C.c_void_p(aligned), out.numel() - (aligned - base), C.byref(n), C.c_void_p(st.cuda_stream)))
     off = aligned - base
     return out[off:off + n.value], n.value
+
+
+def encode_png_batch_device(canvases, outs=None, stream=None, level=None):
+    """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
+    launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns
+    [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas."""
+    import torch
+    n = len(canvases)
+    if n == 0:
+        return []
+    dev = canvases[0].device
+    if outs is None:
+        outs = [torch.empty(int(L.lib.ist_png_bound(int(c.shape[1]), int(c.shape[0]))) + 16, dtype=torch.uint8, device=dev) for c in canvases]
+    if len(outs) != n:
+        raise ValueError("encode_png_batch_device: canvases and outs must have the same length")
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    src, pitch = (C.c_void_p * n)(), (C.c_size_t * n)()
+    w, h = (C.c_int64 * n)(), (C.c_int64 * n)()
+    dst, cap, ln = (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+    offs = []
+    for k, (c, o) in enumerate(zip(canvases, outs)):
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 4 or c.stride(2) != 1 or c.stride(1) != 4:
+            raise TypeError("canvas %d: expected an HxWx4 uint8 CUDA tensor with dense pixels" % k)
+        src[k], pitch[k], h[k], w[k] = c.data_ptr(), c.stride(0), int(c.shape[0]), int(c.shape[1])
+        base = o.data_ptr()
+        aligned = (base + 15) & ~15
+        offs.append(aligned - base)
+        dst[k], cap[k] = aligned, o.numel() - (aligned - base)
+    L.check(L.lib.ist_png_encode_batch_device(_ctx_png(dev.index or 0, level), src, pitch, w, h, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
+    return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(zip(outs, offs))]
 
 
 class StitchJob:

@@ -395,6 +395,15 @@ IST_API int64_t ist_png_bound(int64_t w, int64_t h);
  * pass; the checksums are combined on the host, so the call synchronises `stream` before it returns */
 IST_API int ist_png_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out,
                                   int64_t out_cap, int64_t* out_len, void* stream);
+/* N canvases resident in HBM -> N PNG files in caller device buffers, ONE compression launch (at the context's level) and one
+ * gather launch for all of them; synchronises `stream` before it returns (checksums are combined on the host).  File k is
+ * byte for byte the file ist_png_encode_device writes for canvas k.  Every canvas is checked by the rules of
+ * ist_png_encode_device (out[k] 16-byte aligned, out_cap[k] >= ist_png_bound) before anything is enqueued; a bad one fails the
+ * whole call with a message that names it.  IST_E_INVALID: n <= 0; IST_E_UNSUPPORTED: n > 4096. */
+IST_API int ist_png_encode_batch_device(ist_ctx* ctx, const void* const* canvases, const size_t* pitch,
+                                        const int64_t* w, const int64_t* h, int n, void* const* out,
+                                        const int64_t* out_cap, int64_t* out_len, void* stream);
+IST_API int64_t ist_debug_png_batch_launches(void);   /* compression launches made by batch encodes so far */
 /* host pixels -> PNG bytes (library-owned, release with ist_free) */
 IST_API int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int64_t w, int64_t h,
                                  uint8_t** out_png, int64_t* out_len);
@@ -407,6 +416,14 @@ IST_API int ist_stitch_png(ist_ctx* ctx, const ist_image_desc* images, const uin
                            const size_t* src_pitch, int n_images, int direction, int mode, double gap,
                            const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png,
                            int64_t* out_len);
+/* N x Page.onStitch with the export (index.js:1186-1633): ist_stitch_rgba8_batch with a PNG file in place of each canvas.  Every
+ * sub-batch is rendered by one ist_jobs_launch and encoded straight from device memory by ONE compression launch (at the
+ * context's level) and one gather launch; its files come down while the next sub-batch's sources go up.  out_png[k] /
+ * out_len[k] are what ist_stitch_png returns for request k (the zlib stream byte for byte; IDAT chunk boundaries may differ),
+ * each a pinned block of its real length from the batch class of the result pool (release with ist_free).  A request without
+ * images gets NULL and a zeroed plan; any failing request fails the whole call (the message names it) and nothing is returned. */
+IST_API int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans,
+                                 uint8_t** out_png, int64_t* out_len);
 
 #ifdef __cplusplus
 }

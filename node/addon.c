@@ -12,6 +12,8 @@
  *   stitchSync(...same...)                                             -> {width,height,data}
  *   stitchBatch(requests) / stitchBatchSync(requests): requests[k] = [images, direction, mode, gap, limits, filter]
  *       -> Promise<({width,height,data,plan} | null)[]> / the array itself  (ist_stitch_rgba8_batch: one GPU, many stitches)
+ *   stitchPngBatch(requests) / stitchPngBatchSync(requests): the same requests
+ *       -> Promise<({width,height,png,plan} | null)[]> / the array itself  (ist_stitch_png_batch: one GPU, many PNG files)
  *   render(canvasW, canvasH, clearRGBA, ops, images, filter, region, asPng?) -> Buffer (region pixels, or the PNG file)
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
  *   deviceCount(), lastError(), abiVersion()
@@ -415,6 +417,7 @@ typedef struct {
   ist_stitch_request* reqs;
   ist_plan* plans;
   uint8_t** pixels;
+  int want_png; int64_t* lens;            /* stitchPngBatch: pixels[k] holds request k's PNG file, lens[k] bytes */
   int rc; char err[256];
   napi_deferred deferred; napi_async_work work;
 } batch_job;
@@ -426,7 +429,7 @@ static void batch_free(napi_env env, batch_job* j) {
     if (j->plans) ist_plan_free(&j->plans[k]);
     if (j->pixels && j->pixels[k]) ist_free(j->pixels[k]);
   }
-  free(j->im); free(j->lim); free(j->reqs); free(j->plans); free(j->pixels); free(j);
+  free(j->im); free(j->lim); free(j->reqs); free(j->plans); free(j->pixels); free(j->lens); free(j);
 }
 
 static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_refs) {
@@ -444,6 +447,7 @@ static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_re
   j->reqs = (ist_stitch_request*)calloc(n ? n : 1, sizeof(ist_stitch_request));
   j->plans = (ist_plan*)calloc(n ? n : 1, sizeof(ist_plan));
   j->pixels = (uint8_t**)calloc(n ? n : 1, sizeof(uint8_t*));
+  j->lens = (int64_t*)calloc(n ? n : 1, sizeof(int64_t));
   for (uint32_t k = 0; k < n; k++) {
     napi_value r, a[6]; bool ra = false; uint32_t m = 0;
     napi_get_element(env, argv[0], k, &r);
@@ -478,7 +482,8 @@ static void batch_execute(napi_env env, void* data) {
         snprintf(j->err, sizeof j->err, "request %d: \xe5\x9b\xbe\xe7\x89\x87%d\xe8\xa7\xa3\xe7\xa0\x81\xe5\xbc\x82\xe5\xb8\xb8", k, i);
         return;
       }
-  j->rc = ist_stitch_rgba8_batch(ctx, j->reqs, j->n, j->plans, j->pixels);
+  j->rc = j->want_png ? ist_stitch_png_batch(ctx, j->reqs, j->n, j->plans, j->pixels, j->lens)
+                      : ist_stitch_rgba8_batch(ctx, j->reqs, j->n, j->plans, j->pixels);
   if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
 }
 
@@ -491,12 +496,13 @@ static napi_value batch_result(napi_env env, batch_job* j) {
     if (!j->pixels[k]) { napi_get_null(env, &e); napi_set_element(env, arr, (uint32_t)k, e); continue; }
     const ist_plan* p = &j->plans[k];
     napi_value buf;
-    if (napi_create_external_buffer(env, (size_t)p->canvas_w * (size_t)p->canvas_h * 4, j->pixels[k], free_pixels, NULL, &buf) != napi_ok) return NULL;
+    const size_t bytes = j->want_png ? (size_t)j->lens[k] : (size_t)p->canvas_w * (size_t)p->canvas_h * 4;
+    if (napi_create_external_buffer(env, bytes, j->pixels[k], free_pixels, NULL, &buf) != napi_ok) return NULL;
     j->pixels[k] = NULL;                                  /* the Buffer owns it now */
     napi_create_object(env, &e);
     set_num(env, e, "width", (double)p->canvas_w);
     set_num(env, e, "height", (double)p->canvas_h);
-    napi_set_named_property(env, e, "data", buf);
+    napi_set_named_property(env, e, j->want_png ? "png" : "data", buf);
     napi_set_named_property(env, e, "plan", plan_to_js(env, p));
     napi_set_element(env, arr, (uint32_t)k, e);
   }
@@ -516,20 +522,22 @@ static void batch_complete(napi_env env, napi_status status, void* data) {
   batch_free(env, j);
 }
 
-static napi_value js_stitch_batch(napi_env env, napi_callback_info info) {
+static napi_value batch_async(napi_env env, napi_callback_info info, int want_png) {
   batch_job* j = batch_parse(env, info, 1);
   if (!j) return NULL;
+  j->want_png = want_png;
   napi_value promise, name;
   CHECK(napi_create_promise(env, &j->deferred, &promise));
-  napi_create_string_utf8(env, "imagestitch.stitchBatch", NAPI_AUTO_LENGTH, &name);
+  napi_create_string_utf8(env, want_png ? "imagestitch.stitchPngBatch" : "imagestitch.stitchBatch", NAPI_AUTO_LENGTH, &name);
   CHECK(napi_create_async_work(env, NULL, name, batch_execute, batch_complete, j, &j->work));
   CHECK(napi_queue_async_work(env, j->work));
   return promise;
 }
 
-static napi_value js_stitch_batch_sync(napi_env env, napi_callback_info info) {
+static napi_value batch_sync(napi_env env, napi_callback_info info, int want_png) {
   batch_job* j = batch_parse(env, info, 0);
   if (!j) return NULL;
+  j->want_png = want_png;
   batch_execute(env, j);
   napi_value out = NULL;
   if (j->rc < 0) napi_throw(env, make_error(env, j->rc, j->err));
@@ -540,6 +548,12 @@ static napi_value js_stitch_batch_sync(napi_env env, napi_callback_info info) {
   batch_free(env, j);
   return out;
 }
+
+static napi_value js_stitch_batch(napi_env env, napi_callback_info info) { return batch_async(env, info, 0); }
+static napi_value js_stitch_batch_sync(napi_env env, napi_callback_info info) { return batch_sync(env, info, 0); }
+/* stitchPngBatch / stitchPngBatchSync: the same requests, a PNG file per request (the form setPngLevel chose) */
+static napi_value js_stitch_png_batch(napi_env env, napi_callback_info info) { return batch_async(env, info, 1); }
+static napi_value js_stitch_png_batch_sync(napi_env env, napi_callback_info info) { return batch_sync(env, info, 1); }
 
 static napi_value js_render(napi_env env, napi_callback_info info) {
   size_t argc = 8; napi_value argv[8];
@@ -726,6 +740,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"stitchSync", NULL, js_stitch_sync, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBatch", NULL, js_stitch_batch, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBatchSync", NULL, js_stitch_batch_sync, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchPngBatch", NULL, js_stitch_png_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchPngBatchSync", NULL, js_stitch_png_batch_sync, NULL, NULL, NULL, napi_default, NULL},
       {"stitchFiles", NULL, js_stitch_files, NULL, NULL, NULL, napi_default, NULL},
       {"render", NULL, js_render, NULL, NULL, NULL, napi_default, NULL},
       {"encodePng", NULL, js_encode_png, NULL, NULL, NULL, napi_default, NULL},

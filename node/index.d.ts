@@ -36,6 +36,8 @@ export function stitchBatch(requests: StitchRequest[]): Promise<(StitchResult | 
 export function stitchBatchSync(requests: StitchRequest[]): (StitchResult | null)[];
 export interface StitchPngResult { width: number; height: number; png: Buffer; plan: StitchPlan; }
 export function stitchPng(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchPngResult | null>;
+export function stitchPngBatch(requests: StitchRequest[]): Promise<(StitchPngResult | null)[]>;
+export function stitchPngBatchSync(requests: StitchRequest[]): (StitchPngResult | null)[];
 export function encodePng(data: Uint8Array, width: number, height: number, opts?: { pngLevel?: 0 | 1 }): Buffer;
 export function setPngLevel(level: 0 | 1): void;
 export function decodePng(file: Uint8Array): { width: number; height: number; data: Buffer };

@@ -7,6 +7,7 @@
  *
  *   stitch(images, direction, opts?) -> Promise<{width, height, data: Buffer, plan}>
  *   stitchBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, data, plan} | null)[]>   (one GPU, many stitches)
+ *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
@@ -114,6 +115,16 @@ function stitchBatch(requests) {
   return native.stitchBatch(a);
 }
 function stitchBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchBatchSync(a) : []; }
+/** stitchBatch with the reference's export: resolves one {width, height, png: Buffer, plan} per request - the PNG stitchPng gives
+ *  for it, in the form setPngLevel chose (a per-request pngLevel is refused) - and null for a request without images. The
+ *  canvases never leave the GPU; one compression launch encodes every file of a sub-batch. */
+function stitchPngBatch(requests) {
+  let a;
+  try { a = batchArgs(requests); } catch (e) { return Promise.reject(e); }
+  if (!a.length) return Promise.resolve([]);
+  return native.stitchPngBatch(a);
+}
+function stitchPngBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchPngBatchSync(a) : []; }
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
@@ -152,4 +163,4 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
