@@ -233,3 +233,55 @@ def test_destroying_a_job_does_not_wait_for_an_unrelated_stream():
     still_running = not done.query()
     side.synchronize()
     assert still_running and dt < 0.05, (still_running, dt)
+
+
+# one narrow image sets the width of a 'min' strip; under filter 'area' the others shrink 2.5x to 50x (tap_range's box branch)
+AREA_SIZES = [(64, 90), (3250, 4000), (2400, 1300), (160, 120), (1301, 2000)]
+AREA_ORI = [1, 1, 6, 3, 2]
+
+
+@pytest.mark.parametrize("split", ["band", "rows", "image"])
+def test_area_group_job_with_poisoned_partial_holdings(split):
+    """ist_group_job_launch under 'area' with strong shrinks: each part gets a buffer whose rows above sy0 and below sy1 are poison
+    and a view that starts at sy0, so a box row outside the part's holding changes the result instead of faulting.  Such a row
+    weighs at most 1 / 20 of a box here, which can stay within the oracle's 1 LSB, so the result must also equal, byte for byte,
+    the same job launched on whole images.  (Shrinks of 50.8x and 20.3x: box edges at band cuts are fractional.)"""
+    import torch
+    px = [U.rand_image(860 + i, h, w) for i, (w, h) in enumerate(AREA_SIZES)]
+    opts = {"filter": "area", "mode": "min", "gap": 2}
+    g = ist.StitchGroup([0] * 5)
+    job = g.compile(U.hip_images(px, AREA_ORI), "vertical", dict(opts, split=split))
+    assert {p["slot"] for p in job.parts} == set(range(5))
+    full = [torch.from_numpy(a).cuda() for a in px]
+    srcs, keep = [], []
+    pad = 8
+    for p in job.parts:
+        a, b = p["rows"]
+        t = full[p["image"]]
+        buf = torch.full((b - a + 2 * pad, t.shape[1], 4), 0xEE, dtype=torch.uint8, device="cuda")
+        buf[..., 1] = 0x11
+        buf[pad:pad + b - a] = t[a:b]
+        keep.append(buf)
+        srcs.append((buf[pad:pad + b - a], a))
+    out = torch.full((job.plan.canvas_h, job.plan.canvas_w, 4), 0x5A, dtype=torch.uint8, device="cuda")
+    job.launch(srcs, out)
+    whole = torch.full_like(out, 0x5A)
+    job.launch([full[p["image"]] for p in job.parts], whole)
+    g.sync()
+    assert torch.equal(out, whole)
+    ref, _, _ = U.oracle_stitch(px, "vertical", opts, orientations=AREA_ORI)
+    U.oracle_tolerance(out.cpu().numpy(), ref)
+    job.close()
+
+
+@pytest.mark.parametrize("devices,split", [([0, 0], "band"), ([0, 0, 0], "rows"), ([0] * 5, "image"), ([0] * 8, "auto")])
+@pytest.mark.parametrize("direction", ["vertical", "horizontal"])
+def test_area_on_a_device_list_matches_the_single_device_result(devices, split, direction):
+    sizes = AREA_SIZES if direction == "vertical" else [(h, w) for w, h in AREA_SIZES]
+    px = [U.rand_image(870 + i, h, w, opaque=(i != 2)) for i, (w, h) in enumerate(sizes)]
+    opts = {"filter": "area", "mode": "min", "gap": 3}
+    one = ist.stitch(U.hip_images(px, AREA_ORI), direction, opts)
+    many = ist.stitch(U.hip_images(px, AREA_ORI), direction, dict(opts, devices=devices, split=split))
+    assert np.array_equal(many["data"], one["data"])
+    ref, _, _ = U.oracle_stitch(px, direction, opts, orientations=AREA_ORI)
+    U.oracle_tolerance(many["data"], ref)

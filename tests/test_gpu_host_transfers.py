@@ -194,3 +194,26 @@ def test_page_locked_caller_memory_goes_up_without_staging():
         ref, _, _ = U.oracle_stitch(px, direction, {"filter": "nearest", "mode": "max"})
         got = ist.stitch(imgs, direction, {"filter": "nearest", "mode": "max"})
         assert np.array_equal(got["data"], ref), direction
+
+
+def test_area_duplex_bands_never_read_rows_left_in_the_scratch_by_an_earlier_call():
+    """the duplex path (canvas >= 32 MB) uploads only the rows each band's boxes touch (ist_shard_parts, tap_range) into device scratch
+    that the context reuses.  Poison images of the same shapes go through first, then the real ones under 'area' with strong
+    shrinks, quarter turns and a pitched source: a row a band reads before it is uploaded, or never uploads, is poison"""
+    from imagestitching_amd import _lib as L
+    sizes = [(3000, 1500), (6000, 1400), (12000, 1200), (48000, 300), (1000, 9000), (3000, 600)]     # 1x, 2x, 4x, 16x, 3x turned, 1x
+    ori = [1, 3, 2, 1, 6, 4]
+    px = [U.rand_image(340 + i, h, w, opaque=(i != 1)) for i, (w, h) in enumerate(sizes)]
+    opts = {"filter": "area", "mode": "min", "gap": 1}
+    for direction in ("vertical", "horizontal"):
+        poison = [np.full_like(a, 0xEE) for a in px]
+        before = L.lib.ist_debug_duplex_stitches()
+        ist.stitch(U.hip_images(poison, ori), direction, opts)
+        imgs = U.hip_images(px, ori)
+        wide = np.zeros((px[0].shape[0], px[0].shape[1] + 64, 4), np.uint8)
+        wide[:, :px[0].shape[1]] = px[0]
+        imgs[0]["data"] = wide[:, :px[0].shape[1]]
+        got = ist.stitch(imgs, direction, opts)["data"]
+        assert L.lib.ist_debug_duplex_stitches() - before == 2 and got.nbytes >= (32 << 20), (direction, got.shape)
+        ref, _, _ = U.oracle_stitch(px, direction, opts, orientations=ori, threads=16)
+        U.oracle_tolerance(got, ref)

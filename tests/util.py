@@ -74,3 +74,56 @@ def max_abs_diff(a, b):
 
 def mismatch_fraction(a, b):
     return float((a != b).any(axis=-1).mean()) if a.size else 0.0
+
+
+def oracle_tolerance(got, ref, exact=False):
+    """The op-list tolerance rule against the fp64 oracle: solid pixels within 1 LSB; a translucent pixel of a transparent canvas
+    reads back un-premultiplied (c * 255 / a), so one LSB of the premultiplied value may become up to 1 + ceil(255 / a) LSBs of its
+    colour; `exact` (nearest without edge AA) allows no difference at all.  Returns (differing, total, signed sum) over the channel
+    bytes of the solid pixels: the "rarely different" statistics."""
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    d = got.astype(np.int16) - ref.astype(np.int16)
+    if exact:
+        assert not d.any(), "max diff %d" % int(np.abs(d).max())
+        return 0, int((ref[..., 3] == 255).sum()) * 4, 0
+    a = np.abs(d)
+    assert int(a[..., 3].max(initial=0)) <= 1, "alpha off by %d" % int(a[..., 3].max())
+    solid = ref[..., 3] == 255
+    ds = d[solid]
+    assert int(np.abs(ds).max(initial=0)) <= 1, "solid pixel off by %d" % int(np.abs(ds).max())
+    soft = ~solid & (ref[..., 3] > 0)
+    if soft.any():
+        lim = 1 + np.ceil(255.0 / ref[..., 3][soft].astype(np.float64))
+        assert (a[..., :3][soft].max(axis=-1) <= lim).all(), "translucent readback beyond 1 + ceil(255 / a)"
+    return int((ds != 0).sum()), int(ds.size), int(ds.sum())
+
+
+class RareDiff:
+    """accumulates oracle_tolerance's statistics over many cases and checks that differences are rare and unbiased"""
+
+    def __init__(self):
+        self.diff = self.total = self.signed = 0
+
+    def add(self, stats):
+        self.diff += stats[0]
+        self.total += stats[1]
+        self.signed += stats[2]
+
+    @property
+    def fraction(self):
+        return self.diff / max(1, self.total)
+
+    @property
+    def mean(self):
+        return self.signed / max(1, self.total)
+
+    def check(self, fraction=0.01, mean=0.001):
+        """fewer than `fraction` of the bytes differ, and their signed sum stays within `mean` LSB per byte plus three standard
+        deviations of a sum of that many unbiased +-1 differences (a systematic error - a weight dropped or counted twice - is
+        one-sided)"""
+        assert self.total > 0
+        assert self.fraction < fraction, "%.5f of the solid channel bytes differ from the oracle" % self.fraction
+        assert abs(self.signed) <= mean * self.total + 3.0 * self.diff ** 0.5, "mean signed difference %.6f LSB (%r)" % (self.mean, self)
+
+    def __repr__(self):
+        return "%d of %d solid channel bytes differ (%.2e), mean signed difference %+.2e LSB" % (self.diff, self.total, self.fraction, self.mean)
