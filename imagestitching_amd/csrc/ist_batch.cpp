@@ -401,14 +401,10 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
   for (size_t k = 0; k < n; ++k) {
     const ist_stitch_request& r = reqs[k];
     if (r.n_images <= 0) continue;                        // index.js:1189: nothing to do for this entry
-    ist_limits lim;
-    if (r.limits) lim = *r.limits; else ist_limits_unlimited(&lim);
-    int rc = ist_plan_compute(r.images, r.n_images, r.direction, r.mode, r.gap, &lim, &out_plans[k]);
+    const int rc = plan_with_ops(r.images, r.n_images, r.direction, r.mode, r.gap, r.limits, &out_plans[k], &ops[k]);
     if (rc == IST_NOTHING_TO_DO) { std::memset(&out_plans[k], 0, sizeof(ist_plan)); continue; }
     if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
-    ops[k].resize(static_cast<size_t>(out_plans[k].n_rects) + 1);
-    rc = ist_plan_ops(&out_plans[k], r.images, r.n_images, ops[k].data(), &n_ops[k]);
-    if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
+    n_ops[k] = static_cast<int>(ops[k].size());
     bytes[k] = static_cast<size_t>(out_plans[k].canvas_w) * 4 * static_cast<size_t>(out_plans[k].canvas_h);
     for (int i = 0; i < r.n_images; ++i) bytes[k] += image_bytes(r.images[i]);
     if (out_len) {                                        // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
@@ -433,7 +429,7 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
     if (live) { idx.push_back(static_cast<int>(k)); held += bytes[k]; }
   }
   rc = pipe.finish(rc);
-  if (rc) { const std::string why = g_last_error; const int code = g_last_code; release(); g_last_error = why; g_last_code = code; return rc; }
+  if (rc) { KeepLastError keep; release(); return rc; }
   pipe.apply_patches();
   return IST_OK;
 }

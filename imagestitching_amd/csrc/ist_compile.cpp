@@ -645,23 +645,13 @@ std::unique_ptr<FlatTwin> compile_flat_twin(int64_t canvas_w, int64_t canvas_h, 
   // form; strips under ~64 MB run at the launch floor either way.  A large strip of small images keeps the row form.
   if (total >= (64ll << 20) && total / std::max<int64_t>(1, static_cast<int64_t>(vimg.size())) < (8ll << 20)) return nullptr;
   const int64_t vh = (total + P - 1) / P;
-  if (total % P) {                                    // the wide canvas's last row ends past the region: never written
-    ist_op h;
-    std::memset(&h, 0, sizeof(h));
-    h.kind = IST_OP_HOLE; h.image = -1;
-    h.m[0] = h.m[3] = 1.0;
-    h.d[0] = static_cast<double>((total % P) / 4); h.d[1] = static_cast<double>(vh - 1); h.d[2] = static_cast<double>(vw - (total % P) / 4); h.d[3] = 1.0;
-    vops.push_back(h);
-  }
-  const std::string keep_msg = g_last_error;
-  const int keep_code = g_last_code;
+  if (total % P) vops.push_back(hole_op((total % P) / 4, vh - 1, vw - (total % P) / 4, 1));    // the wide canvas's last row ends past the region: never written
+  KeepLastError keep;                                 // the twin is an optimisation: its failure is nobody's error
   ist_image_desc none;
   std::memset(&none, 0, sizeof(none));
   if (compile_ops(vw, vh, clear_rgba, vops.data(), static_cast<int>(vops.size()), vimg.empty() ? &none : vimg.data(), static_cast<int>(vimg.size()),
-                  filter, nullptr, &t->host) != IST_OK || t->host.kernel_kind != 0) {
-    g_last_error = keep_msg; g_last_code = keep_code;             // the twin is an optimisation: its failure is nobody's error
+                  filter, nullptr, &t->host) != IST_OK || t->host.kernel_kind != 0)
     return nullptr;
-  }
   return t;
 }
 

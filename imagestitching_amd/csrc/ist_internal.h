@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -139,6 +140,28 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
 
 // resolve one op (exposed for tests): returns 0 ok, 1 nothing drawn, <0 error
 int resolve_op(const ist_op& op, int64_t canvas_w, int64_t canvas_h, int img_w, int img_h, DevOp* out, bool edge_aa = false);
+
+// ---- what is built from a cut (ist_shard.cpp, pure CPU): every entry point that cuts a stitch builds its sub-jobs from these;
+// imagestitching_amd/dist.py states the same rules (tests/test_shard_ops.py holds the two together)
+struct RowSpan { int64_t y0, y1; };     // rows [y0, y1)
+ist_op hole_op(int64_t x, int64_t y, int64_t w, int64_t h);      // the launch writes nothing in canvas box (x, y, w, h)
+// every op that is not a draw, plus the draws that some part of `parts` belongs to, in canvas order (a by-rows band's list)
+std::vector<ist_op> shard_band_ops(const ist_op* ops, int n_ops, const std::vector<ist_part>& parts);
+// shard_band_ops(own), then a HOLE over every box of `holes` (delivered by someone else; listed last: nothing lies on top)
+std::vector<ist_op> shard_root_ops(const ist_op* ops, int n_ops, const std::vector<ist_part>& own, const std::vector<ist_region>& holes);
+// one per-draw part: the first fill of the list when it precedes the draw (index.js:1423-1424), then the draw
+std::vector<ist_op> shard_part_ops(const ist_op* ops, int n_ops, const ist_part& part);
+std::vector<ist_part> parts_of_slot(const std::vector<ist_part>& parts, int slot);
+std::map<int, RowSpan> shard_holdings(const std::vector<ist_part>& parts);     // per image: the union of the parts' [sy0, sy1)
+std::vector<RowSpan> uncovered_rows(const std::vector<ist_region>& boxes, int64_t canvas_h);   // rows of [0, canvas_h) no box covers
+
+// ist_plan_compute (limits NULL: unlimited), then the plan's op list; the plan is freed again when the op list fails
+int plan_with_ops(const ist_image_desc* images, int n_images, int direction, int mode, double gap, const ist_limits* limits, ist_plan* plan,
+                  std::vector<ist_op>* ops);
+struct JobDelete { void operator()(ist_job* j) const { ist_job_destroy(j); } };
+using JobPtr = std::unique_ptr<ist_job, JobDelete>;      // a sub-job owned by its caller
+// around a failure the caller tolerates: the thread's g_last_error / g_last_code are what they were before, once it goes out of scope
+struct KeepLastError { std::string msg = g_last_error; int code = g_last_code; ~KeepLastError() { g_last_error = msg; g_last_code = code; } };
 
 // PNG export, compressing form (ist_png_deflate.hip); ist_png_encode_device picks it when the context's level is > 0
 int64_t png_deflate_bound(int64_t w, int64_t h);

@@ -136,31 +136,21 @@ struct ist_group_job {
     bool in_place = false;                // full canvas width: a contiguous byte range of the canvas
     bool local = false;                   // device sink: rendered on the root's device straight into the canvas
     std::vector<size_t> part_idx;         // the parts whose source pointers the unit's job reads
-    ist_job* band_job = nullptr;
+    JobPtr band_job;
     size_t band_off = 0;                  // compact band in the owner's arena
-    ist_job* place_job = nullptr;         // root: staged band -> canvas
+    JobPtr place_job;                     // root: staged band -> canvas
     size_t staging_off = 0;               // root arena (units that are not full-width)
   };
   std::vector<Unit> units;
   int split = IST_SPLIT_IMAGE;            // the effective cut (AUTO resolved)
-  ist_job* root_job = nullptr;
+  JobPtr root_job;
   std::vector<size_t> band_need;          // per device: bytes of band arena this job addresses
   size_t staging_need = 0;
   bool host_sink_ok = false;              // every band is full-width: bands can be DMA'ed straight into a host canvas
-  std::vector<std::pair<int64_t, int64_t>> root_rows;   // host sink: canvas row ranges the root's launch delivers
+  std::vector<RowSpan> root_rows;         // host sink: canvas row ranges the root's launch delivers
 };
 
 namespace {
-
-void group_job_free(ist_group_job* j) {
-  if (!j) return;
-  for (auto& u : j->units) {
-    if (u.band_job) ist_job_destroy(u.band_job);
-    if (u.place_job) ist_job_destroy(u.place_job);
-  }
-  if (j->root_job) ist_job_destroy(j->root_job);
-  delete j;
-}
 
 inline size_t unit_bytes(const ist_group_job::Unit& u) { return static_cast<size_t>(u.X1 - u.X0) * 4 * static_cast<size_t>(u.Y1 - u.Y0); }
 inline size_t round256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
@@ -235,7 +225,7 @@ ist_group* ist_group_create(const int* devices, int ndev) {
 void ist_group_destroy(ist_group* g) {
   if (!g) return;
   (void)group_sync_locked(g);
-  for (auto& c : g->cache) group_job_free(c.job);
+  for (auto& c : g->cache) delete c.job;
   g->cache.clear();
   for (ncclComm_t c : g->comm) if (c) (void)rccl()->CommDestroy(c);
   for (size_t r = 0; r < g->devs.size(); ++r) if (g->band_arena[r]) { DeviceGuard dg(g->devs[r]); dev_free(g->band_arena[r]); }
@@ -265,12 +255,13 @@ ist_group_job* ist_group_job_create(ist_group* g, int64_t canvas_w, int64_t canv
   int n_parts = 0;
   if (ist_shard_parts(ops, n_ops, canvas_w, canvas_h, images, n_images, filter, n_slots, split, cut.data(), static_cast<int>(cut.size()), &n_parts) != IST_OK)
     return nullptr;
-  std::unique_ptr<ist_group_job, void (*)(ist_group_job*)> job(new ist_group_job, group_job_free);
+  cut.resize(static_cast<size_t>(n_parts));
+  std::unique_ptr<ist_group_job> job(new ist_group_job);
   job->g = g; job->cw = canvas_w; job->ch = canvas_h; job->n_images = n_images; job->split = split;
   job->band_need.assign(g->devs.size(), 0);
   static const uint8_t transparent[4] = {0, 0, 0, 0};
   const uint8_t* clear = clear_rgba ? clear_rgba : transparent;
-  for (int k = 0; k < n_parts; ++k) {
+  for (size_t k = 0; k < cut.size(); ++k) {
     ist_group_job::PartRt rt;
     rt.part = cut[k];
     rt.rank = g->slot_rank[static_cast<size_t>(cut[k].slot)];
@@ -283,7 +274,7 @@ ist_group_job* ist_group_job_create(ist_group* g, int64_t canvas_w, int64_t canv
     u.X0 = X0; u.Y0 = Y0; u.X1 = X1; u.Y1 = Y1;
     u.in_place = X0 == 0 && static_cast<int64_t>(X1) == canvas_w;
     u.local = u.rank == 0 && !g->self_send;
-    job->units.push_back(u);
+    job->units.push_back(std::move(u));
     return job->units.back();
   };
   if (by_rows) {
@@ -301,57 +292,25 @@ ist_group_job* ist_group_job_create(ist_group* g, int64_t canvas_w, int64_t canv
       new_unit(p.slot, p.X0, p.Y0, p.X1, p.Y1).part_idx.push_back(k);
     }
   }
-  // the root's own launch: every op that is not a sharded draw (fills), the draws slot 0 owns a part of, and - listed
-  // last, so that nothing lies on top of them - a HOLE over every unit someone else writes
-  std::vector<ist_op> root_ops;
-  std::vector<char> root_draw(static_cast<size_t>(n_ops), 0);
-  for (int k = 0; k < n_parts; ++k) if (cut[k].slot == 0) root_draw[static_cast<size_t>(cut[k].op)] = 1;
-  for (int k = 0; k < n_ops; ++k)
-    if (ops[k].kind != IST_OP_DRAW || root_draw[static_cast<size_t>(k)]) root_ops.push_back(ops[k]);
-  // (a draw that shards into nothing draws nothing: dropping it changes no pixel)
+  // the root's own launch: the draws slot 0 owns a part of, and a HOLE over every unit someone else writes
   job->host_sink_ok = true;
+  std::vector<ist_region> boxes;
   for (auto& u : job->units) {
     if (!u.in_place) job->host_sink_ok = false;
     u.band_off = job->band_need[static_cast<size_t>(u.rank)];
     job->band_need[static_cast<size_t>(u.rank)] += round256(unit_bytes(u));
-    ist_op hole;
-    std::memset(&hole, 0, sizeof hole);
-    hole.kind = IST_OP_HOLE; hole.image = -1;
-    hole.m[0] = 1.0; hole.m[3] = 1.0;
-    hole.d[0] = u.X0; hole.d[1] = u.Y0; hole.d[2] = u.X1 - u.X0; hole.d[3] = u.Y1 - u.Y0;
-    root_ops.push_back(hole);
+    boxes.push_back(ist_region{u.X0, u.Y0, u.X1 - u.X0, u.Y1 - u.Y0});
   }
-  job->root_job = ist_job_create(g->ctx[0], canvas_w, canvas_h, clear, root_ops.data(), static_cast<int>(root_ops.size()), images, n_images, filter, nullptr);
+  const std::vector<ist_op> root_ops = shard_root_ops(ops, n_ops, parts_of_slot(cut, 0), boxes);
+  job->root_job.reset(ist_job_create(g->ctx[0], canvas_w, canvas_h, clear, root_ops.data(), static_cast<int>(root_ops.size()), images, n_images, filter, nullptr));
   if (!job->root_job) return nullptr;
-  // host sink: the canvas rows that no unit delivers come from the root's launch (the complement of the units' rows)
-  if (job->host_sink_ok) {
-    std::vector<std::pair<int64_t, int64_t>> holes;
-    for (const auto& u : job->units) holes.emplace_back(u.Y0, u.Y1);
-    std::sort(holes.begin(), holes.end());
-    int64_t y = 0;
-    for (const auto& h : holes) {
-      if (h.first > y) job->root_rows.emplace_back(y, h.first);
-      y = std::max(y, h.second);
-    }
-    if (y < canvas_h) job->root_rows.emplace_back(y, canvas_h);
-  }
-  // the first fill of the list paints the background of every per-draw band (index.js:1423-1424)
-  int fill_at = -1;
-  for (int k = 0; k < n_ops && fill_at < 0; ++k) if (ops[k].kind == IST_OP_FILL) fill_at = k;
-  std::vector<ist_op> band_ops;
-  for (auto& u : job->units) {
-    band_ops.clear();
-    if (by_rows) {                       // the whole op list, minus the draws that do not reach these rows, in canvas order
-      std::vector<char> mine(static_cast<size_t>(n_ops), 0);
-      for (size_t k : u.part_idx) mine[static_cast<size_t>(job->parts[k].part.op)] = 1;
-      for (int k = 0; k < n_ops; ++k) if (ops[k].kind != IST_OP_DRAW || mine[static_cast<size_t>(k)]) band_ops.push_back(ops[k]);
-    } else {
-      const ist_part& p = job->parts[u.part_idx[0]].part;
-      if (fill_at >= 0 && fill_at < p.op) band_ops.push_back(ops[fill_at]);
-      band_ops.push_back(ops[p.op]);
-    }
-    const ist_region clip{u.X0, u.Y0, u.X1 - u.X0, u.Y1 - u.Y0};
-    u.band_job = ist_job_create(g->ctx[static_cast<size_t>(u.rank)], canvas_w, canvas_h, clear, band_ops.data(), static_cast<int>(band_ops.size()), images, n_images, filter, &clip);
+  // host sink: the canvas rows that no unit delivers come from the root's launch
+  if (job->host_sink_ok) job->root_rows = uncovered_rows(boxes, canvas_h);
+  for (size_t k = 0; k < job->units.size(); ++k) {
+    auto& u = job->units[k];
+    const std::vector<ist_op> band_ops = by_rows ? shard_band_ops(ops, n_ops, parts_of_slot(cut, u.slot))
+                                                 : shard_part_ops(ops, n_ops, job->parts[u.part_idx[0]].part);
+    u.band_job.reset(ist_job_create(g->ctx[static_cast<size_t>(u.rank)], canvas_w, canvas_h, clear, band_ops.data(), static_cast<int>(band_ops.size()), images, n_images, filter, &boxes[k]));
     if (!u.band_job) return nullptr;
     if (u.local || u.in_place) continue;
     // staged: received into a compact band on the root, then placed by a 1:1 draw clipped to the box
@@ -366,13 +325,13 @@ ist_group_job* ist_group_job_create(ist_group* g, int64_t canvas_w, int64_t canv
     ist_image_desc band_desc;
     std::memset(&band_desc, 0, sizeof band_desc);
     band_desc.width = u.X1 - u.X0; band_desc.height = u.Y1 - u.Y0; band_desc.orientation = 1; band_desc.opaque = 1;
-    u.place_job = ist_job_create(g->ctx[0], canvas_w, canvas_h, clear, &put, 1, &band_desc, 1, IST_FILTER_NEAREST, &clip);
+    u.place_job.reset(ist_job_create(g->ctx[0], canvas_w, canvas_h, clear, &put, 1, &band_desc, 1, IST_FILTER_NEAREST, &boxes[k]));
     if (!u.place_job) return nullptr;
   }
   return job.release();
 }
 
-void ist_group_job_destroy(ist_group_job* job) { group_job_free(job); }
+void ist_group_job_destroy(ist_group_job* job) { delete job; }
 
 int ist_group_job_parts(const ist_group_job* job, ist_part* parts, int max_parts, int* n_parts) {
   if (!job || !n_parts) return fail(IST_E_INVALID, "ist_group_job_parts: NULL argument");
@@ -401,7 +360,7 @@ int launch_band(ist_group_job* job, size_t ui, const void* const* src, const siz
   }
   void* dst = to;
   if (compact) dst = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(to) - (static_cast<uintptr_t>(u.Y0) * to_pitch + static_cast<uintptr_t>(u.X0) * 4));
-  return ist_job_launch(u.band_job, one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, to_pitch,
+  return ist_job_launch(u.band_job.get(), one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, to_pitch,
                         job->g->ctx[static_cast<size_t>(u.rank)]->stream);
 }
 
@@ -416,7 +375,7 @@ int launch_root(ist_group_job* job, const void* const* src, const size_t* src_pi
     one[static_cast<size_t>(p.image)] = src[k];
     one_pitch[static_cast<size_t>(p.image)] = src_pitch ? src_pitch[k] : 0;
   }
-  return ist_job_launch(job->root_job, one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, dst_pitch, job->g->ctx[0]->stream);
+  return ist_job_launch(job->root_job.get(), one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, dst_pitch, job->g->ctx[0]->stream);
 }
 
 // the communicators of the group (one per distinct device), on first need.  Caller holds g->mu.
@@ -474,7 +433,7 @@ int group_launch_locked(ist_group_job* job, const void* const* src, const size_t
     if (!u.place_job) continue;
     const void* band = static_cast<const uint8_t*>(g->staging) + u.staging_off;
     const size_t bp = static_cast<size_t>(u.X1 - u.X0) * 4;
-    rc = ist_job_launch(u.place_job, &band, &bp, 1, dst, dst_pitch, g->recv_stream);
+    rc = ist_job_launch(u.place_job.get(), &band, &bp, 1, dst, dst_pitch, g->recv_stream);
     if (rc) return rc;
   }
   return IST_OK;
@@ -526,15 +485,11 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   if (!g) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!out_plan || !out_pixels) return fail(IST_E_INVALID, "ist_group_stitch_rgba8: NULL output");
   *out_pixels = nullptr;
-  ist_limits lim;
-  if (limits) lim = *limits; else ist_limits_unlimited(&lim);
-  int rc = ist_plan_compute(images, n_images, direction, mode, gap, &lim, out_plan);
+  std::vector<ist_op> ops;
+  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
   struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist_plan_free(p); } } pg{out_plan};
-  std::vector<ist_op> ops(static_cast<size_t>(out_plan->n_rects) + 1);
-  int n_ops = 0;
-  rc = ist_plan_ops(out_plan, images, n_images, ops.data(), &n_ops);
-  if (rc != IST_OK) return rc;
+  const int n_ops = static_cast<int>(ops.size());
   static const uint8_t transparent[4] = {0, 0, 0, 0};
   std::lock_guard<std::mutex> glock(g->mu);            // one host-path stitch in flight per group (index.js:772 isStitching)
   // the compiled group job: from the LRU, or compiled now and kept
@@ -553,7 +508,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
       job = ist_group_job_create(g, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, images, n_images, filter, split);
       if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
       if (g->cache.size() >= ist_group::kCacheJobs) {    // every call ends with the group idle: the oldest job is not in flight
-        group_job_free(g->cache.front().job);
+        delete g->cache.front().job;
         g->cache.erase(g->cache.begin());
       }
       g->cache.push_back(ist_group::Cached{key, job});
@@ -564,14 +519,13 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
 
   // holdings: per (device, image) the union of the rows its parts sample, + 16 readable bytes behind the last row
   const size_t nd = g->devs.size();
-  struct Hold { int lo = 0, hi = 0; size_t off = 0; };
-  std::vector<std::map<int, Hold>> hold(nd);
+  std::vector<std::vector<ist_part>> mine(nd);
   for (const auto& rt : job->parts) {
     if (!src || !src[rt.part.image]) return fail(IST_E_DECODE, "图片" + std::to_string(rt.part.image) + "解码异常");
-    auto it = hold[static_cast<size_t>(rt.rank)].find(rt.part.image);
-    if (it == hold[static_cast<size_t>(rt.rank)].end()) { Hold h; h.lo = rt.part.sy0; h.hi = rt.part.sy1; hold[static_cast<size_t>(rt.rank)][rt.part.image] = h; }
-    else { it->second.lo = std::min(it->second.lo, rt.part.sy0); it->second.hi = std::max(it->second.hi, rt.part.sy1); }
+    mine[static_cast<size_t>(rt.rank)].push_back(rt.part);
   }
+  struct Hold { RowSpan rows; size_t off; };
+  std::vector<std::map<int, Hold>> hold(nd);
   auto width_of = [&](int i) { return static_cast<size_t>(images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width); };
   const size_t canvas_pitch = static_cast<size_t>(out_plan->canvas_w) * 4;
   const size_t canvas_bytes = canvas_pitch * static_cast<size_t>(out_plan->canvas_h);
@@ -588,7 +542,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   // part pointers: row 0 of the image as seen from the holding (offsets are known before the uploads run)
   for (size_t r = 0; r < nd; ++r) {
     size_t total = 0;
-    for (auto& kv : hold[r]) { kv.second.off = total; total += round256(width_of(kv.first) * 4 * static_cast<size_t>(kv.second.hi - kv.second.lo) + 16); }
+    for (const auto& kv : shard_holdings(mine[r])) { hold[r][kv.first] = Hold{kv.second, total}; total += round256(width_of(kv.first) * 4 * static_cast<size_t>(kv.second.y1 - kv.second.y0) + 16); }
     DeviceGuard dg(g->devs[r]);
     rc = grow_device(&g->ctx[r]->scratch_src, &g->ctx[r]->scratch_src_bytes, total ? total : 256);
     if (rc) return rc;
@@ -599,7 +553,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
     const auto& rt = job->parts[k];
     const Hold& h = hold[static_cast<size_t>(rt.rank)][rt.part.image];
     const size_t row = width_of(rt.part.image) * 4;
-    psrc[k] = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(g->ctx[static_cast<size_t>(rt.rank)]->scratch_src) + h.off - static_cast<uintptr_t>(h.lo) * row);
+    psrc[k] = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(g->ctx[static_cast<size_t>(rt.rank)]->scratch_src) + h.off - static_cast<uintptr_t>(h.rows.y0) * row);
     ppitch[k] = row;
   }
   // one host thread per device: upload its rows, then (host sink) render its bands and send each home over its own link
@@ -617,8 +571,8 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
       for (auto& kv : hold[r]) {
         const size_t row = width_of(kv.first) * 4, hp = src_pitch ? src_pitch[kv.first] : row;
         if (hp < row) { rc2 = fail(IST_E_INVALID, "src_pitch too small"); break; }
-        up.push_back(RowsCopy{static_cast<uint8_t*>(c->scratch_src) + kv.second.off, src[kv.first] + static_cast<size_t>(kv.second.lo) * hp, nullptr, hp, row,
-                              static_cast<size_t>(kv.second.hi - kv.second.lo)});
+        up.push_back(RowsCopy{static_cast<uint8_t*>(c->scratch_src) + kv.second.off, src[kv.first] + static_cast<size_t>(kv.second.rows.y0) * hp, nullptr, hp, row,
+                              static_cast<size_t>(kv.second.rows.y1 - kv.second.rows.y0)});
       }
       if (rc2 == IST_OK) { if (!c->stager) c->stager.reset(new Stager(c->device)); rc2 = c->stager->upload(up, c->stream); }
       if (rc2 == IST_OK && host_sink) {
@@ -635,7 +589,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
         if (rc2 == IST_OK && r == 0) {                 // the root: everything that is not a band
           rc2 = launch_root(job, psrc.data(), ppitch.data(), root->scratch_dst, canvas_pitch);
           for (size_t q = 0; q < job->root_rows.size() && rc2 == IST_OK; ++q) {
-            const size_t y0 = static_cast<size_t>(job->root_rows[q].first), y1 = static_cast<size_t>(job->root_rows[q].second);
+            const size_t y0 = static_cast<size_t>(job->root_rows[q].y0), y1 = static_cast<size_t>(job->root_rows[q].y1);
             if (hipMemcpyAsync(host + y0 * canvas_pitch, static_cast<uint8_t*>(root->scratch_dst) + y0 * canvas_pitch, (y1 - y0) * canvas_pitch, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
               (void)hipGetLastError();
               rc2 = fail(IST_E_HIP, "result readback failed");

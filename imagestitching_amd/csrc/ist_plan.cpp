@@ -271,3 +271,17 @@ int ist_plan_ops(const ist_plan* plan, const ist_image_desc* images, int n_image
 }
 
 }  // extern "C"
+
+int ist::plan_with_ops(const ist_image_desc* images, int n_images, int direction, int mode, double gap, const ist_limits* limits,
+                       ist_plan* plan, std::vector<ist_op>* ops) {
+  ist_limits lim;
+  if (limits) lim = *limits; else ist_limits_unlimited(&lim);
+  int rc = ist_plan_compute(images, n_images, direction, mode, gap, &lim, plan);
+  if (rc != IST_OK) return rc;
+  ops->resize(static_cast<size_t>(plan->n_rects) + 1);
+  int n_ops = 0;
+  rc = ist_plan_ops(plan, images, n_images, ops->data(), &n_ops);
+  if (rc != IST_OK) { ist_plan_free(plan); return rc; }
+  ops->resize(static_cast<size_t>(n_ops));
+  return IST_OK;
+}

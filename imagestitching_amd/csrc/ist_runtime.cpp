@@ -63,6 +63,8 @@ int grow_device(void** p, size_t* have, size_t need) {
 
 namespace {
 
+const uint8_t kTransparent[4] = {0, 0, 0, 0};     // the clear colour of a new canvas
+
 Stager& stager_of(ist_ctx* ctx) {
   if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device));
   return *ctx->stager;
@@ -82,15 +84,21 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
   return IST_OK;
 }
 
-// the context's second stream (high priority: its small kernels should not queue behind thousands of workgroups of the first)
-int ensure_aux(ist_ctx* ctx) {
-  if (ctx->aux) return IST_OK;
+// a stream of the context, made on first need at the highest priority (`lowest`: the lowest)
+int ensure_stream(hipStream_t* s, bool lowest = false) {
+  if (*s) return IST_OK;
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  if (tuning_mode() && std::getenv("IST_AUX_PRIORITY")) hi = std::atoi(std::getenv("IST_AUX_PRIORITY")) ? hi : lo;     // A/B knob: 0 = lowest
-  if (hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, hi) != hipSuccess) { (void)hipGetLastError(); ctx->aux = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
+  if (hipStreamCreateWithPriority(s, hipStreamNonBlocking, lowest ? lo : hi) != hipSuccess) { (void)hipGetLastError(); *s = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
   return IST_OK;
 }
+// the context's second stream (high priority: its small kernels should not queue behind thousands of workgroups of the first)
+int ensure_aux(ist_ctx* ctx) {
+  static const bool lowest = tuning_mode() && std::getenv("IST_AUX_PRIORITY") && !std::atoi(std::getenv("IST_AUX_PRIORITY"));     // A/B knob: 0 = lowest
+  return ensure_stream(&ctx->aux, lowest);
+}
+// the render stream (high priority: its short kernels should not queue behind the PNG encoder's thousands of workgroups)
+int ensure_render(ist_ctx* ctx) { return ensure_stream(&ctx->render); }
 
 // The PNG file of a canvas in device memory -> a pooled pinned block (freed with ist_free).  `dfile` = device scratch of
 // at least ist_png_bound bytes (nullptr: the context's own).  The compressing encoder hands the file over slab by slab
@@ -227,14 +235,13 @@ ist_job* job_compile(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uin
                      const ist_image_desc* images, int n_images, int filter, const ist_region* clip) {
   if (!ctx) { fail(IST_E_NO_CONTEXT, "无法获取绘图上下文"); return nullptr; }
   if (n_images > kMaxImages) { fail(IST_E_UNSUPPORTED, "more than 128 images in one launch"); return nullptr; }
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   std::unique_ptr<ist_job> job(new ist_job);
   job->ctx = ctx;
-  if (compile_ops(canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, n_images, filter,
+  if (compile_ops(canvas_w, canvas_h, clear_rgba ? clear_rgba : kTransparent, ops, n_ops, images, n_images, filter,
                   clip, &job->host) != IST_OK)
     return nullptr;
   for (const DevOp& o : job->host.ops) job->max_image = std::max(job->max_image, o.image);
-  job->flat = compile_flat_twin(canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, n_images, filter, job->host);
+  job->flat = compile_flat_twin(canvas_w, canvas_h, clear_rgba ? clear_rgba : kTransparent, ops, n_ops, images, n_images, filter, job->host);
   return job.release();
 }
 
@@ -435,9 +442,8 @@ static int render_to_scratch(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, c
                              const ist_op* ops, int n_ops, const ist_image_desc* images, const uint8_t* const* src,
                              const size_t* src_pitch, int n_images, int filter, const ist_region* region,
                              int64_t* out_w, int64_t* out_h) {
-  ist_job* job = ist_job_create(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, n_images, filter, region);
+  const JobPtr job(ist_job_create(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, n_images, filter, region));
   if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
-  struct JobFree { ist_job* j; ~JobFree() { ist_job_destroy(j); } } jf{job};
 
   // stage the sources that the job actually samples
   std::vector<size_t> off(static_cast<size_t>(n_images), 0);
@@ -471,9 +477,9 @@ static int render_to_scratch(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, c
   rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc) return rc;
   const uintptr_t biased = reinterpret_cast<uintptr_t>(ctx->scratch_dst) - (static_cast<uintptr_t>(job->host.ry0) * pitch + static_cast<uintptr_t>(job->host.rx0) * 4);
-  rc = ist_job_launch(job, dsrc.data(), dpitch.data(), n_images, reinterpret_cast<void*>(biased), pitch, ctx->stream);
+  rc = ist_job_launch(job.get(), dsrc.data(), dpitch.data(), n_images, reinterpret_cast<void*>(biased), pitch, ctx->stream);
   if (rc) return rc;
-  // the job's device tables are freed when `jf` goes out of scope: the launch must have consumed them
+  // the job's device tables are freed when `job` goes out of scope: the launch must have consumed them
   IST_HIP(hipStreamSynchronize(ctx->stream));
   if (out_w) *out_w = rw;
   if (out_h) *out_h = rh;
@@ -530,17 +536,11 @@ int ist_stitch_png(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* co
                    ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_png: NULL output");
-  ist_limits lim;
-  if (limits) lim = *limits; else ist_limits_unlimited(&lim);
-  int rc = ist_plan_compute(images, n_images, direction, mode, gap, &lim, out_plan);
+  std::vector<ist_op> ops;
+  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
-  std::vector<ist_op> ops(static_cast<size_t>(out_plan->n_rects) + 1);
-  int n_ops = 0;
-  rc = ist_plan_ops(out_plan, images, n_images, ops.data(), &n_ops);
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
-  if (rc == IST_OK)
-    rc = ist_render_png(ctx, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, images, src, src_pitch,
-                        n_images, filter, out_png, out_len);
+  rc = ist_render_png(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
+                      n_images, filter, out_png, out_len);
   if (rc != IST_OK) ist_plan_free(out_plan);
   return rc;
 }
@@ -966,10 +966,9 @@ class FileDecoder {
 // (or there is nothing to cut): the caller then renders the canvas with ONE launch once every image is there.
 struct BandedJobs {
   bool ok = false;
-  ist_job* bg = nullptr;
-  std::vector<ist_job*> band;            // per part
+  std::vector<JobPtr> band;              // per part
+  JobPtr bg;                             // (released before the bands)
   std::vector<ist_part> parts;           // sorted by Y0
-  ~BandedJobs() { if (bg) ist_job_destroy(bg); for (ist_job* j : band) if (j) ist_job_destroy(j); }
 };
 
 int compile_banded(ist_ctx* ctx, int64_t cw, int64_t ch, const uint8_t clear[4], const ist_op* ops, int n_ops, const ist_image_desc* images,
@@ -983,26 +982,15 @@ int compile_banded(ist_ctx* ctx, int64_t cw, int64_t ch, const uint8_t clear[4],
   if (n_parts > n_images) return IST_OK;
   cut.resize(static_cast<size_t>(n_parts));
   std::stable_sort(cut.begin(), cut.end(), [](const ist_part& a, const ist_part& b) { return a.Y0 < b.Y0; });
-  std::vector<ist_op> bg_ops;
-  int fill_at = -1;
-  for (int k = 0; k < n_ops; ++k) { if (ops[k].kind != IST_OP_DRAW) bg_ops.push_back(ops[k]); if (fill_at < 0 && ops[k].kind == IST_OP_FILL) fill_at = k; }
-  for (const ist_part& p : cut) {
-    ist_op hole;
-    std::memset(&hole, 0, sizeof hole);
-    hole.kind = IST_OP_HOLE; hole.image = -1; hole.m[0] = 1.0; hole.m[3] = 1.0;
-    hole.d[0] = p.X0; hole.d[1] = p.Y0; hole.d[2] = p.X1 - p.X0; hole.d[3] = p.Y1 - p.Y0;
-    bg_ops.push_back(hole);
-  }
-  out->bg = ist_job_create(ctx, cw, ch, clear, bg_ops.data(), static_cast<int>(bg_ops.size()), images, n_images, filter, nullptr);
+  std::vector<ist_region> boxes;
+  for (const ist_part& p : cut) boxes.push_back(ist_region{p.X0, p.Y0, p.X1 - p.X0, p.Y1 - p.Y0});
+  const std::vector<ist_op> bg = shard_root_ops(ops, n_ops, {}, boxes);
+  out->bg.reset(ist_job_create(ctx, cw, ch, clear, bg.data(), static_cast<int>(bg.size()), images, n_images, filter, nullptr));
   if (!out->bg) return g_last_code ? g_last_code : IST_E_INVALID;
-  for (const ist_part& p : cut) {
-    ist_op two[2]; int n2 = 0;
-    if (fill_at >= 0 && fill_at < p.op) two[n2++] = ops[fill_at];
-    two[n2++] = ops[p.op];
-    const ist_region clip{p.X0, p.Y0, p.X1 - p.X0, p.Y1 - p.Y0};
-    ist_job* j = ist_job_create(ctx, cw, ch, clear, two, n2, images, n_images, filter, &clip);
-    if (!j) return g_last_code ? g_last_code : IST_E_INVALID;
-    out->band.push_back(j);
+  for (size_t k = 0; k < cut.size(); ++k) {
+    const std::vector<ist_op> one = shard_part_ops(ops, n_ops, cut[k]);
+    out->band.emplace_back(ist_job_create(ctx, cw, ch, clear, one.data(), static_cast<int>(one.size()), images, n_images, filter, &boxes[k]));
+    if (!out->band.back()) return g_last_code ? g_last_code : IST_E_INVALID;
   }
   out->parts = cut;
   out->ok = true;
@@ -1111,15 +1099,11 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
     std::memset(&d, 0, sizeof d);
     d.width = D.w; d.height = D.h; d.orientation = D.orient ? D.orient : 1; d.opaque = D.jpeg ? 1 : 0; d.file_size = lens[i];
   }
-  ist_limits lim;
-  if (limits) lim = *limits; else ist_limits_unlimited(&lim);
-  rc = ist_plan_compute(descs.data(), n, direction, mode, gap, &lim, out_plan);
+  std::vector<ist_op> ops;
+  rc = plan_with_ops(descs.data(), n, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
   struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist_plan_free(p); } } pg{out_plan};
-  std::vector<ist_op> ops(static_cast<size_t>(out_plan->n_rects) + 1);
-  int n_ops = 0;
-  rc = ist_plan_ops(out_plan, descs.data(), n, ops.data(), &n_ops);
-  if (rc != IST_OK) return rc;
+  const int n_ops = static_cast<int>(ops.size());
 
   // one device arena (the context's, grow-only): bitmaps, JPEG coefficient planes + sample planes, canvas, PNG
   size_t off = 0;
@@ -1152,25 +1136,20 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
   // of image k+1 sat between the slabs of band k and band k+1 and cost its full time; on its own stream it runs beside them.
   rc = ensure_aux(ctx);
   if (rc) return rc;
-  if (!ctx->render) {                                  // (high priority: its short kernels should not queue behind the encoder's thousands of workgroups)
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&ctx->render, hipStreamNonBlocking, hi) != hipSuccess) { (void)hipGetLastError(); ctx->render = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
-  }
+  rc = ensure_render(ctx);
+  if (rc) return rc;
   hipStream_t render = ph.on ? ctx->stream : ctx->render;
   // the stitch, cut per image (compiled while the workers parse): background now, band k when image k is there
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   BandedJobs bj;
-  rc = compile_banded(ctx, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, descs.data(), n, filter, &bj);
+  rc = compile_banded(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), n_ops, descs.data(), n, filter, &bj);
   if (rc) return rc;
   mark("banded jobs compiled");
-  ist_job* whole = nullptr;
-  struct JobFree { ist_job** j; ~JobFree() { if (*j) ist_job_destroy(*j); } } jf{&whole};
+  JobPtr whole;
   if (!bj.ok) {
-    whole = ist_job_create(ctx, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, descs.data(), n, filter, nullptr);
+    whole.reset(ist_job_create(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), n_ops, descs.data(), n, filter, nullptr));
     if (!whole) return g_last_code ? g_last_code : IST_E_INVALID;
   } else {
-    rc = ist_job_launch(bj.bg, dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
+    rc = ist_job_launch(bj.bg.get(), dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
     if (rc) return rc;
   }
   // A draw that only MOVES its image - no scaling, no turn, whole pixels, nothing clipped, an opaque source - needs no bitmap
@@ -1191,7 +1170,7 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
       if (o.s[0] != 0.0 || o.s[1] != 0.0 || o.s[2] != D.w || o.s[3] != D.h || o.d[2] != D.w || o.d[3] != D.h) continue;
       if (X != std::floor(X) || Y != std::floor(Y) || X < 0 || Y < 0 || X + D.w > out_plan->canvas_w || Y + D.h > out_plan->canvas_h) continue;
       if (p.X0 != static_cast<int32_t>(X) || p.Y0 != static_cast<int32_t>(Y) || p.X1 - p.X0 != D.w || p.Y1 - p.Y0 != D.h) continue;
-      if (ist_job_info_get(bj.band[k], &info) != IST_OK || info.tiles_copy != info.n_tiles || info.n_tiles == 0) continue;      // (the compiler agrees: copy tiles only)
+      if (ist_job_info_get(bj.band[k].get(), &info) != IST_OK || info.tiles_copy != info.n_tiles || info.n_tiles == 0) continue;      // (the compiler agrees: copy tiles only)
       bool shared = false;                               // (an image drawn twice keeps its bitmap)
       for (size_t q = 0; q < bj.parts.size(); ++q) if (q != k && bj.parts[q].image == p.image) shared = true;
       if (shared) continue;
@@ -1227,7 +1206,7 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
         int rc2 = fd.finish(render);
         if (rc2) return rc2;
         rendered_whole = true;
-        rc2 = ist_job_launch(whole, dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
+        rc2 = ist_job_launch(whole.get(), dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
         if (rc2) return rc2;
         if (hipEventRecord(ctx->render_done, render) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
       }
@@ -1241,7 +1220,7 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
       const ist_part& p = bj.parts[next_part];
       int rc2 = fd.take(p.image, render);
       if (rc2) return rc2;
-      if (!direct[next_part]) rc2 = ist_job_launch(bj.band[next_part], dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
+      if (!direct[next_part]) rc2 = ist_job_launch(bj.band[next_part].get(), dsrc.data(), dpitch.data(), n, d + o_canvas, canvas_pitch, render);
       if (rc2) return rc2;
       if (hipEventRecord(ctx->img_event[next_part], render) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
       ++next_part;
@@ -1391,14 +1370,13 @@ struct RowBands {
   const uint8_t* const* src = nullptr;
   const size_t* src_pitch = nullptr;
   std::vector<int32_t> cuts;
-  std::vector<ist_part> parts;
-  std::vector<ist_job*> jobs;
+  std::vector<std::map<int, RowSpan>> need;   // per band: the rows of every image it samples
+  std::vector<JobPtr> jobs;
   std::vector<const void*> dsrc;
   std::vector<size_t> dpitch;
   std::vector<int64_t> lo, hi;            // rows of image i already sent: [lo, hi)
   std::vector<RowsCopy> items;
   uint8_t* canvas = nullptr;
-  ~RowBands() { for (ist_job* q : jobs) if (q) ist_job_destroy(q); }
   size_t bw(int i) const { return static_cast<size_t>(images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width); }
   int64_t bh(int i) const { return static_cast<int64_t>(images[i].bmp_height > 0 ? images[i].bmp_height : images[i].height); }
   int64_t y0(int b) const { return cuts[static_cast<size_t>(b)]; }
@@ -1412,30 +1390,29 @@ struct RowBands {
     if (off || total < (32u << 20) || n_images < 1) return IST_OK;
     nb = static_cast<int>(std::min<size_t>(16, std::max<size_t>(2, total / (40u << 20))));
     cuts.assign(static_cast<size_t>(nb) + 1, 0);
-    parts.resize(static_cast<size_t>(std::max(1, n_ops)) * static_cast<size_t>(nb) + 8);
+    std::vector<ist_part> parts(static_cast<size_t>(std::max(1, n_ops)) * static_cast<size_t>(nb) + 8);
     int n_parts = 0;
     {
-      const std::string keep_msg = g_last_error;
-      const int keep_code = g_last_code;
+      KeepLastError keep;                                        // not an error of the call: the one-shot path takes it
       if (ist_shard_row_cuts(ch, nb, cuts.data()) != IST_OK ||
-          ist_shard_parts(ops, n_ops, cw, ch, images, n_images, filter, nb, IST_SPLIT_ROWS, parts.data(), static_cast<int>(parts.size()), &n_parts) != IST_OK) {
-        g_last_error = keep_msg; g_last_code = keep_code;          // not an error of the call: the one-shot path takes it
+          ist_shard_parts(ops, n_ops, cw, ch, images, n_images, filter, nb, IST_SPLIT_ROWS, parts.data(), static_cast<int>(parts.size()), &n_parts) != IST_OK)
         return IST_OK;
-      }
     }
     parts.resize(static_cast<size_t>(n_parts));
-    jobs.assign(static_cast<size_t>(nb), nullptr);
+    // every band compiles the WHOLE op list, clipped to its rows: the flat form looks at every op, so a shorter list could change the band's kernel
+    jobs.resize(static_cast<size_t>(nb)); need.resize(static_cast<size_t>(nb));
     for (int b = 0; b < nb; ++b) {
+      need[static_cast<size_t>(b)] = shard_holdings(parts_of_slot(parts, b));
       if (y0(b) >= y1(b)) continue;
       const ist_region clip{0, static_cast<int32_t>(y0(b)), static_cast<int32_t>(cw), static_cast<int32_t>(y1(b) - y0(b))};
-      jobs[static_cast<size_t>(b)] = ist_job_create(ctx, cw, ch, clear, ops, n_ops, images, n_images, filter, &clip);
+      jobs[static_cast<size_t>(b)].reset(ist_job_create(ctx, cw, ch, clear, ops, n_ops, images, n_images, filter, &clip));
       if (!jobs[static_cast<size_t>(b)]) return g_last_code ? g_last_code : IST_E_INVALID;
     }
     // device scratch: the images the bands draw (whole allocations, filled row range by row range), and the canvas
     std::vector<size_t> at(static_cast<size_t>(n_images), 0);
     std::vector<char> used(static_cast<size_t>(n_images), 0);
     lo.assign(static_cast<size_t>(n_images), -1); hi.assign(static_cast<size_t>(n_images), -1);
-    for (const ist_part& p : parts) if (p.image >= 0 && p.image < n_images) used[static_cast<size_t>(p.image)] = 1;
+    for (const auto& band : need) for (const auto& kv : band) if (kv.first >= 0 && kv.first < n_images) used[static_cast<size_t>(kv.first)] = 1;
     size_t src_bytes = 0;
     for (int i = 0; i < n_images; ++i) {
       if (!used[static_cast<size_t>(i)]) continue;
@@ -1467,10 +1444,9 @@ struct RowBands {
       items.push_back(RowsCopy{static_cast<uint8_t*>(const_cast<void*>(dsrc[static_cast<size_t>(i)])) + static_cast<size_t>(r0) * bw(i) * 4,
                                src[i] + static_cast<size_t>(r0) * hp, nullptr, hp, bw(i) * 4, static_cast<size_t>(r1 - r0)});
     };
-    for (const ist_part& p : parts) {
-      if (p.slot != b || p.image < 0) continue;
-      const int i = p.image;
-      const int64_t a = std::max<int64_t>(0, p.sy0), e = std::min<int64_t>(bh(i), p.sy1);
+    for (const auto& kv : need[static_cast<size_t>(b)]) {
+      const int i = kv.first;
+      const int64_t a = std::max<int64_t>(0, kv.second.y0), e = std::min<int64_t>(bh(i), kv.second.y1);
       if (e <= a) continue;
       int64_t& L0 = lo[static_cast<size_t>(i)]; int64_t& H0 = hi[static_cast<size_t>(i)];
       if (L0 < 0) { send(i, a, e); L0 = a; H0 = e; }
@@ -1480,7 +1456,7 @@ struct RowBands {
       }
     }
     if (!items.empty()) { const int rc = stager_of(ctx).upload_big(items, R, ctx->workers.get()); if (rc) return rc; }
-    return ist_job_launch(jobs[static_cast<size_t>(b)], dsrc.data(), dpitch.data(), n_images, canvas, row, R);
+    return ist_job_launch(jobs[static_cast<size_t>(b)].get(), dsrc.data(), dpitch.data(), n_images, canvas, row, R);
   }
 };
 }  // namespace
@@ -1490,12 +1466,11 @@ struct RowBands {
 static int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, int n_ops, const ist_image_desc* images,
                                 const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter, uint8_t** out_pixels, bool* done) {
   *done = false;
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   static const bool print = std::getenv("IST_TIMING") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) { if (print) std::fprintf(stderr, "[ist timing] host stitch: %-34s at %7.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); };
   RowBands rb;
-  int rc = rb.prepare(ctx, plan->canvas_w, plan->canvas_h, transparent, ops, n_ops, images, src, src_pitch, n_images, filter);
+  int rc = rb.prepare(ctx, plan->canvas_w, plan->canvas_h, kTransparent, ops, n_ops, images, src, src_pitch, n_images, filter);
   if (rc) return rc;
   if (!rb.ok) return IST_OK;
   rc = ensure_aux(ctx);
@@ -1538,19 +1513,15 @@ static int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op
 static int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                              const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
                              uint8_t** out_png, int64_t* out_len) {
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   RowBands rb;
-  int rc = rb.prepare(ctx, canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, src, src_pitch, n_images, filter);
+  int rc = rb.prepare(ctx, canvas_w, canvas_h, clear_rgba ? clear_rgba : kTransparent, ops, n_ops, images, src, src_pitch, n_images, filter);
   if (rc) return rc;
   if (!rb.ok) return 1;
-  if (!ctx->render) {                                  // (high priority: its short kernels should not queue behind the encoder's thousands of workgroups)
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&ctx->render, hipStreamNonBlocking, hi) != hipSuccess) { (void)hipGetLastError(); ctx->render = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
-  }
+  rc = ensure_render(ctx);
+  if (rc) return rc;
   hipStream_t R = ctx->render;
   std::vector<hipEvent_t> ev(static_cast<size_t>(rb.nb), nullptr);
-  int next = 0, failed = IST_OK;
+  int next = 0;
   // the encoder is about to read canvas rows [0, y_end) on `reader`: submit the bands they lie in, order the reader behind the last of them
   auto need_rows = [&](int64_t y_end, void* reader_) -> int {
     hipStream_t reader = static_cast<hipStream_t>(reader_);
@@ -1560,15 +1531,15 @@ static int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, c
       if (rb.y0(b) >= y_end) break;
       if (b >= next) {
         const int rc2 = rb.submit(b, R);
-        if (rc2) { failed = rc2; return rc2; }
+        if (rc2) return rc2;
         if (hipEventCreateWithFlags(&ev[static_cast<size_t>(b)], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[static_cast<size_t>(b)], R) != hipSuccess) {
-          (void)hipGetLastError(); failed = IST_E_HIP; return fail(IST_E_HIP, "hipEventRecord failed");
+          (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed");
         }
         next = b + 1;
       }
       last = b;
     }
-    if (last >= 0 && hipStreamWaitEvent(reader, ev[static_cast<size_t>(last)], 0) != hipSuccess) { (void)hipGetLastError(); failed = IST_E_HIP; return fail(IST_E_HIP, "ordering the export behind the render failed"); }
+    if (last >= 0 && hipStreamWaitEvent(reader, ev[static_cast<size_t>(last)], 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering the export behind the render failed"); }
     return IST_OK;
   };
   int64_t hint = 0;
@@ -1577,7 +1548,6 @@ static int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, c
   (void)hipStreamSynchronize(R); (void)stager_of(ctx).sync(); (void)hipStreamSynchronize(ctx->stream);
   for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   if (rc == IST_OK) g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
-  (void)failed;
   return rc;
 }
 
@@ -1589,22 +1559,17 @@ int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* 
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!out_plan || !out_pixels) return fail(IST_E_INVALID, "ist_stitch_rgba8: NULL output");
   *out_pixels = nullptr;
-  ist_limits lim;
-  if (limits) lim = *limits; else ist_limits_unlimited(&lim);
-  int rc = ist_plan_compute(images, n_images, direction, mode, gap, &lim, out_plan);
+  std::vector<ist_op> ops;
+  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
-  std::vector<ist_op> ops(static_cast<size_t>(out_plan->n_rects) + 1);
-  int n_ops = 0;
-  rc = ist_plan_ops(out_plan, images, n_images, ops.data(), &n_ops);
-  if (rc != IST_OK) { ist_plan_free(out_plan); return rc; }
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
+  const int n_ops = static_cast<int>(ops.size());
   {
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard g(ctx->device);
     bool done = false;
     rc = stitch_banded_duplex(ctx, out_plan, ops.data(), n_ops, images, src, src_pitch, n_images, filter, out_pixels, &done);
     if (rc == IST_OK && !done) {
-      rc = render_to_scratch(ctx, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, images, src, src_pitch,
+      rc = render_to_scratch(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), n_ops, images, src, src_pitch,
                              n_images, filter, nullptr, nullptr, nullptr);
       // the export (index.js:1577-1579): the whole canvas in one DMA into a pinned block of the pool
       if (rc == IST_OK)

@@ -16,7 +16,8 @@
 //                    be anti-aliased: every canvas pixel has one owner, who paints the whole stack there.
 //   IST_SPLIT_AUTO   IMAGE when that cut yields full-width parts only (vertical min / max strips), else ROWS
 // Used by the single-process device group (ist_mgpu.cpp) and, through the C-ABI, by the one-process-per-GPU layout
-// (imagestitching_amd/dist.py), so both cut a job the same way.
+// (imagestitching_amd/dist.py), so both cut a job the same way.  What is built from a cut (hole_op .. uncovered_rows) is here
+// too: the device group, the file pipeline and the host duplex bands (ist_runtime.cpp) all take their sub-jobs from it.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -54,6 +55,61 @@ void tap_range(double k, double o, int lo, int hi, int clo, int chi, int filter,
 }
 
 }  // namespace
+
+ist_op hole_op(int64_t x, int64_t y, int64_t w, int64_t h) {
+  ist_op o;
+  std::memset(&o, 0, sizeof o);
+  o.kind = IST_OP_HOLE; o.image = -1; o.m[0] = 1.0; o.m[3] = 1.0;
+  o.d[0] = static_cast<double>(x); o.d[1] = static_cast<double>(y); o.d[2] = static_cast<double>(w); o.d[3] = static_cast<double>(h);
+  return o;
+}
+
+// (a draw that shards into nothing draws nothing: leaving it out changes no pixel)
+std::vector<ist_op> shard_band_ops(const ist_op* ops, int n_ops, const std::vector<ist_part>& parts) {
+  std::vector<char> mine(static_cast<size_t>(std::max(n_ops, 0)), 0);
+  for (const ist_part& p : parts) mine[static_cast<size_t>(p.op)] = 1;
+  std::vector<ist_op> out;
+  for (int k = 0; k < n_ops; ++k) if (ops[k].kind != IST_OP_DRAW || mine[static_cast<size_t>(k)]) out.push_back(ops[k]);
+  return out;
+}
+
+std::vector<ist_op> shard_root_ops(const ist_op* ops, int n_ops, const std::vector<ist_part>& own, const std::vector<ist_region>& holes) {
+  std::vector<ist_op> out = shard_band_ops(ops, n_ops, own);
+  for (const ist_region& r : holes) out.push_back(hole_op(r.x, r.y, r.w, r.h));
+  return out;
+}
+
+std::vector<ist_op> shard_part_ops(const ist_op* ops, int n_ops, const ist_part& part) {
+  std::vector<ist_op> out;
+  for (int k = 0; k < part.op; ++k) if (ops[k].kind == IST_OP_FILL) { out.push_back(ops[k]); break; }
+  out.push_back(ops[part.op]);
+  return out;
+}
+
+std::vector<ist_part> parts_of_slot(const std::vector<ist_part>& parts, int slot) {
+  std::vector<ist_part> out;
+  for (const ist_part& p : parts) if (p.slot == slot) out.push_back(p);
+  return out;
+}
+
+std::map<int, RowSpan> shard_holdings(const std::vector<ist_part>& parts) {
+  std::map<int, RowSpan> need;
+  for (const ist_part& p : parts) {
+    RowSpan& h = need.emplace(p.image, RowSpan{p.sy0, p.sy1}).first->second;
+    h.y0 = std::min<int64_t>(h.y0, p.sy0); h.y1 = std::max<int64_t>(h.y1, p.sy1);
+  }
+  return need;
+}
+
+std::vector<RowSpan> uncovered_rows(const std::vector<ist_region>& boxes, int64_t canvas_h) {
+  std::vector<RowSpan> covered, out;
+  for (const ist_region& b : boxes) covered.push_back(RowSpan{b.y, static_cast<int64_t>(b.y) + b.h});
+  std::sort(covered.begin(), covered.end(), [](const RowSpan& a, const RowSpan& b) { return a.y0 < b.y0; });
+  int64_t y = 0;
+  for (const RowSpan& c : covered) { if (c.y0 > y) out.push_back(RowSpan{y, c.y0}); y = std::max(y, c.y1); }
+  if (y < canvas_h) out.push_back(RowSpan{y, canvas_h});
+  return out;
+}
 
 }  // namespace ist
 

@@ -9,7 +9,7 @@ FLAGS="-std=c++17 -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-s
 export ASAN_OPTIONS=detect_leaks=0:allocator_may_return_null=1
 if [ "$1" = compile ]; then
   shift
-  g++ $FLAGS "$HERE/fuzz_compile.cpp" "$C/ist_compile.cpp" "$C/ist_plan.cpp" -o "$OUT"
+  g++ $FLAGS "$HERE/fuzz_compile.cpp" "$C/ist_compile.cpp" "$C/ist_plan.cpp" "$C/ist_shard.cpp" -o "$OUT"
 else
   # (IST_FUZZ_REUSE=1: keep a binary that is already there - the tests build the harness once per session)
   if [ -z "$IST_FUZZ_REUSE" ] || [ ! -x "$OUT" ]; then
