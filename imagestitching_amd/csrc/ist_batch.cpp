@@ -25,8 +25,6 @@ namespace {
 std::atomic<int64_t> g_batch_launches{0};
 
 constexpr int kKinds = 5;                               // launch_stitch's kernel forms (Compiled::kernel_kind)
-constexpr size_t kAlign = 256;
-size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
 // The host path splits a batch so that sources + canvases of one sub-batch stay under this many device bytes (a larger
 // request runs alone, with the memory its single stitch would take).  Two sub-batches are in flight (Pipeline below), so the
@@ -60,13 +58,6 @@ int take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
   }
   *out = &s;
   return IST_OK;
-}
-
-// bitmap bytes of one image of a request (the planner's rule: the decoded size when given, else the natural size)
-size_t image_bytes(const ist_image_desc& d) {
-  const size_t w = static_cast<size_t>(std::max(0, d.bmp_width > 0 ? d.bmp_width : d.width));
-  const size_t h = static_cast<size_t>(std::max(0, d.bmp_height > 0 ? d.bmp_height : d.height));
-  return w * 4 * h;
 }
 
 }  // namespace
@@ -126,9 +117,9 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
     if (G.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles of one kernel form");
     const size_t m = G.jobs.size();
     G.n_chunks = (G.n_tiles + (int64_t(1) << kBatchChunkLg) - 1) >> kBatchChunkLg;
-    G.at_args = total;  total = align_up(total + m * sizeof(LaunchArgs));
-    G.at_begin = total; total = align_up(total + (m + 1) * sizeof(int64_t));
-    G.at_chunk = total; total = align_up(total + static_cast<size_t>(G.n_chunks + 1) * sizeof(int32_t));
+    G.at_args = total;  total = round256(total + m * sizeof(LaunchArgs));
+    G.at_begin = total; total = round256(total + (m + 1) * sizeof(int64_t));
+    G.at_chunk = total; total = round256(total + static_cast<size_t>(G.n_chunks + 1) * sizeof(int32_t));
   }
   if (total == 0) return IST_OK;
   std::lock_guard<std::mutex> lk(ctx->batch_mu);
@@ -189,12 +180,8 @@ namespace {
 
 // jobs of a sub-batch whose kernel has completed (its half's kernel_done event): they are dropped without the stream wait of
 // ist_job_destroy, which would also wait for the launch of the NEXT sub-batch queued behind it on the same stream
-void drop_jobs(std::vector<ist_job*>* jobs) {
-  for (ist_job* j : *jobs) {
-    if (!j) continue;
-    j->launched = false; j->n_launched_on = 0; j->launched_many = false;
-    ist_job_destroy(j);
-  }
+void drop_jobs(std::vector<JobPtr>* jobs) {
+  for (JobPtr& j : *jobs) { j->launched = false; j->n_launched_on = 0; j->launched_many = false; }
   jobs->clear();
 }
 
@@ -215,7 +202,7 @@ struct Pipeline {
   const ist_plan* plans;
   uint8_t** out_pixels;
   int64_t* out_len;                       // PNG files out (NULL: canvases)
-  std::vector<ist_job*> jobs[2];          // the jobs whose tables live in half 0 / 1
+  std::vector<JobPtr> jobs[2];            // the jobs whose tables live in half 0 / 1
   bool used[2] = {false, false};
   int next = 0;
   std::vector<std::pair<int, std::vector<PngPatch>>> patches;   // (request, its file's patches), applied after finish()
@@ -239,40 +226,29 @@ struct Pipeline {
   }
 
   int run(const std::vector<int>& idx) {
-    static const uint8_t transparent[4] = {0, 0, 0, 0};
     const size_t n = idx.size();
     const int hi = next; next ^= 1;
     ist_ctx::BatchHalf& H = ctx->batch_half[hi];
-    std::vector<ist_job*> js(n, nullptr);
-    struct Guard { std::vector<ist_job*>* v; ~Guard() { if (v) for (ist_job* j : *v) if (j) ist_job_destroy(j); } } guard{&js};
+    std::vector<JobPtr> js(n);
     std::vector<TableLayout> lay(n);
+    SourceLayout src;                                      // the sources every job samples, request after request
     std::vector<size_t> tab_at(n, 0), dst_at(n, 0), canvas_bytes(n, 0), file_at(n, 0), file_cap(n, 0);
-    std::vector<std::vector<size_t>> src_at(n);
-    size_t tab_total = 0, src_total = 0, dst_total = 0, file_total = 0;
+    size_t tab_total = 0, dst_total = 0, file_total = 0;
     for (size_t q = 0; q < n; ++q) {
       const int k = idx[q];
       const ist_stitch_request& r = reqs[k];
       const ist_plan& p = plans[k];
-      js[q] = job_compile(ctx, p.canvas_w, p.canvas_h, transparent, ops[static_cast<size_t>(k)].data(), n_ops[static_cast<size_t>(k)],
-                          r.images, r.n_images, r.filter, nullptr);
-      if (!js[q]) { const std::string why = g_last_error; return fail(g_last_code ? g_last_code : IST_E_INVALID, "request " + std::to_string(k) + ": " + why); }
+      js[q].reset(job_compile(ctx, p.canvas_w, p.canvas_h, kTransparent, ops[static_cast<size_t>(k)].data(), n_ops[static_cast<size_t>(k)],
+                              r.images, r.n_images, r.filter, nullptr));
+      int rc = js[q] ? src.add(r.images, r.n_images, r.src, r.src_pitch, whole_bitmaps(js[q]->host)) : (g_last_code ? g_last_code : IST_E_INVALID);
+      if (rc) { const std::string why = g_last_error; return fail(rc, "request " + std::to_string(k) + ": " + why); }
       lay[q] = table_layout(*js[q]);
-      tab_at[q] = tab_total; tab_total += align_up(lay[q].total);
-      src_at[q].assign(static_cast<size_t>(r.n_images), SIZE_MAX);      // the sources the job samples
-      for (const DevOp& o : js[q]->host.ops) {
-        if (o.image < 0 || src_at[q][static_cast<size_t>(o.image)] != SIZE_MAX) continue;
-        const int i = o.image;
-        if (!r.src || !r.src[i]) return fail(IST_E_DECODE, "request " + std::to_string(k) + ": 图片" + std::to_string(i) + "解码异常");
-        const size_t row = static_cast<size_t>(js[q]->host.img_w[i]) * 4;
-        if (r.src_pitch && r.src_pitch[i] < row) return fail(IST_E_INVALID, "request " + std::to_string(k) + ": src_pitch too small");
-        src_at[q][static_cast<size_t>(i)] = src_total;
-        src_total += align_up(row * static_cast<size_t>(js[q]->host.img_h[i]));
-      }
+      tab_at[q] = tab_total; tab_total += round256(lay[q].total);
       canvas_bytes[q] = static_cast<size_t>(p.canvas_w) * 4 * static_cast<size_t>(p.canvas_h);
-      dst_at[q] = dst_total; dst_total += align_up(canvas_bytes[q]);
+      dst_at[q] = dst_total; dst_total += round256(canvas_bytes[q]);
       if (out_len) {
         file_cap[q] = static_cast<size_t>(ist_png_bound(p.canvas_w, p.canvas_h));
-        file_at[q] = file_total; file_total += align_up(file_cap[q]);
+        file_at[q] = file_total; file_total += round256(file_cap[q]);
       }
     }
     // the half is free once the launch that read it (two sub-batches ago) is done; its canvases must also be down before they
@@ -284,53 +260,41 @@ struct Pipeline {
     }
     if (!H.kernel_done && hipEventCreateWithFlags(&H.kernel_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.kernel_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
     if (!H.read_done && hipEventCreateWithFlags(&H.read_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.read_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
-    int rc = grow_device(&H.tab, &H.tab_bytes, tab_total ? tab_total : kAlign);
-    if (!rc) rc = grow_device(&H.src, &H.src_bytes, src_total ? src_total : kAlign);
-    if (!rc) rc = grow_device(&H.dst, &H.dst_bytes, dst_total ? dst_total : kAlign);
-    if (!rc && out_len) rc = grow_device(&H.file, &H.file_bytes, file_total ? file_total : kAlign);
+    int rc = grow_device(&H.tab, &H.tab_bytes, tab_total ? tab_total : 256);
+    if (!rc) rc = grow_device(&H.src, &H.src_bytes, src.bytes());
+    if (!rc) rc = grow_device(&H.dst, &H.dst_bytes, dst_total ? dst_total : 256);
+    if (!rc && out_len) rc = grow_device(&H.file, &H.file_bytes, file_total ? file_total : 256);
     if (rc) return rc;
     uint8_t* dtab = static_cast<uint8_t*>(H.tab);
-    uint8_t* dsrc = static_cast<uint8_t*>(H.src);
     uint8_t* ddst = static_cast<uint8_t*>(H.dst);
     // every job's tables in one host block: one item of the staged upload
     std::vector<uint8_t> blob(tab_total, 0);
     std::vector<RowsCopy> up;
     for (size_t q = 0; q < n; ++q) {
       pack_tables(lay[q], blob.data() + tab_at[q]);
-      point_tables(js[q], lay[q], dtab + tab_at[q]);
+      point_tables(js[q].get(), lay[q], dtab + tab_at[q]);
     }
     if (tab_total) up.push_back(RowsCopy{dtab, blob.data(), nullptr, tab_total, tab_total, 1});
-    std::vector<const void*> lsrc;
-    std::vector<size_t> lpitch;
+    const SourceLayout::Placed at = src.place(H.src);
+    src.copy_all(&up);
+    std::vector<ist_job*> ljob(n, nullptr);
     std::vector<int> lcount(n, 0);
     std::vector<void*> ldst(n, nullptr);
     std::vector<size_t> ldst_pitch(n, 0);
     for (size_t q = 0; q < n; ++q) {
-      const ist_stitch_request& r = reqs[idx[q]];
-      const Compiled& h = js[q]->host;
-      for (int i = 0; i < r.n_images; ++i) {
-        const size_t at = src_at[q][static_cast<size_t>(i)];
-        if (at == SIZE_MAX) { lsrc.push_back(nullptr); lpitch.push_back(0); continue; }
-        const size_t row = static_cast<size_t>(h.img_w[i]) * 4;
-        up.push_back(RowsCopy{dsrc + at, r.src[i], nullptr, r.src_pitch ? r.src_pitch[i] : row, row, static_cast<size_t>(h.img_h[i])});
-        lsrc.push_back(dsrc + at);
-        lpitch.push_back(row);
-      }
-      lcount[q] = r.n_images;
+      ljob[q] = js[q].get();
+      lcount[q] = reqs[idx[q]].n_images;
       ldst[q] = ddst + dst_at[q];
       ldst_pitch[q] = static_cast<size_t>(plans[idx[q]].canvas_w) * 4;
     }
-    if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device));
-    if (!ctx->workers) ctx->workers.reset(new WorkerPool());
-    rc = ctx->stager->upload_big(up, ctx->stream, ctx->workers.get());      // (one stream, big pieces: it shares PCIe with the downloads)
+    rc = stager_of(ctx).upload_big(up, ctx->stream, &workers_of(ctx));      // (one stream, big pieces: it shares PCIe with the downloads)
     if (rc) return rc;
     if (used[hi] && hipStreamWaitEvent(ctx->stream, H.read_done, 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering a sub-batch failed"); }
-    rc = ist_jobs_launch(js.data(), static_cast<int>(n), lsrc.data(), lpitch.data(), lcount.data(), ldst.data(), ldst_pitch.data(), ctx->stream);
+    rc = ist_jobs_launch(ljob.data(), static_cast<int>(n), at.ptr.data(), at.pitch.data(), lcount.data(), ldst.data(), ldst_pitch.data(), ctx->stream);
     if (rc) return rc;
     if (hipEventRecord(H.kernel_done, ctx->stream) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
     used[hi] = true;
-    jobs[hi] = js;
-    guard.v = nullptr;                                     // (the pipeline drops them once their launch is done)
+    jobs[hi] = std::move(js);                              // (the pipeline drops them once their launch is done)
     if (out_len) return encode_and_read(idx, H, ddst, dst_at, file_at, file_cap);
     // every canvas into a pinned block of its own, on the aux stream behind the launch
     if (hipStreamWaitEvent(ctx->aux, H.kernel_done, 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering a readback failed"); }
@@ -374,14 +338,6 @@ struct Pipeline {
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-
 // ist_stitch_rgba8_batch (out_len NULL) and ist_stitch_png_batch
 int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels, int64_t* out_len) {
   const size_t n = static_cast<size_t>(n_reqs);
@@ -406,7 +362,8 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
     if (rc < 0) { const std::string why = g_last_error; release(); return fail(rc, "request " + std::to_string(k) + ": " + why); }
     n_ops[k] = static_cast<int>(ops[k].size());
     bytes[k] = static_cast<size_t>(out_plans[k].canvas_w) * 4 * static_cast<size_t>(out_plans[k].canvas_h);
-    for (int i = 0; i < r.n_images; ++i) bytes[k] += image_bytes(r.images[i]);
+    for (int i = 0; i < r.n_images; ++i)
+      bytes[k] += static_cast<size_t>(std::max<int64_t>(0, bitmap_w(r.images[i]))) * 4 * static_cast<size_t>(std::max<int64_t>(0, bitmap_h(r.images[i])));
     if (out_len) {                                        // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
       const int64_t cw = out_plans[k].canvas_w, ch = out_plans[k].canvas_h;
       bytes[k] += static_cast<size_t>(ist_png_bound(cw, ch));
@@ -416,7 +373,7 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) { release(); return fail(IST_E_NO_DEVICE, "hipSetDevice failed"); }
-  int rc = ctx_aux_stream(ctx);
+  int rc = ensure_aux(ctx);
   if (rc) { release(); return rc; }
   // sub-batches: consecutive requests while their device bytes fit the budget, and at most kMaxBatchJobs of them
   Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels, out_len);

@@ -232,8 +232,8 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
   out->img_w.assign(static_cast<size_t>(n_images), 0);
   out->img_h.assign(static_cast<size_t>(n_images), 0);
   for (int i = 0; i < n_images; ++i) {
-    out->img_w[i] = images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width;
-    out->img_h[i] = images[i].bmp_height > 0 ? images[i].bmp_height : images[i].height;
+    out->img_w[i] = static_cast<int32_t>(bitmap_w(images[i]));
+    out->img_h[i] = static_cast<int32_t>(bitmap_h(images[i]));
   }
 
   // region to render
@@ -603,7 +603,7 @@ std::unique_ptr<FlatTwin> compile_flat_twin(int64_t canvas_w, int64_t canvas_h, 
     if (o.kind == IST_OP_DRAW) {
       if (o.image < 0 || o.image >= n_images) return nullptr;
       const ist_image_desc& im = images[o.image];
-      const int64_t iw = im.bmp_width > 0 ? im.bmp_width : im.width, ih = im.bmp_height > 0 ? im.bmp_height : im.height;
+      const int64_t iw = bitmap_w(im), ih = bitmap_h(im);
       if (iw != canvas_w || o.s[0] != 0.0 || o.s[2] != static_cast<double>(canvas_w) || !whole(o.s[1]) || o.s[3] != o.d[3]) return nullptr;
       sy = static_cast<int64_t>(o.s[1]);
       if (sy < 0 || sy + oh > ih) return nullptr;
@@ -675,11 +675,10 @@ extern "C" int ist_debug_flat_form(int64_t canvas_w, int64_t canvas_h, const uin
                                    int64_t* dst_offset, ist_flat_cell* cells, int max_cells, int* n_cells) {
   if (!n_cells || (max_cells > 0 && !cells)) return ist::fail(IST_E_INVALID, "ist_debug_flat_form: NULL argument");
   *n_cells = 0;
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   ist::Compiled primary;
-  int rc = ist::compile_ops(canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, n_images, filter, clip, &primary);
+  int rc = ist::compile_ops(canvas_w, canvas_h, clear_rgba ? clear_rgba : ist::kTransparent, ops, n_ops, images, n_images, filter, clip, &primary);
   if (rc != IST_OK) return rc;
-  const std::unique_ptr<ist::FlatTwin> t = ist::compile_flat_twin(canvas_w, canvas_h, clear_rgba ? clear_rgba : transparent, ops, n_ops, images, n_images, filter, primary);
+  const std::unique_ptr<ist::FlatTwin> t = ist::compile_flat_twin(canvas_w, canvas_h, clear_rgba ? clear_rgba : ist::kTransparent, ops, n_ops, images, n_images, filter, primary);
   if (!t) return IST_OK;
   if (pitch) *pitch = static_cast<int64_t>(ist::kFlatPitch);
   if (dst_offset) *dst_offset = t->dst_delta;

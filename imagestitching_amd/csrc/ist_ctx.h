@@ -101,6 +101,9 @@ struct ist_job {
   int max_image = -1;
 };
 
+// return IST_E_HIP from the calling function when a HIP call fails
+#define IST_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return ist::fail(IST_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
 namespace ist {
 
 struct DeviceGuard {
@@ -131,7 +134,16 @@ int job_launch_args(const ist_job* job, const void* const* src, const size_t* sr
 // the job was launched on `stream` (ist_job_destroy waits for it)
 void note_launch_stream(ist_job* job, void* stream);
 void count_flat_launches(int64_t n);
-int ctx_aux_stream(ist_ctx* ctx);        // the context's second stream (made on first use)
+
+// ---- the context's helpers of the host-buffer entry points (each stream, ring or pool is made on first use) ----
+inline Stager& stager_of(ist_ctx* ctx) { if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device)); return *ctx->stager; }
+inline WorkerPool& workers_of(ist_ctx* ctx) { if (!ctx->workers) ctx->workers.reset(new WorkerPool()); return *ctx->workers; }
+int ensure_aux(ist_ctx* ctx);             // the context's second stream
+int ensure_render(ist_ctx* ctx);          // the context's render stream
+int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t** out);   // device bytes -> a pooled pinned block
+// the PNG file of a canvas in device memory -> a pooled pinned block (need_rows / slab_rows_hint: as png_encode_device_deflate)
+int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
+                const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0);
 
 
 }  // namespace ist

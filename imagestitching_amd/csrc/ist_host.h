@@ -24,6 +24,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ist_internal.h"     // RowsCopy
+
 namespace ist {
 
 // ---- pool of pinned result buffers (process-wide) -----------------------------------------------------------------
@@ -35,13 +37,6 @@ bool pool_give(void* p);                // true when p came from pool_take (the 
 void pool_trim();                       // release every cached block
 
 // ---- staged copies between caller memory and device memory -------------------------------------------------------
-struct RowsCopy {                       // `rows` rows of `row` bytes; the device side is always contiguous (pitch == row)
-  void* dev;                            // device address of the first row
-  const void* host_src;                 // upload: caller memory to read  (pitch host_pitch)
-  void* host_dst;                       // download: caller memory to write (pitch host_pitch)
-  size_t host_pitch, row, rows;
-};
-
 class Stager {
  public:
   explicit Stager(int device) : device_(device) {}

@@ -17,6 +17,13 @@ extern thread_local std::string g_last_error;
 extern thread_local int g_last_code;
 int fail(int code, const std::string& msg);
 
+constexpr uint8_t kTransparent[4] = {0, 0, 0, 0};      // the clear colour of a new canvas
+inline size_t round256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }   // every section of a device block starts 256-aligned
+
+// the size of an image's bitmap (the planner's rule: the decoded size when given, else the natural size)
+inline int64_t bitmap_w(const ist_image_desc& d) { return d.bmp_width > 0 ? d.bmp_width : d.width; }
+inline int64_t bitmap_h(const ist_image_desc& d) { return d.bmp_height > 0 ? d.bmp_height : d.height; }
+
 // Canvas current transformation matrix:  X = a*u + c*v + e ;  Y = b*u + d*v + f
 struct Ctm {
   double a = 1.0, b = 0.0, c = 0.0, d = 1.0, e = 0.0, f = 0.0;
@@ -155,11 +162,46 @@ std::vector<ist_part> parts_of_slot(const std::vector<ist_part>& parts, int slot
 std::map<int, RowSpan> shard_holdings(const std::vector<ist_part>& parts);     // per image: the union of the parts' [sy0, sy1)
 std::vector<RowSpan> uncovered_rows(const std::vector<ist_region>& boxes, int64_t canvas_h);   // rows of [0, canvas_h) no box covers
 
+// ---- caller sources in device scratch (ist_sources.cpp, pure CPU): every host entry point stages the images it samples through this
+struct RowsCopy {                       // `rows` rows of `row` bytes; the device side is always contiguous (pitch == row)
+  void* dev;                            // device address of the first row
+  const void* host_src;                 // upload: caller memory to read  (pitch host_pitch)
+  void* host_dst;                       // download: caller memory to write (pitch host_pitch)
+  size_t host_pitch, row, rows;
+};
+// Readable bytes behind a section's last row.  The kernels send the right edge of a draw's last source row (DevOp::cy1) through registers
+// (ist_kernels.hip, `last_row`), so no load leaves a whole bitmap; on the last row of a holding that ends above cy1 (a band or a slot of a
+// cut) vector loads reach up to 12 bytes past it.  256 covers every path.
+constexpr size_t kSourceTail = 256;
+// One block of device scratch for the sources of one or more requests: per held image a 256-byte aligned section of its held rows
+// (rows * 4 * bitmap width + kSourceTail), in image order.  Images are numbered across the requests.
+class SourceLayout {
+ public:
+  // held: image -> the rows [y0, y1) the launch samples.  Checks them in index order (NULL source or empty bitmap: IST_E_DECODE
+  // "图片<i>解码异常"; a pitch below 4 * bitmap width: IST_E_INVALID "src_pitch too small"); appends nothing on a failure.
+  int add(const ist_image_desc* images, int n_images, const uint8_t* const* src, const size_t* src_pitch, const std::map<int, RowSpan>& held);
+  size_t bytes() const { return total_ ? total_ : 256; }       // (never 0: a device allocation always gets a block)
+  // the sections start at `base`: per image the address of its ROW 0 (NULL: not held) and its pitch, as ist_job_launch takes them
+  struct Placed { std::vector<const void*> ptr; std::vector<size_t> pitch; };
+  Placed place(void* base);
+  RowsCopy copy(int i, int64_t r0, int64_t r1) const;          // rows [r0, r1) of image i into its section (after place())
+  void copy_all(std::vector<RowsCopy>* items) const;           // + every held row, image after image (after place())
+
+ private:
+  struct Image { const uint8_t* src = nullptr; size_t pitch = 0, row = 0, at = 0; RowSpan rows{0, 0}; };   // src NULL: not held
+  std::vector<Image> img_;
+  size_t total_ = 0;                    // bytes of the sections
+  uint8_t* base_ = nullptr;             // where place() put them
+};
+std::map<int, RowSpan> whole_bitmaps(const Compiled& job);     // every image a compiled job draws, all of its rows
+
 // ist_plan_compute (limits NULL: unlimited), then the plan's op list; the plan is freed again when the op list fails
 int plan_with_ops(const ist_image_desc* images, int n_images, int direction, int mode, double gap, const ist_limits* limits, ist_plan* plan,
                   std::vector<ist_op>* ops);
 struct JobDelete { void operator()(ist_job* j) const { ist_job_destroy(j); } };
 using JobPtr = std::unique_ptr<ist_job, JobDelete>;      // a sub-job owned by its caller
+// the plan an entry point has filled in for its caller: freed again on a failure (keep = true once the call succeeds)
+struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist_plan_free(p); } };
 // around a failure the caller tolerates: the thread's g_last_error / g_last_code are what they were before, once it goes out of scope
 struct KeepLastError { std::string msg = g_last_error; int code = g_last_code; ~KeepLastError() { g_last_error = msg; g_last_code = code; } };
 

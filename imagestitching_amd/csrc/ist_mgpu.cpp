@@ -40,7 +40,6 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -144,6 +143,7 @@ struct ist_group_job {
   std::vector<Unit> units;
   int split = IST_SPLIT_IMAGE;            // the effective cut (AUTO resolved)
   JobPtr root_job;
+  std::vector<size_t> root_parts;         // the parts of slot 0 (the root job's sources)
   std::vector<size_t> band_need;          // per device: bytes of band arena this job addresses
   size_t staging_need = 0;
   bool host_sink_ok = false;              // every band is full-width: bands can be DMA'ed straight into a host canvas
@@ -153,7 +153,6 @@ struct ist_group_job {
 namespace {
 
 inline size_t unit_bytes(const ist_group_job::Unit& u) { return static_cast<size_t>(u.X1 - u.X0) * 4 * static_cast<size_t>(u.Y1 - u.Y0); }
-inline size_t round256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 int group_sync_locked(ist_group* g) {
   for (size_t r = 0; r < g->devs.size(); ++r) {
@@ -259,13 +258,13 @@ ist_group_job* ist_group_job_create(ist_group* g, int64_t canvas_w, int64_t canv
   std::unique_ptr<ist_group_job> job(new ist_group_job);
   job->g = g; job->cw = canvas_w; job->ch = canvas_h; job->n_images = n_images; job->split = split;
   job->band_need.assign(g->devs.size(), 0);
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
-  const uint8_t* clear = clear_rgba ? clear_rgba : transparent;
+  const uint8_t* clear = clear_rgba ? clear_rgba : kTransparent;
   for (size_t k = 0; k < cut.size(); ++k) {
     ist_group_job::PartRt rt;
     rt.part = cut[k];
     rt.rank = g->slot_rank[static_cast<size_t>(cut[k].slot)];
     job->parts.push_back(rt);
+    if (rt.part.slot == 0) job->root_parts.push_back(k);
   }
   // units of the non-root slots
   auto new_unit = [&](int slot, int32_t X0, int32_t Y0, int32_t X1, int32_t Y1) -> ist_group_job::Unit& {
@@ -346,36 +345,30 @@ int ist_group_job_parts(const ist_group_job* job, ist_part* parts, int max_parts
 
 namespace {
 
+// sub-job `j` on device `rank`'s stream, with the sources of the parts `mine` lists (the launch's table is by part, a job's by image)
+int launch_parts(ist_group_job* job, ist_job* j, int rank, const std::vector<size_t>& mine, const void* const* src, const size_t* src_pitch,
+                 void* dst, size_t dst_pitch) {
+  std::vector<const void*> one(static_cast<size_t>(job->n_images), nullptr);
+  std::vector<size_t> one_pitch(static_cast<size_t>(job->n_images), 0);
+  for (size_t k : mine) {
+    const ist_part& p = job->parts[k].part;
+    if (!src[k]) return fail(IST_E_DECODE, "图片" + std::to_string(p.image) + "解码异常");
+    one[static_cast<size_t>(p.image)] = src[k];
+    one_pitch[static_cast<size_t>(p.image)] = src_pitch ? src_pitch[k] : 0;
+  }
+  return ist_job_launch(j, one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, dst_pitch, job->g->ctx[static_cast<size_t>(rank)]->stream);
+}
+
 // one unit of a non-root slot into `to` (a compact band, or - biased by the caller - the canvas itself), on its owner's stream
 int launch_band(ist_group_job* job, size_t ui, const void* const* src, const size_t* src_pitch, void* to, size_t to_pitch, bool compact) {
   auto& u = job->units[ui];
-  const size_t ni = static_cast<size_t>(job->n_images);
-  std::vector<const void*> one(ni, nullptr);
-  std::vector<size_t> one_pitch(ni, 0);
-  for (size_t k : u.part_idx) {
-    const ist_part& p = job->parts[k].part;
-    if (!src[k]) return fail(IST_E_DECODE, "图片" + std::to_string(p.image) + "解码异常");
-    one[static_cast<size_t>(p.image)] = src[k];
-    one_pitch[static_cast<size_t>(p.image)] = src_pitch ? src_pitch[k] : 0;
-  }
   void* dst = to;
   if (compact) dst = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(to) - (static_cast<uintptr_t>(u.Y0) * to_pitch + static_cast<uintptr_t>(u.X0) * 4));
-  return ist_job_launch(u.band_job.get(), one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, to_pitch,
-                        job->g->ctx[static_cast<size_t>(u.rank)]->stream);
+  return launch_parts(job, u.band_job.get(), u.rank, u.part_idx, src, src_pitch, dst, to_pitch);
 }
 
 int launch_root(ist_group_job* job, const void* const* src, const size_t* src_pitch, void* dst, size_t dst_pitch) {
-  const size_t ni = static_cast<size_t>(job->n_images);
-  std::vector<const void*> one(ni, nullptr);
-  std::vector<size_t> one_pitch(ni, 0);
-  for (size_t k = 0; k < job->parts.size(); ++k) {
-    const ist_part& p = job->parts[k].part;
-    if (p.slot != 0) continue;
-    if (!src[k]) return fail(IST_E_DECODE, "图片" + std::to_string(p.image) + "解码异常");
-    one[static_cast<size_t>(p.image)] = src[k];
-    one_pitch[static_cast<size_t>(p.image)] = src_pitch ? src_pitch[k] : 0;
-  }
-  return ist_job_launch(job->root_job.get(), one.data(), src_pitch ? one_pitch.data() : nullptr, job->n_images, dst, dst_pitch, job->g->ctx[0]->stream);
+  return launch_parts(job, job->root_job.get(), 0, job->root_parts, src, src_pitch, dst, dst_pitch);
 }
 
 // the communicators of the group (one per distinct device), on first need.  Caller holds g->mu.
@@ -488,9 +481,8 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   std::vector<ist_op> ops;
   int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
-  struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist_plan_free(p); } } pg{out_plan};
+  PlanGuard pg{out_plan};
   const int n_ops = static_cast<int>(ops.size());
-  static const uint8_t transparent[4] = {0, 0, 0, 0};
   std::lock_guard<std::mutex> glock(g->mu);            // one host-path stitch in flight per group (index.js:772 isStitching)
   // the compiled group job: from the LRU, or compiled now and kept
   ist_group_job* job = nullptr;
@@ -505,7 +497,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
         break;
       }
     if (!job) {
-      job = ist_group_job_create(g, out_plan->canvas_w, out_plan->canvas_h, transparent, ops.data(), n_ops, images, n_images, filter, split);
+      job = ist_group_job_create(g, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), n_ops, images, n_images, filter, split);
       if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
       if (g->cache.size() >= ist_group::kCacheJobs) {    // every call ends with the group idle: the oldest job is not in flight
         delete g->cache.front().job;
@@ -517,16 +509,13 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   rc = ensure_arenas(g, job);
   if (rc) return rc;
 
-  // holdings: per (device, image) the union of the rows its parts sample, + 16 readable bytes behind the last row
+  // holdings: per (device, image) the union of the rows its parts sample; every source is checked before anything is allocated
   const size_t nd = g->devs.size();
   std::vector<std::vector<ist_part>> mine(nd);
-  for (const auto& rt : job->parts) {
-    if (!src || !src[rt.part.image]) return fail(IST_E_DECODE, "图片" + std::to_string(rt.part.image) + "解码异常");
-    mine[static_cast<size_t>(rt.rank)].push_back(rt.part);
-  }
-  struct Hold { RowSpan rows; size_t off; };
-  std::vector<std::map<int, Hold>> hold(nd);
-  auto width_of = [&](int i) { return static_cast<size_t>(images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width); };
+  std::vector<ist_part> every;
+  for (const auto& rt : job->parts) { mine[static_cast<size_t>(rt.rank)].push_back(rt.part); every.push_back(rt.part); }
+  rc = SourceLayout().add(images, n_images, src, src_pitch, shard_holdings(every));
+  if (rc) return rc;
   const size_t canvas_pitch = static_cast<size_t>(out_plan->canvas_w) * 4;
   const size_t canvas_bytes = canvas_pitch * static_cast<size_t>(out_plan->canvas_h);
   const bool host_sink = job->host_sink_ok && !g->self_send;
@@ -539,22 +528,23 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   uint8_t* host = static_cast<uint8_t*>(pool_take(canvas_bytes));
   if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the result");
   struct HostGuard { uint8_t* p; ist_group* g; bool keep = false; ~HostGuard() { if (!keep) { (void)group_sync_locked(g); pool_give(p); } } } hg{host, g};
-  // part pointers: row 0 of the image as seen from the holding (offsets are known before the uploads run)
+  // per device, its holdings in its scratch; part pointers: row 0 of the image as seen from the holding
+  std::vector<SourceLayout> lay(nd);
+  std::vector<SourceLayout::Placed> at(nd);
   for (size_t r = 0; r < nd; ++r) {
-    size_t total = 0;
-    for (const auto& kv : shard_holdings(mine[r])) { hold[r][kv.first] = Hold{kv.second, total}; total += round256(width_of(kv.first) * 4 * static_cast<size_t>(kv.second.y1 - kv.second.y0) + 16); }
-    DeviceGuard dg(g->devs[r]);
-    rc = grow_device(&g->ctx[r]->scratch_src, &g->ctx[r]->scratch_src_bytes, total ? total : 256);
+    rc = lay[r].add(images, n_images, src, src_pitch, shard_holdings(mine[r]));
     if (rc) return rc;
+    DeviceGuard dg(g->devs[r]);
+    rc = grow_device(&g->ctx[r]->scratch_src, &g->ctx[r]->scratch_src_bytes, lay[r].bytes());
+    if (rc) return rc;
+    at[r] = lay[r].place(g->ctx[r]->scratch_src);
   }
   std::vector<const void*> psrc(job->parts.size(), nullptr);
   std::vector<size_t> ppitch(job->parts.size(), 0);
   for (size_t k = 0; k < job->parts.size(); ++k) {
     const auto& rt = job->parts[k];
-    const Hold& h = hold[static_cast<size_t>(rt.rank)][rt.part.image];
-    const size_t row = width_of(rt.part.image) * 4;
-    psrc[k] = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(g->ctx[static_cast<size_t>(rt.rank)]->scratch_src) + h.off - static_cast<uintptr_t>(h.rows.y0) * row);
-    ppitch[k] = row;
+    psrc[k] = at[static_cast<size_t>(rt.rank)].ptr[static_cast<size_t>(rt.part.image)];
+    ppitch[k] = at[static_cast<size_t>(rt.rank)].pitch[static_cast<size_t>(rt.part.image)];
   }
   // one host thread per device: upload its rows, then (host sink) render its bands and send each home over its own link
   std::vector<int> up_rc(nd, IST_OK);
@@ -566,15 +556,9 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
     for (size_t r = 0; r < nd; ++r) th.emplace_back([&, r]() {
       ist_ctx* c = g->ctx[r];
       DeviceGuard dg(c->device);
-      int rc2 = IST_OK;
       std::vector<RowsCopy> up;
-      for (auto& kv : hold[r]) {
-        const size_t row = width_of(kv.first) * 4, hp = src_pitch ? src_pitch[kv.first] : row;
-        if (hp < row) { rc2 = fail(IST_E_INVALID, "src_pitch too small"); break; }
-        up.push_back(RowsCopy{static_cast<uint8_t*>(c->scratch_src) + kv.second.off, src[kv.first] + static_cast<size_t>(kv.second.rows.y0) * hp, nullptr, hp, row,
-                              static_cast<size_t>(kv.second.rows.y1 - kv.second.rows.y0)});
-      }
-      if (rc2 == IST_OK) { if (!c->stager) c->stager.reset(new Stager(c->device)); rc2 = c->stager->upload(up, c->stream); }
+      lay[r].copy_all(&up);
+      int rc2 = stager_of(c).upload(up, c->stream);
       if (rc2 == IST_OK && host_sink) {
         for (size_t k = 0; k < job->units.size() && rc2 == IST_OK; ++k) {
           const auto& u = job->units[k];

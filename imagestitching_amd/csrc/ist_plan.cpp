@@ -243,8 +243,8 @@ int ist_plan_ops(const ist_plan* plan, const ist_image_desc* images, int n_image
     const ist_rect& r = plan->rects[i];
     if (r.image < 0 || r.image >= n_images) return fail(IST_E_INVALID, "rect refers to a missing image");
     const ist_image_desc& im = images[r.image];
-    const double bw = im.bmp_width > 0 ? im.bmp_width : im.width;
-    const double bh = im.bmp_height > 0 ? im.bmp_height : im.height;
+    const double bw = static_cast<double>(bitmap_w(im));
+    const double bh = static_cast<double>(bitmap_h(im));
     if (!(bw >= 1.0) || !(bh >= 1.0)) return fail(IST_E_DECODE, "图片" + std::to_string(r.image) + "解码异常");  // index.js:1512-1514
     Ctm t;                                                            // fresh canvas: identity
     if (plan->super_sample != 1.0) t.scale(plan->super_sample, plan->super_sample);   // index.js:1426-1428

@@ -1,4 +1,5 @@
-// ist_runtime.cpp — device context, compiled jobs and the host-buffer convenience path of the C-ABI.
+// ist_runtime.cpp — device context, compiled jobs, image decoding and the file pipeline of the C-ABI (the host-buffer
+// entry points are in ist_host_stitch.cpp).
 //
 // Reference anchors (miniprogram-stitch/miniprogram/): the context stands for the canvas node obtained at
 // pages/index/index.js:1196-1204; a job for the offscreen canvas + recorded draws (utils/canvas.js:131-150,
@@ -19,7 +20,6 @@
 #include <functional>
 #include <memory>
 #include <mutex>
-#include <thread>
 
 #include "ist_ctx.h"
 #include "ist_internal.h"
@@ -28,12 +28,6 @@
 #include "ist_webp.h"
 
 using namespace ist;
-
-#define IST_HIP(expr)                                                                                       \
-  do {                                                                                                      \
-    const hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-  } while (0)
 
 namespace ist {
 int ctx_png_level(const ist_ctx* ctx) { return ctx ? ctx->png_level : 0; }
@@ -59,16 +53,6 @@ int grow_device(void** p, size_t* have, size_t need) {
   *have = need;
   return IST_OK;
 }
-}  // namespace ist
-
-namespace {
-
-const uint8_t kTransparent[4] = {0, 0, 0, 0};     // the clear colour of a new canvas
-
-Stager& stager_of(ist_ctx* ctx) {
-  if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device));
-  return *ctx->stager;
-}
 
 // A buffer the library hands to the caller (freed with ist_free): a pinned block from the pool, filled by ONE linear DMA
 // from device memory, no host copy.  Synchronises `stream`.
@@ -85,7 +69,7 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
 }
 
 // a stream of the context, made on first need at the highest priority (`lowest`: the lowest)
-int ensure_stream(hipStream_t* s, bool lowest = false) {
+static int ensure_stream(hipStream_t* s, bool lowest = false) {
   if (*s) return IST_OK;
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -105,7 +89,7 @@ int ensure_render(ist_ctx* ctx) { return ensure_stream(&ctx->render); }
 // while it is still compressing (png_encode_device_deflate); the stored form is encoded whole and copied once.
 // Caller holds ctx->mu.  Synchronises ctx->stream.
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
-                const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0) {
+                const std::function<int(int64_t, void*)>& need_rows, int64_t slab_rows_hint) {
   const int64_t cap = ist_png_bound(w, h);
   if (!dfile) {
     const int rc = grow_device(&ctx->scratch_file, &ctx->scratch_file_bytes, static_cast<size_t>(cap));
@@ -134,9 +118,7 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
   return IST_OK;
 }
 
-}  // namespace
-
-int ist::ctx_aux_stream(ist_ctx* ctx) { return ensure_aux(ctx); }
+}  // namespace ist
 
 extern "C" {
 
@@ -222,7 +204,6 @@ void ist_ctx_destroy(ist_ctx* ctx) {
 }
 
 static std::atomic<int64_t> g_flat_launches{0};
-static std::atomic<int64_t> g_duplex_stitches{0};
 
 int64_t ist_debug_flat_launches(void) { return g_flat_launches.load(); }
 
@@ -254,7 +235,7 @@ TableLayout table_layout(const ist_job& job) {
     const size_t b[5] = {h.ops.size() * sizeof(DevOp), h.cells.size() * sizeof(DevCell), h.bands.size() * sizeof(DevBand),
                          h.stacks.size() * sizeof(int32_t), h.tiles.size() * sizeof(DevTile)};
     const void* f[5] = {h.ops.data(), h.cells.data(), h.bands.data(), h.stacks.data(), h.tiles.data()};
-    for (int k = 0; k < 5; ++k) { L.bytes[t][k] = b[k]; L.from[t][k] = f[k]; L.at[t][k] = L.total; L.total += (b[k] + 255) & ~static_cast<size_t>(255); }
+    for (int k = 0; k < 5; ++k) { L.bytes[t][k] = b[k]; L.from[t][k] = f[k]; L.at[t][k] = L.total; L.total += round256(b[k]); }
   }
   return L;
 }
@@ -435,116 +416,6 @@ void ist_job_destroy(ist_job* job) {
   delete job;
 }
 
-// host sources -> device scratch -> fused launch into ctx->scratch_dst (left on the device, stream NOT synchronised).
-// The scratch holds exactly the rendered region, rows contiguous (the launch addresses it as if it were the canvas: dst is
-// biased by the region's origin), so every readback is one linear copy.  Caller holds ctx->mu.
-static int render_to_scratch(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
-                             const ist_op* ops, int n_ops, const ist_image_desc* images, const uint8_t* const* src,
-                             const size_t* src_pitch, int n_images, int filter, const ist_region* region,
-                             int64_t* out_w, int64_t* out_h) {
-  const JobPtr job(ist_job_create(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, n_images, filter, region));
-  if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
-
-  // stage the sources that the job actually samples
-  std::vector<size_t> off(static_cast<size_t>(n_images), 0);
-  std::vector<char> used(static_cast<size_t>(n_images), 0);
-  for (const DevOp& o : job->host.ops) if (o.image >= 0) used[o.image] = 1;
-  size_t total = 0;
-  for (int i = 0; i < n_images; ++i) {
-    if (!used[i]) continue;
-    if (!src || !src[i]) return fail(IST_E_DECODE, "图片" + std::to_string(i) + "解码异常");
-    off[i] = total;
-    total += (static_cast<size_t>(job->host.img_w[i]) * 4 * job->host.img_h[i] + 255) & ~static_cast<size_t>(255);
-  }
-  int rc = grow_device(&ctx->scratch_src, &ctx->scratch_src_bytes, total ? total : 256);
-  if (rc) return rc;
-  const int64_t rw = job->host.rx1 - job->host.rx0, rh = job->host.ry1 - job->host.ry0;
-  const size_t pitch = static_cast<size_t>(rw) * 4;
-  rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, pitch * static_cast<size_t>(rh));
-  if (rc) return rc;
-  std::vector<const void*> dsrc(static_cast<size_t>(n_images), nullptr);
-  std::vector<size_t> dpitch(static_cast<size_t>(n_images), 0);
-  std::vector<RowsCopy> up;
-  for (int i = 0; i < n_images; ++i) {
-    if (!used[i]) continue;
-    const size_t row = static_cast<size_t>(job->host.img_w[i]) * 4;
-    const size_t hp = src_pitch ? src_pitch[i] : row;
-    if (hp < row) return fail(IST_E_INVALID, "src_pitch too small");
-    uint8_t* d = static_cast<uint8_t*>(ctx->scratch_src) + off[i];
-    up.push_back(RowsCopy{d, src[i], nullptr, hp, row, static_cast<size_t>(job->host.img_h[i])});
-    dsrc[i] = d; dpitch[i] = row;
-  }
-  rc = stager_of(ctx).upload(up, ctx->stream);
-  if (rc) return rc;
-  const uintptr_t biased = reinterpret_cast<uintptr_t>(ctx->scratch_dst) - (static_cast<uintptr_t>(job->host.ry0) * pitch + static_cast<uintptr_t>(job->host.rx0) * 4);
-  rc = ist_job_launch(job.get(), dsrc.data(), dpitch.data(), n_images, reinterpret_cast<void*>(biased), pitch, ctx->stream);
-  if (rc) return rc;
-  // the job's device tables are freed when `job` goes out of scope: the launch must have consumed them
-  IST_HIP(hipStreamSynchronize(ctx->stream));
-  if (out_w) *out_w = rw;
-  if (out_h) *out_h = rh;
-  return IST_OK;
-}
-
-int ist_render_rgba8(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
-                     const ist_op* ops, int n_ops, const ist_image_desc* images, const uint8_t* const* src,
-                     const size_t* src_pitch, int n_images, int filter, const ist_region* region, uint8_t* dst,
-                     size_t dst_pitch) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!dst) return fail(IST_E_INVALID, "ist_render_rgba8: dst is NULL");
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  // the region that will be read back (same-size export, index.js:1577-1579; or getImageData, 1564): check the caller's
-  // pitch before any work is queued
-  int64_t rw = canvas_w, rh = canvas_h;
-  if (region) {
-    const int64_t rx = std::max<int64_t>(0, region->x), ry = std::max<int64_t>(0, region->y);
-    rw = std::min<int64_t>(canvas_w, static_cast<int64_t>(region->x) + region->w) - rx;
-    rh = std::min<int64_t>(canvas_h, static_cast<int64_t>(region->y) + region->h) - ry;
-  }
-  if (rw > 0 && dst_pitch < static_cast<size_t>(rw) * 4) return fail(IST_E_INVALID, "dst_pitch too small");
-  int rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, region, &rw, &rh);
-  if (rc) return rc;
-  std::vector<RowsCopy> down{RowsCopy{ctx->scratch_dst, nullptr, dst, dst_pitch, static_cast<size_t>(rw) * 4, static_cast<size_t>(rh)}};
-  return stager_of(ctx).download(down, ctx->stream);
-}
-
-// (below, behind RowBands) the same band by band: band b + 1's source rows go up while the encoder compresses band b and sends its slabs down
-static int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
-                             const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
-                             uint8_t** out_png, int64_t* out_len);
-
-// PNG of a rendered op list: the canvas never leaves the device, only the PNG bytes cross PCIe
-int ist_render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops,
-                   int n_ops, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
-                   int n_images, int filter, uint8_t** out_png, int64_t* out_len) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!out_png || !out_len) return fail(IST_E_INVALID, "ist_render_png: NULL output");
-  *out_png = nullptr; *out_len = 0;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  int rc = render_png_banded(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len);
-  if (rc != 1) return rc;                      // (1: not applicable, nothing queued)
-  rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, nullptr, nullptr, nullptr);
-  if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len);
-}
-
-// plan + render + PNG: onStitch stages 2-5 including the export (index.js:1251-1581), decode excluded
-int ist_stitch_png(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
-                   int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter,
-                   ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_png: NULL output");
-  std::vector<ist_op> ops;
-  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
-  if (rc != IST_OK) return rc;
-  rc = ist_render_png(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
-                      n_images, filter, out_png, out_len);
-  if (rc != IST_OK) ist_plan_free(out_plan);
-  return rc;
-}
-
 // ---- JPEG decode: entropy decoding on the host, reconstruction on the GPU (ist_jpeg.cpp / ist_jpeg_kernels.hip) ----------
 extern "C++" {
 namespace {
@@ -554,7 +425,7 @@ namespace {
 struct JpegDevLayout { size_t coef[3], q[3], plane[3], ent[3], start[3], cnt[3]; };
 
 void jpeg_layout(const JpegImage& J, size_t* off, JpegDevLayout* L) {
-  auto take = [&](size_t bytes) { const size_t at = *off; *off += (bytes + 255) & ~static_cast<size_t>(255); return at; };
+  auto take = [&](size_t bytes) { const size_t at = *off; *off += round256(bytes); return at; };
   std::memset(L, 0, sizeof(*L));
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
@@ -566,7 +437,7 @@ void jpeg_layout(const JpegImage& J, size_t* off, JpegDevLayout* L) {
 }
 // the `ent` arena part of a host-decoded image (components in sparse form)
 void jpeg_layout_sparse(const JpegImage& J, size_t* off, JpegDevLayout* L) {
-  auto take = [&](size_t bytes) { const size_t at = *off; *off += (bytes + 255) & ~static_cast<size_t>(255); return at; };
+  auto take = [&](size_t bytes) { const size_t at = *off; *off += round256(bytes); return at; };
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
     if (!C.sparse) continue;
@@ -641,7 +512,7 @@ int ist_jpeg_decode_rgba8(ist_ctx* ctx, const uint8_t* file, int64_t len, uint8_
   DeviceGuard g(ctx->device);
   // one device allocation: coefficients + tables + sample planes + RGBA
   size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~static_cast<size_t>(255); return at; };
+  auto take = [&](size_t bytes) { const size_t at = off; off += round256(bytes); return at; };
   JpegDevLayout L;
   jpeg_layout(J, &off, &L);
   jpeg_layout_sparse(J, &off, &L);                      // (one arena holds both parts here)
@@ -784,8 +655,7 @@ class FileDecoder {
     arena_ = arena; img_ = img; pitch_ = pitch;
     const int rc = ensure_image_lanes(ctx_, n_);
     if (rc) return rc;
-    if (!ctx_->workers) ctx_->workers.reset(new WorkerPool());
-    ctx_->workers->run(n_, [this](int i) { worker(i); });
+    workers_of(ctx_).run(n_, [this](int i) { worker(i); });
     running_ = true;
     if (!ph_->on) return IST_OK;
     // phase timing: the steps one after the other
@@ -1102,12 +972,12 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
   std::vector<ist_op> ops;
   rc = plan_with_ops(descs.data(), n, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
-  struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist_plan_free(p); } } pg{out_plan};
+  PlanGuard pg{out_plan};
   const int n_ops = static_cast<int>(ops.size());
 
   // one device arena (the context's, grow-only): bitmaps, JPEG coefficient planes + sample planes, canvas, PNG
   size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~static_cast<size_t>(255); return at; };
+  auto take = [&](size_t bytes) { const size_t at = off; off += round256(bytes); return at; };
   std::vector<size_t> o_img(static_cast<size_t>(n));
   for (int i = 0; i < n; ++i) o_img[static_cast<size_t>(i)] = take(static_cast<size_t>(fd.dec(i).w) * 4 * fd.dec(i).h + 16);
   fd.layout(&off);
@@ -1319,11 +1189,11 @@ int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, i
   };
   if (n_images == 1) read_one(0);
   else {
-    if (!ctx->workers) ctx->workers.reset(new WorkerPool());
+    WorkerPool& workers = workers_of(ctx);
     tl_mark("paths: files opened");
-    ctx->workers->run(n_images, read_one);
+    workers.run(n_images, read_one);
     tl_mark("paths: read tasks handed out");
-    ctx->workers->wait();
+    workers.wait();
     tl_mark("paths: files read");
   }
   for (size_t i = 0; i < n; ++i) {
@@ -1331,253 +1201,6 @@ int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, i
     if (bad[i]) return fail(IST_E_DECODE, "图片" + std::to_string(i) + "解码异常: the file changed while it was read");
   }
   return stitch_files_png_locked(ctx, ptr.data(), lens.data(), n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len);
-}
-
-// PNG of host pixels (H2D, encode, D2H)
-int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int64_t w, int64_t h, uint8_t** out_png,
-                         int64_t* out_len) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!pixels || !out_png || !out_len || w < 1 || h < 1 || pitch < static_cast<size_t>(w) * 4) return fail(IST_E_INVALID, "ist_png_encode_rgba8: bad argument");
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  const size_t row = static_cast<size_t>(w) * 4;
-  int rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, row * static_cast<size_t>(h));
-  if (rc) return rc;
-  std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
-  rc = stager_of(ctx).upload(up, ctx->stream);
-  if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst, row, w, h, nullptr, out_png, out_len);
-}
-
-// The host paths with both directions of PCIe busy (round 4).  The canvas is cut into row bands (ist_shard_row_cuts: ~40 MB each, cuts on
-// multiples of 8 rows); band b is the whole op list clipped to its rows, and ist_shard_parts (IST_SPLIT_ROWS) names the source rows it
-// samples.  Band by band: the rows not yet on the device go up in 32 MiB pieces on the staging stream (Stager::upload_big), the band is
-// launched behind them, and - ist_stitch_rgba8 - its rows go down into the pinned result on the aux stream while the next band's sources go
-// up, or - ist_render_png / ist_stitch_png - the PNG encoder compresses it and sends its slabs down meanwhile.  Any layout shards this way: a
-// vertical strip (index.js:1522-1538) sends image after image, a horizontal one (1540-1553) a slice of every image per band.  Upload-all,
-// launch, download-all costs 8.1 + 7.5 ms for nine 12 MP images; overlapped the two directions hold 48 GB/s each (tools/exp/duplex2.cpp).
-// An earlier banded attempt (round 2) sent the uploads as 4 MiB chunks on four streams, which collapses to 12.7 GB/s each way as soon as
-// downloads are in flight (tools/exp/duplex.cpp) - the piece size was the problem, not the idea.
-extern "C++" {
-namespace {
-struct RowBands {
-  ist_ctx* ctx = nullptr;
-  bool ok = false;                        // false after prepare(): not applicable (a small canvas, an op list the row cut refuses); nothing was queued
-  int nb = 0, n_images = 0;
-  int64_t cw = 0, ch = 0;
-  size_t row = 0, total = 0;
-  const ist_image_desc* images = nullptr;
-  const uint8_t* const* src = nullptr;
-  const size_t* src_pitch = nullptr;
-  std::vector<int32_t> cuts;
-  std::vector<std::map<int, RowSpan>> need;   // per band: the rows of every image it samples
-  std::vector<JobPtr> jobs;
-  std::vector<const void*> dsrc;
-  std::vector<size_t> dpitch;
-  std::vector<int64_t> lo, hi;            // rows of image i already sent: [lo, hi)
-  std::vector<RowsCopy> items;
-  uint8_t* canvas = nullptr;
-  size_t bw(int i) const { return static_cast<size_t>(images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width); }
-  int64_t bh(int i) const { return static_cast<int64_t>(images[i].bmp_height > 0 ? images[i].bmp_height : images[i].height); }
-  int64_t y0(int b) const { return cuts[static_cast<size_t>(b)]; }
-  int64_t y1(int b) const { return cuts[static_cast<size_t>(b) + 1]; }
-
-  int prepare(ist_ctx* c, int64_t canvas_w, int64_t canvas_h, const uint8_t clear[4], const ist_op* ops, int n_ops, const ist_image_desc* imgs,
-              const uint8_t* const* s, const size_t* sp, int n, int filter) {
-    static const bool off = tuning_mode() && std::getenv("IST_HOST_DUPLEX") && std::atoi(std::getenv("IST_HOST_DUPLEX")) == 0;
-    ctx = c; cw = canvas_w; ch = canvas_h; images = imgs; src = s; src_pitch = sp; n_images = n;
-    row = static_cast<size_t>(cw) * 4; total = row * static_cast<size_t>(ch);
-    if (off || total < (32u << 20) || n_images < 1) return IST_OK;
-    nb = static_cast<int>(std::min<size_t>(16, std::max<size_t>(2, total / (40u << 20))));
-    cuts.assign(static_cast<size_t>(nb) + 1, 0);
-    std::vector<ist_part> parts(static_cast<size_t>(std::max(1, n_ops)) * static_cast<size_t>(nb) + 8);
-    int n_parts = 0;
-    {
-      KeepLastError keep;                                        // not an error of the call: the one-shot path takes it
-      if (ist_shard_row_cuts(ch, nb, cuts.data()) != IST_OK ||
-          ist_shard_parts(ops, n_ops, cw, ch, images, n_images, filter, nb, IST_SPLIT_ROWS, parts.data(), static_cast<int>(parts.size()), &n_parts) != IST_OK)
-        return IST_OK;
-    }
-    parts.resize(static_cast<size_t>(n_parts));
-    // every band compiles the WHOLE op list, clipped to its rows: the flat form looks at every op, so a shorter list could change the band's kernel
-    jobs.resize(static_cast<size_t>(nb)); need.resize(static_cast<size_t>(nb));
-    for (int b = 0; b < nb; ++b) {
-      need[static_cast<size_t>(b)] = shard_holdings(parts_of_slot(parts, b));
-      if (y0(b) >= y1(b)) continue;
-      const ist_region clip{0, static_cast<int32_t>(y0(b)), static_cast<int32_t>(cw), static_cast<int32_t>(y1(b) - y0(b))};
-      jobs[static_cast<size_t>(b)].reset(ist_job_create(ctx, cw, ch, clear, ops, n_ops, images, n_images, filter, &clip));
-      if (!jobs[static_cast<size_t>(b)]) return g_last_code ? g_last_code : IST_E_INVALID;
-    }
-    // device scratch: the images the bands draw (whole allocations, filled row range by row range), and the canvas
-    std::vector<size_t> at(static_cast<size_t>(n_images), 0);
-    std::vector<char> used(static_cast<size_t>(n_images), 0);
-    lo.assign(static_cast<size_t>(n_images), -1); hi.assign(static_cast<size_t>(n_images), -1);
-    for (const auto& band : need) for (const auto& kv : band) if (kv.first >= 0 && kv.first < n_images) used[static_cast<size_t>(kv.first)] = 1;
-    size_t src_bytes = 0;
-    for (int i = 0; i < n_images; ++i) {
-      if (!used[static_cast<size_t>(i)]) continue;
-      if (!src || !src[i] || bw(i) < 1 || bh(i) < 1) return fail(IST_E_DECODE, "图片" + std::to_string(i) + "解码异常");
-      if (src_pitch && src_pitch[i] < bw(i) * 4) return fail(IST_E_INVALID, "src_pitch too small");
-      at[static_cast<size_t>(i)] = src_bytes;
-      src_bytes += (bw(i) * 4 * static_cast<size_t>(bh(i)) + 255 + 256) & ~static_cast<size_t>(255);       // (+ a vector load's reach past the last row sent)
-    }
-    int rc = grow_device(&ctx->scratch_src, &ctx->scratch_src_bytes, src_bytes ? src_bytes : 256);
-    if (rc) return rc;
-    rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, total);
-    if (rc) return rc;
-    if (!ctx->workers) ctx->workers.reset(new WorkerPool());
-    dsrc.assign(static_cast<size_t>(n_images), nullptr);
-    dpitch.assign(static_cast<size_t>(n_images), 0);
-    for (int i = 0; i < n_images; ++i)
-      if (used[static_cast<size_t>(i)]) { dsrc[static_cast<size_t>(i)] = static_cast<uint8_t*>(ctx->scratch_src) + at[static_cast<size_t>(i)]; dpitch[static_cast<size_t>(i)] = bw(i) * 4; }
-    canvas = static_cast<uint8_t*>(ctx->scratch_dst);
-    ok = true;
-    return IST_OK;
-  }
-
-  // sends what band b still needs and launches it, all ordered on R
-  int submit(int b, hipStream_t R) {
-    items.clear();
-    auto send = [&](int i, int64_t r0, int64_t r1) {            // rows [r0, r1) of image i
-      if (r1 <= r0) return;
-      const size_t hp = src_pitch ? src_pitch[i] : bw(i) * 4;
-      items.push_back(RowsCopy{static_cast<uint8_t*>(const_cast<void*>(dsrc[static_cast<size_t>(i)])) + static_cast<size_t>(r0) * bw(i) * 4,
-                               src[i] + static_cast<size_t>(r0) * hp, nullptr, hp, bw(i) * 4, static_cast<size_t>(r1 - r0)});
-    };
-    for (const auto& kv : need[static_cast<size_t>(b)]) {
-      const int i = kv.first;
-      const int64_t a = std::max<int64_t>(0, kv.second.y0), e = std::min<int64_t>(bh(i), kv.second.y1);
-      if (e <= a) continue;
-      int64_t& L0 = lo[static_cast<size_t>(i)]; int64_t& H0 = hi[static_cast<size_t>(i)];
-      if (L0 < 0) { send(i, a, e); L0 = a; H0 = e; }
-      else {                                                     // keep ONE interval per image: a band further down extends it (rows between are sent too)
-        if (a < L0) { send(i, a, L0); L0 = a; }
-        if (e > H0) { send(i, H0, e); H0 = e; }
-      }
-    }
-    if (!items.empty()) { const int rc = stager_of(ctx).upload_big(items, R, ctx->workers.get()); if (rc) return rc; }
-    return ist_job_launch(jobs[static_cast<size_t>(b)].get(), dsrc.data(), dpitch.data(), n_images, canvas, row, R);
-  }
-};
-}  // namespace
-}  // extern "C++"
-
-// *done = false: not applicable, nothing was queued and the caller takes the one-shot path.
-static int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, int n_ops, const ist_image_desc* images,
-                                const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter, uint8_t** out_pixels, bool* done) {
-  *done = false;
-  static const bool print = std::getenv("IST_TIMING") != nullptr;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) { if (print) std::fprintf(stderr, "[ist timing] host stitch: %-34s at %7.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); };
-  RowBands rb;
-  int rc = rb.prepare(ctx, plan->canvas_w, plan->canvas_h, kTransparent, ops, n_ops, images, src, src_pitch, n_images, filter);
-  if (rc) return rc;
-  if (!rb.ok) return IST_OK;
-  rc = ensure_aux(ctx);
-  if (rc) return rc;
-  lap("band jobs compiled, scratch");
-  uint8_t* host = static_cast<uint8_t*>(pool_take(rb.total));
-  if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the result");
-  std::vector<hipEvent_t> ev(static_cast<size_t>(rb.nb), nullptr);
-  hipStream_t R = ctx->stream, D = ctx->aux;
-  // (whatever happens below, the streams are idle before the pinned block or the jobs' tables are given back)
-  auto finish = [&](int code) {
-    (void)hipStreamSynchronize(R); (void)hipStreamSynchronize(D); (void)stager_of(ctx).sync();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (code != IST_OK) pool_give(host);
-    return code;
-  };
-  bool first = true;
-  for (int b = 0; b < rb.nb; ++b) {
-    const int64_t y0 = rb.y0(b), y1 = rb.y1(b);
-    if (y0 >= y1) continue;
-    rc = rb.submit(b, R);
-    if (rc) return finish(rc);
-    hipEvent_t& e = ev[static_cast<size_t>(b)];
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, R) != hipSuccess || hipStreamWaitEvent(D, e, 0) != hipSuccess ||
-        hipMemcpyAsync(host + static_cast<size_t>(y0) * rb.row, rb.canvas + static_cast<size_t>(y0) * rb.row, static_cast<size_t>(y1 - y0) * rb.row, hipMemcpyDeviceToHost, D) != hipSuccess) {
-      (void)hipGetLastError();
-      return finish(fail(IST_E_HIP, "queueing a band's readback failed"));
-    }
-    if (first) { lap("first band queued"); first = false; }
-  }
-  lap("last band queued");
-  if (hipStreamSynchronize(D) != hipSuccess || hipStreamSynchronize(R) != hipSuccess) { (void)hipGetLastError(); return finish(fail(IST_E_HIP, "result readback failed")); }
-  lap("last band in host memory");
-  g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
-  *out_pixels = host;
-  *done = true;
-  return finish(IST_OK);
-}
-
-static int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
-                             const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
-                             uint8_t** out_png, int64_t* out_len) {
-  RowBands rb;
-  int rc = rb.prepare(ctx, canvas_w, canvas_h, clear_rgba ? clear_rgba : kTransparent, ops, n_ops, images, src, src_pitch, n_images, filter);
-  if (rc) return rc;
-  if (!rb.ok) return 1;
-  rc = ensure_render(ctx);
-  if (rc) return rc;
-  hipStream_t R = ctx->render;
-  std::vector<hipEvent_t> ev(static_cast<size_t>(rb.nb), nullptr);
-  int next = 0;
-  // the encoder is about to read canvas rows [0, y_end) on `reader`: submit the bands they lie in, order the reader behind the last of them
-  auto need_rows = [&](int64_t y_end, void* reader_) -> int {
-    hipStream_t reader = static_cast<hipStream_t>(reader_);
-    int last = -1;
-    for (int b = 0; b < rb.nb; ++b) {
-      if (rb.y0(b) >= rb.y1(b)) continue;
-      if (rb.y0(b) >= y_end) break;
-      if (b >= next) {
-        const int rc2 = rb.submit(b, R);
-        if (rc2) return rc2;
-        if (hipEventCreateWithFlags(&ev[static_cast<size_t>(b)], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[static_cast<size_t>(b)], R) != hipSuccess) {
-          (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed");
-        }
-        next = b + 1;
-      }
-      last = b;
-    }
-    if (last >= 0 && hipStreamWaitEvent(reader, ev[static_cast<size_t>(last)], 0) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "ordering the export behind the render failed"); }
-    return IST_OK;
-  };
-  int64_t hint = 0;
-  for (int b = 0; b < rb.nb; ++b) hint = std::max<int64_t>(hint, rb.y1(b) - rb.y0(b));
-  rc = png_to_host(ctx, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint);
-  (void)hipStreamSynchronize(R); (void)stager_of(ctx).sync(); (void)hipStreamSynchronize(ctx->stream);
-  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  if (rc == IST_OK) g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-int64_t ist_debug_duplex_stitches(void) { return g_duplex_stitches.load(); }
-
-int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
-                     int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter,
-                     ist_plan* out_plan, uint8_t** out_pixels) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!out_plan || !out_pixels) return fail(IST_E_INVALID, "ist_stitch_rgba8: NULL output");
-  *out_pixels = nullptr;
-  std::vector<ist_op> ops;
-  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
-  if (rc != IST_OK) return rc;
-  const int n_ops = static_cast<int>(ops.size());
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard g(ctx->device);
-    bool done = false;
-    rc = stitch_banded_duplex(ctx, out_plan, ops.data(), n_ops, images, src, src_pitch, n_images, filter, out_pixels, &done);
-    if (rc == IST_OK && !done) {
-      rc = render_to_scratch(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), n_ops, images, src, src_pitch,
-                             n_images, filter, nullptr, nullptr, nullptr);
-      // the export (index.js:1577-1579): the whole canvas in one DMA into a pinned block of the pool
-      if (rc == IST_OK)
-        rc = read_back_pooled(ctx->scratch_dst, static_cast<size_t>(out_plan->canvas_w) * 4 * static_cast<size_t>(out_plan->canvas_h), ctx->stream, out_pixels);
-    }
-  }
-  if (rc != IST_OK) { ist_plan_free(out_plan); return rc; }
-  return IST_OK;
 }
 
 // buffers handed out by the library: pinned blocks go back to the pool, anything else was malloc'ed

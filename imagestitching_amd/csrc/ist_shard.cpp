@@ -146,8 +146,8 @@ extern "C" int ist_shard_parts(const ist_op* ops, int n_ops, int64_t canvas_w, i
     if (ops[k].kind != IST_OP_DRAW) continue;
     const int i = ops[k].image;
     if (i < 0 || i >= n_images) return fail(IST_E_INVALID, "op refers to a missing image");
-    const int iw = images[i].bmp_width > 0 ? images[i].bmp_width : images[i].width;
-    const int ih = images[i].bmp_height > 0 ? images[i].bmp_height : images[i].height;
+    const int iw = static_cast<int>(bitmap_w(images[i]));
+    const int ih = static_cast<int>(bitmap_h(images[i]));
     if (iw < 1 || ih < 1) return fail(IST_E_DECODE, "图片" + std::to_string(i) + "解码异常");
     Draw d; d.op = k;
     const int rc = resolve_op(ops[k], canvas_w, canvas_h, iw, ih, &d.r, aa);
