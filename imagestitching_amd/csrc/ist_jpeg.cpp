@@ -8,9 +8,13 @@
 // Split for the hardware: entropy decoding is a serial bit stream (host, this file); everything after it — dequantise,
 // 8x8 inverse DCT, chroma upsampling, YCbCr->RGB — is independent per block / per pixel and runs on the GPU
 // (ist_jpeg_kernels.hip) on the coefficient planes this file produces.
-// Supported: SOF0 / SOF1, 8-bit, 1 or 3 components, any sampling factors h,v in {1,2} with luma >= chroma, interleaved
-// and non-interleaved scans, restart intervals; progressive (SOF2: DC/AC first and refinement scans, EOB runs) into dense
-// coefficient planes.  Arithmetic coding, lossless, 12-bit, CMYK: IST_E_UNSUPPORTED.
+// Supported: SOF0 / SOF1, 8-bit, 1 or 3 components; colour files with the first component sampled 1x1, 2x1, 1x2 or 2x2
+// and the other two 1x1 (4:4:4, 4:2:2, 4:4:0, 4:2:0; a lone component is 1x1 whatever its header says); YCbCr or RGB
+// (libjpeg's rule: a JFIF marker means YCbCr, else an Adobe marker's transform 0 means RGB and 1 YCbCr, else component
+// IDs 'R', 'G', 'B' mean RGB, else YCbCr); interleaved and non-interleaved scans in any order, tables defined or redefined
+// between scans (a component's quantisation table is the one in force when its first scan starts), restart intervals;
+// progressive (SOF2: DC/AC first and refinement scans, EOB runs) into dense coefficient planes.  Other sampling layouts
+// (4:1:1, chroma planes larger than 1x1), arithmetic coding, lossless, 12-bit, CMYK: IST_E_UNSUPPORTED.
 // Exactly ONE frame header per file (a second SOF is JERR_SOF_DUPLICATE in libjpeg): every buffer below is sized from it.
 #include <cstdlib>
 #include <cstring>
@@ -159,6 +163,23 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
   uint16_t qt[4][64]; bool have_q[4] = {false, false, false, false};
   int restart_interval = 0;
   bool have_sof = false, progressive = false;
+  bool jfif = false, adobe = false, latched[3] = {false, false, false};
+  int adobe_transform = 0;
+  // a component's quantisation table is fixed when its first scan starts (libjpeg's latch_quant_tables): a DQT between
+  // scans may (re)define slots for the components still to come without touching the ones already decoded
+  auto colour_space = [&]() {       // decided at the frame header and again at the first scan (as libjpeg does)
+    if (J->ncomp != 3) return;
+    if (jfif) J->rgb = false;
+    else if (adobe) J->rgb = adobe_transform == 0;
+    else J->rgb = J->comp[0].id == 'R' && J->comp[1].id == 'G' && J->comp[2].id == 'B';
+  };
+  auto latch = [&](int c) -> bool {
+    if (latched[c]) return true;
+    if (!have_q[J->comp[c].tq]) return false;
+    std::memcpy(J->comp[c].q, qt[J->comp[c].tq], sizeof J->comp[c].q);
+    latched[c] = true;
+    return true;
+  };
   int64_t pos = 2;
   *J = JpegImage();
   while (pos + 4 <= n) {
@@ -171,6 +192,8 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
     if (len < 2 || pos + 2 + len > n) return fail(IST_E_DECODE, "truncated JPEG segment");
     const uint8_t* d = f + pos + 4; const int64_t dl = len - 2;
     if (m == 0xE1 && J->orientation == 0) J->orientation = exif_orientation(d, static_cast<size_t>(dl));
+    else if (m == 0xE0 && dl >= 14 && std::memcmp(d, "JFIF\0", 5) == 0) jfif = true;
+    else if (m == 0xEE && dl >= 12 && std::memcmp(d, "Adobe", 5) == 0) { adobe = true; adobe_transform = d[11]; }
     else if (m == 0xDB) {                                           // DQT
       int64_t o = 0;
       while (o < dl) {
@@ -216,6 +239,7 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
       if (J->ncomp == 3 && (J->comp[1].h != 1 || J->comp[1].v != 1 || J->comp[2].h != 1 || J->comp[2].v != 1))
         return fail(IST_E_UNSUPPORTED, "unusual JPEG sampling layout (chroma must be 1x1)");
       if (J->ncomp == 1) { J->comp[0].h = J->comp[0].v = 1; hmax = vmax = 1; }
+      colour_space();
       J->hmax = hmax; J->vmax = vmax;
       J->mcus_x = (J->width + 8 * hmax - 1) / (8 * hmax); J->mcus_y = (J->height + 8 * vmax - 1) / (8 * vmax);
       for (int c = 0; c < J->ncomp; ++c) {
@@ -227,6 +251,7 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
     } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) return fail(IST_E_UNSUPPORTED, "this JPEG process (lossless / arithmetic) is not supported");
     else if (m == 0xDA) {                                           // SOS
       if (!have_sof) return fail(IST_E_DECODE, "JPEG scan before frame header");
+      if (J->scans == 0) colour_space();
       if (dl < 1) return fail(IST_E_DECODE, "bad JPEG scan header");
       const int ns = d[0];
       if (ns < 1 || ns > J->ncomp || dl < 1 + 2 * ns + 3) return fail(IST_E_DECODE, "bad JPEG scan header");
@@ -262,10 +287,8 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
       }
       if (gs && !progressive && J->scans == 0 && ns == J->ncomp && two_tables && mcu_blocks <= 10 &&      // (T.81 B.2.3: at most 10 blocks per MCU)
           (f + n) - (d + dl) < (1ll << 28)) {      // (32-bit bit positions on the GPU)
-        for (int c = 0; c < J->ncomp; ++c) {
-          if (!have_q[J->comp[c].tq]) return fail(IST_E_DECODE, "JPEG component uses an undefined quantisation table");
-          std::memcpy(J->comp[c].q, qt[J->comp[c].tq], sizeof J->comp[c].q);
-        }
+        for (int c = 0; c < J->ncomp; ++c)
+          if (!latch(c)) return fail(IST_E_DECODE, "JPEG component uses an undefined quantisation table");
         gs->slots = 0;
         for (int s2 = 0; s2 < ns; ++s2) {
           const JpegComp& C = J->comp[ci[s2]];
@@ -378,11 +401,11 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
         }
         gs->stream.clear(); gs->iv.clear();
       }
-      // allocate coefficient planes on first use; copy the quantisation tables in use
+      // latch the quantisation tables of this scan's components; allocate coefficient planes on first use
+      for (int s = 0; s < ns; ++s)
+        if (!latch(ci[s])) return fail(IST_E_DECODE, "JPEG component uses an undefined quantisation table");
       for (int c = 0; c < J->ncomp; ++c) {
         JpegComp& C = J->comp[c];
-        if (!have_q[C.tq]) return fail(IST_E_DECODE, "JPEG component uses an undefined quantisation table");
-        std::memcpy(C.q, qt[C.tq], sizeof C.q);
         const size_t nblk = static_cast<size_t>(C.blocks_x) * C.blocks_y;
         if (progressive) {
           if (C.coef.empty() && !C.coef.alloc_zero(nblk * 64)) return fail(IST_E_NOMEM, "out of memory for the JPEG coefficients");
@@ -532,6 +555,8 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
   }
   if (!have_sof) return fail(IST_E_DECODE, "JPEG without a frame header");
   if (!header_only && J->scans == 0) return fail(IST_E_DECODE, "JPEG without image data");
+  // a component no scan named has no coefficients: a zero table (libjpeg leaves its dequantisation table zero)
+  for (int c = 0; c < J->ncomp; ++c) if (!latched[c]) std::memset(J->comp[c].q, 0, sizeof J->comp[c].q);
   return IST_OK;
 }
 

@@ -50,6 +50,7 @@ struct JpegImage {
   int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0;
   int orientation = 0;                 // EXIF 1..8, 0 = absent
   int scans = 0;
+  bool rgb = false;                    // three components that hold R, G, B (no colour conversion): libjpeg's rule, see ist_jpeg.cpp
   JpegComp comp[3];
 };
 
@@ -133,6 +134,7 @@ struct JpegDeviceJob {
   const int16_t* d_coef[3];
   const uint16_t* q_host[3];           // quantisation tables (HOST memory, natural order): passed by value to the kernel
   uint8_t* d_plane[3];                 // blocks_x*8 bytes per row (chroma only: the luma plane stays in LDS)
+  bool rgb = false;                    // components 0, 1, 2 are R, G, B: upsampled like chroma, not colour-converted
   uint8_t* out; size_t out_pitch;
   bool chroma_done = false;            // jpeg_launch_chroma_idct has already made d_plane[1], d_plane[2] on this stream
 };

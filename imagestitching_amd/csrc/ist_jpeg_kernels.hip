@@ -170,11 +170,13 @@ __device__ __forceinline__ uint32_t ycc_to_rgba(int Yv, int cb, int cr) {
 constexpr bool kFusedHalfTiles = false;   // 16 instead of 32 luma blocks per workgroup of the fused kernel (IST_JPEG_NB=16|32 overrides in tuning mode)
 constexpr int kChromaRows = 10;                                      // chroma tile rows j0-1 .. j0+8; its columns start at i0-4 (dword aligned origin)
 
-template <int HS, int VS, int CP>
+// BOX: replicate instead of blending (libjpeg-turbo's h2v1 / h2v2 upsampling of a plane at most 2 samples wide)
+template <int HS, int VS, int CP, bool BOX>
 __device__ __forceinline__ int chroma_lds(const uint8_t* T, int cw, int i_org, int j_org, int x, int y) {
   // T[(j - j_org) * CP + (i - i_org)]: rows are clamped at load time, columns here
   auto at = [&](int j, int i) { return static_cast<int>(T[(j - j_org) * CP + (clampi(i, 0, cw - 1) - i_org)]); };
   if (HS == 1 && VS == 1) return at(y, x);
+  if (BOX) return at(y / VS, x / HS);
   if (HS == 2 && VS == 1) {                       // h2v1: 3/4 nearer + 1/4 further column
     const int i = x >> 1;
     if (x & 1) return i == cw - 1 ? at(y, i) : (3 * at(y, i) + at(y, i + 1) + 2) >> 2;
@@ -193,7 +195,9 @@ __device__ __forceinline__ int chroma_lds(const uint8_t* T, int cw, int i_org, i
 }
 
 // NB = luma blocks per workgroup (8 lanes each): 32 (256 threads) or 16 (128 threads, half as wide a tile).
-template <int HS, int VS, bool COLOUR, int NB>
+// RGB: the three planes are R, G, B (no colour conversion); BOX: replicated chroma (see chroma_lds).  Both only take the
+// general per-pixel path below: the 4:2:0 photo path is the <2, 2, true, NB, false, false> instantiation alone.
+template <int HS, int VS, bool COLOUR, int NB, bool RGB = false, bool BOX = false>
 __global__ __launch_bounds__(NB * 8) void ist_jpeg_fused_kernel(const ColorArgs A) {
   constexpr int NT = NB * 8;                                             // threads
   constexpr int TW = NB * 8 / VS, TH = 8 * VS, YP = TW + 16;             // tile; bytes per luma tile row: 16 mod 128 keeps the row writes of step 3 off each other's banks
@@ -243,7 +247,7 @@ __global__ __launch_bounds__(NB * 8) void ist_jpeg_fused_kernel(const ColorArgs 
   }
   __syncthreads();
   if (A.exp & 4) { if (t == 0 && Ys[5] == 77 && Cs[3] == 99) A.out[0] = 1; return; }
-  if (COLOUR && HS == 2 && VS == 2) {
+  if (COLOUR && HS == 2 && VS == 2 && !RGB && !BOX) {
     // 4:2:0, the photo case: a thread converts 4 pixels x 2 rows (the rows 2j, 2j+1 that share chroma row j): per plane ONE
     // two-dword LDS read per chroma row j-1, j, j+1 gives the four columns i-1 .. i+2 the eight pixels blend; the vertical 3:1 and the
     // horizontal 3:1 run on pairs of 16-bit lanes in 32-bit registers (every term < 4096), the colour conversion on 24-bit
@@ -321,9 +325,10 @@ __global__ __launch_bounds__(NB * 8) void ist_jpeg_fused_kernel(const ColorArgs 
       const int Yv = static_cast<int>((yy >> (8 * k)) & 255u);
       if (COLOUR) {
         const int x = min(x0 + k, A.width - 1);
-        const int cb = chroma_lds<HS, VS, CP>(Cs, A.cw, i_org, j_org, x, y) - 128;
-        const int cr = chroma_lds<HS, VS, CP>(Cs + kChromaRows * CP, A.cw, i_org, j_org, x, y) - 128;
-        px[k] = ycc_to_rgba(Yv, cb, cr);
+        const int cb = chroma_lds<HS, VS, CP, BOX>(Cs, A.cw, i_org, j_org, x, y);
+        const int cr = chroma_lds<HS, VS, CP, BOX>(Cs + kChromaRows * CP, A.cw, i_org, j_org, x, y);
+        if (RGB) px[k] = static_cast<uint32_t>(Yv) | (static_cast<uint32_t>(cb) << 8) | (static_cast<uint32_t>(cr) << 16) | 0xFF000000u;
+        else px[k] = ycc_to_rgba(Yv, cb - 128, cr - 128);
       } else {
         px[k] = static_cast<uint32_t>(Yv) * 0x010101u | 0xFF000000u;
       }
@@ -404,11 +409,20 @@ int jpeg_launch_reconstruct(const JpegDeviceJob& J, void* stream_) {
   const int tw = nb * 8 / J.vmax, th = 8 * J.vmax;
   const dim3 grid(static_cast<unsigned>((J.blocks_x[0] * 8 + tw - 1) / tw), static_cast<unsigned>((J.blocks_y[0] * 8 + th - 1) / th));
   if (grid.x > 0 && grid.y > 0) {
-#define IST_FUSED(HS, VS, C) do { if (half) hipLaunchKernelGGL((ist_jpeg_fused_kernel<HS, VS, C, 16>), grid, dim3(128), 0, stream, ca); \
-                                  else hipLaunchKernelGGL((ist_jpeg_fused_kernel<HS, VS, C, 32>), grid, dim3(256), 0, stream, ca); } while (0)
+#define IST_FUSED(HS, VS, C, ...) do { if (half) hipLaunchKernelGGL((ist_jpeg_fused_kernel<HS, VS, C, 16, ##__VA_ARGS__>), grid, dim3(128), 0, stream, ca); \
+                                       else hipLaunchKernelGGL((ist_jpeg_fused_kernel<HS, VS, C, 32, ##__VA_ARGS__>), grid, dim3(256), 0, stream, ca); } while (0)
+    // libjpeg-turbo blends h2v1 / h2v2 chroma only when the plane is more than 2 samples wide (jdsample.c), else replicates
+    // it; h1v2 always blends.  Narrow files and RGB files have kernels of their own, so the YCbCr ones keep their code.
+    const bool box = J.hmax == 2 && ca.cw <= 2;
     if (J.ncomp != 3) IST_FUSED(1, 1, false);
-    else if (J.hmax == 2 && J.vmax == 2) IST_FUSED(2, 2, true);
-    else if (J.hmax == 2) IST_FUSED(2, 1, true);
+    else if (J.rgb) {
+      if (J.hmax == 2 && J.vmax == 2) { if (box) IST_FUSED(2, 2, true, true, true); else IST_FUSED(2, 2, true, true, false); }
+      else if (J.hmax == 2) { if (box) IST_FUSED(2, 1, true, true, true); else IST_FUSED(2, 1, true, true, false); }
+      else if (J.vmax == 2) IST_FUSED(1, 2, true, true, false);
+      else IST_FUSED(1, 1, true, true, false);
+    }
+    else if (J.hmax == 2 && J.vmax == 2) { if (box) IST_FUSED(2, 2, true, false, true); else IST_FUSED(2, 2, true); }
+    else if (J.hmax == 2) { if (box) IST_FUSED(2, 1, true, false, true); else IST_FUSED(2, 1, true); }
     else if (J.vmax == 2) IST_FUSED(1, 2, true);
     else IST_FUSED(1, 1, true);
 #undef IST_FUSED

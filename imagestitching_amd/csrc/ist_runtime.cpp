@@ -451,7 +451,7 @@ void jpeg_layout_sparse(const JpegImage& J, size_t* off, JpegDevLayout* L) {
 // what the reconstruction kernels need to know of an image whose coefficient planes are (or will be) in the arena at L
 JpegDeviceJob jpeg_device_job(const JpegImage& J, uint8_t* d, const JpegDevLayout& L, uint8_t* d_out, size_t out_pitch) {
   JpegDeviceJob job;
-  job.width = J.width; job.height = J.height; job.ncomp = J.ncomp; job.hmax = J.hmax; job.vmax = J.vmax;
+  job.width = J.width; job.height = J.height; job.ncomp = J.ncomp; job.hmax = J.hmax; job.vmax = J.vmax; job.rgb = J.rgb;
   for (int c = 0; c < 3; ++c) { job.d_coef[c] = nullptr; job.q_host[c] = nullptr; job.d_plane[c] = nullptr; job.h[c] = job.v[c] = 1; job.blocks_x[c] = job.blocks_y[c] = 0; }
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
