@@ -173,6 +173,17 @@ SYMBOLS = [
     ("ist_stitch_png", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
                                  C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int, C.POINTER(Plan),
                                  C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_bitmap_upload", C.c_void_p, [C.c_void_p, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t]),
+    ("ist_bitmaps_decode", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_void_p)]),
+    ("ist_bitmap_desc", C.c_int, [C.c_void_p, C.POINTER(ImageDesc)]),
+    ("ist_bitmap_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64]),
+    ("ist_bitmap_retain", None, [C.c_void_p]),
+    ("ist_bitmap_release", None, [C.c_void_p]),
+    ("ist_stitch_bitmaps_rgba8", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
+                                           C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8))]),
+    ("ist_stitch_bitmaps_png", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
+                                         C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_debug_bitmap_bytes", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -1,0 +1,211 @@
+// ist_bitmap.cpp — bitmaps the library keeps in HBM between stitches, and the stitch entry points that read them where they are.
+// Reference anchor: the page's bitmap cache (pages/index/index.js:534-627, _getBitmapFromCache / _storeBitmapInCache, used at :1442 and
+// :1515-1517): a user who reorders the photos, changes the gap or the direction and stitches again decodes nothing again.  Here a
+// bitmap is one device block laid out like a staged source (dense rows + kSourceTail, ist_sources.cpp), so a restitch is the fused
+// launch of the host path (ist_host_stitch.cpp, render_to_scratch) with no upload in front of it, plus the readback or the GPU PNG export.
+#include <atomic>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "ist_ctx.h"
+
+using namespace ist;
+
+struct ist_bitmap {
+  std::atomic<int> refs{1};
+  int device = 0;
+  uint8_t* dev = nullptr;                // row 0; rows are 4 * bitmap_w(desc) bytes apart, kSourceTail readable bytes behind the last
+  size_t bytes = 0;                      // the whole block
+  ist_image_desc desc{};
+};
+
+namespace {
+
+std::atomic<int64_t> g_bitmap_bytes{0};
+
+size_t row_of(const ist_image_desc& d) { return static_cast<size_t>(bitmap_w(d)) * 4; }
+
+// a new bitmap with one reference: the block on `device` (the caller has made it current), pixels not yet written
+ist_bitmap* bitmap_alloc(int device, const ist_image_desc& d) {
+  const size_t bytes = round256(row_of(d) * static_cast<size_t>(bitmap_h(d)) + kSourceTail);
+  void* p = nullptr;
+  if (dev_malloc(&p, bytes) != 0) {
+    (void)hipGetLastError();
+    fail(IST_E_NOMEM, "out of device memory for a bitmap (" + std::to_string(bytes >> 20) + " MiB)");
+    return nullptr;
+  }
+  ist_bitmap* b = new ist_bitmap;
+  b->device = device; b->dev = static_cast<uint8_t*>(p); b->bytes = bytes; b->desc = d;
+  g_bitmap_bytes.fetch_add(static_cast<int64_t>(bytes), std::memory_order_relaxed);
+  return b;
+}
+
+// the references one call holds on its bitmaps: taken before anything else, dropped when the call returns
+struct Held {
+  std::vector<ist_bitmap*> b;
+  ~Held() { for (ist_bitmap* x : b) ist_bitmap_release(x); }
+};
+
+// the checks of a stitch call, in this order; on success every bitmap is retained in *held
+int take_bitmaps(const ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, Held* held) {
+  if (!bitmaps) return fail(IST_E_INVALID, "ist_stitch_bitmaps: NULL bitmap table");
+  if (n > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one launch");
+  for (int i = 0; i < n; ++i) {
+    if (!bitmaps[i]) return fail(IST_E_DECODE, "图片" + std::to_string(i) + "解码异常");
+    if (bitmaps[i]->device != ctx->device)
+      return fail(IST_E_INVALID, "bitmap " + std::to_string(i) + " lives on device " + std::to_string(bitmaps[i]->device) + ", the context on device " +
+                                     std::to_string(ctx->device));
+  }
+  held->b.reserve(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) { ist_bitmap_retain(bitmaps[i]); held->b.push_back(bitmaps[i]); }
+  return IST_OK;
+}
+
+// plan + one fused launch from the bitmaps into ctx->scratch_dst (dense canvas rows), then the canvas (want_png = false) or its PNG file
+// into a pooled pinned block.  The launch is the one render_to_scratch makes for the same op list: the sources differ only in where
+// they are, so the pixels are the host path's byte for byte.
+int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits, int filter,
+                   bool want_png, ist_plan* out_plan, uint8_t** out, int64_t* out_len) {
+  Held held;
+  int rc = take_bitmaps(ctx, bitmaps, n, &held);
+  if (rc) return rc;
+  std::vector<ist_image_desc> descs(static_cast<size_t>(n));
+  std::vector<const void*> src(static_cast<size_t>(n));
+  std::vector<size_t> pitch(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    descs[static_cast<size_t>(i)] = bitmaps[i]->desc;
+    src[static_cast<size_t>(i)] = bitmaps[i]->dev;
+    pitch[static_cast<size_t>(i)] = row_of(bitmaps[i]->desc);
+  }
+  std::vector<ist_op> ops;
+  rc = plan_with_ops(descs.data(), n, direction, mode, gap, limits, out_plan, &ops);
+  if (rc != IST_OK) return rc;
+  PlanGuard pg{out_plan};
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
+  const int64_t cw = out_plan->canvas_w, ch = out_plan->canvas_h;
+  const JobPtr job(ist_job_create(ctx, cw, ch, kTransparent, ops.data(), static_cast<int>(ops.size()), descs.data(), n, filter, nullptr));
+  if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
+  const size_t row = static_cast<size_t>(cw) * 4;
+  rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, row * static_cast<size_t>(ch));
+  if (rc) return rc;
+  rc = ist_job_launch(job.get(), src.data(), pitch.data(), n, ctx->scratch_dst, row, ctx->stream);
+  if (rc) return rc;
+  IST_HIP(hipStreamSynchronize(ctx->stream));      // the canvas is complete; the job's tables may go back to the pool
+  if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len);
+  else rc = read_back_pooled(ctx->scratch_dst, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
+  pg.keep = rc == IST_OK;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ist_debug_bitmap_bytes(void) { return g_bitmap_bytes.load(std::memory_order_relaxed); }
+
+ist_bitmap* ist_bitmap_upload(ist_ctx* ctx, const ist_image_desc* desc, const uint8_t* src, size_t src_pitch) {
+  if (!ctx) { fail(IST_E_NO_CONTEXT, "无法获取绘图上下文"); return nullptr; }
+  if (!desc) { fail(IST_E_INVALID, "ist_bitmap_upload: NULL desc"); return nullptr; }
+  // the rules of a staged source (SourceLayout::add)
+  if (!src || bitmap_w(*desc) < 1 || bitmap_h(*desc) < 1) { fail(IST_E_DECODE, "图片0解码异常"); return nullptr; }
+  const size_t row = row_of(*desc);
+  if (src_pitch == 0) src_pitch = row;
+  if (src_pitch < row) { fail(IST_E_INVALID, "src_pitch too small"); return nullptr; }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) { fail(IST_E_NO_DEVICE, "hipSetDevice failed"); return nullptr; }
+  ist_bitmap* b = bitmap_alloc(ctx->device, *desc);
+  if (!b) return nullptr;
+  const std::vector<RowsCopy> up{RowsCopy{b->dev, src, nullptr, src_pitch, row, static_cast<size_t>(bitmap_h(*desc))}};
+  int rc = stager_of(ctx).upload(up, ctx->stream);
+  if (rc == IST_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(IST_E_HIP, "bitmap upload failed"); }
+  if (rc) { ist_bitmap_release(b); return nullptr; }
+  return b;
+}
+
+int ist_bitmaps_decode(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, ist_bitmap** out) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n <= 0) return IST_NOTHING_TO_DO;
+  if (!files || !lens || !out) return fail(IST_E_INVALID, "ist_bitmaps_decode: NULL argument");
+  if (n > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one call");
+  for (int i = 0; i < n; ++i) out[i] = nullptr;
+  std::vector<ist_bitmap*> made;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  const int rc = decode_files_locked(ctx, files, lens, n, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
+    for (int i = 0; i < n; ++i) {
+      ist_bitmap* b = bitmap_alloc(ctx->device, descs[static_cast<size_t>(i)]);
+      if (!b) return g_last_code;
+      made.push_back(b);
+      img[i] = b->dev;
+      pitch[i] = row_of(b->desc);
+    }
+    return IST_OK;
+  });
+  if (rc) {                                        // all or nothing (ctx->stream is idle: nothing writes the blocks any more)
+    KeepLastError keep;
+    for (ist_bitmap* b : made) ist_bitmap_release(b);
+    return rc;
+  }
+  for (int i = 0; i < n; ++i) out[i] = made[static_cast<size_t>(i)];
+  return IST_OK;
+}
+
+int ist_bitmap_desc(const ist_bitmap* b, ist_image_desc* out) {
+  if (!b || !out) return fail(IST_E_INVALID, "ist_bitmap_desc: NULL argument");
+  *out = b->desc;
+  return IST_OK;
+}
+
+int ist_bitmap_download(ist_bitmap* b, uint8_t* dst, size_t dst_pitch, int64_t dst_rows) {
+  if (!b || !dst) return fail(IST_E_INVALID, "ist_bitmap_download: NULL argument");
+  const size_t row = row_of(b->desc);
+  const int64_t rows = bitmap_h(b->desc);
+  if (dst_pitch < row || dst_rows < rows) return fail(IST_E_INVALID, "ist_bitmap_download: the buffer is too small for the bitmap");
+  ist_bitmap_retain(b);
+  Held held{{b}};
+  DeviceGuard g(b->device);
+  if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
+  // (no context here: one synchronous copy on the null stream; every call that writes a bitmap has finished before it returned)
+  IST_HIP(hipMemcpy2D(dst, dst_pitch, b->dev, row, row, static_cast<size_t>(rows), hipMemcpyDeviceToHost));
+  return IST_OK;
+}
+
+void ist_bitmap_retain(ist_bitmap* b) {
+  if (b) b->refs.fetch_add(1, std::memory_order_relaxed);
+}
+
+void ist_bitmap_release(ist_bitmap* b) {
+  if (!b || b->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  {
+    DeviceGuard g(b->device);
+    dev_free(b->dev);
+  }
+  g_bitmap_bytes.fetch_sub(static_cast<int64_t>(b->bytes), std::memory_order_relaxed);
+  delete b;
+}
+
+int ist_stitch_bitmaps_rgba8(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
+                             int filter, ist_plan* out_plan, uint8_t** out_pixels) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out_plan || !out_pixels) return fail(IST_E_INVALID, "ist_stitch_bitmaps_rgba8: NULL output");
+  *out_pixels = nullptr;
+  std::memset(out_plan, 0, sizeof(*out_plan));
+  if (n <= 0) return IST_NOTHING_TO_DO;
+  return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, false, out_plan, out_pixels, nullptr);
+}
+
+int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
+                           int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_bitmaps_png: NULL output");
+  *out_png = nullptr; *out_len = 0;
+  std::memset(out_plan, 0, sizeof(*out_plan));
+  if (n <= 0) return IST_NOTHING_TO_DO;
+  return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, true, out_plan, out_png, out_len);
+}
+
+}  // extern "C"

@@ -144,6 +144,12 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
 // the PNG file of a canvas in device memory -> a pooled pinned block (need_rows / slab_rows_hint: as png_encode_device_deflate)
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
                 const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0);
+// files -> bitmaps in device memory: the decode of ist_decode_files_device and ist_bitmaps_decode (ist_runtime.cpp).  Once every frame
+// header is read, place(descs, img, pitch) is told what each file holds (descs[i]: size, EXIF orientation, opaque, file_size) and
+// fills img[i] / pitch[i] with where bitmap i goes, or fails the call before anything is decoded.  Caller holds ctx->mu; returns
+// with ctx->stream idle.
+int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
+                        const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place);
 
 
 }  // namespace ist

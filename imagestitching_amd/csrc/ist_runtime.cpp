@@ -403,13 +403,19 @@ void ist_job_destroy(ist_job* job) {
     }
     if (job->d_tables) {
       bool kept = false;
+      uint8_t* evicted = nullptr;
       if (idle) {
         std::lock_guard<std::mutex> lk(job->ctx->table_mu);
-        if (static_cast<int>(job->ctx->table_pool.size()) < ist_ctx::kTablePool && job->d_tables_bytes <= (64u << 20)) {
-          job->ctx->table_pool.push_back(ist_ctx::TableBlock{job->d_tables, job->d_tables_bytes});
+        if (job->d_tables_bytes <= (64u << 20)) {
+          // a full pool gives up its OLDEST block for this one, so that a workload that repeats itself (a restitch of the same
+          // layouts) finds the blocks it needs there again instead of allocating on every call behind blocks of earlier work
+          std::vector<ist_ctx::TableBlock>& pool = job->ctx->table_pool;
+          if (static_cast<int>(pool.size()) >= ist_ctx::kTablePool) { evicted = pool.front().p; pool.erase(pool.begin()); }
+          pool.push_back(ist_ctx::TableBlock{job->d_tables, job->d_tables_bytes});
           kept = true;
         }
       }
+      if (evicted) dev_free(evicted);
       if (!kept) dev_free(job->d_tables);
     }
   }
@@ -871,6 +877,39 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
                             double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len);
 
 }  // namespace
+
+namespace ist {
+int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
+                        const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place) {
+  DeviceGuard g(ctx->device);
+  Phases ph(ctx);
+  FileDecoder fd(ctx, files, lens, n, &ph);
+  int rc = fd.headers();
+  if (rc) return rc;
+  // what the planner needs of each file (orientation from the file, like getImageInfo -> index.js:734)
+  std::vector<ist_image_desc> descs(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    const Dec& D = fd.dec(i);
+    ist_image_desc& d = descs[static_cast<size_t>(i)];
+    std::memset(&d, 0, sizeof d);
+    d.width = D.w; d.height = D.h; d.orientation = D.orient ? D.orient : 1; d.opaque = D.jpeg ? 1 : 0; d.file_size = lens[i];
+  }
+  std::vector<uint8_t*> img(static_cast<size_t>(n), nullptr);
+  std::vector<size_t> pitch(static_cast<size_t>(n), 0);
+  rc = place(descs, img.data(), pitch.data());
+  if (rc) return rc;
+  size_t off = 0;
+  fd.layout(&off);
+  rc = grow_device(&ctx->scratch_dec, &ctx->scratch_dec_bytes, off ? off : 256);
+  if (rc) return rc;
+  ph.lap(IST_PHASE_PLAN_ARENA, "device arena", nullptr);
+  rc = fd.start(static_cast<uint8_t*>(ctx->scratch_dec), img.data(), pitch.data());
+  if (rc == IST_OK) rc = fd.finish(ctx->stream);
+  // the bitmaps are complete (or, on a failure, nothing of this call writes them any more); the host coefficients in flight may go
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); if (rc == IST_OK) rc = fail(IST_E_HIP, "hipStreamSynchronize failed"); }
+  return rc;
+}
+}  // namespace ist
 }  // extern "C++"
 
 int ist_ctx_set_timing(ist_ctx* ctx, int on) {
@@ -893,35 +932,18 @@ int ist_decode_files_device(ist_ctx* ctx, const uint8_t* const* files, const int
   if (!files || !lens || !dst || !dst_pitch || !dst_rows) return fail(IST_E_INVALID, "ist_decode_files_device: NULL argument");
   if (n_images > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one call");
   std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  Phases ph(ctx);
-  FileDecoder fd(ctx, files, lens, n_images, &ph);
-  int rc = fd.headers();
-  if (rc) return rc;
-  std::vector<uint8_t*> img(static_cast<size_t>(n_images));
-  for (int i = 0; i < n_images; ++i) {
-    const Dec& D = fd.dec(i);
-    // the file's own header is untrusted: the caller states what its buffer holds
-    if (!dst[i] || dst_pitch[i] < static_cast<size_t>(D.w) * 4 || (dst_pitch[i] & 3) || dst_rows[i] < D.h || (reinterpret_cast<uintptr_t>(dst[i]) & 3))
-      return fail(IST_E_INVALID, "ist_decode_files_device: the buffer of image " + std::to_string(i) + " is too small for " + std::to_string(D.w) + "x" + std::to_string(D.h));
-    img[static_cast<size_t>(i)] = static_cast<uint8_t*>(dst[i]);
-    if (out_descs) {
-      ist_image_desc& d = out_descs[i];
-      std::memset(&d, 0, sizeof d);
-      d.width = D.w; d.height = D.h; d.orientation = D.orient ? D.orient : 1; d.opaque = D.jpeg ? 1 : 0; d.file_size = lens[i];
+  return decode_files_locked(ctx, files, lens, n_images, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
+    for (int i = 0; i < n_images; ++i) {
+      const ist_image_desc& D = descs[static_cast<size_t>(i)];
+      // the file's own header is untrusted: the caller states what its buffer holds
+      if (!dst[i] || dst_pitch[i] < static_cast<size_t>(D.width) * 4 || (dst_pitch[i] & 3) || dst_rows[i] < D.height || (reinterpret_cast<uintptr_t>(dst[i]) & 3))
+        return fail(IST_E_INVALID, "ist_decode_files_device: the buffer of image " + std::to_string(i) + " is too small for " + std::to_string(D.width) + "x" + std::to_string(D.height));
+      img[i] = static_cast<uint8_t*>(dst[i]);
+      pitch[i] = dst_pitch[i];
+      if (out_descs) out_descs[i] = D;
     }
-  }
-  size_t off = 0;
-  fd.layout(&off);
-  rc = grow_device(&ctx->scratch_dec, &ctx->scratch_dec_bytes, off ? off : 256);
-  if (rc) return rc;
-  ph.lap(IST_PHASE_PLAN_ARENA, "device arena", nullptr);
-  rc = fd.start(static_cast<uint8_t*>(ctx->scratch_dec), img.data(), dst_pitch);
-  if (rc) return rc;
-  rc = fd.finish(ctx->stream);
-  if (rc) return rc;
-  IST_HIP(hipStreamSynchronize(ctx->stream));      // the bitmaps are complete; the host coefficients in flight may go
-  return IST_OK;
+    return IST_OK;
+  });
 }
 
 // ---- the whole onStitch for files, device-resident: only file bytes go in and only PNG bytes come out over PCIe -------

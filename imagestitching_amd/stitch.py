@@ -9,6 +9,8 @@ Two ways in:
   Stitcher(device).compile(...)        device-resident: torch CUDA tensors in/out, one fused launch per call
 and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch), stitch_png_batch(requests) (ist_stitch_png_batch),
 launch_jobs(jobs, srcs, outs) (ist_jobs_launch) and encode_png_batch_device(canvases) (ist_png_encode_batch_device).
+Resident bitmaps (ist_bitmap_*): decode_bitmaps(files) / upload_bitmap(image) keep images in HBM, and plan / stitch / stitch_png take
+a list of them in place of host images, so a restitch (reordered, other direction, new gap) uploads and decodes nothing.
 """
 import ctypes as C
 import os
@@ -138,7 +140,7 @@ class StitchPlan:
 def plan(images, direction, opts=None):
     """Pure-CPU planner.  Returns a StitchPlan, or None when there is nothing to stitch (index.js:1189)."""
     o = _merge(opts)
-    descs = _descs(images)
+    descs = _bitmap_descs(images) if _is_bitmap_request(images, o) else _descs(images)
     cplan = L.Plan()
     lim = _limits(o)
     rc = L.check(L.lib.ist_plan_compute(descs, len(images), _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
@@ -193,12 +195,15 @@ def stitch(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) -> {'width', 'height', 'data'}: host arrays through the HIP path.
 
     images[i] = {'width', 'height', 'data': HxWx4 uint8 (RGBA, straight alpha), 'orientation'?: 1..8, 'fileSize'?}
-    or simply an HxWx4 uint8 array.  Returns None when images is empty (the reference returns early).
+    or simply an HxWx4 uint8 array; or a list of Bitmaps (decode_bitmaps / upload_bitmap: nothing is uploaded).  Returns None when
+    images is empty (the reference returns early).
     """
     o = _merge(opts)
     n = len(images)
     if n == 0:
         return None
+    if _is_bitmap_request(images, o):
+        return _stitch_bitmaps(images, n, direction, o, device, False)
     descs = _descs(images)
     keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
     for i, im in enumerate(images):
@@ -252,6 +257,8 @@ def _batch_requests(reqs, why):
         o = _merge(opts)
         if direction not in _DIRECTIONS:
             raise ValueError("request %d: direction must be 'vertical' or 'horizontal'" % k)
+        if any(isinstance(im, Bitmap) for im in images):
+            raise TypeError("request %d: Bitmaps do not apply to a batch (host images only)" % k)
         m = len(images)
         descs = _descs(images)
         ptrs, pitches = (C.c_void_p * max(1, m))(), (C.c_size_t * max(1, m))()
@@ -523,11 +530,13 @@ def encode_png(pixels, device=0, level=None):
 
 def stitch_png(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the reference's export: returns {'width','height','png': bytes}.  The
-    canvas stays on the device; only the PNG crosses PCIe."""
+    canvas stays on the device; only the PNG crosses PCIe.  images may be a list of Bitmaps, as for stitch()."""
     o = _merge(opts)
     n = len(images)
     if n == 0:
         return None
+    if _is_bitmap_request(images, o):
+        return _stitch_bitmaps(images, n, direction, o, device, True)
     descs = _descs(images)
     keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
     for i, im in enumerate(images):
@@ -596,6 +605,146 @@ def encode_png_batch_device(canvases, outs=None, stream=None, level=None):
         dst[k], cap[k] = aligned, o.numel() - (aligned - base)
     L.check(L.lib.ist_png_encode_batch_device(_ctx_png(dev.index or 0, level), src, pitch, w, h, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
     return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(zip(outs, offs))]
+
+
+class Bitmap:
+    """One decoded RGBA8 image resident in HBM and owned by the library (ist_bitmap_*), with what the planner reads of it: width,
+    height (natural size), orientation (EXIF 1..8), opaque, file_size.  Made by decode_bitmaps / upload_bitmap; plan, stitch and
+    stitch_png take a list of them in place of host images and read the pixels where they are (the page's bitmap cache,
+    index.js:534-627).  close() - or garbage collection - drops this reference; a call that is using the bitmap keeps its own until it
+    returns.  48 MB of HBM per 12 MP photo, for as long as the host keeps it."""
+
+    def __init__(self, handle, device):
+        self._h = handle
+        self.device = int(device)
+        self._desc = L.ImageDesc()
+        L.check(L.lib.ist_bitmap_desc(C.c_void_p(handle), C.byref(self._desc)))
+
+    width = property(lambda self: int(self._desc.width))
+    height = property(lambda self: int(self._desc.height))
+    orientation = property(lambda self: int(self._desc.orientation))
+    opaque = property(lambda self: bool(self._desc.opaque))
+    file_size = property(lambda self: int(self._desc.file_size))
+
+    @property
+    def shape(self):
+        """(rows, columns, 4) of the stored pixels (the decoded bitmap, before any EXIF orientation)"""
+        d = self._desc
+        return (int(d.bmp_height or d.height), int(d.bmp_width or d.width), 4)
+
+    def handle(self):
+        if not self._h:
+            raise ValueError("the bitmap has been closed")
+        return self._h
+
+    def download(self):
+        """the pixels as an HxWx4 uint8 array (one copy from HBM)"""
+        out = np.empty(self.shape, np.uint8)
+        L.check(L.lib.ist_bitmap_download(C.c_void_p(self.handle()), out.ctypes.data, out.strides[0], out.shape[0]))
+        return out
+
+    def close(self):
+        if self._h:
+            L.lib.ist_bitmap_release(C.c_void_p(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return "Bitmap(%dx%d, orientation %d, device %d%s)" % (self.width, self.height, self.orientation, self.device, "" if self._h else ", closed")
+
+
+def _is_bitmap_request(images, o):
+    """True for a request made of Bitmaps (None entries allowed: the library rejects them as a missing image), False for one of host
+    images.  A request is one or the other."""
+    if not any(isinstance(im, Bitmap) for im in images):
+        return False
+    if not all(im is None or isinstance(im, Bitmap) for im in images):
+        raise TypeError("a request is either all Bitmaps or all host images, not a mix")
+    if o.get("devices") is not None:
+        raise TypeError("devices= does not apply to Bitmaps: a bitmap lives on one GPU")
+    return True
+
+
+def _bitmap_descs(images):
+    arr = (L.ImageDesc * max(1, len(images)))()
+    for i, b in enumerate(images):
+        if b is not None:
+            arr[i] = b._desc
+    return arr
+
+
+def _stitch_bitmaps(images, n, direction, o, device, png):
+    """stitch / stitch_png of a request made of Bitmaps (ist_stitch_bitmaps_rgba8 / _png)"""
+    bms = (C.c_void_p * n)(*[None if b is None else b.handle() for b in images])
+    cplan = L.Plan()
+    lim = _limits(o)
+    if png:
+        out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
+        rc = L.check(L.lib.ist_stitch_bitmaps_png(_ctx_png(device, o["pngLevel"]), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                                  float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
+    else:
+        out = C.POINTER(C.c_uint8)()
+        rc = L.check(L.lib.ist_stitch_bitmaps_rgba8(_ctx(device), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
+                                                    C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out)))
+    if rc == L.IST_NOTHING_TO_DO:
+        return None
+    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
+    L.lib.ist_plan_free(C.byref(cplan))
+    if png:
+        return {"width": w, "height": h, "png": _take_png(out, ln)}
+    return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
+
+
+def decode_bitmaps(files, device=0):
+    """Image files (bytes, or paths that are read here) -> [Bitmap], decoded straight into HBM by the decoder of stitch_files (baseline
+    JPEG: Huffman decoding + reconstruction on the GPU).  Each bitmap's desc is what stitch_files plans with: size, EXIF orientation,
+    opaque for JPEG, file_size = the file's length.  All or nothing: a file that does not decode raises StitchError('图片k解码异常: ...')
+    and no bitmap is kept."""
+    ctx = _ctx(device)
+    blobs = []
+    for f in files:
+        if isinstance(f, (str, os.PathLike)):
+            with open(f, "rb") as fh:
+                f = fh.read()
+        blobs.append(bytes(f))
+    n = len(blobs)
+    if n == 0:
+        return []
+    cfiles = (C.c_char_p * n)(*blobs)
+    lens = (C.c_int64 * n)(*[len(b) for b in blobs])
+    out = (C.c_void_p * n)()
+    L.check(L.lib.ist_bitmaps_decode(ctx, cfiles, lens, n, out))
+    return [Bitmap(out[i], device) for i in range(n)]
+
+
+def upload_bitmap(image, device=0):
+    """A host image -> Bitmap: an HxWx4 uint8 RGBA array, or a dict as stitch() takes ({'width', 'height', 'data', 'orientation'?,
+    'fileSize'?, 'opaque'?}); the desc is kept as given."""
+    ctx = _ctx(device)
+    desc = _descs([image])
+    a = image.get("data") if isinstance(image, dict) else image
+    if a is None:
+        raise L.StitchError(-6, "图片0解码异常")
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+        raise TypeError("expected an HxWx4 uint8 RGBA array")
+    if a.strides[2] != 1 or a.strides[1] != 4:
+        a = np.ascontiguousarray(a)
+    bw, bh = desc[0].bmp_width or desc[0].width, desc[0].bmp_height or desc[0].height
+    if bw < 1 or bh < 1:
+        raise L.StitchError(-6, "图片0解码异常")
+    if a.shape[0] < bh or a.shape[1] < bw:
+        raise ValueError("the pixels (%dx%d) are smaller than the bitmap (%dx%d)" % (a.shape[1], a.shape[0], bw, bh))
+    h = L.lib.ist_bitmap_upload(ctx, desc, a.ctypes.data, a.strides[0])
+    if not h:                                    # (NULL: the message says which rule failed)
+        msg = L.last_error()
+        raise L.StitchError(-6 if msg.startswith("图片") else -1 if msg.startswith("src_pitch") else -8 if msg.startswith("out of device memory") else -9, msg)
+    return Bitmap(h, device)
 
 
 class StitchJob:

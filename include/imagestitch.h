@@ -425,6 +425,36 @@ IST_API int ist_stitch_png(ist_ctx* ctx, const ist_image_desc* images, const uin
 IST_API int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans,
                                  uint8_t** out_png, int64_t* out_len);
 
+/* ---- resident bitmaps: decode or upload once, stitch again and again from HBM (the page's bitmap cache, index.js:534-627, used at
+ * :1442 and :1515-1517: a reordered, re-gapped or turned stitch decodes nothing again) -------------------------------------------- */
+/* One RGBA8 image in device memory that the LIBRARY owns: one block on the context's device, dense rows (4 * bitmap width bytes) plus
+ * the readable tail every staged source has, and the image's desc (natural size, EXIF orientation, opaque, file_size) for the planner.
+ * Reference-counted: the creator holds one reference (ist_bitmap_release drops it), every call that takes a bitmap holds one of its own
+ * until it returns, and the block is freed when the last one drops - a host may release a bitmap while a call that uses it runs.
+ * A bitmap outlives nothing: it does not keep its context alive, and it is usable with any context of its device. */
+typedef struct ist_bitmap ist_bitmap;
+/* host RGBA8 pixels (bitmap_w x bitmap_h of *desc, rows src_pitch bytes apart; 0 = dense) -> a new bitmap with *desc.  NULL on failure:
+ * IST_E_NO_CONTEXT without a context, IST_E_DECODE '图片0解码异常' for NULL pixels or an empty bitmap, IST_E_INVALID for a short pitch */
+IST_API ist_bitmap* ist_bitmap_upload(ist_ctx* ctx, const ist_image_desc* desc, const uint8_t* src, size_t src_pitch);
+/* files -> n new bitmaps (out[i]): the decode of ist_decode_files_device into blocks of the library, desc[i] as ist_stitch_files_png
+ * plans it (size, EXIF orientation, opaque for JPEG, file_size = lens[i]).  All or nothing: when file k fails, nothing is returned
+ * (out[] is left NULL) and the message is '图片k解码异常: ...'.  n <= 0: IST_NOTHING_TO_DO; more than 128: IST_E_UNSUPPORTED. */
+IST_API int ist_bitmaps_decode(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, ist_bitmap** out);
+IST_API int ist_bitmap_desc(const ist_bitmap* b, ist_image_desc* out);
+/* the pixels back into host memory (dst_rows rows of dst_pitch bytes must hold the bitmap) */
+IST_API int ist_bitmap_download(ist_bitmap* b, uint8_t* dst, size_t dst_pitch, int64_t dst_rows);
+IST_API void ist_bitmap_retain(ist_bitmap* b);
+IST_API void ist_bitmap_release(ist_bitmap* b);
+/* ist_stitch_rgba8 / ist_stitch_png with the bitmaps as the images: the descs are the bitmaps' own, and the one fused launch reads them
+ * where they are (no source crosses PCIe); only the canvas, or its PNG file, comes down.  The result is byte for byte what the host
+ * entry point returns for the same pixels and descs.  A NULL entry is IST_E_DECODE '图片N解码异常', a bitmap of another device than the
+ * context's IST_E_INVALID, more than 128 bitmaps IST_E_UNSUPPORTED, n == 0 IST_NOTHING_TO_DO. */
+IST_API int ist_stitch_bitmaps_rgba8(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap,
+                                     const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_pixels);
+IST_API int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap,
+                                   const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len);
+IST_API int64_t ist_debug_bitmap_bytes(void);   /* device bytes held by the bitmaps alive in this process */
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,11 @@
  *   render(canvasW, canvasH, clearRGBA, ops, images, filter, region, asPng?) -> Buffer (region pixels, or the PNG file)
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
  *   deviceCount(), lastError(), abiVersion()
+ *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[]) -> Promise<handle[]>;
+ *   bitmapDesc(h) -> {width,height,orientation,bmpWidth,bmpHeight,opaque,fileSize};  bitmapDownload(h) -> Buffer;  bitmapRelease(h);
+ *   stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng) -> Promise (as stitch);  stitchBitmapsSync(...same...);
+ *   debugBitmapBytes().  A handle is an object that wraps ONE reference of a bitmap: bitmapRelease drops it (again: nothing), its
+ *   finaliser drops it when the handle is collected unreleased; a stitch holds a reference of its own from the call to its completion.
  *
  * images[i] = {width, height, orientation?, fileSize?, opaque?, bmpWidth?, bmpHeight?, data?: Uint8Array|Buffer}
  * limits    = {platform: 0|1|2, maxSide, maxPixels, superSample} or null (MI355X default: caps lifted, superSample 1)
@@ -215,7 +220,15 @@ typedef struct {
   int devices[64]; int ndev, split;       /* opts.devices / opts.split: ndev 0 = the process-wide single context */
   ist_plan plan; uint8_t* pixels; int rc; char err[256];
   napi_deferred deferred; napi_async_work work;
+  ist_bitmap** bitmaps; int n_bitmaps;    /* stitchBitmaps: the request's bitmaps (NULL entries allowed), one reference each, taken on the JS thread */
 } stitch_job;
+
+static void stitch_job_free(napi_env env, stitch_job* j) {
+  images_free(env, &j->im);
+  for (int i = 0; i < j->n_bitmaps; i++) ist_bitmap_release(j->bitmaps[i]);
+  free(j->bitmaps);
+  free(j);
+}
 
 static void free_pixels(napi_env env, void* data, void* hint) { (void)env; (void)hint; ist_free(data); }
 
@@ -237,6 +250,12 @@ static void stitch_execute(napi_env env, void* data) {
   stitch_job* j = (stitch_job*)data;
   ist_ctx* ctx = get_ctx();
   if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
+  if (j->bitmaps) {
+    j->rc = j->want_png ? ist_stitch_bitmaps_png(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels, &j->png_len)
+                        : ist_stitch_bitmaps_rgba8(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels);
+    if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
+    return;
+  }
   for (int i = 0; i < j->im.n; i++)
     if (!j->im.data[i]) { j->rc = IST_E_DECODE; snprintf(j->err, sizeof j->err, "\xe5\x9b\xbe\xe7\x89\x87%d\xe8\xa7\xa3\xe7\xa0\x81\xe5\xbc\x82\xe5\xb8\xb8", i); return; }
   if (j->ndev > 0 && !j->want_png)
@@ -274,8 +293,7 @@ static void stitch_complete(napi_env env, napi_status status, void* data) {
     else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the output buffer"));
   }
   napi_delete_async_work(env, j->work);
-  images_free(env, &j->im);
-  free(j);
+  stitch_job_free(env, j);
 }
 
 static stitch_job* stitch_parse(napi_env env, napi_callback_info info, int want_refs) {
@@ -401,8 +419,7 @@ static napi_value js_stitch_sync(napi_env env, napi_callback_info info) {
   if (j->rc < 0) { napi_throw(env, make_error(env, j->rc, j->err)); }
   else if (j->rc == IST_NOTHING_TO_DO) napi_get_null(env, &out);
   else out = stitch_result(env, j);
-  images_free(env, &j->im);
-  free(j);
+  stitch_job_free(env, j);
   return out;
 }
 
@@ -724,6 +741,245 @@ static napi_value js_set_png_level(napi_env env, napi_callback_info info) {
   napi_value v; napi_get_undefined(env, &v); return v;
 }
 
+/* ---- resident bitmaps --------------------------------------------------------------------------------------------------- */
+typedef struct { ist_bitmap* b; } bitmap_ref;   /* NULL once released */
+
+static void bitmap_finalize(napi_env env, void* data, void* hint) {
+  (void)env; (void)hint;
+  bitmap_ref* r = (bitmap_ref*)data;
+  if (r->b) ist_bitmap_release(r->b);
+  free(r);
+}
+
+/* a new handle that takes over the caller's reference of b (released again when the handle cannot be made) */
+static napi_value bitmap_wrap(napi_env env, ist_bitmap* b) {
+  napi_value o;
+  bitmap_ref* r = (bitmap_ref*)calloc(1, sizeof *r);
+  if (!r || napi_create_object(env, &o) != napi_ok) { free(r); ist_bitmap_release(b); return NULL; }
+  r->b = b;
+  if (napi_wrap(env, o, r, bitmap_finalize, NULL, NULL) != napi_ok) { free(r); ist_bitmap_release(b); return NULL; }
+  return o;
+}
+
+/* the record of a handle; NULL with a TypeError pending when v is none */
+static bitmap_ref* bitmap_ref_of(napi_env env, napi_value v) {
+  bitmap_ref* r = NULL;
+  if (napi_unwrap(env, v, (void**)&r) != napi_ok || !r) { napi_throw_type_error(env, NULL, "not a Bitmap handle"); return NULL; }
+  return r;
+}
+/* the bitmap of a handle; NULL with an Error pending when it has been released (use after release) */
+static ist_bitmap* bitmap_of(napi_env env, napi_value v) {
+  bitmap_ref* r = bitmap_ref_of(env, v);
+  if (!r) return NULL;
+  if (!r->b) { napi_throw_error(env, NULL, "the bitmap has been released"); return NULL; }
+  return r->b;
+}
+
+/* the code of a failed ist_bitmap_upload (it returns NULL; the message tells which rule failed) */
+static int upload_fail_code(void) {
+  const char* m = ist_last_error();
+  if (!strncmp(m, "\xe5\x9b\xbe\xe7\x89\x87", 6)) return IST_E_DECODE;       /* '图片0解码异常' */
+  if (!strncmp(m, "src_pitch", 9)) return IST_E_INVALID;
+  if (!strncmp(m, "out of device memory", 20)) return IST_E_NOMEM;
+  return IST_E_HIP;
+}
+
+/* uploadBitmap([image]) -> handle: one host image (as stitch takes it) into a bitmap with its desc */
+static napi_value js_upload_bitmap(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 1) { napi_throw_type_error(env, NULL, "uploadBitmap([image])"); return NULL; }
+  images_t im;
+  if (!images_parse(env, argv[0], &im, 0)) { images_free(env, &im); return NULL; }
+  if (im.n != 1) { images_free(env, &im); napi_throw_type_error(env, NULL, "uploadBitmap takes one image"); return NULL; }
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { images_free(env, &im); napi_throw(env, make_error(env, IST_E_NO_DEVICE, g_ctx_err)); return NULL; }
+  ist_bitmap* b = ist_bitmap_upload(ctx, &im.descs[0], im.data[0], im.pitch[0]);
+  images_free(env, &im);
+  if (!b) return throw_ist(env, upload_fail_code());
+  napi_value h = bitmap_wrap(env, b);
+  if (!h) napi_throw_error(env, NULL, "could not wrap the bitmap");
+  return h;
+}
+
+/* decodeBitmaps(files: Buffer[]) -> Promise<handle[]> (ist_bitmaps_decode: all or nothing) */
+typedef struct {
+  int n; const uint8_t** files; int64_t* lens; napi_ref* refs;
+  ist_bitmap** out; int rc; char err[256];
+  napi_deferred deferred; napi_async_work work;
+} decode_job;
+
+static void decode_job_free(napi_env env, decode_job* j) {
+  for (int i = 0; i < j->n; i++) {
+    if (j->refs[i]) napi_delete_reference(env, j->refs[i]);
+    if (j->out[i]) ist_bitmap_release(j->out[i]);
+  }
+  free(j->files); free(j->lens); free(j->refs); free(j->out); free(j);
+}
+
+static void decode_execute(napi_env env, void* data) {
+  (void)env;
+  decode_job* j = (decode_job*)data;
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
+  j->rc = j->n ? ist_bitmaps_decode(ctx, j->files, j->lens, j->n, j->out) : IST_OK;
+  if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
+}
+
+static void decode_complete(napi_env env, napi_status status, void* data) {
+  decode_job* j = (decode_job*)data;
+  (void)status;
+  napi_value arr = NULL;
+  if (j->rc < 0) napi_reject_deferred(env, j->deferred, make_error(env, j->rc, j->err));
+  else if (napi_create_array_with_length(env, (size_t)j->n, &arr) == napi_ok) {
+    int ok = 1;
+    for (int i = 0; i < j->n && ok; i++) {
+      napi_value h = bitmap_wrap(env, j->out[i]);
+      j->out[i] = NULL;                                   /* the handle owns the reference now (or released it) */
+      ok = h && napi_set_element(env, arr, (uint32_t)i, h) == napi_ok;
+    }
+    if (ok) napi_resolve_deferred(env, j->deferred, arr);
+    else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the bitmaps"));
+  } else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not make the result array"));
+  napi_delete_async_work(env, j->work);
+  decode_job_free(env, j);
+}
+
+static napi_value js_decode_bitmaps(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  bool is_arr = false; uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "decodeBitmaps(files: Buffer[])"); return NULL;
+  }
+  napi_get_array_length(env, argv[0], &n);
+  decode_job* j = (decode_job*)calloc(1, sizeof *j);
+  j->n = (int)n;
+  j->files = (const uint8_t**)calloc(n ? n : 1, sizeof(uint8_t*)); j->lens = (int64_t*)calloc(n ? n : 1, sizeof(int64_t));
+  j->refs = (napi_ref*)calloc(n ? n : 1, sizeof(napi_ref)); j->out = (ist_bitmap**)calloc(n ? n : 1, sizeof(ist_bitmap*));
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value e; void* p = NULL; size_t len = 0; bool isbuf = false, ta = false;
+    napi_get_element(env, argv[0], i, &e);
+    napi_is_buffer(env, e, &isbuf); napi_is_typedarray(env, e, &ta);
+    if (isbuf) napi_get_buffer_info(env, e, &p, &len);
+    else if (ta) { napi_typedarray_type tt; napi_value ab; size_t off; napi_get_typedarray_info(env, e, &tt, &len, &p, &ab, &off); }
+    if (!p) { napi_throw_type_error(env, NULL, "files[i] must be a Buffer / Uint8Array"); decode_job_free(env, j); return NULL; }
+    j->files[i] = (const uint8_t*)p; j->lens[i] = (int64_t)len;
+    napi_create_reference(env, e, 1, &j->refs[i]);
+  }
+  napi_value promise, name;
+  CHECK(napi_create_promise(env, &j->deferred, &promise));
+  napi_create_string_utf8(env, "imagestitch.decodeBitmaps", NAPI_AUTO_LENGTH, &name);
+  CHECK(napi_create_async_work(env, NULL, name, decode_execute, decode_complete, j, &j->work));
+  CHECK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
+static napi_value js_bitmap_desc(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 1) { napi_throw_type_error(env, NULL, "bitmapDesc(handle)"); return NULL; }
+  ist_bitmap* b = bitmap_of(env, argv[0]);
+  if (!b) return NULL;
+  ist_image_desc d;
+  const int rc = ist_bitmap_desc(b, &d);
+  if (rc < 0) return throw_ist(env, rc);
+  napi_value o, op;
+  napi_create_object(env, &o);
+  set_num(env, o, "width", d.width); set_num(env, o, "height", d.height); set_num(env, o, "orientation", d.orientation);
+  set_num(env, o, "bmpWidth", d.bmp_width > 0 ? d.bmp_width : d.width); set_num(env, o, "bmpHeight", d.bmp_height > 0 ? d.bmp_height : d.height);
+  napi_get_boolean(env, d.opaque != 0, &op); napi_set_named_property(env, o, "opaque", op);
+  set_num(env, o, "fileSize", (double)d.file_size);
+  return o;
+}
+
+/* bitmapDownload(handle) -> Buffer (bmpWidth * bmpHeight * 4 bytes, dense rows) */
+static napi_value js_bitmap_download(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 1) { napi_throw_type_error(env, NULL, "bitmapDownload(handle)"); return NULL; }
+  ist_bitmap* b = bitmap_of(env, argv[0]);
+  if (!b) return NULL;
+  ist_image_desc d;
+  ist_bitmap_desc(b, &d);
+  const int64_t w = d.bmp_width > 0 ? d.bmp_width : d.width, h = d.bmp_height > 0 ? d.bmp_height : d.height;
+  void* out_data = NULL; napi_value buf;
+  if (napi_create_buffer(env, (size_t)w * (size_t)h * 4, &out_data, &buf) != napi_ok) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  const int rc = ist_bitmap_download(b, (uint8_t*)out_data, (size_t)w * 4, h);
+  if (rc < 0) return throw_ist(env, rc);
+  return buf;
+}
+
+/* bitmapRelease(handle): drops the handle's reference (a released handle: nothing) */
+static napi_value js_bitmap_release(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 1) { napi_throw_type_error(env, NULL, "bitmapRelease(handle)"); return NULL; }
+  bitmap_ref* r = bitmap_ref_of(env, argv[0]);
+  if (!r) return NULL;
+  if (r->b) { ist_bitmap_release(r->b); r->b = NULL; }
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+/* stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng): every bitmap is retained HERE, on the JS thread, so that a
+ * release() or a collection between this call and the work's execution cannot free it */
+static stitch_job* stitch_bitmaps_parse(napi_env env, napi_callback_info info) {
+  size_t argc = 7; napi_value argv[7];
+  bool is_arr = false; uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "stitchBitmaps(bitmaps, direction, mode, gap, limits, filter, asPng)");
+    return NULL;
+  }
+  napi_get_array_length(env, argv[0], &n);
+  stitch_job* j = (stitch_job*)calloc(1, sizeof *j);
+  j->bitmaps = (ist_bitmap**)calloc(n ? n : 1, sizeof(ist_bitmap*));
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value e; napi_valuetype t = napi_undefined;
+    napi_get_element(env, argv[0], i, &e);
+    napi_typeof(env, e, &t);
+    if (t == napi_null || t == napi_undefined) { j->n_bitmaps = (int)i + 1; continue; }   /* a missing image: '图片N解码异常' from the library */
+    ist_bitmap* b = bitmap_of(env, e);
+    if (!b) { stitch_job_free(env, j); return NULL; }
+    ist_bitmap_retain(b);
+    j->bitmaps[i] = b;
+    j->n_bitmaps = (int)i + 1;
+  }
+  int32_t v = 0;
+  napi_get_value_int32(env, argv[1], &v); j->direction = v;
+  napi_get_value_int32(env, argv[2], &v); j->mode = v;
+  napi_get_value_double(env, argv[3], &j->gap);
+  limits_parse(env, argv[4], &j->lim);
+  napi_get_value_int32(env, argv[5], &v); j->filter = v;
+  if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; }
+  return j;
+}
+
+static napi_value js_stitch_bitmaps(napi_env env, napi_callback_info info) {
+  stitch_job* j = stitch_bitmaps_parse(env, info);
+  if (!j) return NULL;
+  napi_value promise, name;
+  CHECK(napi_create_promise(env, &j->deferred, &promise));
+  napi_create_string_utf8(env, "imagestitch.stitchBitmaps", NAPI_AUTO_LENGTH, &name);
+  CHECK(napi_create_async_work(env, NULL, name, stitch_execute, stitch_complete, j, &j->work));
+  CHECK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
+static napi_value js_stitch_bitmaps_sync(napi_env env, napi_callback_info info) {
+  stitch_job* j = stitch_bitmaps_parse(env, info);
+  if (!j) return NULL;
+  stitch_execute(env, j);
+  napi_value out = NULL;
+  if (j->rc < 0) napi_throw(env, make_error(env, j->rc, j->err));
+  else if (j->rc == IST_NOTHING_TO_DO) napi_get_null(env, &out);
+  else out = stitch_result(env, j);
+  stitch_job_free(env, j);
+  return out;
+}
+
+static napi_value js_debug_bitmap_bytes(napi_env env, napi_callback_info info) {
+  (void)info; napi_value v; napi_create_double(env, (double)ist_debug_bitmap_bytes(), &v); return v;
+}
+
 /* environment teardown: nothing of the library may still be in flight when the HIP runtime shuts down (include/imagestitch.h,
  * ist_ctx_sync); the idle pinned result blocks go back to the system */
 static void on_env_cleanup(void* arg) {
@@ -751,6 +1007,14 @@ static napi_value init(napi_env env, napi_value exports) {
       {"deviceCount", NULL, js_device_count, NULL, NULL, NULL, napi_default, NULL},
       {"lastError", NULL, js_last_error, NULL, NULL, NULL, napi_default, NULL},
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_default, NULL},
+      {"uploadBitmap", NULL, js_upload_bitmap, NULL, NULL, NULL, napi_default, NULL},
+      {"decodeBitmaps", NULL, js_decode_bitmaps, NULL, NULL, NULL, napi_default, NULL},
+      {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},
+      {"bitmapDownload", NULL, js_bitmap_download, NULL, NULL, NULL, napi_default, NULL},
+      {"bitmapRelease", NULL, js_bitmap_release, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchBitmaps", NULL, js_stitch_bitmaps, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchBitmapsSync", NULL, js_stitch_bitmaps_sync, NULL, NULL, NULL, napi_default, NULL},
+      {"debugBitmapBytes", NULL, js_debug_bitmap_bytes, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -43,3 +43,19 @@ export function setPngLevel(level: 0 | 1): void;
 export function decodePng(file: Uint8Array): { width: number; height: number; data: Buffer };
 export function stitchFiles(paths: string[], direction: Direction, opts?: StitchOptions, outPath?: string): Promise<StitchPngResult | null>;
 export function decodeImage(file: Uint8Array): { width: number; height: number; orientation: number; opaque: boolean; data: Buffer };
+// resident bitmaps: images kept in GPU memory; stitch / stitchSync / stitchPng / plan take Bitmap[] in place of StitchImage[] (all or
+// none: a mix, or `devices` with bitmaps, is a TypeError; stitchBatch / stitchPngBatch refuse bitmaps)
+export class Bitmap {
+  private constructor();
+  readonly width: number; readonly height: number; readonly orientation: number; readonly opaque: boolean; readonly fileSize: number;
+  readonly bmpWidth: number; readonly bmpHeight: number;
+  download(): Buffer;       // bmpWidth * bmpHeight * 4 bytes, RGBA8
+  release(): void;          // idempotent; any other use afterwards throws
+}
+export function decodeBitmaps(files: (Uint8Array | string)[]): Promise<Bitmap[]>;
+export function uploadBitmap(image: StitchImage): Bitmap;
+export function debugBitmapBytes(): number;
+export function stitch(images: Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split'>): Promise<StitchResult | null>;
+export function stitchSync(images: Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split'>): StitchResult | null;
+export function stitchPng(images: Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split'>): Promise<StitchPngResult | null>;
+export function plan(images: Bitmap[], direction: Direction, opts?: StitchOptions): StitchPlan | null;

@@ -8,6 +8,8 @@
  *   stitch(images, direction, opts?) -> Promise<{width, height, data: Buffer, plan}>
  *   stitchBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, data, plan} | null)[]>   (one GPU, many stitches)
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
+ *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
+ *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
  *
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
@@ -87,13 +89,67 @@ function groupArgs(opts) {
   if (!(split in SPLIT)) throw new TypeError('unknown split ' + split);
   return [false, o.devices, SPLIT[split]];
 }
+// ---- resident bitmaps ----------------------------------------------------------------------------------------------------------
+const MADE_HERE = Symbol('Bitmap');
+/** One decoded RGBA8 image kept in GPU memory by the library (the page's bitmap cache, index.js:534-627): made by decodeBitmaps /
+ *  uploadBitmap, stitched again and again by stitch / stitchSync / stitchPng with nothing decoded or uploaded.  width, height,
+ *  orientation, opaque and fileSize are what the planner reads.  release() drops it (again: nothing); using it afterwards throws.
+ *  A Bitmap that is collected unreleased is released then; a stitch in flight holds the bitmap until it settles. */
+class Bitmap {
+  constructor(token, handle) {
+    if (token !== MADE_HERE) throw new TypeError('Bitmaps are made by decodeBitmaps / uploadBitmap');
+    const d = native.bitmapDesc(handle);
+    const ro = (value) => ({ value, enumerable: true });
+    Object.defineProperties(this, {
+      handle: { value: handle },
+      width: ro(d.width), height: ro(d.height), orientation: ro(d.orientation), opaque: ro(d.opaque), fileSize: ro(d.fileSize),
+      bmpWidth: ro(d.bmpWidth), bmpHeight: ro(d.bmpHeight),
+    });
+  }
+  /** the pixels as they are stored (bmpWidth x bmpHeight, RGBA8, dense rows) */
+  download() { return native.bitmapDownload(this.handle); }
+  release() { native.bitmapRelease(this.handle); }
+}
+// a request made of Bitmaps -> their native handles (null entries stay null: the library rejects them as a missing image); null for a
+// request of host images.  A request is one or the other.
+function bitmapHandles(images, opts) {
+  if (!Array.isArray(images) || !images.some((x) => x instanceof Bitmap)) return null;
+  if (!images.every((x) => x === null || x === undefined || x instanceof Bitmap)) throw new TypeError('a request is either all Bitmaps or all host images, not a mix');
+  if (opts && opts.devices !== undefined && opts.devices !== null) throw new TypeError('devices does not apply to Bitmaps: a bitmap lives on one GPU');
+  return images.map((x) => (x ? x.handle : null));
+}
+/** Image files (Buffers, or paths read here as stitchFiles reads them) -> Bitmaps, decoded straight into GPU memory by the decoder
+ *  of stitchFiles; each one's width / height / orientation / opaque / fileSize is what stitchFiles plans with.  All or nothing: a
+ *  file that does not decode rejects with '图片k解码异常: ...' and no bitmap is kept. */
+async function decodeBitmaps(files) {
+  if (!Array.isArray(files)) throw new TypeError('decodeBitmaps(files: (Uint8Array | string)[])');
+  const fs = require('fs');
+  const bufs = files.map((f) => (typeof f === 'string' ? fs.readFileSync(f) : f));
+  if (!bufs.length) return [];
+  const handles = await native.decodeBitmaps(bufs);
+  return handles.map((h) => new Bitmap(MADE_HERE, h));
+}
+/** One host image ({width, height, data, orientation?, fileSize?, opaque?}, as stitch takes it) -> a Bitmap with that desc. */
+function uploadBitmap(image) { return new Bitmap(MADE_HERE, native.uploadBitmap([image])); }
+/** device bytes held by the live bitmaps of this process */
+function debugBitmapBytes() { return native.debugBitmapBytes(); }
+
 function stitch(images, direction, opts) {
-  let a;
-  try { a = args(images, direction, opts).concat(groupArgs(opts)); } catch (e) { return Promise.reject(e); }
+  let a, h;
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts).concat(h ? [] : groupArgs(opts)); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);      // `if (!originalImages.length) return;` (index.js:1189): no progress, no error
+  if (h) {
+    // (the native call retains every bitmap before it returns: a release() from here on does not free one under the stitch)
+    try { return withProgress(opts, () => native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], false)); } catch (e) { return Promise.reject(e); }
+  }
   return withProgress(opts, () => native.stitch(...a));
 }
-function stitchSync(images, direction, opts) { const a = args(images, direction, opts).concat(groupArgs(opts)); return a[0].length ? native.stitchSync(...a) : null; }
+function stitchSync(images, direction, opts) {
+  const h = bitmapHandles(images, opts);
+  const a = args(images, direction, opts).concat(h ? [] : groupArgs(opts));
+  if (!a[0].length) return null;
+  return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a);
+}
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
 const BATCH_REFUSED = ['devices', 'split', 'pngLevel'];
 function batchArgs(requests) {
@@ -102,6 +158,7 @@ function batchArgs(requests) {
     if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
     const o = r.opts || {};
     for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
+    if (Array.isArray(r.images) && r.images.some((x) => x instanceof Bitmap)) throw new TypeError('request ' + k + ': Bitmaps do not apply to a batch');
     return args(r.images, r.direction, o);
   });
 }
@@ -128,9 +185,12 @@ function stitchPngBatchSync(requests) { const a = batchArgs(requests); return a.
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
-  let a;
-  try { a = args(images, direction, opts); } catch (e) { return Promise.reject(e); }
+  let a, h;
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
+  if (h) {
+    try { return withProgress(opts, () => { pngLevel(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true); }); } catch (e) { return Promise.reject(e); }
+  }
   return withProgress(opts, () => { pngLevel(opts); return native.stitch(...a, true); });
 }
 /** opts.pngLevel: 0 = stored deflate blocks (file = raw size, fastest), 1 = Paeth + run-length + Huffman on the GPU
@@ -159,8 +219,10 @@ async function stitchFiles(paths, direction, opts, outPath) {
 /** Lossless PNG of RGBA8 pixels, encoded on the GPU. */
 function encodePng(data, width, height, opts) { pngLevel(opts); return native.encodePng(data, width, height); }
 function plan(images, direction, opts) {
+  bitmapHandles(images, opts);                        // (the all-or-none rule; a Bitmap carries the fields the planner reads)
   const a = args(images, direction, opts);
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan,
+                   decodeBitmaps, uploadBitmap, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
