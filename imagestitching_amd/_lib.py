@@ -19,7 +19,7 @@ if os.environ.get("IST_TUNING") == "1" and os.environ.get("IST_LIB_PATH"):      
 VERTICAL, HORIZONTAL = 0, 1
 MODE_MIN, MODE_MAX, MODE_ORIGINAL = 0, 1, 2
 PLATFORM_OTHER, PLATFORM_IOS, PLATFORM_ANDROID = 0, 1, 2
-FILTER_NEAREST, FILTER_BILINEAR, FILTER_AREA = 0, 1, 2
+FILTER_NEAREST, FILTER_BILINEAR, FILTER_AREA, FILTER_CUBIC = 0, 1, 2, 3
 SPLIT_IMAGE, SPLIT_BAND, SPLIT_ROWS, SPLIT_AUTO = 0, 1, 2, 3
 
 IST_OK, IST_NOTHING_TO_DO = 0, 1

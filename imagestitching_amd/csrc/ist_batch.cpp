@@ -24,7 +24,7 @@ namespace {
 
 std::atomic<int64_t> g_batch_launches{0};
 
-constexpr int kKinds = 5;                               // launch_stitch's kernel forms (Compiled::kernel_kind)
+constexpr int kKinds = 7;                               // launch_stitch's kernel forms (Compiled::kernel_kind)
 
 // The host path splits a batch so that sources + canvases of one sub-batch stay under this many device bytes (a larger
 // request runs alone, with the memory its single stitch would take).  Two sub-batches are in flight (Pipeline below), so the

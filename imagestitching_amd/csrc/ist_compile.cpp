@@ -101,7 +101,7 @@ int resolve_op(const ist_op& op, int64_t canvas_w, int64_t canvas_h, int img_w, 
 // number of distinct source indices one axis of a draw touches over canvas coordinates [lo, hi)
 static int64_t distinct_taps(double k, double o, int lo, int hi, int clo, int chi, int filter) {
   if (hi <= lo) return 0;
-  if (filter == IST_FILTER_AREA && std::fabs(k) > 1.0) {     // a box of width |k| per canvas pixel: contiguous boxes tile the whole span
+  if ((filter == IST_FILTER_AREA || filter == IST_FILTER_CUBIC) && std::fabs(k) > 1.0) {     // a box of width |k| per canvas pixel: contiguous boxes tile the whole span
     const double a = k * static_cast<double>(lo) + o, b = k * static_cast<double>(hi) + o;
     const double s0 = std::min(a, b), s1 = std::max(a, b);
     const int64_t i0 = static_cast<int64_t>(std::min(std::max(std::floor(s0), -4.0e9), 4.0e9)), i1 = static_cast<int64_t>(std::min(std::max(std::ceil(s1), -4.0e9), 4.0e9)) - 1;
@@ -112,10 +112,14 @@ static int64_t distinct_taps(double k, double o, int lo, int hi, int clo, int ch
   // the taps are monotonic in the canvas coordinate; clamping keeps them so
   auto first_tap = [&](int w) -> int64_t {
     const double s = k * (static_cast<double>(w) + 0.5) + o;
-    const double fl = std::min(std::max(std::floor(filter == IST_FILTER_BILINEAR ? s - 0.5 : s), -4.0e9), 4.0e9);
+    const double fl = std::min(std::max(std::floor(filter != IST_FILTER_NEAREST ? s - 0.5 : s), -4.0e9), 4.0e9);
     return static_cast<int64_t>(fl);
   };
   auto clampi = [&](int64_t v) { return std::min<int64_t>(std::max<int64_t>(v, clo), chi); };
+  if (filter == IST_FILTER_CUBIC) {              // an axis that does not shrink: taps floor(f) - 1 .. floor(f) + 2, every index between the ends
+    const int64_t a = first_tap(lo), b = first_tap(hi - 1);
+    return clampi(std::max(a, b) + 2) - clampi(std::min(a, b) - 1) + 1;
+  }
   const int64_t second = filter == IST_FILTER_BILINEAR ? 1 : 0;
   if (std::fabs(k) <= 1.0) {
     // neighbouring canvas coordinates are at most one source index apart: every index between the ends is touched
@@ -220,9 +224,12 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
   if (n_ops < 0 || (n_ops > 0 && !ops)) return fail(IST_E_INVALID, "compile_ops: bad op list");
   const bool aa = (filter & IST_FILTER_EDGE_AA) != 0;
   filter &= 0xFF;
-  if (filter != IST_FILTER_NEAREST && filter != IST_FILTER_BILINEAR && filter != IST_FILTER_AREA) return fail(IST_E_INVALID, "unknown filter");
+  if (filter != IST_FILTER_NEAREST && filter != IST_FILTER_BILINEAR && filter != IST_FILTER_AREA && filter != IST_FILTER_CUBIC) return fail(IST_E_INVALID, "unknown filter");
   // AREA: minifying draws are averaged per pixel on the general path; everything else about the job is bilinear
+  // CUBIC: a draw that shrinks on both axes compiles as under AREA; one that shrinks on neither takes the streamed cubic path; the
+  // rest (one axis each way, quarter turns, overlaps, edge strips) is evaluated per pixel.  No cell of such a job is bilinear.
   const bool area = filter == IST_FILTER_AREA;
+  const bool cubic = filter == IST_FILTER_CUBIC;
   const int job_filter = filter;
   if (area) filter = IST_FILTER_BILINEAR;
   const CompileKnobs knobs = read_knobs();
@@ -340,13 +347,13 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
   }
 
   // 4. classify + tile each cell
-  bool has_area = false, has_general = false;
+  bool has_area = false, has_general = false, has_cubic = false;
   for (DevCell& cell : out->cells) {
     const bool bg_opaque = (cell.bg >> 24) == 255u;
     const bool partial = cell.tiles_x < 0;
     cell.tiles_x = 0;
     bool minified = false;                        // IST_FILTER_AREA: a draw of the stack shrinks on some axis
-    if (area)
+    if (area || cubic)
       for (int k = 0; k < cell.stack_len; ++k) {
         const DevOp& r = out->ops[out->stacks[cell.stack_off + k]];
         minified |= !(r.flags & OPF_FILL) && (std::fabs(r.kx) > 1.0 || std::fabs(r.ky) > 1.0);
@@ -358,7 +365,7 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
       if (!partial && cell.stack_len == 1 && !knobs.no_lds) {
         const DevOp& r = out->ops[cell.op];
         if (!(r.flags & (OPF_SWAP | OPF_FILL | OPF_HOLE)) && (bg_opaque || (r.flags & OPF_OPAQUE)) && r.cx1 >= r.cx0 && r.cy1 >= r.cy0 &&
-            std::fabs(r.ky) <= 64.0) {
+            std::fabs(r.ky) <= 64.0 && (!cubic || (std::fabs(r.kx) > 1.0 && std::fabs(r.ky) > 1.0))) {
           // Tile width: the row sums (most of the work) run in 64-lane passes of 4 source pixels each, so the x footprint of a
           // tile should fill its pass: the widest tile (<= 128 canvas pixels: 2 per lane) whose footprint fits ONE pass of 256
           // source pixels (two passes: a tuning knob; never faster, 2x slower at 6.6x).  LDS: 4 waves x 256 px x float4 = 16 KiB.
@@ -425,6 +432,19 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
         }
       }
     }
+    if (cubic && cell.path == PATH_SAMPLE) {
+      // ONE axis-aligned draw that shrinks on neither axis, over an opaque colour (or an opaque draw): tile_cubic_stream.  LDS: 4 waves
+      // x one row of float4 row sums over the tile's x footprint, (tile_w - 1) |kx| + 5 source pixels at most (<= 260 at 1:1).
+      if (!knobs.no_lds) {
+        const DevOp& r = out->ops[cell.op];
+        const int64_t wl = (static_cast<int64_t>(std::floor(255.0 * std::fabs(r.kx))) + 5 + 3) & ~3LL;
+        cell.path = PATH_CUBIC_STREAM; cell.tile_w = 256; cell.tile_h = 32; cell.sub_h = 0;
+        out->lds_words = std::max<int32_t>(out->lds_words, static_cast<int32_t>(4 * 4 * wl));
+      } else {
+        cell.path = PATH_GENERAL;
+        if (!bg_opaque) cell.bg = clear_pm;           // (IST_NO_LDS: the per-pixel stack composites over the real canvas colour)
+      }
+    }
     if (cell.path == PATH_SAMPLE && filter == IST_FILTER_BILINEAR && !knobs.no_lds) {
       // stage the tile's source footprint in LDS when it fits the budget with at least 4 output rows per tile
       const DevOp& r = out->ops[cell.op];
@@ -469,7 +489,7 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
         }
       }
     }
-    if (cell.path == PATH_SAMPLE_LDS || cell.path == PATH_SWAP_LDS || cell.path == PATH_SAMPLE_STREAM || cell.path == PATH_AREA_STREAM) {}
+    if (cell.path == PATH_SAMPLE_LDS || cell.path == PATH_SWAP_LDS || cell.path == PATH_SAMPLE_STREAM || cell.path == PATH_AREA_STREAM || cell.path == PATH_CUBIC_STREAM) {}
     else if (cell.path == PATH_GENERAL) { cell.tile_w = 64; cell.tile_h = 64; }
     else if (cell.path == PATH_SAMPLE) { cell.tile_w = 256; cell.tile_h = 32; }
     else { cell.tile_w = knobs.tile_w; cell.tile_h = knobs.tile_h; }   // FILL / COPY: tile_w = 256 << n
@@ -495,11 +515,11 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
     tiles += nt;
     info.out_pixels += w * h;
     out->kernel_kind = std::max<int32_t>(out->kernel_kind, (cell.path == PATH_FILL || cell.path == PATH_COPY) ? 0 : (cell.path == PATH_SAMPLE || cell.path == PATH_SAMPLE_LDS || cell.path == PATH_SAMPLE_STREAM) ? 1 : 2);
-    if (cell.path == PATH_AREA_STREAM) has_area = true; else if (cell.path == PATH_GENERAL || cell.path == PATH_SWAP_LDS) has_general = true;
+    if (cell.path == PATH_AREA_STREAM) has_area = true; else if (cell.path == PATH_CUBIC_STREAM) has_cubic = true; else if (cell.path == PATH_GENERAL || cell.path == PATH_SWAP_LDS) has_general = true;
     switch (cell.path) {
       case PATH_FILL: info.tiles_fill += nt; break;
       case PATH_COPY: info.tiles_copy += nt; break;
-      case PATH_SAMPLE: case PATH_SAMPLE_LDS: case PATH_SAMPLE_STREAM: case PATH_SWAP_LDS: case PATH_AREA_STREAM: info.tiles_sample += nt; break;
+      case PATH_SAMPLE: case PATH_SAMPLE_LDS: case PATH_SAMPLE_STREAM: case PATH_SWAP_LDS: case PATH_AREA_STREAM: case PATH_CUBIC_STREAM: info.tiles_sample += nt; break;
       default: info.tiles_general += nt; break;
     }
     for (int k = 0; k < cell.stack_len; ++k) {
@@ -515,6 +535,9 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
   }
   if (tiles > 2147483647LL) return fail(IST_E_OUTPUT_SIZE, "canvas needs more than 2^31 tiles");
   if (has_area) out->kernel_kind = has_general ? 4 : 3;   // 3: fill / copy / resample / streamed box filter; 4: everything
+  // a cubic job's forms: 5 = fill / copy / streamed box filter / streamed cubic; 6 = + the per-pixel stack under the cubic rule.  One whose
+  // draws all shrink (or are copies) holds neither and launches what the same job launches under AREA (3) or any filter (0).
+  if (cubic && (has_cubic || has_general)) out->kernel_kind = has_general ? 6 : 5;
   // launch order of the bands: the expensive tiles (resampling) first, copies next, fills last, so that the workgroups
   // that finish the launch are the short ones (a strip of mixed scales otherwise ends on whatever its last image needs).
   // Stable: bands of one kind keep their canvas order.

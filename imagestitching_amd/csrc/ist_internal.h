@@ -60,6 +60,8 @@ enum : int32_t {
   PATH_SAMPLE_LDS = 4, // PATH_SAMPLE (bilinear, moderate scale) with the tile's source footprint staged in LDS
   PATH_SAMPLE_STREAM = 6, // PATH_SAMPLE (bilinear): every wave streams its own rows' source row pairs through a private LDS ring
   PATH_AREA_STREAM = 7, // ONE axis-aligned draw that shrinks, IST_FILTER_AREA: box sums per output row, streamed (no barrier)
+  PATH_CUBIC_STREAM = 8, // ONE axis-aligned draw that does not shrink on either axis, IST_FILTER_CUBIC: four weighted source rows per output
+                      // row combined per source column, then four column taps per pixel from LDS, streamed (no barrier)
   PATH_SWAP_LDS = 5,   // ONE quarter-turned draw (EXIF 5-8), bilinear: footprint staged TRANSPOSED in LDS
   PATH_GENERAL = 3    // anything else: paint stack evaluated per pixel in canvas order (swap draws, overlaps,
                       // translucent canvas)
@@ -100,7 +102,8 @@ struct Compiled {
   int filter = IST_FILTER_BILINEAR;
   int32_t lds_words = 0;               // dynamic LDS per workgroup (32-bit words): max(SWAP_LDS patch, lds_half)
   int32_t lds_half = 0;                // the SAMPLE_LDS footprint buffer (the largest footprint any stage needs)
-  int32_t kernel_kind = 0;             // 0: fill/copy cells only; 1: + SAMPLE / SAMPLE_LDS; 2: + SWAP_LDS / GENERAL
+  int32_t kernel_kind = 0;             // 0: fill/copy cells only; 1: + SAMPLE / SAMPLE_LDS; 2: + SWAP_LDS / GENERAL; 3, 4: + AREA_STREAM;
+                                       // 5, 6: IST_FILTER_CUBIC jobs that resample (ist_launch.h)
   std::vector<DevOp> ops;
   std::vector<DevCell> cells;
   std::vector<DevBand> bands;

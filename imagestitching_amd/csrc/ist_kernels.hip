@@ -15,6 +15,7 @@
 //                     once per tile in fp64 (bit-identical to the oracle), rows streamed, fp32 lerp
 //             GENERAL paint stack evaluated per pixel in canvas order (EXIF quarter turns, overlapping draws,
 //                     translucent canvas)
+//             AREA_STREAM / CUBIC_STREAM  the opt-in filters 'area' (box) and 'cubic' (Catmull-Rom), separable, streamed per wave
 //
 // HBM-bound byte movement: no MFMA.
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off (the fp64 coordinate math must not be fused).
@@ -742,6 +743,152 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ CUBIC, streamed
+// IST_FILTER_CUBIC on an axis-aligned draw that shrinks on neither axis: Catmull-Rom (Keys, a = -0.5) at half-pixel centres, four
+// taps per axis, each clamped to the draw's clamp box (include/imagestitch.h states the rule).  Evaluated separably, in the shape of
+// tile_area_stream above and with no workgroup barrier: a wave owns output rows Y0 + wave + 4 j.  For one output row it
+//   1. reads the four source rows of the row's taps with coalesced loads (lane = SP neighbouring source pixels, below) and combines
+//      them in registers with the rows' weights (wave-uniform, packed fp32) into one float4 per SOURCE column,
+//   2. writes those row sums to its private LDS row,
+//   3. lane = canvas pixel: the four column taps of each of its pixels from LDS with the pixel's weights, clamped (the negative
+//      lobes overshoot), composited over the background and stored as 256 contiguous bytes per wave.
+// That is 4 k + 4 weighted float4 sums per output pixel at a source / canvas ratio k <= 1 instead of 16 taps.  The x taps and
+// weights of a lane are the same for every row of the tile: computed once, in fp64.  Source rows are re-read by the about 4 / k
+// output rows that tap them; those re-reads are left to L2 (neighbouring rows belong to the waves of one workgroup).  A wave's LDS
+// operations execute in order, so the phases need no barrier.  LDS row index j holds source column fx0 + j ALREADY clamped, so
+// the taps of step 3 need no clamping of their own.
+IST_DEV void cubic_weights(double t, float w[4]) {
+  w[0] = static_cast<float>(((-0.5 * t + 1.0) * t - 0.5) * t);
+  w[1] = static_cast<float>((1.5 * t - 2.5) * t * t + 1.0);
+  w[2] = static_cast<float>(((-1.5 * t + 2.0) * t + 0.5) * t);
+  w[3] = static_cast<float>((0.5 * t - 0.5) * t * t);
+}
+
+// SP = source pixels per lane in step 1 (one 16-, 8- or 4-byte load per row): the footprint of a 256-pixel tile is 256 |kx| + 4
+// source pixels, so at 2.6x four pixels per lane keep 26 of the 64 lanes busy; the caller picks the SP that fills the wave.
+template <int SP>
+IST_DEV void ld_src(const uint8_t* p, uint32_t v[SP]) {
+  if constexpr (SP == 4) { const u32x4 t = ld16_plain(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  else if constexpr (SP == 2) { const u32x2 t = ld8(p); v[0] = t.x; v[1] = t.y; }
+  else v[0] = ld4(p);
+}
+
+template <bool OPAQUE, int SP>
+IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, int X0, int Y0, int X1, int Y1, uint32_t* lds, bool fresh) {
+  constexpr int NP = 4;                                     // canvas pixels per lane and row: tiles are 256 pixels wide
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  // x footprint of the tile (wave-uniform): the taps are monotonic in X, so the first and last column bound it
+  const double fa = (op.kx * (static_cast<double>(X0) + 0.5) + op.ox) - 0.5, fb = (op.kx * (static_cast<double>(X1 - 1) + 0.5) + op.ox) - 0.5;
+  const int fx0 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(fmin(fa, fb)), -2.0e9), 2.0e9))) - 1;
+  const int fx1 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(fmax(fa, fb)), -2.0e9), 2.0e9))) + 2;
+  const int wl = (fx1 - fx0 + 1 + 3) & ~3;                  // source pixels per LDS row
+  if (16 * wl > A.lds_words) return;                        // uniform; cannot happen (|kx| <= 1 and 256-pixel tiles: the host sizes the row for 260)
+  const int chunks = wl / SP;
+  if (!fresh) __syncthreads();                              // (grid-stride form) every wave is done with the previous tile's LDS
+  float* row = reinterpret_cast<float*>(lds) + static_cast<size_t>(wave) * (4 * wl);
+  const size_t sp = A.pitch[op.image];
+  const uint8_t* src = A.src[op.image];
+  // per lane, once per tile: the first tap and the four weights of each of its canvas pixels on the x axis
+  const int Xl = X0 + lane;
+  int tap[NP]; float wx[NP][4];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const double f = (op.kx * (static_cast<double>(min(Xl + 64 * p, X1 - 1)) + 0.5) + op.ox) - 0.5;
+    const double fl = floor(f);
+    tap[p] = static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9)) - 1 - fx0;
+    cubic_weights(f - fl, wx[p]);
+    __builtin_amdgcn_sched_barrier(0);                      // (one pixel's fp64 temporaries at a time)
+  }
+  uint8_t* d = A.dst + static_cast<size_t>(Xl) * 4;
+#pragma unroll 1
+  for (int Y = Y0 + wave; Y < Y1; Y += 4) {
+    // the four rows of this output row and their weights (wave-uniform; computed once per tile instead they cost ten live registers and
+    // with them a wave of occupancy: slower, LAB_NOTES.md section 2)
+    const double f = (op.ky * (static_cast<double>(Y) + 0.5) + op.oy) - 0.5;
+    const double fl = floor(f);
+    const int iy = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9))) - 1;
+    float wyv[4];
+    cubic_weights(f - fl, wyv);
+    f32x2 wy[4];
+    const uint8_t* g[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wyv[u])));
+      wy[u] = f32x2{w, w};
+      g[u] = src + static_cast<size_t>(min(max(iy + u, op.cy0), op.cy1)) * sp;
+    }
+    // 1 + 2: row sums per source column -> LDS
+#pragma unroll 1
+    for (int c0 = 0; c0 < chunks; c0 += 64) {
+      const int c = c0 + lane;
+      const bool mine = c < chunks;
+      const int xx = fx0 + SP * min(c, chunks - 1);
+      const bool inside = xx >= op.cx0 && xx + (SP - 1) <= op.cx1;
+      f32x2 acc[SP][2];                                     // per source pixel: (r, g), (b, a)
+#pragma unroll
+      for (int q = 0; q < SP; ++q) { acc[q][0] = f32x2{0.f, 0.f}; acc[q][1] = f32x2{0.f, 0.f}; }
+      auto add_px = [&](int q, uint32_t px, f32x2 w2) {
+        f32x2 lo = {static_cast<float>(ch(px, 0)), static_cast<float>(ch(px, 1))};
+        f32x2 hi = {static_cast<float>(ch(px, 2)), static_cast<float>(px >> 24)};
+        if (!OPAQUE) { const f32x2 a2 = {hi.y, hi.y}; lo = lo * a2; hi.x = hi.x * hi.y; }
+        acc[q][0] = __builtin_elementwise_fma(w2, lo, acc[q][0]);
+        acc[q][1] = __builtin_elementwise_fma(w2, hi, acc[q][1]);
+      };
+      if (inside) {
+        uint32_t v[4][SP];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ld_src<SP>(g[u] + static_cast<size_t>(xx) * 4, v[u]);    // (plain loads: the rows are read again by the waves of the next output rows)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+          for (int q = 0; q < SP; ++q) add_px(q, v[u][q], wy[u]);
+        }
+      } else {                                              // a chunk that straddles the source's edge: pixel by pixel, clamped
+        size_t xo[SP];
+#pragma unroll
+        for (int q = 0; q < SP; ++q) xo[q] = static_cast<size_t>(min(max(xx + q, op.cx0), op.cx1)) * 4;
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {                       // (rolled: unrolled, this rare branch set the kernel's register count)
+#pragma unroll
+          for (int q = 0; q < SP; ++q) add_px(q, ld4(g[u] + xo[q]), wy[u]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (mine) {
+#pragma unroll
+        for (int q = 0; q < SP; ++q) {
+          const f32x4 t = {acc[q][0].x, acc[q][0].y, acc[q][1].x, acc[q][1].y};
+          *reinterpret_cast<f32x4*>(row + 4 * (SP * c + q)) = t;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // 3: the four column taps of every canvas pixel, from LDS
+    uint8_t* dp = d + static_cast<size_t>(Y) * A.dst_pitch;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      if (X0 + 64 * p >= X1) break;                         // (wave-uniform: the tile is narrower than 64 * NP)
+      const f32x4* t = reinterpret_cast<const f32x4*>(row) + tap[p];
+      const f32x4 s = ((t[0] * wx[p][0] + t[1] * wx[p][1]) + t[2] * wx[p][2]) + t[3] * wx[p][3];
+      uint32_t o;
+      if (OPAQUE) {                                         // opaque source: the clamped sum replaces the destination
+        o = 0xFF000000u | to_u8(fminf(fmaxf(s.x, 0.f), 255.f)) | (to_u8(fminf(fmaxf(s.y, 0.f), 255.f)) << 8) | (to_u8(fminf(fmaxf(s.z, 0.f), 255.f)) << 16);
+      } else {                                              // premultiplied sums: alpha to [0, 255], colours to [0, alpha], source-over, one rounding
+        const float Aa = fminf(fmaxf(s.w, 0.f), 255.f);
+        const float keep = 1.0f - Aa * (1.0f / 255.0f);
+        o = to_u8(fminf(fminf(fmaxf(s.x * (1.0f / 255.0f), 0.f), Aa) + static_cast<float>(ch(bg, 0)) * keep, 255.f)) |
+            (to_u8(fminf(fminf(fmaxf(s.y * (1.0f / 255.0f), 0.f), Aa) + static_cast<float>(ch(bg, 1)) * keep, 255.f)) << 8) |
+            (to_u8(fminf(fminf(fmaxf(s.z * (1.0f / 255.0f), 0.f), Aa) + static_cast<float>(ch(bg, 2)) * keep, 255.f)) << 16) |
+            (to_u8(fminf(Aa + static_cast<float>(bg >> 24) * keep, 255.f)) << 24);
+      }
+      if (Xl + 64 * p < X1) st4(dp + 256 * p, o);
+      __builtin_amdgcn_sched_barrier(0);                    // (one pixel's taps at a time: the four pixels' LDS reads at once cost 64 registers)
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ SWAP via LDS
 // One quarter-turned draw (EXIF 5-8: source x is driven by canvas Y, source y by canvas X), bilinear.  A 64 x th
 // canvas tile needs a (th*|kx|+2)-column x (64*|ky|+2)-row source patch.  The patch is read row by row with coalesced
@@ -852,10 +999,43 @@ IST_DEV bool tile_swap_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, int
 // ------------------------------------------------------------------------------------------------ GENERAL
 // one pixel through the whole paint stack, in canvas order, on a premultiplied 8-bit destination (what an
 // immediate-mode Canvas with 8-bit premultiplied backing store does call by call)
+// One axis of IST_FILTER_CUBIC for one canvas coordinate: n taps from index i0 (unclamped).  |k| <= 1: the four Catmull-Rom taps;
+// |k| > 1: the box of IST_FILTER_AREA, weights = overlap / |k|.
+struct CubicAxis { int i0, n; bool box; double lo, hi; float inv; float w0, w1, w2, w3; };
+IST_DEV CubicAxis cubic_axis(double k, double o, int w) {
+  CubicAxis a;
+  const double s = k * (static_cast<double>(w) + 0.5) + o;
+  a.box = fabs(k) > 1.0;
+  if (a.box) {
+    const double bw = fabs(k);
+    a.lo = s - 0.5 * bw; a.hi = s + 0.5 * bw;
+    a.i0 = static_cast<int>(fmin(fmax(floor(a.lo), -2.0e9), 2.0e9));
+    a.n = static_cast<int>(fmin(fmax(ceil(a.hi), -2.0e9), 2.0e9)) - a.i0;
+    a.inv = static_cast<float>(1.0 / bw);
+    a.w0 = a.w1 = a.w2 = a.w3 = 0.f;
+  } else {
+    const double f = s - 0.5, fl = floor(f);
+    float w4[4];
+    cubic_weights(f - fl, w4);
+    a.i0 = static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9)) - 1;
+    a.n = 4; a.lo = a.hi = 0.0; a.inv = 1.f;
+    a.w0 = w4[0]; a.w1 = w4[1]; a.w2 = w4[2]; a.w3 = w4[3];
+  }
+  return a;
+}
+IST_DEV float cubic_axis_weight(const CubicAxis& a, int j) {
+  if (!a.box) return j == 0 ? a.w0 : j == 1 ? a.w1 : j == 2 ? a.w2 : a.w3;
+  const double i = static_cast<double>(a.i0) + static_cast<double>(j);
+  return static_cast<float>(fmin(i + 1.0, a.hi) - fmax(i, a.lo)) * a.inv;
+}
+
+// CUBIC: the instantiation knows IST_FILTER_CUBIC (only the forms launched for cubic jobs do: the others keep their code and registers)
+template <bool CUBIC>
 IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int Y) {
   uint32_t d = c.bg;
   const bool nearest = (A.filter & 0xFF) == IST_FILTER_NEAREST;
   const bool area = (A.filter & 0xFF) == IST_FILTER_AREA;
+  const bool cubic = CUBIC && (A.filter & 0xFF) == IST_FILTER_CUBIC;
   const bool edge_aa = (A.filter & IST_FILTER_EDGE_AA) != 0;
   for (int k = 0; k < c.stack_len; ++k) {
     const DevOp op = A.ops[A.stacks[c.stack_off + k]];
@@ -888,7 +1068,7 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
       }
       const double va = floor(static_cast<double>(a) * cov + static_cast<double>(d >> 24) * keep + 0.5);
       d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
-    } else if (area && (fabs(op.kx) > 1.0 || fabs(op.ky) > 1.0)) {
+    } else if (CUBIC ? ((area && (fabs(op.kx) > 1.0 || fabs(op.ky) > 1.0)) || (cubic && fabs(op.kx) > 1.0 && fabs(op.ky) > 1.0)) : (area && (fabs(op.kx) > 1.0 || fabs(op.ky) > 1.0))) {
       // IST_FILTER_AREA on a minifying draw: a box of width max(1, |k|) per axis around the sample position, source pixels
       // weighted by their overlap (fp32 sums of premultiplied taps; the oracle does the same sums in fp64)
       const double sxc = op.kx * (static_cast<double>(wx) + 0.5) + op.ox, syc = op.ky * (static_cast<double>(wy) + 0.5) + op.oy;
@@ -920,6 +1100,37 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
 #pragma unroll
       for (int ch_ = 0; ch_ < 3; ++ch_) {
         const double P = static_cast<double>(accs[ch_]) * norm / 255.0;
+        const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
+        o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
+      }
+      const double va = floor(Aa * cov + static_cast<double>(d >> 24) * keep + 0.5);
+      d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
+    } else if (CUBIC && cubic) {
+      // IST_FILTER_CUBIC with an axis that does not shrink: four Catmull-Rom taps there, the box on an axis that shrinks (a draw that
+      // shrinks on both took the branch above: the same bytes as under IST_FILTER_AREA).  fp32 sums of premultiplied taps, rows first.
+      const CubicAxis ax = cubic_axis(op.kx, op.ox, wx), ay = cubic_axis(op.ky, op.oy, wy);
+      float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+      for (int jy = 0; jy < ay.n; ++jy) {
+        const float oyw = cubic_axis_weight(ay, jy);
+        const uint8_t* srow = src + static_cast<size_t>(min(max(ay.i0 + jy, op.cy0), op.cy1)) * sp;
+        float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+        for (int jx = 0; jx < ax.n; ++jx) {
+          const float oxw = cubic_axis_weight(ax, jx);
+          const uint32_t s = ld4(srow + 4 * static_cast<size_t>(min(max(ax.i0 + jx, op.cx0), op.cx1)));
+          const float a = static_cast<float>(s >> 24);
+          r0 += oxw * (static_cast<float>(ch(s, 0)) * a); r1 += oxw * (static_cast<float>(ch(s, 1)) * a);
+          r2 += oxw * (static_cast<float>(ch(s, 2)) * a); r3 += oxw * a;
+        }
+        acc0 += oyw * r0; acc1 += oyw * r1; acc2 += oyw * r2; acc3 += oyw * r3;
+      }
+      // the negative lobes overshoot: alpha to [0, 255], each premultiplied colour to [0, alpha], before compositing
+      const double Aa = fmin(fmax(static_cast<double>(acc3), 0.0), 255.0);
+      const double keep = 1.0 - cov * (Aa / 255.0);
+      const float accs[3] = {acc0, acc1, acc2};
+      uint32_t o = 0;
+#pragma unroll
+      for (int ch_ = 0; ch_ < 3; ++ch_) {
+        const double P = fmin(fmax(static_cast<double>(accs[ch_]) / 255.0, 0.0), Aa);
         const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
         o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
       }
@@ -960,17 +1171,18 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
   return r | (g << 8) | (b << 16) | (a << 24);
 }
 
+template <bool CUBIC>
 IST_DEV void tile_general(const LaunchArgs& A, const DevCell c, int X0, int Y0, int X1, int Y1) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   const int X = X0 + lane;
   if (X >= X1) return;
   for (int Y = Y0 + wave; Y < Y1; Y += 4)
-    st4(A.dst + static_cast<size_t>(Y) * A.dst_pitch + static_cast<size_t>(X) * 4, pixel_general(A, c, X, Y));
+    st4(A.dst + static_cast<size_t>(Y) * A.dst_pitch + static_cast<size_t>(X) * 4, pixel_general<CUBIC>(A, c, X, Y));
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
-enum : int { HAS_FILL = 1, HAS_COPY = 2, HAS_SAMPLE = 4, HAS_GENERAL = 8, HAS_SWAP = 16, HAS_AREA = 32 };
+enum : int { HAS_FILL = 1, HAS_COPY = 2, HAS_SAMPLE = 4, HAS_GENERAL = 8, HAS_SWAP = 16, HAS_AREA = 32, HAS_CUBIC = 64 };
 
 template <int PATHS, int V>
 IST_DEV void run_tile(const LaunchArgs& A, int64_t tile, bool fresh) {
@@ -1031,12 +1243,25 @@ IST_DEV void run_tile(const LaunchArgs& A, int64_t tile, bool fresh) {
     else { if (opq) tile_area_stream<1, true>(A, op_, c.bg, X0, Y0, X1, Y1, lds); else tile_area_stream<1, false>(A, op_, c.bg, X0, Y0, X1, Y1, lds); }
   } else if ((PATHS & HAS_SWAP) && path == PATH_SWAP_LDS) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    if (!tile_swap_lds(A, op_, c.bg, X0, Y0, X1, Y1, lds)) tile_general(A, c, X0, Y0, X1, Y1);
+    if (!tile_swap_lds(A, op_, c.bg, X0, Y0, X1, Y1, lds)) tile_general<(PATHS & HAS_CUBIC) != 0>(A, c, X0, Y0, X1, Y1);
   } else if ((PATHS & HAS_SAMPLE) && path == PATH_SAMPLE) {
     if ((A.filter & 0xFF) == IST_FILTER_NEAREST) tile_sample<IST_FILTER_NEAREST>(A, op_, c.bg, X0, Y0, X1, Y1);
     else tile_sample<IST_FILTER_BILINEAR>(A, op_, c.bg, X0, Y0, X1, Y1);
+  } else if ((PATHS & HAS_CUBIC) && path == PATH_CUBIC_STREAM) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    // source pixels per lane of the row pass: 4 while the tile's footprint (256 |kx| + 4 pixels) fills a wave that way, else 2, else 1
+    const double akx = fabs(op_.kx);
+    if (op_.flags & OPF_OPAQUE) {
+      if (akx > 0.5) tile_cubic_stream<true, 4>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+      else if (akx > 0.25) tile_cubic_stream<true, 2>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+      else tile_cubic_stream<true, 1>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+    } else {
+      if (akx > 0.5) tile_cubic_stream<false, 4>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+      else if (akx > 0.25) tile_cubic_stream<false, 2>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+      else tile_cubic_stream<false, 1>(A, op_, c.bg, X0, Y0, X1, Y1, lds, fresh);
+    }
   } else if (PATHS & HAS_GENERAL) {
-    tile_general(A, c, X0, Y0, X1, Y1);
+    tile_general<(PATHS & HAS_CUBIC) != 0>(A, c, X0, Y0, X1, Y1);
   }
 }
 
@@ -1058,6 +1283,25 @@ __global__ __launch_bounds__(256) void ist_stitch_kernel(const LaunchArgs A, con
 #endif
 template <int PATHS, int V, bool PERSIST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_area_kernel(const LaunchArgs A, const int64_t n_tiles) {
+  if (PERSIST) {
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) run_tile<PATHS, V>(A, t, false);
+  } else {
+    run_tile<PATHS, V>(A, static_cast<int64_t>(blockIdx.x), true);
+  }
+}
+
+// the instantiations of IST_FILTER_CUBIC jobs that resample (kernel kinds 5 and 6): kernels of their own, so that no other form
+// pays registers for the cubic tile function or for the cubic rule of the per-pixel stack
+#ifndef IST_CUBIC_WAVES         // (compile-time experiment switch: -DIST_CUBIC_WAVES=4 rebuilds the variant LAB_NOTES.md quotes; 0 = the compiler's choice)
+#define IST_CUBIC_WAVES 0
+#endif
+#if IST_CUBIC_WAVES > 0
+#define IST_CUBIC_EU __attribute__((amdgpu_waves_per_eu(IST_CUBIC_WAVES)))
+#else
+#define IST_CUBIC_EU
+#endif
+template <int PATHS, int V, bool PERSIST>
+__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_kernel(const LaunchArgs A, const int64_t n_tiles) {
   if (PERSIST) {
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) run_tile<PATHS, V>(A, t, false);
   } else {
@@ -1104,6 +1348,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WA
   run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
 }
 
+template <int PATHS, int V>
+__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_batch_kernel(const BatchArgs B) {
+  const int64_t tile = static_cast<int64_t>(blockIdx.x);
+  const int j = batch_job_of(B, tile);
+  const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
+  run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
+}
+
+constexpr int kCubicPaths = HAS_FILL | HAS_COPY | HAS_AREA | HAS_CUBIC;       // kind 5; kind 6 = | HAS_GENERAL
+
 int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream) {
   if (args.n_tiles <= 0) return IST_OK;
   if (args.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles");
@@ -1114,6 +1368,8 @@ int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes,
   else if (kind == 1) hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE, 0>), grid, block, dyn_lds_bytes, s, args);
   else if (kind == 3) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
   else if (kind == 4) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
+  else if (kind == 5) hipLaunchKernelGGL((ist_cubic_batch_kernel<kCubicPaths, 0>), grid, block, dyn_lds_bytes, s, args);
+  else if (kind == 6) hipLaunchKernelGGL((ist_cubic_batch_kernel<kCubicPaths | HAS_GENERAL, 0>), grid, block, dyn_lds_bytes, s, args);
   else hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL, 0>), grid, block, dyn_lds_bytes, s, args);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(IST_E_HIP, std::string("batch kernel launch failed: ") + hipGetErrorString(e));
@@ -1124,7 +1380,8 @@ template <int PATHS, int V, bool PERSIST>
 static void launch_one(const LaunchArgs& args, int64_t n_tiles, hipStream_t stream, int persist_blocks, unsigned dyn_lds) {
   const unsigned grid = PERSIST ? static_cast<unsigned>(std::min<int64_t>(n_tiles, persist_blocks)) : static_cast<unsigned>(n_tiles);
   const unsigned dyn = std::max(dyn_lds, static_cast<unsigned>(args.lds_words) * 4u);   // dyn_lds: IST_DYN_LDS tuning knob (unused LDS caps the workgroups per CU)
-  if constexpr ((PATHS & HAS_AREA) != 0) hipLaunchKernelGGL((ist_stitch_area_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
+  if constexpr ((PATHS & HAS_CUBIC) != 0) hipLaunchKernelGGL((ist_cubic_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
+  else if constexpr ((PATHS & HAS_AREA) != 0) hipLaunchKernelGGL((ist_stitch_area_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
   else hipLaunchKernelGGL((ist_stitch_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
 }
 
@@ -1158,6 +1415,8 @@ int launch_stitch(const LaunchArgs& args, int64_t n_tiles, int kind, void* strea
   if (kind == 0 && !full) launch_variant<HAS_FILL | HAS_COPY>(v, persist, args, n_tiles, s, pb, dl);
   else if (kind == 1 && !full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE>(v, persist, args, n_tiles, s, pb, dl);
   else if (kind == 3 && !full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA>(v, persist, args, n_tiles, s, pb, dl);
+  else if (kind == 5) launch_variant<kCubicPaths>(v, persist, args, n_tiles, s, pb, dl);
+  else if (kind == 6) launch_variant<kCubicPaths | HAS_GENERAL>(v, persist, args, n_tiles, s, pb, dl);
   else if (kind == 4 || full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA>(v, persist, args, n_tiles, s, pb, dl);
   else launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL>(v, persist, args, n_tiles, s, pb, dl);
   const hipError_t e = hipGetLastError();

@@ -31,7 +31,8 @@ struct LaunchArgs {
 
 // kind: 0 = the job has only FILL / COPY cells, 1 = + axis-aligned resampling (SAMPLE, SAMPLE_LDS, SAMPLE_STREAM), 3 = + the
 // streamed box filter (AREA_STREAM), 2 = quarter turns / paint stacks (no box filter), 4 = everything: the instantiation
-// with just those paths is launched
+// with just those paths is launched.  IST_FILTER_CUBIC jobs that resample: 5 = FILL / COPY / AREA_STREAM / CUBIC_STREAM, 6 = + the
+// per-pixel paint stack under the cubic rule (no such job holds a bilinear cell).  ist_batch.cpp groups a batch by these (kKinds).
 int launch_stitch(const LaunchArgs& args, int64_t n_tiles, int kind, void* stream);
 
 // Several jobs of one kind in ONE launch (ist_jobs_launch).  Three device tables, uploaded per launch:

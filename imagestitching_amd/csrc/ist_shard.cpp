@@ -31,7 +31,7 @@ namespace {
 
 // source index range one axis of a draw touches over canvas coordinates [lo, hi) (inclusive result, clamped)
 void tap_range(double k, double o, int lo, int hi, int clo, int chi, int filter, int* a, int* b) {
-  if (filter == IST_FILTER_AREA && std::fabs(k) > 1.0) {      // a box of width |k| around every sample position
+  if ((filter == IST_FILTER_AREA || filter == IST_FILTER_CUBIC) && std::fabs(k) > 1.0) {      // a box of width |k| around every sample position
     const double half = 0.5 * std::fabs(k);
     const double c0 = k * (static_cast<double>(lo) + 0.5) + o, c1 = k * (static_cast<double>(hi - 1) + 0.5) + o;
     const double s0 = std::min(c0, c1) - half, s1 = std::max(c0, c1) + half;
@@ -43,13 +43,14 @@ void tap_range(double k, double o, int lo, int hi, int clo, int chi, int filter,
   if (filter == IST_FILTER_AREA) filter = IST_FILTER_BILINEAR;
   auto first_tap = [&](int w) {
     const double s = k * (static_cast<double>(w) + 0.5) + o;
-    double fl = std::floor(filter == IST_FILTER_BILINEAR ? s - 0.5 : s);
+    double fl = std::floor(filter != IST_FILTER_NEAREST ? s - 0.5 : s);
     fl = std::min(std::max(fl, -4.0e9), 4.0e9);
     return static_cast<int64_t>(fl);
   };
   const int64_t t0 = first_tap(lo), t1 = first_tap(hi - 1);           // monotonic in w: the ends bound the range
-  const int64_t span = filter == IST_FILTER_BILINEAR ? 1 : 0;
-  const int64_t mn = std::min(t0, t1), mx = std::max(t0, t1) + span;
+  // bilinear: the pair floor(f), floor(f) + 1; cubic on an axis that does not shrink: the four taps floor(f) - 1 .. floor(f) + 2
+  const int64_t before = filter == IST_FILTER_CUBIC ? 1 : 0, span = filter == IST_FILTER_CUBIC ? 2 : filter == IST_FILTER_BILINEAR ? 1 : 0;
+  const int64_t mn = std::min(t0, t1) - before, mx = std::max(t0, t1) + span;
   *a = static_cast<int>(std::min<int64_t>(std::max<int64_t>(mn, clo), chi));
   *b = static_cast<int>(std::min<int64_t>(std::max<int64_t>(mx, clo), chi));
 }
@@ -137,7 +138,7 @@ extern "C" int ist_shard_parts(const ist_op* ops, int n_ops, int64_t canvas_w, i
   if (canvas_w < 1 || canvas_h < 1 || canvas_w > (1 << 29) || canvas_h > 2147483647LL) return fail(IST_E_OUTPUT_SIZE, "输出尺寸计算失败: canvas size out of range");
   const bool aa = (filter & IST_FILTER_EDGE_AA) != 0;
   const int f = filter & 0xFF;
-  if (f != IST_FILTER_NEAREST && f != IST_FILTER_BILINEAR && f != IST_FILTER_AREA) return fail(IST_E_INVALID, "unknown filter");
+  if (f != IST_FILTER_NEAREST && f != IST_FILTER_BILINEAR && f != IST_FILTER_AREA && f != IST_FILTER_CUBIC) return fail(IST_E_INVALID, "unknown filter");
   *n_parts = 0;
   struct Draw { int op; DevOp r; };
   std::vector<Draw> draws;

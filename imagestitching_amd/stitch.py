@@ -21,7 +21,7 @@ from . import _lib as L
 
 _DIRECTIONS = {"vertical": L.VERTICAL, "horizontal": L.HORIZONTAL}
 _MODES = {"min": L.MODE_MIN, "max": L.MODE_MAX, "original": L.MODE_ORIGINAL}
-_FILTERS = {"nearest": L.FILTER_NEAREST, "bilinear": L.FILTER_BILINEAR, "area": L.FILTER_AREA}
+_FILTERS = {"nearest": L.FILTER_NEAREST, "bilinear": L.FILTER_BILINEAR, "area": L.FILTER_AREA, "cubic": L.FILTER_CUBIC}
 FILTER_EDGE_AA = 0x100
 
 
@@ -43,7 +43,8 @@ _PLATFORMS = {"ios": L.PLATFORM_IOS, "android": L.PLATFORM_ANDROID, "devtools": 
 DEFAULT_OPTS = {
     "mode": "min",          # data.verticalStitchMode / horizontalStitchMode default (index.js:19-20)
     "gap": 0,               # data.gap default (index.js:17)
-    "filter": "bilinear",   # imageSmoothingEnabled = true (index.js:1416-1418); 'nearest' = false; 'area' = opt-in box average of minified axes (IST_FILTER_AREA)
+    "filter": "bilinear",   # imageSmoothingEnabled = true (index.js:1416-1418); 'nearest' = false; 'area' = opt-in box average of minified axes (IST_FILTER_AREA);
+                            # 'cubic' = opt-in Catmull-Rom on axes that do not shrink, the box of 'area' on those that do (IST_FILTER_CUBIC)
     "platform": None,       # None: MI355X default = caps lifted; 'ios' / 'android' / 'devtools' reproduce the phone caps
     "maxSide": None,        # deviceMaxCanvasSize override
     "maxPixels": None,      # deviceMaxCanvasPixels override

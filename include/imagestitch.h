@@ -49,12 +49,22 @@ enum { IST_VERTICAL = 0, IST_HORIZONTAL = 1 };                    /* data.direct
 enum { IST_MODE_MIN = 0, IST_MODE_MAX = 1, IST_MODE_ORIGINAL = 2 };/* data.*StitchMode (index.js:19-20) */
 enum { IST_PLATFORM_OTHER = 0, IST_PLATFORM_IOS = 1, IST_PLATFORM_ANDROID = 2 }; /* sys.platform       */
 enum { IST_OP_FILL = 0, IST_OP_DRAW = 1, IST_OP_HOLE = 2 };
-enum { IST_FILTER_NEAREST = 0, IST_FILTER_BILINEAR = 1, IST_FILTER_AREA = 2 };   /* imageSmoothingEnabled false / true (index.js:1416-1418) */
+enum { IST_FILTER_NEAREST = 0, IST_FILTER_BILINEAR = 1, IST_FILTER_AREA = 2, IST_FILTER_CUBIC = 3 };   /* imageSmoothingEnabled false / true (index.js:1416-1418) */
 /* IST_FILTER_AREA (an option; the contract's default for imageSmoothingQuality = 'high', index.js:1419, stays bilinear): on
  * every source axis that is MINIFIED (|scale| > 1 source pixel per canvas pixel) the sample is the average of the source
  * over the canvas pixel's footprint (a box of that width, pixels weighted by overlap); other axes, and any draw that
  * does not shrink, are bilinear - at |scale| = 1 the box IS the bilinear pair, so the two meet continuously.  The
  * phone-capped plans shrink 12 MP photos 2.2x (iOS) to 6.6x (Android), where point-sampled bilinear aliases. */
+/* IST_FILTER_CUBIC (an option, the counterpart of IST_FILTER_AREA for draws that GROW: the super-sampled small-job plan,
+ * index.js:1363, enlarges 2.2-2.6x; mode 'max' enlarges every image narrower than the widest): decided per source axis of a
+ * draw.  On an axis with |scale| <= 1 (enlarged or 1:1) the sample is the Catmull-Rom cubic convolution (Keys, a = -0.5) at
+ * half-pixel centres: f = s - 0.5, i = floor(f), t = f - i, taps i-1 .. i+2, each clamped to the draw's clamp box, weights
+ *     w(-1) = ((-0.5 t + 1.0) t - 0.5) t      w(0) = (1.5 t - 2.5) t t + 1.0
+ *     w(+1) = ((-1.5 t + 2.0) t + 0.5) t      w(+2) = (0.5 t - 0.5) t t
+ * (they sum to 1; at t = 0 they are (0, 1, 0, 0), so a 1:1 draw at an integer offset is the identity and stays a copy).  On an
+ * axis with |scale| > 1 the sample is the box of IST_FILTER_AREA, unchanged.  The separable sum runs over premultiplied,
+ * unrounded components; the kernel's negative lobes overshoot, so alpha is clamped to [0, 255] and each premultiplied colour
+ * to [0, alpha] before compositing.  Coverage, source-over and the single rounding are those of the bilinear filter. */
 /* OR-ed into a `filter` argument: anti-alias FRACTIONAL rectangle edges by area coverage, as Canvas rasters do (they
  * arise from ctx.scale(superSample), index.js:1426-1428, and from the unrounded cursor, :1432).  Off: a pixel belongs
  * to a draw iff its centre is inside the rectangle.  Integer-edged plans are unaffected either way. */

@@ -12,7 +12,7 @@ export interface StitchImage {
   bmpWidth?: number; bmpHeight?: number;
 }
 export interface StitchOptions {
-  mode?: StitchMode; gap?: number; filter?: 'bilinear' | 'nearest' | 'area';      // 'area': box-average minified axes (one reading of imageSmoothingQuality 'high'); default bilinear
+  mode?: StitchMode; gap?: number; filter?: 'bilinear' | 'nearest' | 'area' | 'cubic';      // 'area': box-average minified axes (one reading of imageSmoothingQuality 'high'); 'cubic': Catmull-Rom on axes that do not shrink, the box of 'area' on those that do; default bilinear
   platform?: 'ios' | 'android' | 'devtools' | 'windows' | 'mac' | 'other';
   maxSide?: number; maxPixels?: number; superSample?: number;
   edgeAA?: boolean;                         // anti-alias fractional rectangle edges (ctx.scale(superSample), unrounded cursor); default: true iff `platform` is given

@@ -14,7 +14,7 @@
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
  * opts      = {mode: 'min'|'max'|'original' (default 'min', index.js:19-20), gap: 0..20 (default 0, index.js:17),
- *              filter: 'bilinear'|'nearest' (imageSmoothingEnabled, index.js:1416), platform: 'ios'|'android'|'devtools'
+ *              filter: 'bilinear'|'nearest' (imageSmoothingEnabled, index.js:1416) | 'area' | 'cubic' (opt-in quality filters), platform: 'ios'|'android'|'devtools'
  *              (reproduces the phone caps, index.js:1323-1336; default: caps lifted, superSample 1),
  *              maxSide, maxPixels (deviceMaxCanvasSize/Pixels), superSample (MAX_SUPER_SAMPLE, index.js:1363),
  *              onProgress: (percent) => void  (the stitchProgress checkpoints of index.js:1193-1611),
@@ -33,7 +33,7 @@ const native = require(path.join(__dirname, 'imagestitch.node'));
 
 const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
-const FILTER = { nearest: 0, bilinear: 1, area: 2 };
+const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
 const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'devices', 'split'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
