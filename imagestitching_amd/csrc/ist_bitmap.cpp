@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ist_ctx.h"
+#include "ist_decode.h"
 
 using namespace ist;
 

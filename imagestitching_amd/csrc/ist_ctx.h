@@ -1,5 +1,5 @@
-// ist_ctx.h — the two opaque handles of the C-ABI, shared by the runtime (ist_runtime.cpp) and the device-group layer
-// (ist_mgpu.cpp).  Reference anchors: a context stands for the canvas node obtained at pages/index/index.js:1196-1204; a
+// ist_ctx.h — the two opaque handles of the C-ABI and the helpers every translation unit that works on a context shares
+// (device scratch, streams, job tables, readback).  Reference anchors: a context stands for the canvas node obtained at pages/index/index.js:1196-1204; a
 // job for the offscreen canvas + the draws recorded on it (utils/canvas.js:131-150, index.js:1391-1428, 1532-1551).
 #ifndef IST_CTX_H_
 #define IST_CTX_H_
@@ -103,6 +103,8 @@ struct ist_job {
 
 // return IST_E_HIP from the calling function when a HIP call fails
 #define IST_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return ist::fail(IST_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+// the same with a fixed message (the runtime's error state is cleared)
+#define IST_HIP_OR(expr, msg) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return ist::fail(IST_E_HIP, msg); } } while (0)
 
 namespace ist {
 
@@ -118,6 +120,8 @@ struct DeviceGuard {
 
 // grow-only device scratch
 int grow_device(void** p, size_t* have, size_t need);
+// carve `bytes` from an arena that is being laid out: the section's offset; *off moves on to the next 256-byte boundary
+inline size_t arena_take(size_t* off, size_t bytes) { const size_t at = *off; *off += round256(bytes); return at; }
 
 // ---- pieces of ist_job_create / ist_job_launch shared with the batch entry points (ist_batch.cpp) ----
 // compile an op list into a job whose tables are NOT uploaded yet (d_tables stays NULL: ist_job_destroy then frees no table block)
@@ -144,13 +148,6 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
 // the PNG file of a canvas in device memory -> a pooled pinned block (need_rows / slab_rows_hint: as png_encode_device_deflate)
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
                 const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0);
-// files -> bitmaps in device memory: the decode of ist_decode_files_device and ist_bitmaps_decode (ist_runtime.cpp).  Once every frame
-// header is read, place(descs, img, pitch) is told what each file holds (descs[i]: size, EXIF orientation, opaque, file_size) and
-// fills img[i] / pitch[i] with where bitmap i goes, or fails the call before anything is decoded.  Caller holds ctx->mu; returns
-// with ctx->stream idle.
-int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
-                        const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place);
-
 
 }  // namespace ist
 

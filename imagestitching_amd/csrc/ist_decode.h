@@ -1,0 +1,80 @@
+// ist_decode.h — files -> bitmaps in HBM (ist_decode.cpp), as far as the file pipeline (ist_files.cpp) and the resident bitmaps
+// (ist_bitmap.cpp) need it.
+#ifndef IST_DECODE_H_
+#define IST_DECODE_H_
+
+#include <chrono>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "ist_ctx.h"
+
+namespace ist {
+
+// what is known of one file: after FileDecoder::headers() the size and orientation, after its worker the decoded form
+struct Dec { int rc = 0; std::string err; bool jpeg = false; JpegImage J; JpegGpuScan G; int w = 0, h = 0, orient = 0; std::vector<uint8_t> px; };
+
+// phase clock: stderr lines under IST_TIMING=1, numbers for ist_ctx_last_timing when the context asked for them.  Phases
+// end with a stream synchronisation only while one of the two is on.
+struct Phases {
+  ist_ctx* ctx; bool print, on;
+  std::chrono::steady_clock::time_point t_prev;
+  explicit Phases(ist_ctx* c);
+  void lap(int phase, const char* what, hipStream_t st);
+};
+
+// where one image's JPEG stages live on the device: offsets into TWO arenas - `main` (coefficient planes, quantisation
+// tables, sample planes: sized from the frame header alone, so it can be laid out before any file is entropy-decoded) and
+// `ent` (the sparse entries of a host-decoded sequential file: sized by the decode)
+struct JpegDevLayout { size_t coef[3], q[3], plane[3], ent[3], start[3], cnt[3]; };
+
+// One call's decode work.  Lifetime: construct -> headers() -> (caller lays out its arena) -> start() -> take(i) for every
+// image the caller consumes, in any order -> finish().  The destructor joins whatever still runs.
+class FileDecoder {
+ public:
+  FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph);
+  ~FileDecoder();
+  // 1. frame headers only (microseconds per file): sizes, sampling, EXIF orientation - what the planner and the arena need
+  int headers();
+  const Dec& dec(int i) const { return dec_[static_cast<size_t>(i)]; }
+  // what the planner needs of each file (orientation from the file, like getImageInfo -> index.js:734)
+  std::vector<ist_image_desc> descs(const int64_t* lens) const;
+  // device bytes of the JPEG stages (coefficient planes, tables, sample planes), carved from *off of the caller's arena
+  void layout(size_t* off);
+  // 2. the workers.  arena: what layout() was sized for; img[i] / pitch[i]: where bitmap i goes (device memory)
+  int start(uint8_t* arena, uint8_t* const* img, const size_t* pitch);
+  // 3. bitmap i is needed by work that will be submitted to `consumer` next.  The first call waits for every image's HOST
+  // side and runs the Huffman batch on `consumer`; then image i is reconstructed (or, a file the GPU path did not take,
+  // uploaded / reconstructed from host coefficients) on `consumer`.  Idempotent per image; one consumer stream per call.
+  int take(int i, hipStream_t consumer);
+  int finish(hipStream_t consumer);       // take() for every image not taken yet
+  int gpu_decoded() const;                // images the GPU entropy decoder took
+
+ private:
+  hipStream_t stream_of(int i) const;
+  void join_all();
+  int first_error();
+  int huffman_all(hipStream_t consumer);
+  int chroma_all(hipStream_t consumer);
+  void worker(int i);
+
+  ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_;
+  std::vector<Dec> dec_;
+  bool running_ = false;                                       // the context's worker pool is on this call's files
+  std::vector<char> on_gpu_, taken_, uploaded_, started_, chroma_done_;      // started_: the image's stream carries uploads of this call; chroma_done_: its chroma planes were made behind the Huffman batch
+  std::vector<JpegDevLayout> jo_;
+  uint8_t* arena_ = nullptr; uint8_t* const* img_ = nullptr; const size_t* pitch_ = nullptr;
+  bool gpu_huffman_ = true, huff_done_ = false, chroma_batch_done_ = false;
+};
+
+// files -> bitmaps in device memory: the decode of ist_decode_files_device and ist_bitmaps_decode.  Once every frame header is
+// read, place(descs, img, pitch) is told what each file holds (descs[i]: size, EXIF orientation, opaque, file_size) and fills
+// img[i] / pitch[i] with where bitmap i goes, or fails the call before anything is decoded.  Caller holds ctx->mu; returns with
+// ctx->stream idle.
+int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
+                        const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place);
+
+}  // namespace ist
+
+#endif  // IST_DECODE_H_

@@ -17,7 +17,7 @@
 //   IST_SPLIT_AUTO   IMAGE when that cut yields full-width parts only (vertical min / max strips), else ROWS
 // Used by the single-process device group (ist_mgpu.cpp) and, through the C-ABI, by the one-process-per-GPU layout
 // (imagestitching_amd/dist.py), so both cut a job the same way.  What is built from a cut (hole_op .. uncovered_rows) is here
-// too: the device group, the file pipeline and the host duplex bands (ist_runtime.cpp) all take their sub-jobs from it.
+// too: the device group, the file pipeline and the host duplex bands all take their sub-jobs from it.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
