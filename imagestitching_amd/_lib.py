@@ -82,6 +82,11 @@ class JobInfo(C.Structure):
                 ("tiles_sample", C.c_int64), ("tiles_general", C.c_int64)]
 
 
+class Preview(C.Structure):
+    _fields_ = [("box_w", C.c_double), ("box_h", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("pixels", C.POINTER(C.c_uint8))]
+
+
 # every symbol include/imagestitch.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ist_abi_version", C.c_int, []),
@@ -184,6 +189,22 @@ SYMBOLS = [
     ("ist_stitch_bitmaps_png", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
                                          C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
     ("ist_debug_bitmap_bytes", C.c_int64, []),
+    ("ist_preview_fit", C.c_int, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("ist_preview_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.c_int32, C.c_int32, C.c_void_p]),
+    ("ist_stitch_png_preview", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
+                                         C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int, C.POINTER(Plan),
+                                         C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64), C.POINTER(Preview)]),
+    ("ist_stitch_bitmaps_png_preview", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
+                                                 C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64), C.POINTER(Preview)]),
+    ("ist_stitch_files_png_preview", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_double,
+                                               C.POINTER(Limits), C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64),
+                                               C.POINTER(Preview)]),
+    ("ist_stitch_paths_png_preview", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_double,
+                                               C.POINTER(Limits), C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64),
+                                               C.POINTER(Preview)]),
+    ("ist_bitmap_preview", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
+    ("ist_debug_preview_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -67,7 +67,7 @@ int take_bitmaps(const ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, Held* he
 // into a pooled pinned block.  The launch is the one render_to_scratch makes for the same op list: the sources differ only in where
 // they are, so the pixels are the host path's byte for byte.
 int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits, int filter,
-                   bool want_png, ist_plan* out_plan, uint8_t** out, int64_t* out_len) {
+                   bool want_png, ist_plan* out_plan, uint8_t** out, int64_t* out_len, ist_preview* preview = nullptr) {
   Held held;
   int rc = take_bitmaps(ctx, bitmaps, n, &held);
   if (rc) return rc;
@@ -95,7 +95,7 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   rc = ist_job_launch(job.get(), src.data(), pitch.data(), n, ctx->scratch_dst, row, ctx->stream);
   if (rc) return rc;
   IST_HIP(hipStreamSynchronize(ctx->stream));      // the canvas is complete; the job's tables may go back to the pool
-  if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len);
+  if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
   else rc = read_back_pooled(ctx->scratch_dst, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
   pg.keep = rc == IST_OK;
   return rc;
@@ -199,14 +199,44 @@ int ist_stitch_bitmaps_rgba8(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, in
   return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, false, out_plan, out_pixels, nullptr);
 }
 
-int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
-                           int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+int ist_stitch_bitmaps_png_preview(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
+                                   int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
+  preview_clear(preview);
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_bitmaps_png: NULL output");
   *out_png = nullptr; *out_len = 0;
   std::memset(out_plan, 0, sizeof(*out_plan));
+  const int rc = preview_check(preview);
+  if (rc) return rc;
   if (n <= 0) return IST_NOTHING_TO_DO;
-  return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, true, out_plan, out_png, out_len);
+  return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, true, out_plan, out_png, out_len, preview);
+}
+
+int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
+                           int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+  return ist_stitch_bitmaps_png_preview(ctx, bitmaps, n, direction, mode, gap, limits, filter, out_plan, out_png, out_len, nullptr);
+}
+
+int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint8_t* dst, size_t dst_pitch) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!b || !dst) return fail(IST_E_INVALID, "ist_bitmap_preview: NULL argument");
+  if (pw < 1 || ph < 1) return fail(IST_E_INVALID, "ist_bitmap_preview: the preview must be at least 1 x 1");
+  const size_t row = static_cast<size_t>(pw) * 4;
+  if (dst_pitch < row) return fail(IST_E_INVALID, "dst_pitch too small");
+  if (b->device != ctx->device)
+    return fail(IST_E_INVALID, "the bitmap lives on device " + std::to_string(b->device) + ", the context on device " + std::to_string(ctx->device));
+  ist_bitmap_retain(b);
+  Held held{{b}};
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
+  int rc = grow_device(&ctx->prev_out, &ctx->prev_out_bytes, row * static_cast<size_t>(ph));
+  if (rc) return rc;
+  // the stored pixels, as ist_bitmap_download's: EXIF orientation is the planner's business
+  rc = preview_enqueue(ctx, b->dev, row_of(b->desc), bitmap_w(b->desc), bitmap_h(b->desc), b->desc.opaque != 0, ctx->prev_out, row, pw, ph, ctx->stream);
+  if (rc) return rc;
+  const std::vector<RowsCopy> down{RowsCopy{ctx->prev_out, nullptr, dst, dst_pitch, row, static_cast<size_t>(ph)}};
+  return stager_of(ctx).download(down, ctx->stream);
 }
 
 }  // extern "C"

@@ -69,6 +69,18 @@ struct ist_ctx {
     hipEvent_t read_done = nullptr;      // behind the downloads that read dst (or file)
   };
   BatchHalf batch_half[2];
+  // previews (ist_preview_host.cpp): the partial sums of the reduce, grow-only; one reduce owns them at a time - a call on another stream
+  // is ordered behind the event of the one before it
+  void* scratch_prev = nullptr; size_t scratch_prev_bytes = 0;
+  hipEvent_t prev_done = nullptr; bool prev_pending = false; hipStream_t prev_last = nullptr;
+  ist_job* prev_job = nullptr;           // the job path's last one-draw job, kept for the next preview of its shape
+  int64_t prev_job_key[5] = {0, 0, 0, 0, 0};
+  std::mutex prev_mu;
+  // ... of the *_png_preview calls and ist_bitmap_preview: the preview's pixels on their way to the host, the stream the reduce
+  // runs on beside the encoder, and the event that orders it behind the last render
+  void* prev_out = nullptr; size_t prev_out_bytes = 0;
+  hipStream_t prev_stream = nullptr;
+  hipEvent_t prev_ready = nullptr;
 };
 
 namespace ist {
@@ -146,8 +158,34 @@ int ensure_aux(ist_ctx* ctx);             // the context's second stream
 int ensure_render(ist_ctx* ctx);          // the context's render stream
 int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t** out);   // device bytes -> a pooled pinned block
 // the PNG file of a canvas in device memory -> a pooled pinned block (need_rows / slab_rows_hint: as png_encode_device_deflate)
+// preview (optional): + the preview of the canvas, one reduce queued behind the last render (PreviewTail below)
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
-                const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0);
+                const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, ist_preview* preview = nullptr);
+
+// ---- previews (ist_preview_host.cpp) ----
+// the checks of an *_png_preview entry point on its ist_preview (NULL: fine, no preview); clears the outputs
+int preview_check(ist_preview* pv);
+// the outputs of an ist_preview cleared (NULL: nothing): the first thing an *_png_preview entry point does, so that `pixels` is NULL on
+// EVERY failure, the ones that are found before preview_check included
+inline void preview_clear(ist_preview* pv) { if (pv) { pv->width = pv->height = 0; pv->pixels = nullptr; } }
+// one preview enqueued on `stream`: the reduce when both axes shrink, a one-draw IST_FILTER_AREA job otherwise.  Arguments checked by the caller.
+int preview_enqueue(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, int64_t h, bool opaque, void* dst, size_t dst_pitch,
+                    int32_t pw, int32_t ph, hipStream_t stream);
+// The preview of a canvas that an export is reading.  prepare() before the encoder; queue(reader) once every render of the canvas has
+// been ordered in front of `reader`: the reduce and its small copy to pinned memory run on ctx->prev_stream behind that point;
+// finish() after the encoder waits for that stream alone and hands the pixels over.  Whatever happens, nothing is in flight and
+// nothing is leaked when the object goes.
+struct PreviewTail {
+  ist_ctx* ctx; const void* canvas; size_t pitch; int64_t w, h; ist_preview* pv;
+  int32_t pw = 0, ph = 0;
+  uint8_t* host = nullptr;
+  bool queued = false;
+  PreviewTail(ist_ctx* c, const void* cv, size_t p, int64_t w_, int64_t h_, ist_preview* v) : ctx(c), canvas(cv), pitch(p), w(w_), h(h_), pv(v) {}
+  ~PreviewTail();
+  int prepare();
+  int queue(hipStream_t reader);
+  int finish();
+};
 
 }  // namespace ist
 

@@ -57,7 +57,8 @@ int compile_banded(ist_ctx* ctx, int64_t cw, int64_t ch, const uint8_t clear[4],
 
 // (the caller holds ctx->mu and has checked the arguments)
 int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
-                            double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+                            double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len,
+                            ist_preview* preview) {
   const int n = n_images;
   DeviceGuard g(ctx->device);
   Phases ph(ctx);
@@ -206,12 +207,12 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
   int64_t hint_rows = 0;
   for (const ist_part& p : bj.parts) hint_rows = std::max<int64_t>(hint_rows, p.Y1 - p.Y0);
   tl_mark("encoder entered");
-  rc = png_to_host(ctx, d + o_canvas, canvas_pitch, out_plan->canvas_w, out_plan->canvas_h, d + o_png, &host, &len, need_rows, hint_rows);
+  rc = png_to_host(ctx, d + o_canvas, canvas_pitch, out_plan->canvas_w, out_plan->canvas_h, d + o_png, &host, &len, need_rows, hint_rows, preview);
   tl_mark("encoder returned (file in host memory)");
   if (rc == IST_OK) rc = fd.finish(render);               // (images whose draw is clipped away entirely)
   (void)hipStreamSynchronize(render);                     // nothing of this call runs on when the arena is handed to the next
   tl_mark("render stream idle");
-  if (rc) { if (host) pool_give(host); (void)hipStreamSynchronize(ctx->stream); return rc; }
+  if (rc) { if (host) pool_give(host); if (preview && preview->pixels) { pool_give(preview->pixels); preview->pixels = nullptr; preview->width = preview->height = 0; } (void)hipStreamSynchronize(ctx->stream); return rc; }
   ph.lap(IST_PHASE_PNG, "PNG encode (GPU) + D2H, overlapped", ctx->stream);
   ph.lap(IST_PHASE_D2H, "(D2H: inside the PNG phase)", nullptr);
   if (ph.print) std::fprintf(stderr, "[ist timing] %d of %d images decoded by the GPU entropy decoder\n", fd.gpu_decoded(), n);
@@ -301,18 +302,32 @@ extern "C" {
 
 int64_t ist_debug_direct_images(void) { return g_direct_images.load(std::memory_order_relaxed); }
 
+int ist_stitch_files_png_preview(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
+                                 double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png,
+                                 int64_t* out_len, ist_preview* preview) {
+  preview_clear(preview);
+  int rc = check_stitch_call("ist_stitch_files_png", ctx, lens ? files : nullptr, n_images, out_plan, out_png, out_len);
+  if (rc < 0) return rc;
+  const int rcp = preview_check(preview);
+  if (rcp) return rcp;
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return stitch_files_png_locked(ctx, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
+}
+
 int ist_stitch_files_png(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
                          double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png,
                          int64_t* out_len) {
-  const int rc = check_stitch_call("ist_stitch_files_png", ctx, lens ? files : nullptr, n_images, out_plan, out_png, out_len);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  return stitch_files_png_locked(ctx, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len);
+  return ist_stitch_files_png_preview(ctx, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, nullptr);
 }
 
-int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, int direction, int mode, double gap, const ist_limits* limits,
-                         int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths, int n_images, int direction, int mode, double gap, const ist_limits* limits,
+                                 int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
+  preview_clear(preview);
   int rc = check_stitch_call("ist_stitch_paths_png", ctx, paths, n_images, out_plan, out_png, out_len);
+  if (rc < 0) return rc;
+  const int rcp = preview_check(preview);
+  if (rcp) return rcp;
   if (rc) return rc;
   tl_begin();
   struct TlEnd { ~TlEnd() { tl_end("ist_stitch_paths_png"); } } tl_end_guard;
@@ -323,7 +338,12 @@ int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, i
   std::vector<int64_t> lens;
   rc = read_paths(ctx, paths, n_images, &ptr, &lens);
   if (rc) return rc;
-  return stitch_files_png_locked(ctx, ptr.data(), lens.data(), n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len);
+  return stitch_files_png_locked(ctx, ptr.data(), lens.data(), n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
+}
+
+int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, int direction, int mode, double gap, const ist_limits* limits,
+                         int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
+  return ist_stitch_paths_png_preview(ctx, paths, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, nullptr);
 }
 
 }  // extern "C"

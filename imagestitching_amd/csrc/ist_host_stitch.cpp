@@ -191,7 +191,7 @@ int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, 
 
 int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                       const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
-                      uint8_t** out_png, int64_t* out_len) {
+                      uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
   RowBands rb;
   int rc = rb.prepare(ctx, canvas_w, canvas_h, clear_rgba ? clear_rgba : kTransparent, ops, n_ops, images, src, src_pitch, n_images, filter);
   if (rc) return rc;
@@ -223,11 +223,25 @@ int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
   };
   int64_t hint = 0;
   for (int b = 0; b < rb.nb; ++b) hint = std::max<int64_t>(hint, rb.y1(b) - rb.y0(b));
-  rc = png_to_host(ctx, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint);
+  rc = png_to_host(ctx, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint, preview);
   (void)hipStreamSynchronize(R); (void)stager_of(ctx).sync(); (void)hipStreamSynchronize(ctx->stream);
   for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   if (rc == IST_OK) g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
   return rc;
+}
+
+// PNG of a rendered op list (+ the preview of its canvas): the canvas never leaves the device.  The caller has checked the arguments.
+int render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+               const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
+               uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
+  *out_png = nullptr; *out_len = 0;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  int rc = render_png_banded(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len, preview);
+  if (rc != 1) return rc;                      // (1: not applicable, nothing queued)
+  rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  return png_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len, nullptr, 0, preview);
 }
 
 }  // namespace
@@ -265,29 +279,31 @@ int ist_render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8
                    int n_images, int filter, uint8_t** out_png, int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!out_png || !out_len) return fail(IST_E_INVALID, "ist_render_png: NULL output");
-  *out_png = nullptr; *out_len = 0;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  int rc = render_png_banded(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len);
-  if (rc != 1) return rc;                      // (1: not applicable, nothing queued)
-  rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, nullptr, nullptr, nullptr);
-  if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len);
+  return render_png(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len, nullptr);
 }
 
 // plan + render + PNG: onStitch stages 2-5 including the export (index.js:1251-1581), decode excluded
+int ist_stitch_png_preview(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
+                           int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter,
+                           ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
+  preview_clear(preview);
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_png: NULL output");
+  int rc = preview_check(preview);
+  if (rc) return rc;
+  std::vector<ist_op> ops;
+  rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
+  if (rc != IST_OK) return rc;
+  rc = render_png(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
+                  n_images, filter, out_png, out_len, preview);
+  if (rc != IST_OK) ist_plan_free(out_plan);
+  return rc;
+}
+
 int ist_stitch_png(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
                    int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter,
                    ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (!out_plan || !out_png || !out_len) return fail(IST_E_INVALID, "ist_stitch_png: NULL output");
-  std::vector<ist_op> ops;
-  int rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
-  if (rc != IST_OK) return rc;
-  rc = ist_render_png(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
-                      n_images, filter, out_png, out_len);
-  if (rc != IST_OK) ist_plan_free(out_plan);
-  return rc;
+  return ist_stitch_png_preview(ctx, images, src, src_pitch, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, nullptr);
 }
 
 int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,

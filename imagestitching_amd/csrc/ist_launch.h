@@ -49,6 +49,28 @@ struct BatchArgs {
 };
 int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream);
 
+// The preview shrink (ist_preview.hip): a w x h RGBA8 source -> pw x ph, both axes shrinking.  Stage 1 runs groups * chunks * ph
+// workgroups, each over <= chunk_rows source rows of one output row's box and the x footprint of per_group neighbouring output
+// pixels (passes x 256 columns), and leaves one float4 per (output row, chunk, output pixel) in `partial`; stage 2 adds the chunks.
+struct PreviewArgs {
+  const uint8_t* src;
+  size_t src_pitch;
+  uint8_t* dst;
+  size_t dst_pitch;
+  float* partial;           // ph * chunks * pw entries of 4 floats, 16-byte aligned
+  double kx, ky;            // w / pw, h / ph
+  int32_t w, h, pw, ph;
+  int32_t per_group;        // output pixels per workgroup along x
+  int32_t groups;           // ceil(pw / per_group)
+  int32_t passes;           // 256-column passes over a group's footprint (> 1 only with per_group == 1)
+  int32_t sub;              // lanes per output pixel in the column sum: a power of two, 1 .. 64
+  int32_t chunk_rows;       // source rows per workgroup, a multiple of 4
+  int32_t chunks;           // ceil(tallest box / chunk_rows)
+};
+// the geometry above for a shape (pure CPU); false when an axis does not shrink or the source is too large for the kernel's ints
+bool preview_geometry(int64_t w, int64_t h, int32_t pw, int32_t ph, PreviewArgs* out);
+int launch_preview(const PreviewArgs& args, bool opaque, void* stream);
+
 }  // namespace ist
 
 #endif  // IST_LAUNCH_H_

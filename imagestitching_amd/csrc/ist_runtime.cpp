@@ -78,7 +78,22 @@ int ensure_render(ist_ctx* ctx) { return ensure_stream(&ctx->render); }
 // while it is still compressing (png_encode_device_deflate); the stored form is encoded whole and copied once.
 // Caller holds ctx->mu.  Synchronises ctx->stream.
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
-                const std::function<int(int64_t, void*)>& need_rows, int64_t slab_rows_hint) {
+                const std::function<int(int64_t, void*)>& need_rows_in, int64_t slab_rows_hint, ist_preview* preview) {
+  // With a preview: the encoder's request for the canvas's LAST rows is the point behind which every render has been ordered in
+  // front of the stream that asked.  The reduce is queued there, on a stream of its own - beside the last slab's compression, not in
+  // front of it, and with no host wait.  Without one, need_rows is the caller's, untouched.
+  PreviewTail tail(ctx, canvas, pitch, w, h, preview);
+  std::function<int(int64_t, void*)> with_preview;
+  if (preview) {
+    const int rc = tail.prepare();
+    if (rc) return rc;
+    with_preview = [&](int64_t y_end, void* reader) -> int {
+      const int rc2 = need_rows_in ? need_rows_in(y_end, reader) : IST_OK;
+      if (rc2 || y_end < h) return rc2;
+      return tail.queue(static_cast<hipStream_t>(reader));
+    };
+  }
+  const std::function<int(int64_t, void*)>& need_rows = preview ? with_preview : need_rows_in;
   const int64_t cap = ist_png_bound(w, h);
   if (!dfile) {
     const int rc = grow_device(&ctx->scratch_file, &ctx->scratch_file_bytes, static_cast<size_t>(cap));
@@ -93,6 +108,7 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
     if (!ctx->png2 && hipStreamCreateWithFlags(&ctx->png2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->png2 = nullptr; }   // (without it the slabs share one stream)
     const int rc = png_encode_device_deflate(ctx, canvas, pitch, w, h, dfile, cap, &len, ctx->stream, host, ctx->aux, need_rows, slab_rows_hint, ctx->png2);
     if (rc) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamSynchronize(ctx->stream); if (ctx->png2) (void)hipStreamSynchronize(ctx->png2); pool_give(host); return rc; }
+    if (preview) { const int rc2 = tail.finish(); if (rc2) { pool_give(host); return rc2; } }
     *out_png = host; *out_len = len;
     return IST_OK;
   }
@@ -103,6 +119,7 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
   uint8_t* host = nullptr;
   rc = read_back_pooled(dfile, static_cast<size_t>(len), ctx->stream, &host);
   if (rc) return rc;
+  if (preview) { rc = tail.finish(); if (rc) { pool_give(host); return rc; } }
   *out_png = host; *out_len = len;
   return IST_OK;
 }
@@ -148,6 +165,7 @@ int ist_ctx_sync(ist_ctx* ctx) {
   if (ctx->aux) ok = (hipStreamSynchronize(ctx->aux) == hipSuccess) && ok;
   if (ctx->render) ok = (hipStreamSynchronize(ctx->render) == hipSuccess) && ok;
   if (ctx->png2) ok = (hipStreamSynchronize(ctx->png2) == hipSuccess) && ok;
+  if (ctx->prev_stream) ok = (hipStreamSynchronize(ctx->prev_stream) == hipSuccess) && ok;
   if (ctx->stager) ok = (ctx->stager->sync() == IST_OK) && ok;
   if (!ok) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipStreamSynchronize failed"); }
   return IST_OK;
@@ -158,6 +176,12 @@ void ist_ctx_destroy(ist_ctx* ctx) {
   DeviceGuard g(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
+  if (ctx->prev_job) ist_job_destroy(ctx->prev_job);
+  if (ctx->prev_stream) { (void)hipStreamSynchronize(ctx->prev_stream); (void)hipStreamDestroy(ctx->prev_stream); }
+  if (ctx->prev_done) { (void)hipEventSynchronize(ctx->prev_done); (void)hipEventDestroy(ctx->prev_done); }
+  if (ctx->prev_ready) (void)hipEventDestroy(ctx->prev_ready);
+  dev_free(ctx->scratch_prev);
+  dev_free(ctx->prev_out);
   dev_free(ctx->scratch_src);
   dev_free(ctx->scratch_dst);
   dev_free(ctx->scratch_dec);

@@ -11,6 +11,9 @@ and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch), stitch
 launch_jobs(jobs, srcs, outs) (ist_jobs_launch) and encode_png_batch_device(canvases) (ist_png_encode_batch_device).
 Resident bitmaps (ist_bitmap_*): decode_bitmaps(files) / upload_bitmap(image) keep images in HBM, and plan / stitch / stitch_png take
 a list of them in place of host images, so a restitch (reordered, other direction, new gap) uploads and decodes nothing.
+Previews (ist_preview_*): opts['preview'] = (box_w, box_h) on stitch_png / stitch_files adds the canvas shrunk to fit that box to the
+result, reduced from HBM beside the export; Bitmap.preview(box_w, box_h) is a thumbnail of a resident bitmap; preview_device(tensor,
+pw, ph) is the device-to-device form and preview_fit(w, h, box_w, box_h) the fit rule.
 """
 import ctypes as C
 import os
@@ -52,6 +55,8 @@ DEFAULT_OPTS = {
     "edgeAA": None,         # anti-alias fractional rectangle edges by area coverage (IST_FILTER_EDGE_AA); None: on iff `platform` is given (edge_aa_of)
     "pngLevel": None,       # PNG export form of the *_png / stitch_files calls: 0 stored, 1 compressed on the GPU; None = DEFAULT_PNG_LEVEL
     "devices": None,        # list of GPU indices (devices[0] = root): shard the stitch over them from this one process (ist_stitch_rgba8_multi)
+    "preview": None,        # (box_w, box_h): stitch_png / stitch_files also return the canvas shrunk to fit that box (the redraw into the preview
+                            # node, index.js:1597-1603), as result['preview'], HxWx4 uint8.  Refused where no canvas stays in HBM behind an export.
     "split": "auto",        # with devices: "image" (image i -> devices[i mod n], BASELINE configs[3]), "band" (equal output rows per device, cut draw
                             # by draw), "rows" (device s owns a band of canvas rows across ALL draws: full-width bands for horizontal strips and
                             # centred rects too, index.js:1540-1553), "auto" = "image" when its parts are full-width (vertical min / max), else "rows"
@@ -85,6 +90,65 @@ def _merge(opts):
             raise TypeError("unknown stitch option(s): %s" % sorted(unknown))
         o.update(opts)
     return o
+
+
+def _no_preview(o, who, why):
+    if o.get("preview") is not None:
+        raise TypeError("%s: the 'preview' option does not apply (%s)" % (who, why))
+
+
+def _preview_arg(o):
+    """the ist_preview of a call whose opts ask for one, or None"""
+    box = o.get("preview")
+    if box is None:
+        return None
+    if o.get("devices"):
+        raise TypeError("the 'preview' option does not apply with devices= (the canvas of a device group is assembled band by band; "
+                        "previews run on one GPU)")
+    try:
+        bw, bh = box
+        bw, bh = float(bw), float(bh)
+    except (TypeError, ValueError):
+        raise TypeError("preview: expected (box_w, box_h)")
+    pv = L.Preview()
+    pv.box_w, pv.box_h = bw, bh
+    return pv
+
+
+def _take_preview(pv):
+    """HxWx4 uint8 view of the preview an *_png_preview call returned (a pinned block of the pool; ist_free when the last view dies)"""
+    return _take_pixels(pv.pixels, int(pv.width), int(pv.height))
+
+
+def preview_fit(w, h, box_w, box_h):
+    """(pw, ph) of a w x h image fitted into a box (ist_preview_fit; index.js:1600-1602, each side at least 1).  Pure CPU."""
+    pw, ph = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib.ist_preview_fit(int(w), int(h), float(box_w), float(box_h), C.byref(pw), C.byref(ph)))
+    return pw.value, ph.value
+
+
+def preview_device(tensor, pw, ph, out=None, stream=None, opaque=False):
+    """An HxWx4 uint8 CUDA tensor (any row pitch) shrunk to ph x pw x 4 on its device (ist_preview_device): what one drawImage of it
+    into a fresh pw x ph canvas reads back under filter 'area'.  Asynchronous on `stream` (default: the tensor's current stream).
+    opaque: the caller's hint that every alpha byte is 255."""
+    import torch
+    if tensor.dtype != torch.uint8 or tensor.dim() != 3 or tensor.shape[2] != 4 or tensor.stride(2) != 1 or tensor.stride(1) != 4:
+        raise TypeError("expected an HxWx4 uint8 CUDA tensor with dense pixels")
+    if not tensor.is_cuda:
+        raise TypeError("preview_device: the source must be a CUDA tensor (host pixels: upload_bitmap(...).preview(...))")
+    pw, ph = int(pw), int(ph)
+    if pw < 1 or ph < 1:
+        raise L.StitchError(-1, "preview_device: the preview must be at least 1 x 1")
+    if out is None:
+        out = torch.empty((ph, pw, 4), dtype=torch.uint8, device=tensor.device)
+    elif (out.dtype != torch.uint8 or out.dim() != 3 or tuple(out.shape) != (ph, pw, 4) or out.stride(2) != 1 or out.stride(1) != 4 or
+          out.device != tensor.device):
+        raise TypeError("preview_device: out must be a %d x %d x 4 uint8 tensor with dense pixels on the source's device" % (ph, pw))
+    st = stream if stream is not None else torch.cuda.current_stream(tensor.device)
+    L.check(L.lib.ist_preview_device(_ctx(tensor.device.index or 0), C.c_void_p(tensor.data_ptr()), tensor.stride(0), int(tensor.shape[1]),
+                                     int(tensor.shape[0]), 1 if opaque else 0, C.c_void_p(out.data_ptr()), out.stride(0),
+                                     pw, ph, C.c_void_p(st.cuda_stream)))
+    return out
 
 
 def _descs(images):
@@ -200,6 +264,7 @@ def stitch(images, direction, opts=None, device=0):
     images is empty (the reference returns early).
     """
     o = _merge(opts)
+    _no_preview(o, "stitch", "the caller gets the pixels; stitch_png / stitch_files keep the canvas in HBM and can add its preview")
     n = len(images)
     if n == 0:
         return None
@@ -239,7 +304,7 @@ def stitch(images, direction, opts=None, device=0):
     return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
 
 
-_BATCH_REFUSED = ("devices", "split", "pngLevel")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files
+_BATCH_REFUSED = ("devices", "split", "pngLevel", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
 
 
 def _batch_requests(reqs, why):
@@ -503,13 +568,21 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     cplan = L.Plan()
     lim = _limits(o)
     out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    rc = L.check(L.lib.ist_stitch_paths_png(_ctx_png(device, o["pngLevel"]), cpaths, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                            C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
+    pv = _preview_arg(o)
+    if pv is None:
+        rc = L.check(L.lib.ist_stitch_paths_png(_ctx_png(device, o["pngLevel"]), cpaths, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
+                                                C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
+    else:
+        rc = L.check(L.lib.ist_stitch_paths_png_preview(_ctx_png(device, o["pngLevel"]), cpaths, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                                        float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
+                                                        C.byref(pv)))
     if rc == L.IST_NOTHING_TO_DO:
         return None
     w, h = int(cplan.canvas_w), int(cplan.canvas_h)
     L.lib.ist_plan_free(C.byref(cplan))
     res = {"width": w, "height": h, "png": _take_png(out, ln, copy)}
+    if pv is not None:
+        res["preview"] = _take_preview(pv)
     if out_path:
         with open(out_path, "wb") as f:
             f.write(res["png"])
@@ -551,13 +624,22 @@ def stitch_png(images, direction, opts=None, device=0):
     cplan = L.Plan()
     lim = _limits(o)
     out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    rc = L.check(L.lib.ist_stitch_png(_ctx_png(device, o["pngLevel"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                      float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
+    pv = _preview_arg(o)
+    if pv is None:
+        rc = L.check(L.lib.ist_stitch_png(_ctx_png(device, o["pngLevel"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                          float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
+    else:
+        rc = L.check(L.lib.ist_stitch_png_preview(_ctx_png(device, o["pngLevel"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                                  float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
+                                                  C.byref(pv)))
     if rc == L.IST_NOTHING_TO_DO:
         return None
     w, h = int(cplan.canvas_w), int(cplan.canvas_h)
     L.lib.ist_plan_free(C.byref(cplan))
-    return {"width": w, "height": h, "png": _take_png(out, ln)}
+    res = {"width": w, "height": h, "png": _take_png(out, ln)}
+    if pv is not None:
+        res["preview"] = _take_preview(pv)
+    return res
 
 
 def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
@@ -644,6 +726,15 @@ class Bitmap:
         L.check(L.lib.ist_bitmap_download(C.c_void_p(self.handle()), out.ctypes.data, out.strides[0], out.shape[0]))
         return out
 
+    def preview(self, box_w, box_h):
+        """the stored pixels shrunk to fit a box (preview_fit of shape; ist_bitmap_preview): an HxWx4 uint8 thumbnail reduced in HBM,
+        without the download.  EXIF orientation is not applied, as in download()."""
+        rows, cols, _ = self.shape
+        pw, ph = preview_fit(cols, rows, box_w, box_h)
+        out = np.empty((ph, pw, 4), np.uint8)
+        L.check(L.lib.ist_bitmap_preview(_ctx(self.device), C.c_void_p(self.handle()), pw, ph, out.ctypes.data, out.strides[0]))
+        return out
+
     def close(self):
         if self._h:
             L.lib.ist_bitmap_release(C.c_void_p(self._h))
@@ -684,7 +775,13 @@ def _stitch_bitmaps(images, n, direction, o, device, png):
     bms = (C.c_void_p * n)(*[None if b is None else b.handle() for b in images])
     cplan = L.Plan()
     lim = _limits(o)
-    if png:
+    pv = _preview_arg(o) if png else None
+    if png and pv is not None:
+        out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
+        rc = L.check(L.lib.ist_stitch_bitmaps_png_preview(_ctx_png(device, o["pngLevel"]), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                                          float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
+                                                          C.byref(pv)))
+    elif png:
         out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
         rc = L.check(L.lib.ist_stitch_bitmaps_png(_ctx_png(device, o["pngLevel"]), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]],
                                                   float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
@@ -697,7 +794,10 @@ def _stitch_bitmaps(images, n, direction, o, device, png):
     w, h = int(cplan.canvas_w), int(cplan.canvas_h)
     L.lib.ist_plan_free(C.byref(cplan))
     if png:
-        return {"width": w, "height": h, "png": _take_png(out, ln)}
+        res = {"width": w, "height": h, "png": _take_png(out, ln)}
+        if pv is not None:
+            res["preview"] = _take_preview(pv)
+        return res
     return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
 
 

@@ -465,6 +465,60 @@ IST_API int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int
                                    const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len);
 IST_API int64_t ist_debug_bitmap_bytes(void);   /* device bytes held by the bitmaps alive in this process */
 
+/* ---- previews: the stitched canvas, or a bitmap, shrunk from HBM (the redraw that follows the export, index.js:1597-1603: the exported
+ * file is loaded back and drawn into the 343 x 457 preview node, shrunk to fit) ------------------------------------------------------ */
+/* There is no raster rule of its own: the preview of a w x h RGBA8 image at pw x ph is what a fresh transparent pw x ph canvas reads back
+ * after ONE drawImage(img, 0, 0, w, h, 0, 0, pw, ph) under IST_FILTER_AREA - the box over premultiplied values on an axis that shrinks,
+ * the bilinear pair on one that does not, one rounding, straight alpha.  A draw that shrinks on BOTH axes (every preview of a result
+ * larger than its box) runs a source-stationary reduce whose time follows 4 * w * h whatever the ratio (ist_preview.hip): every source
+ * byte is read once, partial sums go to scratch of the context with plain stores and are added in a fixed order (no atomics: the same
+ * input gives the same bytes).  Any other draw is a one-draw IST_FILTER_AREA job of the context.  EXIF orientation is not applied: a
+ * bitmap's preview is of its stored pixels, as ist_bitmap_download's are. */
+/* the fit rule (index.js:1600-1602) in IEEE double, Math.round = floor(x + 0.5): scaleFit = min(box_w / w, box_h / h), *out_w =
+ * round(w * scaleFit), *out_h = round(h * scaleFit).  One deviation: each side is at least 1 (for a strip thin enough the reference
+ * computes 0 and draws nothing).  Like the reference, the rule ENLARGES an image smaller than its box.  Pure CPU.  IST_E_INVALID: w or
+ * h < 1, a box side that is not finite or <= 0, a NULL output. */
+IST_API int ist_preview_fit(int64_t w, int64_t h, double box_w, double box_h, int32_t* out_w, int32_t* out_h);
+/* device to device, asynchronous on `stream` (hipStream_t, NULL = default stream), like ist_job_launch.  src: w x h pixels, rows
+ * src_pitch bytes apart (any multiple of 4 that is >= 4 * w); dst: pw x ph, dst_pitch likewise.  opaque: the caller's hint that every
+ * alpha byte is 255 (the alpha bytes are then not read as weights; the preview's are 255).  The partial sums live in grow-only scratch
+ * of the context; calls on different streams are ordered behind each other by an event, never by a host wait.  The one exception is a
+ * draw that does NOT shrink on both axes (the job path): the context keeps the job of the last such shape, and a call with another
+ * shape destroys it - which waits for the streams it ran on - and compiles a new one, whose tables go up with a blocking copy; a
+ * repeated shape enqueues and returns.  Growing the scratch (a larger shape than any before) frees the old block, which also waits
+ * for the device.  IST_E_NO_CONTEXT;
+ * IST_E_INVALID: NULL buffers, w / h / pw / ph < 1, a short or unaligned pitch; IST_E_NO_DEVICE. */
+IST_API int ist_preview_device(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, int64_t h, int opaque,
+                               void* dst, size_t dst_pitch, int32_t pw, int32_t ph, void* stream);
+/* the preview an *_png_preview call returns beside its file */
+typedef struct ist_preview {
+  double  box_w, box_h;     /* in: the node the preview is fitted into (ist_preview_fit) */
+  int32_t width, height;    /* out */
+  uint8_t* pixels;          /* out: library-owned (pinned pool, release with ist_free); pitch 4 * width */
+} ist_preview;
+/* ist_stitch_png / ist_stitch_bitmaps_png / ist_stitch_files_png / ist_stitch_paths_png, with the preview of the canvas the file was
+ * made from: ONE reduce of the canvas in HBM, queued behind the last render on a stream of its own - beside the encoder's last slab,
+ * not in front of it, and with no host wait before the file's trip over PCIe starts.  The file is byte for byte the one the call
+ * without `preview` returns; preview == NULL IS that call (nothing new is launched).  IST_E_INVALID: a box side that is not finite or
+ * <= 0.  On any failure nothing is returned and preview->pixels is NULL. */
+IST_API int ist_stitch_png_preview(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
+                                   int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter,
+                                   ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview);
+IST_API int ist_stitch_bitmaps_png_preview(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap,
+                                           const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len,
+                                           ist_preview* preview);
+IST_API int ist_stitch_files_png_preview(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images,
+                                         int direction, int mode, double gap, const ist_limits* limits, int filter,
+                                         ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview);
+IST_API int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths, int n_images,
+                                         int direction, int mode, double gap, const ist_limits* limits, int filter,
+                                         ist_plan* out_plan, uint8_t** out_png, int64_t* out_len, ist_preview* preview);
+/* a bitmap's stored pixels at pw x ph into host memory (ph rows of dst_pitch >= 4 * pw bytes): a thumbnail without the 48 MB of
+ * ist_bitmap_download.  IST_E_INVALID: NULL bitmap or dst, pw / ph < 1, a short pitch, a bitmap of another device than the context's. */
+IST_API int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint8_t* dst, size_t dst_pitch);
+/* launches of the source-stationary reduce in this process so far (tests tell it from the job path with it) */
+IST_API int64_t ist_debug_preview_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

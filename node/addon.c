@@ -221,6 +221,7 @@ typedef struct {
   ist_plan plan; uint8_t* pixels; int rc; char err[256];
   napi_deferred deferred; napi_async_work work;
   ist_bitmap** bitmaps; int n_bitmaps;    /* stitchBitmaps: the request's bitmaps (NULL entries allowed), one reference each, taken on the JS thread */
+  int want_preview; ist_preview pv;       /* stitchPng {preview: {width, height}}: the canvas shrunk to fit that box, beside the file */
 } stitch_job;
 
 static void stitch_job_free(napi_env env, stitch_job* j) {
@@ -232,14 +233,38 @@ static void stitch_job_free(napi_env env, stitch_job* j) {
 
 static void free_pixels(napi_env env, void* data, void* hint) { (void)env; (void)hint; ist_free(data); }
 
+/* trailing (previewWidth, previewHeight) arguments of a native PNG call: both numbers -> *pv armed with the box */
+static int preview_parse(napi_env env, napi_value w, napi_value h, ist_preview* pv) {
+  napi_valuetype tw = napi_undefined, th = napi_undefined;
+  napi_typeof(env, w, &tw); napi_typeof(env, h, &th);
+  if (tw != napi_number || th != napi_number) return 0;
+  memset(pv, 0, sizeof *pv);
+  napi_get_value_double(env, w, &pv->box_w);
+  napi_get_value_double(env, h, &pv->box_h);
+  return 1;
+}
+
+/* {width, height, data} over the library's pinned block (ist_free when the Buffer is collected); NULL when it cannot be wrapped */
+static napi_value preview_to_js(napi_env env, ist_preview* pv) {
+  napi_value o, buf;
+  if (napi_create_external_buffer(env, (size_t)pv->width * (size_t)pv->height * 4, pv->pixels, free_pixels, NULL, &buf) != napi_ok) { ist_free(pv->pixels); pv->pixels = NULL; return NULL; }
+  pv->pixels = NULL;
+  napi_create_object(env, &o);
+  set_num(env, o, "width", (double)pv->width);
+  set_num(env, o, "height", (double)pv->height);
+  napi_set_named_property(env, o, "data", buf);
+  return o;
+}
+
 static napi_value stitch_result(napi_env env, stitch_job* j) {
   napi_value o, buf;
   napi_create_object(env, &o);
   const size_t bytes = j->want_png ? (size_t)j->png_len : (size_t)j->plan.canvas_w * (size_t)j->plan.canvas_h * 4;
-  if (napi_create_external_buffer(env, bytes, j->pixels, free_pixels, NULL, &buf) != napi_ok) { ist_free(j->pixels); return NULL; }
+  if (napi_create_external_buffer(env, bytes, j->pixels, free_pixels, NULL, &buf) != napi_ok) { ist_free(j->pixels); if (j->want_preview) ist_free(j->pv.pixels); return NULL; }
   set_num(env, o, "width", (double)j->plan.canvas_w);
   set_num(env, o, "height", (double)j->plan.canvas_h);
   napi_set_named_property(env, o, j->want_png ? "png" : "data", buf);
+  if (j->want_preview && j->pv.pixels) { napi_value pv = preview_to_js(env, &j->pv); if (pv) napi_set_named_property(env, o, "preview", pv); }
   napi_set_named_property(env, o, "plan", plan_to_js(env, &j->plan));
   ist_plan_free(&j->plan);
   return o;
@@ -251,7 +276,8 @@ static void stitch_execute(napi_env env, void* data) {
   ist_ctx* ctx = get_ctx();
   if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
   if (j->bitmaps) {
-    j->rc = j->want_png ? ist_stitch_bitmaps_png(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels, &j->png_len)
+    j->rc = j->want_png ? ist_stitch_bitmaps_png_preview(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels, &j->png_len,
+                                                         j->want_preview ? &j->pv : NULL)
                         : ist_stitch_bitmaps_rgba8(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels);
     if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
     return;
@@ -262,8 +288,8 @@ static void stitch_execute(napi_env env, void* data) {
     j->rc = ist_stitch_rgba8_multi(j->devices, j->ndev, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim,
                                    j->filter, j->split, &j->plan, &j->pixels);
   else if (j->want_png)
-    j->rc = ist_stitch_png(ctx, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim,
-                           j->filter, &j->plan, &j->pixels, &j->png_len);
+    j->rc = ist_stitch_png_preview(ctx, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim,
+                                   j->filter, &j->plan, &j->pixels, &j->png_len, j->want_preview ? &j->pv : NULL);
   else
     j->rc = ist_stitch_rgba8(ctx, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim,
                              j->filter, &j->plan, &j->pixels);
@@ -297,9 +323,9 @@ static void stitch_complete(napi_env env, napi_status status, void* data) {
 }
 
 static stitch_job* stitch_parse(napi_env env, napi_callback_info info, int want_refs) {
-  size_t argc = 9; napi_value argv[9];
+  size_t argc = 11; napi_value argv[11];
   if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6) {
-    napi_throw_type_error(env, NULL, "stitch(images, direction, mode, gap, limits, filter)");
+    napi_throw_type_error(env, NULL, "stitch(images, direction, mode, gap, limits, filter, asPng, devices, split, previewWidth, previewHeight)");
     return NULL;
   }
   stitch_job* j = (stitch_job*)calloc(1, sizeof *j);
@@ -321,6 +347,7 @@ static stitch_job* stitch_parse(napi_env env, napi_callback_info info, int want_
     }
   }
   if (argc > 8) { napi_get_value_int32(env, argv[8], &v); j->split = v; }
+  if (argc > 10 && j->want_png) j->want_preview = preview_parse(env, argv[9], argv[10], &j->pv);
   return j;
 }
 
@@ -343,6 +370,7 @@ typedef struct {
   int n; const uint8_t** files; int64_t* lens; napi_ref* refs;
   int direction, mode, filter; double gap; ist_limits lim;
   ist_plan plan; uint8_t* png; int64_t png_len; int rc; char err[256];
+  int want_preview; ist_preview pv;
   napi_deferred deferred; napi_async_work work;
 } files_job;
 
@@ -351,7 +379,8 @@ static void files_execute(napi_env env, void* data) {
   files_job* j = (files_job*)data;
   ist_ctx* ctx = get_ctx();
   if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
-  j->rc = ist_stitch_files_png(ctx, j->files, j->lens, j->n, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->png, &j->png_len);
+  j->rc = ist_stitch_files_png_preview(ctx, j->files, j->lens, j->n, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->png, &j->png_len,
+                                       j->want_preview ? &j->pv : NULL);
   if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
 }
 
@@ -364,8 +393,10 @@ static void files_complete(napi_env env, napi_status status, void* data) {
     napi_value o, buf;
     napi_create_object(env, &o);
     if (napi_create_external_buffer(env, (size_t)j->png_len, j->png, free_pixels, NULL, &buf) != napi_ok) {
-      ist_free(j->png); napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the PNG buffer"));
+      ist_free(j->png); if (j->want_preview) ist_free(j->pv.pixels);
+      napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the PNG buffer"));
     } else {
+      if (j->want_preview && j->pv.pixels) { napi_value pv = preview_to_js(env, &j->pv); if (pv) napi_set_named_property(env, o, "preview", pv); }
       set_num(env, o, "width", (double)j->plan.canvas_w); set_num(env, o, "height", (double)j->plan.canvas_h);
       napi_set_named_property(env, o, "png", buf);
       napi_set_named_property(env, o, "plan", plan_to_js(env, &j->plan));
@@ -379,8 +410,8 @@ static void files_complete(napi_env env, napi_status status, void* data) {
 }
 
 static napi_value js_stitch_files(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
-  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6) { napi_throw_type_error(env, NULL, "stitchFiles(files, direction, mode, gap, limits, filter)"); return NULL; }
+  size_t argc = 8; napi_value argv[8];
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6) { napi_throw_type_error(env, NULL, "stitchFiles(files, direction, mode, gap, limits, filter, previewWidth, previewHeight)"); return NULL; }
   bool is_arr = false; uint32_t n = 0;
   if (napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, NULL, "files must be an array of Buffers"); return NULL; }
   napi_get_array_length(env, argv[0], &n);
@@ -403,6 +434,7 @@ static napi_value js_stitch_files(napi_env env, napi_callback_info info) {
   napi_get_value_double(env, argv[3], &j->gap);
   limits_parse(env, argv[4], &j->lim);
   napi_get_value_int32(env, argv[5], &v); j->filter = v;
+  if (argc > 7) j->want_preview = preview_parse(env, argv[6], argv[7], &j->pv);
   napi_value promise, name;
   CHECK(napi_create_promise(env, &j->deferred, &promise));
   napi_create_string_utf8(env, "imagestitch.stitchFiles", NAPI_AUTO_LENGTH, &name);
@@ -909,6 +941,33 @@ static napi_value js_bitmap_download(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* bitmapPreview(handle, boxWidth, boxHeight) -> {width, height, data}: the stored pixels shrunk to fit the box (ist_preview_fit, then
+ * ist_bitmap_preview: reduced in GPU memory, only the preview crosses PCIe) */
+static napi_value js_bitmap_preview(napi_env env, napi_callback_info info) {
+  size_t argc = 3; napi_value argv[3];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) { napi_throw_type_error(env, NULL, "bitmapPreview(handle, width, height)"); return NULL; }
+  ist_bitmap* b = bitmap_of(env, argv[0]);
+  if (!b) return NULL;
+  ist_preview pv;
+  if (!preview_parse(env, argv[1], argv[2], &pv)) { napi_throw_type_error(env, NULL, "bitmapPreview(handle, width, height): the box sides must be numbers"); return NULL; }
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { napi_throw(env, make_error(env, IST_E_NO_DEVICE, g_ctx_err)); return NULL; }
+  ist_image_desc d;
+  ist_bitmap_desc(b, &d);
+  int rc = ist_preview_fit(d.bmp_width > 0 ? d.bmp_width : d.width, d.bmp_height > 0 ? d.bmp_height : d.height, pv.box_w, pv.box_h, &pv.width, &pv.height);
+  if (rc < 0) return throw_ist(env, rc);
+  void* out_data = NULL; napi_value buf, o;
+  if (napi_create_buffer(env, (size_t)pv.width * (size_t)pv.height * 4, &out_data, &buf) != napi_ok) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  rc = ist_bitmap_preview(ctx, b, pv.width, pv.height, (uint8_t*)out_data, (size_t)pv.width * 4);
+  if (rc < 0) return throw_ist(env, rc);
+  napi_create_object(env, &o);
+  set_num(env, o, "width", (double)pv.width);
+  set_num(env, o, "height", (double)pv.height);
+  napi_set_named_property(env, o, "data", buf);
+  return o;
+}
+
 /* bitmapRelease(handle): drops the handle's reference (a released handle: nothing) */
 static napi_value js_bitmap_release(napi_env env, napi_callback_info info) {
   size_t argc = 1; napi_value argv[1];
@@ -923,10 +982,10 @@ static napi_value js_bitmap_release(napi_env env, napi_callback_info info) {
 /* stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng): every bitmap is retained HERE, on the JS thread, so that a
  * release() or a collection between this call and the work's execution cannot free it */
 static stitch_job* stitch_bitmaps_parse(napi_env env, napi_callback_info info) {
-  size_t argc = 7; napi_value argv[7];
+  size_t argc = 9; napi_value argv[9];
   bool is_arr = false; uint32_t n = 0;
   if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
-    napi_throw_type_error(env, NULL, "stitchBitmaps(bitmaps, direction, mode, gap, limits, filter, asPng)");
+    napi_throw_type_error(env, NULL, "stitchBitmaps(bitmaps, direction, mode, gap, limits, filter, asPng, previewWidth, previewHeight)");
     return NULL;
   }
   napi_get_array_length(env, argv[0], &n);
@@ -950,6 +1009,7 @@ static stitch_job* stitch_bitmaps_parse(napi_env env, napi_callback_info info) {
   limits_parse(env, argv[4], &j->lim);
   napi_get_value_int32(env, argv[5], &v); j->filter = v;
   if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; }
+  if (argc > 8 && j->want_png) j->want_preview = preview_parse(env, argv[7], argv[8], &j->pv);
   return j;
 }
 
@@ -1011,6 +1071,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"decodeBitmaps", NULL, js_decode_bitmaps, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDownload", NULL, js_bitmap_download, NULL, NULL, NULL, napi_default, NULL},
+      {"bitmapPreview", NULL, js_bitmap_preview, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapRelease", NULL, js_bitmap_release, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBitmaps", NULL, js_stitch_bitmaps, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBitmapsSync", NULL, js_stitch_bitmaps_sync, NULL, NULL, NULL, napi_default, NULL},

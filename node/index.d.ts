@@ -19,6 +19,7 @@ export interface StitchOptions {
   onProgress?: (percent: number) => void;   // stitchProgress checkpoints (index.js:1193-1611)
   pngLevel?: 0 | 1;                         // PNG export form: 0 stored, 1 compressed on the GPU (process-wide once set)
   devices?: number[];                       // GPUs to shard the stitch over from this process; devices[0] is the root (RCCL gather over xGMI)
+  preview?: { width: number; height: number };   // stitchPng / stitchFiles only: also resolve the canvas shrunk to fit this box (the preview node, index.js:1597-1603); refused by stitch, stitchSync, the batches and with `devices`
   split?: 'image' | 'band' | 'rows' | 'auto';   // with devices: image i -> devices[i mod n] | equal output rows per GPU, draw by draw | GPU s owns canvas rows across all draws (horizontal strips: full-width bands) | default 'auto': 'image' when its parts are full-width, else 'rows'
 }
 export interface PlanRect { image: number; orientation: number; dx: number; dy: number; dw: number; dh: number; }
@@ -30,11 +31,12 @@ export interface StitchResult { width: number; height: number; data: Buffer; pla
 export function stitch(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchResult | null>;
 export function stitchSync(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchResult | null;
 export function plan(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchPlan | null;
-// one request of a batch: a stitch on the batch's GPU (devices / split / pngLevel are refused with a TypeError)
-export interface StitchRequest { images: StitchImage[]; direction: Direction; opts?: Omit<StitchOptions, 'devices' | 'split' | 'pngLevel' | 'onProgress'>; }
+// one request of a batch: a stitch on the batch's GPU (devices / split / pngLevel / preview are refused with a TypeError)
+export interface StitchRequest { images: StitchImage[]; direction: Direction; opts?: Omit<StitchOptions, 'devices' | 'split' | 'pngLevel' | 'preview' | 'onProgress'>; }
 export function stitchBatch(requests: StitchRequest[]): Promise<(StitchResult | null)[]>;
 export function stitchBatchSync(requests: StitchRequest[]): (StitchResult | null)[];
-export interface StitchPngResult { width: number; height: number; png: Buffer; plan: StitchPlan; }
+export interface Preview { width: number; height: number; data: Buffer; }     // RGBA8, straight alpha, dense rows
+export interface StitchPngResult { width: number; height: number; png: Buffer; plan: StitchPlan; preview?: Preview; }   // preview: only when opts.preview was given
 export function stitchPng(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchPngResult | null>;
 export function stitchPngBatch(requests: StitchRequest[]): Promise<(StitchPngResult | null)[]>;
 export function stitchPngBatchSync(requests: StitchRequest[]): (StitchPngResult | null)[];
@@ -50,6 +52,7 @@ export class Bitmap {
   readonly width: number; readonly height: number; readonly orientation: number; readonly opaque: boolean; readonly fileSize: number;
   readonly bmpWidth: number; readonly bmpHeight: number;
   download(): Buffer;       // bmpWidth * bmpHeight * 4 bytes, RGBA8
+  preview(width: number, height: number): Preview;   // the stored pixels shrunk to fit the box, reduced in GPU memory (no EXIF turn, as download())
   release(): void;          // idempotent; any other use afterwards throws
 }
 export function decodeBitmaps(files: (Uint8Array | string)[]): Promise<Bitmap[]>;

@@ -10,6 +10,9 @@
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
+ *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
+ *       that box (the redraw into the preview node, index.js:1597-1603), reduced in GPU memory beside the export;
+ *       Bitmap.preview(width, height) is the same of a resident bitmap
  *
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
@@ -24,7 +27,8 @@
  *              on their GPUs, one grouped RCCL send/recv batch over xGMI gathers the bands into the root's canvas),
  *              split: 'image' (image i -> devices[i mod n], the BASELINE layout) | 'band' (equal output rows per GPU, cut draw by draw)
  *                     | 'rows' (GPU s owns a band of canvas rows across ALL draws: full-width bands for horizontal strips too,
- *                     index.js:1540-1553) | 'auto' (default: 'image' when its parts are full-width, else 'rows')}
+ *                     index.js:1540-1553) | 'auto' (default: 'image' when its parts are full-width, else 'rows'),
+ *              preview: {width, height} - stitchPng / stitchFiles only: the box the result's preview is fitted into}
  * Errors reject with Error('拼图失败：' + reason) like the reference's catch (index.js:1618-1624); err.code is the
  * C-ABI code.  No pixel arithmetic happens in JavaScript; there is no CPU fallback.
  */
@@ -35,7 +39,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'devices', 'split'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'devices', 'split', 'preview'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -89,6 +93,18 @@ function groupArgs(opts) {
   if (!(split in SPLIT)) throw new TypeError('unknown split ' + split);
   return [false, o.devices, SPLIT[split]];
 }
+// opts.preview -> the trailing (previewWidth, previewHeight) arguments of a native PNG call ([] without one)
+function previewArgs(opts) {
+  const p = opts ? opts.preview : undefined;
+  if (p === undefined || p === null) return [];
+  if (opts.devices !== undefined && opts.devices !== null) throw new TypeError('preview does not apply with devices: previews run on one GPU');
+  if (typeof p !== 'object' || typeof p.width !== 'number' || typeof p.height !== 'number') throw new TypeError('preview must be {width, height}');
+  return [p.width, p.height];
+}
+// the calls that hand the pixels to the caller, or run a batch, keep no canvas behind an export to preview
+function noPreview(opts, who) {
+  if (opts && opts.preview !== undefined && opts.preview !== null) throw new TypeError(who + ': option preview does not apply (the caller gets the pixels; use stitchPng / stitchFiles)');
+}
 // ---- resident bitmaps ----------------------------------------------------------------------------------------------------------
 const MADE_HERE = Symbol('Bitmap');
 /** One decoded RGBA8 image kept in GPU memory by the library (the page's bitmap cache, index.js:534-627): made by decodeBitmaps /
@@ -108,6 +124,9 @@ class Bitmap {
   }
   /** the pixels as they are stored (bmpWidth x bmpHeight, RGBA8, dense rows) */
   download() { return native.bitmapDownload(this.handle); }
+  /** the stored pixels shrunk to fit a width x height box (index.js:1600-1602; EXIF orientation is not applied, as in download()):
+   *  {width, height, data}, reduced in GPU memory - a thumbnail without the download */
+  preview(width, height) { return native.bitmapPreview(this.handle, width, height); }
   release() { native.bitmapRelease(this.handle); }
 }
 // a request made of Bitmaps -> their native handles (null entries stay null: the library rejects them as a missing image); null for a
@@ -136,7 +155,7 @@ function debugBitmapBytes() { return native.debugBitmapBytes(); }
 
 function stitch(images, direction, opts) {
   let a, h;
-  try { h = bitmapHandles(images, opts); a = args(images, direction, opts).concat(h ? [] : groupArgs(opts)); } catch (e) { return Promise.reject(e); }
+  try { noPreview(opts, 'stitch'); h = bitmapHandles(images, opts); a = args(images, direction, opts).concat(h ? [] : groupArgs(opts)); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);      // `if (!originalImages.length) return;` (index.js:1189): no progress, no error
   if (h) {
     // (the native call retains every bitmap before it returns: a release() from here on does not free one under the stitch)
@@ -145,13 +164,14 @@ function stitch(images, direction, opts) {
   return withProgress(opts, () => native.stitch(...a));
 }
 function stitchSync(images, direction, opts) {
+  noPreview(opts, 'stitchSync');
   const h = bitmapHandles(images, opts);
   const a = args(images, direction, opts).concat(h ? [] : groupArgs(opts));
   if (!a[0].length) return null;
   return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
-const BATCH_REFUSED = ['devices', 'split', 'pngLevel'];
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'preview'];
 function batchArgs(requests) {
   if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
   return requests.map((r, k) => {
@@ -185,13 +205,13 @@ function stitchPngBatchSync(requests) { const a = batchArgs(requests); return a.
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
-  let a, h;
-  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); } catch (e) { return Promise.reject(e); }
+  let a, h, pv;
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
   if (h) {
-    try { return withProgress(opts, () => { pngLevel(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true); }); } catch (e) { return Promise.reject(e); }
+    try { return withProgress(opts, () => { pngLevel(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true, ...pv); }); } catch (e) { return Promise.reject(e); }
   }
-  return withProgress(opts, () => { pngLevel(opts); return native.stitch(...a, true); });
+  return withProgress(opts, () => { pngLevel(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
 }
 /** opts.pngLevel: 0 = stored deflate blocks (file = raw size, fastest), 1 = Paeth + run-length + Huffman on the GPU
  *  (photographs about half, screenshots a few per cent). A process-wide setting of the native context. */
@@ -209,10 +229,11 @@ function decodeImage(file) { return native.decodeImage(file); }
 async function stitchFiles(paths, direction, opts, outPath) {
   const fs = require('fs');
   const a = args([], direction, opts);
+  const pv = previewArgs(opts);
   if (!paths || !paths.length) return null;
   const files = paths.map((p) => fs.readFileSync(p));
   // one native call: Huffman / inflate on host threads, reconstruction + stitch + PNG on the GPU, buffers stay in HBM
-  const res = await withProgress(opts, () => { pngLevel(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5]); });
+  const res = await withProgress(opts, () => { pngLevel(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5], ...pv); });
   if (res && outPath) fs.writeFileSync(outPath, res.png);
   return res;
 }
