@@ -20,6 +20,8 @@ VERTICAL, HORIZONTAL = 0, 1
 MODE_MIN, MODE_MAX, MODE_ORIGINAL = 0, 1, 2
 PLATFORM_OTHER, PLATFORM_IOS, PLATFORM_ANDROID = 0, 1, 2
 FILTER_NEAREST, FILTER_BILINEAR, FILTER_AREA, FILTER_CUBIC = 0, 1, 2, 3
+# ist_debug_cell.path (include/imagestitch.h)
+PATH_FILL, PATH_COPY, PATH_SAMPLE, PATH_GENERAL, PATH_SAMPLE_LDS, PATH_SWAP_LDS, PATH_SAMPLE_STREAM, PATH_AREA_STREAM, PATH_CUBIC_STREAM = range(9)
 SPLIT_IMAGE, SPLIT_BAND, SPLIT_ROWS, SPLIT_AUTO = 0, 1, 2, 3
 
 IST_OK, IST_NOTHING_TO_DO = 0, 1
@@ -69,6 +71,11 @@ class FlatCell(C.Structure):
                 ("src_offset", C.c_int64), ("bg", C.c_uint32), ("opaque", C.c_int32)]
 
 
+class DebugCell(C.Structure):
+    _fields_ = [("path", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32), ("sub_h", C.c_int32),
+                ("X0", C.c_int32), ("Y0", C.c_int32), ("X1", C.c_int32), ("Y1", C.c_int32), ("tiles", C.c_int64)]
+
+
 class StitchRequest(C.Structure):
     _fields_ = [("images", C.POINTER(ImageDesc)), ("src", C.POINTER(C.c_void_p)), ("src_pitch", C.POINTER(C.c_size_t)),
                 ("n_images", C.c_int32), ("direction", C.c_int32), ("mode", C.c_int32), ("gap", C.c_double),
@@ -108,6 +115,8 @@ SYMBOLS = [
     ("ist_op_box", C.c_int, [C.POINTER(Op), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
     ("ist_debug_flat_form", C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int,
                                       C.POINTER(Region), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(FlatCell), C.c_int, C.POINTER(C.c_int)]),
+    ("ist_debug_cells", C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int,
+                                  C.POINTER(Region), C.POINTER(DebugCell), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ist_shard_parts", C.c_int, [C.POINTER(Op), C.c_int, C.c_int64, C.c_int64, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(Part), C.c_int, C.POINTER(C.c_int)]),
     ("ist_shard_row_cuts", C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int32)]),

@@ -725,3 +725,30 @@ extern "C" int ist_debug_flat_form(int64_t canvas_w, int64_t canvas_h, const uin
   *n_cells = n;
   return n > max_cells && max_cells > 0 ? ist::fail(IST_E_INVALID, "ist_debug_flat_form: more cells than max_cells") : IST_OK;
 }
+
+// The cells of a job as ist_job_create compiles them - pure CPU, for tests (tests/test_cell_paths.py restates the classification rule
+// and checks it against these records; the GPU tests assert the form a case runs before they launch it).
+extern "C" int ist_debug_cells(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+                               const ist_image_desc* images, int n_images, int filter, const ist_region* clip, ist_debug_cell* cells,
+                               int max_cells, int* n_cells, int* kernel_kind, int* tile_table) {
+  if (!n_cells || (max_cells > 0 && !cells)) return ist::fail(IST_E_INVALID, "ist_debug_cells: NULL argument");
+  *n_cells = 0;
+  ist::Compiled job;
+  const int rc = ist::compile_ops(canvas_w, canvas_h, clear_rgba ? clear_rgba : ist::kTransparent, ops, n_ops, images, n_images, filter, clip, &job);
+  if (rc != IST_OK) return rc;
+  if (kernel_kind) *kernel_kind = job.kernel_kind;
+  if (tile_table) *tile_table = job.tiles.empty() ? 0 : 1;
+  int n = 0;
+  for (const ist::DevCell& c : job.cells) {
+    if (n < max_cells) {
+      ist_debug_cell& o = cells[n];
+      std::memset(&o, 0, sizeof(o));
+      o.path = c.path; o.tile_w = c.tile_w; o.tile_h = c.tile_h; o.sub_h = c.sub_h;
+      o.X0 = c.X0; o.Y0 = c.Y0; o.X1 = c.X1; o.Y1 = c.Y1;
+      o.tiles = static_cast<int64_t>(c.tiles_x) * ((static_cast<int64_t>(c.Y1) - c.Y0 + c.tile_h - 1) / c.tile_h);
+    }
+    ++n;
+  }
+  *n_cells = n;
+  return n > max_cells && max_cells > 0 ? ist::fail(IST_E_INVALID, "ist_debug_cells: more cells than max_cells") : IST_OK;
+}

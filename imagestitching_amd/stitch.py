@@ -902,6 +902,20 @@ class StitchJob:
             pass
 
 
+def debug_cells(canvas_w, canvas_h, ops, n_ops, descs, n_images, filter="bilinear", clear=(0, 0, 0, 0), clip=None):
+    """The cells Stitcher.compile_ops would compile for the same arguments (ist_debug_cells: pure CPU, no device): returns
+    (cells, kernel_kind, tile_table) with one dict per cell - path (_lib.PATH_*), tile_w, tile_h, sub_h, X0, Y0, X1, Y1, tiles."""
+    clr = (C.c_uint8 * 4)(*clear)
+    region = C.byref(L.Region(*[int(v) for v in clip])) if clip is not None else None
+    f = _FILTERS[filter] if isinstance(filter, str) else int(filter)
+    n, kind, table = C.c_int(0), C.c_int(0), C.c_int(0)
+    L.check(L.lib.ist_debug_cells(int(canvas_w), int(canvas_h), clr, ops, int(n_ops), descs, int(n_images), f, region, None, 0, C.byref(n), None, None))
+    arr = (L.DebugCell * max(1, n.value))()
+    L.check(L.lib.ist_debug_cells(int(canvas_w), int(canvas_h), clr, ops, int(n_ops), descs, int(n_images), f, region, arr, n.value, C.byref(n),
+                                  C.byref(kind), C.byref(table)))
+    return [{k: getattr(arr[i], k) for k, _ in L.DebugCell._fields_} for i in range(n.value)], kind.value, bool(table.value)
+
+
 class Stitcher:
     """Device-resident stitcher: one per GPU (one process per GPU in the multi-GPU layout)."""
 

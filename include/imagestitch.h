@@ -188,6 +188,34 @@ typedef struct ist_flat_cell {
 IST_API int ist_debug_flat_form(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                                 const ist_image_desc* images, int n_images, int filter, const ist_region* clip, int64_t* pitch,
                                 int64_t* dst_offset, ist_flat_cell* cells, int max_cells, int* n_cells);
+/* The tile path of a compiled cell: ist_flat_cell.path and ist_debug_cell.path.  Which one a cell gets depends on its paint stack, on the
+ * filter and on the draw's scales (|kx|, |ky|: source pixels per canvas pixel) alone - never on the pixels.
+ *   0 FILL           a constant colour
+ *   1 COPY           one 1:1 draw at an integer offset over an opaque colour (or an opaque draw): rows are moved, flips included
+ *   2 SAMPLE         one axis-aligned draw, gathered tap by tap straight from HBM (nearest; bilinear where no staged form fits)
+ *   3 GENERAL        anything else: the paint stack evaluated per pixel (overlaps, fractional edge strips, strong quarter-turned shrinks)
+ *   4 SAMPLE_LDS     SAMPLE, bilinear, |kx| <= 4 and |ky| < 2: a stage of sub_h rows' footprint in LDS, tile_h / sub_h stages per tile
+ *   5 SWAP_LDS       one quarter-turned bilinear draw: the footprint staged transposed in LDS; tiles 64 wide and 64 / 32 / 16 high
+ *   6 SAMPLE_STREAM  SAMPLE, bilinear, |ky| >= 2: every wave streams its rows' source row pairs through a ring of sub_h pairs
+ *   7 AREA_STREAM    one axis-aligned shrinking draw under IST_FILTER_AREA: streamed box sums
+ *   8 CUBIC_STREAM   one axis-aligned draw that shrinks on neither axis under IST_FILTER_CUBIC */
+enum { IST_PATH_FILL = 0, IST_PATH_COPY = 1, IST_PATH_SAMPLE = 2, IST_PATH_GENERAL = 3, IST_PATH_SAMPLE_LDS = 4, IST_PATH_SWAP_LDS = 5,
+       IST_PATH_SAMPLE_STREAM = 6, IST_PATH_AREA_STREAM = 7, IST_PATH_CUBIC_STREAM = 8 };
+/* The cells of an op list as ist_job_create compiles them (pure CPU: no context, no device; a test aid).  One record per cell, in
+ * canvas order: its path (above), the tile shape the kernel walks it in (tile_w x tile_h canvas pixels; sub_h = rows per LDS stage
+ * on path 4, ring depth on path 6, else 0), its canvas box (half open) and its number of tiles.  *kernel_kind (optional) = the kernel
+ * form the job launches (0: fill / copy only; 1: + the axis-aligned resampling paths; 2: + SWAP_LDS / GENERAL; 3-4: with AREA_STREAM;
+ * 5-6: with CUBIC_STREAM); *tile_table (optional) = 1 when the job carries a per-tile table, 0 when the kernel finds a tile's cell by
+ * searching the band and cell prefixes (fill / copy jobs, jobs of more than 4 Mi tiles).  max_cells = 0 only counts. */
+typedef struct ist_debug_cell {
+  int32_t path;
+  int32_t tile_w, tile_h, sub_h;
+  int32_t X0, Y0, X1, Y1;
+  int64_t tiles;
+} ist_debug_cell;
+IST_API int ist_debug_cells(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+                            const ist_image_desc* images, int n_images, int filter, const ist_region* clip, ist_debug_cell* cells,
+                            int max_cells, int* n_cells, int* kernel_kind, int* tile_table);
 
 /* ---- sharding: one stitch cut into parts for a group of GPUs (pure CPU) ----------------------------------------- */
 /* The per-image iterations of onStitch are independent once the cursor is planned (index.js:1439-1554).  A PART is a

@@ -35,7 +35,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_header_compiles_as_plain_c(tmp_path):
     c = tmp_path / "t.c"
-    c.write_text('#include "imagestitch.h"\nint main(void){ ist_plan p; (void)p; return sizeof(ist_op) == 128 ? 0 : 1; }\n')
+    c.write_text('#include "imagestitch.h"\nint main(void){ ist_plan p; (void)p; return sizeof(ist_op) == 128 && sizeof(ist_debug_cell) == 40 ? 0 : 1; }\n')
     exe = tmp_path / "t"
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
     assert subprocess.call([str(exe)]) == 0
@@ -45,6 +45,7 @@ def test_struct_layouts_match_ctypes():
     from imagestitching_amd import _lib as L
     assert C.sizeof(L.ImageDesc) == 32 and C.sizeof(L.Limits) == 32 and C.sizeof(L.Rect) == 40
     assert C.sizeof(L.Op) == 128 and C.sizeof(L.Plan) == 64 and C.sizeof(L.JobInfo) == 88
+    assert C.sizeof(L.FlatCell) == 40 and C.sizeof(L.DebugCell) == 40
 
 
 def test_no_cpu_fallback_without_device():

@@ -9,11 +9,30 @@ import pytest
 import imagestitching_amd as ist
 from imagestitching_amd import _lib as L
 from oracle import oracle as O
+from tests import bilinear_forms as B
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
 
 BILINEAR_TOL = 1   # LSB per channel, stated by BASELINE.json north_star
+RARE = U.RareDiff()   # every bilinear _check of the module: beyond +-1 LSB, differences from the oracle must be rare and unbiased
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _rare_and_unbiased():
+    yield
+    print("bilinear stitches against the oracle:", RARE)
+    RARE.check()       # fewer than 1 % of the solid channel bytes differ, no signed drift (tests/util.py)
+
+
+def _forms(pixels, direction, opts=None, orientations=None):
+    """the kernel forms the stitch compiles to (ist_debug_cells): names as in tests/bilinear_forms.py - LDS-256/8, STREAM-128, DIRECT ..."""
+    from imagestitching_amd.stitch import _filter_of, _merge
+    o = _merge(opts)
+    p = ist.plan(U.hip_images(pixels, orientations), direction, o)
+    ops, n_ops = p.ops()
+    cells, _, _ = ist.debug_cells(p.canvas_w, p.canvas_h, ops, n_ops, p._descs, len(pixels), _filter_of(o))
+    return {B.name((c["path"], c["tile_w"], c["tile_h"], c["sub_h"])) for c in cells}
 
 
 def _check(pixels, direction, opts=None, orientations=None):
@@ -28,6 +47,8 @@ def _check(pixels, direction, opts=None, orientations=None):
     else:
         d = U.max_abs_diff(out, ref)
         assert d <= BILINEAR_TOL, "bilinear max |diff| = %d" % d
+        if opts.get("filter", "bilinear") == "bilinear":
+            RARE.add(U.oracle_tolerance(out, ref))
     return out, ref
 
 
@@ -89,6 +110,8 @@ def test_ragged_and_tiny(filt):
 def test_heavy_downscale(filt):
     """the phone-capped plans shrink 12 MP photos 6.6x: nearest gathers directly, bilinear streams row pairs through LDS."""
     px = [U.smooth_image(120, 300, 2000), U.rand_image(121, 260, 1900), U.rand_image(122, 90, 300)]
+    forms = _forms(px, "vertical", {"filter": filt, "mode": "min"})          # 6.67x and 6.33x down, and a copy
+    assert forms == ({"DIRECT", "COPY"} if filt == "nearest" else {"STREAM-64", "COPY"}), forms
     _check(px, "vertical", {"filter": filt, "mode": "min"})
     _check(px, "horizontal", {"filter": filt, "mode": "min"})
     _check(px, "vertical", {"filter": filt, "platform": "android", "maxSide": 256, "maxPixels": 256 * 256})
@@ -124,8 +147,12 @@ def test_lds_staged_path_edges():
     _check(px, "vertical", {"filter": "bilinear", "mode": "max"})
     _check(px, "vertical", {"filter": "bilinear", "mode": "max"}, orientations=[2, 3, 4, 2])
     _check(px, "horizontal", {"filter": "bilinear", "mode": "max", "gap": 1})
+    assert _forms(px, "vertical", {"filter": "bilinear", "mode": "max"}) == {"LDS-256/32", "COPY"}        # enlarged 1.9x .. 500x: the tallest stage
+    assert _forms(px, "horizontal", {"filter": "bilinear", "mode": "max", "gap": 1}) >= {"LDS-256/32", "COPY"}
     _check([U.rand_image(144, 300, 700), U.rand_image(145, 450, 1050)], "vertical", {"filter": "bilinear", "mode": "min"})   # 1.5x down
-    _check([U.rand_image(146, 300, 700), U.rand_image(147, 1200, 2450)], "vertical", {"filter": "bilinear", "mode": "min"})  # 3.5x down
+    assert "LDS-256/8" in _forms([U.rand_image(144, 300, 700), U.rand_image(145, 450, 1050)], "vertical", {"filter": "bilinear", "mode": "min"})
+    _check([U.rand_image(146, 300, 700), U.rand_image(147, 1200, 2450)], "vertical", {"filter": "bilinear", "mode": "min"})  # 3.5x down (streamed: |ky| >= 2)
+    assert "STREAM-128" in _forms([U.rand_image(146, 300, 700), U.rand_image(147, 1200, 2450)], "vertical", {"filter": "bilinear", "mode": "min"})
 
 
 @pytest.mark.parametrize("direction", ["vertical", "horizontal"])
@@ -135,9 +162,12 @@ def test_streamed_path_scales_and_edges(direction):
     that are no multiple of 64, so the store count per row changes), tiles shorter than 8 rows, the bottom-right tile whose
     last source row goes through registers."""
     base = (301, 77) if direction == "vertical" else (77, 301)        # the smallest image fixes the strip's cross size
+    want = {2.0: "STREAM-256", 2.2: "STREAM-256", 2.9: "STREAM-256", 3.5: "STREAM-128", 6.65: "STREAM-64", 12.0: "STREAM-64", 17.0: "DIRECT"}
     for n, k in enumerate([2.0, 2.2, 2.9, 3.5, 6.65, 12.0, 17.0]):
         w, h = int(round(base[0] * k)), int(round(base[1] * k))
         px = [U.rand_image(300 + n, base[1], base[0]), U.rand_image(310 + n, h, w, opaque=(n % 2 == 0)), U.smooth_image(320 + n, h + 3, w + 5)]
+        forms = _forms(px, direction, {"filter": "bilinear", "mode": "min", "gap": n % 3})
+        assert forms - {"FILL"} == {"COPY", want[k]}, (k, forms)
         _check(px, direction, {"filter": "bilinear", "mode": "min", "gap": n % 3})
     px = [U.rand_image(330, 129, 517), U.rand_image(331, 400, 1300), U.rand_image(332, 1033, 2068, opaque=False)]
     for o in (2, 3, 4):
