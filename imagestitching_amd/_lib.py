@@ -23,6 +23,8 @@ FILTER_NEAREST, FILTER_BILINEAR, FILTER_AREA, FILTER_CUBIC = 0, 1, 2, 3
 # ist_debug_cell.path (include/imagestitch.h)
 PATH_FILL, PATH_COPY, PATH_SAMPLE, PATH_GENERAL, PATH_SAMPLE_LDS, PATH_SWAP_LDS, PATH_SAMPLE_STREAM, PATH_AREA_STREAM, PATH_CUBIC_STREAM = range(9)
 SPLIT_IMAGE, SPLIT_BAND, SPLIT_ROWS, SPLIT_AUTO = 0, 1, 2, 3
+THUMB_FILL, THUMB_FIT = 0, 1
+TURN_FLIP_X, TURN_FLIP_Y, TURN_TRANSPOSE = 1, 2, 4
 
 IST_OK, IST_NOTHING_TO_DO = 0, 1
 ERROR_NAMES = {-1: "IST_E_INVALID", -2: "IST_E_SIZE_UNAVAILABLE", -3: "IST_E_OUTPUT_SIZE", -4: "IST_E_NO_CONTEXT",
@@ -92,6 +94,15 @@ class JobInfo(C.Structure):
 class Preview(C.Structure):
     _fields_ = [("box_w", C.c_double), ("box_h", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
                 ("pixels", C.POINTER(C.c_uint8))]
+
+
+class ThumbSpec(C.Structure):
+    _fields_ = [("cell_w", C.c_int32), ("cell_h", C.c_int32), ("mode", C.c_int32), ("apply_orientation", C.c_int32)]
+
+
+class ThumbItem(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("src_x", C.c_int32), ("src_y", C.c_int32), ("src_w", C.c_int32),
+                ("src_h", C.c_int32), ("turn", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
 # every symbol include/imagestitch.h declares: (name, restype, argtypes)
@@ -214,6 +225,12 @@ SYMBOLS = [
                                                C.POINTER(Preview)]),
     ("ist_bitmap_preview", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
     ("ist_debug_preview_launches", C.c_int64, []),
+    ("ist_thumb_layout", C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(ThumbSpec), C.POINTER(ThumbItem), C.POINTER(C.c_int64)]),
+    ("ist_thumbs_device", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(ThumbSpec),
+                                    C.c_void_p, C.c_int64, C.POINTER(ThumbItem), C.c_void_p]),
+    ("ist_bitmaps_thumbs", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(ThumbSpec), C.POINTER(ThumbItem),
+                                     C.POINTER(C.POINTER(C.c_uint8))]),
+    ("ist_debug_thumb_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -31,8 +31,12 @@ constexpr int kKinds = 7;                               // launch_stitch's kerne
 // context keeps at most twice this much device scratch for batches.
 constexpr size_t kSubBatchBytes = size_t(512) << 20;
 
+}  // namespace
+
+namespace ist {
+
 // A ring slot large enough for `bytes`, free to be overwritten: the kernels that read it last time have completed.
-int take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
+int batch_take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
   ist_ctx::BatchSlot& s = ctx->batch_ring[ctx->batch_next];
   ctx->batch_next = (ctx->batch_next + 1) % ist_ctx::kBatchRing;
   if (s.pending) {
@@ -60,7 +64,7 @@ int take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
   return IST_OK;
 }
 
-}  // namespace
+}  // namespace ist
 
 extern "C" {
 
@@ -124,7 +128,7 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
   if (total == 0) return IST_OK;
   std::lock_guard<std::mutex> lk(ctx->batch_mu);
   ist_ctx::BatchSlot* slot = nullptr;
-  int rc = take_slot(ctx, total, &slot);
+  int rc = batch_take_slot(ctx, total, &slot);
   if (rc) return rc;
   uint8_t* h = static_cast<uint8_t*>(slot->host);
   for (const Group& G : grp) {

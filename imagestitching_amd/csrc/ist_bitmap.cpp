@@ -103,6 +103,12 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
 
 }  // namespace
 
+namespace ist {
+void bitmap_view(const ist_bitmap* b, int* device, const uint8_t** row0, size_t* pitch, ist_image_desc* desc) {
+  *device = b->device; *row0 = b->dev; *pitch = row_of(b->desc); *desc = b->desc;
+}
+}  // namespace ist
+
 extern "C" {
 
 int64_t ist_debug_bitmap_bytes(void) { return g_bitmap_bytes.load(std::memory_order_relaxed); }

@@ -151,6 +151,10 @@ int job_launch_args(const ist_job* job, const void* const* src, const size_t* sr
 void note_launch_stream(ist_job* job, void* stream);
 void count_flat_launches(int64_t n);
 
+// a slot of ctx->batch_ring large enough for `bytes` whose last readers have completed (ctx->batch_mu held by the caller, who records
+// slot->done behind the kernels that read the slot's device block and sets slot->pending)
+int batch_take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out);
+
 // ---- the context's helpers of the host-buffer entry points (each stream, ring or pool is made on first use) ----
 inline Stager& stager_of(ist_ctx* ctx) { if (!ctx->stager) ctx->stager.reset(new Stager(ctx->device)); return *ctx->stager; }
 inline WorkerPool& workers_of(ist_ctx* ctx) { if (!ctx->workers) ctx->workers.reset(new WorkerPool()); return *ctx->workers; }
@@ -171,6 +175,10 @@ inline void preview_clear(ist_preview* pv) { if (pv) { pv->width = pv->height = 
 // one preview enqueued on `stream`: the reduce when both axes shrink, a one-draw IST_FILTER_AREA job otherwise.  Arguments checked by the caller.
 int preview_enqueue(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, int64_t h, bool opaque, void* dst, size_t dst_pitch,
                     int32_t pw, int32_t ph, hipStream_t stream);
+// the event of the reduce's scratch, made on first use (ctx->prev_mu held)
+int preview_event(ist_ctx* ctx);
+// what a call that has retained a bitmap reads of it (ist_bitmap.cpp): its device, row 0, the row pitch and the desc
+void bitmap_view(const ist_bitmap* b, int* device, const uint8_t** row0, size_t* pitch, ist_image_desc* desc);
 // The preview of a canvas that an export is reading.  prepare() before the encoder; queue(reader) once every render of the canvas has
 // been ordered in front of `reader`: the reduce and its small copy to pinned memory run on ctx->prev_stream behind that point;
 // finish() after the encoder waits for that stream alone and hands the pixels over.  Whatever happens, nothing is in flight and

@@ -66,10 +66,30 @@ struct PreviewArgs {
   int32_t sub;              // lanes per output pixel in the column sum: a power of two, 1 .. 64
   int32_t chunk_rows;       // source rows per workgroup, a multiple of 4
   int32_t chunks;           // ceil(tallest box / chunk_rows)
+  int32_t turn;             // batch launches only (kTurn* below): where stage 2 stores pixel (X, Y); the single-image kernels store it at (X, Y)
+  int32_t pad_;
 };
 // the geometry above for a shape (pure CPU); false when an axis does not shrink or the source is too large for the kernel's ints
 bool preview_geometry(int64_t w, int64_t h, int32_t pw, int32_t ph, PreviewArgs* out);
 int launch_preview(const PreviewArgs& args, bool opaque, void* stream);
+
+// Many reduces of one form (opaque or not) in ONE launch per stage (ist_thumbs_device).  Three device tables, uploaded per launch:
+//   items[n]          each reduce's PreviewArgs, as launch_preview would pass them by value; `partial` is the item's own range of the
+//                     scratch, `dst` / `dst_pitch` those of the TURNED image ((turn & kTurnTranspose) ? ph x pw : pw x ph)
+//   wg_begin[n + 1]   first stage-1 workgroup of every item (groups * chunks * ph each); wg_begin[n] = the grid
+//   px_begin[n + 1]   first stage-2 thread of every item: pw * ph rounded up to whole workgroups of 256 each, so that a workgroup
+//                     never straddles two items and the lookup stays wave-uniform
+// The turn: reduced pixel (X, Y) is mirrored inside the reduced image (kTurnFlipX: X -> pw - 1 - X, kTurnFlipY likewise), then
+// kTurnTranspose swaps the two coordinates.
+enum : int32_t { kTurnFlipX = 1, kTurnFlipY = 2, kTurnTranspose = 4 };
+struct PreviewBatchArgs {
+  const PreviewArgs* items;
+  const int64_t* wg_begin;
+  const int64_t* px_begin;
+  int32_t n;
+  int32_t pad_;
+};
+int launch_preview_batch(const PreviewBatchArgs& args, int64_t n_wgs, int64_t n_px, bool opaque, void* stream);
 
 }  // namespace ist
 

@@ -22,6 +22,9 @@
 // (at most RC / 4 rows per lane, four waves, a tree over the columns, C chunks): integer-valued until the fractional end weights
 // come in, so that a box of 705 600 taps keeps its mean to well under an LSB where one running fp32 sum loses half of one.
 // Weights, clamping and rounding are those of the area branch of tile_area_stream (opaque) and pixel_general (ist_kernels.hip).
+// Both stages are __device__ bodies of a PreviewArgs: the single-image kernels run one reduce per launch, their batch twins (the
+// thumbnails of a grid of images, ist_thumbs.cpp) many - each workgroup looks its item up first - and stage 2 of a twin stores the
+// pixel where the item's turn (mirrors, transposition: an EXIF orientation) puts it.
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off (the fp64 coordinate math must not be fused).
 #include <hip/hip_runtime.h>
 
@@ -64,15 +67,15 @@ IST_DEV void add_px(f32x4& acc, uint32_t px, float wy) {
   acc += v * wy;
 }
 
+// stage 1 of one reduce: workgroup `id` of its groups * chunks * ph
 template <bool OPAQUE>
-__global__ __launch_bounds__(256) void ist_preview_partial_kernel(const PreviewArgs A) {
+IST_DEV void preview_partial(const PreviewArgs& A, const int64_t id) {
   __shared__ f32x4 wave_sum[4][256];     // per wave: the column sums of its rows
   __shared__ f32x4 col_sum[256];         // the four waves together
   const int tid = static_cast<int>(threadIdx.x);
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // workgroup -> (Y, c, g), g fastest: neighbours in the grid read neighbouring columns of the same rows
-  const int64_t id = static_cast<int64_t>(blockIdx.x);
   const int g = static_cast<int>(id % A.groups);
   const int64_t yc = id / A.groups;
   const int c = static_cast<int>(yc % A.chunks);
@@ -144,9 +147,9 @@ __global__ __launch_bounds__(256) void ist_preview_partial_kernel(const PreviewA
 // round half up to a byte (v in [0, 255]: to_u8 of ist_kernels.hip)
 IST_DEV uint32_t to_u8(float v) { return static_cast<uint32_t>(v + 0.5f); }
 
+// stage 2 of one reduce: thread `idx` of its pw * ph (or beyond them: nothing).  turn: where the pixel is stored (ist_launch.h)
 template <bool OPAQUE>
-__global__ __launch_bounds__(256) void ist_preview_finish_kernel(const PreviewArgs A) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+IST_DEV void preview_finish(const PreviewArgs& A, const int64_t idx, const int turn) {
   if (idx >= static_cast<int64_t>(A.pw) * A.ph) return;
   const int X = static_cast<int>(idx % A.pw), Y = static_cast<int>(idx / A.pw);
   const f32x4* part = reinterpret_cast<const f32x4*>(A.partial) + static_cast<int64_t>(Y) * A.chunks * A.pw + X;
@@ -166,7 +169,54 @@ __global__ __launch_bounds__(256) void ist_preview_finish_kernel(const PreviewAr
     else if (a == 0u) o = 0u;
     else o = min(255u, (r * 255u + a / 2u) / a) | (min(255u, (gg * 255u + a / 2u) / a) << 8) | (min(255u, (b * 255u + a / 2u) / a) << 16) | (a << 24);
   }
-  *reinterpret_cast<uint32_t*>(A.dst + static_cast<size_t>(Y) * A.dst_pitch + static_cast<size_t>(X) * 4) = o;
+  const int Xf = (turn & kTurnFlipX) ? A.pw - 1 - X : X, Yf = (turn & kTurnFlipY) ? A.ph - 1 - Y : Y;
+  const int col = (turn & kTurnTranspose) ? Yf : Xf, row = (turn & kTurnTranspose) ? Xf : Yf;
+  *reinterpret_cast<uint32_t*>(A.dst + static_cast<size_t>(row) * A.dst_pitch + static_cast<size_t>(col) * 4) = o;
+}
+
+template <bool OPAQUE>
+__global__ __launch_bounds__(256) void ist_preview_partial_kernel(const PreviewArgs A) {
+  preview_partial<OPAQUE>(A, static_cast<int64_t>(blockIdx.x));
+}
+
+template <bool OPAQUE>
+__global__ __launch_bounds__(256) void ist_preview_finish_kernel(const PreviewArgs A) {
+  preview_finish<OPAQUE>(A, static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x, 0);
+}
+
+// ------------------------------------------------------------------------------------------------ batch
+// Many reduces in one launch per stage (ist_thumbs_device): the workgroups of all items are numbered item-major, a workgroup finds its
+// item by binary search over the items' first workgroups (stage 2: their first threads, whole workgroups each) and runs the body
+// above on that item's PreviewArgs.  The lookup is wave-uniform; the tables are read through the constant address space, so the
+// item's arguments arrive in scalar registers as a kernarg PreviewArgs does.
+typedef const __attribute__((address_space(4))) PreviewArgs ConstPreviewArgs;
+typedef const __attribute__((address_space(4))) int64_t ConstI64;
+
+IST_DEV int batch_item_of(ConstI64* begin, int n, int64_t at) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {                                   // the last item whose first entry is <= at
+    const int mid = (lo + hi + 1) >> 1;
+    if (begin[mid] <= at) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+
+template <bool OPAQUE>
+__global__ __launch_bounds__(256) void ist_preview_partial_batch_kernel(const PreviewBatchArgs B) {
+  const int64_t wg = static_cast<int64_t>(blockIdx.x);
+  ConstI64* begin = (ConstI64*)B.wg_begin;
+  const int j = batch_item_of(begin, B.n, wg);
+  const PreviewArgs& A = *(const PreviewArgs*)((ConstPreviewArgs*)B.items + j);
+  preview_partial<OPAQUE>(A, wg - begin[j]);
+}
+
+template <bool OPAQUE>
+__global__ __launch_bounds__(256) void ist_preview_finish_batch_kernel(const PreviewBatchArgs B) {
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * 256;
+  ConstI64* begin = (ConstI64*)B.px_begin;
+  const int j = batch_item_of(begin, B.n, first);
+  const PreviewArgs& A = *(const PreviewArgs*)((ConstPreviewArgs*)B.items + j);
+  preview_finish<OPAQUE>(A, first - begin[j] + threadIdx.x, A.turn);
 }
 
 }  // namespace
@@ -185,6 +235,22 @@ int launch_preview(const PreviewArgs& A, bool opaque, void* stream) {
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(IST_E_HIP, std::string("preview launch failed: ") + hipGetErrorString(e));
+  return IST_OK;
+}
+
+int launch_preview_batch(const PreviewBatchArgs& B, int64_t n_wgs, int64_t n_px, bool opaque, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t fin = (n_px + 255) / 256;
+  if (n_wgs < 1 || fin < 1 || n_wgs > 2147483647ll || fin > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "thumbnails too large for one launch");
+  if (opaque) {
+    hipLaunchKernelGGL(ist_preview_partial_batch_kernel<true>, dim3(static_cast<unsigned>(n_wgs)), dim3(256), 0, s, B);
+    hipLaunchKernelGGL(ist_preview_finish_batch_kernel<true>, dim3(static_cast<unsigned>(fin)), dim3(256), 0, s, B);
+  } else {
+    hipLaunchKernelGGL(ist_preview_partial_batch_kernel<false>, dim3(static_cast<unsigned>(n_wgs)), dim3(256), 0, s, B);
+    hipLaunchKernelGGL(ist_preview_finish_batch_kernel<false>, dim3(static_cast<unsigned>(fin)), dim3(256), 0, s, B);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(IST_E_HIP, std::string("thumbnail launch failed: ") + hipGetErrorString(e));
   return IST_OK;
 }
 

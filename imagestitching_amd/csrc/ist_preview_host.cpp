@@ -23,6 +23,8 @@ int ensure_event(hipEvent_t* e) {
 }
 }  // namespace
 
+int preview_event(ist_ctx* ctx) { return ensure_event(&ctx->prev_done); }
+
 // Workgroup shape of the reduce for a shape.  A group of per_group output pixels has an x footprint of at most per_group * kx + 2
 // source columns (+ 1 for a rounding error at either end): one 256-column pass while that fits, otherwise one pixel per group and as
 // many passes as its box needs.  A chunk is 64 rows (16 per wave); boxes taller than 64 chunks get taller chunks, so that stage 2 never

@@ -14,6 +14,9 @@ a list of them in place of host images, so a restitch (reordered, other directio
 Previews (ist_preview_*): opts['preview'] = (box_w, box_h) on stitch_png / stitch_files adds the canvas shrunk to fit that box to the
 result, reduced from HBM beside the export; Bitmap.preview(box_w, box_h) is a thumbnail of a resident bitmap; preview_device(tensor,
 pw, ph) is the device-to-device form and preview_fit(w, h, box_w, box_h) the fit rule.
+Thumbnails (ist_thumb_*): thumbnails(bitmaps, cell) is the page's grid of chosen images - every bitmap cropped to the cell's aspect
+ratio ('fill') or fitted into it ('fit'), turned by its EXIF orientation and shrunk, all in one launch pair and one copy down;
+thumbnails_device(tensors, cell) is the device-to-device form and thumbnail_layout(descs, cell, mode) the rule.
 """
 import ctypes as C
 import os
@@ -149,6 +152,105 @@ def preview_device(tensor, pw, ph, out=None, stream=None, opaque=False):
                                      int(tensor.shape[0]), 1 if opaque else 0, C.c_void_p(out.data_ptr()), out.stride(0),
                                      pw, ph, C.c_void_p(st.cuda_stream)))
     return out
+
+
+_THUMB_MODES = {"fill": L.THUMB_FILL, "fit": L.THUMB_FIT}
+
+
+def _thumb_spec(cell, mode, orient):
+    try:
+        tw, th = cell
+        tw, th = int(tw), int(th)
+    except (TypeError, ValueError):
+        raise TypeError("thumbnails: expected cell = (width, height)")
+    if mode not in _THUMB_MODES:
+        raise ValueError("thumbnails: mode must be 'fill' or 'fit'")
+    return L.ThumbSpec(tw, th, _THUMB_MODES[mode], 1 if orient else 0)
+
+
+def _thumb_items(items, n):
+    return [{"width": int(t.width), "height": int(t.height), "offset": int(t.offset), "window": (int(t.src_x), int(t.src_y), int(t.src_w), int(t.src_h)),
+             "turn": int(t.turn)} for t in items[:n]]
+
+
+def thumbnail_layout(descs, cell, mode, orient=True):
+    """The thumbnail rule (ist_thumb_layout; pure CPU) for a list of images as stitch() takes them, Bitmaps, or (width, height[,
+    orientation]) tuples: per image {'width', 'height'} of the thumbnail, its 'offset' in the output block, the 'window' (x, y, w, h) of
+    the STORED pixels it shows and the 'turn' (TURN_FLIP_X | TURN_FLIP_Y mirror the shrunk window, then TURN_TRANSPOSE swaps its axes)."""
+    n = len(descs)
+    arr = (L.ImageDesc * max(1, n))()
+    for i, d in enumerate(descs):
+        if isinstance(d, Bitmap):
+            arr[i] = d._desc
+        elif isinstance(d, tuple):
+            arr[i] = L.ImageDesc(int(d[0]), int(d[1]), int(d[2]) if len(d) > 2 else 1, 0, 0, 0, 0)
+        else:
+            arr[i] = _descs([d])[0]
+    items = (L.ThumbItem * max(1, n))()
+    spec = _thumb_spec(cell, mode, orient)
+    L.check(L.lib.ist_thumb_layout(arr, n, C.byref(spec), items, None))
+    return _thumb_items(items, n)
+
+
+def thumbnails_device(tensors, cell, mode="fill", orientations=None, opaque=False, out=None, stream=None, orient=True):
+    """HxWx4 uint8 CUDA tensors (any row pitch, one device) -> their thumbnails for a cell (width, height), on the device
+    (ist_thumbs_device): a list of HxWx4 views of ONE dense uint8 tensor.  orientations: EXIF orientation per tensor (default: all 1);
+    orient=False ignores them (the stored pixels, as thumbnails(..., orient=False)).
+    opaque: the caller's hint that every alpha byte is 255, one bool or one per tensor.  out: a 1-D uint8 CUDA tensor that holds the
+    thumbnails back to back.  Asynchronous on `stream` (default: the device's current stream) unless an image is smaller than its
+    cell on an axis."""
+    import torch
+    n = len(tensors)
+    if n == 0:
+        return []
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError("thumbnails_device: the sources must be CUDA tensors (host pixels: upload_bitmap, then thumbnails)")
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 4 or t.stride(2) != 1 or t.stride(1) != 4:
+            raise TypeError("expected HxWx4 uint8 CUDA tensors with dense pixels")
+        if t.device != tensors[0].device:
+            raise TypeError("thumbnails_device: the sources must live on one device")
+    dev = tensors[0].device
+    orientations = [1] * n if orientations is None else list(orientations)
+    opaques = [bool(opaque)] * n if isinstance(opaque, (bool, int)) else [bool(o) for o in opaque]
+    if len(orientations) != n or len(opaques) != n:
+        raise ValueError("thumbnails_device: one orientation (and one opaque flag) per tensor")
+    descs = (L.ImageDesc * n)(*[L.ImageDesc(int(t.shape[1]), int(t.shape[0]), int(o or 0), 0, 0, 1 if q else 0, 0)
+                                for t, o, q in zip(tensors, orientations, opaques)])
+    spec = _thumb_spec(cell, mode, orient)
+    items = (L.ThumbItem * n)()
+    total = C.c_int64(0)
+    L.check(L.lib.ist_thumb_layout(descs, n, C.byref(spec), items, C.byref(total)))
+    if out is None:
+        out = torch.empty((max(1, total.value),), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or out.device != dev or out.numel() < total.value:
+        raise TypeError("thumbnails_device: out must be a dense 1-D uint8 tensor of at least %d bytes on the sources' device" % total.value)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    pitches = (C.c_size_t * n)(*[t.stride(0) for t in tensors])
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    L.check(L.lib.ist_thumbs_device(_ctx(dev.index or 0), descs, ptrs, pitches, n, C.byref(spec), C.c_void_p(out.data_ptr()), out.numel(), items,
+                                    C.c_void_p(st.cuda_stream)))
+    return [out[t.offset:t.offset + 4 * t.width * t.height].view(t.height, t.width, 4) for t in items]
+
+
+def thumbnails(bitmaps, cell, mode="fill", orient=True):
+    """Resident bitmaps -> their thumbnails for a cell (width, height) (ist_bitmaps_thumbs): a list of HxWx4 uint8 arrays, views of ONE
+    block that came down in one copy.  mode 'fill' crops to the cell's aspect ratio (aspectFill), 'fit' fits the whole image into the
+    cell (aspectFit); orient=False shows the stored pixels as Bitmap.preview does."""
+    n = len(bitmaps)
+    if n == 0:
+        return []
+    if not all(isinstance(b, Bitmap) for b in bitmaps):
+        raise TypeError("thumbnails: expected Bitmaps (decode_bitmaps / upload_bitmap)")
+    device = bitmaps[0].device
+    spec = _thumb_spec(cell, mode, orient)
+    bms = (C.c_void_p * n)(*[b.handle() for b in bitmaps])
+    items = (L.ThumbItem * n)()
+    out = C.POINTER(C.c_uint8)()
+    L.check(L.lib.ist_bitmaps_thumbs(_ctx(device), bms, n, C.byref(spec), items, C.byref(out)))
+    total = int(items[n - 1].offset) + 4 * int(items[n - 1].width) * int(items[n - 1].height)
+    block = _take_pixels(out, total // 4, 1).reshape(-1)
+    return [block[t.offset:t.offset + 4 * t.width * t.height].reshape(t.height, t.width, 4) for t in items]
 
 
 def _descs(images):

@@ -547,6 +547,66 @@ IST_API int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t 
 /* launches of the source-stationary reduce in this process so far (tests tell it from the job path with it) */
 IST_API int64_t ist_debug_preview_launches(void);
 
+/* ---- thumbnails: a grid of images cropped, turned and shrunk together (the page's grid of chosen images: one <image mode="aspectFill">
+ * per image at thumbWpx x thumbWpx, pages/index/index.wxml:4-22, cell size from index.js:313-343; the modal image of index.wxml:202 is
+ * the aspectFit form) ------------------------------------------------------------------------------------------------------------- */
+/* The rule, pure CPU, IEEE double without FMA (like ist_preview_fit).  A stored bitmap bw x bh (bmp_width / bmp_height of its desc when
+ * given, else width / height) has orientation o in 1..8 (0 or anything outside 1..8 counts as 1).  Its DISPLAYED size W x H is bw x bh
+ * for o <= 4 and bh x bw for o >= 5, and the displayed image is the standard EXIF one (S the stored array, rows first):
+ *     1  S              2  S[:, ::-1]         3  S[::-1, ::-1]       4  S[::-1]
+ *     5  S.T            6  S.T[:, ::-1]       7  S.T[::-1, ::-1]     8  S.T[::-1]
+ * (6 is the quarter turn clockwise).  Orientation 7 is the TRUE transverse here.  The stitch reproduces utils/canvas.js:187-192 as
+ * written, which is a quirk of drawWithOrientation; an <image> node never goes through that function, so a thumbnail does not copy it.
+ * IST_THUMB_FILL (aspectFill) into a cell tw x th, everything in displayed space:
+ *     tw / W >= th / H:  cw = W, ch = clamp(floor(th * W / tw + 0.5), 1, H);    otherwise:  ch = H, cw = clamp(floor(tw * H / th + 0.5), 1, W)
+ *     cx = floor((W - cw) / 2), cy = floor((H - ch) / 2);  the window (cx, cy, cw, ch) is shrunk to tw x th
+ * IST_THUMB_FIT (aspectFit): the window is the whole image, the output is ist_preview_fit(W, H, tw, th).
+ * apply_orientation == 0: every image is treated as o = 1 (ist_bitmap_preview's stored pixels, with a crop).
+ * Pixels: the window is mapped back into stored space - a mirrored axis puts the floor's spare pixel on the other side
+ * (x_stored = bw - cx - cw) - and the output is the displayed-space orientation of the PREVIEW (the contract above: one drawImage
+ * under IST_FILTER_AREA on a fresh transparent canvas) of that stored window at the output size, sides swapped for o >= 5.  No new
+ * weights, clamps or rounding. */
+enum { IST_THUMB_FILL = 0, IST_THUMB_FIT = 1 };
+/* ist_thumb_item.turn: the reduced stored window is mirrored along x (FLIP_X) and / or y (FLIP_Y), THEN its axes are swapped (TRANSPOSE) */
+enum { IST_TURN_FLIP_X = 1, IST_TURN_FLIP_Y = 2, IST_TURN_TRANSPOSE = 4 };
+typedef struct ist_thumb_spec {
+  int32_t cell_w, cell_h;       /* tw, th: >= 1 */
+  int32_t mode;                 /* IST_THUMB_FILL / IST_THUMB_FIT */
+  int32_t apply_orientation;    /* 0: every image as orientation 1 */
+} ist_thumb_spec;
+typedef struct ist_thumb_item {
+  int32_t width, height;        /* the thumbnail, displayed space */
+  int32_t src_x, src_y, src_w, src_h;   /* the window in STORED space */
+  int32_t turn;                 /* IST_TURN_* bits that take the shrunk stored window to the thumbnail */
+  int32_t reserved;
+  int64_t offset;               /* of the thumbnail's first byte in the output block; rows are 4 * width bytes, thumbnails dense */
+} ist_thumb_item;
+/* the rule for n images: out[k] for descs[k]; offsets are dense (out[k + 1].offset = out[k].offset + 4 * width * height), *out_bytes
+ * (optional) their end.  IST_E_INVALID: NULL descs / spec / out, n < 0, a cell side < 1, an unknown mode, an empty image (the message
+ * names it); IST_E_UNSUPPORTED: n > 4096. */
+IST_API int ist_thumb_layout(const ist_image_desc* descs, int n, const ist_thumb_spec* spec, ist_thumb_item* out, int64_t* out_bytes);
+/* device to device, asynchronous on `stream` like ist_preview_device: image k is bitmap_w x bitmap_h of descs[k] at src[k], rows
+ * pitch[k] bytes apart (a multiple of 4, >= 4 * width); thumbnail k lands at dst + out[k].offset (dst_cap bytes must hold them all).
+ * Images that shrink on both axes are reduced TOGETHER: per form (descs[k].opaque set or not) one stage-1 and one stage-2 launch of
+ * the batch twins of the preview reduce cover every such image of a sub-batch - as many images as keep the partial sums within
+ * 256 MiB of the context's grow-only preview scratch (every image of a 9-image grid, and of any grid of phone photos) - and their
+ * table goes up in one copy.  The crop costs nothing (a window is a base address and a size) and the turn lives in stage 2's store;
+ * pixel for pixel the bytes are ist_preview_device's of the stored window, turned.  An image that does NOT shrink on both axes (smaller
+ * than its cell on an axis: the rare case) is a one-draw IST_FILTER_AREA job whose CTM is the turn; those jobs are launched together
+ * by one ist_jobs_launch and then destroyed, which waits for `stream` - a call with such an image is not asynchronous.  Those jobs
+ * are compiled before anything is enqueued: a call that fails on one of them leaves nothing in flight.
+ * IST_E_NO_CONTEXT; IST_E_INVALID: what ist_thumb_layout rejects, NULL tables, n < 1, a short dst_cap, a short or unaligned pitch;
+ * IST_E_DECODE '图片N解码异常': src[N] is NULL; IST_E_UNSUPPORTED: n > 4096. */
+IST_API int ist_thumbs_device(ist_ctx* ctx, const ist_image_desc* descs, const void* const* src, const size_t* pitch, int n,
+                              const ist_thumb_spec* spec, void* dst, int64_t dst_cap, ist_thumb_item* out, void* stream);
+/* the same over resident bitmaps (descs and pixels are the bitmaps' own), and the thumbnails come down in ONE copy into ONE pinned
+ * block of the pool: *out_pixels (release with ist_free), thumbnail k at out[k].offset.  A NULL bitmap is IST_E_DECODE '图片N解码异常', a
+ * bitmap of another device than the context's IST_E_INVALID; the call holds its own references until it returns.  n < 1: IST_E_INVALID. */
+IST_API int ist_bitmaps_thumbs(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, const ist_thumb_spec* spec, ist_thumb_item* out,
+                               uint8_t** out_pixels);
+/* launch PAIRS (one stage-1 + one stage-2 launch of the batch reduce) made by thumbnail calls in this process so far */
+IST_API int64_t ist_debug_thumb_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

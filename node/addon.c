@@ -968,6 +968,102 @@ static napi_value js_bitmap_preview(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* thumbnails(handles, cellWidth, cellHeight, mode, orient) -> Promise<[{width, height, data}]> (ist_bitmaps_thumbs: the grid of chosen
+ * images, index.wxml:4-22 - every bitmap cropped or fitted, turned and shrunk in one launch pair per form, one copy down).  Every
+ * data Buffer is a view of ONE pinned block, given back to the pool when the last of them is collected.  The bitmaps are retained
+ * HERE, on the JS thread, as stitchBitmaps retains them. */
+typedef struct {
+  int n; ist_bitmap** bitmaps; ist_thumb_spec spec; ist_thumb_item* items; uint8_t* pixels;
+  int rc; char err[256];
+  napi_deferred deferred; napi_async_work work;
+} thumbs_job;
+typedef struct { uint8_t* pixels; int live; } thumbs_block;
+
+static void thumbs_job_free(thumbs_job* j) {
+  for (int i = 0; i < j->n; i++) if (j->bitmaps[i]) ist_bitmap_release(j->bitmaps[i]);
+  if (j->pixels) ist_free(j->pixels);
+  free(j->bitmaps); free(j->items); free(j);
+}
+
+static void thumbs_view_gone(napi_env env, void* data, void* hint) {
+  (void)env; (void)data;
+  thumbs_block* blk = (thumbs_block*)hint;               /* (finalizers run on the JS thread: no lock) */
+  if (--blk->live == 0) { ist_free(blk->pixels); free(blk); }
+}
+
+static void thumbs_execute(napi_env env, void* data) {
+  (void)env;
+  thumbs_job* j = (thumbs_job*)data;
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
+  j->rc = ist_bitmaps_thumbs(ctx, j->bitmaps, j->n, &j->spec, j->items, &j->pixels);
+  if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
+}
+
+static void thumbs_complete(napi_env env, napi_status status, void* data) {
+  thumbs_job* j = (thumbs_job*)data;
+  (void)status;
+  napi_value arr = NULL;
+  if (j->rc < 0) napi_reject_deferred(env, j->deferred, make_error(env, j->rc, j->err));
+  else if (napi_create_array_with_length(env, (size_t)j->n, &arr) == napi_ok) {
+    thumbs_block* blk = (thumbs_block*)calloc(1, sizeof *blk);
+    blk->pixels = j->pixels; blk->live = 1;               /* (this function's own hold, dropped below) */
+    j->pixels = NULL;
+    int ok = 1;
+    for (int i = 0; i < j->n && ok; i++) {
+      const ist_thumb_item* t = &j->items[i];
+      napi_value o, buf;
+      blk->live++;
+      if (napi_create_external_buffer(env, (size_t)t->width * (size_t)t->height * 4, blk->pixels + t->offset, thumbs_view_gone, blk, &buf) != napi_ok) { blk->live--; ok = 0; break; }
+      napi_create_object(env, &o);
+      set_num(env, o, "width", (double)t->width);
+      set_num(env, o, "height", (double)t->height);
+      napi_set_named_property(env, o, "data", buf);
+      ok = napi_set_element(env, arr, (uint32_t)i, o) == napi_ok;
+    }
+    if (--blk->live == 0) { ist_free(blk->pixels); free(blk); }
+    if (ok) napi_resolve_deferred(env, j->deferred, arr);
+    else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not wrap the thumbnails"));
+  } else napi_reject_deferred(env, j->deferred, make_error(env, IST_E_NOMEM, "could not make the result array"));
+  napi_delete_async_work(env, j->work);
+  thumbs_job_free(j);
+}
+
+static napi_value js_thumbnails(napi_env env, napi_callback_info info) {
+  size_t argc = 5; napi_value argv[5];
+  bool is_arr = false; uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 5 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "thumbnails(bitmaps, cellWidth, cellHeight, mode, orient)"); return NULL;
+  }
+  napi_get_array_length(env, argv[0], &n);
+  thumbs_job* j = (thumbs_job*)calloc(1, sizeof *j);
+  j->bitmaps = (ist_bitmap**)calloc(n ? n : 1, sizeof(ist_bitmap*));
+  j->items = (ist_thumb_item*)calloc(n ? n : 1, sizeof(ist_thumb_item));
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value e; napi_valuetype t = napi_undefined;
+    napi_get_element(env, argv[0], i, &e);
+    napi_typeof(env, e, &t);
+    j->n = (int)i + 1;
+    if (t == napi_null || t == napi_undefined) continue;   /* a missing image: '图片N解码异常' from the library */
+    ist_bitmap* b = bitmap_of(env, e);
+    if (!b) { thumbs_job_free(j); return NULL; }
+    ist_bitmap_retain(b);
+    j->bitmaps[i] = b;
+  }
+  double w = 0, h = 0; int32_t v = 0; bool orient = true;
+  napi_get_value_double(env, argv[1], &w); napi_get_value_double(env, argv[2], &h);
+  j->spec.cell_w = w >= 1 && w <= 2147483647.0 ? (int32_t)w : 0;      /* (0: the library's 'the cell must be at least 1 x 1') */
+  j->spec.cell_h = h >= 1 && h <= 2147483647.0 ? (int32_t)h : 0;
+  napi_get_value_int32(env, argv[3], &v); j->spec.mode = v;
+  napi_get_value_bool(env, argv[4], &orient); j->spec.apply_orientation = orient ? 1 : 0;
+  napi_value promise, name;
+  CHECK(napi_create_promise(env, &j->deferred, &promise));
+  napi_create_string_utf8(env, "imagestitch.thumbnails", NAPI_AUTO_LENGTH, &name);
+  CHECK(napi_create_async_work(env, NULL, name, thumbs_execute, thumbs_complete, j, &j->work));
+  CHECK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
 /* bitmapRelease(handle): drops the handle's reference (a released handle: nothing) */
 static napi_value js_bitmap_release(napi_env env, napi_callback_info info) {
   size_t argc = 1; napi_value argv[1];
@@ -1072,6 +1168,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDownload", NULL, js_bitmap_download, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapPreview", NULL, js_bitmap_preview, NULL, NULL, NULL, napi_default, NULL},
+      {"thumbnails", NULL, js_thumbnails, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapRelease", NULL, js_bitmap_release, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBitmaps", NULL, js_stitch_bitmaps, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBitmapsSync", NULL, js_stitch_bitmaps_sync, NULL, NULL, NULL, napi_default, NULL},

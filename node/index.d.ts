@@ -57,6 +57,11 @@ export class Bitmap {
 }
 export function decodeBitmaps(files: (Uint8Array | string)[]): Promise<Bitmap[]>;
 export function uploadBitmap(image: StitchImage): Bitmap;
+// the grid of chosen images (index.wxml:4-22): every bitmap as a thumbnail for the cell - 'fill' (default) crops to the cell's aspect ratio
+// (aspectFill), 'fit' fits the whole image into it (aspectFit) - turned by its EXIF orientation unless orient is false, all of them
+// reduced in GPU memory by one launch pair and brought down in one copy; the results are in the order given
+export interface ThumbnailCell { width: number; height: number; mode?: 'fill' | 'fit'; orient?: boolean; }
+export function thumbnails(bitmaps: Bitmap[], cell: ThumbnailCell): Promise<Preview[]>;
 export function debugBitmapBytes(): number;
 export function stitch(images: Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split'>): Promise<StitchResult | null>;
 export function stitchSync(images: Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split'>): StitchResult | null;

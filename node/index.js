@@ -13,6 +13,8 @@
  *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
  *       that box (the redraw into the preview node, index.js:1597-1603), reduced in GPU memory beside the export;
  *       Bitmap.preview(width, height) is the same of a resident bitmap
+ *   thumbnails(bitmaps, {width, height, mode, orient}) resolves [{width, height, data}]: the grid of chosen images, every bitmap cropped
+ *       ('fill') or fitted ('fit') to the cell, turned by its EXIF orientation and shrunk, in one launch pair and one copy down
  *
  * images[i] = {width, height, data: Uint8Array (RGBA8, straight alpha, row-major), orientation?: 1..8, fileSize?, opaque?}
  * direction = 'vertical' | 'horizontal'                         (data.direction, index.js:16)
@@ -150,6 +152,19 @@ async function decodeBitmaps(files) {
 }
 /** One host image ({width, height, data, orientation?, fileSize?, opaque?}, as stitch takes it) -> a Bitmap with that desc. */
 function uploadBitmap(image) { return new Bitmap(MADE_HERE, native.uploadBitmap([image])); }
+/** The grid of chosen images (index.wxml:4-22): every Bitmap as a thumbnail for a width x height cell, all of them cropped or fitted,
+ *  turned and shrunk in GPU memory by one launch pair and brought down in one copy.  mode 'fill' (default) crops to the cell's aspect
+ *  ratio (aspectFill), 'fit' fits the whole image into the cell (aspectFit, index.wxml:202); orient: false shows the stored pixels as
+ *  Bitmap.preview does.  Resolves [{width, height, data}] (RGBA8, straight alpha, dense rows), in the order given. */
+function thumbnails(bitmaps, cell) {
+  const c = cell || {};
+  if (!Array.isArray(bitmaps) || !bitmaps.every((x) => x === null || x === undefined || x instanceof Bitmap)) return Promise.reject(new TypeError('thumbnails(bitmaps: Bitmap[], {width, height, mode?, orient?})'));
+  if (typeof c.width !== 'number' || typeof c.height !== 'number') return Promise.reject(new TypeError('thumbnails: the cell must be {width, height}'));
+  const mode = c.mode === undefined ? 'fill' : c.mode;
+  if (mode !== 'fill' && mode !== 'fit') return Promise.reject(new TypeError("thumbnails: mode must be 'fill' or 'fit'"));
+  if (!bitmaps.length) return Promise.resolve([]);
+  try { return native.thumbnails(bitmaps.map((x) => (x ? x.handle : null)), c.width, c.height, mode === 'fit' ? 1 : 0, c.orient !== false); } catch (e) { return Promise.reject(e); }      // (a released Bitmap throws on this thread)
+}
 /** device bytes held by the live bitmaps of this process */
 function debugBitmapBytes() { return native.debugBitmapBytes(); }
 
@@ -246,4 +261,4 @@ function plan(images, direction, opts) {
 }
 
 module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan,
-                   decodeBitmaps, uploadBitmap, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+                   decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
