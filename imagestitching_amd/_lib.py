@@ -231,6 +231,18 @@ SYMBOLS = [
     ("ist_bitmaps_thumbs", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(ThumbSpec), C.POINTER(ThumbItem),
                                      C.POINTER(C.POINTER(C.c_uint8))]),
     ("ist_debug_thumb_launches", C.c_int64, []),
+    ("ist_jpeg_quant_tables", C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    ("ist_jpeg_bound", C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    ("ist_jpeg_encode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64), C.c_void_p]),
+    ("ist_jpeg_encode_rgba8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                        C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_stitch_jpeg", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
+                                  C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int, C.c_int, C.c_int, C.POINTER(Plan),
+                                  C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_stitch_bitmaps_jpeg", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
+                                          C.c_int, C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_debug_jpeg_encode_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -63,11 +63,11 @@ int take_bitmaps(const ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, Held* he
   return IST_OK;
 }
 
-// plan + one fused launch from the bitmaps into ctx->scratch_dst (dense canvas rows), then the canvas (want_png = false) or its PNG file
-// into a pooled pinned block.  The launch is the one render_to_scratch makes for the same op list: the sources differ only in where
+// plan + one fused launch from the bitmaps into ctx->scratch_dst (dense canvas rows), then the canvas (want_png = false), its PNG file or
+// (jpeg = {quality, subsampling}) its JPEG file into a pooled pinned block.  The launch is the one render_to_scratch makes for the same op list: the sources differ only in where
 // they are, so the pixels are the host path's byte for byte.
 int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits, int filter,
-                   bool want_png, ist_plan* out_plan, uint8_t** out, int64_t* out_len, ist_preview* preview = nullptr) {
+                   bool want_png, ist_plan* out_plan, uint8_t** out, int64_t* out_len, ist_preview* preview = nullptr, const int* jpeg = nullptr) {
   Held held;
   int rc = take_bitmaps(ctx, bitmaps, n, &held);
   if (rc) return rc;
@@ -83,10 +83,11 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   rc = plan_with_ops(descs.data(), n, direction, mode, gap, limits, out_plan, &ops);
   if (rc != IST_OK) return rc;
   PlanGuard pg{out_plan};
+  const int64_t cw = out_plan->canvas_w, ch = out_plan->canvas_h;
+  if (jpeg) { rc = jpeg_check_export("ist_stitch_bitmaps_jpeg", cw, ch, jpeg[0], jpeg[1]); if (rc) return rc; }
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
-  const int64_t cw = out_plan->canvas_w, ch = out_plan->canvas_h;
   const JobPtr job(ist_job_create(ctx, cw, ch, kTransparent, ops.data(), static_cast<int>(ops.size()), descs.data(), n, filter, nullptr));
   if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
   const size_t row = static_cast<size_t>(cw) * 4;
@@ -95,7 +96,8 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   rc = ist_job_launch(job.get(), src.data(), pitch.data(), n, ctx->scratch_dst, row, ctx->stream);
   if (rc) return rc;
   IST_HIP(hipStreamSynchronize(ctx->stream));      // the canvas is complete; the job's tables may go back to the pool
-  if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
+  if (jpeg) rc = jpeg_to_host(ctx, ctx->scratch_dst, row, cw, ch, jpeg[0], jpeg[1], out, out_len);
+  else if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
   else rc = read_back_pooled(ctx->scratch_dst, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
   pg.keep = rc == IST_OK;
   return rc;
@@ -221,6 +223,19 @@ int ist_stitch_bitmaps_png_preview(ist_ctx* ctx, ist_bitmap* const* bitmaps, int
 int ist_stitch_bitmaps_png(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
                            int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len) {
   return ist_stitch_bitmaps_png_preview(ctx, bitmaps, n, direction, mode, gap, limits, filter, out_plan, out_png, out_len, nullptr);
+}
+
+int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
+                            int filter, int quality, int subsampling, ist_plan* out_plan, uint8_t** out_jpeg, int64_t* out_len) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out_plan || !out_jpeg || !out_len) return fail(IST_E_INVALID, "ist_stitch_bitmaps_jpeg: NULL output");
+  *out_jpeg = nullptr; *out_len = 0;
+  std::memset(out_plan, 0, sizeof(*out_plan));
+  const int rc = jpeg_check_options("ist_stitch_bitmaps_jpeg", quality, subsampling);
+  if (rc) return rc;
+  if (n <= 0) return IST_NOTHING_TO_DO;
+  const int jpeg[2] = {quality, subsampling};
+  return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, false, out_plan, out_jpeg, out_len, nullptr, jpeg);
 }
 
 int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint8_t* dst, size_t dst_pitch) {

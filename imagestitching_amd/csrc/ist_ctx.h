@@ -24,7 +24,8 @@ struct ist_ctx {
   void* scratch_dec = nullptr; size_t scratch_dec_bytes = 0;   // JPEG coefficient / sample planes of ist_decode_files_device
   void* scratch_huff = nullptr; size_t scratch_huff_bytes = 0; // GPU Huffman decoder: scans, tables, per-subsequence state
   void* scratch_png = nullptr; size_t scratch_png_bytes = 0;   // compressing PNG encoder: one slot per 16 KiB chunk + its tables
-  void* scratch_file = nullptr; size_t scratch_file_bytes = 0; // device image of a PNG file on its way to the host
+  void* scratch_file = nullptr; size_t scratch_file_bytes = 0; // device image of a PNG or JPEG file on its way to the host
+  void* scratch_jpg = nullptr; size_t scratch_jpg_bytes = 0;   // JPEG encoder: tables, one slab of coefficients, one slot per restart interval
   void* scratch_arena = nullptr; size_t scratch_arena_bytes = 0; // file pipeline: bitmaps + JPEG planes + canvas + PNG of one call
   // file pipeline (ist_stitch_files_png / ist_decode_files_device): one stream + event + Huffman scratch per image, so that
   // the images' decode chains (upload -> Huffman passes -> reconstruction) overlap each other and the export of the bands
@@ -165,6 +166,14 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
 // preview (optional): + the preview of the canvas, one reduce queued behind the last render (PreviewTail below)
 int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
                 const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, ist_preview* preview = nullptr);
+
+// ---- JPEG export (ist_jpeg_encode.hip) ----
+// the baseline JFIF file of a canvas in device memory -> a pooled pinned block of its real length.  Caller holds ctx->mu; the canvas is
+// complete on ctx->stream, which is synchronised.  The arguments have passed jpeg_check_export.
+int jpeg_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, uint8_t** out_jpeg,
+                 int64_t* out_len);
+int jpeg_check_options(const char* who, int quality, int subsampling);                       // IST_E_INVALID: quality outside 1..100, unknown subsampling
+int jpeg_check_export(const char* who, int64_t w, int64_t h, int quality, int subsampling);  // + IST_E_UNSUPPORTED: a side above 65535
 
 // ---- previews (ist_preview_host.cpp) ----
 // the checks of an *_png_preview entry point on its ist_preview (NULL: fine, no preview); clears the outputs

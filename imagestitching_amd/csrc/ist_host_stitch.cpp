@@ -334,6 +334,33 @@ int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* 
   return rc;
 }
 
+// plan + render + JPEG: ist_stitch_png with the other export (utils/canvas.js:205-221, fileType 'jpg').  The canvas is rendered in one
+// launch into the context's scratch - the pixels every path of ist_stitch_rgba8 delivers - and only the file comes down.
+int ist_stitch_jpeg(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
+                    int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter, int quality,
+                    int subsampling, ist_plan* out_plan, uint8_t** out_jpeg, int64_t* out_len) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out_plan || !out_jpeg || !out_len) return fail(IST_E_INVALID, "ist_stitch_jpeg: NULL output");
+  *out_jpeg = nullptr; *out_len = 0;
+  int rc = jpeg_check_options("ist_stitch_jpeg", quality, subsampling);
+  if (rc) return rc;
+  std::vector<ist_op> ops;
+  rc = plan_with_ops(images, n_images, direction, mode, gap, limits, out_plan, &ops);
+  if (rc != IST_OK) return rc;
+  PlanGuard pg{out_plan};
+  rc = jpeg_check_export("ist_stitch_jpeg", out_plan->canvas_w, out_plan->canvas_h, quality, subsampling);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  rc = render_to_scratch(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
+                         n_images, filter, nullptr, nullptr, nullptr);
+  if (rc == IST_OK)
+    rc = jpeg_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(out_plan->canvas_w) * 4, out_plan->canvas_w, out_plan->canvas_h, quality, subsampling,
+                      out_jpeg, out_len);
+  pg.keep = rc == IST_OK;
+  return rc;
+}
+
 // PNG of host pixels (H2D, encode, D2H)
 int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int64_t w, int64_t h, uint8_t** out_png,
                          int64_t* out_len) {

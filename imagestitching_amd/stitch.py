@@ -762,6 +762,95 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
     return out[off:off + n.value], n.value
 
 
+JPEG_SUBSAMPLING = {"444": 0, "420": 1}      # IST_JPEG_444 / IST_JPEG_420
+
+
+def _jpeg_args(quality, subsampling):
+    """(quality, IST_JPEG_*) of a JPEG export, checked: an integer quality 1..100, subsampling '420' or '444'"""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)):
+        raise TypeError("quality: expected an integer 1..100")
+    if not 1 <= int(quality) <= 100:
+        raise ValueError("quality must be 1..100")
+    if str(subsampling) not in JPEG_SUBSAMPLING:
+        raise ValueError("subsampling must be '420' or '444'")
+    return int(quality), JPEG_SUBSAMPLING[str(subsampling)]
+
+
+def encode_jpeg(pixels, quality=90, subsampling="420", device=0):
+    """Baseline JFIF file (bytes) of an HxWx4 uint8 array, encoded on the GPU (ist_jpeg_encode_rgba8; the export with fileType 'jpg',
+    utils/canvas.js:205-221).  Alpha is not read.  The file is pinned byte for byte by include/imagestitch.h."""
+    q, ss = _jpeg_args(quality, subsampling)
+    a = np.asarray(pixels)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise TypeError("expected an HxWx4 uint8 RGBA array")
+    if a.strides[2] != 1 or a.strides[1] != 4 or a.strides[0] < 4 * a.shape[1] or a.strides[0] % 4:
+        a = np.ascontiguousarray(a).copy()
+    out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
+    L.check(L.lib.ist_jpeg_encode_rgba8(_ctx(device), a.ctypes.data, a.strides[0], a.shape[1], a.shape[0], q, ss, C.byref(out), C.byref(n)))
+    return _take_png(out, n)
+
+
+def encode_jpeg_device(canvas, quality=90, subsampling="420", out=None, stream=None):
+    """JPEG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor, any row pitch that is a multiple of 4) into a CUDA uint8
+    tensor (ist_jpeg_encode_device); returns (tensor, length) like encode_png_device.  out: optional, ist_jpeg_bound + 16 bytes."""
+    import torch
+    q, ss = _jpeg_args(quality, subsampling)
+    if canvas.dtype != torch.uint8 or canvas.dim() != 3 or canvas.shape[2] != 4 or canvas.stride(2) != 1 or canvas.stride(1) != 4:
+        raise TypeError("expected an HxWx4 uint8 CUDA tensor with dense pixels")
+    h, w = int(canvas.shape[0]), int(canvas.shape[1])
+    cap = int(L.lib.ist_jpeg_bound(w, h, ss))
+    if out is None:
+        out = torch.empty(max(cap, 0) + 16, dtype=torch.uint8, device=canvas.device)      # (no bound: the call names what is wrong with the size)
+    base = out.data_ptr()
+    aligned = (base + 15) & ~15
+    st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
+    n = C.c_int64(0)
+    L.check(L.lib.ist_jpeg_encode_device(_ctx(canvas.device.index or 0), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h, q, ss,
+                                         C.c_void_p(aligned), out.numel() - (aligned - base), C.byref(n), C.c_void_p(st.cuda_stream)))
+    off = aligned - base
+    return out[off:off + n.value], n.value
+
+
+def stitch_jpeg(images, direction, opts=None, device=0):
+    """stitch(images, direction, opts) with the JPEG export: returns {'width', 'height', 'jpeg': bytes} (ist_stitch_jpeg /
+    ist_stitch_bitmaps_jpeg).  opts['quality'] (1..100, default 90) and opts['subsampling'] ('420' default, or '444') choose the file;
+    the canvas stays on the device and only the file crosses PCIe.  images may be a list of Bitmaps, as for stitch_png()."""
+    opts = dict(opts or {})
+    q, ss = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
+    o = _merge(opts)
+    _no_preview(o, "stitch_jpeg", "previews are built beside the PNG export")
+    if o.get("devices") is not None:
+        raise TypeError("stitch_jpeg: devices= does not apply (the JPEG export runs on one GPU)")
+    n = len(images)
+    if n == 0:
+        return None
+    cplan = L.Plan()
+    lim = _limits(o)
+    out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
+    if _is_bitmap_request(images, o):
+        bms = (C.c_void_p * n)(*[None if b is None else b.handle() for b in images])
+        rc = L.check(L.lib.ist_stitch_bitmaps_jpeg(_ctx(device), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
+                                                   C.byref(lim), _filter_of(o), q, ss, C.byref(cplan), C.byref(out), C.byref(ln)))
+    else:
+        descs = _descs(images)
+        keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+        for i, im in enumerate(images):
+            a = im["data"] if isinstance(im, dict) else im
+            if a is None:
+                raise L.StitchError(-6, "图片%d解码异常" % i)
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            ptrs[i] = a.ctypes.data
+            pitches[i] = a.strides[0]
+        rc = L.check(L.lib.ist_stitch_jpeg(_ctx(device), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
+                                           float(o["gap"] or 0), C.byref(lim), _filter_of(o), q, ss, C.byref(cplan), C.byref(out), C.byref(ln)))
+    if rc == L.IST_NOTHING_TO_DO:
+        return None
+    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
+    L.lib.ist_plan_free(C.byref(cplan))
+    return {"width": w, "height": h, "jpeg": _take_png(out, ln)}
+
+
 def encode_png_batch_device(canvases, outs=None, stream=None, level=None):
     """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
     launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns

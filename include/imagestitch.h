@@ -607,6 +607,61 @@ IST_API int ist_bitmaps_thumbs(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, 
 /* launch PAIRS (one stage-1 + one stage-2 launch of the batch reduce) made by thumbnail calls in this process so far */
 IST_API int64_t ist_debug_thumb_launches(void);
 
+/* ---- export: baseline JPEG (fileType 'jpg'; the seam is safeCanvasToTempFilePath's `prefer`, utils/canvas.js:205-221; the page's
+ *      other file producer, wx.compressImage, utils/canvas.js:262, writes JPEGs) -------------------------------------------------
+ * A w x h RGBA8 canvas becomes a baseline JFIF file, 1 <= w, h <= 65535 (a larger side: IST_E_UNSUPPORTED, the message names the
+ * side).  quality is 1..100, subsampling IST_JPEG_420 or IST_JPEG_444.  The file is pinned byte for byte; all arithmetic is signed
+ * integer, '>>' an arithmetic shift, '//' floor division of non-negative numbers:
+ *   - ALPHA IS NOT READ: R, G and B are taken as stored.  Every stitched canvas is opaque (the plan's white fill sits under
+ *     source-over); a caller with a translucent canvas composites it first.
+ *   - colour, per pixel:   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *                          Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *                          Cr = ( 32768 R - 27439 G -  5329 B + 8388608 + 32767) >> 16        (all in 0..255, no clamp)
+ *   - padding: the planes are extended to whole MCUs (16x16 for 4:2:0, 8x8 for 4:4:4) by repeating the last column and row;
+ *   - 4:2:0 chroma, after padding: (a + b + c + d + 2) >> 2 over each 2x2;  level shift: s = v - 128;
+ *   - FDCT, integer matrix form: T[u][x] = 2896 for u = 0, else sign * {4017, 3784, 3406, 2896, 2276, 1567, 799}[k-1] with
+ *     k = (2x+1) u mod 32 folded into the first quadrant (= round(8192 a(u) cos((2x+1) u pi / 16)), a(0) = sqrt(1/8), a(u) = 1/2);
+ *     rows r[y][u] = (sum_x T[u][x] s[y][x] + 512) >> 10, columns c[v][u] = (sum_y T[v][y] r[y][u] + 4096) >> 13: c is 8 x the
+ *     orthonormal coefficient, every intermediate fits 32 bits;
+ *   - quantisation tables: libjpeg's rule on T.81 tables K.1 / K.2: scale = 5000 // Q for Q < 50, else 200 - 2 Q;
+ *     q = clamp((base scale + 50) // 100, 1, 255); luma in slot 0, chroma in slot 1;
+ *   - quantise: k = sign(c) ((|c| + 4 q) // (8 q)); AC values clamped to +-1023 (a guard: 8-bit input does not reach it);
+ *   - container: SOI, APP0 (JFIF 1.01, units 0, density 1x1), DQT 0, DQT 1 (8-bit, zig-zag order), DHT DC0, DC1, AC0, AC1 (Annex K
+ *     tables K.3 - K.6), DRI = R, SOF0 (components 1, 2, 3; slots 0, 1, 1), SOS, the intervals, EOI.  One interleaved scan; R =
+ *     ceil(w / MCU width), so one restart interval is one MCU row: its DC predictors restart, it is padded with 1 bits to a byte,
+ *     every 0xFF is followed by 0x00, and RST((k-1) mod 8) stands between intervals k-1 and k.
+ * Such files are eligible for the library's own GPU Huffman decoder (ist_decode_files_device). */
+enum { IST_JPEG_444 = 0, IST_JPEG_420 = 1 };
+/* the two quantisation tables of a quality, natural order.  Pure CPU.  IST_E_INVALID: quality outside 1..100, a NULL table */
+IST_API int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
+/* an upper bound of the file's size that the encoder guarantees; negative for bad arguments (a side < 1 or > 65535, an unknown
+ * subsampling).  Pure CPU.  A block is at most 22 bits of DC (an 11-bit code + 11 bits) + 63 x 26 bits of AC (a 16-bit code + 10
+ * bits) = 1660 bits before stuffing; stuffing at most doubles a byte: 415 bytes per block.  An interval adds at most one pad byte
+ * (which may be stuffed) and its 2-byte marker, the file 629 bytes of header and 2 of EOI:
+ *     bound = 1024 + MCU rows x (blocks per MCU row x 415 + 16). */
+IST_API int64_t ist_jpeg_bound(int64_t w, int64_t h, int subsampling);
+/* encode a canvas that is resident in HBM into a device buffer (16-byte aligned, out_cap >= ist_jpeg_bound): transform, entropy
+ * code and gather run on `stream`, which is synchronised before the call returns (the host lays the intervals out).  Every argument
+ * is checked before anything is enqueued.  IST_E_NO_CONTEXT; IST_E_INVALID: quality outside 1..100, an unknown subsampling, NULL
+ * buffers, w or h < 1, a pitch < 4 w or not a multiple of 4, a short out_cap, an unaligned out; IST_E_UNSUPPORTED: a side above 65535. */
+IST_API int ist_jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling,
+                                   void* out, int64_t out_cap, int64_t* out_len, void* stream);
+/* host pixels -> JPEG bytes (a pooled pinned block of the file's length, release with ist_free) */
+IST_API int ist_jpeg_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int64_t w, int64_t h, int quality, int subsampling,
+                                  uint8_t** out_jpeg, int64_t* out_len);
+/* ist_stitch_png / ist_stitch_bitmaps_png with the JPEG export: the canvas is rendered exactly as for ist_stitch_rgba8 and never
+ * leaves the device; only the file comes down, in one copy of its real length.  The file is byte for byte ist_jpeg_encode_device of
+ * the canvas ist_stitch_rgba8 returns.  Errors: those of the PNG call, and of ist_jpeg_encode_device for quality, subsampling and the
+ * canvas size (checked before anything is rendered). */
+IST_API int ist_stitch_jpeg(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch,
+                            int n_images, int direction, int mode, double gap, const ist_limits* limits, int filter, int quality,
+                            int subsampling, ist_plan* out_plan, uint8_t** out_jpeg, int64_t* out_len);
+IST_API int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap,
+                                    const ist_limits* limits, int filter, int quality, int subsampling, ist_plan* out_plan,
+                                    uint8_t** out_jpeg, int64_t* out_len);
+/* transform launches (one per slab of MCU rows) made by JPEG encodes in this process so far */
+IST_API int64_t ist_debug_jpeg_encode_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

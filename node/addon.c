@@ -16,6 +16,8 @@
  *       -> Promise<({width,height,png,plan} | null)[]> / the array itself  (ist_stitch_png_batch: one GPU, many PNG files)
  *   render(canvasW, canvasH, clearRGBA, ops, images, filter, region, asPng?) -> Buffer (region pixels, or the PNG file)
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
+ *   encodeJpeg(data, width, height, quality, subsampling) -> Buffer;  stitch / stitchBitmaps(..., filter, {quality, subsampling})
+ *       resolve {width,height,jpeg} (ist_stitch_jpeg / ist_stitch_bitmaps_jpeg: asPng given as an object is the JPEG export)
  *   deviceCount(), lastError(), abiVersion()
  *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[]) -> Promise<handle[]>;
  *   bitmapDesc(h) -> {width,height,orientation,bmpWidth,bmpHeight,opaque,fileSize};  bitmapDownload(h) -> Buffer;  bitmapRelease(h);
@@ -222,6 +224,7 @@ typedef struct {
   napi_deferred deferred; napi_async_work work;
   ist_bitmap** bitmaps; int n_bitmaps;    /* stitchBitmaps: the request's bitmaps (NULL entries allowed), one reference each, taken on the JS thread */
   int want_preview; ist_preview pv;       /* stitchPng {preview: {width, height}}: the canvas shrunk to fit that box, beside the file */
+  int want_jpeg, quality, subsampling;    /* stitchJpeg: `pixels` holds the JPEG file bytes (png_len of them) */
 } stitch_job;
 
 static void stitch_job_free(napi_env env, stitch_job* j) {
@@ -232,6 +235,18 @@ static void stitch_job_free(napi_env env, stitch_job* j) {
 }
 
 static void free_pixels(napi_env env, void* data, void* hint) { (void)env; (void)hint; ist_free(data); }
+
+/* the asPng argument of a native stitch call as the JPEG export (stitchJpeg): an object {quality, subsampling: IST_JPEG_*} */
+static int jpeg_parse(napi_env env, napi_value v, int* quality, int* subsampling) {
+  napi_valuetype t = napi_undefined;
+  napi_typeof(env, v, &t);
+  if (t != napi_object) return 0;
+  napi_value q, s; int32_t x = 0;
+  *quality = 90; *subsampling = IST_JPEG_420;
+  if (napi_get_named_property(env, v, "quality", &q) == napi_ok && napi_get_value_int32(env, q, &x) == napi_ok) *quality = x;
+  if (napi_get_named_property(env, v, "subsampling", &s) == napi_ok && napi_get_value_int32(env, s, &x) == napi_ok) *subsampling = x;
+  return 1;
+}
 
 /* trailing (previewWidth, previewHeight) arguments of a native PNG call: both numbers -> *pv armed with the box */
 static int preview_parse(napi_env env, napi_value w, napi_value h, ist_preview* pv) {
@@ -259,11 +274,11 @@ static napi_value preview_to_js(napi_env env, ist_preview* pv) {
 static napi_value stitch_result(napi_env env, stitch_job* j) {
   napi_value o, buf;
   napi_create_object(env, &o);
-  const size_t bytes = j->want_png ? (size_t)j->png_len : (size_t)j->plan.canvas_w * (size_t)j->plan.canvas_h * 4;
+  const size_t bytes = (j->want_png || j->want_jpeg) ? (size_t)j->png_len : (size_t)j->plan.canvas_w * (size_t)j->plan.canvas_h * 4;
   if (napi_create_external_buffer(env, bytes, j->pixels, free_pixels, NULL, &buf) != napi_ok) { ist_free(j->pixels); if (j->want_preview) ist_free(j->pv.pixels); return NULL; }
   set_num(env, o, "width", (double)j->plan.canvas_w);
   set_num(env, o, "height", (double)j->plan.canvas_h);
-  napi_set_named_property(env, o, j->want_png ? "png" : "data", buf);
+  napi_set_named_property(env, o, j->want_jpeg ? "jpeg" : j->want_png ? "png" : "data", buf);
   if (j->want_preview && j->pv.pixels) { napi_value pv = preview_to_js(env, &j->pv); if (pv) napi_set_named_property(env, o, "preview", pv); }
   napi_set_named_property(env, o, "plan", plan_to_js(env, &j->plan));
   ist_plan_free(&j->plan);
@@ -276,7 +291,9 @@ static void stitch_execute(napi_env env, void* data) {
   ist_ctx* ctx = get_ctx();
   if (!ctx) { j->rc = IST_E_NO_DEVICE; snprintf(j->err, sizeof j->err, "%s", g_ctx_err); return; }
   if (j->bitmaps) {
-    j->rc = j->want_png ? ist_stitch_bitmaps_png_preview(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels, &j->png_len,
+    j->rc = j->want_jpeg ? ist_stitch_bitmaps_jpeg(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, j->quality, j->subsampling,
+                                                   &j->plan, &j->pixels, &j->png_len)
+          : j->want_png ? ist_stitch_bitmaps_png_preview(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels, &j->png_len,
                                                          j->want_preview ? &j->pv : NULL)
                         : ist_stitch_bitmaps_rgba8(ctx, j->bitmaps, j->n_bitmaps, j->direction, j->mode, j->gap, &j->lim, j->filter, &j->plan, &j->pixels);
     if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
@@ -284,7 +301,10 @@ static void stitch_execute(napi_env env, void* data) {
   }
   for (int i = 0; i < j->im.n; i++)
     if (!j->im.data[i]) { j->rc = IST_E_DECODE; snprintf(j->err, sizeof j->err, "\xe5\x9b\xbe\xe7\x89\x87%d\xe8\xa7\xa3\xe7\xa0\x81\xe5\xbc\x82\xe5\xb8\xb8", i); return; }
-  if (j->ndev > 0 && !j->want_png)
+  if (j->want_jpeg)
+    j->rc = ist_stitch_jpeg(ctx, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim, j->filter, j->quality, j->subsampling,
+                            &j->plan, &j->pixels, &j->png_len);
+  else if (j->ndev > 0 && !j->want_png)
     j->rc = ist_stitch_rgba8_multi(j->devices, j->ndev, j->im.descs, j->im.data, j->im.pitch, j->im.n, j->direction, j->mode, j->gap, &j->lim,
                                    j->filter, j->split, &j->plan, &j->pixels);
   else if (j->want_png)
@@ -336,7 +356,7 @@ static stitch_job* stitch_parse(napi_env env, napi_callback_info info, int want_
   napi_get_value_double(env, argv[3], &j->gap);
   limits_parse(env, argv[4], &j->lim);
   napi_get_value_int32(env, argv[5], &v); j->filter = v;
-  if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; }
+  if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; j->want_jpeg = jpeg_parse(env, argv[6], &j->quality, &j->subsampling); }
   if (argc > 7) {                                       /* devices: number[] */
     bool is_arr = false; uint32_t n = 0;
     if (napi_is_array(env, argv[7], &is_arr) == napi_ok && is_arr) {
@@ -696,6 +716,29 @@ static napi_value js_encode_png(napi_env env, napi_callback_info info) {
   if (rc < 0) return throw_ist(env, rc);
   napi_value buf;
   if (napi_create_external_buffer(env, (size_t)n, png, free_pixels, NULL, &buf) != napi_ok) { ist_free(png); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  return buf;
+}
+
+/* encodeJpeg(data: Uint8Array RGBA, width, height, quality, subsampling: IST_JPEG_*) -> Buffer (JFIF file bytes; alpha is not read) */
+static napi_value js_encode_jpeg(napi_env env, napi_callback_info info) {
+  size_t argc = 5; napi_value argv[5];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 5) { napi_throw_type_error(env, NULL, "encodeJpeg(data, width, height, quality, subsampling)"); return NULL; }
+  bool ta = false, isbuf = false; void* p = NULL; size_t len = 0;
+  napi_is_buffer(env, argv[0], &isbuf); napi_is_typedarray(env, argv[0], &ta);
+  if (isbuf) napi_get_buffer_info(env, argv[0], &p, &len);
+  else if (ta) { napi_typedarray_type tt; napi_value ab; size_t off; napi_get_typedarray_info(env, argv[0], &tt, &len, &p, &ab, &off); }
+  double w = 0, h = 0; int32_t quality = 0, subsampling = -1;
+  napi_get_value_double(env, argv[1], &w); napi_get_value_double(env, argv[2], &h);
+  napi_get_value_int32(env, argv[3], &quality); napi_get_value_int32(env, argv[4], &subsampling);
+  if (!p || w < 1 || h < 1 || (double)len < w * h * 4) { napi_throw_range_error(env, NULL, "data is smaller than width*height*4"); return NULL; }
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { napi_throw(env, make_error(env, IST_E_NO_DEVICE, g_ctx_err)); return NULL; }
+  uint8_t* jpg = NULL; int64_t n = 0;
+  const int rc = ist_jpeg_encode_rgba8(ctx, (const uint8_t*)p, (size_t)w * 4, (int64_t)w, (int64_t)h, quality, subsampling, &jpg, &n);
+  if (rc < 0) return throw_ist(env, rc);
+  napi_value buf;
+  if (napi_create_external_buffer(env, (size_t)n, jpg, free_pixels, NULL, &buf) != napi_ok) { ist_free(jpg); napi_throw_error(env, NULL, "out of memory"); return NULL; }
   return buf;
 }
 
@@ -1104,7 +1147,7 @@ static stitch_job* stitch_bitmaps_parse(napi_env env, napi_callback_info info) {
   napi_get_value_double(env, argv[3], &j->gap);
   limits_parse(env, argv[4], &j->lim);
   napi_get_value_int32(env, argv[5], &v); j->filter = v;
-  if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; }
+  if (argc > 6) { bool b = false; napi_get_value_bool(env, argv[6], &b); j->want_png = b ? 1 : 0; j->want_jpeg = jpeg_parse(env, argv[6], &j->quality, &j->subsampling); }
   if (argc > 8 && j->want_png) j->want_preview = preview_parse(env, argv[7], argv[8], &j->pv);
   return j;
 }
@@ -1157,6 +1200,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"stitchFiles", NULL, js_stitch_files, NULL, NULL, NULL, napi_default, NULL},
       {"render", NULL, js_render, NULL, NULL, NULL, napi_default, NULL},
       {"encodePng", NULL, js_encode_png, NULL, NULL, NULL, napi_default, NULL},
+      {"encodeJpeg", NULL, js_encode_jpeg, NULL, NULL, NULL, napi_default, NULL},
       {"setPngLevel", NULL, js_set_png_level, NULL, NULL, NULL, napi_default, NULL},
       {"decodePng", NULL, js_decode_png, NULL, NULL, NULL, napi_default, NULL},
       {"decodeImage", NULL, js_decode_image, NULL, NULL, NULL, napi_default, NULL},

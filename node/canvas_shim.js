@@ -162,6 +162,17 @@ function makeEnvironment({ platform = 'devtools', files = {}, storage = {}, reco
         env.exports[p].file = file;
       }
     }
+    // fileType 'jpg' / 'jpeg' of the whole canvas at its own size: the baseline JFIF file of the pixels just rendered (GPU encoder, 4:2:0).
+    // wx's quality is in (0, 1]; absent means 100.  Alpha is not read: a stitched canvas is opaque.
+    if (!env.recordOnly && (o.fileType === 'jpg' || o.fileType === 'jpeg') && (o.x || 0) === 0 && (o.y || 0) === 0 && w === canvas.width && h === canvas.height) {
+      const q = typeof o.quality === 'number' ? Math.min(100, Math.max(1, Math.round(100 * o.quality))) : 100;
+      env.exports[p].jpeg = native.encodeJpeg(data, w, h, q, 1);
+      if (env.outDir) {
+        const file = require('path').join(env.outDir, 'export' + (env.nextExport - 1) + '.jpg');
+        require('fs').writeFileSync(file, env.exports[p].jpeg);
+        env.exports[p].file = file;
+      }
+    }
     env.files[p] = { width: w, height: h, data, opaque: true };
     return { tempFilePath: p };
   };

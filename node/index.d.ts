@@ -41,6 +41,11 @@ export function stitchPng(images: StitchImage[], direction: Direction, opts?: St
 export function stitchPngBatch(requests: StitchRequest[]): Promise<(StitchPngResult | null)[]>;
 export function stitchPngBatchSync(requests: StitchRequest[]): (StitchPngResult | null)[];
 export function encodePng(data: Uint8Array, width: number, height: number, opts?: { pngLevel?: 0 | 1 }): Buffer;
+// the export with fileType 'jpg': a baseline JFIF file, pinned byte for byte by include/imagestitch.h (alpha is not read); preview and devices are refused
+export interface JpegOptions { quality?: number; subsampling?: '420' | '444' | 420 | 444; }      // quality: an integer 1..100, default 90; subsampling default '420'
+export interface StitchJpegResult { width: number; height: number; jpeg: Buffer; plan: StitchPlan; }
+export function stitchJpeg(images: StitchImage[] | Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split' | 'preview' | 'pngLevel'> & JpegOptions): Promise<StitchJpegResult | null>;
+export function encodeJpeg(data: Uint8Array, width: number, height: number, opts?: JpegOptions): Buffer;
 export function setPngLevel(level: 0 | 1): void;
 export function decodePng(file: Uint8Array): { width: number; height: number; data: Buffer };
 export function stitchFiles(paths: string[], direction: Direction, opts?: StitchOptions, outPath?: string): Promise<StitchPngResult | null>;

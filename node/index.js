@@ -7,6 +7,8 @@
  *
  *   stitch(images, direction, opts?) -> Promise<{width, height, data: Buffer, plan}>
  *   stitchBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, data, plan} | null)[]>   (one GPU, many stitches)
+ *   stitchJpeg(images | Bitmap[], direction, opts + {quality, subsampling}) -> Promise<{width, height, jpeg, plan}>   (baseline JFIF)
+ *   encodeJpeg(data, width, height, {quality, subsampling}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
@@ -228,6 +230,36 @@ function stitchPng(images, direction, opts) {
   }
   return withProgress(opts, () => { pngLevel(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
 }
+const SUBSAMPLING = { 444: 0, 420: 1 };          // IST_JPEG_444 / IST_JPEG_420
+// {quality, subsampling} of a JPEG export, checked: an integer quality 1..100 (default 90), subsampling '420' (default) or '444'
+function jpegArgs(o) {
+  const quality = (o && o.quality !== undefined && o.quality !== null) ? o.quality : 90;
+  const ss = String((o && o.subsampling !== undefined && o.subsampling !== null) ? o.subsampling : '420');
+  if (!Number.isInteger(quality) || quality < 1 || quality > 100) throw new RangeError('quality must be an integer 1..100');
+  if (!(ss in SUBSAMPLING)) throw new TypeError("subsampling must be '420' or '444'");
+  return { quality, subsampling: SUBSAMPLING[ss] };
+}
+/** stitch + the export with fileType 'jpg' (utils/canvas.js:205-221): resolves {width, height, jpeg: Buffer (a baseline JFIF file),
+ *  plan}. opts.quality (1..100, default 90) and opts.subsampling ('420' default, '444') choose the file, which is pinned byte for
+ *  byte by include/imagestitch.h; alpha is not read. images may be Bitmap[]. The canvas never leaves the GPU. preview and devices
+ *  do not apply. */
+function stitchJpeg(images, direction, opts) {
+  let a, h, j;
+  try {
+    const o = Object.assign({}, opts || {});
+    j = jpegArgs(o); delete o.quality; delete o.subsampling;
+    if (o.preview !== undefined && o.preview !== null) throw new TypeError('stitchJpeg: option preview does not apply (previews are built beside the PNG export)');
+    if (o.devices !== undefined && o.devices !== null) throw new TypeError('stitchJpeg: option devices does not apply (the JPEG export runs on one GPU)');
+    h = bitmapHandles(images, o); a = args(images, direction, o);
+  } catch (e) { return Promise.reject(e); }
+  if (!a[0].length) return Promise.resolve(null);
+  if (h) {
+    try { return withProgress(opts, () => native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], j)); } catch (e) { return Promise.reject(e); }
+  }
+  return withProgress(opts, () => native.stitch(...a, j));
+}
+/** Baseline JFIF file of RGBA8 pixels, encoded on the GPU: encodeJpeg(data, width, height, {quality, subsampling}). Synchronous. */
+function encodeJpeg(data, width, height, opts) { const j = jpegArgs(opts); return native.encodeJpeg(data, width, height, j.quality, j.subsampling); }
 /** opts.pngLevel: 0 = stored deflate blocks (file = raw size, fastest), 1 = Paeth + run-length + Huffman on the GPU
  *  (photographs about half, screenshots a few per cent). A process-wide setting of the native context. */
 function pngLevel(opts) { if (opts && opts.pngLevel !== undefined && opts.pngLevel !== null) native.setPngLevel(opts.pngLevel | 0); }
@@ -260,5 +292,5 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchFiles, encodePng, setPngLevel, decodePng, decodeImage, plan,
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, decodePng, decodeImage, plan,
                    decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
