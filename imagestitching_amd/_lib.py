@@ -243,6 +243,13 @@ SYMBOLS = [
     ("ist_stitch_bitmaps_jpeg", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(Limits), C.c_int,
                                           C.c_int, C.c_int, C.POINTER(Plan), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
     ("ist_debug_jpeg_encode_launches", C.c_int64, []),
+    ("ist_jpeg_batch_layout", C.c_int64, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    ("ist_jpeg_encode_batch_device", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.c_void_p]),
+    ("ist_stitch_jpeg_batch", C.c_int, [C.c_void_p, C.POINTER(StitchRequest), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(Plan),
+                                        C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_debug_jpeg_batch_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -16,6 +17,7 @@
 
 #include "ist_ctx.h"
 #include "ist_internal.h"
+#include "ist_jpeg_enc.h"
 #include "ist_launch.h"
 
 using namespace ist;
@@ -29,7 +31,12 @@ constexpr int kKinds = 7;                               // launch_stitch's kerne
 // The host path splits a batch so that sources + canvases of one sub-batch stay under this many device bytes (a larger
 // request runs alone, with the memory its single stitch would take).  Two sub-batches are in flight (Pipeline below), so the
 // context keeps at most twice this much device scratch for batches.
-constexpr size_t kSubBatchBytes = size_t(512) << 20;
+// (IST_TUNING=1 IST_BATCH_BYTES=<bytes> overrides, read once, so that small canvases cross sub-batches)
+constexpr size_t kSubBatchBytesDefault = size_t(512) << 20;
+size_t sub_batch_bytes() {
+  static const long long knob = (tuning_mode() && std::getenv("IST_BATCH_BYTES")) ? std::atoll(std::getenv("IST_BATCH_BYTES")) : 0;
+  return knob > 0 ? static_cast<size_t>(knob) : kSubBatchBytesDefault;
+}
 
 }  // namespace
 
@@ -198,6 +205,8 @@ void drop_jobs(std::vector<JobPtr>* jobs) {
 // half's canvas area into its file area by one compression launch (+ one gather launch) on ctx->stream, and the files come down on
 // the aux stream, each exactly as long as it is; the few header / trailer bytes no kernel writes are patched into the host copies
 // once the downloads are done (apply_patches).
+// With quality / subsampling (ist_stitch_jpeg_batch) every result is a JPEG file: the same, through the batch encoder of
+// ist_jpeg_encode.hip, whose gather writes every byte of a file - nothing is patched.
 struct Pipeline {
   ist_ctx* ctx;
   const ist_stitch_request* reqs;
@@ -205,7 +214,9 @@ struct Pipeline {
   const std::vector<int>& n_ops;
   const ist_plan* plans;
   uint8_t** out_pixels;
-  int64_t* out_len;                       // PNG files out (NULL: canvases)
+  int64_t* out_len;                       // PNG or JPEG files out (NULL: canvases)
+  const int* quality = nullptr;           // JPEG files out: per request (NULL: PNG)
+  const int* subsampling = nullptr;
   std::vector<JobPtr> jobs[2];            // the jobs whose tables live in half 0 / 1
   bool used[2] = {false, false};
   int next = 0;
@@ -251,7 +262,7 @@ struct Pipeline {
       canvas_bytes[q] = static_cast<size_t>(p.canvas_w) * 4 * static_cast<size_t>(p.canvas_h);
       dst_at[q] = dst_total; dst_total += round256(canvas_bytes[q]);
       if (out_len) {
-        file_cap[q] = static_cast<size_t>(ist_png_bound(p.canvas_w, p.canvas_h));
+        file_cap[q] = static_cast<size_t>(quality ? ist_jpeg_bound(p.canvas_w, p.canvas_h, subsampling[k]) : ist_png_bound(p.canvas_w, p.canvas_h));
         file_at[q] = file_total; file_total += round256(file_cap[q]);
       }
     }
@@ -318,6 +329,7 @@ struct Pipeline {
                       const std::vector<size_t>& file_at, const std::vector<size_t>& file_cap) {
     const size_t n = idx.size();
     uint8_t* dfile = static_cast<uint8_t*>(H.file);
+    if (quality) return encode_and_read_jpeg(idx, H, ddst, dst_at, file_at, file_cap);
     std::vector<PngBatchFile> files(n);
     for (size_t q = 0; q < n; ++q) {
       const ist_plan& p = plans[idx[q]];
@@ -340,10 +352,38 @@ struct Pipeline {
     if (hipEventRecord(H.read_done, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
     return IST_OK;
   }
+
+  // ... -> JPEG files: one transform, one entropy and one gather launch per round of the batch encoder for all of them
+  int encode_and_read_jpeg(const std::vector<int>& idx, ist_ctx::BatchHalf& H, uint8_t* ddst, const std::vector<size_t>& dst_at,
+                           const std::vector<size_t>& file_at, const std::vector<size_t>& file_cap) {
+    const size_t n = idx.size();
+    uint8_t* dfile = static_cast<uint8_t*>(H.file);
+    std::vector<JpegBatchFile> files(n);
+    for (size_t q = 0; q < n; ++q) {
+      const ist_plan& p = plans[idx[q]];
+      files[q] = JpegBatchFile{ddst + dst_at[q], static_cast<size_t>(p.canvas_w) * 4, p.canvas_w, p.canvas_h, quality[idx[q]], subsampling[idx[q]],
+                               dfile + file_at[q], static_cast<int64_t>(file_cap[q]), 0};
+      const int rc = jpeg_batch_check(files[q], "request", idx[q]);
+      if (rc) return rc;
+    }
+    const int rc = jpeg_encode_batch(ctx, files, ctx->stream, "request", idx.data());
+    if (rc) return rc;
+    for (size_t q = 0; q < n; ++q) {
+      const size_t len = static_cast<size_t>(files[q].len);
+      uint8_t* host = static_cast<uint8_t*>(pool_take_batch(len));
+      if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the results");
+      out_pixels[idx[q]] = host;                           // (the caller's release() gives it back, after finish())
+      out_len[idx[q]] = files[q].len;
+      if (hipMemcpyAsync(host, dfile + file_at[q], len, hipMemcpyDeviceToHost, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "queueing a readback failed"); }
+    }
+    if (hipEventRecord(H.read_done, ctx->aux) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed"); }
+    return IST_OK;
+  }
 };
 
-// ist_stitch_rgba8_batch (out_len NULL) and ist_stitch_png_batch
-int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels, int64_t* out_len) {
+// ist_stitch_rgba8_batch (out_len NULL), ist_stitch_png_batch and (quality, subsampling given) ist_stitch_jpeg_batch
+int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels, int64_t* out_len,
+                 const int* quality = nullptr, const int* subsampling = nullptr) {
   const size_t n = static_cast<size_t>(n_reqs);
   for (size_t k = 0; k < n; ++k) { out_pixels[k] = nullptr; std::memset(&out_plans[k], 0, sizeof(ist_plan)); if (out_len) out_len[k] = 0; }
   auto release = [&]() {
@@ -368,7 +408,11 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
     bytes[k] = static_cast<size_t>(out_plans[k].canvas_w) * 4 * static_cast<size_t>(out_plans[k].canvas_h);
     for (int i = 0; i < r.n_images; ++i)
       bytes[k] += static_cast<size_t>(std::max<int64_t>(0, bitmap_w(r.images[i]))) * 4 * static_cast<size_t>(std::max<int64_t>(0, bitmap_h(r.images[i])));
-    if (out_len) {                                        // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
+    if (quality) {                                        // + its file (the encoder's scratch is its own, bounded by its budget)
+      const int rcj = jpeg_check_export(("request " + std::to_string(k)).c_str(), out_plans[k].canvas_w, out_plans[k].canvas_h, quality[k], subsampling[k]);
+      if (rcj) { KeepLastError keep; release(); return rcj; }
+      bytes[k] += static_cast<size_t>(ist_jpeg_bound(out_plans[k].canvas_w, out_plans[k].canvas_h, subsampling[k]));
+    } else if (out_len) {                                 // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
       const int64_t cw = out_plans[k].canvas_w, ch = out_plans[k].canvas_h;
       bytes[k] += static_cast<size_t>(ist_png_bound(cw, ch));
       if (ctx->png_level > 0) bytes[k] += static_cast<size_t>(png_deflate_chunks(cw, ch) * png_deflate_slot_bytes());
@@ -381,11 +425,13 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
   if (rc) { release(); return rc; }
   // sub-batches: consecutive requests while their device bytes fit the budget, and at most kMaxBatchJobs of them
   Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels, out_len);
+  pipe.quality = quality; pipe.subsampling = subsampling;
   std::vector<int> idx;
   size_t held = 0;
+  const size_t budget = sub_batch_bytes();
   for (size_t k = 0; k <= n && rc == IST_OK; ++k) {
     const bool live = k < n && n_ops[k] > 0;
-    const bool flush = !idx.empty() && (k == n || (live && (held + bytes[k] > kSubBatchBytes || idx.size() >= static_cast<size_t>(kMaxBatchJobs))));
+    const bool flush = !idx.empty() && (k == n || (live && (held + bytes[k] > budget || idx.size() >= static_cast<size_t>(kMaxBatchJobs))));
     if (flush) { rc = pipe.run(idx); idx.clear(); held = 0; }
     if (live) { idx.push_back(static_cast<int>(k)); held += bytes[k]; }
   }
@@ -409,6 +455,20 @@ int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_req
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_png || !out_len))) return fail(IST_E_INVALID, "ist_stitch_png_batch: NULL argument");
   return stitch_batch(ctx, reqs, n_reqs, out_plans, out_png, out_len);
+}
+
+int ist_stitch_jpeg_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, const int* quality, const int* subsampling,
+                          ist_plan* out_plans, uint8_t** out_jpeg, int64_t* out_len) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !quality || !subsampling || !out_plans || !out_jpeg || !out_len)))
+    return fail(IST_E_INVALID, "ist_stitch_jpeg_batch: NULL argument");
+  // the options of EVERY request, the ones without images included, before anything is planned
+  for (int k = 0; k < n_reqs; ++k) { out_jpeg[k] = nullptr; out_len[k] = 0; std::memset(&out_plans[k], 0, sizeof(ist_plan)); }
+  for (int k = 0; k < n_reqs; ++k) {
+    const int rc = jpeg_check_options(("request " + std::to_string(k)).c_str(), quality[k], subsampling[k]);
+    if (rc) return rc;
+  }
+  return stitch_batch(ctx, reqs, n_reqs, out_plans, out_jpeg, out_len, quality, subsampling);
 }
 
 }  // extern "C"

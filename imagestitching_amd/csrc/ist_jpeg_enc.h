@@ -1,0 +1,100 @@
+// ist_jpeg_enc.h — the JPEG export's host side that needs no device (ist_jpeg_enc_host.cpp): tables, the file header, the geometry
+// of a canvas, and how a batch of canvases is cut into rounds and pieces; plus what the batch entry points share.
+// The kernels and the two encoders are in ist_jpeg_encode.hip.
+#ifndef IST_JPEG_ENC_H_
+#define IST_JPEG_ENC_H_
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/imagestitch.h"
+
+struct ist_ctx;
+
+namespace ist {
+
+constexpr size_t kJpegEncBudget = 256u << 20;     // coefficient scratch + interval slots of one slab (one round of a batch)
+constexpr int kJpegBlockBits = 22 + 63 * 26;      // most bits of one block: DC code 11 + 11 magnitude bits, 63 x (AC code 16 + 10)
+constexpr int kJpegBlockBytes = 2 * kJpegBlockBits / 8;      // ... as bytes when every byte is 0xFF and stuffed: 415
+static_assert(kJpegBlockBits == 1660 && kJpegBlockBytes * 8 == 2 * kJpegBlockBits, "slot bound");
+constexpr int kJpegHeaderBytes = 629;             // SOI ... SOS of every file the encoder writes
+
+// what the kernels read beside the canvas: one block per quality
+struct JpegTables {
+  uint32_t dc[2][16];        // Huffman code of a DC size: length << 16 | code (slot 0 luma, 1 chroma)
+  uint32_t ac[2][256];       // ... of an AC run/size symbol (0: the symbol has no code)
+  uint8_t q[2][64];          // quantisation tables, natural order
+  uint8_t zz_of[64];         // natural index -> zig-zag position
+};
+
+struct JpegGeometry {
+  int mcu_w, mcu_h, bpm;         // MCU size in pixels, blocks per MCU
+  int64_t mcus_x, mcus_y, row_blocks;
+  int64_t slot;                  // bytes of one interval's slot (a multiple of 16)
+  int64_t row_cost() const { return row_blocks * 128 + slot; }      // scratch of one MCU row: its coefficients and its slot
+};
+inline JpegGeometry jpeg_geometry(int64_t w, int64_t h, int subsampling) {
+  JpegGeometry g;
+  g.mcu_w = g.mcu_h = subsampling == IST_JPEG_420 ? 16 : 8;
+  g.bpm = subsampling == IST_JPEG_420 ? 6 : 3;
+  g.mcus_x = (w + g.mcu_w - 1) / g.mcu_w; g.mcus_y = (h + g.mcu_h - 1) / g.mcu_h;
+  g.row_blocks = g.mcus_x * g.bpm;
+  g.slot = (g.row_blocks * kJpegBlockBytes + 2 + 15) & ~15ll;      // + the byte the pad can add, and one so that no real length reaches it
+  return g;
+}
+
+void jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);       // libjpeg: jpeg_quality_scaling, jpeg_add_quant_table
+void jpeg_enc_tables(int quality, JpegTables* T);                                // everything the kernels read for one quality
+// SOI, APP0, DQT x 2, DHT x 4, DRI, SOF0, SOS
+std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart);
+
+// ---- batches (ist_jpeg_encode_batch_device, ist_stitch_jpeg_batch) ----
+// one file of a batch: a canvas in device memory -> its JPEG in a 16-byte aligned device buffer of `cap` >= ist_jpeg_bound bytes
+struct JpegBatchFile { const void* canvas; size_t pitch; int64_t w, h; int quality, subsampling; uint8_t* out; int64_t cap; int64_t len; };
+
+// What a workgroup of a batch kernel reads about its piece (a run of MCU rows of one file, encoded in one round).  Read through
+// scalar loads: plain data, 128 bytes.
+struct JpegPiece {
+  const uint8_t* canvas; size_t pitch;
+  const JpegTables* tab;         // the tables of the file's quality
+  int16_t* coef;                 // the piece's blocks in the round's scratch
+  uint8_t* slots;                // ... and its intervals' slots
+  uint8_t* out; int64_t out_cap; // the file
+  const uint8_t* head;           // the file's header (in the round's table block), written by the file's interval 0
+  int64_t slot;                  // bytes of one slot
+  int32_t w, h, is420, mcus_x, mcus_y, row_blocks, bpm, head_len;
+  int32_t mcu_row0, mcu_rows;    // the piece's MCU rows (= restart intervals) of the file
+  int32_t wg0, iv0;              // its first workgroup of the transform grid, its first interval of the entropy and gather grids
+  int32_t gx, reserved;          // transform workgroups per MCU row
+};
+static_assert(sizeof(JpegPiece) == 128, "piece record");
+
+// the pieces of a batch in encoding order (the rule of ist_jpeg_batch_layout); budget > 0
+std::vector<ist_jpeg_piece> jpeg_batch_pieces(const JpegBatchFile* files, int n, int64_t budget);
+
+// One round of a batch: pieces [p0, p1) of the list.  Where everything sits in the round's table block (one host-to-device copy)
+// and in the scratch, and the sizes of the three grids.
+struct JpegRound {
+  int p0 = 0, p1 = 0;
+  std::vector<int> quality;                      // the distinct qualities of the round's files, in order of first use
+  size_t at_tables = 0, at_heads = 0, at_pieces = 0, table_bytes = 0;
+  size_t at_slots = 0, scratch_bytes = 0;        // the scratch: every piece's coefficients, then every piece's slots
+  int64_t wgs = 0, ivs = 0;
+};
+JpegRound jpeg_round_plan(const JpegBatchFile* files, const ist_jpeg_piece* pieces, int p0, int p1);
+// the host image of the round's table block.  dev / scratch: where the block and the scratch are on the device (never read here)
+void jpeg_round_pack(const JpegRound& R, const JpegBatchFile* files, const ist_jpeg_piece* pieces, uint8_t* host, const uint8_t* dev,
+                     uint8_t* scratch);
+
+int64_t jpeg_batch_budget();                     // kJpegEncBudget, or IST_TUNING=1 IST_JPEG_ENC_BUDGET=<bytes> (read once)
+int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k);      // the rules of ist_jpeg_encode_device for file k (message: "<what> k: ...")
+void count_jpeg_batch_launch();
+// every file in one transform, one entropy and one gather launch per round on `stream`, which is idle when the call returns; file k is
+// byte for byte what ist_jpeg_encode_device writes.  The arguments have passed jpeg_batch_check.  A message about file k names it
+// "<what> ids[k]" (ids NULL: k itself).  (ist_jpeg_encode.hip)
+int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* stream, const char* what = "file", const int* ids = nullptr);
+
+}  // namespace ist
+
+#endif  // IST_JPEG_ENC_H_

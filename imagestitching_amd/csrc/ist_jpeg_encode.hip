@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ist_ctx.h"
+#include "ist_jpeg_enc.h"
 
 namespace ist {
 
@@ -34,82 +35,13 @@ namespace {
 
 std::atomic<int64_t> g_launches{0};
 
-constexpr size_t kBudget = 256u << 20;     // coefficient scratch + interval slots of one slab
-constexpr int kBlockBits = 22 + 63 * 26;   // most bits of one block: DC code 11 + 11 magnitude bits, 63 x (AC code 16 + 10)
-constexpr int kBlockBytes = 2 * kBlockBits / 8;      // ... as bytes when every byte is 0xFF and stuffed: 415
-static_assert(kBlockBits == 1660 && kBlockBytes * 8 == 2 * kBlockBits, "slot bound");
+// (the tables, the header and the geometry are host code without a device: ist_jpeg_enc.h)
+constexpr size_t kBudget = kJpegEncBudget;
+constexpr int kBlockBits = kJpegBlockBits;
 constexpr int kBatch = 256;                // blocks per batch of the entropy kernel = its threads
 constexpr int kImgWords = (7 + kBatch * kBlockBits + 31) / 32 + 2;      // LDS bit image of a batch behind a carried partial byte
-
-// T.81 Annex K: the example quantisation tables K.1 / K.2 (natural order) and the Huffman tables K.3 - K.6 (BITS, HUFFVAL)
-const uint8_t kQLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
-                            14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
-                            49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-const uint8_t kQChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
-                              47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-                              99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,
-                             6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38,
-                             31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};       // zig-zag position -> natural index
-const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
-const uint8_t kAcVals[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-
-// what the kernels read beside the canvas: one block at the head of the context's JPEG scratch
-struct JpegTables {
-  uint32_t dc[2][16];        // Huffman code of a DC size: length << 16 | code (slot 0 luma, 1 chroma)
-  uint32_t ac[2][256];       // ... of an AC run/size symbol (0: the symbol has no code)
-  uint8_t q[2][64];          // quantisation tables, natural order
-  uint8_t zz_of[64];         // natural index -> zig-zag position
-};
-
-void huff_codes(const uint8_t* bits, const uint8_t* vals, uint32_t* out) {       // T.81 C.2: canonical codes
-  uint32_t code = 0; int k = 0;
-  for (int l = 1; l <= 16; ++l) {
-    for (int i = 0; i < bits[l - 1]; ++i) out[vals[k++]] = (static_cast<uint32_t>(l) << 16) | code++;
-    code <<= 1;
-  }
-}
-
-void quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {           // libjpeg: jpeg_quality_scaling, jpeg_add_quant_table
-  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-  for (int i = 0; i < 64; ++i) {
-    luma[i] = static_cast<uint8_t>(std::min(255, std::max(1, (kQLuma[i] * scale + 50) / 100)));
-    chroma[i] = static_cast<uint8_t>(std::min(255, std::max(1, (kQChroma[i] * scale + 50) / 100)));
-  }
-}
-
-struct Geometry {
-  int mcu_w, mcu_h, bpm;         // MCU size in pixels, blocks per MCU
-  int64_t mcus_x, mcus_y, row_blocks;
-  int64_t slot;                  // bytes of one interval's slot (a multiple of 16)
-};
-Geometry geometry(int64_t w, int64_t h, int subsampling) {
-  Geometry g;
-  g.mcu_w = g.mcu_h = subsampling == IST_JPEG_420 ? 16 : 8;
-  g.bpm = subsampling == IST_JPEG_420 ? 6 : 3;
-  g.mcus_x = (w + g.mcu_w - 1) / g.mcu_w; g.mcus_y = (h + g.mcu_h - 1) / g.mcu_h;
-  g.row_blocks = g.mcus_x * g.bpm;
-  g.slot = (g.row_blocks * kBlockBytes + 2 + 15) & ~15ll;      // + the byte the pad can add, and one so that no real length reaches it
-  return g;
-}
+typedef JpegGeometry Geometry;
+inline Geometry geometry(int64_t w, int64_t h, int subsampling) { return jpeg_geometry(w, h, subsampling); }
 
 // ---- transform ---------------------------------------------------------------------------------------------------------
 struct XformArgs {
@@ -129,7 +61,8 @@ __device__ __forceinline__ int fdct_coef(int u, int x) {
   return sign * c;
 }
 
-__global__ __launch_bounds__(256) void ist_jpeg_transform_kernel(const XformArgs A) {
+// one workgroup of the transform: MCUs [bx * (1 or 4), ...) of MCU row A.mcu_row0 + by; by counts from the first row of A.coef
+__device__ __forceinline__ void jpeg_transform(const XformArgs& A, const int bx, const int by) {
   __shared__ int sT[64], sQ[128], sZ[64];
   __shared__ int sS[12 * 64], sR[12 * 64];        // level-shifted samples / row-pass results (later: the quantised blocks), block by block
   __shared__ int sC[2][256];                      // 4:2:0: full-resolution chroma of the MCU
@@ -138,8 +71,8 @@ __global__ __launch_bounds__(256) void ist_jpeg_transform_kernel(const XformArgs
   if (tid < 128) sQ[tid] = A.tab->q[tid >> 6][tid & 63];
   const int tw = A.is420 ? 16 : 32, sh = A.is420 ? 4 : 5;
   const int px = tid & (tw - 1), py = tid >> sh;
-  const int64_t mcu_y = static_cast<int64_t>(A.mcu_row0) + blockIdx.y;
-  const int x = min(static_cast<int>(blockIdx.x) * tw + px, A.w - 1);                 // (clamped reads: the edge padding)
+  const int64_t mcu_y = static_cast<int64_t>(A.mcu_row0) + by;
+  const int x = min(bx * tw + px, A.w - 1);                 // (clamped reads: the edge padding)
   const int y = static_cast<int>(min(mcu_y * (A.is420 ? 16 : 8) + py, static_cast<int64_t>(A.h) - 1));
   const uint32_t p = *reinterpret_cast<const uint32_t*>(A.canvas + static_cast<size_t>(y) * A.pitch + 4 * static_cast<size_t>(x));
   const int R = p & 255u, G = (p >> 8) & 255u, B = (p >> 16) & 255u;                  // (alpha is not read)
@@ -184,12 +117,16 @@ __global__ __launch_bounds__(256) void ist_jpeg_transform_kernel(const XformArgs
   }
   __syncthreads();
   // the workgroup's blocks are consecutive in coding order: one run of 32-bit stores
-  const int64_t mcu0 = static_cast<int64_t>(blockIdx.x) * (A.is420 ? 1 : 4);
+  const int64_t mcu0 = static_cast<int64_t>(bx) * (A.is420 ? 1 : 4);
   const int mcus = static_cast<int>(min(static_cast<int64_t>(A.is420 ? 1 : 4), static_cast<int64_t>(A.mcus_x) - mcu0));
   const int words = mcus * (A.is420 ? 6 : 3) * 32;
-  uint32_t* dst = reinterpret_cast<uint32_t*>(A.coef) + ((static_cast<int64_t>(blockIdx.y) * A.mcus_x + mcu0) * (A.is420 ? 6 : 3)) * 32;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(A.coef) + ((static_cast<int64_t>(by) * A.mcus_x + mcu0) * (A.is420 ? 6 : 3)) * 32;
   for (int i = tid; i < words; i += 256)
     dst[i] = (static_cast<uint32_t>(sS[2 * i]) & 0xFFFFu) | (static_cast<uint32_t>(sS[2 * i + 1]) << 16);
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_transform_kernel(const XformArgs A) {
+  jpeg_transform(A, static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y));
 }
 
 // ---- entropy code ------------------------------------------------------------------------------------------------------
@@ -268,7 +205,8 @@ __device__ __forceinline__ int block_scan(int v, uint32_t* ws, int* total) {
   return base + incl - v;
 }
 
-__global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs A) {
+// one workgroup of the entropy coder: interval iv of A (its coefficients, its slot, its length)
+__device__ __forceinline__ void jpeg_entropy(const EntropyArgs& A, const int iv) {
   __shared__ uint32_t img[kImgWords];
   __shared__ uint32_t sDc[32], sAc[512];
   __shared__ uint32_t ws_bits[4], ws_ff[4];
@@ -276,8 +214,8 @@ __global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs
   if (tid < 32) sDc[tid] = A.tab->dc[tid >> 4][tid & 15];
   for (int i = tid; i < 512; i += 256) sAc[i] = A.tab->ac[i >> 8][i & 255];
   __syncthreads();
-  const int16_t* coef = A.coef + static_cast<int64_t>(blockIdx.x) * A.row_blocks * 64;
-  uint8_t* slot = A.slots + static_cast<int64_t>(blockIdx.x) * A.slot;
+  const int16_t* coef = A.coef + static_cast<int64_t>(iv) * A.row_blocks * 64;
+  uint8_t* slot = A.slots + static_cast<int64_t>(iv) * A.slot;
   int64_t out_pos = 0;
   int carry_bits = 0; uint32_t carry_val = 0;            // the partial last byte of the batches so far (its bits at the top of a byte)
   for (int base = 0; base < A.row_blocks; base += kBatch) {
@@ -333,55 +271,89 @@ __global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs
     carry_bits = (total + pad) & 7;
     carry_val = carry_bits ? (img_byte(img, nb) & (0xFF00u >> carry_bits) & 255u) : 0u;
   }
-  if (tid == 0) A.len[blockIdx.x] = static_cast<uint32_t>(min(out_pos, A.slot));
+  if (tid == 0) A.len[iv] = static_cast<uint32_t>(min(out_pos, A.slot));
 }
+
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs A) { jpeg_entropy(A, static_cast<int>(blockIdx.x)); }
 
 // ---- gather ------------------------------------------------------------------------------------------------------------
 struct GatherArgs { const uint8_t* slots; int64_t slot; uint8_t* out; const int64_t* dst; const uint32_t* len; int32_t first; };
 
-// interval first + blockIdx.x: len bytes from its slot to file offset dst (any alignment, so bytes: the 16-byte units of the
+// interval first + i: len bytes from its slot to file offset dst (any alignment, so bytes: the 16-byte units of the
 // PNG gather need slots that are multiples of 16), behind RST((k - 1) mod 8) for every interval but the file's first
-__global__ __launch_bounds__(256) void ist_jpeg_gather_kernel(const GatherArgs G) {
-  const int k = G.first + static_cast<int>(blockIdx.x);
-  const uint8_t* s = G.slots + static_cast<int64_t>(blockIdx.x) * G.slot;
-  uint8_t* d = G.out + G.dst[blockIdx.x];
-  const int n = static_cast<int>(G.len[blockIdx.x]);
+__device__ __forceinline__ void jpeg_gather(const GatherArgs& G, const int i) {
+  const int k = G.first + i;
+  const uint8_t* s = G.slots + static_cast<int64_t>(i) * G.slot;
+  uint8_t* d = G.out + G.dst[i];
+  const int n = static_cast<int>(G.len[i]);
   if (k > 0 && threadIdx.x < 2) d[static_cast<int>(threadIdx.x) - 2] = threadIdx.x == 0 ? 0xFF : static_cast<uint8_t>(0xD0 + ((k - 1) & 7));
-  for (int i = threadIdx.x; i < n; i += 256) d[i] = s[i];
+  for (int j = threadIdx.x; j < n; j += 256) d[j] = s[j];
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_gather_kernel(const GatherArgs G) { jpeg_gather(G, static_cast<int>(blockIdx.x)); }
+
+// ---- batch -------------------------------------------------------------------------------------------------------------
+// The intervals of many files in one grid per kernel (ist_jpeg_encode_batch_device).  The unit is the PIECE, a run of MCU rows of one
+// file (JpegPiece, ist_jpeg_enc.h); the workgroups of all pieces are numbered piece-major, a workgroup finds its piece by binary
+// search over the pieces' first workgroups (transform) or first intervals (entropy, gather) and runs the body above on arguments made
+// from the piece's record.  The search is wave-uniform and the record is read through the constant address space, so the arguments
+// arrive in scalar registers as a kernarg struct does (the thumbnail twins of ist_preview.hip are the model).
+struct JpegBatchArgs {
+  const JpegPiece* pieces; int32_t n;
+  uint32_t* len;                 // per interval of the round: bytes written (pinned host memory, as the single encoder's)
+  const int64_t* dst;            // ... and its place in its file, laid out by the host between entropy and gather
+};
+typedef const __attribute__((address_space(4))) JpegPiece ConstPiece;
+
+template <bool BY_WG>
+__device__ __forceinline__ int jpeg_piece_of(ConstPiece* pieces, int n, int at) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {                                   // the last piece whose first entry is <= at
+    const int mid = (lo + hi + 1) >> 1;
+    if ((BY_WG ? pieces[mid].wg0 : pieces[mid].iv0) <= at) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_transform_batch_kernel(const JpegBatchArgs B) {
+  const int wg = static_cast<int>(blockIdx.x);
+  ConstPiece* P = (ConstPiece*)B.pieces + jpeg_piece_of<true>((ConstPiece*)B.pieces, B.n, wg);
+  const int local = wg - P->wg0, by = local / P->gx;
+  XformArgs A;
+  A.canvas = P->canvas; A.pitch = P->pitch; A.w = P->w; A.h = P->h; A.tab = P->tab; A.coef = P->coef;
+  A.mcus_x = P->mcus_x; A.mcu_row0 = P->mcu_row0; A.is420 = P->is420;
+  jpeg_transform(A, local - by * P->gx, by);
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_batch_kernel(const JpegBatchArgs B) {
+  const int iv = static_cast<int>(blockIdx.x);
+  ConstPiece* P = (ConstPiece*)B.pieces + jpeg_piece_of<false>((ConstPiece*)B.pieces, B.n, iv);
+  EntropyArgs A;
+  A.coef = P->coef; A.tab = P->tab; A.slots = P->slots; A.len = B.len + P->iv0;
+  A.row_blocks = P->row_blocks; A.bpm = P->bpm; A.slot = P->slot;
+  jpeg_entropy(A, iv - P->iv0);
+}
+
+// ... and the gather writes what no interval holds: the file's header (by the workgroup of the file's interval 0) and its EOI marker
+// (behind the file's last interval), so that every byte of a file comes from this launch
+__global__ __launch_bounds__(256) void ist_jpeg_gather_batch_kernel(const JpegBatchArgs B) {
+  const int iv = static_cast<int>(blockIdx.x);
+  ConstPiece* P = (ConstPiece*)B.pieces + jpeg_piece_of<false>((ConstPiece*)B.pieces, B.n, iv);
+  const int i = iv - P->iv0, k = P->mcu_row0 + i;
+  const GatherArgs G{P->slots, P->slot, P->out, B.dst + P->iv0, B.len + P->iv0, P->mcu_row0};
+  jpeg_gather(G, i);
+  if (k == 0) {
+    const uint8_t* head = P->head; uint8_t* out = P->out;
+    const int n = static_cast<int>(min(static_cast<int64_t>(P->head_len), P->out_cap));
+    for (int j = threadIdx.x; j < n; j += 256) out[j] = head[j];
+  }
+  if (k == P->mcus_y - 1 && threadIdx.x < 2) {
+    const int64_t at = G.dst[i] + static_cast<int64_t>(G.len[i]) + threadIdx.x;
+    if (at < P->out_cap) P->out[at] = threadIdx.x == 0 ? 0xFF : 0xD9;
+  }
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-void seg(std::vector<uint8_t>* o, int marker, const std::vector<uint8_t>& body) {
-  o->push_back(0xFF); o->push_back(static_cast<uint8_t>(marker));
-  o->push_back(static_cast<uint8_t>((body.size() + 2) >> 8)); o->push_back(static_cast<uint8_t>((body.size() + 2) & 255));
-  o->insert(o->end(), body.begin(), body.end());
-}
-
-// SOI, APP0, DQT x 2, DHT x 4, DRI, SOF0, SOS
-std::vector<uint8_t> header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart) {
-  std::vector<uint8_t> o{0xFF, 0xD8};
-  seg(&o, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
-  for (int s = 0; s < 2; ++s) {
-    std::vector<uint8_t> b{static_cast<uint8_t>(s)};
-    for (int k = 0; k < 64; ++k) b.push_back(T.q[s][kZigzag[k]]);
-    seg(&o, 0xDB, b);
-  }
-  for (int tc = 0; tc < 2; ++tc)
-    for (int s = 0; s < 2; ++s) {
-      std::vector<uint8_t> b{static_cast<uint8_t>(tc * 16 + s)};
-      const uint8_t* bits = tc ? kAcBits[s] : kDcBits[s];
-      b.insert(b.end(), bits, bits + 16);
-      if (tc) b.insert(b.end(), kAcVals[s], kAcVals[s] + 162); else b.insert(b.end(), kDcVals, kDcVals + 12);
-      seg(&o, 0xC4, b);
-    }
-  seg(&o, 0xDD, {static_cast<uint8_t>(restart >> 8), static_cast<uint8_t>(restart & 255)});
-  const uint8_t hv = subsampling == IST_JPEG_420 ? 0x22 : 0x11;
-  seg(&o, 0xC0, {8, static_cast<uint8_t>(h >> 8), static_cast<uint8_t>(h & 255), static_cast<uint8_t>(w >> 8), static_cast<uint8_t>(w & 255), 3,
-                 1, hv, 0, 2, 0x11, 1, 3, 0x11, 1});
-  seg(&o, 0xDA, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
-  return o;
-}
-
 // MCU rows per slab: what kBudget holds (IST_TUNING=1 IST_JPEG_ENC_ROWS=<rows> overrides, so that a small canvas crosses slabs)
 int64_t slab_rows_of(const Geometry& g) {
   static const int64_t knob = (tuning_mode() && std::getenv("IST_JPEG_ENC_ROWS")) ? std::atoll(std::getenv("IST_JPEG_ENC_ROWS")) : 0;
@@ -404,17 +376,24 @@ int check_args(const char* who, const void* canvas, size_t pitch, int64_t w, int
 
 }  // namespace
 
+int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k) {
+  const std::string who = std::string(what) + " " + std::to_string(k);
+  const int rc = check_args(who.c_str(), f.canvas, f.pitch, f.w, f.h, f.quality, f.subsampling);
+  if (rc) return rc;
+  if (!f.out) return fail(IST_E_INVALID, who + ": NULL output");
+  if ((reinterpret_cast<uintptr_t>(f.out) & 15) != 0) return fail(IST_E_INVALID, who + ": JPEG output buffer must be 16-byte aligned");
+  if (f.cap < ist_jpeg_bound(f.w, f.h, f.subsampling)) return fail(IST_E_INVALID, who + ": JPEG output buffer too small (see ist_jpeg_bound)");
+  return IST_OK;
+}
+
 // The file of a canvas in device memory into `out` (device, out_cap bytes).  The arguments have been checked.  Synchronises `stream`.
 int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, void* out,
                        int64_t out_cap, int64_t* out_len, hipStream_t stream) {
   const Geometry g = geometry(w, h, subsampling);
   const int64_t slab_rows = slab_rows_of(g);
   JpegTables T;
-  std::memset(&T, 0, sizeof T);
-  for (int s = 0; s < 2; ++s) { huff_codes(kDcBits[s], kDcVals, T.dc[s]); huff_codes(kAcBits[s], kAcVals[s], T.ac[s]); }
-  quant_tables(quality, T.q[0], T.q[1]);
-  for (int k = 0; k < 64; ++k) T.zz_of[kZigzag[k]] = static_cast<uint8_t>(k);
-  const std::vector<uint8_t> head = header(w, h, subsampling, T, g.mcus_x);
+  jpeg_enc_tables(quality, &T);
+  const std::vector<uint8_t> head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x);
   if (static_cast<int64_t>(head.size()) + 2 > out_cap) return fail(IST_E_INVALID, "JPEG output buffer too small (see ist_jpeg_bound)");
 
   const size_t o_coef = round256(sizeof T), coef_bytes = round256(static_cast<size_t>(slab_rows * g.row_blocks) * 128);
@@ -467,6 +446,79 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
   return IST_OK;
 }
 
+// Many canvases, round by round (jpeg_batch_pieces): the round's tables, headers and piece records go up in ONE copy through the
+// ring of ist_jobs_launch, then one transform and one entropy launch for all its pieces, one synchronisation in which the host lays the
+// intervals out per file, and one gather launch, which also writes headers and EOI markers.  Nothing else is copied.
+int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* stream_, const char* what, const int* ids) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int n = static_cast<int>(files.size());
+  const std::vector<ist_jpeg_piece> pieces = jpeg_batch_pieces(files.data(), n, jpeg_batch_budget());
+  const int n_pieces = static_cast<int>(pieces.size());
+  std::vector<JpegRound> rounds;
+  int64_t max_ivs = 0;
+  size_t max_scratch = 0;
+  for (int p0 = 0; p0 < n_pieces;) {
+    int p1 = p0 + 1;
+    while (p1 < n_pieces && pieces[p1].round == pieces[p0].round) ++p1;
+    rounds.push_back(jpeg_round_plan(files.data(), pieces.data(), p0, p1));
+    const JpegRound& R = rounds.back();
+    if (R.wgs > 2147483647ll) return fail(IST_E_UNSUPPORTED, "a JPEG batch round of more than 2^31 - 1 workgroups");
+    max_ivs = std::max(max_ivs, R.ivs); max_scratch = std::max(max_scratch, R.scratch_bytes);
+    p0 = p1;
+  }
+  // The ring and the scratch are held for the whole call: a second batch encode on this context waits here, so neither grows
+  // nor overwrites the scratch under this one's kernels.  A slot is refilled two rounds later at the earliest, behind the
+  // synchronisation of the round in between, which is queued behind this round's gather: no event is needed WHILE the lock is held
+  // through the last synchronisation (Drain below; whoever drops that must record slot->done and set slot->pending instead).
+  std::lock_guard<std::mutex> lk(ctx->batch_mu);
+  int rc = grow_device(&ctx->scratch_jpg, &ctx->scratch_jpg_bytes, max_scratch);
+  if (rc) return rc;
+  uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg);
+  // per interval of a round: its length (written by the kernel) and its place in its file (read by the gather), in pinned memory
+  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(static_cast<size_t>(max_ivs) * 16))};
+  if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
+  int64_t* const dst = reinterpret_cast<int64_t*>(res.p);
+  uint32_t* const len = reinterpret_cast<uint32_t*>(res.p + 8 * static_cast<size_t>(max_ivs));
+  std::vector<int64_t> pos(static_cast<size_t>(n), kJpegHeaderBytes);
+  // Every way out leaves the stream idle (kernels in flight read the slot and write `res`).
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
+  for (const JpegRound& R : rounds) {
+    ist_ctx::BatchSlot* slot = nullptr;
+    rc = batch_take_slot(ctx, R.table_bytes, &slot);
+    if (rc) return rc;
+    uint8_t* const d = static_cast<uint8_t*>(slot->dev);
+    jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch);
+    IST_HIP(hipMemcpyAsync(d, slot->host, R.table_bytes, hipMemcpyHostToDevice, stream));
+    const JpegBatchArgs B{reinterpret_cast<const JpegPiece*>(d + R.at_pieces), R.p1 - R.p0, len, dst};
+    hipLaunchKernelGGL(ist_jpeg_transform_batch_kernel, dim3(static_cast<unsigned>(R.wgs)), dim3(256), 0, stream, B);
+    IST_HIP(hipGetLastError());
+    count_jpeg_batch_launch();
+    hipLaunchKernelGGL(ist_jpeg_entropy_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
+    IST_HIP(hipGetLastError());
+    IST_HIP(hipStreamSynchronize(stream));
+    int64_t iv = 0;
+    for (int p = R.p0; p < R.p1; ++p) {
+      const ist_jpeg_piece& pc = pieces[static_cast<size_t>(p)];
+      JpegBatchFile& f = files[static_cast<size_t>(pc.file)];
+      const Geometry g = geometry(f.w, f.h, f.subsampling);
+      int64_t at = pos[static_cast<size_t>(pc.file)];
+      for (int64_t k = 0; k < pc.mcu_rows; ++k, ++iv) {
+        if (pc.mcu_row0 + k > 0) at += 2;              // RSTn
+        if (len[iv] < 1 || static_cast<int64_t>(len[iv]) >= g.slot) return fail(IST_E_HIP, "JPEG entropy kernel returned an impossible interval length");
+        dst[iv] = at;
+        at += len[iv];
+      }
+      if (at + 2 > f.cap) return fail(IST_E_INVALID, std::string(what) + " " + std::to_string(ids ? ids[pc.file] : pc.file) + ": JPEG output buffer too small (see ist_jpeg_bound)");
+      pos[static_cast<size_t>(pc.file)] = at;
+      if (pc.mcu_row0 + pc.mcu_rows == g.mcus_y) f.len = at + 2;
+    }
+    hipLaunchKernelGGL(ist_jpeg_gather_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(256), 0, stream, B);
+    IST_HIP(hipGetLastError());
+  }
+  IST_HIP(hipStreamSynchronize(stream));
+  return IST_OK;
+}
+
 // ... into a pooled pinned block of the file's real length.  Caller holds ctx->mu; the canvas is complete on ctx->stream.
 int jpeg_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, uint8_t** out_jpeg,
                  int64_t* out_len) {
@@ -501,14 +553,14 @@ int64_t ist_debug_jpeg_encode_launches(void) { return g_launches.load(std::memor
 int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {
   if (quality < 1 || quality > 100) return fail(IST_E_INVALID, "ist_jpeg_quant_tables: quality must be 1..100");
   if (!luma || !chroma) return fail(IST_E_INVALID, "ist_jpeg_quant_tables: NULL table");
-  quant_tables(quality, luma, chroma);
+  jpeg_quant_tables(quality, luma, chroma);
   return IST_OK;
 }
 
 int64_t ist_jpeg_bound(int64_t w, int64_t h, int subsampling) {
   if (w < 1 || h < 1 || w > 65535 || h > 65535 || (subsampling != IST_JPEG_444 && subsampling != IST_JPEG_420)) return -1;
   const Geometry g = geometry(w, h, subsampling);
-  return 1024 + g.mcus_y * (g.row_blocks * kBlockBytes + 16);
+  return 1024 + g.mcus_y * (g.row_blocks * kJpegBlockBytes + 16);
 }
 
 int ist_jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, void* out,

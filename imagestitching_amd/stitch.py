@@ -8,7 +8,8 @@ Two ways in:
   stitch(images, direction, opts)      host RGBA8 arrays in, host RGBA8 array out   (ist_stitch_rgba8)
   Stitcher(device).compile(...)        device-resident: torch CUDA tensors in/out, one fused launch per call
 and their batched forms: stitch_batch(requests) (ist_stitch_rgba8_batch), stitch_png_batch(requests) (ist_stitch_png_batch),
-launch_jobs(jobs, srcs, outs) (ist_jobs_launch) and encode_png_batch_device(canvases) (ist_png_encode_batch_device).
+launch_jobs(jobs, srcs, outs) (ist_jobs_launch), encode_png_batch_device(canvases) (ist_png_encode_batch_device),
+stitch_jpeg_batch(requests) (ist_stitch_jpeg_batch) and encode_jpeg_batch_device(canvases) (ist_jpeg_encode_batch_device).
 Resident bitmaps (ist_bitmap_*): decode_bitmaps(files) / upload_bitmap(image) keep images in HBM, and plan / stitch / stitch_png take
 a list of them in place of host images, so a restitch (reordered, other direction, new gap) uploads and decodes nothing.
 Previews (ist_preview_*): opts['preview'] = (box_w, box_h) on stitch_png / stitch_files adds the canvas shrunk to fit that box to the
@@ -849,6 +850,92 @@ def stitch_jpeg(images, direction, opts=None, device=0):
     w, h = int(cplan.canvas_w), int(cplan.canvas_h)
     L.lib.ist_plan_free(C.byref(cplan))
     return {"width": w, "height": h, "jpeg": _take_png(out, ln)}
+
+
+def _per_file(value, n, name):
+    """one value for all n files, or a sequence of length n"""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError("%s: expected one value or a sequence of length %d, got %d" % (name, n, len(value)))
+        return list(value)
+    return [value] * n
+
+
+def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None, stream=None):
+    """JPEG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch that is a multiple of 4) in
+    one transform, one entropy and one gather launch per round (ist_jpeg_encode_batch_device).  quality and subsampling: one value for
+    all files or a sequence of length n.  outs: optional CUDA uint8 tensors of at least ist_jpeg_bound + 16 bytes each.  Returns
+    [(tensor, length)], each file byte for byte what encode_jpeg_device gives for that canvas."""
+    import torch
+    canvases = list(canvases)
+    n = len(canvases)
+    if n == 0:
+        return []
+    args = []
+    for k, (q, s) in enumerate(zip(_per_file(quality, n, "quality"), _per_file(subsampling, n, "subsampling"))):
+        try:
+            args.append(_jpeg_args(q, s))
+        except (TypeError, ValueError) as e:
+            raise type(e)("file %d: %s" % (k, e)) from None
+    for k, c in enumerate(canvases):
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 4 or c.stride(2) != 1 or c.stride(1) != 4:
+            raise TypeError("canvas %d: expected an HxWx4 uint8 CUDA tensor with dense pixels" % k)
+    dev = canvases[0].device
+    if outs is None:      # (no bound: the call names what is wrong with the size)
+        outs = [torch.empty(max(int(L.lib.ist_jpeg_bound(int(c.shape[1]), int(c.shape[0]), a[1])), 0) + 16, dtype=torch.uint8, device=dev)
+                for c, a in zip(canvases, args)]
+    if len(outs) != n:
+        raise ValueError("encode_jpeg_batch_device: canvases and outs must have the same length")
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    src, pitch = (C.c_void_p * n)(), (C.c_size_t * n)()
+    w, h = (C.c_int64 * n)(), (C.c_int64 * n)()
+    qs, ss = (C.c_int * n)(*[a[0] for a in args]), (C.c_int * n)(*[a[1] for a in args])
+    dst, cap, ln = (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+    offs = []
+    for k, (c, o) in enumerate(zip(canvases, outs)):
+        src[k], pitch[k], h[k], w[k] = c.data_ptr(), c.stride(0), int(c.shape[0]), int(c.shape[1])
+        base = o.data_ptr()
+        aligned = (base + 15) & ~15
+        offs.append(aligned - base)
+        dst[k], cap[k] = aligned, o.numel() - (aligned - base)
+    L.check(L.lib.ist_jpeg_encode_batch_device(_ctx(dev.index or 0), src, pitch, w, h, qs, ss, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
+    return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(zip(outs, offs))]
+
+
+def stitch_jpeg_batch(requests, device=0):
+    """Many independent stitch_jpeg() calls in one go (ist_stitch_jpeg_batch): stitch_png_batch with a JPEG file in place of each
+    PNG.  requests as for stitch_batch; each request's opts may carry 'quality' (1..100, default 90) and 'subsampling' ('420'
+    default, or '444').  Returns a list of {'width', 'height', 'jpeg': bytes}, with None for a request without images; each file is
+    stitch_jpeg(*requests[k])['jpeg'], byte for byte."""
+    reqs = list(requests)
+    if not reqs:
+        return []
+    n = len(reqs)
+    plain, qs, ss = [], (C.c_int * n)(), (C.c_int * n)()
+    for k, r in enumerate(reqs):
+        if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
+            raise TypeError("request %d: expected (images, direction) or (images, direction, opts)" % k)
+        opts = dict(r[2] or {}) if len(r) == 3 else {}
+        try:
+            qs[k], ss[k] = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
+        except (TypeError, ValueError) as e:
+            raise type(e)("request %d: %s" % (k, e)) from None
+        plain.append((r[0], r[1], opts))
+    creqs, keep = _batch_requests(plain, "one GPU, JPEG files out")
+    ctx = _ctx(device)
+    plans = (L.Plan * n)()
+    outs = (C.POINTER(C.c_uint8) * n)()
+    lens = (C.c_int64 * n)()
+    L.check(L.lib.ist_stitch_jpeg_batch(ctx, creqs, n, qs, ss, plans, outs, lens))
+    res = []
+    for k in range(n):
+        if not outs[k]:
+            res.append(None)
+            continue
+        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
+        L.lib.ist_plan_free(C.byref(plans[k]))
+        res.append({"width": w, "height": h, "jpeg": _take_png(outs[k], C.c_int64(lens[k]))})
+    return res
 
 
 def encode_png_batch_device(canvases, outs=None, stream=None, level=None):

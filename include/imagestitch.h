@@ -662,6 +662,37 @@ IST_API int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, in
 /* transform launches (one per slab of MCU rows) made by JPEG encodes in this process so far */
 IST_API int64_t ist_debug_jpeg_encode_launches(void);
 
+/* ---- batched JPEG export: many canvases per launch --------------------------------------------------------------------------
+ * The encoder's unit of work is the restart interval (one MCU row), and an interval of file A needs an interval of file B as little
+ * as another interval of file A: a batch is the intervals of many files in one grid per kernel.  A batch runs in ROUNDS: as many
+ * MCU rows, in file order, as keep coefficients + interval slots within the encoder's scratch budget (256 MiB).  One MCU row costs
+ * row_blocks * 128 + slot bytes, row_blocks = ceil(w / MCU width) x blocks per MCU, slot = (row_blocks * 415 + 2 + 15) & ~15.  A round
+ * closes when the next row would not fit; a row above the budget on its own gets a round to itself.  The run of consecutive MCU
+ * rows of one file in one round is a PIECE; a file above the budget spans rounds as several pieces, in order.  One round is one
+ * transform, one entropy and one gather launch, one stream synchronisation (the host lays the intervals out, per file) and ONE
+ * host-to-device copy (tables, headers, piece records); the gather writes every byte of a file, header and EOI included. */
+typedef struct ist_jpeg_piece { int32_t file, round, mcu_row0, mcu_rows; } ist_jpeg_piece;
+/* pieces of a batch in encoding order; budget_bytes 0 = the encoder's own.  Returns the number of pieces (also when out is NULL or cap
+ * is too small: nothing is written beyond cap), negative on a bad argument (n < 1, a NULL array, a side outside 1..65535, an unknown
+ * subsampling, a negative budget or cap).  Pure CPU. */
+IST_API int64_t ist_jpeg_batch_layout(const int64_t* w, const int64_t* h, const int* subsampling, int n,
+                                      int64_t budget_bytes, ist_jpeg_piece* out, int64_t cap);
+/* ist_jpeg_encode_device for n canvases: file k is byte for byte the file that call writes for canvas k with quality[k] and
+ * subsampling[k].  Every file is checked by that call's rules before anything is enqueued; a bad file fails the whole call with a
+ * message that names it ("file k: ...").  n <= 0 or a NULL array: IST_E_INVALID; n > 4096: IST_E_UNSUPPORTED.  `stream` is
+ * synchronised before the call returns. */
+IST_API int ist_jpeg_encode_batch_device(ist_ctx* ctx, const void* const* canvases, const size_t* pitch, const int64_t* w,
+                                         const int64_t* h, const int* quality, const int* subsampling, int n,
+                                         void* const* out, const int64_t* out_cap, int64_t* out_len, void* stream);
+/* ist_stitch_png_batch with a JPEG in place of each PNG: the same sub-batches through the same two halves, each sub-batch's canvases
+ * encoded by the batch encoder; file k is byte for byte the file ist_stitch_jpeg returns for request k with quality[k] and
+ * subsampling[k].  A request without images gets NULL, length 0 and a zeroed plan.  All or nothing: a failing request fails the
+ * call, the message names it ("request k: ..."), and nothing is returned. */
+IST_API int ist_stitch_jpeg_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, const int* quality,
+                                  const int* subsampling, ist_plan* out_plans, uint8_t** out_jpeg, int64_t* out_len);
+/* rounds (one transform launch each) made by batch encodes in this process so far */
+IST_API int64_t ist_debug_jpeg_batch_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@
  *       -> Promise<({width,height,data,plan} | null)[]> / the array itself  (ist_stitch_rgba8_batch: one GPU, many stitches)
  *   stitchPngBatch(requests) / stitchPngBatchSync(requests): the same requests
  *       -> Promise<({width,height,png,plan} | null)[]> / the array itself  (ist_stitch_png_batch: one GPU, many PNG files)
+ *   stitchJpegBatch(requests) / stitchJpegBatchSync(requests): requests[k] = [..., quality, subsampling]
+ *       -> Promise<({width,height,jpeg,plan} | null)[]> / the array itself  (ist_stitch_jpeg_batch: one GPU, many JPEG files)
  *   render(canvasW, canvasH, clearRGBA, ops, images, filter, region, asPng?) -> Buffer (region pixels, or the PNG file)
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
  *   encodeJpeg(data, width, height, quality, subsampling) -> Buffer;  stitch / stitchBitmaps(..., filter, {quality, subsampling})
@@ -486,7 +488,8 @@ typedef struct {
   ist_stitch_request* reqs;
   ist_plan* plans;
   uint8_t** pixels;
-  int want_png; int64_t* lens;            /* stitchPngBatch: pixels[k] holds request k's PNG file, lens[k] bytes */
+  int want_png; int64_t* lens;            /* stitchPngBatch (1) / stitchJpegBatch (2): pixels[k] holds request k's file, lens[k] bytes */
+  int* quality; int* subsampling;         /* stitchJpegBatch: requests[k][6], requests[k][7] */
   int rc; char err[256];
   napi_deferred deferred; napi_async_work work;
 } batch_job;
@@ -498,7 +501,7 @@ static void batch_free(napi_env env, batch_job* j) {
     if (j->plans) ist_plan_free(&j->plans[k]);
     if (j->pixels && j->pixels[k]) ist_free(j->pixels[k]);
   }
-  free(j->im); free(j->lim); free(j->reqs); free(j->plans); free(j->pixels); free(j->lens); free(j);
+  free(j->im); free(j->lim); free(j->reqs); free(j->plans); free(j->pixels); free(j->lens); free(j->quality); free(j->subsampling); free(j);
 }
 
 static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_refs) {
@@ -517,6 +520,8 @@ static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_re
   j->plans = (ist_plan*)calloc(n ? n : 1, sizeof(ist_plan));
   j->pixels = (uint8_t**)calloc(n ? n : 1, sizeof(uint8_t*));
   j->lens = (int64_t*)calloc(n ? n : 1, sizeof(int64_t));
+  j->quality = (int*)calloc(n ? n : 1, sizeof(int));
+  j->subsampling = (int*)calloc(n ? n : 1, sizeof(int));
   for (uint32_t k = 0; k < n; k++) {
     napi_value r, a[6]; bool ra = false; uint32_t m = 0;
     napi_get_element(env, argv[0], k, &r);
@@ -533,6 +538,12 @@ static batch_job* batch_parse(napi_env env, napi_callback_info info, int want_re
     napi_get_value_double(env, a[3], &q->gap);
     limits_parse(env, a[4], &j->lim[k]);
     napi_get_value_int32(env, a[5], &v); q->filter = v;
+    j->quality[k] = 90; j->subsampling[k] = IST_JPEG_420;
+    if (m >= 8) {
+      napi_value e;
+      napi_get_element(env, r, 6, &e); if (napi_get_value_int32(env, e, &v) == napi_ok) j->quality[k] = v;
+      napi_get_element(env, r, 7, &e); if (napi_get_value_int32(env, e, &v) == napi_ok) j->subsampling[k] = v;
+    }
     q->images = j->im[k].descs; q->src = j->im[k].data; q->src_pitch = j->im[k].pitch; q->n_images = j->im[k].n; q->limits = &j->lim[k];
   }
   return j;
@@ -551,8 +562,9 @@ static void batch_execute(napi_env env, void* data) {
         snprintf(j->err, sizeof j->err, "request %d: \xe5\x9b\xbe\xe7\x89\x87%d\xe8\xa7\xa3\xe7\xa0\x81\xe5\xbc\x82\xe5\xb8\xb8", k, i);
         return;
       }
-  j->rc = j->want_png ? ist_stitch_png_batch(ctx, j->reqs, j->n, j->plans, j->pixels, j->lens)
-                      : ist_stitch_rgba8_batch(ctx, j->reqs, j->n, j->plans, j->pixels);
+  j->rc = j->want_png == 2 ? ist_stitch_jpeg_batch(ctx, j->reqs, j->n, j->quality, j->subsampling, j->plans, j->pixels, j->lens)
+          : j->want_png  ? ist_stitch_png_batch(ctx, j->reqs, j->n, j->plans, j->pixels, j->lens)
+                         : ist_stitch_rgba8_batch(ctx, j->reqs, j->n, j->plans, j->pixels);
   if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", ist_last_error());
 }
 
@@ -571,7 +583,7 @@ static napi_value batch_result(napi_env env, batch_job* j) {
     napi_create_object(env, &e);
     set_num(env, e, "width", (double)p->canvas_w);
     set_num(env, e, "height", (double)p->canvas_h);
-    napi_set_named_property(env, e, j->want_png ? "png" : "data", buf);
+    napi_set_named_property(env, e, j->want_png == 2 ? "jpeg" : j->want_png ? "png" : "data", buf);
     napi_set_named_property(env, e, "plan", plan_to_js(env, p));
     napi_set_element(env, arr, (uint32_t)k, e);
   }
@@ -597,7 +609,7 @@ static napi_value batch_async(napi_env env, napi_callback_info info, int want_pn
   j->want_png = want_png;
   napi_value promise, name;
   CHECK(napi_create_promise(env, &j->deferred, &promise));
-  napi_create_string_utf8(env, want_png ? "imagestitch.stitchPngBatch" : "imagestitch.stitchBatch", NAPI_AUTO_LENGTH, &name);
+  napi_create_string_utf8(env, want_png == 2 ? "imagestitch.stitchJpegBatch" : want_png ? "imagestitch.stitchPngBatch" : "imagestitch.stitchBatch", NAPI_AUTO_LENGTH, &name);
   CHECK(napi_create_async_work(env, NULL, name, batch_execute, batch_complete, j, &j->work));
   CHECK(napi_queue_async_work(env, j->work));
   return promise;
@@ -623,6 +635,9 @@ static napi_value js_stitch_batch_sync(napi_env env, napi_callback_info info) { 
 /* stitchPngBatch / stitchPngBatchSync: the same requests, a PNG file per request (the form setPngLevel chose) */
 static napi_value js_stitch_png_batch(napi_env env, napi_callback_info info) { return batch_async(env, info, 1); }
 static napi_value js_stitch_png_batch_sync(napi_env env, napi_callback_info info) { return batch_sync(env, info, 1); }
+/* stitchJpegBatch / stitchJpegBatchSync: requests[k] = [..., quality, subsampling], a JPEG file per request (ist_stitch_jpeg_batch) */
+static napi_value js_stitch_jpeg_batch(napi_env env, napi_callback_info info) { return batch_async(env, info, 2); }
+static napi_value js_stitch_jpeg_batch_sync(napi_env env, napi_callback_info info) { return batch_sync(env, info, 2); }
 
 static napi_value js_render(napi_env env, napi_callback_info info) {
   size_t argc = 8; napi_value argv[8];
@@ -1197,6 +1212,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"stitchBatchSync", NULL, js_stitch_batch_sync, NULL, NULL, NULL, napi_default, NULL},
       {"stitchPngBatch", NULL, js_stitch_png_batch, NULL, NULL, NULL, napi_default, NULL},
       {"stitchPngBatchSync", NULL, js_stitch_png_batch_sync, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchJpegBatch", NULL, js_stitch_jpeg_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"stitchJpegBatchSync", NULL, js_stitch_jpeg_batch_sync, NULL, NULL, NULL, napi_default, NULL},
       {"stitchFiles", NULL, js_stitch_files, NULL, NULL, NULL, napi_default, NULL},
       {"render", NULL, js_render, NULL, NULL, NULL, napi_default, NULL},
       {"encodePng", NULL, js_encode_png, NULL, NULL, NULL, napi_default, NULL},

@@ -46,6 +46,10 @@ export interface JpegOptions { quality?: number; subsampling?: '420' | '444' | 4
 export interface StitchJpegResult { width: number; height: number; jpeg: Buffer; plan: StitchPlan; }
 export function stitchJpeg(images: StitchImage[] | Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split' | 'preview' | 'pngLevel'> & JpegOptions): Promise<StitchJpegResult | null>;
 export function encodeJpeg(data: Uint8Array, width: number, height: number, opts?: JpegOptions): Buffer;
+// stitchPngBatch with a JPEG in place of each PNG: file k is the file stitchJpeg resolves for request k; null for a request without images
+export interface StitchJpegRequest { images: StitchImage[]; direction: Direction; opts?: StitchRequest['opts'] & JpegOptions; }
+export function stitchJpegBatch(requests: StitchJpegRequest[]): Promise<(StitchJpegResult | null)[]>;
+export function stitchJpegBatchSync(requests: StitchJpegRequest[]): (StitchJpegResult | null)[];
 export function setPngLevel(level: 0 | 1): void;
 export function decodePng(file: Uint8Array): { width: number; height: number; data: Buffer };
 export function stitchFiles(paths: string[], direction: Direction, opts?: StitchOptions, outPath?: string): Promise<StitchPngResult | null>;

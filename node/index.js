@@ -10,6 +10,7 @@
  *   stitchJpeg(images | Bitmap[], direction, opts + {quality, subsampling}) -> Promise<{width, height, jpeg, plan}>   (baseline JFIF)
  *   encodeJpeg(data, width, height, {quality, subsampling}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
+ *   stitchJpegBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, jpeg, plan} | null)[]>  (one GPU, many JPEG files)
  *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
  *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
@@ -189,14 +190,17 @@ function stitchSync(images, direction, opts) {
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
 const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'preview'];
+// the native arguments of request k of a batch, opts given apart (the JPEG batch takes its own two out first)
+function batchRequest(r, k, o) {
+  for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
+  if (Array.isArray(r.images) && r.images.some((x) => x instanceof Bitmap)) throw new TypeError('request ' + k + ': Bitmaps do not apply to a batch');
+  return args(r.images, r.direction, o);
+}
 function batchArgs(requests) {
   if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
   return requests.map((r, k) => {
     if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
-    const o = r.opts || {};
-    for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
-    if (Array.isArray(r.images) && r.images.some((x) => x instanceof Bitmap)) throw new TypeError('request ' + k + ': Bitmaps do not apply to a batch');
-    return args(r.images, r.direction, o);
+    return batchRequest(r, k, r.opts || {});
   });
 }
 /** Many independent stitches in one call (one GPU): resolves an array with one {width, height, data, plan} per request
@@ -230,6 +234,31 @@ function stitchPng(images, direction, opts) {
   }
   return withProgress(opts, () => { pngLevel(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
 }
+// requests[k] of stitchJpegBatch -> [...what a batch request is, quality, subsampling]; every error names its request
+function jpegBatchArgs(requests) {
+  if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
+  return requests.map((r, k) => {
+    if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
+    const o = Object.assign({}, r.opts || {});
+    try {
+      const j = jpegArgs(o); delete o.quality; delete o.subsampling;
+      return batchRequest(r, k, o).concat([j.quality, j.subsampling]);
+    } catch (e) {
+      if (!e.message.startsWith('request ' + k)) e.message = 'request ' + k + ': ' + e.message;
+      throw e;
+    }
+  });
+}
+/** stitchPngBatch with the JPEG export: resolves one {width, height, jpeg: Buffer, plan} per request - the file stitchJpeg gives for
+ *  it - and null for a request without images. Each request's opts may carry quality (1..100, default 90) and subsampling ('420'
+ *  default, '444'). One transform, one entropy and one gather launch encode every file of a sub-batch. */
+function stitchJpegBatch(requests) {
+  let a;
+  try { a = jpegBatchArgs(requests); } catch (e) { return Promise.reject(e); }
+  if (!a.length) return Promise.resolve([]);
+  return native.stitchJpegBatch(a);
+}
+function stitchJpegBatchSync(requests) { const a = jpegBatchArgs(requests); return a.length ? native.stitchJpegBatchSync(a) : []; }
 const SUBSAMPLING = { 444: 0, 420: 1 };          // IST_JPEG_444 / IST_JPEG_420
 // {quality, subsampling} of a JPEG export, checked: an integer quality 1..100 (default 90), subsampling '420' (default) or '444'
 function jpegArgs(o) {
@@ -292,5 +321,5 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, decodePng, decodeImage, plan,
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, decodePng, decodeImage, plan,
                    decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };

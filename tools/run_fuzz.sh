@@ -2,6 +2,7 @@
 # Sanitizer (ASan + UBSan, CPU only) fuzzing of the host-side code that faces untrusted input.
 #   tools/run_fuzz.sh ITERS seed1 [seed2 ...]     mutation-fuzz the file parsers (PNG / JPEG / BMP / GIF / WebP) from seed files
 #   tools/run_fuzz.sh compile ITERS               random + hostile op lists through the op-list compiler, invariants checked
+#   tools/run_fuzz.sh jpegbatch ITERS [SEED]      random batches through the rounds, header blob and piece records of the batched JPEG export
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); C=$ROOT/imagestitching_amd/csrc
 OUT=${IST_FUZZ_BIN:-/tmp/ist_fuzz}
@@ -10,6 +11,9 @@ export ASAN_OPTIONS=detect_leaks=0:allocator_may_return_null=1
 if [ "$1" = compile ]; then
   shift
   g++ $FLAGS "$HERE/fuzz_compile.cpp" "$C/ist_compile.cpp" "$C/ist_plan.cpp" "$C/ist_shard.cpp" -o "$OUT"
+elif [ "$1" = jpegbatch ]; then
+  shift
+  g++ $FLAGS "$HERE/check_jpeg_batch_host.cpp" "$C/ist_jpeg_enc_host.cpp" -o "$OUT"
 else
   # (IST_FUZZ_REUSE=1: keep a binary that is already there - the tests build the harness once per session)
   if [ -z "$IST_FUZZ_REUSE" ] || [ ! -x "$OUT" ]; then
