@@ -225,6 +225,7 @@ SYMBOLS = [
                                                C.POINTER(Preview)]),
     ("ist_bitmap_preview", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
     ("ist_debug_preview_launches", C.c_int64, []),
+    ("ist_debug_preview_geometry", C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("ist_thumb_layout", C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(ThumbSpec), C.POINTER(ThumbItem), C.POINTER(C.c_int64)]),
     ("ist_thumbs_device", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(ThumbSpec),
                                     C.c_void_p, C.c_int64, C.POINTER(ThumbItem), C.c_void_p]),

@@ -148,6 +148,15 @@ extern "C" {
 
 int64_t ist_debug_preview_launches(void) { return g_preview_launches.load(std::memory_order_relaxed); }
 
+int ist_debug_preview_geometry(int64_t w, int64_t h, int32_t pw, int32_t ph, int32_t out[6]) {
+  if (!out) return fail(IST_E_INVALID, "ist_debug_preview_geometry: NULL output");
+  std::memset(out, 0, 6 * sizeof(int32_t));
+  PreviewArgs a;
+  if (!preview_geometry(w, h, pw, ph, &a)) return 1;         // the job path
+  out[0] = a.per_group; out[1] = a.groups; out[2] = a.passes; out[3] = a.sub; out[4] = a.chunk_rows; out[5] = a.chunks;
+  return IST_OK;
+}
+
 int ist_preview_fit(int64_t w, int64_t h, double box_w, double box_h, int32_t* out_w, int32_t* out_h) {
   if (!out_w || !out_h) return fail(IST_E_INVALID, "ist_preview_fit: NULL output");
   *out_w = *out_h = 0;

@@ -546,6 +546,11 @@ IST_API int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths,
 IST_API int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint8_t* dst, size_t dst_pitch);
 /* launches of the source-stationary reduce in this process so far (tests tell it from the job path with it) */
 IST_API int64_t ist_debug_preview_launches(void);
+/* the workgroup shape the reduce runs a w x h -> pw x ph preview with (pure CPU, no context: tests assert the regime of a case with
+ * it, as with ist_debug_cells): out = per_group (output pixels that share one 256-column footprint), groups (per output row), passes
+ * (256-column passes over a footprint), sub (lanes that fold one box), chunk_rows, chunks (row chunks per box).  Returns 1 with out
+ * zeroed for a shape that does not shrink on both axes (the job path).  IST_E_INVALID: NULL out. */
+IST_API int ist_debug_preview_geometry(int64_t w, int64_t h, int32_t pw, int32_t ph, int32_t out[6]);
 
 /* ---- thumbnails: a grid of images cropped, turned and shrunk together (the page's grid of chosen images: one <image mode="aspectFill">
  * per image at thumbWpx x thumbWpx, pages/index/index.wxml:4-22, cell size from index.js:313-343; the modal image of index.wxml:202 is
