@@ -1107,26 +1107,29 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
       d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
     } else if (CUBIC && cubic) {
       // IST_FILTER_CUBIC with an axis that does not shrink: four Catmull-Rom taps there, the box on an axis that shrinks (a draw that
-      // shrinks on both took the branch above: the same bytes as under IST_FILTER_AREA).  fp32 sums of premultiplied taps, rows first.
+      // shrinks on both took the branch above: the same bytes as under IST_FILTER_AREA).  Sums of premultiplied taps, rows first, the
+      // fp32 weights of the streamed path but fp64 sums: a premultiplied tap has 16 bits, so at dyadic weights (a 2x enlargement: 128ths
+      // per axis) an fp32 sum drops bits the streamed path, which leaves opaque taps unmultiplied, keeps - and every exact rounding tie
+      // x.5, 3 % of the bytes of a 2x enlargement, fell to x (tests/test_gpu_cubic_regimes.py, the IST_NO_LDS child, SP2/opaque/2r).
       const CubicAxis ax = cubic_axis(op.kx, op.ox, wx), ay = cubic_axis(op.ky, op.oy, wy);
-      float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+      double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
       for (int jy = 0; jy < ay.n; ++jy) {
-        const float oyw = cubic_axis_weight(ay, jy);
+        const double oyw = static_cast<double>(cubic_axis_weight(ay, jy));
         const uint8_t* srow = src + static_cast<size_t>(min(max(ay.i0 + jy, op.cy0), op.cy1)) * sp;
-        float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+        double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
         for (int jx = 0; jx < ax.n; ++jx) {
-          const float oxw = cubic_axis_weight(ax, jx);
+          const double oxw = static_cast<double>(cubic_axis_weight(ax, jx));
           const uint32_t s = ld4(srow + 4 * static_cast<size_t>(min(max(ax.i0 + jx, op.cx0), op.cx1)));
-          const float a = static_cast<float>(s >> 24);
-          r0 += oxw * (static_cast<float>(ch(s, 0)) * a); r1 += oxw * (static_cast<float>(ch(s, 1)) * a);
-          r2 += oxw * (static_cast<float>(ch(s, 2)) * a); r3 += oxw * a;
+          const uint32_t a = s >> 24;
+          r0 += oxw * static_cast<double>(ch(s, 0) * a); r1 += oxw * static_cast<double>(ch(s, 1) * a);
+          r2 += oxw * static_cast<double>(ch(s, 2) * a); r3 += oxw * static_cast<double>(a);
         }
         acc0 += oyw * r0; acc1 += oyw * r1; acc2 += oyw * r2; acc3 += oyw * r3;
       }
       // the negative lobes overshoot: alpha to [0, 255], each premultiplied colour to [0, alpha], before compositing
-      const double Aa = fmin(fmax(static_cast<double>(acc3), 0.0), 255.0);
+      const double Aa = fmin(fmax(acc3, 0.0), 255.0);
       const double keep = 1.0 - cov * (Aa / 255.0);
-      const float accs[3] = {acc0, acc1, acc2};
+      const double accs[3] = {acc0, acc1, acc2};
       uint32_t o = 0;
 #pragma unroll
       for (int ch_ = 0; ch_ < 3; ++ch_) {

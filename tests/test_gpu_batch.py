@@ -14,6 +14,7 @@ import torch
 import imagestitching_amd as ist
 from imagestitching_amd import _lib as L
 from imagestitching_amd.stitch import _filter_of, _merge
+from tests import cubic_reference as R
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -32,9 +33,11 @@ def _rand_entry(rng, k):
     px = [U.rand_image(1000 * k + i, int(rng.integers(6, 180)), int(rng.integers(6, 180)), opaque=opaque) for i in range(n)]
     ori = [int(v) for v in rng.integers(1, 9, n)] if rng.random() < 0.4 else [1] * n
     opts = {"mode": str(rng.choice(["min", "max", "original"])), "gap": int(rng.choice([0, 0, 3, 8])),
-            "filter": str(rng.choice(["nearest", "bilinear", "area"]))}
+            "filter": str(rng.choice(["nearest", "bilinear", "area", "cubic"]))}
     if rng.random() < 0.25:
         opts["edgeAA"] = True
+    if rng.random() < 0.5:
+        opts["superSample"] = 2.2                             # (a canvas 2.2x as large: most draws are enlarged, which under 'cubic' is the streamed Catmull-Rom path)
     direction = str(rng.choice(["vertical", "horizontal"]))
     clip = None
     if rng.random() < 0.25:
@@ -102,7 +105,7 @@ def test_random_batches_match_single_launches_write_every_clip_pixel_and_keep_th
         before = _batch_launches()
         ist.launch_jobs([e["job"] for e in es], [e["srcs"] for e in es], outs)
         torch.cuda.synchronize()
-        assert 1 <= _batch_launches() - before <= 5
+        assert 1 <= _batch_launches() - before <= 7           # one launch per kernel kind: five, and the two of cubic jobs (5: streamed cubic, 6: + the per-pixel stack)
         assert bool((raw[guard] == GUARD).all()), "a byte outside every canvas changed"
         results.append([o.cpu().numpy() for o in outs])
     for k, e in enumerate(es):
@@ -113,12 +116,16 @@ def test_random_batches_match_single_launches_write_every_clip_pixel_and_keep_th
         inside[y0:y0 + h, x0:x0 + w] = True
         assert np.array_equal(results[0][k][inside], results[1][k][inside]), "entry %d: a clip pixel was not written" % k
         assert (results[1][k][~inside] == POISON_B).all() and (results[0][k][~inside] == POISON_A).all(), "entry %d: wrote outside its clip" % k
-    # every entry against the oracle (area, edge AA and clipped entries included: the reference cropped to the clip): nearest
+    # every entry against the oracle (area, cubic, edge AA and clipped entries included: the reference cropped to the clip): nearest
     # without AA exact, otherwise the op-list rule, and differences rare
     stats = U.RareDiff()
     for k, e in enumerate(es):
-        ref, _, _ = U.oracle_stitch(e["px"], e["direction"], e["opts"], e["ori"])
-        assert (ref[..., 3] == 255).all()          # a strip is filled white first: every pixel is solid (within 1 LSB, or exact)
+        if e["opts"]["filter"] == "cubic":         # (the oracle does not know the filter: the fp64 reference of tests/cubic_reference.py on the plan's ops)
+            p = e["plan"]
+            ref = R.render_ops(p.canvas_w, p.canvas_h, R.plan_ops(p), None, e["px"], "cubic", edge_aa=U.edge_aa_of(e["opts"]))
+        else:
+            ref, _, _ = U.oracle_stitch(e["px"], e["direction"], e["opts"], e["ori"])
+        assert ref.shape[:2] == e["shape"] and (ref[..., 3] == 255).all()          # a strip is filled white first: every pixel is solid (within 1 LSB, or exact)
         x0, y0, w, h = e["clip"] if e["clip"] else (0, 0, e["shape"][1], e["shape"][0])
         exact = e["opts"]["filter"] == "nearest" and not e["opts"].get("edgeAA")
         try:

@@ -23,25 +23,12 @@ import imagestitching_amd as ist
 from imagestitching_amd import _lib as L
 from imagestitching_amd.stitch import _ctx
 from tests import cubic_reference as R
+from tests import cubic_render as G
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
-CUBIC, AA = 3, 0x100
-
-
-def _c_ops(ops_o):
-    ops = (L.Op * len(ops_o))()
-    for i, o in enumerate(ops_o):
-        ops[i].m[:] = o["m"]
-        if o["kind"] == "fill":
-            ops[i].kind = 0; ops[i].image = -1; ops[i].d[:] = o["rect"]; ops[i].rgba[:] = o["rgba"]
-        else:
-            ops[i].kind = 1; ops[i].image = o["image"]; ops[i].s[:] = o["s"]; ops[i].d[:] = o["d"]
-    return ops
-
-
-def _descs(px, opaque=None):
-    return (L.ImageDesc * len(px))(*[L.ImageDesc(a.shape[1], a.shape[0], 1, 0, 0, int(bool(opaque and opaque[k])), 0) for k, a in enumerate(px)])
+CUBIC, AA = G.CUBIC, G.AA
+_c_ops, _descs = G.c_ops, G.descs
 
 
 def _render_host(cw, ch, clear, ops_o, px, aa):
@@ -56,29 +43,7 @@ def _render_host(cw, ch, clear, ops_o, px, aa):
     return out
 
 
-GUARD = 3          # poisoned rows above and below the canvas, and poisoned columns to its right (the row pitch is wider than the canvas)
-
-
-def _render_job(cw, ch, clear, ops_o, px, opaque, filt=CUBIC):
-    """A compiled job on device tensors.  The canvas sits inside a larger tensor of 0x5A (guard rows above and below, a pitch 5
-    pixels wider than the canvas); every source sits inside a larger tensor of poison with its true pitch, so a tap outside the
-    bitmap reads poison instead of a neighbour's valid bytes.  Returns (canvas, job.info) after checking the guards."""
-    job = ist.Stitcher(0).compile_ops(cw, ch, _c_ops(ops_o), len(ops_o), _descs(px, opaque), len(px), filt, clear=clear)
-    big = torch.full((ch + 2 * GUARD, cw + 5, 4), 0x5A, dtype=torch.uint8, device="cuda")
-    out = big[GUARD:GUARD + ch, :cw]
-    srcs = []
-    for a in px:
-        h, w = a.shape[:2]
-        host = np.full((h + 4, w + 7, 4), 0xC3, np.uint8)
-        host[2:2 + h, 3:3 + w] = a
-        srcs.append(torch.from_numpy(host).cuda()[2:2 + h, 3:3 + w])
-    job.launch(srcs, out)
-    torch.cuda.synchronize()
-    info = dict(job.info)
-    job.close()
-    whole = big.cpu().numpy()
-    assert (whole[:GUARD] == 0x5A).all() and (whole[GUARD + ch:] == 0x5A).all() and (whole[:, cw:] == 0x5A).all(), "a write left the canvas"
-    return whole[GUARD:GUARD + ch, :cw].copy(), info
+_render_job = G.render_job          # (guard rows, a wider canvas pitch, sources embedded in poison: tests/cubic_render.py)
 
 
 # ------------------------------------------------------------------------------------------------ op-list fuzz

@@ -285,3 +285,48 @@ def test_area_on_a_device_list_matches_the_single_device_result(devices, split, 
     assert np.array_equal(many["data"], one["data"])
     ref, _, _ = U.oracle_stitch(px, direction, opts, orientations=AREA_ORI)
     U.oracle_tolerance(many["data"], ref)
+
+
+# a 'max' strip super-sampled 2.2x: every draw is enlarged 2.2x to 8x, mirrored (3, 2) or not: the streamed cubic path on every part
+CUBIC_SIZES = [(260, 110), (70, 95), (131, 140), (201, 77)]
+CUBIC_ORI = [1, 3, 2, 1]
+
+
+@pytest.mark.parametrize("split", ["band", "rows", "image"])
+def test_cubic_group_job_with_poisoned_partial_holdings(split):
+    """ist_group_job_launch under 'cubic': a part holds one source row more at either end than under bilinear (the taps floor(f) - 1 ..
+    floor(f) + 2).  Each part gets a buffer whose rows above sy0 and below sy1 are poison and a view that starts at sy0, so a fourth-tap
+    row that is not held, or a row tap clamped to the holding instead of to the draw, changes bytes: the result must equal, byte for
+    byte, the same job launched on whole images, and satisfy the op-list rule against the fp64 reference."""
+    import torch
+    from tests import cubic_reference as R
+    px = [U.rand_image(890 + i, h, w, opaque=(i != 2)) for i, (w, h) in enumerate(CUBIC_SIZES)]
+    opts = {"filter": "cubic", "mode": "max", "superSample": 2.2, "gap": 2}
+    g = ist.StitchGroup([0] * 5)
+    job = g.compile(U.hip_images(px, CUBIC_ORI), "vertical", dict(opts, split=split))
+    assert job.plan.super_sample == 2.2 and job.plan.canvas_w == int(260 * 2.2)
+    assert len({p["slot"] for p in job.parts}) >= 4 and {p["image"] for p in job.parts} == {0, 1, 2, 3}
+    assert split == "image" or any(0 < p["rows"][0] or p["rows"][1] < CUBIC_SIZES[p["image"]][1] for p in job.parts)      # (some holding is partial)
+    full = [torch.from_numpy(a).cuda() for a in px]
+    srcs, keep = [], []
+    pad = 8
+    for p in job.parts:
+        a, b = p["rows"]
+        t = full[p["image"]]
+        buf = torch.full((b - a + 2 * pad, t.shape[1], 4), 0xEE, dtype=torch.uint8, device="cuda")
+        buf[..., 1] = 0x11
+        buf[pad:pad + b - a] = t[a:b]
+        keep.append(buf)
+        srcs.append((buf[pad:pad + b - a], a))
+    out = torch.full((job.plan.canvas_h, job.plan.canvas_w, 4), 0x5A, dtype=torch.uint8, device="cuda")
+    job.launch(srcs, out)
+    whole = torch.full_like(out, 0x5A)
+    job.launch([full[p["image"]] for p in job.parts], whole)
+    g.sync()
+    assert torch.equal(out, whole)
+    ref = R.render_ops(job.plan.canvas_w, job.plan.canvas_h, R.plan_ops(job.plan), None, px, "cubic")
+    stats = U.RareDiff()
+    stats.add(U.oracle_tolerance(out.cpu().numpy(), ref))
+    print("cubic group job (%s):" % split, stats)
+    stats.check()
+    job.close()
