@@ -18,6 +18,11 @@ pw, ph) is the device-to-device form and preview_fit(w, h, box_w, box_h) the fit
 Thumbnails (ist_thumb_*): thumbnails(bitmaps, cell) is the page's grid of chosen images - every bitmap cropped to the cell's aspect
 ratio ('fill') or fitted into it ('fit'), turned by its EXIF orientation and shrunk, all in one launch pair and one copy down;
 thumbnails_device(tensors, cell) is the device-to-device form and thumbnail_layout(descs, cell, mode) the rule.
+
+What callers bring is judged in one place each, before any context is asked for: host pixels by _host_sources (type, stored size, and a
+view with padded rows is read where it is - only reversed, repeated or interleaved layouts are copied, once), canvases in HBM by
+_check_canvas, an encoder's output tensor by _file_out.  _plan_args / _plan_size are the argument run and the epilogue of every
+planning call, _stitch the one choice of entry point behind stitch / stitch_png / stitch_jpeg, _run_batch the three batches' call.
 """
 import ctypes as C
 import os
@@ -136,10 +141,7 @@ def preview_device(tensor, pw, ph, out=None, stream=None, opaque=False):
     into a fresh pw x ph canvas reads back under filter 'area'.  Asynchronous on `stream` (default: the tensor's current stream).
     opaque: the caller's hint that every alpha byte is 255."""
     import torch
-    if tensor.dtype != torch.uint8 or tensor.dim() != 3 or tensor.shape[2] != 4 or tensor.stride(2) != 1 or tensor.stride(1) != 4:
-        raise TypeError("expected an HxWx4 uint8 CUDA tensor with dense pixels")
-    if not tensor.is_cuda:
-        raise TypeError("preview_device: the source must be a CUDA tensor (host pixels: upload_bitmap(...).preview(...))")
+    _check_canvas(tensor, "preview_device: ")
     pw, ph = int(pw), int(ph)
     if pw < 1 or ph < 1:
         raise L.StitchError(-1, "preview_device: the preview must be at least 1 x 1")
@@ -204,14 +206,7 @@ def thumbnails_device(tensors, cell, mode="fill", orientations=None, opaque=Fals
     n = len(tensors)
     if n == 0:
         return []
-    for t in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError("thumbnails_device: the sources must be CUDA tensors (host pixels: upload_bitmap, then thumbnails)")
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 4 or t.stride(2) != 1 or t.stride(1) != 4:
-            raise TypeError("expected HxWx4 uint8 CUDA tensors with dense pixels")
-        if t.device != tensors[0].device:
-            raise TypeError("thumbnails_device: the sources must live on one device")
-    dev = tensors[0].device
+    dev = _check_canvases(tensors, "thumbnails_device: ")
     orientations = [1] * n if orientations is None else list(orientations)
     opaques = [bool(opaque)] * n if isinstance(opaque, (bool, int)) else [bool(o) for o in opaque]
     if len(orientations) != n or len(opaques) != n:
@@ -305,14 +300,27 @@ class StitchPlan:
             pass
 
 
+def _plan_args(direction, o):
+    """The argument run every planning entry point of the library shares, from (direction, merged opts): direction, mode, gap,
+    limits, filter.  (ctypes passes the Limits by reference and the tuple keeps it alive over the call.)"""
+    return _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0), _limits(o), _filter_of(o)
+
+
+def _plan_size(rc, cplan):
+    """(canvas_w, canvas_h) of the plan a stitch call filled in, with the plan freed; None when there was nothing to stitch"""
+    if rc == L.IST_NOTHING_TO_DO:
+        return None
+    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
+    L.lib.ist_plan_free(C.byref(cplan))
+    return w, h
+
+
 def plan(images, direction, opts=None):
     """Pure-CPU planner.  Returns a StitchPlan, or None when there is nothing to stitch (index.js:1189)."""
     o = _merge(opts)
     descs = _bitmap_descs(images) if _is_bitmap_request(images, o) else _descs(images)
     cplan = L.Plan()
-    lim = _limits(o)
-    rc = L.check(L.lib.ist_plan_compute(descs, len(images), _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                        C.byref(lim), C.byref(cplan)))
+    rc = L.check(L.lib.ist_plan_compute(descs, len(images), *_plan_args(direction, o)[:4], C.byref(cplan)))
     if rc == L.IST_NOTHING_TO_DO:
         return None
     return StitchPlan(cplan, descs, len(images))
@@ -359,52 +367,98 @@ def _ctx_png(device, level):
     return c
 
 
-def stitch(images, direction, opts=None, device=0):
-    """stitch(images, direction, opts) -> {'width', 'height', 'data'}: host arrays through the HIP path.
+def _rgba(a, who=""):
+    """The type and shape rule of host pixels: an HxWx4 uint8 array (anything np.asarray makes one of)"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+        raise TypeError(who + "expected an HxWx4 uint8 RGBA array")
+    return a
 
-    images[i] = {'width', 'height', 'data': HxWx4 uint8 (RGBA, straight alpha), 'orientation'?: 1..8, 'fileSize'?}
-    or simply an HxWx4 uint8 array; or a list of Bitmaps (decode_bitmaps / upload_bitmap: nothing is uploaded).  Returns None when
-    images is empty (the reference returns early).
-    """
-    o = _merge(opts)
-    _no_preview(o, "stitch", "the caller gets the pixels; stitch_png / stitch_files keep the canvas in HBM and can add its preview")
+
+def _host_rows(a, desc=None, who="", align=1):
+    """The size and layout rule of one image's host pixels (after _rgba) -> (array to keep alive, its address, row pitch).  The array
+    covers the stored size of its desc (bitmap_w x bitmap_h of the library, which reads that much).  A view goes as it is when its
+    pixels are dense and its rows at least 4 * columns (and a multiple of `align`) apart; anything else - reversed or repeated rows,
+    interleaved columns - is copied once."""
+    if desc is not None:
+        bw, bh = desc.bmp_width if desc.bmp_width > 0 else desc.width, desc.bmp_height if desc.bmp_height > 0 else desc.height
+        if a.shape[0] < bh or a.shape[1] < bw:
+            raise ValueError("%sthe pixels (%dx%d) are smaller than the bitmap (%dx%d)" % (who, a.shape[1], a.shape[0], bw, bh))
+    pitch = a.strides[0]
+    if a.strides[2] != 1 or a.strides[1] != 4 or pitch < 4 * a.shape[1] or pitch % align:
+        a, pitch = np.ascontiguousarray(a), 4 * a.shape[1]
+    return a, a.ctypes.data, pitch
+
+
+def _host_sources(images, who="", descs=None, holes=False):
+    """The one marshal of a request's host pixels -> (descs, ptrs, pitches, keep): images as stitch() takes them, each under the rules
+    of _rgba and _host_rows, with `keep` what must stay alive during the call.  who: 'request k' in a batch.  Nothing here needs a
+    device, so every entry point marshals before it asks for its context.  render_ops brings its own descs and has holes (None: an
+    image no op draws); everywhere else missing pixels are the reference's decode failure."""
+    n = len(images)
+    each = (who + ", " if who else "") + "image %d: "
+    arrays = []
+    for i, im in enumerate(images):
+        a = im.get("data") if isinstance(im, dict) else im
+        if a is None and not holes:
+            raise L.StitchError(-6, "%s图片%d解码异常" % (who + ": " if who else "", i))
+        arrays.append(a if a is None else _rgba(a, each % i))
+    if descs is None:
+        descs = _descs(images)
+    keep, ptrs, pitches = [], (C.c_void_p * max(1, n))(), (C.c_size_t * max(1, n))()
+    for i, a in enumerate(arrays):
+        if a is not None:
+            a, ptrs[i], pitches[i] = _host_rows(a, descs[i], each % i)
+            keep.append(a)
+    return descs, ptrs, pitches, keep
+
+
+def _stitch(images, direction, o, device, kind, jpeg=()):
+    """stitch / stitch_png / stitch_jpeg behind their option rules: one library call chosen by (host images | Bitmaps) x kind, kind =
+    'rgba8' (pixels; with devices= the sharded ist_stitch_rgba8_multi), 'png' (+ '_preview' when opts ask for one) or 'jpeg' (jpeg =
+    (quality, IST_JPEG_*)): ist_stitch_<kind>[_preview] / ist_stitch_bitmaps_<kind>[_preview]."""
     n = len(images)
     if n == 0:
         return None
     if _is_bitmap_request(images, o):
-        return _stitch_bitmaps(images, n, direction, o, device, False)
-    descs = _descs(images)
-    keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-    for i, im in enumerate(images):
-        a = im["data"] if isinstance(im, dict) else im
-        if a is None:
-            raise L.StitchError(-6, "图片%d解码异常" % i)
-        a = np.asarray(a)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
-            raise TypeError("image %d: expected an HxWx4 uint8 RGBA array" % i)
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        keep.append(a)
-        ptrs[i] = a.ctypes.data
-        pitches[i] = a.strides[0]
-    # ist_stitch_rgba8 (what the N-API addon binds): plan, render, and the export as ONE DMA into a pinned block of the
-    # library's pool; the numpy array below is a view of that block (no host copy) and returns it to the pool when it
-    # is garbage collected
-    cplan = L.Plan()
-    lim = _limits(o)
-    out = C.POINTER(C.c_uint8)()
-    if o.get("devices"):
-        devs = (C.c_int * len(o["devices"]))(*[int(d) for d in o["devices"]])
-        rc = L.check(L.lib.ist_stitch_rgba8_multi(devs, len(o["devices"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                                  float(o["gap"] or 0), C.byref(lim), _filter_of(o), _SPLITS[o["split"]], C.byref(cplan), C.byref(out)))
+        name, srcs = "ist_stitch_bitmaps_" + kind, ((C.c_void_p * n)(*[None if b is None else b.handle() for b in images]),)
     else:
-        rc = L.check(L.lib.ist_stitch_rgba8(_ctx(device), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                            float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out)))
-    if rc == L.IST_NOTHING_TO_DO:
+        descs, ptrs, pitches, keep = _host_sources(images)
+        name, srcs = "ist_stitch_" + kind, (descs, ptrs, pitches)
+    pv = _preview_arg(o) if kind == "png" else None
+    cplan, out, ln = L.Plan(), C.POINTER(C.c_uint8)(), C.c_int64(0)
+    tail = [C.byref(cplan), C.byref(out)] + ([] if kind == "rgba8" else [C.byref(ln)]) + ([] if pv is None else [C.byref(pv)])
+    if kind == "rgba8" and o.get("devices"):
+        devs = (C.c_int * len(o["devices"]))(*[int(d) for d in o["devices"]])
+        name, head, mid = name + "_multi", (devs, len(devs)), (_SPLITS[o["split"]],)
+    else:
+        head, mid = (_ctx_png(device, o["pngLevel"]) if kind == "png" else _ctx(device),), jpeg
+    # (rgba8, what the N-API addon binds: plan, render, and the export as ONE DMA into a pinned block of the library's pool; the numpy
+    # array below is a view of that block - no host copy - and returns it to the pool when it is garbage collected)
+    fn = getattr(L.lib, name + ("_preview" if pv is not None else ""))
+    size = _plan_size(L.check(fn(*head, *srcs, n, *_plan_args(direction, o), *mid, *tail)), cplan)
+    if size is None:
         return None
-    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
-    L.lib.ist_plan_free(C.byref(cplan))
-    return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
+    res = {"width": size[0], "height": size[1]}
+    if kind == "rgba8":
+        res["data"] = _take_pixels(out, *size)
+    else:
+        res[kind] = _take_png(out, ln)
+    if pv is not None:
+        res["preview"] = _take_preview(pv)
+    return res
+
+
+def stitch(images, direction, opts=None, device=0):
+    """stitch(images, direction, opts) -> {'width', 'height', 'data'}: host arrays through the HIP path.
+
+    images[i] = {'width', 'height', 'data': HxWx4 uint8 (RGBA, straight alpha), 'orientation'?: 1..8, 'fileSize'?}
+    or simply an HxWx4 uint8 array; or a list of Bitmaps (decode_bitmaps / upload_bitmap: nothing is uploaded).  A view with padded
+    rows is read where it is (_host_rows).  Returns None when images is empty (the reference returns early).
+    """
+    o = _merge(opts)
+    _no_preview(o, "stitch", "the caller gets the pixels; stitch_png / stitch_files keep the canvas in HBM and can add its preview")
+    return _stitch(images, direction, o, device, "rgba8")
 
 
 _BATCH_REFUSED = ("devices", "split", "pngLevel", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
@@ -428,27 +482,27 @@ def _batch_requests(reqs, why):
             raise ValueError("request %d: direction must be 'vertical' or 'horizontal'" % k)
         if any(isinstance(im, Bitmap) for im in images):
             raise TypeError("request %d: Bitmaps do not apply to a batch (host images only)" % k)
-        m = len(images)
-        descs = _descs(images)
-        ptrs, pitches = (C.c_void_p * max(1, m))(), (C.c_size_t * max(1, m))()
-        arrays = []
-        for i, im in enumerate(images):
-            a = im["data"] if isinstance(im, dict) else im
-            if a is None:
-                raise L.StitchError(-6, "request %d: 图片%d解码异常" % (k, i))
-            a = np.asarray(a)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
-                raise TypeError("request %d, image %d: expected an HxWx4 uint8 RGBA array" % (k, i))
-            if a.strides[2] != 1 or a.strides[1] != 4:
-                a = np.ascontiguousarray(a)
-            arrays.append(a)
-            ptrs[i] = a.ctypes.data
-            pitches[i] = a.strides[0]
-        lim = _limits(o)
+        descs, ptrs, pitches, arrays = _host_sources(images, "request %d" % k)
+        d, m, gap, lim, f = _plan_args(direction, o)
         keep.append((descs, ptrs, pitches, arrays, lim))
-        creqs[k] = L.StitchRequest(descs, ptrs, pitches, m, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                   C.pointer(lim), _filter_of(o), 0)
+        creqs[k] = L.StitchRequest(descs, ptrs, pitches, len(images), d, m, gap, C.pointer(lim), f, 0)
     return creqs, keep
+
+
+def _run_batch(fn, ctx, creqs, extra=(), key=None):
+    """One batched stitch call and its result list: per request None (no images), the canvas (key None: HxWx4 uint8) or
+    {'width', 'height', key: file bytes}"""
+    n = len(creqs)
+    plans, outs, lens = (L.Plan * n)(), (C.POINTER(C.c_uint8) * n)(), (C.c_int64 * n)()
+    L.check(fn(ctx, creqs, n, *extra, plans, outs, *([] if key is None else [lens])))
+    res = []
+    for k in range(n):
+        if not outs[k]:
+            res.append(None)
+            continue
+        w, h = _plan_size(L.IST_OK, plans[k])
+        res.append(_take_pixels(outs[k], w, h) if key is None else {"width": w, "height": h, key: _take_png(outs[k], C.c_int64(lens[k]))})
+    return res
 
 
 def stitch_batch(requests, device=0):
@@ -460,21 +514,8 @@ def stitch_batch(requests, device=0):
     reqs = list(requests)
     if not reqs:
         return []
-    n = len(reqs)
     creqs, keep = _batch_requests(reqs, "one GPU, pixels out")
-    ctx = _ctx(device)
-    plans = (L.Plan * n)()
-    outs = (C.POINTER(C.c_uint8) * n)()
-    L.check(L.lib.ist_stitch_rgba8_batch(ctx, creqs, n, plans, outs))
-    res = []
-    for k in range(n):
-        if not outs[k]:
-            res.append(None)
-            continue
-        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
-        L.lib.ist_plan_free(C.byref(plans[k]))
-        res.append(_take_pixels(outs[k], w, h))
-    return res
+    return _run_batch(L.lib.ist_stitch_rgba8_batch, _ctx(device), creqs)
 
 
 def stitch_png_batch(requests, device=0, level=None):
@@ -486,22 +527,8 @@ def stitch_png_batch(requests, device=0, level=None):
     reqs = list(requests)
     if not reqs:
         return []
-    n = len(reqs)
     creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=")
-    ctx = _ctx_png(device, level)
-    plans = (L.Plan * n)()
-    outs = (C.POINTER(C.c_uint8) * n)()
-    lens = (C.c_int64 * n)()
-    L.check(L.lib.ist_stitch_png_batch(ctx, creqs, n, plans, outs, lens))
-    res = []
-    for k in range(n):
-        if not outs[k]:
-            res.append(None)
-            continue
-        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
-        L.lib.ist_plan_free(C.byref(plans[k]))
-        res.append({"width": w, "height": h, "png": _take_png(outs[k], C.c_int64(lens[k]))})
-    return res
+    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level), creqs, key="png")
 
 
 def launch_jobs(jobs, srcs, outs, stream=None):
@@ -543,14 +570,7 @@ def render_ops(canvas_w, canvas_h, ops, n_ops, descs, srcs, filter="bilinear", c
     """A recorded Canvas op list -> HxWx4 uint8 (ist_render_rgba8: what the Canvas-2D shim's export / getImageData binds).
     srcs: list of HxWx4 uint8 arrays (None for images no op draws)."""
     n = len(srcs)
-    keep, ptrs, pitches = [], (C.c_void_p * max(1, n))(), (C.c_size_t * max(1, n))()
-    for i, a in enumerate(srcs):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a)
-        keep.append(a)
-        ptrs[i] = a.ctypes.data
-        pitches[i] = a.strides[0]
+    descs, ptrs, pitches, keep = _host_sources(srcs, descs=descs, holes=True)
     reg, rw, rh = None, int(canvas_w), int(canvas_h)
     if region is not None:
         x, y, w, h = [int(v) for v in region]
@@ -573,8 +593,9 @@ def stitch_via_c_abi(images, direction, opts=None, device=0):
 
 
 def _take_png(out, n, copy=True):
-    """The library's malloc'ed PNG as Python bytes (one copy), or with copy=False as a memoryview over the C buffer
-    itself, released through ist_free when the view is garbage collected (a 146 MB file costs ~20 ms to copy)."""
+    """The library's malloc'ed file - a PNG or, despite the name, a JPEG - as Python bytes (one copy), or with copy=False as a
+    memoryview over the C buffer itself, released through ist_free when the view is garbage collected (a 146 MB file costs ~20 ms
+    to copy)."""
     if copy:
         try:
             return C.string_at(out, n.value)
@@ -668,21 +689,14 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     # the library reads the files itself (ist_stitch_paths_png: one parked worker per file, into blocks its context keeps).
     # (Reading nine 12 MP JPEGs into Python bytes cost ~1 ms of the call; opening and mapping them from Python still 0.2 ms.)
     cpaths = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
-    cplan = L.Plan()
-    lim = _limits(o)
-    out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
+    cplan, out, ln = L.Plan(), C.POINTER(C.c_uint8)(), C.c_int64(0)
     pv = _preview_arg(o)
-    if pv is None:
-        rc = L.check(L.lib.ist_stitch_paths_png(_ctx_png(device, o["pngLevel"]), cpaths, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                                C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
-    else:
-        rc = L.check(L.lib.ist_stitch_paths_png_preview(_ctx_png(device, o["pngLevel"]), cpaths, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                                        float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
-                                                        C.byref(pv)))
-    if rc == L.IST_NOTHING_TO_DO:
+    fn = L.lib.ist_stitch_paths_png if pv is None else L.lib.ist_stitch_paths_png_preview
+    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
+                                 *([] if pv is None else [C.byref(pv)]))), cplan)
+    if size is None:
         return None
-    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
-    L.lib.ist_plan_free(C.byref(cplan))
+    w, h = size
     res = {"width": w, "height": h, "png": _take_png(out, ln, copy)}
     if pv is not None:
         res["preview"] = _take_preview(pv)
@@ -695,71 +709,30 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
 def encode_png(pixels, device=0, level=None):
     """Lossless PNG (colour type 6) of an HxWx4 uint8 array, encoded on the GPU (export step, utils/canvas.js:205-242).
     level 0: stored deflate blocks; 1: Paeth + run-length + Huffman (ist_ctx_set_png_level)."""
-    a = np.asarray(pixels)
-    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
-        raise TypeError("expected an HxWx4 uint8 RGBA array")
-    if a.strides[2] != 1 or a.strides[1] != 4 or a.strides[0] < 4 * a.shape[1]:
-        a = np.ascontiguousarray(a).copy()
+    a, ptr, pitch = _host_rows(_rgba(pixels))
     out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level), a.ctypes.data, a.strides[0], a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
+    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
     return _take_png(out, n)
 
 
 def stitch_png(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the reference's export: returns {'width','height','png': bytes}.  The
-    canvas stays on the device; only the PNG crosses PCIe.  images may be a list of Bitmaps, as for stitch()."""
-    o = _merge(opts)
-    n = len(images)
-    if n == 0:
-        return None
-    if _is_bitmap_request(images, o):
-        return _stitch_bitmaps(images, n, direction, o, device, True)
-    descs = _descs(images)
-    keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-    for i, im in enumerate(images):
-        a = im["data"] if isinstance(im, dict) else im
-        if a is None:
-            raise L.StitchError(-6, "图片%d解码异常" % i)
-        a = np.ascontiguousarray(a)
-        keep.append(a)
-        ptrs[i] = a.ctypes.data
-        pitches[i] = a.strides[0]
-    cplan = L.Plan()
-    lim = _limits(o)
-    out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    pv = _preview_arg(o)
-    if pv is None:
-        rc = L.check(L.lib.ist_stitch_png(_ctx_png(device, o["pngLevel"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                          float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
-    else:
-        rc = L.check(L.lib.ist_stitch_png_preview(_ctx_png(device, o["pngLevel"]), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                                  float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
-                                                  C.byref(pv)))
-    if rc == L.IST_NOTHING_TO_DO:
-        return None
-    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
-    L.lib.ist_plan_free(C.byref(cplan))
-    res = {"width": w, "height": h, "png": _take_png(out, ln)}
-    if pv is not None:
-        res["preview"] = _take_preview(pv)
-    return res
+    canvas stays on the device; only the PNG crosses PCIe.  images are marshalled as stitch() marshals them (padded views are read
+    where they are); they may be a list of Bitmaps."""
+    return _stitch(images, direction, _merge(opts), device, "png")
 
 
 def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
     """PNG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor) into a CUDA uint8 tensor; returns (tensor, length)."""
     import torch
+    _check_canvas(canvas, "encode_png_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
-    cap = int(L.lib.ist_png_bound(w, h))
-    if out is None:
-        out = torch.empty(cap + 16, dtype=torch.uint8, device=canvas.device)
-    base = out.data_ptr()
-    aligned = (base + 15) & ~15
+    out, off, dst, cap = _file_out(out, L.lib.ist_png_bound(w, h), canvas.device)
     st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
     n = C.c_int64(0)
     dev = canvas.device.index if device is None else device
     L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
-                                        C.c_void_p(aligned), out.numel() - (aligned - base), C.byref(n), C.c_void_p(st.cuda_stream)))
-    off = aligned - base
+                                        C.c_void_p(dst), cap, C.byref(n), C.c_void_p(st.cuda_stream)))
     return out[off:off + n.value], n.value
 
 
@@ -781,13 +754,12 @@ def encode_jpeg(pixels, quality=90, subsampling="420", device=0):
     """Baseline JFIF file (bytes) of an HxWx4 uint8 array, encoded on the GPU (ist_jpeg_encode_rgba8; the export with fileType 'jpg',
     utils/canvas.js:205-221).  Alpha is not read.  The file is pinned byte for byte by include/imagestitch.h."""
     q, ss = _jpeg_args(quality, subsampling)
-    a = np.asarray(pixels)
-    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+    a = _rgba(pixels)
+    if a.shape[0] < 1 or a.shape[1] < 1:
         raise TypeError("expected an HxWx4 uint8 RGBA array")
-    if a.strides[2] != 1 or a.strides[1] != 4 or a.strides[0] < 4 * a.shape[1] or a.strides[0] % 4:
-        a = np.ascontiguousarray(a).copy()
+    a, ptr, pitch = _host_rows(a, align=4)
     out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    L.check(L.lib.ist_jpeg_encode_rgba8(_ctx(device), a.ctypes.data, a.strides[0], a.shape[1], a.shape[0], q, ss, C.byref(out), C.byref(n)))
+    L.check(L.lib.ist_jpeg_encode_rgba8(_ctx(device), ptr, pitch, a.shape[1], a.shape[0], q, ss, C.byref(out), C.byref(n)))
     return _take_png(out, n)
 
 
@@ -796,60 +768,28 @@ def encode_jpeg_device(canvas, quality=90, subsampling="420", out=None, stream=N
     tensor (ist_jpeg_encode_device); returns (tensor, length) like encode_png_device.  out: optional, ist_jpeg_bound + 16 bytes."""
     import torch
     q, ss = _jpeg_args(quality, subsampling)
-    if canvas.dtype != torch.uint8 or canvas.dim() != 3 or canvas.shape[2] != 4 or canvas.stride(2) != 1 or canvas.stride(1) != 4:
-        raise TypeError("expected an HxWx4 uint8 CUDA tensor with dense pixels")
+    _check_canvas(canvas, "encode_jpeg_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
-    cap = int(L.lib.ist_jpeg_bound(w, h, ss))
-    if out is None:
-        out = torch.empty(max(cap, 0) + 16, dtype=torch.uint8, device=canvas.device)      # (no bound: the call names what is wrong with the size)
-    base = out.data_ptr()
-    aligned = (base + 15) & ~15
+    out, off, dst, cap = _file_out(out, L.lib.ist_jpeg_bound(w, h, ss), canvas.device)
     st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
     n = C.c_int64(0)
     L.check(L.lib.ist_jpeg_encode_device(_ctx(canvas.device.index or 0), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h, q, ss,
-                                         C.c_void_p(aligned), out.numel() - (aligned - base), C.byref(n), C.c_void_p(st.cuda_stream)))
-    off = aligned - base
+                                         C.c_void_p(dst), cap, C.byref(n), C.c_void_p(st.cuda_stream)))
     return out[off:off + n.value], n.value
 
 
 def stitch_jpeg(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the JPEG export: returns {'width', 'height', 'jpeg': bytes} (ist_stitch_jpeg /
     ist_stitch_bitmaps_jpeg).  opts['quality'] (1..100, default 90) and opts['subsampling'] ('420' default, or '444') choose the file;
-    the canvas stays on the device and only the file crosses PCIe.  images may be a list of Bitmaps, as for stitch_png()."""
+    the canvas stays on the device and only the file crosses PCIe.  images as for stitch_png(): marshalled as stitch() marshals them,
+    or a list of Bitmaps."""
     opts = dict(opts or {})
-    q, ss = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
+    jpeg = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
     o = _merge(opts)
     _no_preview(o, "stitch_jpeg", "previews are built beside the PNG export")
     if o.get("devices") is not None:
         raise TypeError("stitch_jpeg: devices= does not apply (the JPEG export runs on one GPU)")
-    n = len(images)
-    if n == 0:
-        return None
-    cplan = L.Plan()
-    lim = _limits(o)
-    out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    if _is_bitmap_request(images, o):
-        bms = (C.c_void_p * n)(*[None if b is None else b.handle() for b in images])
-        rc = L.check(L.lib.ist_stitch_bitmaps_jpeg(_ctx(device), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                                   C.byref(lim), _filter_of(o), q, ss, C.byref(cplan), C.byref(out), C.byref(ln)))
-    else:
-        descs = _descs(images)
-        keep, ptrs, pitches = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-        for i, im in enumerate(images):
-            a = im["data"] if isinstance(im, dict) else im
-            if a is None:
-                raise L.StitchError(-6, "图片%d解码异常" % i)
-            a = np.ascontiguousarray(a)
-            keep.append(a)
-            ptrs[i] = a.ctypes.data
-            pitches[i] = a.strides[0]
-        rc = L.check(L.lib.ist_stitch_jpeg(_ctx(device), descs, ptrs, pitches, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                           float(o["gap"] or 0), C.byref(lim), _filter_of(o), q, ss, C.byref(cplan), C.byref(out), C.byref(ln)))
-    if rc == L.IST_NOTHING_TO_DO:
-        return None
-    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
-    L.lib.ist_plan_free(C.byref(cplan))
-    return {"width": w, "height": h, "jpeg": _take_png(out, ln)}
+    return _stitch(images, direction, o, device, "jpeg", jpeg)
 
 
 def _per_file(value, n, name):
@@ -866,7 +806,6 @@ def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None,
     one transform, one entropy and one gather launch per round (ist_jpeg_encode_batch_device).  quality and subsampling: one value for
     all files or a sequence of length n.  outs: optional CUDA uint8 tensors of at least ist_jpeg_bound + 16 bytes each.  Returns
     [(tensor, length)], each file byte for byte what encode_jpeg_device gives for that canvas."""
-    import torch
     canvases = list(canvases)
     n = len(canvases)
     if n == 0:
@@ -877,29 +816,9 @@ def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None,
             args.append(_jpeg_args(q, s))
         except (TypeError, ValueError) as e:
             raise type(e)("file %d: %s" % (k, e)) from None
-    for k, c in enumerate(canvases):
-        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 4 or c.stride(2) != 1 or c.stride(1) != 4:
-            raise TypeError("canvas %d: expected an HxWx4 uint8 CUDA tensor with dense pixels" % k)
-    dev = canvases[0].device
-    if outs is None:      # (no bound: the call names what is wrong with the size)
-        outs = [torch.empty(max(int(L.lib.ist_jpeg_bound(int(c.shape[1]), int(c.shape[0]), a[1])), 0) + 16, dtype=torch.uint8, device=dev)
-                for c, a in zip(canvases, args)]
-    if len(outs) != n:
-        raise ValueError("encode_jpeg_batch_device: canvases and outs must have the same length")
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    src, pitch = (C.c_void_p * n)(), (C.c_size_t * n)()
-    w, h = (C.c_int64 * n)(), (C.c_int64 * n)()
     qs, ss = (C.c_int * n)(*[a[0] for a in args]), (C.c_int * n)(*[a[1] for a in args])
-    dst, cap, ln = (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
-    offs = []
-    for k, (c, o) in enumerate(zip(canvases, outs)):
-        src[k], pitch[k], h[k], w[k] = c.data_ptr(), c.stride(0), int(c.shape[0]), int(c.shape[1])
-        base = o.data_ptr()
-        aligned = (base + 15) & ~15
-        offs.append(aligned - base)
-        dst[k], cap[k] = aligned, o.numel() - (aligned - base)
-    L.check(L.lib.ist_jpeg_encode_batch_device(_ctx(dev.index or 0), src, pitch, w, h, qs, ss, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
-    return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(zip(outs, offs))]
+    return _encode_batch_device(L.lib.ist_jpeg_encode_batch_device, _ctx, "encode_jpeg_batch_device", canvases,
+                                lambda k, w, h: L.lib.ist_jpeg_bound(w, h, ss[k]), outs, stream, (qs, ss))
 
 
 def stitch_jpeg_batch(requests, device=0):
@@ -922,50 +841,79 @@ def stitch_jpeg_batch(requests, device=0):
             raise type(e)("request %d: %s" % (k, e)) from None
         plain.append((r[0], r[1], opts))
     creqs, keep = _batch_requests(plain, "one GPU, JPEG files out")
-    ctx = _ctx(device)
-    plans = (L.Plan * n)()
-    outs = (C.POINTER(C.c_uint8) * n)()
-    lens = (C.c_int64 * n)()
-    L.check(L.lib.ist_stitch_jpeg_batch(ctx, creqs, n, qs, ss, plans, outs, lens))
-    res = []
-    for k in range(n):
-        if not outs[k]:
-            res.append(None)
-            continue
-        w, h = int(plans[k].canvas_w), int(plans[k].canvas_h)
-        L.lib.ist_plan_free(C.byref(plans[k]))
-        res.append({"width": w, "height": h, "jpeg": _take_png(outs[k], C.c_int64(lens[k]))})
-    return res
+    return _run_batch(L.lib.ist_stitch_jpeg_batch, _ctx(device), creqs, (qs, ss), "jpeg")
 
 
 def encode_png_batch_device(canvases, outs=None, stream=None, level=None):
     """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
     launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns
     [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas."""
+    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level), "encode_png_batch_device", list(canvases),
+                                lambda k, w, h: L.lib.ist_png_bound(w, h), outs, stream)
+
+
+def _encode_batch_device(fn, ctx_of, who, canvases, bound, outs, stream, extra=()):
+    """encode_png_batch_device / encode_jpeg_batch_device behind their own arguments: canvases under _check_canvases, one _file_out per
+    file (bound(k, w, h): the size to allocate where the caller brought none), one call, [(tensor, length)]"""
     import torch
     n = len(canvases)
     if n == 0:
         return []
-    dev = canvases[0].device
-    if outs is None:
-        outs = [torch.empty(int(L.lib.ist_png_bound(int(c.shape[1]), int(c.shape[0]))) + 16, dtype=torch.uint8, device=dev) for c in canvases]
-    if len(outs) != n:
-        raise ValueError("encode_png_batch_device: canvases and outs must have the same length")
+    if outs is not None and len(outs) != n:
+        raise ValueError(who + ": canvases and outs must have the same length")
+    dev = _check_canvases(canvases)
     st = stream if stream is not None else torch.cuda.current_stream(dev)
     src, pitch = (C.c_void_p * n)(), (C.c_size_t * n)()
     w, h = (C.c_int64 * n)(), (C.c_int64 * n)()
     dst, cap, ln = (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
-    offs = []
-    for k, (c, o) in enumerate(zip(canvases, outs)):
-        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 4 or c.stride(2) != 1 or c.stride(1) != 4:
-            raise TypeError("canvas %d: expected an HxWx4 uint8 CUDA tensor with dense pixels" % k)
+    files = []
+    for k, c in enumerate(canvases):
         src[k], pitch[k], h[k], w[k] = c.data_ptr(), c.stride(0), int(c.shape[0]), int(c.shape[1])
-        base = o.data_ptr()
-        aligned = (base + 15) & ~15
-        offs.append(aligned - base)
-        dst[k], cap[k] = aligned, o.numel() - (aligned - base)
-    L.check(L.lib.ist_png_encode_batch_device(_ctx_png(dev.index or 0, level), src, pitch, w, h, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
-    return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(zip(outs, offs))]
+        o, off, dst[k], cap[k] = _file_out(None if outs is None else outs[k], bound(k, w[k], h[k]), dev, "file %d: " % k)
+        files.append((o, off))
+    L.check(fn(ctx_of(dev.index or 0), src, pitch, w, h, *extra, n, dst, cap, ln, C.c_void_p(st.cuda_stream)))
+    return [(o[off:off + ln[k]], int(ln[k])) for k, (o, off) in enumerate(files)]
+
+
+def _canvas_form(t, who=""):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 4 or t.stride(2) != 1 or t.stride(1) != 4:
+        raise TypeError(who + "expected an HxWx4 uint8 CUDA tensor with dense pixels")
+
+
+def _check_canvas(t, who="", device=None):
+    """The rule of a canvas in HBM: a torch tensor, HxWx4 uint8 with dense pixels (any row pitch), on a GPU - on `device` where it
+    shares a call with others.  Handing the library anything else as a device pointer is a GPU fault, not an error code."""
+    _canvas_form(t, who)
+    if not t.is_cuda:
+        raise TypeError(who + "canvases must be CUDA tensors (host pixels: upload_bitmap, or the entry points that take arrays)")
+    if device is not None and t.device != device:
+        raise TypeError(who + "the canvases of one call must live on one device (%s, not %s)" % (device, t.device))
+
+
+def _check_canvases(tensors, who=""):
+    """_check_canvas for the canvases of one call, which share a device: the one returned.  The form of every canvas is judged
+    before where any of them lives, so 'canvas k: ...' names a malformed one whatever the others are."""
+    for k, t in enumerate(tensors):
+        _canvas_form(t, "%scanvas %d: " % (who, k))
+    for k, t in enumerate(tensors):
+        _check_canvas(t, "%scanvas %d: " % (who, k), tensors[0].device)
+    return tensors[0].device
+
+
+def _file_out(out, cap, device, who=""):
+    """Where an encoder writes its file -> (tensor, offset, pointer, capacity): `out`, a dense 1-D uint8 CUDA tensor on the canvas's
+    device, or cap + 16 fresh bytes; the file starts at the first 16-byte boundary.  (Whether the capacity is enough is the library's
+    to say: it names the bound.)"""
+    import torch
+    device = torch.device(device)
+    if out is None:
+        out = torch.empty(max(int(cap), 0) + 16, dtype=torch.uint8, device=device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or out.device != device:
+        raise TypeError(who + "out must be a dense 1-D uint8 CUDA tensor on the canvas's device")
+    base = out.data_ptr()
+    aligned = (base + 15) & ~15
+    return out, aligned - base, aligned, out.numel() - (aligned - base)
 
 
 class Bitmap:
@@ -1048,37 +996,6 @@ def _bitmap_descs(images):
     return arr
 
 
-def _stitch_bitmaps(images, n, direction, o, device, png):
-    """stitch / stitch_png of a request made of Bitmaps (ist_stitch_bitmaps_rgba8 / _png)"""
-    bms = (C.c_void_p * n)(*[None if b is None else b.handle() for b in images])
-    cplan = L.Plan()
-    lim = _limits(o)
-    pv = _preview_arg(o) if png else None
-    if png and pv is not None:
-        out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-        rc = L.check(L.lib.ist_stitch_bitmaps_png_preview(_ctx_png(device, o["pngLevel"]), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                                          float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln),
-                                                          C.byref(pv)))
-    elif png:
-        out, ln = C.POINTER(C.c_uint8)(), C.c_int64(0)
-        rc = L.check(L.lib.ist_stitch_bitmaps_png(_ctx_png(device, o["pngLevel"]), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]],
-                                                  float(o["gap"] or 0), C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out), C.byref(ln)))
-    else:
-        out = C.POINTER(C.c_uint8)()
-        rc = L.check(L.lib.ist_stitch_bitmaps_rgba8(_ctx(device), bms, n, _DIRECTIONS[direction], _MODES[o["mode"]], float(o["gap"] or 0),
-                                                    C.byref(lim), _filter_of(o), C.byref(cplan), C.byref(out)))
-    if rc == L.IST_NOTHING_TO_DO:
-        return None
-    w, h = int(cplan.canvas_w), int(cplan.canvas_h)
-    L.lib.ist_plan_free(C.byref(cplan))
-    if png:
-        res = {"width": w, "height": h, "png": _take_png(out, ln)}
-        if pv is not None:
-            res["preview"] = _take_preview(pv)
-        return res
-    return {"width": w, "height": h, "data": _take_pixels(out, w, h)}
-
-
 def decode_bitmaps(files, device=0):
     """Image files (bytes, or paths that are read here) -> [Bitmap], decoded straight into HBM by the decoder of stitch_files (baseline
     JPEG: Huffman decoding + reconstruction on the GPU).  Each bitmap's desc is what stitch_files plans with: size, EXIF orientation,
@@ -1104,22 +1021,13 @@ def decode_bitmaps(files, device=0):
 def upload_bitmap(image, device=0):
     """A host image -> Bitmap: an HxWx4 uint8 RGBA array, or a dict as stitch() takes ({'width', 'height', 'data', 'orientation'?,
     'fileSize'?, 'opaque'?}); the desc is kept as given."""
-    ctx = _ctx(device)
-    desc = _descs([image])
     a = image.get("data") if isinstance(image, dict) else image
     if a is None:
         raise L.StitchError(-6, "图片0解码异常")
-    a = np.asarray(a)
-    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
-        raise TypeError("expected an HxWx4 uint8 RGBA array")
-    if a.strides[2] != 1 or a.strides[1] != 4:
-        a = np.ascontiguousarray(a)
-    bw, bh = desc[0].bmp_width or desc[0].width, desc[0].bmp_height or desc[0].height
-    if bw < 1 or bh < 1:
-        raise L.StitchError(-6, "图片0解码异常")
-    if a.shape[0] < bh or a.shape[1] < bw:
-        raise ValueError("the pixels (%dx%d) are smaller than the bitmap (%dx%d)" % (a.shape[1], a.shape[0], bw, bh))
-    h = L.lib.ist_bitmap_upload(ctx, desc, a.ctypes.data, a.strides[0])
+    a = _rgba(a)
+    desc = _descs([image])
+    a, ptr, pitch = _host_rows(a, desc[0])
+    h = L.lib.ist_bitmap_upload(_ctx(device), desc, ptr, pitch)
     if not h:                                    # (NULL: the message says which rule failed)
         msg = L.last_error()
         raise L.StitchError(-6 if msg.startswith("图片") else -1 if msg.startswith("src_pitch") else -8 if msg.startswith("out of device memory") else -9, msg)

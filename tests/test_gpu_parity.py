@@ -196,6 +196,83 @@ def test_strided_host_buffers():
     assert np.array_equal(got["data"], ref)
 
 
+def _input_forms(px):
+    """the same pixels as the host may hold them: dense, a view with padded rows (out of a 40 pixel wide buffer), rows in reverse order
+    in memory (a negative row stride)"""
+    pitched = []
+    for k, a in enumerate(px):
+        big = U.rand_image(90 + k, a.shape[0], 40)
+        big[:, 3:3 + a.shape[1]] = a
+        pitched.append(big[:, 3:3 + a.shape[1]])
+    reversed_rows = [np.flipud(a[::-1].copy()) for a in px]
+    assert pitched[0].strides[0] == 160 and reversed_rows[0].strides[0] == -96
+    return {"dense": px, "pitched": pitched, "reversed": reversed_rows}
+
+
+def test_every_host_entry_point_reads_every_input_form_alike():
+    """One marshal for host pixels (stitch.py _host_sources): stitch, stitch_png, stitch_jpeg and their batches return byte for byte
+    the same for dense arrays, padded views and reversed rows; the dense form is pinned against the oracle, the known strip, the
+    decoded PNG and the JPEG reference."""
+    from tests import jpeg_encode_reference as JR
+    px = [U.rand_image(80, 16, 24), U.rand_image(81, 9, 24)]
+    opts = {"gap": 3}
+    out, _ = _check(px, "vertical", opts)
+    strip = np.full((28, 24, 4), 255, np.uint8)
+    strip[:16], strip[19:] = px
+    assert np.array_equal(out, strip)                                     # equal widths: the plan is the identity
+    calls = {"stitch": lambda im: ist.stitch(im, "vertical", opts)["data"].tobytes(),
+             "stitch_png": lambda im: ist.stitch_png(im, "vertical", opts)["png"],
+             "stitch_jpeg": lambda im: ist.stitch_jpeg(im, "vertical", opts)["jpeg"],
+             "stitch_batch": lambda im: b"".join(a.tobytes() for a in ist.stitch_batch([(im, "vertical", opts), (im[::-1], "vertical", opts)])),
+             "stitch_png_batch": lambda im: b"".join(r["png"] for r in ist.stitch_png_batch([(im, "vertical", opts), (im[::-1], "vertical", opts)])),
+             "stitch_jpeg_batch": lambda im: b"".join(r["jpeg"] for r in ist.stitch_jpeg_batch([(im, "vertical", opts), (im[::-1], "vertical", opts)]))}
+    forms = _input_forms(px)
+    swapped = np.concatenate([strip[19:], strip[16:19], strip[:16]])
+    for name, call in calls.items():
+        want = call(forms["dense"])
+        for form in ("pitched", "reversed"):
+            assert call(forms[form]) == want, (name, form)
+            assert call(U.hip_images(forms[form])) == want, (name, form, "dicts")
+    assert calls["stitch"](px) == strip.tobytes() and calls["stitch_batch"](px) == strip.tobytes() + swapped.tobytes()
+    png, jpeg = calls["stitch_png"](px), calls["stitch_jpeg"](px)
+    assert np.array_equal(ist.decode_png(png), strip) and jpeg == JR.encode(strip, 90, "420")
+    pngs = ist.stitch_png_batch([(px, "vertical", opts), (px[::-1], "vertical", opts)])
+    assert np.array_equal(ist.decode_png(pngs[0]["png"]), strip) and np.array_equal(ist.decode_png(pngs[1]["png"]), swapped)
+    assert calls["stitch_jpeg_batch"](px) == jpeg + JR.encode(swapped, 90, "420")
+
+
+def _batch_encoders():
+    return ((ist.encode_png_batch_device, lambda c: int(L.lib.ist_png_bound(c.shape[1], c.shape[0])), L.lib.ist_debug_png_batch_launches),
+            (ist.encode_jpeg_batch_device, lambda c: int(L.lib.ist_jpeg_bound(c.shape[1], c.shape[0], 1)), L.lib.ist_debug_jpeg_batch_launches))
+
+
+def test_batch_encoders_write_the_same_files_into_the_callers_tensors():
+    """outs given (at an odd address: the file starts at the next 16-byte boundary) against outs allocated by the call"""
+    import torch
+    canvases = [torch.from_numpy(U.rand_image(82 + k, h, 24)).cuda() for k, h in enumerate((28, 9))]
+    for encode, bound, _ in _batch_encoders():
+        want = [bytes(t[:n].cpu().numpy()) for t, n in encode(canvases)]
+        outs = [torch.empty(bound(c) + 33, dtype=torch.uint8, device="cuda")[1:] for c in canvases]
+        got = encode(canvases, outs=outs)
+        assert [bytes(t[:n].cpu().numpy()) for t, n in got] == want
+        for (t, n), o in zip(got, outs):
+            assert t.data_ptr() % 16 == 0 and o.data_ptr() <= t.data_ptr() < o.data_ptr() + 16
+        for bad in (outs[0].cpu(), outs[0].view(-1, 1), outs[0][::2]):
+            with pytest.raises(TypeError, match="out must be"):
+                encode(canvases, outs=[bad, outs[1]])
+
+
+@pytest.mark.skipif(L.lib.ist_device_count() < 2, reason="needs two GPUs: a canvas on a second device")
+def test_batch_encoders_refuse_a_canvas_on_another_device_before_any_launch():
+    import torch
+    canvases = [torch.from_numpy(U.rand_image(84, 9, 24)).to("cuda:%d" % d) for d in (0, 1)]
+    for encode, _, launches in _batch_encoders():
+        before = launches()
+        with pytest.raises(TypeError, match="canvas 1: .*one device"):
+            encode(canvases)
+        assert launches() == before
+
+
 def _device_stitch(px, direction, opts, orientations=None):
     import torch
     st = ist.Stitcher(0)
