@@ -251,6 +251,8 @@ SYMBOLS = [
     ("ist_stitch_jpeg_batch", C.c_int, [C.c_void_p, C.POINTER(StitchRequest), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(Plan),
                                         C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
     ("ist_debug_jpeg_batch_launches", C.c_int64, []),
+    ("ist_jpeg_optimal_table", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int)]),
+    ("ist_debug_jpeg_histogram_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -26,6 +26,7 @@ struct ist_ctx {
   void* scratch_png = nullptr; size_t scratch_png_bytes = 0;   // compressing PNG encoder: one slot per 16 KiB chunk + its tables
   void* scratch_file = nullptr; size_t scratch_file_bytes = 0; // device image of a PNG or JPEG file on its way to the host
   void* scratch_jpg = nullptr; size_t scratch_jpg_bytes = 0;   // JPEG encoder: tables, one slab of coefficients, one slot per restart interval
+  void* scratch_jpg_counts = nullptr; size_t scratch_jpg_counts_bytes = 0;   // ... IST_JPEG_OPTIMIZE: 544 64-bit symbol counters per optimised file of a call
   void* scratch_arena = nullptr; size_t scratch_arena_bytes = 0; // file pipeline: bitmaps + JPEG planes + canvas + PNG of one call
   // file pipeline (ist_stitch_files_png / ist_decode_files_device): one stream + event + Huffman scratch per image, so that
   // the images' decode chains (upload -> Huffman passes -> reconstruction) overlap each other and the export of the bands

@@ -18,7 +18,16 @@ constexpr size_t kJpegEncBudget = 256u << 20;     // coefficient scratch + inter
 constexpr int kJpegBlockBits = 22 + 63 * 26;      // most bits of one block: DC code 11 + 11 magnitude bits, 63 x (AC code 16 + 10)
 constexpr int kJpegBlockBytes = 2 * kJpegBlockBits / 8;      // ... as bytes when every byte is 0xFF and stuffed: 415
 static_assert(kJpegBlockBits == 1660 && kJpegBlockBytes * 8 == 2 * kJpegBlockBits, "slot bound");
-constexpr int kJpegHeaderBytes = 629;             // SOI ... SOS of every file the encoder writes
+constexpr int kJpegHeaderBytes = 629;             // SOI ... SOS of every file with the Annex K tables; the most with optimised ones
+// IST_JPEG_OPTIMIZE: a DC code may be 16 bits long: 27 + 63 x 26 bits, 417 bytes
+constexpr int kJpegBlockBitsWide = 27 + 63 * 26;
+constexpr int kJpegBlockBytesWide = (2 * kJpegBlockBitsWide + 7) / 8;
+static_assert(kJpegBlockBitsWide == 1665 && kJpegBlockBytesWide == 417, "slot bound of optimised files");
+constexpr int kJpegCounters = 2 * (16 + 256);     // symbol counts of one file: per slot, 16 DC sizes then 256 AC symbols (int64 each)
+
+inline bool jpeg_ss_known(int subsampling) { const int b = subsampling & ~IST_JPEG_OPTIMIZE; return b == IST_JPEG_444 || b == IST_JPEG_420; }
+inline bool jpeg_ss_420(int subsampling) { return (subsampling & ~IST_JPEG_OPTIMIZE) == IST_JPEG_420; }
+inline bool jpeg_ss_optimize(int subsampling) { return (subsampling & IST_JPEG_OPTIMIZE) != 0; }
 
 // what the kernels read beside the canvas: one block per quality
 struct JpegTables {
@@ -32,22 +41,30 @@ struct JpegGeometry {
   int mcu_w, mcu_h, bpm;         // MCU size in pixels, blocks per MCU
   int64_t mcus_x, mcus_y, row_blocks;
   int64_t slot;                  // bytes of one interval's slot (a multiple of 16)
+  int block_bytes;               // most bytes of one block: 415, or 417 with optimised tables
   int64_t row_cost() const { return row_blocks * 128 + slot; }      // scratch of one MCU row: its coefficients and its slot
 };
 inline JpegGeometry jpeg_geometry(int64_t w, int64_t h, int subsampling) {
   JpegGeometry g;
-  g.mcu_w = g.mcu_h = subsampling == IST_JPEG_420 ? 16 : 8;
-  g.bpm = subsampling == IST_JPEG_420 ? 6 : 3;
+  g.mcu_w = g.mcu_h = jpeg_ss_420(subsampling) ? 16 : 8;
+  g.bpm = jpeg_ss_420(subsampling) ? 6 : 3;
   g.mcus_x = (w + g.mcu_w - 1) / g.mcu_w; g.mcus_y = (h + g.mcu_h - 1) / g.mcu_h;
   g.row_blocks = g.mcus_x * g.bpm;
-  g.slot = (g.row_blocks * kJpegBlockBytes + 2 + 15) & ~15ll;      // + the byte the pad can add, and one so that no real length reaches it
+  g.block_bytes = jpeg_ss_optimize(subsampling) ? kJpegBlockBytesWide : kJpegBlockBytes;
+  g.slot = (g.row_blocks * g.block_bytes + 2 + 15) & ~15ll;      // + the byte the pad can add, and one so that no real length reaches it
   return g;
 }
 
 void jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);       // libjpeg: jpeg_quality_scaling, jpeg_add_quant_table
 void jpeg_enc_tables(int quality, JpegTables* T);                                // everything the kernels read for one quality
-// SOI, APP0, DQT x 2, DHT x 4, DRI, SOF0, SOS
-std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart);
+// BITS / HUFFVAL of the four tables of a file, in DHT order: DC0, DC1, AC0, AC1
+struct JpegHuffSpec { uint8_t bits[4][16]; uint8_t vals[4][256]; int n[4]; };
+// the optimal table of 256 counts (>= 0), the rule of include/imagestitch.h; returns the number of values
+int jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[256]);
+// an optimised file's tables from its counts (kJpegCounters of them): the codes into T->dc / T->ac (0: no code), the specs into H
+void jpeg_enc_tables_optimal(int quality, const int64_t* counts, JpegTables* T, JpegHuffSpec* H);
+// SOI, APP0, DQT x 2, DHT x 4 (H, or Annex K when NULL), DRI, SOF0, SOS
+std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart, const JpegHuffSpec* H = nullptr);
 
 // ---- batches (ist_jpeg_encode_batch_device, ist_stitch_jpeg_batch) ----
 // one file of a batch: a canvas in device memory -> its JPEG in a 16-byte aligned device buffer of `cap` >= ist_jpeg_bound bytes
@@ -66,7 +83,8 @@ struct JpegPiece {
   int32_t w, h, is420, mcus_x, mcus_y, row_blocks, bpm, head_len;
   int32_t mcu_row0, mcu_rows;    // the piece's MCU rows (= restart intervals) of the file
   int32_t wg0, iv0;              // its first workgroup of the transform grid, its first interval of the entropy and gather grids
-  int32_t gx, reserved;          // transform workgroups per MCU row
+  int32_t gx;                    // transform workgroups per MCU row
+  int32_t hist;                  // IST_JPEG_OPTIMIZE: the file's block of counters (kJpegCounters each); -1: Annex K tables, not counted
 };
 static_assert(sizeof(JpegPiece) == 128, "piece record");
 
@@ -78,14 +96,19 @@ std::vector<ist_jpeg_piece> jpeg_batch_pieces(const JpegBatchFile* files, int n,
 struct JpegRound {
   int p0 = 0, p1 = 0;
   std::vector<int> quality;                      // the distinct qualities of the round's files, in order of first use
+  std::vector<int> opt_files;                    // the round's files with IST_JPEG_OPTIMIZE, in order: their own tables follow the qualities'
   size_t at_tables = 0, at_heads = 0, at_pieces = 0, table_bytes = 0;
   size_t at_slots = 0, scratch_bytes = 0;        // the scratch: every piece's coefficients, then every piece's slots
   int64_t wgs = 0, ivs = 0;
 };
 JpegRound jpeg_round_plan(const JpegBatchFile* files, const ist_jpeg_piece* pieces, int p0, int p1);
 // the host image of the round's table block.  dev / scratch: where the block and the scratch are on the device (never read here)
+// An optimised file as a batch sees it: its block of counters and, once they are counted, its tables and its header.
+struct JpegOptFile { int hist = -1; bool built = false; JpegTables T; std::vector<uint8_t> head; };
+// opt: per file of the batch (NULL: no file is optimised).  A file whose tables are not built yet gets the Annex K codes beside its
+// quantisers (what the transform reads) and a header of the most bytes.
 void jpeg_round_pack(const JpegRound& R, const JpegBatchFile* files, const ist_jpeg_piece* pieces, uint8_t* host, const uint8_t* dev,
-                     uint8_t* scratch);
+                     uint8_t* scratch, const JpegOptFile* opt = nullptr);
 
 int64_t jpeg_batch_budget();                     // kJpegEncBudget, or IST_TUNING=1 IST_JPEG_ENC_BUDGET=<bytes> (read once)
 int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k);      // the rules of ist_jpeg_encode_device for file k (message: "<what> k: ...")

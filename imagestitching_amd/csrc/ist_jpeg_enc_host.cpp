@@ -71,6 +71,75 @@ void jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {
   }
 }
 
+// T.81 K.2 with the tie rules of include/imagestitch.h ("the table of one histogram").  257 leaves at most, so the quadratic
+// search for the two smallest nodes is some 10^5 steps; a tree may be as deep as its leaves are many (no limit but the arrays').
+int jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[256]) {
+  constexpr int kLeaves = 257;
+  typedef unsigned __int128 Weight;               // (257 counts of up to 2^63 - 1)
+  Weight weight[kLeaves];
+  int id[kLeaves], owner[kLeaves], size[kLeaves];  // a node lives at the index of the leaf that founded it; owner: a leaf's node
+  bool alive[kLeaves];
+  int nodes = 0;
+  for (int s = 0; s < kLeaves; ++s) {
+    const int64_t f = s < 256 ? freq[s] : 1;
+    alive[s] = f > 0; weight[s] = static_cast<Weight>(f > 0 ? f : 0); id[s] = s; owner[s] = s; size[s] = 0;
+    nodes += alive[s];
+  }
+  std::memset(bits, 0, 16);
+  if (nodes == 1) return 0;                        // nothing but the reserved symbol
+  for (; nodes > 1; --nodes) {
+    int a = -1, b = -1;                            // the smallest and the second smallest by (weight, id)
+    for (int k = 0; k < kLeaves; ++k) {
+      if (!alive[k]) continue;
+      auto less = [&](int x, int y) { return weight[x] < weight[y] || (weight[x] == weight[y] && id[x] < id[y]); };
+      if (a < 0 || less(k, a)) { b = a; a = k; }
+      else if (b < 0 || less(k, b)) b = k;
+    }
+    for (int s = 0; s < kLeaves; ++s)
+      if (owner[s] == a || owner[s] == b) { ++size[s]; owner[s] = a; }
+    weight[a] += weight[b]; id[a] = std::min(id[a], id[b]); alive[b] = false;
+  }
+  int count[kLeaves + 1] = {0};                    // BITS before the limit: a size is at most 256
+  for (int s = 0; s < kLeaves; ++s)
+    if (owner[s] == owner[256]) ++count[size[s]];  // (every leaf that took part ends in the one node left)
+  int i = kLeaves - 1;
+  for (; i > 16; --i)                              // figure K.3
+    while (count[i] > 0) {
+      int j = i - 2;
+      while (j > 0 && count[j] == 0) --j;
+      count[i] -= 2; count[i - 1] += 1; count[j + 1] += 2; count[j] -= 1;
+    }
+  while (count[i] == 0) --i;
+  --count[i];                                      // the reserved code point
+  for (int l = 1; l <= 16; ++l) bits[l - 1] = static_cast<uint8_t>(count[l]);
+  int n = 0;
+  for (int l = 1; l < kLeaves; ++l)                // by (size before the limit, symbol)
+    for (int s = 0; s < 256; ++s)
+      if (freq[s] > 0 && size[s] == l) vals[n++] = static_cast<uint8_t>(s);
+  return n;
+}
+
+void jpeg_enc_tables_optimal(int quality, const int64_t* counts, JpegTables* T, JpegHuffSpec* H) {
+  jpeg_enc_tables(quality, T);
+  std::memset(T->dc, 0, sizeof T->dc); std::memset(T->ac, 0, sizeof T->ac);
+  std::memset(H, 0, sizeof *H);
+  for (int tc = 0; tc < 2; ++tc)
+    for (int s = 0; s < 2; ++s) {
+      int64_t freq[256] = {0};
+      const int64_t* c = counts + s * (16 + 256) + (tc ? 16 : 0);
+      for (int k = 0; k < (tc ? 256 : 16); ++k) freq[k] = c[k];
+      const int t = tc * 2 + s;
+      H->n[t] = jpeg_optimal_table(freq, H->bits[t], H->vals[t]);
+      if (tc) {
+        huff_codes(H->bits[t], H->vals[t], T->ac[s]);
+      } else {
+        uint32_t codes[256] = {0};                 // (counts of sizes above 11 cannot be: the difference is clamped; no code leaves T->dc)
+        huff_codes(H->bits[t], H->vals[t], codes);
+        std::memcpy(T->dc[s], codes, sizeof T->dc[s]);
+      }
+    }
+}
+
 void jpeg_enc_tables(int quality, JpegTables* T) {
   std::memset(T, 0, sizeof *T);
   for (int s = 0; s < 2; ++s) { huff_codes(kDcBits[s], kDcVals, T->dc[s]); huff_codes(kAcBits[s], kAcVals[s], T->ac[s]); }
@@ -78,7 +147,7 @@ void jpeg_enc_tables(int quality, JpegTables* T) {
   for (int k = 0; k < 64; ++k) T->zz_of[kZigzag[k]] = static_cast<uint8_t>(k);
 }
 
-std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart) {
+std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart, const JpegHuffSpec* H) {
   std::vector<uint8_t> o{0xFF, 0xD8};
   seg(&o, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
   for (int s = 0; s < 2; ++s) {
@@ -89,13 +158,19 @@ std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, cons
   for (int tc = 0; tc < 2; ++tc)
     for (int s = 0; s < 2; ++s) {
       std::vector<uint8_t> b{static_cast<uint8_t>(tc * 16 + s)};
-      const uint8_t* bits = tc ? kAcBits[s] : kDcBits[s];
-      b.insert(b.end(), bits, bits + 16);
-      if (tc) b.insert(b.end(), kAcVals[s], kAcVals[s] + 162); else b.insert(b.end(), kDcVals, kDcVals + 12);
+      if (H) {
+        const int t = tc * 2 + s;
+        b.insert(b.end(), H->bits[t], H->bits[t] + 16);
+        b.insert(b.end(), H->vals[t], H->vals[t] + H->n[t]);
+      } else {
+        const uint8_t* bits = tc ? kAcBits[s] : kDcBits[s];
+        b.insert(b.end(), bits, bits + 16);
+        if (tc) b.insert(b.end(), kAcVals[s], kAcVals[s] + 162); else b.insert(b.end(), kDcVals, kDcVals + 12);
+      }
       seg(&o, 0xC4, b);
     }
   seg(&o, 0xDD, {static_cast<uint8_t>(restart >> 8), static_cast<uint8_t>(restart & 255)});
-  const uint8_t hv = subsampling == IST_JPEG_420 ? 0x22 : 0x11;
+  const uint8_t hv = jpeg_ss_420(subsampling) ? 0x22 : 0x11;
   seg(&o, 0xC0, {8, static_cast<uint8_t>(h >> 8), static_cast<uint8_t>(h & 255), static_cast<uint8_t>(w >> 8), static_cast<uint8_t>(w & 255), 3,
                  1, hv, 0, 2, 0x11, 1, 3, 0x11, 1});
   seg(&o, 0xDA, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
@@ -130,16 +205,20 @@ JpegRound jpeg_round_plan(const JpegBatchFile* files, const ist_jpeg_piece* piec
   for (int p = p0; p < p1; ++p) {
     const JpegBatchFile& f = files[pieces[p].file];
     const JpegGeometry g = jpeg_geometry(f.w, f.h, f.subsampling);
-    if (std::find(R.quality.begin(), R.quality.end(), f.quality) == R.quality.end()) R.quality.push_back(f.quality);
+    if (jpeg_ss_optimize(f.subsampling)) {
+      if (R.opt_files.empty() || R.opt_files.back() != pieces[p].file) R.opt_files.push_back(pieces[p].file);
+    } else if (std::find(R.quality.begin(), R.quality.end(), f.quality) == R.quality.end()) {
+      R.quality.push_back(f.quality);
+    }
     if (pieces[p].mcu_row0 == 0) heads += (kJpegHeaderBytes + 15) & ~size_t(15);
-    const int64_t gx = f.subsampling == IST_JPEG_420 ? g.mcus_x : (g.mcus_x + 3) / 4;
+    const int64_t gx = jpeg_ss_420(f.subsampling) ? g.mcus_x : (g.mcus_x + 3) / 4;
     R.wgs += gx * pieces[p].mcu_rows;
     R.ivs += pieces[p].mcu_rows;
     coef += static_cast<size_t>(pieces[p].mcu_rows * g.row_blocks) * 128;
     slots += static_cast<size_t>(pieces[p].mcu_rows * g.slot);
   }
   R.at_tables = 0;
-  R.at_heads = round256(R.quality.size() * sizeof(JpegTables));
+  R.at_heads = round256((R.quality.size() + R.opt_files.size()) * sizeof(JpegTables));
   R.at_pieces = round256(R.at_heads + heads);
   R.table_bytes = R.at_pieces + static_cast<size_t>(p1 - p0) * sizeof(JpegPiece);
   R.at_slots = round256(coef);
@@ -148,17 +227,23 @@ JpegRound jpeg_round_plan(const JpegBatchFile* files, const ist_jpeg_piece* piec
 }
 
 void jpeg_round_pack(const JpegRound& R, const JpegBatchFile* files, const ist_jpeg_piece* pieces, uint8_t* host, const uint8_t* dev,
-                     uint8_t* scratch) {
+                     uint8_t* scratch, const JpegOptFile* opt) {
   std::memset(host, 0, R.table_bytes);
   JpegTables* tabs = reinterpret_cast<JpegTables*>(host + R.at_tables);
   for (size_t q = 0; q < R.quality.size(); ++q) jpeg_enc_tables(R.quality[q], &tabs[q]);
+  for (size_t k = 0; k < R.opt_files.size(); ++k) {
+    const int f = R.opt_files[k];
+    if (opt && opt[f].built) tabs[R.quality.size() + k] = opt[f].T; else jpeg_enc_tables(files[f].quality, &tabs[R.quality.size() + k]);
+  }
   JpegPiece* rec = reinterpret_cast<JpegPiece*>(host + R.at_pieces);
   size_t head_at = R.at_heads, coef_at = 0, slot_at = R.at_slots;
   int64_t wg = 0, iv = 0;
   for (int p = R.p0; p < R.p1; ++p) {
     const JpegBatchFile& f = files[pieces[p].file];
     const JpegGeometry g = jpeg_geometry(f.w, f.h, f.subsampling);
-    const size_t q = static_cast<size_t>(std::find(R.quality.begin(), R.quality.end(), f.quality) - R.quality.begin());
+    const bool optimize = jpeg_ss_optimize(f.subsampling);
+    const size_t q = optimize ? R.quality.size() + static_cast<size_t>(std::find(R.opt_files.begin(), R.opt_files.end(), pieces[p].file) - R.opt_files.begin())
+                              : static_cast<size_t>(std::find(R.quality.begin(), R.quality.end(), f.quality) - R.quality.begin());
     JpegPiece& P = rec[p - R.p0];
     P.canvas = static_cast<const uint8_t*>(f.canvas); P.pitch = f.pitch;
     P.tab = reinterpret_cast<const JpegTables*>(dev + R.at_tables) + q;
@@ -166,14 +251,16 @@ void jpeg_round_pack(const JpegRound& R, const JpegBatchFile* files, const ist_j
     P.slots = scratch + slot_at;
     P.out = f.out; P.out_cap = f.cap;
     P.slot = g.slot;
-    P.w = static_cast<int32_t>(f.w); P.h = static_cast<int32_t>(f.h); P.is420 = f.subsampling == IST_JPEG_420;
+    P.w = static_cast<int32_t>(f.w); P.h = static_cast<int32_t>(f.h); P.is420 = jpeg_ss_420(f.subsampling);
     P.mcus_x = static_cast<int32_t>(g.mcus_x); P.mcus_y = static_cast<int32_t>(g.mcus_y);
     P.row_blocks = static_cast<int32_t>(g.row_blocks); P.bpm = g.bpm;
     P.mcu_row0 = pieces[p].mcu_row0; P.mcu_rows = pieces[p].mcu_rows;
     P.wg0 = static_cast<int32_t>(wg); P.iv0 = static_cast<int32_t>(iv);
     P.gx = static_cast<int32_t>(P.is420 ? g.mcus_x : (g.mcus_x + 3) / 4);
+    P.hist = optimize && opt ? opt[pieces[p].file].hist : -1;
     if (P.mcu_row0 == 0) {
-      const std::vector<uint8_t> head = jpeg_enc_header(f.w, f.h, f.subsampling, tabs[q], g.mcus_x);
+      const bool own = optimize && opt && opt[pieces[p].file].built;
+      const std::vector<uint8_t> head = own ? opt[pieces[p].file].head : jpeg_enc_header(f.w, f.h, f.subsampling, tabs[q], g.mcus_x);
       std::memcpy(host + head_at, head.data(), head.size());
       P.head = dev + head_at; P.head_len = static_cast<int32_t>(head.size());
       head_at += (kJpegHeaderBytes + 15) & ~size_t(15);
@@ -200,7 +287,7 @@ int64_t ist_jpeg_batch_layout(const int64_t* w, const int64_t* h, const int* sub
   if (n < 1 || !w || !h || !subsampling || budget_bytes < 0 || cap < 0) return -1;
   std::vector<JpegBatchFile> files(static_cast<size_t>(n));
   for (int k = 0; k < n; ++k) {
-    if (w[k] < 1 || h[k] < 1 || w[k] > 65535 || h[k] > 65535 || (subsampling[k] != IST_JPEG_444 && subsampling[k] != IST_JPEG_420)) return -1;
+    if (w[k] < 1 || h[k] < 1 || w[k] > 65535 || h[k] > 65535 || !jpeg_ss_known(subsampling[k])) return -1;
     files[static_cast<size_t>(k)] = JpegBatchFile{nullptr, 0, w[k], h[k], 0, subsampling[k], nullptr, 0, 0};
   }
   const std::vector<ist_jpeg_piece> pieces = jpeg_batch_pieces(files.data(), n, budget_bytes > 0 ? budget_bytes : jpeg_batch_budget());

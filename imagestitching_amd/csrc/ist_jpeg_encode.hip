@@ -16,6 +16,14 @@
 //     from the coefficient scratch (the previous block of its component), so nothing but that byte is carried;
 //   * the host prefix-sums the interval lengths and a gather kernel copies every interval behind its RSTn marker.
 // The canvas is encoded in slabs of MCU rows so that coefficients + slots stay within kBudget of the context's scratch.
+//
+// IST_JPEG_OPTIMIZE (the file's own Huffman tables) puts "whole file counted" in front of "first interval coded":
+//   * histogram kernel: one wave per block, lane k = coefficient k; the ballot of the non-zero AC lanes is the block's run structure,
+//     so every lane finds its own run/size symbol; counts go into a histogram per wave in LDS and from there, once per workgroup and
+//     non-zero bin, into the file's 544 64-bit counters (integer adds commute: the counts do not depend on the order);
+//   * the host builds the four tables from the counts (jpeg_enc_tables_optimal), writes the header from them and sends both up;
+//   * the entropy kernel's wide instantiation (a DC code may be 16 bits: 1665 bits per block) codes with them.  It reports a symbol
+//     without a code as an interval of length 0, which the host refuses.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,13 +41,13 @@ namespace ist {
 
 namespace {
 
-std::atomic<int64_t> g_launches{0};
+std::atomic<int64_t> g_launches{0}, g_hist_launches{0};
 
 // (the tables, the header and the geometry are host code without a device: ist_jpeg_enc.h)
 constexpr size_t kBudget = kJpegEncBudget;
 constexpr int kBlockBits = kJpegBlockBits;
 constexpr int kBatch = 256;                // blocks per batch of the entropy kernel = its threads
-constexpr int kImgWords = (7 + kBatch * kBlockBits + 31) / 32 + 2;      // LDS bit image of a batch behind a carried partial byte
+constexpr int img_words(int block_bits) { return (7 + kBatch * block_bits + 31) / 32 + 2; }      // LDS bit image of a batch behind a carried partial byte
 typedef JpegGeometry Geometry;
 inline Geometry geometry(int64_t w, int64_t h, int subsampling) { return jpeg_geometry(w, h, subsampling); }
 
@@ -153,12 +161,14 @@ struct BitWriter {
 __device__ __forceinline__ int size_of(int a) { return a ? 32 - __clz(a) : 0; }      // a >= 0
 
 // one block: its bit count (EMIT false) or its codes into the image.  c: 64 coefficients, zig-zag order, two per word
-template <bool EMIT>
-__device__ __forceinline__ int code_block(const uint32_t (&c)[32], int diff, const uint32_t* dc, const uint32_t* ac, BitWriter* bw) {
+// GUARD (counting pass only): *bad becomes non-zero when the block holds a symbol that the tables have no code for
+template <bool EMIT, bool GUARD = false>
+__device__ __forceinline__ int code_block(const uint32_t (&c)[32], int diff, const uint32_t* dc, const uint32_t* ac, BitWriter* bw, int* bad = nullptr) {
   int bits;
   {
     const int s = size_of(diff < 0 ? -diff : diff);
     const uint32_t h = dc[s];
+    if (GUARD) *bad |= h == 0u;
     bits = static_cast<int>(h >> 16) + s;
     if (EMIT) bw->put(((h & 0xFFFFu) << s) | (static_cast<uint32_t>(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1u)), bits);
   }
@@ -169,6 +179,7 @@ __device__ __forceinline__ int code_block(const uint32_t (&c)[32], int diff, con
     if (v == 0) { ++run; continue; }
     while (run >= 16) {                                   // ZRL
       const uint32_t z = ac[0xF0];
+      if (GUARD) *bad |= z == 0u;
       bits += static_cast<int>(z >> 16);
       if (EMIT) bw->put(z & 0xFFFFu, static_cast<int>(z >> 16));
       run -= 16;
@@ -176,6 +187,7 @@ __device__ __forceinline__ int code_block(const uint32_t (&c)[32], int diff, con
     v = max(-1023, min(1023, v));                          // (the transform clamps already: this keeps the slot bound whatever the scratch holds)
     const int s = size_of(v < 0 ? -v : v);
     const uint32_t h = ac[run * 16 + s];
+    if (GUARD) *bad |= h == 0u;
     const int l = static_cast<int>(h >> 16) + s;
     bits += l;
     if (EMIT) bw->put(((h & 0xFFFFu) << s) | (static_cast<uint32_t>(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), l);
@@ -183,6 +195,7 @@ __device__ __forceinline__ int code_block(const uint32_t (&c)[32], int diff, con
   }
   if (run > 0) {                                           // EOB
     const uint32_t e = ac[0];
+    if (GUARD) *bad |= e == 0u;
     bits += static_cast<int>(e >> 16);
     if (EMIT) bw->put(e & 0xFFFFu, static_cast<int>(e >> 16));
   }
@@ -205,9 +218,12 @@ __device__ __forceinline__ int block_scan(int v, uint32_t* ws, int* total) {
   return base + incl - v;
 }
 
-// one workgroup of the entropy coder: interval iv of A (its coefficients, its slot, its length)
+// one workgroup of the entropy coder: interval iv of A (its coefficients, its slot, its length).  BLOCK_BITS: the most bits of a
+// block under the tables in use (it sizes the image); GUARD: the tables may lack a code (optimised tables): such an interval gets
+// length 0
+template <int BLOCK_BITS, bool GUARD>
 __device__ __forceinline__ void jpeg_entropy(const EntropyArgs& A, const int iv) {
-  __shared__ uint32_t img[kImgWords];
+  __shared__ uint32_t img[img_words(BLOCK_BITS)];
   __shared__ uint32_t sDc[32], sAc[512];
   __shared__ uint32_t ws_bits[4], ws_ff[4];
   const int tid = threadIdx.x;
@@ -218,6 +234,7 @@ __device__ __forceinline__ void jpeg_entropy(const EntropyArgs& A, const int iv)
   uint8_t* slot = A.slots + static_cast<int64_t>(iv) * A.slot;
   int64_t out_pos = 0;
   int carry_bits = 0; uint32_t carry_val = 0;            // the partial last byte of the batches so far (its bits at the top of a byte)
+  int bad = 0;
   for (int base = 0; base < A.row_blocks; base += kBatch) {
     const int j = base + tid;
     const bool on = j < A.row_blocks;
@@ -239,7 +256,7 @@ __device__ __forceinline__ void jpeg_entropy(const EntropyArgs& A, const int iv)
       for (int q = 0; q < 32; ++q) c[q] = 0;
     }
     const uint32_t* dc = sDc + comp * 16; const uint32_t* ac = sAc + comp * 256;
-    const int mybits = on ? code_block<false>(c, diff, dc, ac, nullptr) : 0;
+    const int mybits = on ? code_block<false, GUARD>(c, diff, dc, ac, nullptr, &bad) : 0;
     int sum;
     const int start = carry_bits + block_scan(mybits, ws_bits, &sum);      // (its barrier: the last batch's image has been read by everybody)
     const int total = carry_bits + sum;
@@ -271,10 +288,82 @@ __device__ __forceinline__ void jpeg_entropy(const EntropyArgs& A, const int iv)
     carry_bits = (total + pad) & 7;
     carry_val = carry_bits ? (img_byte(img, nb) & (0xFF00u >> carry_bits) & 255u) : 0u;
   }
-  if (tid == 0) A.len[iv] = static_cast<uint32_t>(min(out_pos, A.slot));
+  if (GUARD) bad = __syncthreads_or(bad);
+  if (tid == 0) A.len[iv] = bad ? 0u : static_cast<uint32_t>(min(out_pos, A.slot));
 }
 
-__global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs A) { jpeg_entropy(A, static_cast<int>(blockIdx.x)); }
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_kernel(const EntropyArgs A) { jpeg_entropy<kBlockBits, false>(A, static_cast<int>(blockIdx.x)); }
+// ... for files with optimised tables
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_wide_kernel(const EntropyArgs A) {
+  jpeg_entropy<kJpegBlockBitsWide, true>(A, static_cast<int>(blockIdx.x));
+}
+
+// ---- symbol counts (IST_JPEG_OPTIMIZE) ---------------------------------------------------------------------------------
+struct HistArgs {
+  const int16_t* coef;           // the intervals of a slab, as the entropy kernel reads them
+  int64_t* counters;             // the file's kJpegCounters counters
+  int32_t row_blocks, bpm;
+};
+constexpr int kHistBlocks = 128;         // blocks of one workgroup: part `part` of an interval is its blocks [part * kHistBlocks, ...)
+constexpr int kHistStep = 8;             // blocks a wave has in flight: its loads are issued before the first of them is counted
+
+// one block by one wave: v = coefficient `lane` (zig-zag order), pred = the DC predictor (read by lane 0 only); h: the wave's own
+// counters of the block's component (16 DC sizes, then 256 AC symbols)
+__device__ __forceinline__ void count_block(int v, int pred, int lane, uint32_t* h) {
+  const bool nz = lane > 0 && v != 0;
+  const unsigned long long m = __ballot(nz);                 // bit k: AC coefficient k is not zero
+  if (nz) {
+    const unsigned long long lower = m & ((1ull << lane) - 1ull);
+    const int prev = lower ? 63 - __clzll(lower) : 0;        // the non-zero coefficient before this one (0: the DC)
+    const int run = lane - prev - 1;
+    const int s = size_of(min(v < 0 ? -v : v, 1023));
+    atomicAdd(&h[16 + (((run & 15) << 4) | s)], 1u);
+    if (run >= 16) atomicAdd(&h[16 + 0xF0], static_cast<uint32_t>(run >> 4));      // ZRLs
+  }
+  if (lane == 0) {
+    const int d = max(-2047, min(2047, v - pred));
+    atomicAdd(&h[size_of(d < 0 ? -d : d)], 1u);
+    if (!(m >> 63)) atomicAdd(&h[16], 1u);                   // EOB: the block ends in zeros
+  }
+}
+
+// one workgroup of the histogram: part `part` of interval iv.  A wave takes kHistStep blocks (contiguous bytes) per step.
+__device__ __forceinline__ void jpeg_histogram(const HistArgs& A, const int iv, const int part) {
+  __shared__ uint32_t h[4][kJpegCounters];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b0 = part * kHistBlocks, b1 = min(A.row_blocks, b0 + kHistBlocks);
+  if (b0 >= A.row_blocks) return;                            // (uniform)
+  for (int i = tid; i < 4 * kJpegCounters; i += 256) (&h[0][0])[i] = 0;
+  __syncthreads();
+  const int16_t* coef = A.coef + static_cast<int64_t>(iv) * A.row_blocks * 64;
+  for (int j0 = b0 + kHistStep * wave; j0 < b1; j0 += 4 * kHistStep) {
+    int v[kHistStep], pred[kHistStep], comp[kHistStep];
+#pragma unroll
+    for (int u = 0; u < kHistStep; ++u) {
+      const int j = j0 + u;
+      v[u] = 0; pred[u] = 0; comp[u] = 0;
+      if (j < b1) {                                           // (uniform)
+        v[u] = coef[static_cast<int64_t>(j) * 64 + lane];
+        const int pos = j % A.bpm;                            // as jpeg_entropy: the previous block of the same component
+        comp[u] = A.bpm == 6 ? (pos >= 4) : (pos != 0);
+        const int back = A.bpm == 3 ? 3 : (pos == 0 ? 3 : (pos < 4 ? 1 : 6));
+        if (j >= back) pred[u] = coef[static_cast<int64_t>(j - back) * 64];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kHistStep; ++u)
+      if (j0 + u < b1) count_block(v[u], pred[u], lane, h[wave] + comp[u] * (16 + 256));
+  }
+  __syncthreads();
+  for (int i = tid; i < kJpegCounters; i += 256) {
+    const uint32_t n = h[0][i] + h[1][i] + h[2][i] + h[3][i];      // (at most kHistBlocks x 64 symbols)
+    if (n) atomicAdd(reinterpret_cast<unsigned long long*>(A.counters) + i, static_cast<unsigned long long>(n));
+  }
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_histogram_kernel(const HistArgs A) {
+  jpeg_histogram(A, static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y));
+}
 
 // ---- gather ------------------------------------------------------------------------------------------------------------
 struct GatherArgs { const uint8_t* slots; int64_t slot; uint8_t* out; const int64_t* dst; const uint32_t* len; int32_t first; };
@@ -325,13 +414,34 @@ __global__ __launch_bounds__(256) void ist_jpeg_transform_batch_kernel(const Jpe
   jpeg_transform(A, local - by * P->gx, by);
 }
 
-__global__ __launch_bounds__(256) void ist_jpeg_entropy_batch_kernel(const JpegBatchArgs B) {
-  const int iv = static_cast<int>(blockIdx.x);
+// the entropy twin's body: interval iv of the round, coded by jpeg_entropy<BLOCK_BITS, GUARD> on its piece's arguments
+template <int BLOCK_BITS, bool GUARD>
+__device__ __forceinline__ void jpeg_entropy_batch(const JpegBatchArgs& B, const int iv) {
   ConstPiece* P = (ConstPiece*)B.pieces + jpeg_piece_of<false>((ConstPiece*)B.pieces, B.n, iv);
   EntropyArgs A;
   A.coef = P->coef; A.tab = P->tab; A.slots = P->slots; A.len = B.len + P->iv0;
   A.row_blocks = P->row_blocks; A.bpm = P->bpm; A.slot = P->slot;
-  jpeg_entropy(A, iv - P->iv0);
+  jpeg_entropy<BLOCK_BITS, GUARD>(A, iv - P->iv0);
+}
+
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_batch_kernel(const JpegBatchArgs B) {
+  jpeg_entropy_batch<kBlockBits, false>(B, static_cast<int>(blockIdx.x));
+}
+// ... for a round that holds a file with optimised tables (bits are bits, and the slot sizes are the pieces' own)
+__global__ __launch_bounds__(256) void ist_jpeg_entropy_wide_batch_kernel(const JpegBatchArgs B) {
+  jpeg_entropy_batch<kJpegBlockBitsWide, true>(B, static_cast<int>(blockIdx.x));
+}
+
+// the histogram of the round's optimised pieces: interval blockIdx.x of the round, part blockIdx.y of it
+struct JpegHistBatchArgs { const JpegPiece* pieces; int32_t n; int64_t* counters; };
+__global__ __launch_bounds__(256) void ist_jpeg_histogram_batch_kernel(const JpegHistBatchArgs B) {
+  const int iv = static_cast<int>(blockIdx.x);
+  ConstPiece* P = (ConstPiece*)B.pieces + jpeg_piece_of<false>((ConstPiece*)B.pieces, B.n, iv);
+  if (P->hist < 0) return;                                   // (uniform: a file with the Annex K tables)
+  HistArgs A;
+  A.coef = P->coef; A.counters = B.counters + static_cast<int64_t>(P->hist) * kJpegCounters;
+  A.row_blocks = P->row_blocks; A.bpm = P->bpm;
+  jpeg_histogram(A, iv - P->iv0, static_cast<int>(blockIdx.y));
 }
 
 // ... and the gather writes what no interval holds: the file's header (by the workgroup of the file's interval 0) and its EOI marker
@@ -366,7 +476,7 @@ int64_t slab_rows_of(const Geometry& g) {
 // every rule of ist_jpeg_encode_device but the context's
 int check_args(const char* who, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling) {
   if (quality < 1 || quality > 100) return fail(IST_E_INVALID, std::string(who) + ": quality must be 1..100");
-  if (subsampling != IST_JPEG_444 && subsampling != IST_JPEG_420) return fail(IST_E_INVALID, std::string(who) + ": unknown subsampling");
+  if (!jpeg_ss_known(subsampling)) return fail(IST_E_INVALID, std::string(who) + ": unknown subsampling");
   if (!canvas || w < 1 || h < 1) return fail(IST_E_INVALID, std::string(who) + ": bad argument");
   if (w > 65535) return fail(IST_E_UNSUPPORTED, std::string(who) + ": a JPEG is at most 65535 wide (width " + std::to_string(w) + ")");
   if (h > 65535) return fail(IST_E_UNSUPPORTED, std::string(who) + ": a JPEG is at most 65535 high (height " + std::to_string(h) + ")");
@@ -387,48 +497,85 @@ int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k) {
 }
 
 // The file of a canvas in device memory into `out` (device, out_cap bytes).  The arguments have been checked.  Synchronises `stream`.
+// IST_JPEG_OPTIMIZE: every slab is transformed and counted first (no host wait between slabs: stream order protects the scratch), one
+// synchronisation brings the counts down, the tables and the header go up, and the slab loop runs with the wide entropy kernel.  A
+// file of one slab keeps its coefficients; a file of N > 1 slabs is transformed twice.
 int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, void* out,
                        int64_t out_cap, int64_t* out_len, hipStream_t stream) {
   const Geometry g = geometry(w, h, subsampling);
+  const bool optimize = jpeg_ss_optimize(subsampling);
   const int64_t slab_rows = slab_rows_of(g);
   JpegTables T;
   jpeg_enc_tables(quality, &T);
-  const std::vector<uint8_t> head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x);
+  std::vector<uint8_t> head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x);      // (optimised: no header is longer than this one)
   if (static_cast<int64_t>(head.size()) + 2 > out_cap) return fail(IST_E_INVALID, "JPEG output buffer too small (see ist_jpeg_bound)");
 
   const size_t o_coef = round256(sizeof T), coef_bytes = round256(static_cast<size_t>(slab_rows * g.row_blocks) * 128);
   const size_t o_slots = o_coef + coef_bytes, total = o_slots + static_cast<size_t>(slab_rows * g.slot);
   int rc = grow_device(&ctx->scratch_jpg, &ctx->scratch_jpg_bytes, total);
   if (rc) return rc;
+  constexpr size_t kCountBytes = static_cast<size_t>(kJpegCounters) * 8;
+  if (optimize) { rc = grow_device(&ctx->scratch_jpg_counts, &ctx->scratch_jpg_counts_bytes, kCountBytes); if (rc) return rc; }
   uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg);
-  // per interval of a slab: its length (written by the kernel) and its place in the file (read by the gather), in pinned memory
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(static_cast<size_t>(slab_rows) * 16))};
+  // per interval of a slab: its length (written by the kernel) and its place in the file (read by the gather), in pinned memory;
+  // behind them the counts of an optimised file
+  const size_t o_counts = static_cast<size_t>(slab_rows) * 16;
+  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(o_counts + (optimize ? kCountBytes : 0)))};
   if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
   int64_t* const dst = reinterpret_cast<int64_t*>(res.p);
   uint32_t* const len = reinterpret_cast<uint32_t*>(res.p + 8 * static_cast<size_t>(slab_rows));
   // (every way out below leaves the stream idle: kernels in flight write `res` and read the tables)
   struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
   IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  XformArgs X;
+  X.canvas = static_cast<const uint8_t*>(canvas); X.pitch = pitch; X.w = static_cast<int32_t>(w); X.h = static_cast<int32_t>(h);
+  X.tab = reinterpret_cast<const JpegTables*>(scratch); X.coef = reinterpret_cast<int16_t*>(scratch + o_coef);
+  X.mcus_x = static_cast<int32_t>(g.mcus_x); X.mcu_row0 = 0; X.is420 = jpeg_ss_420(subsampling);
+  const unsigned gx = static_cast<unsigned>(X.is420 ? g.mcus_x : (g.mcus_x + 3) / 4);
+  auto transform = [&](int64_t r0, int64_t rows) -> int {
+    X.mcu_row0 = static_cast<int32_t>(r0);
+    hipLaunchKernelGGL(ist_jpeg_transform_kernel, dim3(gx, static_cast<unsigned>(rows)), dim3(256), 0, stream, X);
+    IST_HIP(hipGetLastError());
+    g_launches.fetch_add(1, std::memory_order_relaxed);
+    return IST_OK;
+  };
+  bool kept = false;                                 // the (only) slab's coefficients are in the scratch already
+  if (optimize) {
+    int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts);
+    IST_HIP(hipMemsetAsync(counters, 0, kCountBytes, stream));
+    const HistArgs H{X.coef, counters, static_cast<int32_t>(g.row_blocks), g.bpm};
+    const unsigned parts = static_cast<unsigned>((g.row_blocks + kHistBlocks - 1) / kHistBlocks);
+    for (int64_t r0 = 0; r0 < g.mcus_y; r0 += slab_rows) {
+      const int64_t rows = std::min(slab_rows, g.mcus_y - r0);
+      rc = transform(r0, rows);
+      if (rc) return rc;
+      hipLaunchKernelGGL(ist_jpeg_histogram_kernel, dim3(static_cast<unsigned>(rows), parts), dim3(256), 0, stream, H);
+      IST_HIP(hipGetLastError());
+      g_hist_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    IST_HIP(hipMemcpyAsync(res.p + o_counts, counters, kCountBytes, hipMemcpyDeviceToHost, stream));
+    IST_HIP(hipStreamSynchronize(stream));
+    JpegHuffSpec spec;
+    jpeg_enc_tables_optimal(quality, reinterpret_cast<const int64_t*>(res.p + o_counts), &T, &spec);
+    head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x, &spec);
+    IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
+    kept = g.mcus_y <= slab_rows;
+  }
   IST_HIP(hipMemcpyAsync(out, head.data(), head.size(), hipMemcpyHostToDevice, stream));
   int64_t pos = static_cast<int64_t>(head.size());
   for (int64_t r0 = 0; r0 < g.mcus_y; r0 += slab_rows) {
     const int64_t rows = std::min(slab_rows, g.mcus_y - r0);
-    XformArgs X;
-    X.canvas = static_cast<const uint8_t*>(canvas); X.pitch = pitch; X.w = static_cast<int32_t>(w); X.h = static_cast<int32_t>(h);
-    X.tab = reinterpret_cast<const JpegTables*>(scratch); X.coef = reinterpret_cast<int16_t*>(scratch + o_coef);
-    X.mcus_x = static_cast<int32_t>(g.mcus_x); X.mcu_row0 = static_cast<int32_t>(r0); X.is420 = subsampling == IST_JPEG_420;
-    const unsigned gx = static_cast<unsigned>(X.is420 ? g.mcus_x : (g.mcus_x + 3) / 4);
-    hipLaunchKernelGGL(ist_jpeg_transform_kernel, dim3(gx, static_cast<unsigned>(rows)), dim3(256), 0, stream, X);
-    IST_HIP(hipGetLastError());
-    g_launches.fetch_add(1, std::memory_order_relaxed);
+    if (!kept) { rc = transform(r0, rows); if (rc) return rc; }
     EntropyArgs E;
     E.coef = X.coef; E.tab = X.tab; E.slots = scratch + o_slots; E.len = len;
     E.row_blocks = static_cast<int32_t>(g.row_blocks); E.bpm = g.bpm; E.slot = g.slot;
-    hipLaunchKernelGGL(ist_jpeg_entropy_kernel, dim3(static_cast<unsigned>(rows)), dim3(kBatch), 0, stream, E);
+    if (optimize) hipLaunchKernelGGL(ist_jpeg_entropy_wide_kernel, dim3(static_cast<unsigned>(rows)), dim3(kBatch), 0, stream, E);
+    else hipLaunchKernelGGL(ist_jpeg_entropy_kernel, dim3(static_cast<unsigned>(rows)), dim3(kBatch), 0, stream, E);
     IST_HIP(hipGetLastError());
     IST_HIP(hipStreamSynchronize(stream));
     for (int64_t k = 0; k < rows; ++k) {
       if (r0 + k > 0) pos += 2;                      // RSTn
+      // (length 0 is also what the wide kernel reports for a symbol that the file's tables have no code for)
       if (len[k] < 1 || static_cast<int64_t>(len[k]) >= g.slot) return fail(IST_E_HIP, "JPEG entropy kernel returned an impossible interval length");
       dst[k] = pos;
       pos += len[k];
@@ -449,12 +596,20 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
 // Many canvases, round by round (jpeg_batch_pieces): the round's tables, headers and piece records go up in ONE copy through the
 // ring of ist_jobs_launch, then one transform and one entropy launch for all its pieces, one synchronisation in which the host lays the
 // intervals out per file, and one gather launch, which also writes headers and EOI markers.  Nothing else is copied.
+// Files with IST_JPEG_OPTIMIZE have tables and a header of their own, which need the file's counts.  A batch of one round counts
+// between its transform and its entropy launch (one more synchronisation, the counts down, the table block up again); a batch of
+// several rounds first transforms and counts every round that holds an optimised piece, then runs its rounds as ever.
 int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* stream_, const char* what, const int* ids) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int n = static_cast<int>(files.size());
   const std::vector<ist_jpeg_piece> pieces = jpeg_batch_pieces(files.data(), n, jpeg_batch_budget());
   const int n_pieces = static_cast<int>(pieces.size());
+  std::vector<JpegOptFile> opt(static_cast<size_t>(n));
+  int n_opt = 0;
+  for (int k = 0; k < n; ++k)
+    if (jpeg_ss_optimize(files[static_cast<size_t>(k)].subsampling)) opt[static_cast<size_t>(k)].hist = n_opt++;
   std::vector<JpegRound> rounds;
+  std::vector<unsigned> hist_parts;                  // per round: the parts of the longest interval among its optimised pieces
   int64_t max_ivs = 0;
   size_t max_scratch = 0;
   for (int p0 = 0; p0 < n_pieces;) {
@@ -464,36 +619,101 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
     const JpegRound& R = rounds.back();
     if (R.wgs > 2147483647ll) return fail(IST_E_UNSUPPORTED, "a JPEG batch round of more than 2^31 - 1 workgroups");
     max_ivs = std::max(max_ivs, R.ivs); max_scratch = std::max(max_scratch, R.scratch_bytes);
+    int64_t longest = 0;
+    for (int f : R.opt_files) longest = std::max(longest, geometry(files[static_cast<size_t>(f)].w, files[static_cast<size_t>(f)].h, files[static_cast<size_t>(f)].subsampling).row_blocks);
+    hist_parts.push_back(static_cast<unsigned>((longest + kHistBlocks - 1) / kHistBlocks));
     p0 = p1;
   }
   // The ring and the scratch are held for the whole call: a second batch encode on this context waits here, so neither grows
   // nor overwrites the scratch under this one's kernels.  A slot is refilled two rounds later at the earliest, behind the
   // synchronisation of the round in between, which is queued behind this round's gather: no event is needed WHILE the lock is held
   // through the last synchronisation (Drain below; whoever drops that must record slot->done and set slot->pending instead).
+  // (A counted round is synchronised before the next one starts.)
   std::lock_guard<std::mutex> lk(ctx->batch_mu);
   int rc = grow_device(&ctx->scratch_jpg, &ctx->scratch_jpg_bytes, max_scratch);
   if (rc) return rc;
+  const size_t count_bytes = static_cast<size_t>(n_opt) * kJpegCounters * 8;
+  if (n_opt) { rc = grow_device(&ctx->scratch_jpg_counts, &ctx->scratch_jpg_counts_bytes, count_bytes); if (rc) return rc; }
   uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg);
-  // per interval of a round: its length (written by the kernel) and its place in its file (read by the gather), in pinned memory
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(static_cast<size_t>(max_ivs) * 16))};
+  int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts);
+  // per interval of a round: its length (written by the kernel) and its place in its file (read by the gather), in pinned memory;
+  // behind them the counts of the optimised files
+  const size_t o_counts = static_cast<size_t>(max_ivs) * 16;
+  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(o_counts + count_bytes))};
   if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
   int64_t* const dst = reinterpret_cast<int64_t*>(res.p);
   uint32_t* const len = reinterpret_cast<uint32_t*>(res.p + 8 * static_cast<size_t>(max_ivs));
-  std::vector<int64_t> pos(static_cast<size_t>(n), kJpegHeaderBytes);
+  std::vector<int64_t> pos(static_cast<size_t>(n), kJpegHeaderBytes);      // (an optimised file's: its own header's length, below)
   // Every way out leaves the stream idle (kernels in flight read the slot and write `res`).
   struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
-  for (const JpegRound& R : rounds) {
-    ist_ctx::BatchSlot* slot = nullptr;
-    rc = batch_take_slot(ctx, R.table_bytes, &slot);
-    if (rc) return rc;
+  // one round's table block up, its transform and, for its optimised pieces, their histogram
+  auto transform = [&](const JpegRound& R, ist_ctx::BatchSlot* slot, bool count, unsigned parts) -> int {
     uint8_t* const d = static_cast<uint8_t*>(slot->dev);
-    jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch);
+    jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch, opt.data());
     IST_HIP(hipMemcpyAsync(d, slot->host, R.table_bytes, hipMemcpyHostToDevice, stream));
     const JpegBatchArgs B{reinterpret_cast<const JpegPiece*>(d + R.at_pieces), R.p1 - R.p0, len, dst};
     hipLaunchKernelGGL(ist_jpeg_transform_batch_kernel, dim3(static_cast<unsigned>(R.wgs)), dim3(256), 0, stream, B);
     IST_HIP(hipGetLastError());
     count_jpeg_batch_launch();
-    hipLaunchKernelGGL(ist_jpeg_entropy_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
+    if (count) {
+      const JpegHistBatchArgs HB{B.pieces, B.n, counters};
+      hipLaunchKernelGGL(ist_jpeg_histogram_batch_kernel, dim3(static_cast<unsigned>(R.ivs), parts), dim3(256), 0, stream, HB);
+      IST_HIP(hipGetLastError());
+      g_hist_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    return IST_OK;
+  };
+  // the counts down (one synchronisation), then every optimised file's tables and header
+  auto build_tables = [&]() -> int {
+    IST_HIP(hipMemcpyAsync(res.p + o_counts, counters, count_bytes, hipMemcpyDeviceToHost, stream));
+    IST_HIP(hipStreamSynchronize(stream));
+    for (int k = 0; k < n; ++k) {
+      JpegOptFile& o = opt[static_cast<size_t>(k)];
+      if (o.hist < 0) continue;
+      const JpegBatchFile& f = files[static_cast<size_t>(k)];
+      JpegHuffSpec spec;
+      jpeg_enc_tables_optimal(f.quality, reinterpret_cast<const int64_t*>(res.p + o_counts) + static_cast<size_t>(o.hist) * kJpegCounters, &o.T, &spec);
+      o.head = jpeg_enc_header(f.w, f.h, f.subsampling, o.T, geometry(f.w, f.h, f.subsampling).mcus_x, &spec);
+      o.built = true;
+      pos[static_cast<size_t>(k)] = static_cast<int64_t>(o.head.size());
+    }
+    return IST_OK;
+  };
+  const bool one_round = rounds.size() == 1;
+  if (n_opt) {
+    IST_HIP(hipMemsetAsync(counters, 0, count_bytes, stream));
+    if (!one_round) {
+      for (size_t r = 0; r < rounds.size(); ++r) {
+        if (rounds[r].opt_files.empty()) continue;
+        ist_ctx::BatchSlot* slot = nullptr;
+        rc = batch_take_slot(ctx, rounds[r].table_bytes, &slot);
+        if (rc) return rc;
+        rc = transform(rounds[r], slot, true, hist_parts[r]);
+        if (rc) return rc;
+        IST_HIP(hipStreamSynchronize(stream));       // the next round rewrites the scratch (and, two rounds on, the slot)
+      }
+      rc = build_tables();
+      if (rc) return rc;
+    }
+  }
+  for (size_t r = 0; r < rounds.size(); ++r) {
+    const JpegRound& R = rounds[r];
+    const bool wide = !R.opt_files.empty();
+    ist_ctx::BatchSlot* slot = nullptr;
+    rc = batch_take_slot(ctx, R.table_bytes, &slot);
+    if (rc) return rc;
+    uint8_t* const d = static_cast<uint8_t*>(slot->dev);
+    rc = transform(R, slot, wide && one_round, hist_parts[r]);
+    if (rc) return rc;
+    const JpegBatchArgs B{reinterpret_cast<const JpegPiece*>(d + R.at_pieces), R.p1 - R.p0, len, dst};
+    if (wide && one_round) {                         // the coefficients stay; the block goes up again with the files' own tables and headers
+      rc = build_tables();
+      if (rc) return rc;
+      jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch, opt.data());
+      IST_HIP(hipMemcpyAsync(d, slot->host, R.table_bytes, hipMemcpyHostToDevice, stream));
+    }
+    if (wide) hipLaunchKernelGGL(ist_jpeg_entropy_wide_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
+    else hipLaunchKernelGGL(ist_jpeg_entropy_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
     IST_HIP(hipGetLastError());
     IST_HIP(hipStreamSynchronize(stream));
     int64_t iv = 0;
@@ -504,6 +724,7 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
       int64_t at = pos[static_cast<size_t>(pc.file)];
       for (int64_t k = 0; k < pc.mcu_rows; ++k, ++iv) {
         if (pc.mcu_row0 + k > 0) at += 2;              // RSTn
+        // (length 0 is also what the wide kernel reports for a symbol that the file's tables have no code for)
         if (len[iv] < 1 || static_cast<int64_t>(len[iv]) >= g.slot) return fail(IST_E_HIP, "JPEG entropy kernel returned an impossible interval length");
         dst[iv] = at;
         at += len[iv];
@@ -549,6 +770,7 @@ using namespace ist;
 extern "C" {
 
 int64_t ist_debug_jpeg_encode_launches(void) { return g_launches.load(std::memory_order_relaxed); }
+int64_t ist_debug_jpeg_histogram_launches(void) { return g_hist_launches.load(std::memory_order_relaxed); }
 
 int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {
   if (quality < 1 || quality > 100) return fail(IST_E_INVALID, "ist_jpeg_quant_tables: quality must be 1..100");
@@ -557,10 +779,18 @@ int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {
   return IST_OK;
 }
 
+int ist_jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[256], int* n_vals) {
+  if (!freq || !bits || !vals || !n_vals) return fail(IST_E_INVALID, "ist_jpeg_optimal_table: NULL argument");
+  for (int s = 0; s < 256; ++s)
+    if (freq[s] < 0) return fail(IST_E_INVALID, "ist_jpeg_optimal_table: negative count");
+  *n_vals = jpeg_optimal_table(freq, bits, vals);
+  return IST_OK;
+}
+
 int64_t ist_jpeg_bound(int64_t w, int64_t h, int subsampling) {
-  if (w < 1 || h < 1 || w > 65535 || h > 65535 || (subsampling != IST_JPEG_444 && subsampling != IST_JPEG_420)) return -1;
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || !jpeg_ss_known(subsampling)) return -1;
   const Geometry g = geometry(w, h, subsampling);
-  return 1024 + g.mcus_y * (g.row_blocks * kJpegBlockBytes + 16);
+  return 1024 + g.mcus_y * (g.row_blocks * g.block_bytes + 16);
 }
 
 int ist_jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, void* out,

@@ -189,6 +189,7 @@ void ist_ctx_destroy(ist_ctx* ctx) {
   dev_free(ctx->scratch_png);
   dev_free(ctx->scratch_file);
   dev_free(ctx->scratch_jpg);
+  dev_free(ctx->scratch_jpg_counts);
   dev_free(ctx->scratch_arena);
   dev_free(ctx->scratch_ent);
   for (hipStream_t st : ctx->img_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }

@@ -737,23 +737,28 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
 
 
 JPEG_SUBSAMPLING = {"444": 0, "420": 1}      # IST_JPEG_444 / IST_JPEG_420
+JPEG_OPTIMIZE = 0x100                        # IST_JPEG_OPTIMIZE, OR-ed into the subsampling
 
 
-def _jpeg_args(quality, subsampling):
-    """(quality, IST_JPEG_*) of a JPEG export, checked: an integer quality 1..100, subsampling '420' or '444'"""
+def _jpeg_args(quality, subsampling, optimize=False):
+    """(quality, IST_JPEG_* [| IST_JPEG_OPTIMIZE]) of a JPEG export, checked: an integer quality 1..100, subsampling '420' or '444',
+    optimize a bool (the file's own Huffman tables)"""
+    if not isinstance(optimize, bool):
+        raise TypeError("optimize: expected a bool")
     if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)):
         raise TypeError("quality: expected an integer 1..100")
     if not 1 <= int(quality) <= 100:
         raise ValueError("quality must be 1..100")
     if str(subsampling) not in JPEG_SUBSAMPLING:
         raise ValueError("subsampling must be '420' or '444'")
-    return int(quality), JPEG_SUBSAMPLING[str(subsampling)]
+    return int(quality), JPEG_SUBSAMPLING[str(subsampling)] | (JPEG_OPTIMIZE if optimize else 0)
 
 
-def encode_jpeg(pixels, quality=90, subsampling="420", device=0):
+def encode_jpeg(pixels, quality=90, subsampling="420", device=0, optimize=False):
     """Baseline JFIF file (bytes) of an HxWx4 uint8 array, encoded on the GPU (ist_jpeg_encode_rgba8; the export with fileType 'jpg',
-    utils/canvas.js:205-221).  Alpha is not read.  The file is pinned byte for byte by include/imagestitch.h."""
-    q, ss = _jpeg_args(quality, subsampling)
+    utils/canvas.js:205-221).  Alpha is not read.  The file is pinned byte for byte by include/imagestitch.h.  optimize=True: the
+    file carries the Huffman tables that are optimal for its own symbols (IST_JPEG_OPTIMIZE) - the same pixels in fewer bytes."""
+    q, ss = _jpeg_args(quality, subsampling, optimize)
     a = _rgba(pixels)
     if a.shape[0] < 1 or a.shape[1] < 1:
         raise TypeError("expected an HxWx4 uint8 RGBA array")
@@ -763,11 +768,12 @@ def encode_jpeg(pixels, quality=90, subsampling="420", device=0):
     return _take_png(out, n)
 
 
-def encode_jpeg_device(canvas, quality=90, subsampling="420", out=None, stream=None):
+def encode_jpeg_device(canvas, quality=90, subsampling="420", out=None, stream=None, optimize=False):
     """JPEG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor, any row pitch that is a multiple of 4) into a CUDA uint8
-    tensor (ist_jpeg_encode_device); returns (tensor, length) like encode_png_device.  out: optional, ist_jpeg_bound + 16 bytes."""
+    tensor (ist_jpeg_encode_device); returns (tensor, length) like encode_png_device.  out: optional, ist_jpeg_bound + 16 bytes (the
+    bound of the optimised file when optimize=True: it is the larger one)."""
     import torch
-    q, ss = _jpeg_args(quality, subsampling)
+    q, ss = _jpeg_args(quality, subsampling, optimize)
     _check_canvas(canvas, "encode_jpeg_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
     out, off, dst, cap = _file_out(out, L.lib.ist_jpeg_bound(w, h, ss), canvas.device)
@@ -780,11 +786,11 @@ def encode_jpeg_device(canvas, quality=90, subsampling="420", out=None, stream=N
 
 def stitch_jpeg(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the JPEG export: returns {'width', 'height', 'jpeg': bytes} (ist_stitch_jpeg /
-    ist_stitch_bitmaps_jpeg).  opts['quality'] (1..100, default 90) and opts['subsampling'] ('420' default, or '444') choose the file;
-    the canvas stays on the device and only the file crosses PCIe.  images as for stitch_png(): marshalled as stitch() marshals them,
+    ist_stitch_bitmaps_jpeg).  opts['quality'] (1..100, default 90), opts['subsampling'] ('420' default, or '444') and
+    opts['optimize'] (a bool, default False: the file's own Huffman tables) choose the file; the canvas stays on the device and only the file crosses PCIe.  images as for stitch_png(): marshalled as stitch() marshals them,
     or a list of Bitmaps."""
     opts = dict(opts or {})
-    jpeg = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
+    jpeg = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"), opts.pop("optimize", False))
     o = _merge(opts)
     _no_preview(o, "stitch_jpeg", "previews are built beside the PNG export")
     if o.get("devices") is not None:
@@ -801,19 +807,19 @@ def _per_file(value, n, name):
     return [value] * n
 
 
-def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None, stream=None):
+def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None, stream=None, optimize=False):
     """JPEG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch that is a multiple of 4) in
     one transform, one entropy and one gather launch per round (ist_jpeg_encode_batch_device).  quality and subsampling: one value for
-    all files or a sequence of length n.  outs: optional CUDA uint8 tensors of at least ist_jpeg_bound + 16 bytes each.  Returns
+    all files or a sequence of length n, and so is optimize (a batch may mix optimised and standard files).  outs: optional CUDA uint8 tensors of at least ist_jpeg_bound + 16 bytes each.  Returns
     [(tensor, length)], each file byte for byte what encode_jpeg_device gives for that canvas."""
     canvases = list(canvases)
     n = len(canvases)
     if n == 0:
         return []
     args = []
-    for k, (q, s) in enumerate(zip(_per_file(quality, n, "quality"), _per_file(subsampling, n, "subsampling"))):
+    for k, (q, s, o) in enumerate(zip(_per_file(quality, n, "quality"), _per_file(subsampling, n, "subsampling"), _per_file(optimize, n, "optimize"))):
         try:
-            args.append(_jpeg_args(q, s))
+            args.append(_jpeg_args(q, s, o))
         except (TypeError, ValueError) as e:
             raise type(e)("file %d: %s" % (k, e)) from None
     qs, ss = (C.c_int * n)(*[a[0] for a in args]), (C.c_int * n)(*[a[1] for a in args])
@@ -823,8 +829,8 @@ def encode_jpeg_batch_device(canvases, quality=90, subsampling="420", outs=None,
 
 def stitch_jpeg_batch(requests, device=0):
     """Many independent stitch_jpeg() calls in one go (ist_stitch_jpeg_batch): stitch_png_batch with a JPEG file in place of each
-    PNG.  requests as for stitch_batch; each request's opts may carry 'quality' (1..100, default 90) and 'subsampling' ('420'
-    default, or '444').  Returns a list of {'width', 'height', 'jpeg': bytes}, with None for a request without images; each file is
+    PNG.  requests as for stitch_batch; each request's opts may carry 'quality' (1..100, default 90), 'subsampling' ('420'
+    default, or '444') and 'optimize' (a bool, default False).  Returns a list of {'width', 'height', 'jpeg': bytes}, with None for a request without images; each file is
     stitch_jpeg(*requests[k])['jpeg'], byte for byte."""
     reqs = list(requests)
     if not reqs:
@@ -836,7 +842,7 @@ def stitch_jpeg_batch(requests, device=0):
             raise TypeError("request %d: expected (images, direction) or (images, direction, opts)" % k)
         opts = dict(r[2] or {}) if len(r) == 3 else {}
         try:
-            qs[k], ss[k] = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"))
+            qs[k], ss[k] = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"), opts.pop("optimize", False))
         except (TypeError, ValueError) as e:
             raise type(e)("request %d: %s" % (k, e)) from None
         plain.append((r[0], r[1], opts))

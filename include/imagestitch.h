@@ -635,15 +635,47 @@ IST_API int64_t ist_debug_thumb_launches(void);
  *     tables K.3 - K.6), DRI = R, SOF0 (components 1, 2, 3; slots 0, 1, 1), SOS, the intervals, EOI.  One interleaved scan; R =
  *     ceil(w / MCU width), so one restart interval is one MCU row: its DC predictors restart, it is padded with 1 bits to a byte,
  *     every 0xFF is followed by 0x00, and RST((k-1) mod 8) stands between intervals k-1 and k.
- * Such files are eligible for the library's own GPU Huffman decoder (ist_decode_files_device). */
+ * Such files are eligible for the library's own GPU Huffman decoder (ist_decode_files_device).
+ *
+ * OPTIMISED HUFFMAN TABLES: IST_JPEG_OPTIMIZE, OR-ed into any `subsampling` argument below (as IST_FILTER_EDGE_AA is OR-ed into
+ * `filter`), gives the file the four Huffman tables that are optimal for its own symbols.  Only the four DHT segments (still in
+ * the order DC0, DC1, AC0, AC1) and the codes in the scan differ from the file without the flag; colour, padding, FDCT, quantiser,
+ * clamps, DQTs, DRI, SOF0, SOS, the intervals, their padding, stuffing, the RSTn order and EOI do not.  Without the flag every call
+ * does what it did before the flag existed.  Any value other than IST_JPEG_444 / IST_JPEG_420 with or without the flag is an
+ * unknown subsampling (2, 3, 7, -1, 0x200, 0x102, ...).
+ *   - symbol counts, exact 64-bit integers taken over the whole file, all intervals together (a 65535 x 65535 4:4:4 file has more
+ *     than 2^32 AC symbols):
+ *       DC slot 0: the size category 0..11 of every Y block's DC difference; the predictor restarts at 0 at the start of every
+ *                  interval and the difference is clamped to +-2047 (as the scan codes it);   DC slot 1: the same over Cb and Cr;
+ *       AC slot 0 (Y) / slot 1 (Cb, Cr): every run/size symbol 16 run + size a block emits, AC values clamped to +-1023; 0xF0 once
+ *                  per ZRL (16 zeros in front of a non-zero value), 0x00 once per block that ends in zeros;
+ *   - the table of one histogram (T.81 K.2; ist_jpeg_optimal_table is this rule):
+ *       1. leaves: every symbol with a count > 0, and a reserved symbol 256 with count 1; a leaf is a node (weight, id = symbol);
+ *       2. repeatedly take the two nodes that are smallest by (weight, id) and merge them into (sum of weights, smaller id); the
+ *          code size of every symbol inside the merged node grows by 1;
+ *       3. BITS[l] = number of leaves of size l, the reserved one included;
+ *       4. while a size above 16 is populated (T.81 figure K.3), from the largest size i downwards: take two from size i, find
+ *          the nearest populated j <= i - 2, then BITS[i] -= 2, BITS[i-1] += 1, BITS[j+1] += 2, BITS[j] -= 1;
+ *       5. remove one code from the largest populated size (the reserved point: no code is all ones);
+ *       6. HUFFVAL = the real symbols sorted by (size before step 4, symbol value);
+ *       7. codes are canonical (T.81 C.2).
+ *     An empty histogram gives 16 zero BITS and no values (no real file has one: every table sees a DC symbol or an EOB).
+ *   - bound: an optimised DC code may be 16 bits long (Annex K's longest is 11), so a block is at most 27 + 63 x 26 = 1665 bits, 417
+ *     bytes after stuffing: with the flag slot = (row_blocks * 417 + 2 + 15) & ~15 and
+ *         bound = 1024 + MCU rows x (blocks per MCU row x 417 + 16);
+ *     the header is at most 629 bytes (a DC table has at most 12 symbols, an AC table at most 162, as in Annex K). */
 enum { IST_JPEG_444 = 0, IST_JPEG_420 = 1 };
+enum { IST_JPEG_OPTIMIZE = 0x100 };
+/* BITS (16 counts, lengths 1..16) and HUFFVAL (n_vals symbols) of the optimal table of 256 symbol counts, by the rule above.  Pure
+ * CPU, no context.  IST_E_INVALID: a NULL argument, a negative count. */
+IST_API int ist_jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
 /* the two quantisation tables of a quality, natural order.  Pure CPU.  IST_E_INVALID: quality outside 1..100, a NULL table */
 IST_API int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
 /* an upper bound of the file's size that the encoder guarantees; negative for bad arguments (a side < 1 or > 65535, an unknown
  * subsampling).  Pure CPU.  A block is at most 22 bits of DC (an 11-bit code + 11 bits) + 63 x 26 bits of AC (a 16-bit code + 10
  * bits) = 1660 bits before stuffing; stuffing at most doubles a byte: 415 bytes per block.  An interval adds at most one pad byte
  * (which may be stuffed) and its 2-byte marker, the file 629 bytes of header and 2 of EOI:
- *     bound = 1024 + MCU rows x (blocks per MCU row x 415 + 16). */
+ *     bound = 1024 + MCU rows x (blocks per MCU row x 415 + 16)        (with IST_JPEG_OPTIMIZE: 417, see above). */
 IST_API int64_t ist_jpeg_bound(int64_t w, int64_t h, int subsampling);
 /* encode a canvas that is resident in HBM into a device buffer (16-byte aligned, out_cap >= ist_jpeg_bound): transform, entropy
  * code and gather run on `stream`, which is synchronised before the call returns (the host lays the intervals out).  Every argument
@@ -664,8 +696,12 @@ IST_API int ist_stitch_jpeg(ist_ctx* ctx, const ist_image_desc* images, const ui
 IST_API int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap,
                                     const ist_limits* limits, int filter, int quality, int subsampling, ist_plan* out_plan,
                                     uint8_t** out_jpeg, int64_t* out_len);
-/* transform launches (one per slab of MCU rows) made by JPEG encodes in this process so far */
+/* transform launches (one per slab of MCU rows) made by JPEG encodes in this process so far.  With IST_JPEG_OPTIMIZE the whole file
+ * is counted before its first interval is coded: a file of one slab keeps its coefficients (1 launch), a file of N > 1 slabs is
+ * transformed twice (2 N launches). */
 IST_API int64_t ist_debug_jpeg_encode_launches(void);
+/* histogram launches (IST_JPEG_OPTIMIZE: one per slab of a single file, one per counted round of a batch) so far */
+IST_API int64_t ist_debug_jpeg_histogram_launches(void);
 
 /* ---- batched JPEG export: many canvases per launch --------------------------------------------------------------------------
  * The encoder's unit of work is the restart interval (one MCU row), and an interval of file A needs an interval of file B as little
@@ -675,7 +711,11 @@ IST_API int64_t ist_debug_jpeg_encode_launches(void);
  * closes when the next row would not fit; a row above the budget on its own gets a round to itself.  The run of consecutive MCU
  * rows of one file in one round is a PIECE; a file above the budget spans rounds as several pieces, in order.  One round is one
  * transform, one entropy and one gather launch, one stream synchronisation (the host lays the intervals out, per file) and ONE
- * host-to-device copy (tables, headers, piece records); the gather writes every byte of a file, header and EOI included. */
+ * host-to-device copy (tables, headers, piece records); the gather writes every byte of a file, header and EOI included.
+ * Files with IST_JPEG_OPTIMIZE (their rows cost the 417-byte slot) may be mixed with files without: a batch of one round
+ * transforms once, counts the optimised pieces, synchronises once more and sends the block up again with the files' own tables
+ * and headers; a batch of several rounds first transforms and counts every round that holds an optimised piece, then runs its
+ * rounds (at most two transform launches per round). */
 typedef struct ist_jpeg_piece { int32_t file, round, mcu_row0, mcu_rows; } ist_jpeg_piece;
 /* pieces of a batch in encoding order; budget_bytes 0 = the encoder's own.  Returns the number of pieces (also when out is NULL or cap
  * is too small: nothing is written beyond cap), negative on a bad argument (n < 1, a NULL array, a side outside 1..65535, an unknown

@@ -42,7 +42,7 @@ export function stitchPngBatch(requests: StitchRequest[]): Promise<(StitchPngRes
 export function stitchPngBatchSync(requests: StitchRequest[]): (StitchPngResult | null)[];
 export function encodePng(data: Uint8Array, width: number, height: number, opts?: { pngLevel?: 0 | 1 }): Buffer;
 // the export with fileType 'jpg': a baseline JFIF file, pinned byte for byte by include/imagestitch.h (alpha is not read); preview and devices are refused
-export interface JpegOptions { quality?: number; subsampling?: '420' | '444' | 420 | 444; }      // quality: an integer 1..100, default 90; subsampling default '420'
+export interface JpegOptions { quality?: number; subsampling?: '420' | '444' | 420 | 444; optimize?: boolean; }      // quality: an integer 1..100, default 90; subsampling default '420'; optimize default false: the file's own Huffman tables (smaller file, same pixels)
 export interface StitchJpegResult { width: number; height: number; jpeg: Buffer; plan: StitchPlan; }
 export function stitchJpeg(images: StitchImage[] | Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split' | 'preview' | 'pngLevel'> & JpegOptions): Promise<StitchJpegResult | null>;
 export function encodeJpeg(data: Uint8Array, width: number, height: number, opts?: JpegOptions): Buffer;

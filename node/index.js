@@ -7,8 +7,8 @@
  *
  *   stitch(images, direction, opts?) -> Promise<{width, height, data: Buffer, plan}>
  *   stitchBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, data, plan} | null)[]>   (one GPU, many stitches)
- *   stitchJpeg(images | Bitmap[], direction, opts + {quality, subsampling}) -> Promise<{width, height, jpeg, plan}>   (baseline JFIF)
- *   encodeJpeg(data, width, height, {quality, subsampling}) -> Buffer
+ *   stitchJpeg(images | Bitmap[], direction, opts + {quality, subsampling, optimize}) -> Promise<{width, height, jpeg, plan}>   (baseline JFIF)
+ *   encodeJpeg(data, width, height, {quality, subsampling, optimize}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   stitchJpegBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, jpeg, plan} | null)[]>  (one GPU, many JPEG files)
  *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
@@ -241,7 +241,7 @@ function jpegBatchArgs(requests) {
     if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
     const o = Object.assign({}, r.opts || {});
     try {
-      const j = jpegArgs(o); delete o.quality; delete o.subsampling;
+      const j = jpegArgs(o); delete o.quality; delete o.subsampling; delete o.optimize;
       return batchRequest(r, k, o).concat([j.quality, j.subsampling]);
     } catch (e) {
       if (!e.message.startsWith('request ' + k)) e.message = 'request ' + k + ': ' + e.message;
@@ -260,23 +260,26 @@ function stitchJpegBatch(requests) {
 }
 function stitchJpegBatchSync(requests) { const a = jpegBatchArgs(requests); return a.length ? native.stitchJpegBatchSync(a) : []; }
 const SUBSAMPLING = { 444: 0, 420: 1 };          // IST_JPEG_444 / IST_JPEG_420
-// {quality, subsampling} of a JPEG export, checked: an integer quality 1..100 (default 90), subsampling '420' (default) or '444'
+// {quality, subsampling} of a JPEG export, checked: an integer quality 1..100 (default 90), subsampling '420' (default) or '444',
+// optimize a boolean (default false: the file's own Huffman tables, IST_JPEG_OPTIMIZE = 0x100 OR-ed into the subsampling)
 function jpegArgs(o) {
   const quality = (o && o.quality !== undefined && o.quality !== null) ? o.quality : 90;
   const ss = String((o && o.subsampling !== undefined && o.subsampling !== null) ? o.subsampling : '420');
   if (!Number.isInteger(quality) || quality < 1 || quality > 100) throw new RangeError('quality must be an integer 1..100');
   if (!(ss in SUBSAMPLING)) throw new TypeError("subsampling must be '420' or '444'");
-  return { quality, subsampling: SUBSAMPLING[ss] };
+  const optimize = (o && o.optimize !== undefined && o.optimize !== null) ? o.optimize : false;
+  if (typeof optimize !== 'boolean') throw new TypeError('optimize must be a boolean');
+  return { quality, subsampling: SUBSAMPLING[ss] | (optimize ? 0x100 : 0) };
 }
 /** stitch + the export with fileType 'jpg' (utils/canvas.js:205-221): resolves {width, height, jpeg: Buffer (a baseline JFIF file),
- *  plan}. opts.quality (1..100, default 90) and opts.subsampling ('420' default, '444') choose the file, which is pinned byte for
+ *  plan}. opts.quality (1..100, default 90) and opts.subsampling ('420' default, '444') and opts.optimize (a boolean, default false: the file's own Huffman tables) choose the file, which is pinned byte for
  *  byte by include/imagestitch.h; alpha is not read. images may be Bitmap[]. The canvas never leaves the GPU. preview and devices
  *  do not apply. */
 function stitchJpeg(images, direction, opts) {
   let a, h, j;
   try {
     const o = Object.assign({}, opts || {});
-    j = jpegArgs(o); delete o.quality; delete o.subsampling;
+    j = jpegArgs(o); delete o.quality; delete o.subsampling; delete o.optimize;
     if (o.preview !== undefined && o.preview !== null) throw new TypeError('stitchJpeg: option preview does not apply (previews are built beside the PNG export)');
     if (o.devices !== undefined && o.devices !== null) throw new TypeError('stitchJpeg: option devices does not apply (the JPEG export runs on one GPU)');
     h = bitmapHandles(images, o); a = args(images, direction, o);

@@ -3,6 +3,7 @@
 #   tools/run_fuzz.sh ITERS seed1 [seed2 ...]     mutation-fuzz the file parsers (PNG / JPEG / BMP / GIF / WebP) from seed files
 #   tools/run_fuzz.sh compile ITERS               random + hostile op lists through the op-list compiler, invariants checked
 #   tools/run_fuzz.sh jpegbatch ITERS [SEED]      random batches through the rounds, header blob and piece records of the batched JPEG export
+#   tools/run_fuzz.sh jpegoptimize ITERS [SEED]   random + adversarial symbol counts through the optimal-table builder and the DHT / header writer
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); C=$ROOT/imagestitching_amd/csrc
 OUT=${IST_FUZZ_BIN:-/tmp/ist_fuzz}
@@ -14,6 +15,9 @@ if [ "$1" = compile ]; then
 elif [ "$1" = jpegbatch ]; then
   shift
   g++ $FLAGS "$HERE/check_jpeg_batch_host.cpp" "$C/ist_jpeg_enc_host.cpp" -o "$OUT"
+elif [ "$1" = jpegoptimize ]; then
+  shift
+  g++ $FLAGS "$HERE/check_jpeg_optimize_host.cpp" "$C/ist_jpeg_enc_host.cpp" -o "$OUT"
 else
   # (IST_FUZZ_REUSE=1: keep a binary that is already there - the tests build the harness once per session)
   if [ -z "$IST_FUZZ_REUSE" ] || [ ! -x "$OUT" ]; then
