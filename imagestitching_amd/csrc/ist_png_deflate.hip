@@ -91,7 +91,8 @@ __device__ __forceinline__ uint32_t paeth4(uint32_t cur, uint32_t a, uint32_t b,
   return ((cur | 0x80808080u) - (pred & 0x7F7F7F7Fu)) ^ ((cur ^ ~pred) & 0x80808080u);
 }
 
-// deflate length symbol for a match of l bytes (3 <= l <= 66): symbol, extra-bit count, extra-bit value
+// deflate length symbol for a match of l bytes (3 <= l <= 63: a match never leaves its 64-byte span, whose first byte is a literal;
+// symbols 257 .. 276, at most 3 extra bits): symbol, extra-bit count, extra-bit value
 __device__ __forceinline__ void len_code(int l, int* sym, int* eb, int* ev) {
   const int m = l - 3;
   if (m < 8) { *sym = 257 + m; *eb = 0; *ev = 0; return; }
@@ -329,7 +330,8 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   // COMPLETE (inflate rejects an incomplete literal/length code).  Every shortening costs a multiple of the smallest unit
   // left, so the rounds end with the slack at exactly zero (<= 12 rounds over 3000 random histograms; photo chunks need
   // 2-4).  Which symbols of a length class go first is decided by symbol index, so the file is the same on every run.
-  // Against Huffman's lengths the token bits grow by 0.4 % (photo chunks) to 1.2 % (noise) - tools/sim_code_lengths.py -
+  // Against Huffman's lengths the token bits grow by 0.5 % (photo chunks) to 1.2 % (the bench's synthetic content; 2.3 % on noise,
+  // which is stored anyway) - tools/sim_code_lengths.py -
   // and the sort (36-45 barrier steps), the serial two-queue merge (n - 1 dependent LDS round trips on one thread), the
   // depth walk and the 286-long rank loops are gone: 24 us of a chunk's ~90 (IST_PNG_PHASES) become a few.
   // Lane j holds symbols j, 64 + j, ... 256 + j.  A chunk whose code does not complete in 16 rounds is stored.

@@ -66,19 +66,31 @@ def shannon_complete(counts, max_rounds=16):
     return (length if slack == 0 else None), rounds
 
 
-def tokens(row):
-    """a row's bytes as the encoder's symbols: literals, a run of equal bytes as one literal + length symbols"""
-    sym, i, r = [], 0, row.tolist()
-    while i < len(r):
-        j = i
-        while j + 1 < len(r) and r[j + 1] == r[i] and j - i < 65:
-            j += 1
-        sym.append(r[i])
-        if j - i + 1 >= 4:
-            sym.append(257 + min(28, (j - i - 3) // 4))
-            i = j + 1
-        else:
-            i += 1
+def length_symbol(n):
+    """RFC 1951 length symbol of a match of n bytes (the encoder sends 3 .. 63), as the kernel's len_code computes it"""
+    m = n - 3
+    if m < 8:
+        return 257 + m
+    e = m.bit_length() - 3
+    return 257 + 4 * (e + 1) + ((m >> e) & 3)
+
+
+def tokens(chunk, span=64):
+    """a chunk's bytes as the encoder's symbols.  The chunk is cut into spans of 64 bytes; inside a span a run of R >= 4 equal
+    bytes is its first byte as a literal + ONE length symbol for the other R - 1 (distance 1), shorter runs are literals, and no
+    run continues into the next span.  End-of-block closes the list."""
+    sym, r = [], list(np.asarray(chunk).tolist())
+    for s0 in range(0, len(r), span):
+        end, i = min(s0 + span, len(r)), s0
+        while i < end:
+            j = i + 1
+            while j < end and r[j] == r[i]:
+                j += 1
+            if j - i >= 4:
+                sym += [r[i], length_symbol(j - i - 1)]
+            else:
+                sym += [r[i]] * (j - i)
+            i = j
     sym.append(256)
     return sym
 
