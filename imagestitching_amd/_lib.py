@@ -136,6 +136,7 @@ SYMBOLS = [
     ("ist_ctx_destroy", None, [C.c_void_p]),
     ("ist_ctx_sync", C.c_int, [C.c_void_p]),
     ("ist_ctx_set_png_level", C.c_int, [C.c_void_p, C.c_int]),
+    ("ist_ctx_set_png_color", C.c_int, [C.c_void_p, C.c_int]),
     ("ist_job_create", C.c_void_p, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(Op), C.c_int,
                                     C.POINTER(ImageDesc), C.c_int, C.c_int, C.POINTER(Region)]),
     ("ist_job_info_get", C.c_int, [C.c_void_p, C.POINTER(JobInfo)]),
@@ -226,6 +227,7 @@ SYMBOLS = [
     ("ist_bitmap_preview", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
     ("ist_debug_preview_launches", C.c_int64, []),
     ("ist_debug_preview_geometry", C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("ist_debug_png_grid", C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("ist_thumb_layout", C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(ThumbSpec), C.POINTER(ThumbItem), C.POINTER(C.c_int64)]),
     ("ist_thumbs_device", C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(ThumbSpec),
                                     C.c_void_p, C.c_int64, C.POINTER(ThumbItem), C.c_void_p]),

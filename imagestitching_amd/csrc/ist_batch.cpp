@@ -338,7 +338,9 @@ struct Pipeline {
       const int rc = png_batch_check(files[q], idx[q]);
       if (rc) { const std::string why = g_last_error; return fail(rc, "request " + std::to_string(idx[q]) + ": " + why); }
     }
-    int rc = ctx->png_level > 0 ? png_encode_batch_deflate(ctx, files, ctx->stream, true) : png_encode_batch_stored(ctx, files, ctx->stream, true);
+    int rc = ctx_png_form_check(ctx);
+    if (rc) return rc;
+    rc = ctx->png_level > 0 ? png_encode_batch_deflate(ctx, files, ctx->stream, true) : png_encode_batch_stored(ctx, files, ctx->stream, true);
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) {
       const size_t len = static_cast<size_t>(files[q].len);
@@ -415,6 +417,8 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
     } else if (out_len) {                                 // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
       const int64_t cw = out_plans[k].canvas_w, ch = out_plans[k].canvas_h;
       bytes[k] += static_cast<size_t>(ist_png_bound(cw, ch));
+      // (the RGBA chunk count whatever the context's colour form: the RGB form never has more chunks, and a budget that does not depend
+      // on the form cuts the same sub-batches for both)
       if (ctx->png_level > 0) bytes[k] += static_cast<size_t>(png_deflate_chunks(cw, ch) * png_deflate_slot_bytes());
     }
   }
@@ -454,6 +458,7 @@ int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_r
 int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_png, int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_png || !out_len))) return fail(IST_E_INVALID, "ist_stitch_png_batch: NULL argument");
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   return stitch_batch(ctx, reqs, n_reqs, out_plans, out_png, out_len);
 }
 

@@ -85,6 +85,7 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   PlanGuard pg{out_plan};
   const int64_t cw = out_plan->canvas_w, ch = out_plan->canvas_h;
   if (jpeg) { rc = jpeg_check_export("ist_stitch_bitmaps_jpeg", cw, ch, jpeg[0], jpeg[1]); if (rc) return rc; }
+  if (want_png) { rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");

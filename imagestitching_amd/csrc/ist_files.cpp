@@ -311,6 +311,7 @@ int ist_stitch_files_png_preview(ist_ctx* ctx, const uint8_t* const* files, cons
   const int rcp = preview_check(preview);
   if (rcp) return rcp;
   if (rc) return rc;
+  { const int rcf = ctx_png_form_check(ctx); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
   return stitch_files_png_locked(ctx, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
 }
@@ -329,6 +330,7 @@ int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths, int n_i
   const int rcp = preview_check(preview);
   if (rcp) return rcp;
   if (rc) return rc;
+  { const int rcf = ctx_png_form_check(ctx); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
   tl_begin();
   struct TlEnd { ~TlEnd() { tl_end("ist_stitch_paths_png"); } } tl_end_guard;
   std::lock_guard<std::mutex> lock(ctx->mu);

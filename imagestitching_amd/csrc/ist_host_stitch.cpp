@@ -235,6 +235,7 @@ int render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t c
                const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
                uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
   *out_png = nullptr; *out_len = 0;
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   int rc = render_png_banded(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len, preview);
@@ -366,6 +367,7 @@ int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int6
                          int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!pixels || !out_png || !out_len || w < 1 || h < 1 || pitch < static_cast<size_t>(w) * 4) return fail(IST_E_INVALID, "ist_png_encode_rgba8: bad argument");
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   const size_t row = static_cast<size_t>(w) * 4;

@@ -209,7 +209,7 @@ struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist
 struct KeepLastError { std::string msg = g_last_error; int code = g_last_code; ~KeepLastError() { g_last_error = msg; g_last_code = code; } };
 
 // PNG export, compressing form (ist_png_deflate.hip); ist_png_encode_device picks it when the context's level is > 0
-int64_t png_deflate_bound(int64_t w, int64_t h);
+int64_t png_deflate_bound(int64_t w, int64_t h, int color = IST_PNG_RGBA);   // (the RGBA bound holds for both colour forms)
 // host_out (pinned, out_cap bytes) + aux stream, both optional: the file also lands in host memory, slab by slab, while
 // later slabs are still being compressed
 // need_rows (optional): called with (y, s) before work that reads canvas rows [0, y) is submitted to stream s (`stream` or
@@ -220,6 +220,10 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
                               int64_t* out_len, void* stream, uint8_t* host_out, void* aux,
                               const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, void* stream2 = nullptr);
 int ctx_png_level(const ist_ctx* ctx);
+int ctx_png_color(const ist_ctx* ctx);                      // IST_PNG_RGBA / IST_PNG_RGB (ist_ctx_set_png_color)
+// IST_E_UNSUPPORTED for the one pair of settings no encoder serves: the stored form (level 0) in RGB.  Every *_png entry point
+// calls it before anything is enqueued, and so does every place that picks between the stored and the compressing encoder.
+int ctx_png_form_check(const ist_ctx* ctx);
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p);   // the context's grow-only PNG scratch (kept across calls)
 
 // ---- batch PNG export (ist_png_encode_batch_device, ist_stitch_png_batch) ----
@@ -233,7 +237,8 @@ struct PngBatchFile { const void* canvas; size_t pitch; int64_t w, h; uint8_t* o
 int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
 int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
 int png_batch_check(const PngBatchFile& f, int k);          // the rules of ist_png_encode_device for file k (message names it)
-int64_t png_deflate_chunks(int64_t w, int64_t h);           // chunks (= slots of SLOT bytes) of the compressing form
+int64_t png_deflate_chunks(int64_t w, int64_t h, int color = IST_PNG_RGBA);   // chunks (= slots of SLOT bytes) of the compressing form
+void png_deflate_grid(int64_t w, int64_t h, int color, int64_t out[4]);       // n_chunks, rows_per_chunk, pieces_per_row, piece_px
 int64_t png_deflate_slot_bytes();
 void count_png_batch_launch();
 

@@ -53,6 +53,7 @@ int ist_png_encode_batch_device(ist_ctx* ctx, const void* const* canvases, const
     const int rc = png_batch_check(f, k);
     if (rc) return rc;
   }
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
   const int rc = ctx_png_level(ctx) > 0 ? png_encode_batch_deflate(ctx, files, stream, false) : png_encode_batch_stored(ctx, files, stream, false);

@@ -222,7 +222,10 @@ __device__ __forceinline__ int walk_span(const uint32_t (&sp)[16], int n, const 
   return bits;
 }
 
-// One workgroup compresses chunk `chunk` of the canvas P describes (the body of both compressing kernels below).
+// One workgroup compresses chunk `chunk` of the canvas P describes (the body of the compressing kernels below).  BPP: bytes of a
+// pixel in the filtered stream - 4 (RGBA, colour type 6) or 3 (RGB, colour type 2: the canvas is still read a dword per pixel, the
+// alpha byte of the residual is not stored).  Only step A knows it; from step B on a chunk is bytes.
+template <int BPP>
 __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t chunk) {
   // ONE buffer, two lives: the filtered chunk (padded layout) until every thread has taken its span into registers, then the
   // Huffman scratch and the output bit stream
@@ -248,7 +251,7 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
     x0 = piece * P.piece_px; npr = static_cast<int>(min(static_cast<int64_t>(P.piece_px), P.w - x0));
   }
   const int hasf = x0 == 0 ? 1 : 0;
-  const int rowlen = hasf + 4 * npr;
+  const int rowlen = hasf + BPP * npr;
   const int len = rowlen * nrows;                // <= CH by construction
 
   for (int i = tid; i < 288; i += 256) { hist[i] = 0; clen[i] = 0; code[i] = 0; }
@@ -274,7 +277,7 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
           b[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x));
           if (x > 0) c[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x - 1));
         }
-        pos[u] = r * rowlen + hasf + 4 * xx;
+        pos[u] = r * rowlen + hasf + BPP * xx;
         first[u] = hasf && xx == 0;
         if (first[u]) filt[padpos(r * rowlen)] = 4;              // filter type of the row
       }
@@ -284,7 +287,7 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
       if (!on[u]) continue;
       const uint32_t fv = paeth4(cur[u], a[u], b[u], c[u]);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
+      for (int k = 0; k < BPP; ++k) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
     }
   }
   __syncthreads();
@@ -517,7 +520,15 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_kernel(const DeflArgs P) {
-  deflate_chunk(P, P.chunk0 + blockIdx.x);
+  deflate_chunk<4>(P, P.chunk0 + blockIdx.x);
+}
+// the RGB form (IST_PNG_RGB): the same body on 3 bytes per pixel.  amdgpu_waves_per_eu(5), not 7: under the 72-register cap of 7 waves
+// the body spills 16 VGPRs (68 bytes of private segment per thread, the 4-byte kernels' too); at 6 waves (80 registers) still 8; at 5 it
+// has 96 registers, no spill and no private segment.  The price is resident waves: measured 1.69-1.71 ms against 1.54-1.55 ms for the
+// spilling build on the 4032 x 27216 bench canvas (profiles/r13_png_rgb_waves.txt) - still below the RGBA form's 1.72-1.74 ms.  A body
+// that fits 72 registers would serve both forms; it is a change of steps B - E.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_rgb_kernel(const DeflArgs P) {
+  deflate_chunk<3>(P, P.chunk0 + blockIdx.x);
 }
 
 // ---- batch twins: the chunks of many canvases in ONE launch (png_encode_batch_deflate).  Chunks are numbered file-major;
@@ -545,7 +556,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void i
   P.tables = B.tables; P.xpow16 = B.xpow16;
   P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
   P.chunk0 = 0; P.dbg = nullptr;
-  deflate_chunk(P, g - base);
+  deflate_chunk<4>(P, g - base);
+}
+
+// the RGB form of the batch.  (Its own copy of the twelve lines above: shared through a function they compile to other code, and the
+// 4-byte kernel is to stay the code object it was.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_rgb_batch_kernel(const DeflBatchArgs B) {
+  const int64_t g = blockIdx.x;
+  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
+  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
+  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
+  DeflArgs P;
+  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
+  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
+  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
+  P.tables = B.tables; P.xpow16 = B.xpow16;
+  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
+  P.chunk0 = 0; P.dbg = nullptr;
+  deflate_chunk<3>(P, g - base);
 }
 
 struct GatherArgs { const uint8_t* slots; uint8_t* out; const int64_t* dst; const uint32_t* len16; int64_t chunk0; };
@@ -581,11 +609,15 @@ void put32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = (v >> 16) & 0xFF; p[
 
 struct ChunkGrid { int64_t n_chunks; int rows_per_chunk, pieces_per_row, piece_px; };
 
-ChunkGrid make_grid(int64_t w, int64_t h) {
+// bytes of a pixel in the filtered stream of a colour form (IST_PNG_RGBA / IST_PNG_RGB)
+int bpp_of(int color) { return color == IST_PNG_RGB ? 3 : 4; }
+
+ChunkGrid make_grid(int64_t w, int64_t h, int color) {
   ChunkGrid g{0, 0, 0, 0};
-  const int64_t R = 4 * w + 1;
+  const int bpp = bpp_of(color);
+  const int64_t R = bpp * w + 1;
   if (R <= CH) { g.rows_per_chunk = static_cast<int>(CH / R); g.n_chunks = (h + g.rows_per_chunk - 1) / g.rows_per_chunk; }
-  else { g.piece_px = (CH - 1) / 4; g.pieces_per_row = static_cast<int>((w + g.piece_px - 1) / g.piece_px); g.n_chunks = h * g.pieces_per_row; }
+  else { g.piece_px = (CH - 1) / bpp; g.pieces_per_row = static_cast<int>((w + g.piece_px - 1) / g.piece_px); g.n_chunks = h * g.pieces_per_row; }
   return g;
 }
 
@@ -622,13 +654,13 @@ struct FileLayout {
   std::vector<PngPatch>* patches = nullptr;
   FileLayout() : T(defl_tables().T), xpow(defl_tables().xpow), limit(idat_limit()) {}
   void feed(const uint8_t* p, int k) { for (int i = 0; i < k; ++i) reg = crc_byte(T, reg, p[i]); }
-  void header(int64_t w, int64_t h, std::vector<PngPatch>* out) {
+  void header(int64_t w, int64_t h, int color, std::vector<PngPatch>* out) {
     PngPatch pt; std::memset(&pt, 0, sizeof pt);
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     std::memcpy(pt.b, sig, 8);
     put32(pt.b + 8, 13); std::memcpy(pt.b + 12, "IHDR", 4);
     put32(pt.b + 16, static_cast<uint32_t>(w)); put32(pt.b + 20, static_cast<uint32_t>(h));
-    pt.b[24] = 8; pt.b[25] = 6; pt.b[26] = 0; pt.b[27] = 0; pt.b[28] = 0;
+    pt.b[24] = 8; pt.b[25] = color == IST_PNG_RGB ? 2 : 6; pt.b[26] = 0; pt.b[27] = 0; pt.b[28] = 0;
     uint32_t c = 0xFFFFFFFFu;
     for (int i = 12; i < 29; ++i) c = crc_byte(T, c, pt.b[i]);
     put32(pt.b + 29, c ^ 0xFFFFFFFFu);
@@ -696,9 +728,10 @@ struct FileLayout {
 
 }  // namespace
 
-// upper bound of the compressed form: every chunk stored
-int64_t png_deflate_bound(int64_t w, int64_t h) {
-  const ChunkGrid g = make_grid(w, h);
+// upper bound of the compressed form: every chunk stored.  (The RGB form never has more chunks than the RGBA one: the RGBA bound
+// - the one ist_png_bound reports - holds for both.)
+int64_t png_deflate_bound(int64_t w, int64_t h, int color) {
+  const ChunkGrid g = make_grid(w, h, color);
   const int64_t data = g.n_chunks * SLOT + 16;
   return kDataStart + data + (data / idat_limit() + 2) * 12 + 64;
 }
@@ -709,9 +742,11 @@ int64_t png_deflate_bound(int64_t w, int64_t h) {
 int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap,
                               int64_t* out_len, void* stream_, uint8_t* host_out, void* aux_,
                               const std::function<int(int64_t, void*)>& need_rows, int64_t slab_rows_hint, void* stream2_) {
-  const ChunkGrid g = make_grid(w, h);
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
+  const int color = ctx_png_color(ctx);
+  const ChunkGrid g = make_grid(w, h, color);
   if (g.n_chunks > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
-  if (png_deflate_bound(w, h) > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
+  if (png_deflate_bound(w, h, color) > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipStream_t aux = host_out ? static_cast<hipStream_t>(aux_) : stream;
   // slabs alternate between two streams (when the caller has a second one): consecutive kernels of ONE stream do not overlap,
@@ -811,7 +846,8 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     A.rows_per_chunk = g.rows_per_chunk; A.pieces_per_row = g.pieces_per_row; A.piece_px = g.piece_px;
     A.chunk0 = static_cast<int64_t>(c0);
     A.dbg = d_dbg;
-    hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
+    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     PNG_HIP(hipGetLastError());
     tl_mark("png:   compression launched, slab", static_cast<long>(s));
     PNG_HIP(hipEventCreateWithFlags(&evs.ev[s], hipEventDisableTiming));
@@ -826,7 +862,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   FileLayout lay;
   int64_t* const dst = dstp.p;
   std::vector<std::vector<PngPatch>> slab_patches(n_slabs);     // (all of them live until the final synchronisation)
-  lay.header(w, h, &slab_patches[0]);
+  lay.header(w, h, color, &slab_patches[0]);
   for (size_t s = 0; s < n_slabs; ++s) {
     const size_t c0 = slab_at[s], cn = slab_at[s + 1] - c0;
     if (s + 1 < n_slabs) { const int rc = compress(s + 1); if (rc) return rc; tl_mark("png: submitted the compression of slab", static_cast<long>(s + 1)); }
@@ -910,18 +946,24 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   return IST_OK;
 }
 
-int64_t png_deflate_chunks(int64_t w, int64_t h) { return make_grid(w, h).n_chunks; }
+int64_t png_deflate_chunks(int64_t w, int64_t h, int color) { return make_grid(w, h, color).n_chunks; }
+void png_deflate_grid(int64_t w, int64_t h, int color, int64_t out[4]) {
+  const ChunkGrid g = make_grid(w, h, color);
+  out[0] = g.n_chunks; out[1] = g.rows_per_chunk; out[2] = g.pieces_per_row; out[3] = g.piece_px;
+}
 int64_t png_deflate_slot_bytes() { return SLOT; }
 
 // The compressing form of a batch: every chunk of every file in ONE ist_png_deflate_batch_kernel launch, the host layout of
 // each file (FileLayout, as for one file), then every chunk of every file in ONE ist_png_gather_batch_kernel launch.
 int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
   const size_t nf = files.size();
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
+  const int color = ctx_png_color(ctx);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::vector<ChunkGrid> grid(nf);
   std::vector<int64_t> begin(nf + 1, 0);
   for (size_t k = 0; k < nf; ++k) {
-    grid[k] = make_grid(files[k].w, files[k].h);
+    grid[k] = make_grid(files[k].w, files[k].h, color);
     begin[k + 1] = begin[k] + grid[k].n_chunks;
   }
   if (begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
@@ -964,7 +1006,8 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   B.slots = scratch + o_slots;
   B.len16 = res; B.crc = res + n; B.ad_a = res + 2 * n; B.ad_b = res + 3 * n; B.ad_n = res + 4 * n;
   B.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); B.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
-  hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
+  if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
+  else hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
   PNG_HIP(hipGetLastError());
   count_png_batch_launch();
   PNG_HIP(hipStreamSynchronize(stream));
@@ -975,7 +1018,7 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
     const size_t c0 = static_cast<size_t>(begin[k]), cn = static_cast<size_t>(begin[k + 1] - begin[k]);
     FileLayout lay;
     f.patches.clear();
-    lay.header(f.w, f.h, &f.patches);
+    lay.header(f.w, f.h, color, &f.patches);
     const int rc = lay.slab(res + c0, res + n + c0, res + 2 * n + c0, res + 3 * n + c0, res + 4 * n + c0, cn, dst + c0,
                             static_cast<int64_t>(reinterpret_cast<uintptr_t>(f.out)), true, &f.patches);
     if (rc) { const std::string why = g_last_error; return fail(rc, "file " + std::to_string(k) + ": " + why); }

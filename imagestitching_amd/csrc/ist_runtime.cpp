@@ -22,6 +22,12 @@ using namespace ist;
 
 namespace ist {
 int ctx_png_level(const ist_ctx* ctx) { return ctx ? ctx->png_level : 0; }
+int ctx_png_color(const ist_ctx* ctx) { return ctx ? ctx->png_color : IST_PNG_RGBA; }
+int ctx_png_form_check(const ist_ctx* ctx) {
+  if (ctx && ctx->png_level == 0 && ctx->png_color == IST_PNG_RGB)
+    return fail(IST_E_UNSUPPORTED, "RGB PNG export needs the compressing encoder (pngLevel 1): the stored form writes RGBA only");
+  return IST_OK;
+}
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p) {
   const int rc = grow_device(&ctx->scratch_png, &ctx->scratch_png_bytes, need);
   *p = ctx->scratch_png;
@@ -94,6 +100,7 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
     };
   }
   const std::function<int(int64_t, void*)>& need_rows = preview ? with_preview : need_rows_in;
+  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int64_t cap = ist_png_bound(w, h);
   if (!dfile) {
     const int rc = grow_device(&ctx->scratch_file, &ctx->scratch_file_bytes, static_cast<size_t>(cap));
@@ -155,6 +162,19 @@ int ist_ctx_set_png_level(ist_ctx* ctx, int level) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (level < 0 || level > 1) return fail(IST_E_INVALID, "PNG level must be 0 (stored) or 1 (compressed)");
   ctx->png_level = level;
+  return IST_OK;
+}
+
+int ist_ctx_set_png_color(ist_ctx* ctx, int color) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (color != IST_PNG_RGBA && color != IST_PNG_RGB) return fail(IST_E_INVALID, "PNG colour must be IST_PNG_RGBA (0) or IST_PNG_RGB (1)");
+  ctx->png_color = color;
+  return IST_OK;
+}
+
+int ist_debug_png_grid(int64_t w, int64_t h, int color, int64_t out[4]) {
+  if (w < 1 || h < 1 || !out || (color != IST_PNG_RGBA && color != IST_PNG_RGB)) return fail(IST_E_INVALID, "ist_debug_png_grid: bad argument");
+  png_deflate_grid(w, h, color, out);
   return IST_OK;
 }
 

@@ -63,6 +63,7 @@ DEFAULT_OPTS = {
     "superSample": None,    # None: 1 when platform is None, reference rule (index.js:1363) otherwise
     "edgeAA": None,         # anti-alias fractional rectangle edges by area coverage (IST_FILTER_EDGE_AA); None: on iff `platform` is given (edge_aa_of)
     "pngLevel": None,       # PNG export form of the *_png / stitch_files calls: 0 stored, 1 compressed on the GPU; None = DEFAULT_PNG_LEVEL
+    "pngColor": None,       # PNG colour form of the same calls: 'rgba' (colour type 6) or 'rgb' (colour type 2: alpha is not read; level 1 only); None = 'rgba'
     "devices": None,        # list of GPU indices (devices[0] = root): shard the stitch over them from this one process (ist_stitch_rgba8_multi)
     "preview": None,        # (box_w, box_h): stitch_png / stitch_files also return the canvas shrunk to fit that box (the redraw into the preview
                             # node, index.js:1597-1603), as result['preview'], HxWx4 uint8.  Refused where no canvas stays in HBM behind an export.
@@ -74,6 +75,24 @@ DEFAULT_OPTS = {
 _SPLITS = {"image": L.SPLIT_IMAGE, "band": L.SPLIT_BAND, "rows": L.SPLIT_ROWS, "auto": L.SPLIT_AUTO}
 
 DEFAULT_PNG_LEVEL = 1
+PNG_COLORS = {"rgba": 0, "rgb": 1}           # IST_PNG_RGBA / IST_PNG_RGB
+
+
+def _png_color(color):
+    """IST_PNG_* of a pngColor / color= value (None: RGBA), checked before any library call"""
+    if color is None:
+        return PNG_COLORS["rgba"]
+    if not isinstance(color, str) or color not in PNG_COLORS:
+        raise ValueError("pngColor must be 'rgba' or 'rgb', not %r" % (color,))
+    return PNG_COLORS[color]
+
+
+def debug_png_grid(w, h, color="rgba"):
+    """(n_chunks, rows_per_chunk (0: pieces of a row), pieces_per_row, piece_px) of the compressing encoder's chunk grid for a w x h
+    canvas in a colour form (ist_debug_png_grid).  Pure CPU."""
+    out = (C.c_int64 * 4)()
+    L.check(L.lib.ist_debug_png_grid(int(w), int(h), _png_color(color), out))
+    return tuple(int(v) for v in out)
 
 
 def _limits(opts):
@@ -359,11 +378,14 @@ def _ctx(device=0):
     return c
 
 
-def _ctx_png(device, level):
-    """The context with its PNG export form set (ist_ctx_set_png_level): a per-context setting, so concurrent callers
-    that want different forms on one device should serialise."""
+def _ctx_png(device, level, color=None):
+    """The context with its PNG export form set (ist_ctx_set_png_level, ist_ctx_set_png_color - level and colour together, so a call
+    never inherits the colour of the one before it): a per-context setting, so concurrent callers that want different forms on one
+    device should serialise.  An unknown colour raises ValueError before the context is asked for."""
+    form = _png_color(color)
     c = _ctx(device)
     L.check(L.lib.ist_ctx_set_png_level(c, int(DEFAULT_PNG_LEVEL if level is None else level)))
+    L.check(L.lib.ist_ctx_set_png_color(c, form))
     return c
 
 
@@ -432,7 +454,7 @@ def _stitch(images, direction, o, device, kind, jpeg=()):
         devs = (C.c_int * len(o["devices"]))(*[int(d) for d in o["devices"]])
         name, head, mid = name + "_multi", (devs, len(devs)), (_SPLITS[o["split"]],)
     else:
-        head, mid = (_ctx_png(device, o["pngLevel"]) if kind == "png" else _ctx(device),), jpeg
+        head, mid = (_ctx_png(device, o["pngLevel"], o["pngColor"]) if kind == "png" else _ctx(device),), jpeg
     # (rgba8, what the N-API addon binds: plan, render, and the export as ONE DMA into a pinned block of the library's pool; the numpy
     # array below is a view of that block - no host copy - and returns it to the pool when it is garbage collected)
     fn = getattr(L.lib, name + ("_preview" if pv is not None else ""))
@@ -461,7 +483,7 @@ def stitch(images, direction, opts=None, device=0):
     return _stitch(images, direction, o, device, "rgba8")
 
 
-_BATCH_REFUSED = ("devices", "split", "pngLevel", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
+_BATCH_REFUSED = ("devices", "split", "pngLevel", "pngColor", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
 
 
 def _batch_requests(reqs, why):
@@ -518,17 +540,18 @@ def stitch_batch(requests, device=0):
     return _run_batch(L.lib.ist_stitch_rgba8_batch, _ctx(device), creqs)
 
 
-def stitch_png_batch(requests, device=0, level=None):
+def stitch_png_batch(requests, device=0, level=None, color=None):
     """Many independent stitch_png() calls in one go (ist_stitch_png_batch): stitch_batch with a PNG file in place of each
     canvas.  Every sub-batch is rendered by one launch per kernel form and encoded by ONE compression launch; only the files
-    cross PCIe.  requests as for stitch_batch (no per-request pngLevel: `level` chooses the form for the whole batch, 0 stored,
-    1 compressed, None = DEFAULT_PNG_LEVEL).  Returns a list of {'width', 'height', 'png': bytes}, with None for a request
+    cross PCIe.  requests as for stitch_batch (no per-request pngLevel or pngColor: `level` chooses the form for the whole batch, 0
+    stored, 1 compressed, None = DEFAULT_PNG_LEVEL, and `color` its colour form, 'rgba' or 'rgb' as opts['pngColor']).  Returns a list of {'width', 'height', 'png': bytes}, with None for a request
     without images; each file's zlib stream is stitch_png(*requests[k])['png']'s, byte for byte."""
     reqs = list(requests)
     if not reqs:
         return []
-    creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=")
-    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level), creqs, key="png")
+    _png_color(color)
+    creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=, color=")
+    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level, color), creqs, key="png")
 
 
 def launch_jobs(jobs, srcs, outs, stream=None):
@@ -683,6 +706,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     stitch launch -> PNG export on the GPU.  Only file bytes go in and PNG bytes come out over PCIe.
     Returns {'width','height','png'} and writes out_path when given.  The mini-program's whole onStitch: index.js:1441-1581."""
     o = _merge(opts)
+    _png_color(o["pngColor"])
     n = len(paths)
     if n == 0:
         return None
@@ -692,7 +716,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     cplan, out, ln = L.Plan(), C.POINTER(C.c_uint8)(), C.c_int64(0)
     pv = _preview_arg(o)
     fn = L.lib.ist_stitch_paths_png if pv is None else L.lib.ist_stitch_paths_png_preview
-    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
+    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"], o["pngColor"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
                                  *([] if pv is None else [C.byref(pv)]))), cplan)
     if size is None:
         return None
@@ -706,12 +730,14 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     return res
 
 
-def encode_png(pixels, device=0, level=None):
-    """Lossless PNG (colour type 6) of an HxWx4 uint8 array, encoded on the GPU (export step, utils/canvas.js:205-242).
-    level 0: stored deflate blocks; 1: Paeth + run-length + Huffman (ist_ctx_set_png_level)."""
+def encode_png(pixels, device=0, level=None, color=None):
+    """Lossless PNG of an HxWx4 uint8 array, encoded on the GPU (export step, utils/canvas.js:205-242).
+    level 0: stored deflate blocks; 1: Paeth + run-length + Huffman (ist_ctx_set_png_level).  color 'rgba' (default, colour type 6) or
+    'rgb' (colour type 2: alpha is not read; level 1 only - ist_ctx_set_png_color)."""
+    _png_color(color)
     a, ptr, pitch = _host_rows(_rgba(pixels))
     out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
+    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level, color), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
     return _take_png(out, n)
 
 
@@ -719,11 +745,15 @@ def stitch_png(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the reference's export: returns {'width','height','png': bytes}.  The
     canvas stays on the device; only the PNG crosses PCIe.  images are marshalled as stitch() marshals them (padded views are read
     where they are); they may be a list of Bitmaps."""
-    return _stitch(images, direction, _merge(opts), device, "png")
+    o = _merge(opts)
+    _png_color(o["pngColor"])
+    return _stitch(images, direction, o, device, "png")
 
 
-def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
-    """PNG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor) into a CUDA uint8 tensor; returns (tensor, length)."""
+def encode_png_device(canvas, out=None, stream=None, device=None, level=None, color=None):
+    """PNG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor) into a CUDA uint8 tensor; returns (tensor, length).
+    level, color: as encode_png."""
+    _png_color(color)
     import torch
     _check_canvas(canvas, "encode_png_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
@@ -731,7 +761,7 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None):
     st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
     n = C.c_int64(0)
     dev = canvas.device.index if device is None else device
-    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
+    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level, color), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
                                         C.c_void_p(dst), cap, C.byref(n), C.c_void_p(st.cuda_stream)))
     return out[off:off + n.value], n.value
 
@@ -850,11 +880,12 @@ def stitch_jpeg_batch(requests, device=0):
     return _run_batch(L.lib.ist_stitch_jpeg_batch, _ctx(device), creqs, (qs, ss), "jpeg")
 
 
-def encode_png_batch_device(canvases, outs=None, stream=None, level=None):
+def encode_png_batch_device(canvases, outs=None, stream=None, level=None, color=None):
     """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
     launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns
-    [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas."""
-    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level), "encode_png_batch_device", list(canvases),
+    [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas at the same level and color."""
+    _png_color(color)
+    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level, color), "encode_png_batch_device", list(canvases),
                                 lambda k, w, h: L.lib.ist_png_bound(w, h), outs, stream)
 
 

@@ -831,6 +831,20 @@ static napi_value js_set_png_level(napi_env env, napi_callback_info info) {
   napi_value v; napi_get_undefined(env, &v); return v;
 }
 
+/* setPngColor(color): 0 RGBA (colour type 6), 1 RGB (colour type 2, alpha not read; level 1 only) - ist_ctx_set_png_color; applies
+ * to every PNG this process exports afterwards */
+static napi_value js_set_png_color(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  int32_t color = 0;
+  if (argc < 1 || napi_get_value_int32(env, argv[0], &color) != napi_ok) { napi_throw_type_error(env, NULL, "setPngColor(color)"); return NULL; }
+  ist_ctx* ctx = get_ctx();
+  if (!ctx) { napi_throw(env, make_error(env, IST_E_NO_DEVICE, g_ctx_err)); return NULL; }
+  const int rc = ist_ctx_set_png_color(ctx, color);
+  if (rc < 0) return throw_ist(env, rc);
+  napi_value v; napi_get_undefined(env, &v); return v;
+}
+
 /* ---- resident bitmaps --------------------------------------------------------------------------------------------------- */
 typedef struct { ist_bitmap* b; } bitmap_ref;   /* NULL once released */
 
@@ -1219,6 +1233,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"encodePng", NULL, js_encode_png, NULL, NULL, NULL, napi_default, NULL},
       {"encodeJpeg", NULL, js_encode_jpeg, NULL, NULL, NULL, napi_default, NULL},
       {"setPngLevel", NULL, js_set_png_level, NULL, NULL, NULL, napi_default, NULL},
+      {"setPngColor", NULL, js_set_png_color, NULL, NULL, NULL, napi_default, NULL},
       {"decodePng", NULL, js_decode_png, NULL, NULL, NULL, napi_default, NULL},
       {"decodeImage", NULL, js_decode_image, NULL, NULL, NULL, napi_default, NULL},
       {"deviceCount", NULL, js_device_count, NULL, NULL, NULL, napi_default, NULL},

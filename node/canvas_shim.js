@@ -136,6 +136,7 @@ class ShimCanvas {
                                 bitmaps: bitmaps.map((b) => [b.width, b.height]) });
       return Buffer.alloc(Math.min((reg ? reg.w * reg.h : this._w * this._h) * 4, 1 << 16));   // placeholder pixels
     }
+    if (asPng) native.setPngColor(0);   // a Canvas may be translucent: its export keeps the alpha channel whatever a stitchPng call chose before
     return native.render(this._w, this._h, new Uint8Array([0, 0, 0, 0]), packed, bitmaps, (smoothing ? 1 : 0) | (this._env.edgeAA === false ? 0 : 0x100), reg, !!asPng);
   }
 }

@@ -44,7 +44,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'devices', 'split', 'preview'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'devices', 'split', 'preview'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -189,7 +189,7 @@ function stitchSync(images, direction, opts) {
   return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
-const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'preview'];
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'preview'];
 // the native arguments of request k of a batch, opts given apart (the JPEG batch takes its own two out first)
 function batchRequest(r, k, o) {
   for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
@@ -214,25 +214,27 @@ function stitchBatch(requests) {
 }
 function stitchBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchBatchSync(a) : []; }
 /** stitchBatch with the reference's export: resolves one {width, height, png: Buffer, plan} per request - the PNG stitchPng gives
- *  for it, in the form setPngLevel chose (a per-request pngLevel is refused) - and null for a request without images. The
- *  canvases never leave the GPU; one compression launch encodes every file of a sub-batch. */
-function stitchPngBatch(requests) {
+ *  for it, in the form setPngLevel / setPngColor chose or opts = {pngLevel, pngColor} chooses for the whole batch (a per-request
+ *  pngLevel or pngColor is refused) - and null for a request without images. The canvases never leave the GPU; one compression
+ *  launch encodes every file of a sub-batch. */
+function stitchPngBatch(requests, opts) {
   let a;
-  try { a = batchArgs(requests); } catch (e) { return Promise.reject(e); }
+  try { a = batchArgs(requests); pngColorOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a.length) return Promise.resolve([]);
+  try { pngForm(opts); } catch (e) { return Promise.reject(e); }
   return native.stitchPngBatch(a);
 }
-function stitchPngBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchPngBatchSync(a) : []; }
+function stitchPngBatchSync(requests, opts) { const a = batchArgs(requests); pngColorOf(opts); if (!a.length) return []; pngForm(opts); return native.stitchPngBatchSync(a); }
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
   let a, h, pv;
-  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); } catch (e) { return Promise.reject(e); }
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
   if (h) {
-    try { return withProgress(opts, () => { pngLevel(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true, ...pv); }); } catch (e) { return Promise.reject(e); }
+    try { return withProgress(opts, () => { pngForm(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true, ...pv); }); } catch (e) { return Promise.reject(e); }
   }
-  return withProgress(opts, () => { pngLevel(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
+  return withProgress(opts, () => { pngForm(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
 }
 // requests[k] of stitchJpegBatch -> [...what a batch request is, quality, subsampling]; every error names its request
 function jpegBatchArgs(requests) {
@@ -296,6 +298,21 @@ function encodeJpeg(data, width, height, opts) { const j = jpegArgs(opts); retur
  *  (photographs about half, screenshots a few per cent). A process-wide setting of the native context. */
 function pngLevel(opts) { if (opts && opts.pngLevel !== undefined && opts.pngLevel !== null) native.setPngLevel(opts.pngLevel | 0); }
 function setPngLevel(level) { native.setPngLevel(level | 0); }
+/** opts.pngColor: 'rgba' = colour type 6 (default), 'rgb' = colour type 2 - alpha is not read (every stitched canvas is opaque; a
+ *  caller with a translucent one composites it first), pngLevel 1 only: 12-17 per cent fewer bytes on photographs. A process-wide
+ *  setting of the native context, like pngLevel; an unknown value is a TypeError before any native call. */
+const PNG_COLOR = { rgba: 0, rgb: 1 };             // IST_PNG_RGBA / IST_PNG_RGB
+function pngColorOf(opts) {
+  if (!opts || opts.pngColor === undefined || opts.pngColor === null) return null;
+  if (typeof opts.pngColor !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_COLOR, opts.pngColor)) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
+  return PNG_COLOR[opts.pngColor];
+}
+function pngForm(opts) { pngLevel(opts); const c = pngColorOf(opts); if (c !== null) native.setPngColor(c); }
+function setPngColor(color) {
+  const c = pngColorOf({ pngColor: color });
+  if (c === null) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
+  native.setPngColor(c);
+}
 /** PNG file bytes -> {width, height, data} (RGBA8, straight alpha). Host decode: the Image.src step for 'png' inputs
  *  (utils/canvas.js:27-121; SUPPORTED_IMAGE_TYPES, index.js:4). JPEG / WebP / HEIC are not built: err.code '-7'. */
 function decodePng(file) { return native.decodePng(file); }
@@ -309,20 +326,21 @@ async function stitchFiles(paths, direction, opts, outPath) {
   const fs = require('fs');
   const a = args([], direction, opts);
   const pv = previewArgs(opts);
+  pngColorOf(opts);
   if (!paths || !paths.length) return null;
   const files = paths.map((p) => fs.readFileSync(p));
   // one native call: Huffman / inflate on host threads, reconstruction + stitch + PNG on the GPU, buffers stay in HBM
-  const res = await withProgress(opts, () => { pngLevel(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5], ...pv); });
+  const res = await withProgress(opts, () => { pngForm(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5], ...pv); });
   if (res && outPath) fs.writeFileSync(outPath, res.png);
   return res;
 }
 /** Lossless PNG of RGBA8 pixels, encoded on the GPU. */
-function encodePng(data, width, height, opts) { pngLevel(opts); return native.encodePng(data, width, height); }
+function encodePng(data, width, height, opts) { pngForm(opts); return native.encodePng(data, width, height); }
 function plan(images, direction, opts) {
   bitmapHandles(images, opts);                        // (the all-or-none rule; a Bitmap carries the fields the planner reads)
   const a = args(images, direction, opts);
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, decodePng, decodeImage, plan,
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, decodePng, decodeImage, plan,
                    decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
