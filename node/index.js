@@ -89,14 +89,14 @@ function withProgress(opts, run) {
   return run().then((r) => { cb(90); cb(96); cb(100); return r; }, (e) => { cb(0); throw e; });       // failure resets to 0 (:1622)
 }
 
-// opts.devices -> the trailing (asPng, devices, split) arguments of the native call
+// opts.devices -> the (devices, split) arguments that follow asPng in the native call ([] without a device group)
 function groupArgs(opts) {
   const o = opts || {};
   if (o.devices === undefined || o.devices === null) return [];
   if (!Array.isArray(o.devices) || !o.devices.length || !o.devices.every((d) => Number.isInteger(d) && d >= 0)) throw new TypeError('devices must be a non-empty array of GPU indices');
   const split = o.split || 'auto';
   if (!(split in SPLIT)) throw new TypeError('unknown split ' + split);
-  return [false, o.devices, SPLIT[split]];
+  return [o.devices, SPLIT[split]];
 }
 // opts.preview -> the trailing (previewWidth, previewHeight) arguments of a native PNG call ([] without one)
 function previewArgs(opts) {
@@ -171,22 +171,27 @@ function thumbnails(bitmaps, cell) {
 /** device bytes held by the live bitmaps of this process */
 function debugBitmapBytes() { return native.debugBitmapBytes(); }
 
+// One stitch through the native call of its sources: the handles h of a Bitmap request, or (h null) the host images of a = args().
+// asPng is the native argument of that name (false, true, or the JPEG export's {quality, subsampling}), rest what follows it for host
+// images, pv = previewArgs(opts); before (pngForm) runs inside the progress, ahead of the call.
+function runStitch(opts, h, a, asPng, rest, pv, before) {
+  const run = () => { if (before) before(); return h ? native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], asPng, ...pv) : native.stitch(...a, asPng, ...rest, ...pv); };
+  if (!h) return withProgress(opts, run);
+  // (the native call retains every bitmap before it returns: a release() from here on does not free one under the stitch)
+  try { return withProgress(opts, run); } catch (e) { return Promise.reject(e); }      // (a released Bitmap throws on this thread)
+}
 function stitch(images, direction, opts) {
-  let a, h;
-  try { noPreview(opts, 'stitch'); h = bitmapHandles(images, opts); a = args(images, direction, opts).concat(h ? [] : groupArgs(opts)); } catch (e) { return Promise.reject(e); }
+  let a, h, g;
+  try { noPreview(opts, 'stitch'); h = bitmapHandles(images, opts); a = args(images, direction, opts); g = h ? [] : groupArgs(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);      // `if (!originalImages.length) return;` (index.js:1189): no progress, no error
-  if (h) {
-    // (the native call retains every bitmap before it returns: a release() from here on does not free one under the stitch)
-    try { return withProgress(opts, () => native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], false)); } catch (e) { return Promise.reject(e); }
-  }
-  return withProgress(opts, () => native.stitch(...a));
+  return runStitch(opts, h, a, false, g, []);
 }
 function stitchSync(images, direction, opts) {
   noPreview(opts, 'stitchSync');
   const h = bitmapHandles(images, opts);
-  const a = args(images, direction, opts).concat(h ? [] : groupArgs(opts));
+  const a = args(images, direction, opts), g = h ? [] : groupArgs(opts);
   if (!a[0].length) return null;
-  return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a);
+  return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a, false, ...g);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
 const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'preview'];
@@ -196,13 +201,15 @@ function batchRequest(r, k, o) {
   if (Array.isArray(r.images) && r.images.some((x) => x instanceof Bitmap)) throw new TypeError('request ' + k + ': Bitmaps do not apply to a batch');
   return args(r.images, r.direction, o);
 }
-function batchArgs(requests) {
+// the requests of a batch, each turned into its native arguments by one(r, k)
+function eachRequest(requests, one) {
   if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
   return requests.map((r, k) => {
     if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
-    return batchRequest(r, k, r.opts || {});
+    return one(r, k);
   });
 }
+function batchArgs(requests) { return eachRequest(requests, (r, k) => batchRequest(r, k, r.opts || {})); }
 /** Many independent stitches in one call (one GPU): resolves an array with one {width, height, data, plan} per request
  *  - the same bytes stitchSync returns for it - and null for a request without images.  Each request is one onStitch
  *  (index.js:1186-1633); their canvases are rendered by one kernel launch per kernel form. */
@@ -231,16 +238,11 @@ function stitchPng(images, direction, opts) {
   let a, h, pv;
   try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
-  if (h) {
-    try { return withProgress(opts, () => { pngForm(opts); return native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], true, ...pv); }); } catch (e) { return Promise.reject(e); }
-  }
-  return withProgress(opts, () => { pngForm(opts); return pv.length ? native.stitch(...a, true, null, 0, ...pv) : native.stitch(...a, true); });
+  return runStitch(opts, h, a, true, pv.length ? [null, 0] : [], pv, () => pngForm(opts));      // (no devices, split 0 ahead of the preview box)
 }
 // requests[k] of stitchJpegBatch -> [...what a batch request is, quality, subsampling]; every error names its request
 function jpegBatchArgs(requests) {
-  if (!Array.isArray(requests)) throw new TypeError('requests must be an array of {images, direction, opts?}');
-  return requests.map((r, k) => {
-    if (!r || typeof r !== 'object') throw new TypeError('request ' + k + ' must be {images, direction, opts?}');
+  return eachRequest(requests, (r, k) => {
     const o = Object.assign({}, r.opts || {});
     try {
       const j = jpegArgs(o); delete o.quality; delete o.subsampling; delete o.optimize;
@@ -287,10 +289,7 @@ function stitchJpeg(images, direction, opts) {
     h = bitmapHandles(images, o); a = args(images, direction, o);
   } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
-  if (h) {
-    try { return withProgress(opts, () => native.stitchBitmaps(h, a[1], a[2], a[3], a[4], a[5], j)); } catch (e) { return Promise.reject(e); }
-  }
-  return withProgress(opts, () => native.stitch(...a, j));
+  return runStitch(opts, h, a, j, [], []);
 }
 /** Baseline JFIF file of RGBA8 pixels, encoded on the GPU: encodeJpeg(data, width, height, {quality, subsampling}). Synchronous. */
 function encodeJpeg(data, width, height, opts) { const j = jpegArgs(opts); return native.encodeJpeg(data, width, height, j.quality, j.subsampling); }
