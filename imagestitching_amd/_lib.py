@@ -105,6 +105,11 @@ class ThumbItem(C.Structure):
                 ("src_h", C.c_int32), ("turn", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
+class JpegCoefInfo(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("launches", C.c_int32), ("ncomp", C.c_int32), ("reserved", C.c_int32),
+                ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3)]
+
+
 # every symbol include/imagestitch.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ist_abi_version", C.c_int, []),
@@ -112,6 +117,8 @@ SYMBOLS = [
     ("ist_device_count", C.c_int, []),
     ("ist_debug_device_allocs", C.c_int64, []),
     ("ist_debug_gpu_entropy_files", C.c_int64, []),
+    ("ist_debug_gpu_entropy_sync_launches", C.c_int64, []),
+    ("ist_debug_jpeg_gpu_coefficients", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(JpegCoefInfo)]),
     ("ist_debug_direct_images", C.c_int64, []),
     ("ist_debug_host_sink_stitches", C.c_int64, []),
     ("ist_debug_flat_launches", C.c_int64, []),

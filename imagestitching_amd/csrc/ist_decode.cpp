@@ -20,6 +20,7 @@ using namespace ist;
 
 namespace {
 std::atomic<int64_t> g_gpu_entropy_files{0};
+std::atomic<int64_t> g_gpu_entropy_sync_launches{0};
 
 // ---- JPEG decode: entropy decoding on the host, reconstruction on the GPU (ist_jpeg.cpp / ist_jpeg_kernels.hip) ----------
 void jpeg_layout(const JpegImage& J, size_t* off, JpegDevLayout* L) {
@@ -333,7 +334,9 @@ int FileDecoder::huffman_all(hipStream_t consumer) {
     items.push_back(it); who.push_back(i);
   }
   std::vector<uint8_t> okv;
-  rc = jpeg_gpu_entropy_decode(items, &okv, consumer, &ctx_->scratch_huff, &ctx_->scratch_huff_bytes);
+  int launches = 0;
+  rc = jpeg_gpu_entropy_decode(items, &okv, consumer, &ctx_->scratch_huff, &ctx_->scratch_huff_bytes, &launches);
+  g_gpu_entropy_sync_launches.fetch_add(launches, std::memory_order_relaxed);
   if (rc) return rc;
   for (size_t q = 0; q < who.size(); ++q) {
     on_gpu_[static_cast<size_t>(who[q])] = okv[q] ? 1 : 0;
@@ -439,6 +442,50 @@ int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t
 extern "C" {
 
 int64_t ist_debug_gpu_entropy_files(void) { return g_gpu_entropy_files.load(std::memory_order_relaxed); }
+int64_t ist_debug_gpu_entropy_sync_launches(void) { return g_gpu_entropy_sync_launches.load(std::memory_order_relaxed); }
+
+// The GPU entropy decoder's coefficients of ONE file, read back: the same parse, the same jpeg_gpu_entropy_decode and the same dense
+// planes the file pipeline hands to the reconstruction kernels - minus the reconstruction.  A file the decoder hands back (ok = 0)
+// leaves the caller's planes untouched.
+int ist_debug_jpeg_gpu_coefficients(ist_ctx* ctx, const uint8_t* file, int64_t len, int16_t* const* planes, const int64_t* plane_elems,
+                                    ist_jpeg_coef_info* info) {
+  if (!file || len <= 0 || !info || (planes && !plane_elems)) return fail(IST_E_INVALID, "ist_debug_jpeg_gpu_coefficients: bad argument");
+  std::memset(info, 0, sizeof *info);
+  JpegImage J;
+  JpegGpuScan G;
+  int rc = jpeg_parse_and_entropy_decode(file, len, &J, false, &G);
+  if (rc) return rc;
+  if (!G.eligible) return fail(IST_E_UNSUPPORTED, "ist_debug_jpeg_gpu_coefficients: not a file the GPU entropy decoder takes");
+  info->ncomp = J.ncomp;
+  for (int c = 0; c < J.ncomp; ++c) { info->blocks_x[c] = J.comp[c].blocks_x; info->blocks_y[c] = J.comp[c].blocks_y; }
+  if (!planes) return IST_OK;                           // the geometry only: what the caller sizes its planes from
+  size_t off = 0, o_coef[3] = {0, 0, 0}, nblk[3] = {0, 0, 0};
+  for (int c = 0; c < J.ncomp; ++c) {
+    nblk[c] = static_cast<size_t>(J.comp[c].blocks_x) * J.comp[c].blocks_y;
+    if (!planes[c] || plane_elems[c] < 0 || static_cast<uint64_t>(plane_elems[c]) < nblk[c] * 64) return fail(IST_E_INVALID, "ist_debug_jpeg_gpu_coefficients: plane " + std::to_string(c) + " is too small");
+    o_coef[c] = arena_take(&off, nblk[c] * 128);
+  }
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  rc = grow_device(&ctx->scratch_arena, &ctx->scratch_arena_bytes, off);
+  if (rc) return rc;
+  uint8_t* d = static_cast<uint8_t*>(ctx->scratch_arena);
+  JpegGpuItem it; it.J = &J; it.S = &G;
+  for (int c = 0; c < 3; ++c) it.d_coef[c] = c < J.ncomp ? reinterpret_cast<int16_t*>(d + o_coef[c]) : nullptr;
+  std::vector<JpegGpuItem> items(1, it);
+  std::vector<uint8_t> okv;
+  int launches = 0;
+  rc = jpeg_gpu_entropy_decode(items, &okv, ctx->stream, &ctx->scratch_huff, &ctx->scratch_huff_bytes, &launches);
+  g_gpu_entropy_sync_launches.fetch_add(launches, std::memory_order_relaxed);
+  if (rc) return rc;
+  info->launches = launches;
+  info->ok = !okv.empty() && okv[0] ? 1 : 0;
+  if (info->ok)
+    for (int c = 0; c < J.ncomp; ++c) IST_HIP(hipMemcpyAsync(planes[c], d + o_coef[c], nblk[c] * 128, hipMemcpyDeviceToHost, ctx->stream));
+  IST_HIP(hipStreamSynchronize(ctx->stream));           // nothing of this call may still read the arena when the next call reuses it
+  return IST_OK;
+}
 
 int ist_ctx_set_timing(ist_ctx* ctx, int on) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");

@@ -691,8 +691,9 @@ __global__ __launch_bounds__(kWriteThreads) void ist_jpeg_write_kernel(const Wri
 
 }  // namespace
 
-int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream_, void** scratch, size_t* scratch_bytes) {
+int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream_, void** scratch, size_t* scratch_bytes, int* launches) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (launches) *launches = 0;
   const size_t n_img = items.size();
   static const bool timing = std::getenv("IST_TIMING") != nullptr;
   auto t_prev = std::chrono::steady_clock::now();
@@ -880,6 +881,7 @@ int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<u
     tl_mark("huffman: synchronisation launch done, pass", static_cast<long>(pass));
     if (!*h_flag) { converged = true; break; }
   }
+  if (launches) *launches = passes_run;
   if (timing) std::fprintf(stderr, "[ist timing] GPU Huffman: %d subsequences of %d bits, %s after %d launches\n", ns, kSubBits, converged ? "fixed point" : "NO fixed point", passes_run);
   if (!converged) { JG_HIP(hipStreamSynchronize(stream)); return IST_OK; }      // every ok[] stays 0: the host decodes
   lap("sync passes");

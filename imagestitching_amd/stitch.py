@@ -686,6 +686,19 @@ def decode_files_device(blobs, device=0, out=None):
     return out, imgs
 
 
+def debug_jpeg_gpu_coefficients(blob, device=0):
+    """The GPU Huffman decoder's coefficients of one file (ist_debug_jpeg_gpu_coefficients): {'ok', 'launches', 'planes'}, planes =
+    one blocks_y x blocks_x x 64 int16 array per component (natural order, DC integrated, not dequantised), None when the decoder
+    handed the file back (ok False).  Raises StitchError(-7) for a file the GPU decoder does not take."""
+    info = L.JpegCoefInfo()
+    L.check(L.lib.ist_debug_jpeg_gpu_coefficients(None, blob, len(blob), None, None, C.byref(info)))
+    planes = [np.zeros((info.blocks_y[c], info.blocks_x[c], 64), np.int16) for c in range(info.ncomp)]
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
+    elems = (C.c_int64 * 3)(*[p.size for p in planes])
+    L.check(L.lib.ist_debug_jpeg_gpu_coefficients(_ctx(device), blob, len(blob), ptrs, elems, C.byref(info)))
+    return {"ok": bool(info.ok), "launches": int(info.launches), "planes": planes if info.ok else None}
+
+
 PHASES = ("host_decode", "plan_arena", "entropy_gpu", "reconstruct", "stitch", "png", "d2h")
 
 

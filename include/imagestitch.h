@@ -144,6 +144,23 @@ IST_API int64_t ist_debug_device_allocs(void);
 /* JPEG files whose entropy-coded scan the GPU Huffman decoder has decoded AND validated in this process so far (files it
  * handed back to the host decoder do not count).  Tests use it to tell the GPU path from the silent host fall-back. */
 IST_API int64_t ist_debug_gpu_entropy_files(void);
+/* synchronisation launches the GPU Huffman decoder has made in this process so far, summed over its calls (one call decodes a whole
+ * batch of files: its launches are those of the file that settles last).  Two per call is the floor; a file whose MCU slots all share
+ * both Huffman tables takes about one per 48 subsequences of 1024 bits, 64 at the most. */
+IST_API int64_t ist_debug_gpu_entropy_sync_launches(void);
+/* The GPU Huffman decoder's coefficients of ONE file, read back (a test aid: pixels cannot tell a wrong coefficient that the IDCT's
+ * clamp hides).  The file is parsed and decoded alone, exactly as the file pipeline would, and the dense planes the reconstruction
+ * kernels read - blocks_y * blocks_x * 64 int16 per component, natural order, DC integrated, not dequantised - are copied to
+ * planes[c] (plane_elems[c] = the int16 each can hold).  info: ok = 1 when the decoder validated the file (0: it would be handed to
+ * the host decoder; the planes are left untouched), launches = its synchronisation launches, and the plane geometry.  planes = NULL
+ * fills the geometry only and needs neither a context nor a device.  IST_E_UNSUPPORTED: not a file the GPU decoder takes
+ * (progressive, several scans, more than two tables of a class, too many restart intervals). */
+typedef struct ist_jpeg_coef_info {
+  int32_t ok, launches, ncomp, reserved;
+  int32_t blocks_x[3], blocks_y[3];
+} ist_jpeg_coef_info;
+IST_API int ist_debug_jpeg_gpu_coefficients(ist_ctx* ctx, const uint8_t* file, int64_t len, int16_t* const* planes, const int64_t* plane_elems,
+                                            ist_jpeg_coef_info* info);
 /* images the file pipeline has reconstructed STRAIGHT INTO the canvas so far (a draw that only moves an opaque image: no bitmap of
  * its own, no stitch launch for it).  Tests use it to tell that path from the general one, which makes the same pixels. */
 IST_API int64_t ist_debug_direct_images(void);

@@ -347,7 +347,7 @@ def _seg(marker, payload, fill):
 
 
 def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None, ac_slots=None, restart=0, fill=0,
-               noise=False, tables="front", seed=0):
+               noise=False, tables="front", seed=0, trace=None):
     """Entropy-code a Frame.
 
     sof: 0 (baseline) or 1 (extended sequential: 16-bit quantisation tables where a value exceeds 255).
@@ -360,6 +360,8 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
     noise: COM and APPn segments between scans, bytes behind EOI.
     tables: 'front' (every DQT / DHT before the frame) or 'scan' (each scan's tables just in front of it: quantisation
     tables appear right before a component's first scan, Huffman slots are redefined per scan when their content changes).
+    trace: a list that receives, per scan, what was coded (tests/jpeg_sync_model.py works from it): the _symbols events, the
+    length in bits of every event (code or magnitude bits), the event index where each restart interval starts, and the slots.
     """
     n = len(f.comps)
     scans = scans or [list(range(n))]
@@ -447,6 +449,9 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
             assert np.all(ln[sym[m]] > 0), "symbol without a code"
             codes[m], lens[m] = cd[sym[m]], ln[sym[m]]
         bounds = np.searchsorted(iv, np.arange(n_iv + 1))
+        if trace is not None:
+            trace.append({"comps": list(cs), "cls": cls, "comp": comp, "sym": sym, "lens": lens.copy(), "bounds": bounds,
+                          "dc_slots": tuple(dc_slots), "ac_slots": tuple(ac_slots)})
         for k in range(n_iv):
             if k:
                 out += b"\xff" * fill + bytes([0xFF, 0xD0 + (k - 1) % 8])

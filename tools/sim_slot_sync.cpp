@@ -73,6 +73,7 @@ int main(int argc, char** argv) {
   truth[0] = S;
   for (int i = 0; i < nsub; ++i) { S = run(S, std::min<int64_t>((i + 1) * SUB, G.bits)); truth[static_cast<size_t>(i) + 1] = S; }
   long same = 0, pz_only = 0, diff = 0, g_ok = 0, g_pz = 0, g_bad = 0;
+  int worst_a_out = 0;
   for (int i = 1; i + 1 < nsub; i += 3) {
     const int64_t lim = (i + 1) * SUB;
     const St& T1 = truth[static_cast<size_t>(i) + 1];
@@ -155,12 +156,88 @@ int main(int argc, char** argv) {
         hist_b[static_cast<size_t>(std::min(passes, 63))]++; worst_b = std::max(worst_b, passes);
       }
     }
+    worst_a_out = worst_a;
     std::printf("passes a workgroup needs (first launch; %d subsequences + %d ghost lanes per workgroup): one hypothesis: worst %d, two hypotheses: worst %d\n", WG, GH, worst_a, worst_b);
     std::printf("  histogram, one hypothesis :");
     for (int k = 0; k < 64; ++k) if (hist_a[static_cast<size_t>(k)]) std::printf(" %d:%d", k, hist_a[static_cast<size_t>(k)]);
     std::printf("\n  histogram, two hypotheses:");
     for (int k = 0; k < 64; ++k) if (hist_b[static_cast<size_t>(k)]) std::printf(" %d:%d", k, hist_b[static_cast<size_t>(k)]);
     std::printf("\n");
+  }
+  // ---- how many LAUNCHES does the host loop make?  The whole synchronisation replayed: 48 inner passes per workgroup and launch, ghost
+  // lanes in the first launch only, later launches from the exit states and start states the previous one left, the first lane of a
+  // workgroup from its left neighbour's exit of the PREVIOUS launch, and the kernel's flag rule - a launch is not the fixed point when
+  // a workgroup ran out of inner passes or the exit of its last lane moved.  The checkpoint is replayed too (the state kCheckBits = 256 bits
+  // into the subsequence, kept from the last full decode, across launches): a re-decode that arrives there in the recorded state keeps
+  // the old exit - checked here against decoding on - and those that do so in a LATER launch than the one that recorded it are counted:
+  // they are the ones whose tally is "new first leg + old second leg" from state that crossed a launch.  A workgroup that needs more than 48 passes makes the SECOND launch do real work; a third one
+  // follows only when that work reaches a workgroup's last lane.
+  int launches = 0, carried_hits = 0; bool fixed_point = false;
+  std::string carried_at;
+  {
+    const int WG = 128, GH = 8, INNER = 48, MAXL = 64;
+    auto eq = [](const St& a, const St& b) { return a.p == b.p && a.c == b.c && a.z == b.z; };
+    const size_t N = static_cast<size_t>(nsub);
+    std::vector<St> prev(N), out(N), start(N), ck(N);
+    for (int L = 0; L < MAXL && !fixed_point; ++L) {
+      bool changed = false;
+      for (int g0 = 0; g0 < nsub; g0 += WG) {
+        const int n_ghost = L == 0 ? std::min(GH, g0) : 0;
+        const int first = g0 - n_ghost, last = std::min(nsub, g0 + WG), n = last - first;          // lanes [first, last): ghosts, then owned
+        std::vector<St> st(static_cast<size_t>(n)), my(static_cast<size_t>(n)), ex(static_cast<size_t>(n));
+        std::vector<char> have(static_cast<size_t>(n), 0), ck_old(static_cast<size_t>(n), 0);
+        std::vector<St> ckl(static_cast<size_t>(n));
+        bool any = true;
+        if (L > 0) {
+          any = false;
+          for (int e = 0; e < n; ++e) {
+            const size_t g = static_cast<size_t>(first + e);
+            st[static_cast<size_t>(e)] = start[g]; my[static_cast<size_t>(e)] = prev[g]; have[static_cast<size_t>(e)] = 1;
+            ckl[static_cast<size_t>(e)] = ck[g]; ck_old[static_cast<size_t>(e)] = 1;
+            if (g != 0 && !eq(start[g], prev[g - 1])) any = true;
+          }
+        }
+        bool settled = !any;
+        for (int it = 0; any && it < INNER; ++it) {
+          bool redo_any = false;
+          std::vector<St> nmy = my;
+          for (int e = 0; e < n; ++e) {
+            const int i = first + e;
+            St sp{0, 0, 0};
+            if (i != 0) {
+              if (L == 0) sp = (it == 0 || e == 0) ? St{static_cast<int64_t>(i) * SUB, 0, 0} : ex[static_cast<size_t>(e) - 1];
+              else sp = (it == 0 || e == 0) ? prev[static_cast<size_t>(i) - 1] : ex[static_cast<size_t>(e) - 1];
+            }
+            if (have[static_cast<size_t>(e)] && eq(st[static_cast<size_t>(e)], sp)) continue;
+            const int64_t limit = std::min<int64_t>((static_cast<int64_t>(i) + 1) * SUB, G.bits);
+            const St mid = run(sp, std::min<int64_t>(static_cast<int64_t>(i) * SUB + 256, limit));
+            if (have[static_cast<size_t>(e)] && eq(mid, ckl[static_cast<size_t>(e)])) {              // in step with the last full decode: its exit stands
+              if (!eq(run(mid, limit), my[static_cast<size_t>(e)])) { std::printf("the checkpoint rule broke at subsequence %d\n", i); return 3; }
+              if (ck_old[static_cast<size_t>(e)]) { ++carried_hits; carried_at += (carried_at.empty() ? "" : ",") + std::to_string(i); }
+            } else {
+              ckl[static_cast<size_t>(e)] = mid; ck_old[static_cast<size_t>(e)] = 0;
+              nmy[static_cast<size_t>(e)] = run(mid, limit);
+            }
+            st[static_cast<size_t>(e)] = sp; have[static_cast<size_t>(e)] = 1; redo_any = true;
+          }
+          my = nmy; ex = my;
+          if (!redo_any) { settled = true; break; }
+        }
+        for (int e = n_ghost; e < n; ++e) {
+          const size_t g = static_cast<size_t>(first + e);
+          const bool is_last = e - n_ghost == WG - 1 || first + e + 1 == nsub;
+          if (!settled || (is_last && !eq(prev[g], my[static_cast<size_t>(e)]))) changed = true;
+          out[g] = my[static_cast<size_t>(e)]; start[g] = st[static_cast<size_t>(e)]; ck[g] = ckl[static_cast<size_t>(e)];
+        }
+      }
+      prev = out;
+      launches = L + 1;
+      if (L > 0 && !changed) fixed_point = true;
+    }
+    bool exact = fixed_point;
+    for (int i = 0; exact && i < nsub; ++i) exact = eq(prev[static_cast<size_t>(i)], truth[static_cast<size_t>(i) + 1]);
+    std::printf("host loop replayed: %d launches, %d re-decodes met a checkpoint recorded in an earlier launch, %s%s\n", launches, carried_hits, fixed_point ? "fixed point" : "NO fixed point", fixed_point && !exact ? " - BUT NOT THE TRUE STATES" : "");
+    if (fixed_point && !exact) return 3;
   }
   // ---- loop trips of a counting pass if ONE look-up resolved up to two AC symbols (an index of W bits holding both codes and their magnitude
   // bits; never across a block end; the first symbol of a block - DC - always alone): trips per symbol along the true path of the scan
@@ -183,7 +260,10 @@ int main(int argc, char** argv) {
                   static_cast<double>(G.bits) / syms.size());
     }
   }
-  const double t = static_cast<double>(same + pz_only + diff), tg = static_cast<double>(g_ok + g_pz + g_bad);
+  const double t = std::max(1.0, static_cast<double>(same + pz_only + diff)), tg = std::max(1.0, static_cast<double>(g_ok + g_pz + g_bad));
+  // one machine-readable line (tests/test_jpeg_sync_model.py): worst_passes = the replay's cap means "did not settle in one launch"
+  std::printf("SYNC nsub=%d slots=%d worst_passes=%d pass_cap=64 launches=%d fixed_point=%d carried_checkpoint_hits=%d at=[%s] slot_wrong_exit_slot_wrong=%.3f guess_exit_true=%.3f\n", nsub, G.slots, worst_a_out, launches,
+              fixed_point ? 1 : 0, carried_hits, carried_at.c_str(), pz_only / t, g_ok / tg);
   std::printf("%d subsequences of %lld bits, %d blocks per MCU\n", nsub, static_cast<long long>(SUB), G.slots);
   std::printf("start = true (position, index), wrong slot:   exit true %.3f | slot wrong only %.3f | elsewhere %.3f\n", same / t, pz_only / t, diff / t);
   std::printf("start = guess (block at the boundary, slot 0): exit true %.3f | slot wrong only %.3f | elsewhere %.3f\n", g_ok / tg, g_pz / tg, g_bad / tg);
