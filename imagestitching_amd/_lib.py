@@ -116,6 +116,7 @@ SYMBOLS = [
     ("ist_last_error", C.c_char_p, []),
     ("ist_device_count", C.c_int, []),
     ("ist_debug_device_allocs", C.c_int64, []),
+    ("ist_debug_live_handles", C.c_int, [C.POINTER(C.c_int64)]),
     ("ist_debug_gpu_entropy_files", C.c_int64, []),
     ("ist_debug_gpu_entropy_sync_launches", C.c_int64, []),
     ("ist_debug_jpeg_gpu_coefficients", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(JpegCoefInfo)]),

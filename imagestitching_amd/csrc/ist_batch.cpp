@@ -50,23 +50,12 @@ int batch_take_slot(ist_ctx* ctx, size_t bytes, ist_ctx::BatchSlot** out) {
     if (hipEventSynchronize(s.done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier batch failed"); }
     s.pending = false;
   }
-  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError(); s.done = nullptr;
-    return fail(IST_E_HIP, "hipEventCreate failed");
-  }
-  if (s.bytes < bytes) {
-    if (s.host) (void)hipHostFree(s.host);
-    dev_free(s.dev);
-    s.host = nullptr; s.dev = nullptr; s.bytes = 0;
-    size_t want = size_t(64) << 10;
-    while (want < bytes) want <<= 1;
-    if (hipHostMalloc(&s.host, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.host = nullptr; return fail(IST_E_NOMEM, "out of pinned host memory for the batch table"); }
-    if (dev_malloc(&s.dev, want) != 0) {
-      (void)hipGetLastError(); (void)hipHostFree(s.host); s.host = nullptr; s.dev = nullptr;
-      return fail(IST_E_NOMEM, "out of device memory for the batch table");
-    }
-    s.bytes = want;
-  }
+  const int rc = s.done.ensure();
+  if (rc) return rc;
+  size_t want = size_t(64) << 10;           // (a power of two: a slot grows in few steps)
+  while (want < bytes) want <<= 1;
+  if (s.host.grow(want)) return fail(IST_E_NOMEM, "out of pinned host memory for the batch table");
+  if (s.dev.grow(want)) return fail(IST_E_NOMEM, "out of device memory for the batch table");
   *out = &s;
   return IST_OK;
 }
@@ -137,7 +126,7 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
   ist_ctx::BatchSlot* slot = nullptr;
   int rc = batch_take_slot(ctx, total, &slot);
   if (rc) return rc;
-  uint8_t* h = static_cast<uint8_t*>(slot->host);
+  uint8_t* h = static_cast<uint8_t*>(slot->host.p);
   for (const Group& G : grp) {
     if (G.jobs.empty()) continue;
     const size_t m = G.jobs.size();
@@ -160,7 +149,7 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
     }
     cj[G.n_chunks] = static_cast<int32_t>(m - 1);
   }
-  uint8_t* d = static_cast<uint8_t*>(slot->dev);
+  uint8_t* d = static_cast<uint8_t*>(slot->dev.p);
   if (hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "uploading the batch table failed"); }
   int launches = 0;
   for (int kind = 0; kind < kKinds && rc == IST_OK; ++kind) {
@@ -271,17 +260,17 @@ struct Pipeline {
     if (used[hi]) {
       if (hipEventSynchronize(H.kernel_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
       drop_jobs(&jobs[hi]);
-      if ((H.dst_bytes < dst_total || H.file_bytes < file_total) && hipEventSynchronize(H.read_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
+      if ((H.dst.bytes < dst_total || H.file.bytes < file_total) && hipEventSynchronize(H.read_done) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "waiting for an earlier sub-batch failed"); }
     }
-    if (!H.kernel_done && hipEventCreateWithFlags(&H.kernel_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.kernel_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
-    if (!H.read_done && hipEventCreateWithFlags(&H.read_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); H.read_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
-    int rc = grow_device(&H.tab, &H.tab_bytes, tab_total ? tab_total : 256);
-    if (!rc) rc = grow_device(&H.src, &H.src_bytes, src.bytes());
-    if (!rc) rc = grow_device(&H.dst, &H.dst_bytes, dst_total ? dst_total : 256);
-    if (!rc && out_len) rc = grow_device(&H.file, &H.file_bytes, file_total ? file_total : 256);
+    int rc = H.kernel_done.ensure();
+    if (!rc) rc = H.read_done.ensure();
+    if (!rc) rc = H.tab.grow(tab_total ? tab_total : 256);
+    if (!rc) rc = H.src.grow(src.bytes());
+    if (!rc) rc = H.dst.grow(dst_total ? dst_total : 256);
+    if (!rc && out_len) rc = H.file.grow(file_total ? file_total : 256);
     if (rc) return rc;
-    uint8_t* dtab = static_cast<uint8_t*>(H.tab);
-    uint8_t* ddst = static_cast<uint8_t*>(H.dst);
+    uint8_t* dtab = static_cast<uint8_t*>(H.tab.p);
+    uint8_t* ddst = static_cast<uint8_t*>(H.dst.p);
     // every job's tables in one host block: one item of the staged upload
     std::vector<uint8_t> blob(tab_total, 0);
     std::vector<RowsCopy> up;
@@ -290,7 +279,7 @@ struct Pipeline {
       point_tables(js[q].get(), lay[q], dtab + tab_at[q]);
     }
     if (tab_total) up.push_back(RowsCopy{dtab, blob.data(), nullptr, tab_total, tab_total, 1});
-    const SourceLayout::Placed at = src.place(H.src);
+    const SourceLayout::Placed at = src.place(H.src.p);
     src.copy_all(&up);
     std::vector<ist_job*> ljob(n, nullptr);
     std::vector<int> lcount(n, 0);
@@ -328,7 +317,7 @@ struct Pipeline {
   int encode_and_read(const std::vector<int>& idx, ist_ctx::BatchHalf& H, uint8_t* ddst, const std::vector<size_t>& dst_at,
                       const std::vector<size_t>& file_at, const std::vector<size_t>& file_cap) {
     const size_t n = idx.size();
-    uint8_t* dfile = static_cast<uint8_t*>(H.file);
+    uint8_t* dfile = static_cast<uint8_t*>(H.file.p);
     if (quality) return encode_and_read_jpeg(idx, H, ddst, dst_at, file_at, file_cap);
     std::vector<PngBatchFile> files(n);
     for (size_t q = 0; q < n; ++q) {
@@ -359,7 +348,7 @@ struct Pipeline {
   int encode_and_read_jpeg(const std::vector<int>& idx, ist_ctx::BatchHalf& H, uint8_t* ddst, const std::vector<size_t>& dst_at,
                            const std::vector<size_t>& file_at, const std::vector<size_t>& file_cap) {
     const size_t n = idx.size();
-    uint8_t* dfile = static_cast<uint8_t*>(H.file);
+    uint8_t* dfile = static_cast<uint8_t*>(H.file.p);
     std::vector<JpegBatchFile> files(n);
     for (size_t q = 0; q < n; ++q) {
       const ist_plan& p = plans[idx[q]];

@@ -16,9 +16,9 @@ using namespace ist;
 struct ist_bitmap {
   std::atomic<int> refs{1};
   int device = 0;
-  uint8_t* dev = nullptr;                // row 0; rows are 4 * bitmap_w(desc) bytes apart, kSourceTail readable bytes behind the last
-  size_t bytes = 0;                      // the whole block
+  DevBuf block;                          // row 0 first; rows are 4 * bitmap_w(desc) bytes apart, kSourceTail readable bytes behind the last
   ist_image_desc desc{};
+  uint8_t* px() const { return static_cast<uint8_t*>(block.p); }
 };
 
 namespace {
@@ -30,16 +30,14 @@ size_t row_of(const ist_image_desc& d) { return static_cast<size_t>(bitmap_w(d))
 // a new bitmap with one reference: the block on `device` (the caller has made it current), pixels not yet written
 ist_bitmap* bitmap_alloc(int device, const ist_image_desc& d) {
   const size_t bytes = round256(row_of(d) * static_cast<size_t>(bitmap_h(d)) + kSourceTail);
-  void* p = nullptr;
-  if (dev_malloc(&p, bytes) != 0) {
-    (void)hipGetLastError();
+  std::unique_ptr<ist_bitmap> b(new ist_bitmap);
+  if (b->block.grow(bytes)) {
     fail(IST_E_NOMEM, "out of device memory for a bitmap (" + std::to_string(bytes >> 20) + " MiB)");
     return nullptr;
   }
-  ist_bitmap* b = new ist_bitmap;
-  b->device = device; b->dev = static_cast<uint8_t*>(p); b->bytes = bytes; b->desc = d;
+  b->device = device; b->desc = d;
   g_bitmap_bytes.fetch_add(static_cast<int64_t>(bytes), std::memory_order_relaxed);
-  return b;
+  return b.release();
 }
 
 // the references one call holds on its bitmaps: taken before anything else, dropped when the call returns
@@ -76,7 +74,7 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   std::vector<size_t> pitch(static_cast<size_t>(n));
   for (int i = 0; i < n; ++i) {
     descs[static_cast<size_t>(i)] = bitmaps[i]->desc;
-    src[static_cast<size_t>(i)] = bitmaps[i]->dev;
+    src[static_cast<size_t>(i)] = bitmaps[i]->px();
     pitch[static_cast<size_t>(i)] = row_of(bitmaps[i]->desc);
   }
   std::vector<ist_op> ops;
@@ -92,14 +90,14 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   const JobPtr job(ist_job_create(ctx, cw, ch, kTransparent, ops.data(), static_cast<int>(ops.size()), descs.data(), n, filter, nullptr));
   if (!job) return g_last_code ? g_last_code : IST_E_INVALID;
   const size_t row = static_cast<size_t>(cw) * 4;
-  rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, row * static_cast<size_t>(ch));
+  rc = ctx->scratch_dst.grow(row * static_cast<size_t>(ch));
   if (rc) return rc;
-  rc = ist_job_launch(job.get(), src.data(), pitch.data(), n, ctx->scratch_dst, row, ctx->stream);
+  rc = ist_job_launch(job.get(), src.data(), pitch.data(), n, ctx->scratch_dst.p, row, ctx->stream);
   if (rc) return rc;
   IST_HIP(hipStreamSynchronize(ctx->stream));      // the canvas is complete; the job's tables may go back to the pool
-  if (jpeg) rc = jpeg_to_host(ctx, ctx->scratch_dst, row, cw, ch, jpeg[0], jpeg[1], out, out_len);
-  else if (want_png) rc = png_to_host(ctx, ctx->scratch_dst, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
-  else rc = read_back_pooled(ctx->scratch_dst, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
+  if (jpeg) rc = jpeg_to_host(ctx, ctx->scratch_dst.p, row, cw, ch, jpeg[0], jpeg[1], out, out_len);
+  else if (want_png) rc = png_to_host(ctx, ctx->scratch_dst.p, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
+  else rc = read_back_pooled(ctx->scratch_dst.p, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
   pg.keep = rc == IST_OK;
   return rc;
 }
@@ -108,7 +106,7 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
 
 namespace ist {
 void bitmap_view(const ist_bitmap* b, int* device, const uint8_t** row0, size_t* pitch, ist_image_desc* desc) {
-  *device = b->device; *row0 = b->dev; *pitch = row_of(b->desc); *desc = b->desc;
+  *device = b->device; *row0 = b->px(); *pitch = row_of(b->desc); *desc = b->desc;
 }
 }  // namespace ist
 
@@ -129,7 +127,7 @@ ist_bitmap* ist_bitmap_upload(ist_ctx* ctx, const ist_image_desc* desc, const ui
   if (!g.ok) { fail(IST_E_NO_DEVICE, "hipSetDevice failed"); return nullptr; }
   ist_bitmap* b = bitmap_alloc(ctx->device, *desc);
   if (!b) return nullptr;
-  const std::vector<RowsCopy> up{RowsCopy{b->dev, src, nullptr, src_pitch, row, static_cast<size_t>(bitmap_h(*desc))}};
+  const std::vector<RowsCopy> up{RowsCopy{b->px(), src, nullptr, src_pitch, row, static_cast<size_t>(bitmap_h(*desc))}};
   int rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc == IST_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(IST_E_HIP, "bitmap upload failed"); }
   if (rc) { ist_bitmap_release(b); return nullptr; }
@@ -150,7 +148,7 @@ int ist_bitmaps_decode(ist_ctx* ctx, const uint8_t* const* files, const int64_t*
       ist_bitmap* b = bitmap_alloc(ctx->device, descs[static_cast<size_t>(i)]);
       if (!b) return g_last_code;
       made.push_back(b);
-      img[i] = b->dev;
+      img[i] = b->px();
       pitch[i] = row_of(b->desc);
     }
     return IST_OK;
@@ -180,7 +178,7 @@ int ist_bitmap_download(ist_bitmap* b, uint8_t* dst, size_t dst_pitch, int64_t d
   DeviceGuard g(b->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
   // (no context here: one synchronous copy on the null stream; every call that writes a bitmap has finished before it returned)
-  IST_HIP(hipMemcpy2D(dst, dst_pitch, b->dev, row, row, static_cast<size_t>(rows), hipMemcpyDeviceToHost));
+  IST_HIP(hipMemcpy2D(dst, dst_pitch, b->px(), row, row, static_cast<size_t>(rows), hipMemcpyDeviceToHost));
   return IST_OK;
 }
 
@@ -190,11 +188,7 @@ void ist_bitmap_retain(ist_bitmap* b) {
 
 void ist_bitmap_release(ist_bitmap* b) {
   if (!b || b->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
-  {
-    DeviceGuard g(b->device);
-    dev_free(b->dev);
-  }
-  g_bitmap_bytes.fetch_sub(static_cast<int64_t>(b->bytes), std::memory_order_relaxed);
+  g_bitmap_bytes.fetch_sub(static_cast<int64_t>(b->block.bytes), std::memory_order_relaxed);
   delete b;
 }
 
@@ -252,12 +246,12 @@ int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
-  int rc = grow_device(&ctx->prev_out, &ctx->prev_out_bytes, row * static_cast<size_t>(ph));
+  int rc = ctx->prev_out.grow(row * static_cast<size_t>(ph));
   if (rc) return rc;
   // the stored pixels, as ist_bitmap_download's: EXIF orientation is the planner's business
-  rc = preview_enqueue(ctx, b->dev, row_of(b->desc), bitmap_w(b->desc), bitmap_h(b->desc), b->desc.opaque != 0, ctx->prev_out, row, pw, ph, ctx->stream);
+  rc = preview_enqueue(ctx, b->px(), row_of(b->desc), bitmap_w(b->desc), bitmap_h(b->desc), b->desc.opaque != 0, ctx->prev_out.p, row, pw, ph, ctx->stream);
   if (rc) return rc;
-  const std::vector<RowsCopy> down{RowsCopy{ctx->prev_out, nullptr, dst, dst_pitch, row, static_cast<size_t>(ph)}};
+  const std::vector<RowsCopy> down{RowsCopy{ctx->prev_out.p, nullptr, dst, dst_pitch, row, static_cast<size_t>(ph)}};
   return stager_of(ctx).download(down, ctx->stream);
 }
 

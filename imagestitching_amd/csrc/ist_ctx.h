@@ -12,41 +12,36 @@
 
 #include "ist_jpeg.h"
 
+#include "ist_device.h"
 #include "ist_host.h"
 #include "ist_internal.h"
 #include "ist_launch.h"
 
 struct ist_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;          // host-buffer entry points run here; the device path takes the caller's stream
-  void* scratch_src = nullptr; size_t scratch_src_bytes = 0;
-  void* scratch_dst = nullptr; size_t scratch_dst_bytes = 0;
-  void* scratch_dec = nullptr; size_t scratch_dec_bytes = 0;   // JPEG coefficient / sample planes of ist_decode_files_device
-  void* scratch_huff = nullptr; size_t scratch_huff_bytes = 0; // GPU Huffman decoder: scans, tables, per-subsequence state
-  void* scratch_png = nullptr; size_t scratch_png_bytes = 0;   // compressing PNG encoder: one slot per 16 KiB chunk + its tables
-  void* scratch_file = nullptr; size_t scratch_file_bytes = 0; // device image of a PNG or JPEG file on its way to the host
-  void* scratch_jpg = nullptr; size_t scratch_jpg_bytes = 0;   // JPEG encoder: tables, one slab of coefficients, one slot per restart interval
-  void* scratch_jpg_counts = nullptr; size_t scratch_jpg_counts_bytes = 0;   // ... IST_JPEG_OPTIMIZE: 544 64-bit symbol counters per optimised file of a call
-  void* scratch_arena = nullptr; size_t scratch_arena_bytes = 0; // file pipeline: bitmaps + JPEG planes + canvas + PNG of one call
-  // file pipeline (ist_stitch_files_png / ist_decode_files_device): one stream + event + Huffman scratch per image, so that
-  // the images' decode chains (upload -> Huffman passes -> reconstruction) overlap each other and the export of the bands
+  ist::DevBuf scratch_src;
+  ist::DevBuf scratch_dst;
+  ist::DevBuf scratch_dec;          // JPEG coefficient / sample planes of ist_decode_files_device
+  ist::DevBuf scratch_huff;         // GPU Huffman decoder: scans, tables, per-subsequence state
+  ist::DevBuf scratch_png;          // compressing PNG encoder: one slot per 16 KiB chunk + its tables
+  ist::DevBuf scratch_file;         // device image of a PNG or JPEG file on its way to the host
+  ist::DevBuf scratch_jpg;          // JPEG encoder: tables, one slab of coefficients, one slot per restart interval
+  ist::DevBuf scratch_jpg_counts;   // ... IST_JPEG_OPTIMIZE: 544 64-bit symbol counters per optimised file of a call
+  ist::DevBuf scratch_arena;        // file pipeline: bitmaps + JPEG planes + canvas + PNG of one call
+  ist::DevBuf scratch_ent;          // sparse coefficient entries of host-decoded JPEGs (progressive, restart intervals)
+  // file pipeline (ist_stitch_files_png / ist_decode_files_device): one stream (img_stream, below) + event + Huffman scratch per image,
+  // so that the images' decode chains (upload -> Huffman passes -> reconstruction) overlap each other and the export of the bands
   // that are already final; grow-only, made on first use
-  std::vector<hipStream_t> img_stream;
-  std::vector<hipEvent_t> img_event;
-  std::vector<void*> img_huff; std::vector<size_t> img_huff_bytes;
+  std::vector<ist::Event> img_event;
+  std::vector<ist::DevBuf> img_huff;
   std::unique_ptr<ist::WorkerPool> workers;   // parked host threads for the per-file work of a call (made on first use)
   std::vector<ist::ScanBuf> scan_bufs;        // de-stuffed scans of the last call: their memory is reused (a fresh 1.8 MB block per image and call is 450 page faults on its parse thread)
   std::vector<ist::ScanBuf> file_bufs;        // ist_stitch_paths_png: the files' bytes, read (not mapped) into blocks kept from call to call
-  void* scratch_ent = nullptr; size_t scratch_ent_bytes = 0;   // sparse coefficient entries of host-decoded JPEGs (progressive, restart intervals)
-  hipStream_t render = nullptr;          // file pipeline: Huffman batch + per-image reconstruction + band launches, beside the PNG encoder on `stream`
-  hipEvent_t render_done = nullptr;
-  hipStream_t png2 = nullptr;            // the compressing PNG encoder alternates its slabs between `stream` and this one
-  hipStream_t aux = nullptr;             // second stream of the host-path entry points (PNG slabs travel on it while later ones compress)
+  ist::Event render_done;
   // device blocks of destroyed jobs' tables, re-used by the next job of this context instead of a hipMalloc + hipFree pair
   // per job (a free also synchronises the device); at most kTablePool blocks are kept (the file pipeline compiles one job per image + one)
   static constexpr int kTablePool = 32;
-  struct TableBlock { uint8_t* p; size_t bytes; };
-  std::vector<TableBlock> table_pool;
+  std::vector<ist::DevBuf> table_pool;
   std::mutex table_mu;
   std::mutex mu;                         // one host-path stitch in flight per context (index.js:772 isStitching)
   int png_level = 1;                     // 1: Paeth + run-length + Huffman; 0: stored deflate blocks (ist_ctx_set_png_level)
@@ -54,36 +49,52 @@ struct ist_ctx {
   std::unique_ptr<ist::Stager> stager;   // pinned staging ring, built on first use
   bool timing_on = false;                // ist_ctx_set_timing: the file pipeline records its phase times (adds a sync per phase)
   double last_ms[IST_PHASE_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // An event that is recorded on CALLERS' streams behind the last reader of a block of the context: no wait for the context's own
+  // streams covers it, so it is waited for itself before it goes - and it is declared BEHIND the blocks it guards, so that it goes first.
+  struct LastUse : ist::Event { ~LastUse() { if (e) (void)hipEventSynchronize(e); } };
   // ist_jobs_launch: the per-launch job table goes up through a small ring of (pinned block, device block, event).  The event is
   // recorded behind the kernels that read the slot's device block; the slot is filled again only after it has completed.
   static constexpr int kBatchRing = 4;
-  struct BatchSlot { void* host = nullptr; void* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool pending = false; };
+  struct BatchSlot { ist::PinnedBuf host; ist::DevBuf dev; bool pending = false; LastUse done; };
   BatchSlot batch_ring[kBatchRing];
   int batch_next = 0;
   std::mutex batch_mu;
   // ist_stitch_rgba8_batch: two halves of device scratch (op tables, sources, canvases of one sub-batch each), so that one sub-batch's
   // sources go up while the previous one's canvases come down; grow-only, each bounded by the sub-batch budget (ist_batch.cpp)
   struct BatchHalf {
-    void* tab = nullptr; size_t tab_bytes = 0;
-    void* src = nullptr; size_t src_bytes = 0;
-    void* dst = nullptr; size_t dst_bytes = 0;
-    void* file = nullptr; size_t file_bytes = 0;   // ist_stitch_png_batch: the sub-batch's PNG files (ist_png_bound each)
-    hipEvent_t kernel_done = nullptr;    // behind the launch that reads tab / src
-    hipEvent_t read_done = nullptr;      // behind the downloads that read dst (or file)
+    ist::DevBuf tab, src, dst;
+    ist::DevBuf file;                    // ist_stitch_png_batch: the sub-batch's PNG files (ist_png_bound each)
+    ist::Event kernel_done;              // behind the launch that reads tab / src
+    ist::Event read_done;                // behind the downloads that read dst (or file)
   };
   BatchHalf batch_half[2];
   // previews (ist_preview_host.cpp): the partial sums of the reduce, grow-only; one reduce owns them at a time - a call on another stream
   // is ordered behind the event of the one before it
-  void* scratch_prev = nullptr; size_t scratch_prev_bytes = 0;
-  hipEvent_t prev_done = nullptr; bool prev_pending = false; hipStream_t prev_last = nullptr;
+  ist::DevBuf scratch_prev;
+  LastUse prev_done; bool prev_pending = false; hipStream_t prev_last = nullptr;
   ist_job* prev_job = nullptr;           // the job path's last one-draw job, kept for the next preview of its shape
   int64_t prev_job_key[5] = {0, 0, 0, 0, 0};
   std::mutex prev_mu;
-  // ... of the *_png_preview calls and ist_bitmap_preview: the preview's pixels on their way to the host, the stream the reduce
-  // runs on beside the encoder, and the event that orders it behind the last render
-  void* prev_out = nullptr; size_t prev_out_bytes = 0;
-  hipStream_t prev_stream = nullptr;
-  hipEvent_t prev_ready = nullptr;
+  // ... of the *_png_preview calls and ist_bitmap_preview: the preview's pixels on their way to the host, and the event that orders
+  // the reduce behind the last render
+  ist::DevBuf prev_out;
+  ist::Event prev_ready;
+  // The streams come LAST: members go in reverse order of declaration, so every stream is waited for and destroyed (Stream's
+  // destructor) before the first block above is freed.  A stream added here is picked up by streams() below, which is all that
+  // ist_ctx_sync and ist_ctx_destroy know about them.
+  ist::Stream stream;                    // host-buffer entry points run here; the device path takes the caller's stream
+  ist::Stream aux;                       // second stream of the host-path entry points (PNG slabs travel on it while later ones compress)
+  ist::Stream render;                    // file pipeline: Huffman batch + per-image reconstruction + band launches, beside the PNG encoder on `stream`
+  ist::Stream png2;                      // the compressing PNG encoder alternates its slabs between `stream` and this one
+  ist::Stream prev_stream;               // the reduce of a *_png_preview call runs here, beside the encoder
+  std::vector<ist::Stream> img_stream;   // file pipeline: the images' decode chains
+  // every stream the context has made so far
+  std::vector<hipStream_t> streams() const {
+    std::vector<hipStream_t> v;
+    for (const ist::Stream* s : {&stream, &aux, &render, &png2, &prev_stream}) if (*s) v.push_back(*s);
+    for (const ist::Stream& s : img_stream) v.push_back(s);
+    return v;
+  }
 };
 
 namespace ist {
@@ -102,8 +113,7 @@ struct ist_job {
   ist::Compiled host;
   std::unique_ptr<ist::FlatTwin> flat;   // or none: the job is not made of whole dense rows (ist_internal.h)
   ist::DevTables flat_dt;
-  uint8_t* d_tables = nullptr;           // ONE device allocation holding the five tables below
-  size_t d_tables_bytes = 0;
+  ist::DevBuf d_tables;                  // ONE device allocation holding the five tables below (from, and back to, ctx->table_pool)
   // the streams the job was launched on since it was created (ist_job_destroy waits for THOSE before it hands the tables to
   // the next job - not for the whole device: other streams of a shared device keep running); more than kStreams distinct
   // ones fall back to a device-wide wait
@@ -123,18 +133,6 @@ struct ist_job {
 
 namespace ist {
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// grow-only device scratch
-int grow_device(void** p, size_t* have, size_t need);
 // carve `bytes` from an arena that is being laid out: the section's offset; *off moves on to the next 256-byte boundary
 inline size_t arena_take(size_t* off, size_t bytes) { const size_t at = *off; *off += round256(bytes); return at; }
 
@@ -186,8 +184,6 @@ inline void preview_clear(ist_preview* pv) { if (pv) { pv->width = pv->height = 
 // one preview enqueued on `stream`: the reduce when both axes shrink, a one-draw IST_FILTER_AREA job otherwise.  Arguments checked by the caller.
 int preview_enqueue(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, int64_t h, bool opaque, void* dst, size_t dst_pitch,
                     int32_t pw, int32_t ph, hipStream_t stream);
-// the event of the reduce's scratch, made on first use (ctx->prev_mu held)
-int preview_event(ist_ctx* ctx);
 // what a call that has retained a bitmap reads of it (ist_bitmap.cpp): its device, row 0, the row pitch and the desc
 void bitmap_view(const ist_bitmap* b, int* device, const uint8_t** row0, size_t* pitch, ist_image_desc* desc);
 // The preview of a canvas that an export is reading.  prepare() before the encoder; queue(reader) once every render of the canvas has

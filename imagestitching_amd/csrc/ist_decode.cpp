@@ -119,9 +119,9 @@ int ist_jpeg_decode_rgba8(ist_ctx* ctx, const uint8_t* file, int64_t len, uint8_
   const size_t row = static_cast<size_t>(J.width) * 4;
   const size_t o_out = arena_take(&off, row * J.height);
   uint8_t* d = nullptr;
-  rc = grow_device(&ctx->scratch_arena, &ctx->scratch_arena_bytes, off);
+  rc = ctx->scratch_arena.grow(off);
   if (rc) return rc;
-  d = static_cast<uint8_t*>(ctx->scratch_arena);
+  d = static_cast<uint8_t*>(ctx->scratch_arena.p);
   rc = jpeg_enqueue(J, d, d, L, d + o_out, row, ctx->stream);
   if (rc) return rc;
   std::vector<RowsCopy> down{RowsCopy{d + o_out, nullptr, out, out_pitch, row, static_cast<size_t>(J.height)}};
@@ -185,16 +185,18 @@ constexpr int kImgStreams = 8;           // image i runs on stream i mod kImgStr
 static int ensure_image_lanes(ist_ctx* ctx, int n) {
   const size_t want = static_cast<size_t>(std::min(n, kImgStreams));
   while (ctx->img_stream.size() < want) {
-    hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipStreamCreate failed"); }
-    ctx->img_stream.push_back(st);
+    Stream st;
+    const int rc = st.ensure();
+    if (rc) return rc;
+    ctx->img_stream.push_back(std::move(st));
   }
   while (ctx->img_event.size() < static_cast<size_t>(n)) {
-    hipEvent_t ev = nullptr;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventCreate failed"); }
-    ctx->img_event.push_back(ev);
+    Event ev;
+    const int rc = ev.ensure();
+    if (rc) return rc;
+    ctx->img_event.push_back(std::move(ev));
   }
-  if (ctx->img_huff.size() < static_cast<size_t>(n)) { ctx->img_huff.resize(static_cast<size_t>(n), nullptr); ctx->img_huff_bytes.resize(static_cast<size_t>(n), 0); }
+  if (ctx->img_huff.size() < static_cast<size_t>(n)) ctx->img_huff.resize(static_cast<size_t>(n));
   if (ctx->scan_bufs.size() < static_cast<size_t>(n)) ctx->scan_bufs.resize(static_cast<size_t>(n));
   return IST_OK;
 }
@@ -294,9 +296,10 @@ int FileDecoder::take(int i, hipStream_t consumer) {
   jpeg_layout_sparse(D.J, &need, &L);
   if (need) {                                      // one block serves the host-decoded images in turn
     (void)hipStreamSynchronize(consumer);
-    if (need > ctx_->scratch_ent_bytes) { rc = grow_device(&ctx_->scratch_ent, &ctx_->scratch_ent_bytes, need + need / 2); if (rc) return rc; }
+    rc = ctx_->scratch_ent.grow(need, need / 2);
+    if (rc) return rc;
   }
-  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent), L, img_[i], pitch_[i], consumer, false);
+  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, img_[i], pitch_[i], consumer, false);
 }
 
 int FileDecoder::finish(hipStream_t consumer) {
@@ -328,14 +331,14 @@ int FileDecoder::huffman_all(hipStream_t consumer) {
     JpegGpuItem it; it.J = &D.J; it.S = &D.G;
     for (int c = 0; c < 3; ++c) it.d_coef[c] = c < D.J.ncomp ? reinterpret_cast<int16_t*>(arena_ + jo_[k].coef[c]) : nullptr;
     if (uploaded_[k]) {
-      it.d_stream = static_cast<const uint8_t*>(ctx_->img_huff[k]);
+      it.d_stream = static_cast<const uint8_t*>(ctx_->img_huff[k].p);
       IST_HIP_OR(hipStreamWaitEvent(consumer, ctx_->img_event[k], 0), "hipStreamWaitEvent failed");
     }
     items.push_back(it); who.push_back(i);
   }
   std::vector<uint8_t> okv;
   int launches = 0;
-  rc = jpeg_gpu_entropy_decode(items, &okv, consumer, &ctx_->scratch_huff, &ctx_->scratch_huff_bytes, &launches);
+  rc = jpeg_gpu_entropy_decode(items, &okv, consumer, &ctx_->scratch_huff, &launches);
   g_gpu_entropy_sync_launches.fetch_add(launches, std::memory_order_relaxed);
   if (rc) return rc;
   for (size_t q = 0; q < who.size(); ++q) {
@@ -401,14 +404,10 @@ void FileDecoder::worker(int i) {
   D.J = std::move(full);
   if (!D.G.eligible) return;
   const size_t bytes = D.G.stream.size();
-  if (ctx_->img_huff_bytes[k] < bytes) {
-    dev_free(ctx_->img_huff[k]); ctx_->img_huff[k] = nullptr; ctx_->img_huff_bytes[k] = 0;
-    if (dev_malloc(&ctx_->img_huff[k], bytes + bytes / 4) != 0) { (void)hipGetLastError(); return; }
-    ctx_->img_huff_bytes[k] = bytes + bytes / 4;
-  }
+  if (ctx_->img_huff[k].grow(bytes, bytes / 4)) return;
   hipStream_t st = stream_of(i);
   started_[k] = 1;
-  if (hipMemcpyAsync(ctx_->img_huff[k], D.G.stream.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+  if (hipMemcpyAsync(ctx_->img_huff[k].p, D.G.stream.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipEventRecord(ctx_->img_event[k], st) != hipSuccess) { (void)hipGetLastError(); return; }
   uploaded_[k] = 1;
 }
@@ -427,10 +426,10 @@ int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t
   if (rc) return rc;
   size_t off = 0;
   fd.layout(&off);
-  rc = grow_device(&ctx->scratch_dec, &ctx->scratch_dec_bytes, off ? off : 256);
+  rc = ctx->scratch_dec.grow(off ? off : 256);
   if (rc) return rc;
   ph.lap(IST_PHASE_PLAN_ARENA, "device arena", nullptr);
-  rc = fd.start(static_cast<uint8_t*>(ctx->scratch_dec), img.data(), pitch.data());
+  rc = fd.start(static_cast<uint8_t*>(ctx->scratch_dec.p), img.data(), pitch.data());
   if (rc == IST_OK) rc = fd.finish(ctx->stream);
   // the bitmaps are complete (or, on a failure, nothing of this call writes them any more); the host coefficients in flight may go
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); if (rc == IST_OK) rc = fail(IST_E_HIP, "hipStreamSynchronize failed"); }
@@ -468,15 +467,15 @@ int ist_debug_jpeg_gpu_coefficients(ist_ctx* ctx, const uint8_t* file, int64_t l
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
-  rc = grow_device(&ctx->scratch_arena, &ctx->scratch_arena_bytes, off);
+  rc = ctx->scratch_arena.grow(off);
   if (rc) return rc;
-  uint8_t* d = static_cast<uint8_t*>(ctx->scratch_arena);
+  uint8_t* d = static_cast<uint8_t*>(ctx->scratch_arena.p);
   JpegGpuItem it; it.J = &J; it.S = &G;
   for (int c = 0; c < 3; ++c) it.d_coef[c] = c < J.ncomp ? reinterpret_cast<int16_t*>(d + o_coef[c]) : nullptr;
   std::vector<JpegGpuItem> items(1, it);
   std::vector<uint8_t> okv;
   int launches = 0;
-  rc = jpeg_gpu_entropy_decode(items, &okv, ctx->stream, &ctx->scratch_huff, &ctx->scratch_huff_bytes, &launches);
+  rc = jpeg_gpu_entropy_decode(items, &okv, ctx->stream, &ctx->scratch_huff, &launches);
   g_gpu_entropy_sync_launches.fetch_add(launches, std::memory_order_relaxed);
   if (rc) return rc;
   info->launches = launches;

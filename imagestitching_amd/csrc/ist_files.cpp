@@ -86,9 +86,9 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
   const size_t o_canvas = arena_take(&off, canvas_pitch * static_cast<size_t>(out_plan->canvas_h));
   const int64_t png_cap = ist_png_bound(out_plan->canvas_w, out_plan->canvas_h);
   const size_t o_png = arena_take(&off, static_cast<size_t>(png_cap));
-  rc = grow_device(&ctx->scratch_arena, &ctx->scratch_arena_bytes, off);
+  rc = ctx->scratch_arena.grow(off);
   if (rc) return rc;
-  uint8_t* d = static_cast<uint8_t*>(ctx->scratch_arena);
+  uint8_t* d = static_cast<uint8_t*>(ctx->scratch_arena.p);
   ph.lap(IST_PHASE_PLAN_ARENA, "plan + device arena", nullptr);
   std::vector<uint8_t*> img(static_cast<size_t>(n));
   std::vector<const void*> dsrc(static_cast<size_t>(n));
@@ -153,7 +153,8 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
     if (render != reader) IST_HIP_OR(hipStreamWaitEvent(reader, ev, 0), "ordering the export behind the render failed");
     return IST_OK;
   };
-  if (!ctx->render_done && hipEventCreateWithFlags(&ctx->render_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ctx->render_done = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
+  rc = ctx->render_done.ensure();
+  if (rc) return rc;
   // The FIRST request renders everything: behind the Huffman batch every image is reconstructed and its band rendered on the
   // render stream, an event per band (the images' upload events are free again by then).  History (rocprofv3 timelines,
   // profiles/r03_file_pipeline_kernels.txt is the last of them): (1) pulling band k+1 only when slab k+1 was about to be

@@ -129,48 +129,20 @@ inline uint8_t* dev_of(const RowsCopy& it, const Piece& p) { return static_cast<
 
 }  // namespace
 
-void Stager::release_lane(Lane& l) {
-  if (l.stream) (void)hipStreamSynchronize(l.stream);
-  for (int s = 0; s < 2; ++s) { if (l.done[s]) (void)hipEventDestroy(l.done[s]); if (l.chunk[s]) (void)hipHostFree(l.chunk[s]); l.done[s] = nullptr; l.chunk[s] = nullptr; }
-  if (l.tail) (void)hipEventDestroy(l.tail);
-  if (l.stream) (void)hipStreamDestroy(l.stream);
-  l.tail = nullptr; l.stream = nullptr;
-}
-
-Stager::~Stager() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device_) != hipSuccess) return;
-  if (big_.stream) (void)hipStreamSynchronize(big_.stream);
-  for (int s = 0; s < 2; ++s) { if (big_.done[s]) (void)hipEventDestroy(big_.done[s]); if (big_.piece[s]) (void)hipHostFree(big_.piece[s]); }
-  if (big_.tail) (void)hipEventDestroy(big_.tail);
-  if (big_.stream) (void)hipStreamDestroy(big_.stream);
-  for (Lane& l : lanes_) release_lane(l);
-  if (gate_) (void)hipEventDestroy(gate_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
 int Stager::ensure() {
   if (!lanes_.empty()) return IST_OK;
   std::vector<Lane> lanes(kLanes);
-  hipEvent_t gate = nullptr;
-  bool ok = hipEventCreateWithFlags(&gate, hipEventDisableTiming) == hipSuccess;
+  Event gate;
+  bool ok = gate.ensure() == IST_OK;
   for (Lane& l : lanes) {
-    ok = ok && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&l.tail, hipEventDisableTiming) == hipSuccess;
+    ok = ok && l.stream.ensure() == IST_OK && l.tail.ensure() == IST_OK;
     for (int s = 0; s < 2 && ok; ++s)
-      ok = hipHostMalloc(&l.chunk[s], kChunk, hipHostMallocDefault) == hipSuccess &&
-           hipEventCreateWithFlags(&l.done[s], hipEventDisableTiming) == hipSuccess &&
+      ok = l.chunk[s].grow(kChunk) == IST_OK && l.done[s].ensure() == IST_OK &&
            hipEventRecord(l.done[s], l.stream) == hipSuccess;           // recorded once: synchronising it is always legal
   }
-  if (!ok) {                    // nothing half-built is published: the next call starts over
-    (void)hipGetLastError();
-    for (Lane& l : lanes) release_lane(l);
-    if (gate) (void)hipEventDestroy(gate);
-    return fail(IST_E_HIP, "allocating the pinned staging ring failed");
-  }
+  if (!ok) { (void)hipGetLastError(); return fail(IST_E_HIP, "allocating the pinned staging ring failed"); }   // nothing half-built is published: the next call starts over
   lanes_.swap(lanes);
-  gate_ = gate;
+  gate_ = std::move(gate);
   return IST_OK;
 }
 
@@ -179,18 +151,11 @@ namespace { constexpr size_t kBigPiece = 32u << 20; constexpr int kBigPackers = 
 int Stager::ensure_big() {
   if (big_.stream) return IST_OK;
   Big b;
-  bool ok = hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&b.tail, hipEventDisableTiming) == hipSuccess;
+  bool ok = b.stream.ensure() == IST_OK && b.tail.ensure() == IST_OK;
   for (int s = 0; s < 2 && ok; ++s)
-    ok = hipHostMalloc(&b.piece[s], kBigPiece, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&b.done[s], hipEventDisableTiming) == hipSuccess &&
-         hipEventRecord(b.done[s], b.stream) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (int s = 0; s < 2; ++s) { if (b.done[s]) (void)hipEventDestroy(b.done[s]); if (b.piece[s]) (void)hipHostFree(b.piece[s]); }
-    if (b.tail) (void)hipEventDestroy(b.tail);
-    if (b.stream) (void)hipStreamDestroy(b.stream);
-    return fail(IST_E_HIP, "allocating the large staging pieces failed");
-  }
-  big_ = b;
+    ok = b.piece[s].grow(kBigPiece) == IST_OK && b.done[s].ensure() == IST_OK && hipEventRecord(b.done[s], b.stream) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); return fail(IST_E_HIP, "allocating the large staging pieces failed"); }
+  big_ = std::move(b);
   return IST_OK;
 }
 
@@ -221,7 +186,7 @@ int Stager::upload_big(const std::vector<RowsCopy>& items, hipStream_t after, Wo
       const size_t nr = std::min(per, it.rows - r0);
       const int s = static_cast<int>(big_.k++ & 1u);
       if (hipEventSynchronize(big_.done[s]) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "host-to-device staging failed"); }   // the piece's previous copy has left
-      uint8_t* piece = static_cast<uint8_t*>(big_.piece[s]);
+      uint8_t* piece = static_cast<uint8_t*>(big_.piece[s].p);
       const int workers = static_cast<int>(std::min<size_t>(kBigPackers, std::max<size_t>(1, nr * it.row >> 20)));
       const size_t share = (nr + static_cast<size_t>(workers) - 1) / static_cast<size_t>(workers);
       auto part = [&](int w) {
@@ -278,7 +243,7 @@ int Stager::run(const std::vector<RowsCopy>& items, bool up, hipStream_t other) 
       const RowsCopy& it = items[p.item];
       const int s = static_cast<int>(k++ & 1u);
       if (hipEventSynchronize(L.done[s]) != hipSuccess) { err = 1; break; }        // the chunk's previous DMA has landed
-      uint8_t* chunk = static_cast<uint8_t*>(L.chunk[s]);
+      uint8_t* chunk = static_cast<uint8_t*>(L.chunk[s].p);
       if (up) {
         pack(it, p, chunk);
         if (hipMemcpyAsync(dev_of(it, p), chunk, piece_bytes(p), hipMemcpyHostToDevice, L.stream) != hipSuccess) { err = 1; break; }
@@ -294,7 +259,7 @@ int Stager::run(const std::vector<RowsCopy>& items, bool up, hipStream_t other) 
         const int s = static_cast<int>((k + d) & 1u);
         if (!pending[s]) continue;
         if (hipEventSynchronize(L.done[s]) != hipSuccess) { err = 1; continue; }
-        unpack(items[pending[s]->item], *pending[s], static_cast<const uint8_t*>(L.chunk[s]));
+        unpack(items[pending[s]->item], *pending[s], static_cast<const uint8_t*>(L.chunk[s].p));
       }
   };
   if (n_lanes == 1) work(0);

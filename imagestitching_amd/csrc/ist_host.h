@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "ist_device.h"
 #include "ist_internal.h"     // RowsCopy
 
 namespace ist {
@@ -39,10 +40,7 @@ void pool_trim();                       // release every cached block
 // ---- staged copies between caller memory and device memory -------------------------------------------------------
 class Stager {
  public:
-  explicit Stager(int device) : device_(device) {}
-  ~Stager();
-  Stager(const Stager&) = delete;
-  Stager& operator=(const Stager&) = delete;
+  explicit Stager(int device) : device_(device) {}   // (destroyed with its device current: ist_ctx_destroy)
   // Uploads every item; on return the copies are ENQUEUED and `after` (a stream of the same device) has been made to
   // wait for them, so work submitted to `after` next sees the data.  The caller's buffers are no longer needed.
   int upload(const std::vector<RowsCopy>& items, hipStream_t after);
@@ -57,14 +55,14 @@ class Stager {
   int upload_big(const std::vector<RowsCopy>& items, hipStream_t after, class WorkerPool* pool);
 
  private:
-  struct Lane { hipStream_t stream = nullptr; void* chunk[2] = {nullptr, nullptr}; hipEvent_t done[2] = {nullptr, nullptr}; hipEvent_t tail = nullptr; };
+  // (the stream is the LAST member of both: it goes first, waited for, before the pinned blocks its copies use)
+  struct Lane { PinnedBuf chunk[2]; Event done[2]; Event tail; Stream stream; };
   int ensure();
-  static void release_lane(Lane& l);
   int run(const std::vector<RowsCopy>& items, bool up, hipStream_t other);
   int device_;
   std::vector<Lane> lanes_;
-  hipEvent_t gate_ = nullptr;
-  struct Big { hipStream_t stream = nullptr; void* piece[2] = {nullptr, nullptr}; hipEvent_t done[2] = {nullptr, nullptr}; hipEvent_t tail = nullptr; unsigned k = 0; } big_;
+  Event gate_;
+  struct Big { PinnedBuf piece[2]; Event done[2]; Event tail; unsigned k = 0; Stream stream; } big_;
   int ensure_big();
 };
 

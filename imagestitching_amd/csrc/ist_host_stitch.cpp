@@ -31,18 +31,18 @@ int render_to_scratch(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
   SourceLayout lay;
   int rc = lay.add(images, n_images, src, src_pitch, whole_bitmaps(job->host));
   if (rc) return rc;
-  rc = grow_device(&ctx->scratch_src, &ctx->scratch_src_bytes, lay.bytes());
+  rc = ctx->scratch_src.grow(lay.bytes());
   if (rc) return rc;
   const int64_t rw = job->host.rx1 - job->host.rx0, rh = job->host.ry1 - job->host.ry0;
   const size_t pitch = static_cast<size_t>(rw) * 4;
-  rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, pitch * static_cast<size_t>(rh));
+  rc = ctx->scratch_dst.grow(pitch * static_cast<size_t>(rh));
   if (rc) return rc;
-  const SourceLayout::Placed at = lay.place(ctx->scratch_src);
+  const SourceLayout::Placed at = lay.place(ctx->scratch_src.p);
   std::vector<RowsCopy> up;
   lay.copy_all(&up);
   rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc) return rc;
-  const uintptr_t biased = reinterpret_cast<uintptr_t>(ctx->scratch_dst) - (static_cast<uintptr_t>(job->host.ry0) * pitch + static_cast<uintptr_t>(job->host.rx0) * 4);
+  const uintptr_t biased = reinterpret_cast<uintptr_t>(ctx->scratch_dst.p) - (static_cast<uintptr_t>(job->host.ry0) * pitch + static_cast<uintptr_t>(job->host.rx0) * 4);
   rc = ist_job_launch(job.get(), at.ptr.data(), at.pitch.data(), n_images, reinterpret_cast<void*>(biased), pitch, ctx->stream);
   if (rc) return rc;
   // the job's device tables are freed when `job` goes out of scope: the launch must have consumed them
@@ -110,13 +110,13 @@ struct RowBands {
     for (const auto& band : need) for (const auto& kv : band) whole[kv.first] = RowSpan{0, bitmap_h(images[kv.first])};
     int rc = lay.add(images, n_images, s, sp, whole);
     if (rc) return rc;
-    rc = grow_device(&ctx->scratch_src, &ctx->scratch_src_bytes, lay.bytes());
+    rc = ctx->scratch_src.grow(lay.bytes());
     if (rc) return rc;
-    rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, total);
+    rc = ctx->scratch_dst.grow(total);
     if (rc) return rc;
-    at = lay.place(ctx->scratch_src);
+    at = lay.place(ctx->scratch_src.p);
     lo.assign(static_cast<size_t>(n_images), -1); hi.assign(static_cast<size_t>(n_images), -1);
-    canvas = static_cast<uint8_t*>(ctx->scratch_dst);
+    canvas = static_cast<uint8_t*>(ctx->scratch_dst.p);
     ok = true;
     return IST_OK;
   }
@@ -157,12 +157,11 @@ int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, 
   lap("band jobs compiled, scratch");
   uint8_t* host = static_cast<uint8_t*>(pool_take(rb.total));
   if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the result");
-  std::vector<hipEvent_t> ev(static_cast<size_t>(rb.nb), nullptr);
+  std::vector<Event> ev(static_cast<size_t>(rb.nb));   // (made per band that is submitted; they go after the waits below)
   hipStream_t R = ctx->stream, D = ctx->aux;
   // (whatever happens below, the streams are idle before the pinned block or the jobs' tables are given back)
   auto finish = [&](int code) {
     (void)hipStreamSynchronize(R); (void)hipStreamSynchronize(D); (void)stager_of(ctx).sync();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     if (code != IST_OK) pool_give(host);
     return code;
   };
@@ -172,8 +171,8 @@ int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, 
     if (y0 >= y1) continue;
     rc = rb.submit(b, R);
     if (rc) return finish(rc);
-    hipEvent_t& e = ev[static_cast<size_t>(b)];
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, R) != hipSuccess || hipStreamWaitEvent(D, e, 0) != hipSuccess ||
+    Event& e = ev[static_cast<size_t>(b)];
+    if (e.ensure() != IST_OK || hipEventRecord(e, R) != hipSuccess || hipStreamWaitEvent(D, e, 0) != hipSuccess ||
         hipMemcpyAsync(host + static_cast<size_t>(y0) * rb.row, rb.canvas + static_cast<size_t>(y0) * rb.row, static_cast<size_t>(y1 - y0) * rb.row, hipMemcpyDeviceToHost, D) != hipSuccess) {
       (void)hipGetLastError();
       return finish(fail(IST_E_HIP, "queueing a band's readback failed"));
@@ -199,7 +198,7 @@ int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
   rc = ensure_render(ctx);
   if (rc) return rc;
   hipStream_t R = ctx->render;
-  std::vector<hipEvent_t> ev(static_cast<size_t>(rb.nb), nullptr);
+  std::vector<Event> ev(static_cast<size_t>(rb.nb));   // (made per band that is submitted; they go after the waits below)
   int next = 0;
   // the encoder is about to read canvas rows [0, y_end) on `reader`: submit the bands they lie in, order the reader behind the last of them
   auto need_rows = [&](int64_t y_end, void* reader_) -> int {
@@ -211,7 +210,7 @@ int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
       if (b >= next) {
         const int rc2 = rb.submit(b, R);
         if (rc2) return rc2;
-        if (hipEventCreateWithFlags(&ev[static_cast<size_t>(b)], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[static_cast<size_t>(b)], R) != hipSuccess) {
+        if (ev[static_cast<size_t>(b)].ensure() != IST_OK || hipEventRecord(ev[static_cast<size_t>(b)], R) != hipSuccess) {
           (void)hipGetLastError(); return fail(IST_E_HIP, "hipEventRecord failed");
         }
         next = b + 1;
@@ -225,7 +224,6 @@ int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
   for (int b = 0; b < rb.nb; ++b) hint = std::max<int64_t>(hint, rb.y1(b) - rb.y0(b));
   rc = png_to_host(ctx, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint, preview);
   (void)hipStreamSynchronize(R); (void)stager_of(ctx).sync(); (void)hipStreamSynchronize(ctx->stream);
-  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   if (rc == IST_OK) g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
   return rc;
 }
@@ -242,7 +240,7 @@ int render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t c
   if (rc != 1) return rc;                      // (1: not applicable, nothing queued)
   rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, nullptr, nullptr, nullptr);
   if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len, nullptr, 0, preview);
+  return png_to_host(ctx, ctx->scratch_dst.p, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len, nullptr, 0, preview);
 }
 
 }  // namespace
@@ -270,7 +268,7 @@ int ist_render_rgba8(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uin
   if (rw > 0 && dst_pitch < static_cast<size_t>(rw) * 4) return fail(IST_E_INVALID, "dst_pitch too small");
   int rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, region, &rw, &rh);
   if (rc) return rc;
-  std::vector<RowsCopy> down{RowsCopy{ctx->scratch_dst, nullptr, dst, dst_pitch, static_cast<size_t>(rw) * 4, static_cast<size_t>(rh)}};
+  std::vector<RowsCopy> down{RowsCopy{ctx->scratch_dst.p, nullptr, dst, dst_pitch, static_cast<size_t>(rw) * 4, static_cast<size_t>(rh)}};
   return stager_of(ctx).download(down, ctx->stream);
 }
 
@@ -328,7 +326,7 @@ int ist_stitch_rgba8(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* 
                              n_images, filter, nullptr, nullptr, nullptr);
       // the export (index.js:1577-1579): the whole canvas in one DMA into a pinned block of the pool
       if (rc == IST_OK)
-        rc = read_back_pooled(ctx->scratch_dst, static_cast<size_t>(out_plan->canvas_w) * 4 * static_cast<size_t>(out_plan->canvas_h), ctx->stream, out_pixels);
+        rc = read_back_pooled(ctx->scratch_dst.p, static_cast<size_t>(out_plan->canvas_w) * 4 * static_cast<size_t>(out_plan->canvas_h), ctx->stream, out_pixels);
     }
   }
   pg.keep = rc == IST_OK;
@@ -356,7 +354,7 @@ int ist_stitch_jpeg(ist_ctx* ctx, const ist_image_desc* images, const uint8_t* c
   rc = render_to_scratch(ctx, out_plan->canvas_w, out_plan->canvas_h, kTransparent, ops.data(), static_cast<int>(ops.size()), images, src, src_pitch,
                          n_images, filter, nullptr, nullptr, nullptr);
   if (rc == IST_OK)
-    rc = jpeg_to_host(ctx, ctx->scratch_dst, static_cast<size_t>(out_plan->canvas_w) * 4, out_plan->canvas_w, out_plan->canvas_h, quality, subsampling,
+    rc = jpeg_to_host(ctx, ctx->scratch_dst.p, static_cast<size_t>(out_plan->canvas_w) * 4, out_plan->canvas_w, out_plan->canvas_h, quality, subsampling,
                       out_jpeg, out_len);
   pg.keep = rc == IST_OK;
   return rc;
@@ -371,12 +369,12 @@ int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int6
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   const size_t row = static_cast<size_t>(w) * 4;
-  int rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, row * static_cast<size_t>(h));
+  int rc = ctx->scratch_dst.grow(row * static_cast<size_t>(h));
   if (rc) return rc;
-  std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
+  std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst.p, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
   rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst, row, w, h, nullptr, out_png, out_len);
+  return png_to_host(ctx, ctx->scratch_dst.p, row, w, h, nullptr, out_png, out_len);
 }
 
 }  // extern "C"

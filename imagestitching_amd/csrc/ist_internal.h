@@ -128,10 +128,9 @@ struct FlatTwin {
 std::unique_ptr<FlatTwin> compile_flat_twin(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                                             const ist_image_desc* images, int n_images, int filter, const Compiled& primary);
 
-// every device allocation of the library goes through these two (counted: ist_debug_device_allocs).  dev_malloc returns
-// the hipError_t as an int (0 = hipSuccess) so that this header needs nothing of HIP.
+// every device allocation of the library goes through this one (counted: ist_debug_device_allocs), called by DevBuf (ist_device.h),
+// which also frees.  It returns the hipError_t as an int (0 = hipSuccess) so that this header needs nothing of HIP.
 int dev_malloc(void** p, size_t bytes);
-void dev_free(void* p);
 
 // true when the process was started with IST_TUNING=1 (decided once): only then are tuning knobs read from the environment
 bool tuning_mode();

@@ -154,9 +154,10 @@ std::vector<int16_t> jpeg_dense_coefficients(const JpegComp& c);
 // d_stream (optional): the de-stuffed scan ALREADY on the device (256-byte aligned, S->stream.size() bytes, uploaded by the
 // caller - e.g. by the image's parse thread while other images are still being parsed); NULL: uploaded here.
 struct JpegGpuItem { const JpegImage* J; const JpegGpuScan* S; int16_t* d_coef[3]; const uint8_t* d_stream = nullptr; };
-// scratch / scratch_bytes (optional): a grow-only device buffer the caller keeps across calls
+struct DevBuf;   // (ist_device.h)
+// scratch (optional): a grow-only device buffer the caller keeps across calls
 // launches (optional): the synchronisation launches this call made (0 when nothing was launched)
-int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream, void** scratch = nullptr, size_t* scratch_bytes = nullptr,
+int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream, DevBuf* scratch = nullptr,
                             int* launches = nullptr);
 
 }  // namespace ist

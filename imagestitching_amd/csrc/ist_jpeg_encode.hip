@@ -512,11 +512,11 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
 
   const size_t o_coef = round256(sizeof T), coef_bytes = round256(static_cast<size_t>(slab_rows * g.row_blocks) * 128);
   const size_t o_slots = o_coef + coef_bytes, total = o_slots + static_cast<size_t>(slab_rows * g.slot);
-  int rc = grow_device(&ctx->scratch_jpg, &ctx->scratch_jpg_bytes, total);
+  int rc = ctx->scratch_jpg.grow(total);
   if (rc) return rc;
   constexpr size_t kCountBytes = static_cast<size_t>(kJpegCounters) * 8;
-  if (optimize) { rc = grow_device(&ctx->scratch_jpg_counts, &ctx->scratch_jpg_counts_bytes, kCountBytes); if (rc) return rc; }
-  uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg);
+  if (optimize) { rc = ctx->scratch_jpg_counts.grow(kCountBytes); if (rc) return rc; }
+  uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg.p);
   // per interval of a slab: its length (written by the kernel) and its place in the file (read by the gather), in pinned memory;
   // behind them the counts of an optimised file
   const size_t o_counts = static_cast<size_t>(slab_rows) * 16;
@@ -541,7 +541,7 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
   };
   bool kept = false;                                 // the (only) slab's coefficients are in the scratch already
   if (optimize) {
-    int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts);
+    int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts.p);
     IST_HIP(hipMemsetAsync(counters, 0, kCountBytes, stream));
     const HistArgs H{X.coef, counters, static_cast<int32_t>(g.row_blocks), g.bpm};
     const unsigned parts = static_cast<unsigned>((g.row_blocks + kHistBlocks - 1) / kHistBlocks);
@@ -630,12 +630,12 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
   // through the last synchronisation (Drain below; whoever drops that must record slot->done and set slot->pending instead).
   // (A counted round is synchronised before the next one starts.)
   std::lock_guard<std::mutex> lk(ctx->batch_mu);
-  int rc = grow_device(&ctx->scratch_jpg, &ctx->scratch_jpg_bytes, max_scratch);
+  int rc = ctx->scratch_jpg.grow(max_scratch);
   if (rc) return rc;
   const size_t count_bytes = static_cast<size_t>(n_opt) * kJpegCounters * 8;
-  if (n_opt) { rc = grow_device(&ctx->scratch_jpg_counts, &ctx->scratch_jpg_counts_bytes, count_bytes); if (rc) return rc; }
-  uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg);
-  int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts);
+  if (n_opt) { rc = ctx->scratch_jpg_counts.grow(count_bytes); if (rc) return rc; }
+  uint8_t* const scratch = static_cast<uint8_t*>(ctx->scratch_jpg.p);
+  int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts.p);
   // per interval of a round: its length (written by the kernel) and its place in its file (read by the gather), in pinned memory;
   // behind them the counts of the optimised files
   const size_t o_counts = static_cast<size_t>(max_ivs) * 16;
@@ -648,9 +648,9 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
   struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
   // one round's table block up, its transform and, for its optimised pieces, their histogram
   auto transform = [&](const JpegRound& R, ist_ctx::BatchSlot* slot, bool count, unsigned parts) -> int {
-    uint8_t* const d = static_cast<uint8_t*>(slot->dev);
-    jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch, opt.data());
-    IST_HIP(hipMemcpyAsync(d, slot->host, R.table_bytes, hipMemcpyHostToDevice, stream));
+    uint8_t* const d = static_cast<uint8_t*>(slot->dev.p);
+    jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host.p), d, scratch, opt.data());
+    IST_HIP(hipMemcpyAsync(d, slot->host.p, R.table_bytes, hipMemcpyHostToDevice, stream));
     const JpegBatchArgs B{reinterpret_cast<const JpegPiece*>(d + R.at_pieces), R.p1 - R.p0, len, dst};
     hipLaunchKernelGGL(ist_jpeg_transform_batch_kernel, dim3(static_cast<unsigned>(R.wgs)), dim3(256), 0, stream, B);
     IST_HIP(hipGetLastError());
@@ -702,15 +702,15 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
     ist_ctx::BatchSlot* slot = nullptr;
     rc = batch_take_slot(ctx, R.table_bytes, &slot);
     if (rc) return rc;
-    uint8_t* const d = static_cast<uint8_t*>(slot->dev);
+    uint8_t* const d = static_cast<uint8_t*>(slot->dev.p);
     rc = transform(R, slot, wide && one_round, hist_parts[r]);
     if (rc) return rc;
     const JpegBatchArgs B{reinterpret_cast<const JpegPiece*>(d + R.at_pieces), R.p1 - R.p0, len, dst};
     if (wide && one_round) {                         // the coefficients stay; the block goes up again with the files' own tables and headers
       rc = build_tables();
       if (rc) return rc;
-      jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host), d, scratch, opt.data());
-      IST_HIP(hipMemcpyAsync(d, slot->host, R.table_bytes, hipMemcpyHostToDevice, stream));
+      jpeg_round_pack(R, files.data(), pieces.data(), static_cast<uint8_t*>(slot->host.p), d, scratch, opt.data());
+      IST_HIP(hipMemcpyAsync(d, slot->host.p, R.table_bytes, hipMemcpyHostToDevice, stream));
     }
     if (wide) hipLaunchKernelGGL(ist_jpeg_entropy_wide_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
     else hipLaunchKernelGGL(ist_jpeg_entropy_batch_kernel, dim3(static_cast<unsigned>(R.ivs)), dim3(kBatch), 0, stream, B);
@@ -744,13 +744,13 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
 int jpeg_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, uint8_t** out_jpeg,
                  int64_t* out_len) {
   const int64_t cap = ist_jpeg_bound(w, h, subsampling);
-  int rc = grow_device(&ctx->scratch_file, &ctx->scratch_file_bytes, static_cast<size_t>(cap));
+  int rc = ctx->scratch_file.grow(static_cast<size_t>(cap));
   if (rc) return rc;
   int64_t len = 0;
-  rc = jpeg_encode_device(ctx, canvas, pitch, w, h, quality, subsampling, ctx->scratch_file, cap, &len, ctx->stream);
+  rc = jpeg_encode_device(ctx, canvas, pitch, w, h, quality, subsampling, ctx->scratch_file.p, cap, &len, ctx->stream);
   if (rc) return rc;
   uint8_t* host = nullptr;
-  rc = read_back_pooled(ctx->scratch_file, static_cast<size_t>(len), ctx->stream, &host);
+  rc = read_back_pooled(ctx->scratch_file.p, static_cast<size_t>(len), ctx->stream, &host);
   if (rc) return rc;
   *out_jpeg = host; *out_len = len;
   return IST_OK;
@@ -815,12 +815,12 @@ int ist_jpeg_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
   const size_t row = static_cast<size_t>(w) * 4;
-  rc = grow_device(&ctx->scratch_dst, &ctx->scratch_dst_bytes, row * static_cast<size_t>(h));
+  rc = ctx->scratch_dst.grow(row * static_cast<size_t>(h));
   if (rc) return rc;
-  std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
+  std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst.p, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
   rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc) return rc;
-  return jpeg_to_host(ctx, ctx->scratch_dst, row, w, h, quality, subsampling, out_jpeg, out_len);
+  return jpeg_to_host(ctx, ctx->scratch_dst.p, row, w, h, quality, subsampling, out_jpeg, out_len);
 }
 
 }  // extern "C"

@@ -691,7 +691,7 @@ __global__ __launch_bounds__(kWriteThreads) void ist_jpeg_write_kernel(const Wri
 
 }  // namespace
 
-int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream_, void** scratch, size_t* scratch_bytes, int* launches) {
+int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<uint8_t>* ok, void* stream_, DevBuf* scratch, int* launches) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (launches) *launches = 0;
   const size_t n_img = items.size();
@@ -799,19 +799,10 @@ int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<u
   const size_t o_tally = take(16 * static_cast<size_t>(ns)), o_half = take(16 * static_cast<size_t>(n_half)), o_flag = take(4), o_err = take(4 * n_unit);
   // the caller's grow-only scratch (a context keeps it across calls: no allocation, and no implicit device synchronisation
   // of a free, per call), or a one-off allocation
-  uint8_t* d = nullptr;
-  struct Free { void* p; ~Free() { dev_free(p); } } fr{nullptr};
-  if (scratch && scratch_bytes) {
-    if (*scratch_bytes < off) {
-      if (*scratch) { dev_free(*scratch); *scratch = nullptr; *scratch_bytes = 0; }
-      if (dev_malloc(scratch, off + off / 4) != 0) { (void)hipGetLastError(); return fail(IST_E_NOMEM, "out of device memory for the Huffman decoder"); }
-      *scratch_bytes = off + off / 4;
-    }
-    d = static_cast<uint8_t*>(*scratch);
-  } else {
-    if (dev_malloc(reinterpret_cast<void**>(&d), off) != 0) { (void)hipGetLastError(); return fail(IST_E_NOMEM, "out of device memory for the Huffman decoder"); }
-    fr.p = d;
-  }
+  DevBuf one_off;
+  DevBuf& block = scratch ? *scratch : one_off;
+  if (block.grow(off, scratch ? off / 4 : 0)) return fail(IST_E_NOMEM, "out of device memory for the Huffman decoder");
+  uint8_t* const d = static_cast<uint8_t*>(block.p);
   // pinned block: [small inputs | results: flag, half totals, error words]
   const size_t res_bytes = 256 + 16 * static_cast<size_t>(n_half) + 4 * n_unit;
   struct Pin { uint8_t* p; ~Pin() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(small_bytes + res_bytes))};

@@ -106,13 +106,13 @@ struct ist_group {
   std::vector<int> devs;                  // distinct devices, devs[0] = the root's
   std::vector<int> slot_rank;             // slot -> index into devs (= RCCL rank)
   std::vector<ist_ctx*> ctx;              // one context per distinct device (its stream carries the renders and sends)
-  hipStream_t recv_stream = nullptr;      // root device: receives + placement launches, beside the root's own launch
+  Stream recv_stream;                     // root device: receives + placement launches, beside the root's own launch
   std::vector<ncclComm_t> comm;           // one communicator handle per distinct device; empty while the group is one device
   bool self_send = false;                 // test knob (IST_TUNING=1 IST_GROUP_SELF_SEND=1): same-device bands also travel through RCCL
   std::mutex mu;
   // grow-only arenas (jobs hold offsets into them): compact bands per device, staging bands on the root
-  std::vector<void*> band_arena; std::vector<size_t> band_bytes;
-  void* staging = nullptr; size_t staging_bytes = 0;
+  std::vector<DevBuf> band_arena;
+  DevBuf staging;
   // compiled jobs of the one-call host path, most recently used last
   struct Cached { std::string key; ist_group_job* job; };
   std::vector<Cached> cache;
@@ -166,22 +166,18 @@ int group_sync_locked(ist_group* g) {
 
 // the arenas cover what `job` addresses; growing one waits for the group's streams first (earlier launches may still use it)
 int ensure_arenas(ist_group* g, const ist_group_job* job) {
-  bool grow = job->staging_need > g->staging_bytes;
-  for (size_t r = 0; r < g->devs.size(); ++r) grow = grow || job->band_need[r] > g->band_bytes[r];
+  bool grow = job->staging_need > g->staging.bytes;
+  for (size_t r = 0; r < g->devs.size(); ++r) grow = grow || job->band_need[r] > g->band_arena[r].bytes;
   if (!grow) return IST_OK;
   int rc = group_sync_locked(g);
   if (rc) return rc;
   for (size_t r = 0; r < g->devs.size(); ++r) {
-    if (job->band_need[r] <= g->band_bytes[r]) continue;
     DeviceGuard dg(g->devs[r]);
-    rc = grow_device(&g->band_arena[r], &g->band_bytes[r], job->band_need[r]);
+    rc = g->band_arena[r].grow(job->band_need[r]);
     if (rc) return fail(IST_E_NOMEM, "out of device memory for the bands of device " + std::to_string(g->devs[r]));
   }
-  if (job->staging_need > g->staging_bytes) {
-    DeviceGuard dg(g->devs[0]);
-    rc = grow_device(&g->staging, &g->staging_bytes, job->staging_need);
-    if (rc) return fail(IST_E_NOMEM, "out of device memory for the staging bands");
-  }
+  DeviceGuard dg(g->devs[0]);
+  if (g->staging.grow(job->staging_need)) return fail(IST_E_NOMEM, "out of device memory for the staging bands");
   return IST_OK;
 }
 
@@ -208,11 +204,10 @@ ist_group* ist_group_create(const int* devices, int ndev) {
     if (!c) return nullptr;
     g->ctx.push_back(c);
   }
-  g->band_arena.assign(g->devs.size(), nullptr);
-  g->band_bytes.assign(g->devs.size(), 0);
+  g->band_arena.resize(g->devs.size());
   {
     DeviceGuard dg(g->devs[0]);
-    if (hipStreamCreateWithFlags(&g->recv_stream, hipStreamNonBlocking) != hipSuccess) { fail(IST_E_HIP, "hipStreamCreate failed"); return nullptr; }
+    if (g->recv_stream.ensure() != IST_OK) return nullptr;
   }
   g->self_send = tuning_mode() && std::getenv("IST_GROUP_SELF_SEND") != nullptr;
   // (the RCCL communicators are made on the first launch that gathers over xGMI - ensure_rccl: the host-sink path never
@@ -227,11 +222,9 @@ void ist_group_destroy(ist_group* g) {
   for (auto& c : g->cache) delete c.job;
   g->cache.clear();
   for (ncclComm_t c : g->comm) if (c) (void)rccl()->CommDestroy(c);
-  for (size_t r = 0; r < g->devs.size(); ++r) if (g->band_arena[r]) { DeviceGuard dg(g->devs[r]); dev_free(g->band_arena[r]); }
-  if (g->staging) { DeviceGuard dg(g->devs[0]); dev_free(g->staging); }
-  if (g->recv_stream) { DeviceGuard dg(g->devs[0]); (void)hipStreamDestroy(g->recv_stream); }
+  { DeviceGuard dg(g->devs[0]); Stream last(std::move(g->recv_stream)); }   // (idle: waited for above; destroyed on the device it was made on)
   for (ist_ctx* c : g->ctx) ist_ctx_destroy(c);
-  delete g;
+  delete g;                               // (the arenas and the staging block: each with its own device current)
 }
 
 int64_t ist_debug_host_sink_stitches(void) { return g_host_sink_stitches.load(std::memory_order_relaxed); }
@@ -395,7 +388,7 @@ int group_launch_locked(ist_group_job* job, const void* const* src, const size_t
     auto& u = job->units[k];
     if (u.local) rc = launch_band(job, k, src, src_pitch, dst, dst_pitch, false);
     else {
-      rc = launch_band(job, k, src, src_pitch, static_cast<uint8_t*>(g->band_arena[static_cast<size_t>(u.rank)]) + u.band_off,
+      rc = launch_band(job, k, src, src_pitch, static_cast<uint8_t*>(g->band_arena[static_cast<size_t>(u.rank)].p) + u.band_off,
                        static_cast<size_t>(u.X1 - u.X0) * 4, true);
       any_remote = true;
     }
@@ -413,8 +406,8 @@ int group_launch_locked(ist_group_job* job, const void* const* src, const size_t
     if (u.local) continue;
     const size_t bytes = unit_bytes(u);
     void* into = u.in_place ? static_cast<void*>(static_cast<uint8_t*>(dst) + static_cast<size_t>(u.Y0) * dst_pitch)
-                            : static_cast<void*>(static_cast<uint8_t*>(g->staging) + u.staging_off);
-    const void* band = static_cast<const uint8_t*>(g->band_arena[static_cast<size_t>(u.rank)]) + u.band_off;
+                            : static_cast<void*>(static_cast<uint8_t*>(g->staging.p) + u.staging_off);
+    const void* band = static_cast<const uint8_t*>(g->band_arena[static_cast<size_t>(u.rank)].p) + u.band_off;
     nrc = R->Send(band, bytes, kNcclUint8, 0, g->comm[static_cast<size_t>(u.rank)], g->ctx[static_cast<size_t>(u.rank)]->stream);
     if (!nrc) nrc = R->Recv(into, bytes, kNcclUint8, u.rank, g->comm[0], g->recv_stream);
     if (nrc) { (void)R->GroupEnd(); return nccl_fail("ncclSend/ncclRecv", nrc); }
@@ -424,7 +417,7 @@ int group_launch_locked(ist_group_job* job, const void* const* src, const size_t
   // 4. staged bands: placed behind their receive (same stream)
   for (auto& u : job->units) {
     if (!u.place_job) continue;
-    const void* band = static_cast<const uint8_t*>(g->staging) + u.staging_off;
+    const void* band = static_cast<const uint8_t*>(g->staging.p) + u.staging_off;
     const size_t bp = static_cast<size_t>(u.X1 - u.X0) * 4;
     rc = ist_job_launch(u.place_job.get(), &band, &bp, 1, dst, dst_pitch, g->recv_stream);
     if (rc) return rc;
@@ -522,7 +515,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   ist_ctx* root = g->ctx[0];
   {
     DeviceGuard dg(root->device);
-    rc = grow_device(&root->scratch_dst, &root->scratch_dst_bytes, canvas_bytes);
+    rc = root->scratch_dst.grow(canvas_bytes);
     if (rc) return rc;
   }
   uint8_t* host = static_cast<uint8_t*>(pool_take(canvas_bytes));
@@ -535,9 +528,9 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
     rc = lay[r].add(images, n_images, src, src_pitch, shard_holdings(mine[r]));
     if (rc) return rc;
     DeviceGuard dg(g->devs[r]);
-    rc = grow_device(&g->ctx[r]->scratch_src, &g->ctx[r]->scratch_src_bytes, lay[r].bytes());
+    rc = g->ctx[r]->scratch_src.grow(lay[r].bytes());
     if (rc) return rc;
-    at[r] = lay[r].place(g->ctx[r]->scratch_src);
+    at[r] = lay[r].place(g->ctx[r]->scratch_src.p);
   }
   std::vector<const void*> psrc(job->parts.size(), nullptr);
   std::vector<size_t> ppitch(job->parts.size(), 0);
@@ -563,7 +556,7 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
         for (size_t k = 0; k < job->units.size() && rc2 == IST_OK; ++k) {
           const auto& u = job->units[k];
           if (static_cast<size_t>(u.rank) != r) continue;
-          uint8_t* band = static_cast<uint8_t*>(g->band_arena[r]) + u.band_off;
+          uint8_t* band = static_cast<uint8_t*>(g->band_arena[r].p) + u.band_off;
           rc2 = launch_band(job, k, psrc.data(), ppitch.data(), band, canvas_pitch, true);
           if (rc2 == IST_OK && hipMemcpyAsync(host + static_cast<size_t>(u.Y0) * canvas_pitch, band, unit_bytes(u), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
             (void)hipGetLastError();
@@ -571,10 +564,10 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
           }
         }
         if (rc2 == IST_OK && r == 0) {                 // the root: everything that is not a band
-          rc2 = launch_root(job, psrc.data(), ppitch.data(), root->scratch_dst, canvas_pitch);
+          rc2 = launch_root(job, psrc.data(), ppitch.data(), root->scratch_dst.p, canvas_pitch);
           for (size_t q = 0; q < job->root_rows.size() && rc2 == IST_OK; ++q) {
             const size_t y0 = static_cast<size_t>(job->root_rows[q].y0), y1 = static_cast<size_t>(job->root_rows[q].y1);
-            if (hipMemcpyAsync(host + y0 * canvas_pitch, static_cast<uint8_t*>(root->scratch_dst) + y0 * canvas_pitch, (y1 - y0) * canvas_pitch, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+            if (hipMemcpyAsync(host + y0 * canvas_pitch, static_cast<uint8_t*>(root->scratch_dst.p) + y0 * canvas_pitch, (y1 - y0) * canvas_pitch, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
               (void)hipGetLastError();
               rc2 = fail(IST_E_HIP, "result readback failed");
             }
@@ -588,12 +581,12 @@ int ist_group_stitch_rgba8(ist_group* g, const ist_image_desc* images, const uin
   }
   for (size_t r = 0; r < nd; ++r) if (up_rc[r]) return fail(up_rc[r], up_err[r]);
   if (!host_sink) {
-    rc = group_launch_locked(job, psrc.data(), ppitch.data(), root->scratch_dst, canvas_pitch);
+    rc = group_launch_locked(job, psrc.data(), ppitch.data(), root->scratch_dst.p, canvas_pitch);
     if (rc) return rc;
     rc = group_sync_locked(g);
     if (rc) return rc;
     DeviceGuard dg(root->device);
-    if (hipMemcpyAsync(host, root->scratch_dst, canvas_bytes, hipMemcpyDeviceToHost, root->stream) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "result readback failed"); }
+    if (hipMemcpyAsync(host, root->scratch_dst.p, canvas_bytes, hipMemcpyDeviceToHost, root->stream) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "result readback failed"); }
   }
   rc = group_sync_locked(g);
   if (rc) return rc;

@@ -800,10 +800,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   // ---- every slab's compression goes out now, each followed by the copy of its per-chunk results and an event
   // (pinned: a device-to-host copy into pageable memory would block this thread until the slab is compressed, and the
   // slabs' launches would no longer run ahead of the host)
-  struct Events { std::vector<hipEvent_t> ev; ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } } evs;   // (a slab that was never launched has no event: destroying NULL would leave a sticky error for the next launch check)
-  evs.ev.assign(n_slabs, nullptr);
-  Events gathered;
-  gathered.ev.assign(n_slabs, nullptr);
+  std::vector<Event> evs(n_slabs), gathered(n_slabs);   // (a slab that was never launched has an empty one)
 
   struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(20 * per_slab * n_slabs))};
   if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
@@ -811,19 +808,16 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   // staged copy per slab on the aux stream; those, and the header patches, were ~0.5 ms of stream time per slab)
   struct PinnedDst { int64_t* p; ~PinnedDst() { if (p) pool_give(p); } } dstp{static_cast<int64_t*>(pool_take(8 * n))};
   if (!dstp.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
-  unsigned long long* d_dbg = nullptr;
+  DevBuf dbg;
   // EVERY way out of this function below - the errors too - first waits for both streams: the kernels in flight write their
   // per-chunk results into `res` and read `dstp` in place, and a block given back to the pool while slab s+1 is still
   // compressing could be handed to another thread's call.  (Declared after the two blocks: destroyed before them.)
   struct Drain {
-    hipStream_t a, b, c; unsigned long long** dbg; bool armed = true;
-    ~Drain() {
-      if (armed) { (void)hipStreamSynchronize(a); if (b != a) (void)hipStreamSynchronize(b); if (c != a && c != b) (void)hipStreamSynchronize(c); }
-      if (*dbg) { dev_free(*dbg); *dbg = nullptr; }
-    }
-  } drain{stream, aux, stream2, &d_dbg};
+    hipStream_t a, b, c; bool armed = true;
+    ~Drain() { if (armed) { (void)hipStreamSynchronize(a); if (b != a) (void)hipStreamSynchronize(b); if (c != a && c != b) (void)hipStreamSynchronize(c); } }
+  } drain{stream, aux, stream2};
   static const bool phases = tuning_mode() && std::getenv("IST_PNG_PHASES") != nullptr;      // (IST_TUNING=1 processes only)
-  if (phases && dev_malloc(reinterpret_cast<void**>(&d_dbg), 64 * n) != hipSuccess) d_dbg = nullptr;
+  if (phases) { KeepLastError tolerated; (void)dbg.grow(64 * n); }
   // test knob (IST_TUNING=1 IST_PNG_FAIL_AT=<slab>): fail the layout of that slab the way a damaged result would, so that the
   // error path above is exercised with kernels in flight
   static const long fail_at = (tuning_mode() && std::getenv("IST_PNG_FAIL_AT")) ? std::atol(std::getenv("IST_PNG_FAIL_AT")) : -1;
@@ -845,13 +839,13 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     A.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); A.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
     A.rows_per_chunk = g.rows_per_chunk; A.pieces_per_row = g.pieces_per_row; A.piece_px = g.piece_px;
     A.chunk0 = static_cast<int64_t>(c0);
-    A.dbg = d_dbg;
+    A.dbg = static_cast<unsigned long long*>(dbg.p);
     if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     PNG_HIP(hipGetLastError());
     tl_mark("png:   compression launched, slab", static_cast<long>(s));
-    PNG_HIP(hipEventCreateWithFlags(&evs.ev[s], hipEventDisableTiming));
-    PNG_HIP(hipEventRecord(evs.ev[s], st));
+    { const int rc = evs[s].ensure(); if (rc) return rc; }
+    PNG_HIP(hipEventRecord(evs[s], st));
     return IST_OK;
   };
   // one slab ahead: slab s+1 is compressing while the host lays out slab s and the aux stream carries it away
@@ -866,7 +860,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   for (size_t s = 0; s < n_slabs; ++s) {
     const size_t c0 = slab_at[s], cn = slab_at[s + 1] - c0;
     if (s + 1 < n_slabs) { const int rc = compress(s + 1); if (rc) return rc; tl_mark("png: submitted the compression of slab", static_cast<long>(s + 1)); }
-    PNG_HIP(hipEventSynchronize(evs.ev[s]));
+    PNG_HIP(hipEventSynchronize(evs[s]));
     tl_mark("png: compressed (event passed), slab", static_cast<long>(s));
     if (fail_at >= 0 && static_cast<size_t>(fail_at) == s) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length (forced: IST_PNG_FAIL_AT)");
     const uint8_t* r = res.p + 20 * per_slab * s;
@@ -894,9 +888,9 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     PNG_HIP(hipGetLastError());
     tl_mark("png:   gather launched, slab", static_cast<long>(s));
     if (host_out) {
-      PNG_HIP(hipEventCreateWithFlags(&gathered.ev[s], hipEventDisableTiming));
-      PNG_HIP(hipEventRecord(gathered.ev[s], gs));
-      PNG_HIP(hipStreamWaitEvent(aux, gathered.ev[s], 0));
+      { const int rc = gathered[s].ensure(); if (rc) return rc; }
+      PNG_HIP(hipEventRecord(gathered[s], gs));
+      PNG_HIP(hipStreamWaitEvent(aux, gathered[s], 0));
       tl_mark("png:   event created + recorded + aux ordered behind it, slab", static_cast<long>(s));
     }
     if (!host_out)                                     // (with a host sink the headers are written there, below)
@@ -930,9 +924,9 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   if (stream2 != stream) PNG_HIP(hipStreamSynchronize(stream2));
   tl_mark("png: encoder streams idle");
   drain.armed = false;                                 // the streams are idle
-  if (d_dbg) {
+  if (dbg.p) {
     std::vector<unsigned long long> hdbg(8 * n);
-    (void)hipMemcpy(hdbg.data(), d_dbg, 64 * n, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hdbg.data(), dbg.p, 64 * n, hipMemcpyDeviceToHost);
     double sum[6] = {0, 0, 0, 0, 0, 0};
     for (size_t j = 0; j < n; ++j) for (int k = 0; k < 6; ++k) sum[k] += static_cast<double>(hdbg[8 * j + k + 1] - hdbg[8 * j + k]);
     static const char* names[6] = {"A load+filter", "B histogram+adler", "C code build", "D bit counts+scan", "body emit", "E slot write+crc"};

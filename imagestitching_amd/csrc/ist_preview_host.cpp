@@ -15,15 +15,7 @@ namespace ist {
 
 namespace {
 std::atomic<int64_t> g_preview_launches{0};
-
-int ensure_event(hipEvent_t* e) {
-  if (*e) return IST_OK;
-  if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); *e = nullptr; return fail(IST_E_HIP, "hipEventCreate failed"); }
-  return IST_OK;
-}
 }  // namespace
-
-int preview_event(ist_ctx* ctx) { return ensure_event(&ctx->prev_done); }
 
 // Workgroup shape of the reduce for a shape.  A group of per_group output pixels has an x footprint of at most per_group * kx + 2
 // source columns (+ 1 for a rounding error at either end): one 256-column pass while that fits, otherwise one pixel per group and as
@@ -64,15 +56,15 @@ int preview_enqueue(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, 
   if (preview_geometry(w, h, pw, ph, &a)) {
     const size_t need = static_cast<size_t>(ph) * static_cast<size_t>(a.chunks) * static_cast<size_t>(pw) * 16;
     // (growing frees the old block, which waits for the device: a reduce still in flight has finished with it by then)
-    int rc = grow_device(&ctx->scratch_prev, &ctx->scratch_prev_bytes, need);
+    int rc = ctx->scratch_prev.grow(need);
     if (rc) return rc;
-    rc = ensure_event(&ctx->prev_done);
+    rc = ctx->prev_done.ensure();
     if (rc) return rc;
     // one reduce owns the partial sums at a time: a call on another stream than the last one starts behind it
     if (ctx->prev_pending && ctx->prev_last != stream) IST_HIP_OR(hipStreamWaitEvent(stream, ctx->prev_done, 0), "ordering a preview behind the previous one failed");
     a.src = static_cast<const uint8_t*>(src); a.src_pitch = src_pitch;
     a.dst = static_cast<uint8_t*>(dst); a.dst_pitch = dst_pitch;
-    a.partial = static_cast<float*>(ctx->scratch_prev);
+    a.partial = static_cast<float*>(ctx->scratch_prev.p);
     rc = launch_preview(a, opaque, stream);
     if (rc) return rc;
     IST_HIP_OR(hipEventRecord(ctx->prev_done, stream), "hipEventRecord failed");
@@ -111,10 +103,11 @@ int PreviewTail::prepare() {
   int rc = ist_preview_fit(w, h, pv->box_w, pv->box_h, &pw, &ph);
   if (rc) return rc;
   const size_t bytes = static_cast<size_t>(pw) * 4 * static_cast<size_t>(ph);
-  rc = grow_device(&ctx->prev_out, &ctx->prev_out_bytes, bytes);
+  rc = ctx->prev_out.grow(bytes);
   if (rc) return rc;
-  if (!ctx->prev_stream && hipStreamCreateWithFlags(&ctx->prev_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->prev_stream = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
-  rc = ensure_event(&ctx->prev_ready);
+  rc = ctx->prev_stream.ensure();
+  if (rc) return rc;
+  rc = ctx->prev_ready.ensure();
   if (rc) return rc;
   host = static_cast<uint8_t*>(pool_take(bytes));
   if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the preview");
@@ -127,9 +120,9 @@ int PreviewTail::queue(hipStream_t reader) {
   IST_HIP_OR(hipStreamWaitEvent(ctx->prev_stream, ctx->prev_ready, 0), "ordering the preview behind the render failed");
   queued = true;                                            // (from here on the destructor waits for the stream)
   // (not `opaque`: a canvas rendered from a recorded op list may hold translucent pixels; for an opaque one the bytes are the same rule)
-  const int rc = preview_enqueue(ctx, canvas, pitch, w, h, false, ctx->prev_out, static_cast<size_t>(pw) * 4, pw, ph, ctx->prev_stream);
+  const int rc = preview_enqueue(ctx, canvas, pitch, w, h, false, ctx->prev_out.p, static_cast<size_t>(pw) * 4, pw, ph, ctx->prev_stream);
   if (rc) return rc;
-  IST_HIP_OR(hipMemcpyAsync(host, ctx->prev_out, static_cast<size_t>(pw) * 4 * static_cast<size_t>(ph), hipMemcpyDeviceToHost, ctx->prev_stream), "queueing the preview's readback failed");
+  IST_HIP_OR(hipMemcpyAsync(host, ctx->prev_out.p, static_cast<size_t>(pw) * 4 * static_cast<size_t>(ph), hipMemcpyDeviceToHost, ctx->prev_stream), "queueing the preview's readback failed");
   return IST_OK;
 }
 

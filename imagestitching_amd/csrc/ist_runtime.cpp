@@ -28,25 +28,13 @@ int ctx_png_form_check(const ist_ctx* ctx) {
     return fail(IST_E_UNSUPPORTED, "RGB PNG export needs the compressing encoder (pngLevel 1): the stored form writes RGBA only");
   return IST_OK;
 }
-int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p) {
-  const int rc = grow_device(&ctx->scratch_png, &ctx->scratch_png_bytes, need);
-  *p = ctx->scratch_png;
-  return rc;
-}
+int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p) { const int rc = ctx->scratch_png.grow(need); *p = ctx->scratch_png.p; return rc; }
 
 static std::atomic<int64_t> g_dev_allocs{0};
+std::atomic<int64_t> g_live_handles[4];
 int dev_malloc(void** p, size_t bytes) {
   g_dev_allocs.fetch_add(1, std::memory_order_relaxed);
   return static_cast<int>(hipMalloc(p, bytes));
-}
-void dev_free(void* p) { if (p) (void)hipFree(p); }
-
-int grow_device(void** p, size_t* have, size_t need) {
-  if (*have >= need) return IST_OK;
-  if (*p) { dev_free(*p); *p = nullptr; *have = 0; }
-  if (dev_malloc(p, need) != 0) { (void)hipGetLastError(); return fail(IST_E_NOMEM, "out of device memory (" + std::to_string(need >> 20) + " MiB)"); }
-  *have = need;
-  return IST_OK;
 }
 
 // A buffer the library hands to the caller (freed with ist_free): a pinned block from the pool, filled by ONE linear DMA
@@ -63,21 +51,13 @@ int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t*
   return IST_OK;
 }
 
-// a stream of the context, made on first need at the highest priority (`lowest`: the lowest)
-static int ensure_stream(hipStream_t* s, bool lowest = false) {
-  if (*s) return IST_OK;
-  int lo = 0, hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  if (hipStreamCreateWithPriority(s, hipStreamNonBlocking, lowest ? lo : hi) != hipSuccess) { (void)hipGetLastError(); *s = nullptr; return fail(IST_E_HIP, "hipStreamCreate failed"); }
-  return IST_OK;
-}
 // the context's second stream (high priority: its small kernels should not queue behind thousands of workgroups of the first)
 int ensure_aux(ist_ctx* ctx) {
   static const bool lowest = tuning_mode() && std::getenv("IST_AUX_PRIORITY") && !std::atoi(std::getenv("IST_AUX_PRIORITY"));     // A/B knob: 0 = lowest
-  return ensure_stream(&ctx->aux, lowest);
+  return ctx->aux.ensure(lowest ? Stream::kLowest : Stream::kHighest);
 }
 // the render stream (high priority: its short kernels should not queue behind the PNG encoder's thousands of workgroups)
-int ensure_render(ist_ctx* ctx) { return ensure_stream(&ctx->render); }
+int ensure_render(ist_ctx* ctx) { return ctx->render.ensure(Stream::kHighest); }
 
 // The PNG file of a canvas in device memory -> a pooled pinned block (freed with ist_free).  `dfile` = device scratch of
 // at least ist_png_bound bytes (nullptr: the context's own).  The compressing encoder hands the file over slab by slab
@@ -103,16 +83,16 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
   { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int64_t cap = ist_png_bound(w, h);
   if (!dfile) {
-    const int rc = grow_device(&ctx->scratch_file, &ctx->scratch_file_bytes, static_cast<size_t>(cap));
+    const int rc = ctx->scratch_file.grow(static_cast<size_t>(cap));
     if (rc) return rc;
-    dfile = ctx->scratch_file;
+    dfile = ctx->scratch_file.p;
   }
   int64_t len = 0;
   if (ctx->png_level > 0) {
     { const int rc = ensure_aux(ctx); if (rc) return rc; }
     uint8_t* host = static_cast<uint8_t*>(pool_take(static_cast<size_t>(cap)));
     if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the result");
-    if (!ctx->png2 && hipStreamCreateWithFlags(&ctx->png2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->png2 = nullptr; }   // (without it the slabs share one stream)
+    { KeepLastError tolerated; (void)ctx->png2.ensure(); }   // (without it the slabs share one stream)
     const int rc = png_encode_device_deflate(ctx, canvas, pitch, w, h, dfile, cap, &len, ctx->stream, host, ctx->aux, need_rows, slab_rows_hint, ctx->png2);
     if (rc) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamSynchronize(ctx->stream); if (ctx->png2) (void)hipStreamSynchronize(ctx->png2); pool_give(host); return rc; }
     if (preview) { const int rc2 = tail.finish(); if (rc2) { pool_give(host); return rc2; } }
@@ -137,6 +117,12 @@ extern "C" {
 
 int64_t ist_debug_device_allocs(void) { return g_dev_allocs.load(std::memory_order_relaxed); }
 
+int ist_debug_live_handles(int64_t out[4]) {
+  if (!out) return fail(IST_E_INVALID, "ist_debug_live_handles: NULL output");
+  for (int k = 0; k < 4; ++k) out[k] = g_live_handles[k].load(std::memory_order_relaxed);
+  return IST_OK;
+}
+
 int ist_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -151,10 +137,7 @@ ist_ctx* ist_ctx_create(int device) {
   if (!g.ok) { fail(IST_E_NO_DEVICE, "hipSetDevice failed"); return nullptr; }
   std::unique_ptr<ist_ctx> c(new ist_ctx);
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    fail(IST_E_HIP, "hipStreamCreate failed");
-    return nullptr;
-  }
+  if (c->stream.ensure() != IST_OK) return nullptr;
   return c.release();
 }
 
@@ -181,58 +164,23 @@ int ist_debug_png_grid(int64_t w, int64_t h, int color, int64_t out[4]) {
 int ist_ctx_sync(ist_ctx* ctx) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   DeviceGuard g(ctx->device);
-  bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
-  if (ctx->aux) ok = (hipStreamSynchronize(ctx->aux) == hipSuccess) && ok;
-  if (ctx->render) ok = (hipStreamSynchronize(ctx->render) == hipSuccess) && ok;
-  if (ctx->png2) ok = (hipStreamSynchronize(ctx->png2) == hipSuccess) && ok;
-  if (ctx->prev_stream) ok = (hipStreamSynchronize(ctx->prev_stream) == hipSuccess) && ok;
+  // (every stream, the per-image ones included: those are idle on return from every entry point, so a caller observes nothing of it)
+  bool ok = true;
+  for (hipStream_t st : ctx->streams()) ok = (hipStreamSynchronize(st) == hipSuccess) && ok;
   if (ctx->stager) ok = (ctx->stager->sync() == IST_OK) && ok;
   if (!ok) { (void)hipGetLastError(); return fail(IST_E_HIP, "hipStreamSynchronize failed"); }
   return IST_OK;
 }
 
+// Everything the context holds is a member that releases itself (ist_ctx.h: the streams first, each waited for).  What is left to say
+// here is the order of what is NOT a plain member: the kept preview job hands its tables to the pool, the workers and the stager stop.
 void ist_ctx_destroy(ist_ctx* ctx) {
   if (!ctx) return;
   DeviceGuard g(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
+  for (hipStream_t st : ctx->streams()) (void)hipStreamSynchronize(st);
   if (ctx->prev_job) ist_job_destroy(ctx->prev_job);
-  if (ctx->prev_stream) { (void)hipStreamSynchronize(ctx->prev_stream); (void)hipStreamDestroy(ctx->prev_stream); }
-  if (ctx->prev_done) { (void)hipEventSynchronize(ctx->prev_done); (void)hipEventDestroy(ctx->prev_done); }
-  if (ctx->prev_ready) (void)hipEventDestroy(ctx->prev_ready);
-  dev_free(ctx->scratch_prev);
-  dev_free(ctx->prev_out);
-  dev_free(ctx->scratch_src);
-  dev_free(ctx->scratch_dst);
-  dev_free(ctx->scratch_dec);
-  dev_free(ctx->scratch_huff);
-  dev_free(ctx->scratch_png);
-  dev_free(ctx->scratch_file);
-  dev_free(ctx->scratch_jpg);
-  dev_free(ctx->scratch_jpg_counts);
-  dev_free(ctx->scratch_arena);
-  dev_free(ctx->scratch_ent);
-  for (hipStream_t st : ctx->img_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  for (hipEvent_t ev : ctx->img_event) if (ev) (void)hipEventDestroy(ev);
-  for (void* q : ctx->img_huff) dev_free(q);
-  if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-  if (ctx->render) { (void)hipStreamSynchronize(ctx->render); (void)hipStreamDestroy(ctx->render); }
-  if (ctx->png2) { (void)hipStreamSynchronize(ctx->png2); (void)hipStreamDestroy(ctx->png2); }
-  if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
-  for (const ist_ctx::TableBlock& b : ctx->table_pool) dev_free(b.p);
-  for (ist_ctx::BatchSlot& s : ctx->batch_ring) {
-    if (s.done) { (void)hipEventSynchronize(s.done); (void)hipEventDestroy(s.done); }
-    if (s.host) (void)hipHostFree(s.host);
-    dev_free(s.dev);
-  }
-  for (ist_ctx::BatchHalf& h : ctx->batch_half) {
-    dev_free(h.tab); dev_free(h.src); dev_free(h.dst); dev_free(h.file);
-    if (h.kernel_done) (void)hipEventDestroy(h.kernel_done);
-    if (h.read_done) (void)hipEventDestroy(h.read_done);
-  }
   ctx->workers.reset();
   ctx->stager.reset();
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -374,20 +322,19 @@ ist_job* ist_job_create(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const 
       std::lock_guard<std::mutex> lk(ctx->table_mu);
       for (size_t k = 0; k < ctx->table_pool.size(); ++k)
         if (ctx->table_pool[k].bytes >= total && ctx->table_pool[k].bytes <= 4 * total + (1u << 20)) {
-          job->d_tables = ctx->table_pool[k].p; job->d_tables_bytes = ctx->table_pool[k].bytes;
+          job->d_tables = std::move(ctx->table_pool[k]);
           ctx->table_pool.erase(ctx->table_pool.begin() + static_cast<std::ptrdiff_t>(k));
           break;
         }
     }
-    if (!job->d_tables && dev_malloc(reinterpret_cast<void**>(&job->d_tables), total) == hipSuccess) job->d_tables_bytes = total;
-    if (!job->d_tables ||
-        hipMemcpy(job->d_tables, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {      // blocking: the tables are in place when this returns
+    if (job->d_tables.grow(total) != IST_OK ||
+        hipMemcpy(job->d_tables.p, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {      // blocking: the tables are in place when this returns
       (void)hipGetLastError();
       fail(IST_E_HIP, "uploading the op tables failed");
       ist_job_destroy(job.release());
       return nullptr;
     }
-    point_tables(job.get(), lay, job->d_tables);
+    point_tables(job.get(), lay, static_cast<uint8_t*>(job->d_tables.p));
   }
   return job.release();
 }
@@ -434,22 +381,14 @@ void ist_job_destroy(ist_job* job) {
         if (hipStreamSynchronize(job->launched_on[k]) != hipSuccess) { (void)hipGetLastError(); per_stream = false; }
       if (!per_stream) { idle = hipDeviceSynchronize() == hipSuccess; if (!idle) (void)hipGetLastError(); }
     }
-    if (job->d_tables) {
-      bool kept = false;
-      uint8_t* evicted = nullptr;
-      if (idle) {
-        std::lock_guard<std::mutex> lk(job->ctx->table_mu);
-        if (job->d_tables_bytes <= (64u << 20)) {
-          // a full pool gives up its OLDEST block for this one, so that a workload that repeats itself (a restitch of the same
-          // layouts) finds the blocks it needs there again instead of allocating on every call behind blocks of earlier work
-          std::vector<ist_ctx::TableBlock>& pool = job->ctx->table_pool;
-          if (static_cast<int>(pool.size()) >= ist_ctx::kTablePool) { evicted = pool.front().p; pool.erase(pool.begin()); }
-          pool.push_back(ist_ctx::TableBlock{job->d_tables, job->d_tables_bytes});
-          kept = true;
-        }
-      }
-      if (evicted) dev_free(evicted);
-      if (!kept) dev_free(job->d_tables);
+    DevBuf evicted;                       // (freed outside the lock)
+    if (job->d_tables.p && idle && job->d_tables.bytes <= (64u << 20)) {
+      // a full pool gives up its OLDEST block for this one, so that a workload that repeats itself (a restitch of the same
+      // layouts) finds the blocks it needs there again instead of allocating on every call behind blocks of earlier work
+      std::lock_guard<std::mutex> lk(job->ctx->table_mu);
+      std::vector<DevBuf>& pool = job->ctx->table_pool;
+      if (static_cast<int>(pool.size()) >= ist_ctx::kTablePool) { evicted = std::move(pool.front()); pool.erase(pool.begin()); }
+      pool.push_back(std::move(job->d_tables));
     }
   }
   delete job;

@@ -116,7 +116,7 @@ int launch_sub_batch(ist_ctx* ctx, std::vector<Reduce>& items, size_t first, siz
   Form form[2];
   size_t at = 0;
   for (size_t q = first; q < last; ++q) {                   // every item its own range of the partial sums
-    items[q].a.partial = reinterpret_cast<float*>(static_cast<uint8_t*>(ctx->scratch_prev) + at);
+    items[q].a.partial = reinterpret_cast<float*>(static_cast<uint8_t*>(ctx->scratch_prev.p) + at);
     at += items[q].partial_bytes;
     form[items[q].opaque ? 1 : 0].idx.push_back(q);
   }
@@ -132,7 +132,7 @@ int launch_sub_batch(ist_ctx* ctx, std::vector<Reduce>& items, size_t first, siz
   ist_ctx::BatchSlot* slot = nullptr;
   int rc = batch_take_slot(ctx, total, &slot);
   if (rc) return rc;
-  uint8_t* h = static_cast<uint8_t*>(slot->host);
+  uint8_t* h = static_cast<uint8_t*>(slot->host.p);
   for (Form& F : form) {
     if (F.idx.empty()) continue;
     const size_t m = F.idx.size();
@@ -148,7 +148,7 @@ int launch_sub_batch(ist_ctx* ctx, std::vector<Reduce>& items, size_t first, siz
     }
     wb[m] = F.wgs; pb[m] = F.px;
   }
-  uint8_t* d = static_cast<uint8_t*>(slot->dev);
+  uint8_t* d = static_cast<uint8_t*>(slot->dev.p);
   if (hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, stream) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "uploading the thumbnail table failed"); }
   int launches = 0;
   for (int f = 0; f < 2 && rc == IST_OK; ++f) {
@@ -224,9 +224,9 @@ int thumbs_enqueue(ist_ctx* ctx, const ist_image_desc* descs, const void* const*
     cut.push_back(red.size());
     std::lock_guard<std::mutex> lock(ctx->prev_mu);
     // (growing frees the old block, which waits for the device: a reduce still in flight has finished with it by then)
-    int rc = grow_device(&ctx->scratch_prev, &ctx->scratch_prev_bytes, most);
+    int rc = ctx->scratch_prev.grow(most);
     if (rc) return rc;
-    rc = preview_event(ctx);
+    rc = ctx->prev_done.ensure();
     if (rc) return rc;
     // one reduce owns the partial sums at a time: a call on another stream than the last one starts behind it (the sub-batches of this
     // call follow each other on `stream`)
@@ -299,11 +299,11 @@ int ist_bitmaps_thumbs(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, const is
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
-  rc = grow_device(&ctx->prev_out, &ctx->prev_out_bytes, static_cast<size_t>(total));
+  rc = ctx->prev_out.grow(static_cast<size_t>(total));
   if (rc) return rc;
-  rc = thumbs_enqueue(ctx, descs.data(), src.data(), pitch.data(), n, out, static_cast<uint8_t*>(ctx->prev_out), ctx->stream);
+  rc = thumbs_enqueue(ctx, descs.data(), src.data(), pitch.data(), n, out, static_cast<uint8_t*>(ctx->prev_out.p), ctx->stream);
   if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // (nothing of this call is in flight when it returns)
-  return read_back_pooled(ctx->prev_out, static_cast<size_t>(total), ctx->stream, out_pixels);
+  return read_back_pooled(ctx->prev_out.p, static_cast<size_t>(total), ctx->stream, out_pixels);
 }
 
 }  // extern "C"

@@ -141,6 +141,11 @@ IST_API int ist_device_count(void);                                   /* 0 when 
 /* device allocations (hipMalloc calls) the library has made in this process so far.  A measurement aid for hosts and tests:
  * the steady state of every entry point allocates nothing (scratch, arenas and table blocks are kept and re-used). */
 IST_API int64_t ist_debug_device_allocs(void);
+/* What the library has asked the HIP runtime for in this process and not yet given back: out[0] device blocks, out[1] pinned host
+ * blocks (the pool of result buffers that ist_free / ist_pool_trim manage is not counted), out[2] streams, out[3] events.  A test aid:
+ * the steady state of every entry point leaves all four where they were, and destroying a context (group, bitmap, job) returns
+ * everything it made.  IST_E_INVALID when out is NULL; four zeros in a process that has not used a device. */
+IST_API int ist_debug_live_handles(int64_t out[4]);
 /* JPEG files whose entropy-coded scan the GPU Huffman decoder has decoded AND validated in this process so far (files it
  * handed back to the host decoder do not count).  Tests use it to tell the GPU path from the silent host fall-back. */
 IST_API int64_t ist_debug_gpu_entropy_files(void);
