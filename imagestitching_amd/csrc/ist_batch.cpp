@@ -26,8 +26,6 @@ namespace {
 
 std::atomic<int64_t> g_batch_launches{0};
 
-constexpr int kKinds = 7;                               // launch_stitch's kernel forms (Compiled::kernel_kind)
-
 // The host path splits a batch so that sources + canvases of one sub-batch stay under this many device bytes (a larger
 // request runs alone, with the memory its single stitch would take).  Two sub-batches are in flight (Pipeline below), so the
 // context keeps at most twice this much device scratch for batches.
@@ -101,11 +99,12 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
   }
   // one group per kernel form; jobs without tiles (an empty clip) launch nothing
   struct Group { std::vector<int> jobs; int64_t n_tiles = 0; unsigned lds = 0; size_t at_args = 0, at_begin = 0, at_chunk = 0; int64_t n_chunks = 0; };
-  Group grp[kKinds];
+  Group grp[kKernelKinds];
   for (int k = 0; k < n_jobs; ++k) {
     const Compiled& r = *run[static_cast<size_t>(k)];
     if (r.info.n_tiles <= 0) continue;
-    const int kind = std::min(std::max(r.kernel_kind, 0), kKinds - 1);
+    // (a number that names no kind is grouped as the launchers run it, as KIND_GENERAL; the compiler writes none)
+    const int kind = r.kernel_kind >= 0 && r.kernel_kind < kKernelKinds ? r.kernel_kind : KIND_GENERAL;
     Group& G = grp[kind];
     G.jobs.push_back(k);
     G.n_tiles += r.info.n_tiles;
@@ -152,7 +151,7 @@ int ist_jobs_launch(ist_job* const* jobs, int n_jobs, const void* const* src, co
   uint8_t* d = static_cast<uint8_t*>(slot->dev.p);
   if (hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); return fail(IST_E_HIP, "uploading the batch table failed"); }
   int launches = 0;
-  for (int kind = 0; kind < kKinds && rc == IST_OK; ++kind) {
+  for (int kind = 0; kind < kKernelKinds && rc == IST_OK; ++kind) {
     const Group& G = grp[kind];
     if (G.jobs.empty()) continue;
     BatchArgs b;

@@ -235,7 +235,7 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
   const CompileKnobs knobs = read_knobs();
   out->canvas_w = canvas_w; out->canvas_h = canvas_h; out->filter = job_filter | (aa ? IST_FILTER_EDGE_AA : 0);
   out->ops.clear(); out->cells.clear(); out->stacks.clear(); out->bands.clear(); out->tiles.clear();
-  out->lds_words = 0; out->lds_half = 0; out->kernel_kind = 0;
+  out->lds_words = 0; out->lds_half = 0; out->kernel_kind = KIND_COPY;
   out->img_w.assign(static_cast<size_t>(n_images), 0);
   out->img_h.assign(static_cast<size_t>(n_images), 0);
   for (int i = 0; i < n_images; ++i) {
@@ -514,7 +514,7 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
     cell.tile_begin = tiles;
     tiles += nt;
     info.out_pixels += w * h;
-    out->kernel_kind = std::max<int32_t>(out->kernel_kind, (cell.path == PATH_FILL || cell.path == PATH_COPY) ? 0 : (cell.path == PATH_SAMPLE || cell.path == PATH_SAMPLE_LDS || cell.path == PATH_SAMPLE_STREAM) ? 1 : 2);
+    out->kernel_kind = std::max<int32_t>(out->kernel_kind, (cell.path == PATH_FILL || cell.path == PATH_COPY) ? KIND_COPY : (cell.path == PATH_SAMPLE || cell.path == PATH_SAMPLE_LDS || cell.path == PATH_SAMPLE_STREAM) ? KIND_SAMPLE : KIND_GENERAL);
     if (cell.path == PATH_AREA_STREAM) has_area = true; else if (cell.path == PATH_CUBIC_STREAM) has_cubic = true; else if (cell.path == PATH_GENERAL || cell.path == PATH_SWAP_LDS) has_general = true;
     switch (cell.path) {
       case PATH_FILL: info.tiles_fill += nt; break;
@@ -534,10 +534,10 @@ int compile_ops(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4],
     }
   }
   if (tiles > 2147483647LL) return fail(IST_E_OUTPUT_SIZE, "canvas needs more than 2^31 tiles");
-  if (has_area) out->kernel_kind = has_general ? 4 : 3;   // 3: fill / copy / resample / streamed box filter; 4: everything
-  // a cubic job's forms: 5 = fill / copy / streamed box filter / streamed cubic; 6 = + the per-pixel stack under the cubic rule.  One whose
-  // draws all shrink (or are copies) holds neither and launches what the same job launches under AREA (3) or any filter (0).
-  if (cubic && (has_cubic || has_general)) out->kernel_kind = has_general ? 6 : 5;
+  if (has_area) out->kernel_kind = has_general ? KIND_FULL : KIND_AREA;
+  // a cubic job has forms of its own (ist_launch.h).  One whose draws all shrink (or are copies) holds neither a cubic nor a per-pixel cell
+  // and launches what the same job launches under AREA (KIND_AREA) or any filter (KIND_COPY).
+  if (cubic && (has_cubic || has_general)) out->kernel_kind = has_general ? KIND_CUBIC_GENERAL : KIND_CUBIC;
   // launch order of the bands: the expensive tiles (resampling) first, copies next, fills last, so that the workgroups
   // that finish the launch are the short ones (a strip of mixed scales otherwise ends on whatever its last image needs).
   // Stable: bands of one kind keep their canvas order.
@@ -603,7 +603,7 @@ static bool whole(double v) { return v == std::floor(v) && std::fabs(v) < 9.0e15
 std::unique_ptr<FlatTwin> compile_flat_twin(int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                                             const ist_image_desc* images, int n_images, int filter, const Compiled& primary) {
   static const bool off = tuning_mode() && std::getenv("IST_FLAT") && std::atoi(std::getenv("IST_FLAT")) == 0;
-  if (off || primary.kernel_kind != 0) return nullptr;
+  if (off || primary.kernel_kind != KIND_COPY) return nullptr;
   const int64_t row = canvas_w * 4, P = static_cast<int64_t>(kFlatPitch), vw = P / 4;
   // a clip that takes whole rows (the band of a device group, a band of the file pipeline) is a shorter canvas that starts at the clip's
   // first row: the twin addresses bytes from there (dst_delta), so its rows are aligned like the band buffer itself
@@ -673,7 +673,7 @@ std::unique_ptr<FlatTwin> compile_flat_twin(int64_t canvas_w, int64_t canvas_h, 
   ist_image_desc none;
   std::memset(&none, 0, sizeof(none));
   if (compile_ops(vw, vh, clear_rgba, vops.data(), static_cast<int>(vops.size()), vimg.empty() ? &none : vimg.data(), static_cast<int>(vimg.size()),
-                  filter, nullptr, &t->host) != IST_OK || t->host.kernel_kind != 0)
+                  filter, nullptr, &t->host) != IST_OK || t->host.kernel_kind != KIND_COPY)
     return nullptr;
   return t;
 }

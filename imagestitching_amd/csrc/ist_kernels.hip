@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ist_internal.h"
 #include "ist_launch.h"
@@ -143,15 +144,36 @@ IST_DEV uint32_t bilerp_over(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t 
   return o;
 }
 
+// The opaque-or-over choice of the bilinear tile paths for a lane's NP pixels: the packed opaque blend when the draw is
+// opaque (wave-uniform hint) or all 4 NP taps are, else source-over on the background pixel by pixel.  tile_swap_lds calls
+// it.  THREE paths spell the same choice out instead, and a change of the rule must reach them too: tile_sample (through the
+// helper its kernels came out two registers lower, an occupancy they were never measured at) and the row blend of
+// tile_sample_lds / tile_sample_stream (measured slower as a helper; see the note above tile_sample_lds).
+template <int NP>
+IST_DEV void blend_taps(const uint32_t p00[NP], const uint32_t p01[NP], const uint32_t p10[NP], const uint32_t p11[NP],
+                        const float tx[NP], float ty, bool opaque, uint32_t bg, uint32_t o[NP]) {
+  uint32_t all = 0xFFFFFFFFu;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) all &= p00[p] & p01[p] & p10[p] & p11[p];
+  if (opaque || (all >> 24) == 255u) bilerpN_opaque<NP>(p00, p01, p10, p11, tx, ty, o);
+  else {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) o[p] = bilerp_over(p00[p], p01[p], p10[p], p11[p], tx[p], ty, bg, false);
+  }
+}
+
+// the int of an already rounded coordinate, clamp_int(floor(x)) or clamp_int(ceil(x)): held inside the int range first, so
+// that a far-off sample position converts to a defined value (which the callers then clamp to the source's box)
+IST_DEV int clamp_int(double v) { return static_cast<int>(fmin(fmax(v, -2.0e9), 2.0e9)); }
+
 // one axis of the sampling map for the bilinear filter: first tap index (clamped so that base+1 is readable when
 // the axis has >= 2 samples) and the weight of the second tap
 struct Tap { int32_t base; float t; };
 IST_DEV Tap bilinear_tap(double k, double o, int w, int lo, int hi) {
   const double f = (k * (static_cast<double>(w) + 0.5) + o) - 0.5;
-  double fl = floor(f);
+  const double fl = floor(f);
   float t = static_cast<float>(f - fl);
-  fl = fmin(fmax(fl, -2.0e9), 2.0e9);
-  const int i0 = static_cast<int>(fl);
+  const int i0 = clamp_int(fl);
   Tap r;
   const int top = hi > lo ? hi - 1 : lo;
   r.base = min(max(i0, lo), top);
@@ -161,9 +183,7 @@ IST_DEV Tap bilinear_tap(double k, double o, int w, int lo, int hi) {
   return r;
 }
 IST_DEV int nearest_tap(double k, double o, int w, int lo, int hi) {
-  double fl = floor(k * (static_cast<double>(w) + 0.5) + o);
-  fl = fmin(fmax(fl, -2.0e9), 2.0e9);
-  return min(max(static_cast<int>(fl), lo), hi);
+  return min(max(clamp_int(floor(k * (static_cast<double>(w) + 0.5) + o)), lo), hi);
 }
 
 // ragged right edge of a cell: the last lane of a row segment holds 1..3 pixels
@@ -279,9 +299,7 @@ IST_DEV void tile_sample(const LaunchArgs& A, const DevOp op, uint32_t bg, int X
       o.y = over_int(ld4(row + 4 * static_cast<size_t>(ix[1])), bg);
       o.z = over_int(ld4(row + 4 * static_cast<size_t>(ix[2])), bg);
       o.w = over_int(ld4(row + 4 * static_cast<size_t>(ix[3])), bg);
-      uint8_t* dp = d + static_cast<size_t>(Y) * A.dst_pitch;
-      if (nv >= 4) st16(dp, o);
-      else { st4(dp, o.x); if (nv > 1) st4(dp + 4, o.y); if (nv > 2) st4(dp + 8, o.z); }
+      st_px(d + static_cast<size_t>(Y) * A.dst_pitch, o, nv);
     }
     return;
   }
@@ -309,14 +327,15 @@ IST_DEV void tile_sample(const LaunchArgs& A, const DevOp op, uint32_t bg, int X
       wx[p] = tx[p].t;
       all &= p00[p] & p01[p] & p10[p] & p11[p];
     }
+    // (spelled out, not blend_taps<4>: through the helper the kernels that hold this path came out two registers lower - a change
+    // of occupancy this path's callers were never measured at)
     if ((op.flags & OPF_OPAQUE) || (all >> 24) == 255u) bilerp4_opaque(p00, p01, p10, p11, wx, ty.t, o);
     else {
 #pragma unroll
       for (int p = 0; p < 4; ++p) o[p] = bilerp_over(p00[p], p01[p], p10[p], p11[p], wx[p], ty.t, bg, false);
     }
-    uint8_t* dp = d + static_cast<size_t>(Y) * A.dst_pitch;
-    if (nv >= 4) { const u32x4 v = {o[0], o[1], o[2], o[3]}; st16(dp, v); }
-    else { st4(dp, o[0]); if (nv > 1) st4(dp + 4, o[1]); if (nv > 2) st4(dp + 8, o[2]); }
+    const u32x4 v = {o[0], o[1], o[2], o[3]};
+    st_px(d + static_cast<size_t>(Y) * A.dst_pitch, v, nv);
   }
 }
 
@@ -347,6 +366,74 @@ IST_DEV Tap row_tap(const RowTaps& r, int j) {
 // The footprint buffer is dynamic LDS sized by the host (LaunchArgs.lds_half words = the largest footprint any stage
 // of any cell needs).
 
+// x footprint of a tile (wave-uniform): the taps are monotonic in X, so the tile's corners bound it
+struct XFoot { int fx0, wl; };                    // first source column; LDS row stride in pixels (multiple of 4: 16-B aligned rows)
+IST_DEV XFoot x_footprint(const DevOp& op, int X0, int X1) {
+  const Tap xa = bilinear_tap(op.kx, op.ox, X0, op.cx0, op.cx1), xb = bilinear_tap(op.kx, op.ox, X1 - 1, op.cx0, op.cx1);
+  const int fx0 = __builtin_amdgcn_readfirstlane(min(xa.base, xb.base)), fx1 = __builtin_amdgcn_readfirstlane(max(xa.base, xb.base) + 1);
+  XFoot f; f.fx0 = fx0; f.wl = (fx1 - fx0 + 4) & ~3;
+  return f;
+}
+
+// the 16-byte chunk at source column col of row grow, reading nothing past column cx1 (the row's last sampled one): four
+// clamped 4-byte loads where the chunk straddles it
+IST_DEV u32x4 ld16_clamped(const uint8_t* grow, int col, int cx1) {
+  if (col + 3 <= cx1) return ld16(grow + static_cast<size_t>(col) * 4);
+  u32x4 v;
+  v.x = ld4(grow + static_cast<size_t>(min(col, cx1)) * 4);
+  v.y = ld4(grow + static_cast<size_t>(min(col + 1, cx1)) * 4);
+  v.z = ld4(grow + static_cast<size_t>(min(col + 2, cx1)) * 4);
+  v.w = ld4(grow + static_cast<size_t>(min(col + 3, cx1)) * 4);
+  return v;
+}
+
+// One footprint row, `chunks` 16-byte chunks from source column fx0 of grow, -> lrow; a pass moves 64 lanes x 16 B = 256 px.
+// LDS-DMA (global_load_lds_dwordx4): per-lane global address, LDS destination = uniform base + lane*16, no VGPR staging, so
+// every pass of the wave is in flight at once.
+// THE EDGE RULE, for every path that stages rows: reading up to 12 B past the last sampled column is harmless (next row of
+// the same bitmap) except on the last sampled row (last_row: source row >= cy1), where it could leave the allocation: that
+// row's edge pass goes through registers instead, clamped to cx1.
+// Returns whether every pass was DMA: a register pass issues another number of vector memory operations, so a caller that
+// waits with a counted s_waitcnt must stop counting once this is false.
+IST_DEV bool stage_row(const uint8_t* grow, uint32_t* lrow, int chunks, int fx0, int cx1, bool last_row) {
+  const int lane = threadIdx.x & 63;
+  bool dma = true;
+  for (int c0 = 0; c0 < chunks; c0 += 64) {
+    const int c = c0 + lane;
+    const int col = fx0 + 4 * c;
+    const bool edge = last_row && (fx0 + 4 * min(c0 + 63, chunks - 1) + 3 > cx1);    // wave-uniform
+    if (!edge) {
+      if (c < chunks)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)(grow + static_cast<size_t>(col) * 4),
+                                         (__attribute__((address_space(3))) uint32_t*)(lrow + 4 * c0), 16, 0, 0);
+    } else {
+      dma = false;
+      if (c < chunks) *reinterpret_cast<u32x4*>(lrow + 4 * c) = ld16_clamped(grow, col, cx1);
+    }
+  }
+  return dma;
+}
+
+// Lane l owns pixels X0 + l + 64 p (p = 0..NP-1), NOT NP neighbours: consecutive lanes then read LDS words |kx| apart
+// instead of 4|kx| apart (measured: 77 % of the LDS cycles were bank conflicts with the neighbour mapping), and each
+// of the NP stores of a wave is still 256 contiguous bytes.  Lanes past a ragged right edge keep computing (on the
+// last column) and only skip their stores: the row taps are exchanged with v_readlane and the barriers of later
+// stages need every wave.  lx = first tap's index in the staged row, wx = weight of the second (fp64, as the oracle).
+template <int NP>
+IST_DEV void lane_taps(const DevOp& op, int fx0, int Xl, int X1, int lx[NP], float wx[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const Tap t = bilinear_tap(op.kx, op.ox, min(Xl + 64 * p, X1 - 1), op.cx0, op.cx1);
+    lx[p] = t.base - fx0; wx[p] = t.t;
+  }
+}
+
+// THE ROW BLEND of tile_sample_lds and tile_sample_stream - four LDS taps per pixel from the staged rows r0 (weight 1 - ty)
+// and r1 -> the opaque-or-over choice of blend_taps -> one 256-B-per-wave store per 64-pixel column - is the same text in both
+// and stays spelled out: as a shared blend_row<NP> helper it had the parent's registers and instruction counts, and the
+// bilinear draws still measured 0.3-0.4 % slower in every round of a quiet A/B (profiles/r15_bench_vs_parent.txt); spelled
+// out they measure as before.  Change the two copies together.
+
 // NP = pixels per lane and row: the tile is 64 * NP pixels wide.  The host picks the width per cell (ist_compile.cpp): a
 // strong shrink has a tall footprint per output row, and a narrower, taller tile then carries more output pixels per
 // 24 KiB of footprint (kx = ky = 1.87: 128 x 12 instead of 256 x 4) and re-reads fewer halo rows.
@@ -360,10 +447,8 @@ IST_DEV void tile_sample_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, i
   // Measured on MI355X (tools/exp_mixed.py): 2 stages per workgroup beat 1 by ~4 %; more stages leave too few
   // workgroups for the tail; a double-buffered variant (stage s+1 loading under stage s's arithmetic) lost 10-20 %
   // because the second buffer halves the workgroups per CU.
-  // x footprint (wave-uniform, shared by all stages): the taps are monotonic in X, so the tile's corners bound it
-  const Tap xa = bilinear_tap(op.kx, op.ox, X0, op.cx0, op.cx1), xb = bilinear_tap(op.kx, op.ox, X1 - 1, op.cx0, op.cx1);
-  const int fx0 = __builtin_amdgcn_readfirstlane(min(xa.base, xb.base)), fx1 = __builtin_amdgcn_readfirstlane(max(xa.base, xb.base) + 1);
-  const int wl = (fx1 - fx0 + 4) & ~3;            // LDS row stride in pixels (multiple of 4: 16-B aligned rows)
+  const XFoot xf = x_footprint(op, X0, X1);                 // (shared by all stages)
+  const int fx0 = xf.fx0, wl = xf.wl;
   const int nsub = (Y1 - Y0 + sub_h - 1) / sub_h;
   // y footprint of stage s: first source row + row count (wave-uniform)
   auto foot = [&](int s, int* fy0, int* fh) {
@@ -380,38 +465,11 @@ IST_DEV void tile_sample_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, i
   }
   const size_t sp = A.pitch[op.image];
   const uint8_t* src = A.src[op.image];
-  // ---- stage: wave w takes footprint rows w, w+4, ...; a pass moves 64 lanes x 16 B = 256 px of one row.
-  // LDS-DMA (global_load_lds_dwordx4): per-lane global address, LDS destination = uniform base + lane*16, no VGPR
-  // staging, so every pass of the wave is in flight at once.
+  // ---- stage: wave w takes footprint rows w, w+4, ... (stage_row: LDS-DMA, so every pass of the wave is in flight at once)
   const int chunks = wl >> 2;
   auto stage = [&](int fy0, int fh, uint32_t* buf) {
-    for (int r = wave; r < fh; r += 4) {
-      const uint8_t* grow = src + static_cast<size_t>(fy0 + r) * sp;
-      uint32_t* lrow = buf + r * wl;
-      // reading up to 12 B past the last sampled column is harmless (next row of the same bitmap) except on the last
-      // sampled row, where it could leave the allocation: that row's edge pass goes through registers instead
-      const bool last_row = (fy0 + r) >= op.cy1;
-      for (int c0 = 0; c0 < chunks; c0 += 64) {
-        const int c = c0 + lane;
-        const int col = fx0 + 4 * c;
-        const bool edge = last_row && (fx0 + 4 * min(c0 + 63, chunks - 1) + 3 > op.cx1);    // wave-uniform
-        if (!edge) {
-          if (c < chunks)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)(grow + static_cast<size_t>(col) * 4),
-                                             (__attribute__((address_space(3))) uint32_t*)(lrow + 4 * c0), 16, 0, 0);
-        } else if (c < chunks) {
-          u32x4 v;
-          if (col + 3 <= op.cx1) v = ld16(grow + static_cast<size_t>(col) * 4);
-          else {
-            v.x = ld4(grow + static_cast<size_t>(min(col, op.cx1)) * 4);
-            v.y = ld4(grow + static_cast<size_t>(min(col + 1, op.cx1)) * 4);
-            v.z = ld4(grow + static_cast<size_t>(min(col + 2, op.cx1)) * 4);
-            v.w = ld4(grow + static_cast<size_t>(min(col + 3, op.cx1)) * 4);
-          }
-          *reinterpret_cast<u32x4*>(lrow + 4 * c) = v;
-        }
-      }
-    }
+    for (int r = wave; r < fh; r += 4)
+      stage_row(src + static_cast<size_t>(fy0 + r) * sp, buf + r * wl, chunks, fx0, op.cx1, (fy0 + r) >= op.cy1);
   };
   // The first stage's loads go out BEFORE the per-lane set-up below (four fp64 column taps per lane, ~0.4 us): a
   // workgroup that has just started then already has its footprint in flight while it computes them.
@@ -419,19 +477,10 @@ IST_DEV void tile_sample_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, i
   foot(0, &fy0, &fh);
   if (!fresh) __syncthreads();                            // every wave is done reading the previous tile's footprint
   stage(fy0, fh, lds);
-  // Lane l owns pixels X0 + l + 64 p (p = 0..3), NOT 4 neighbours: consecutive lanes then read LDS words |kx| apart
-  // instead of 4|kx| apart (measured: 77 % of the LDS cycles were bank conflicts with the neighbour mapping), and each
-  // of the 4 stores of a wave is still 256 contiguous bytes.  Lanes past a ragged right edge keep computing (on the
-  // last column) and only skip their stores: the row taps below are exchanged with v_readlane and the barriers of
-  // later stages need every wave.
-  int Xl = X0 + lane;
+  int Xl = X0 + lane;                                     // (lane_taps: lane l owns pixels X0 + l + 64 p)
   asm volatile("" : "+v"(Xl));                            // (keeps the tap arithmetic below the loads issued above)
   int lx[NP]; float wx[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const Tap t = bilinear_tap(op.kx, op.ox, min(Xl + 64 * p, X1 - 1), op.cx0, op.cx1);
-    lx[p] = t.base - fx0; wx[p] = t.t;
-  }
+  lane_taps<NP>(op, fx0, Xl, X1, lx, wx);
   uint8_t* d = A.dst + static_cast<size_t>(Xl) * 4;
   const bool opaque = (op.flags & OPF_OPAQUE) != 0;
   // one stage's arithmetic: LDS taps -> blend -> 256-B-per-wave stores
@@ -441,6 +490,7 @@ IST_DEV void tile_sample_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, i
       const Tap ty = row_tap(rows, Y - Ya);
       const uint32_t* r0 = buf + (ty.base - sfy0) * wl;
       const uint32_t* r1 = r0 + wl;
+      // (the row blend is spelled out here and in tile_sample_stream, not shared: see the note above this function)
       uint32_t o[NP];
       uint32_t p00[NP], p01[NP], p10[NP], p11[NP];
 #pragma unroll
@@ -502,9 +552,8 @@ template <int NP>
 IST_DEV void tile_sample_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, int X0, int Y0, int X1, int Y1, int depth, uint32_t* lds, bool fresh) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  const Tap xa = bilinear_tap(op.kx, op.ox, X0, op.cx0, op.cx1), xb = bilinear_tap(op.kx, op.ox, X1 - 1, op.cx0, op.cx1);
-  const int fx0 = __builtin_amdgcn_readfirstlane(min(xa.base, xb.base)), fx1 = __builtin_amdgcn_readfirstlane(max(xa.base, xb.base) + 1);
-  const int wl = (fx1 - fx0 + 4) & ~3;            // LDS row stride in pixels (multiple of 4: 16-B aligned rows)
+  const XFoot xf = x_footprint(op, X0, X1);
+  const int fx0 = xf.fx0, wl = xf.wl;
   if (depth < 2 || Y1 - Y0 > 64 || op.cx1 <= op.cx0 || op.cy1 <= op.cy0 || 8 * depth * wl > A.lds_words) {   // uniform; not expected
     tile_sample<IST_FILTER_BILINEAR>(A, op, bg, X0, Y0, X1, Y1);
     return;
@@ -525,34 +574,7 @@ IST_DEV void tile_sample_stream(const LaunchArgs& A, const DevOp op, uint32_t bg
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int sy = ty.base + h;
-      const uint8_t* grow = src + static_cast<size_t>(sy) * sp;
-      uint32_t* lrow = ring + (2 * slot + h) * wl;
-      // reading up to 12 B past the last sampled column is harmless (next row of the same bitmap) except on the last
-      // sampled row, where it could leave the allocation: that row's edge pass goes through registers instead
-      const bool last_row = sy >= op.cy1;
-      for (int c0 = 0; c0 < chunks; c0 += 64) {
-        const int c = c0 + lane;
-        const int col = fx0 + 4 * c;
-        const bool edge = last_row && (fx0 + 4 * min(c0 + 63, chunks - 1) + 3 > op.cx1);    // wave-uniform
-        if (!edge) {
-          if (c < chunks)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)(grow + static_cast<size_t>(col) * 4),
-                                             (__attribute__((address_space(3))) uint32_t*)(lrow + 4 * c0), 16, 0, 0);
-        } else {
-          counted = false;
-          if (c < chunks) {
-            u32x4 v;
-            if (col + 3 <= op.cx1) v = ld16(grow + static_cast<size_t>(col) * 4);
-            else {
-              v.x = ld4(grow + static_cast<size_t>(min(col, op.cx1)) * 4);
-              v.y = ld4(grow + static_cast<size_t>(min(col + 1, op.cx1)) * 4);
-              v.z = ld4(grow + static_cast<size_t>(min(col + 2, op.cx1)) * 4);
-              v.w = ld4(grow + static_cast<size_t>(min(col + 3, op.cx1)) * 4);
-            }
-            *reinterpret_cast<u32x4*>(lrow + 4 * c) = v;
-          }
-        }
-      }
+      counted &= stage_row(src + static_cast<size_t>(sy) * sp, ring + (2 * slot + h) * wl, chunks, fx0, op.cx1, sy >= op.cy1);
     }
   };
   // prologue: the first depth-1 row pairs go out BEFORE the per-lane set-up (four fp64 column taps per lane)
@@ -561,11 +583,7 @@ IST_DEV void tile_sample_stream(const LaunchArgs& A, const DevOp op, uint32_t bg
   int Xl = X0 + lane;
   asm volatile("" : "+v"(Xl));                            // (keeps the tap arithmetic below the loads issued above)
   int lx[NP]; float wx[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const Tap t = bilinear_tap(op.kx, op.ox, min(Xl + 64 * p, X1 - 1), op.cx0, op.cx1);
-    lx[p] = t.base - fx0; wx[p] = t.t;
-  }
+  lane_taps<NP>(op, fx0, Xl, X1, lx, wx);
   uint8_t* d = A.dst + static_cast<size_t>(Xl) * 4;
   const bool opaque = (op.flags & OPF_OPAQUE) != 0;
   int slot = 0, nslot = ahead;                            // ring slot of row j / of row j + depth - 1
@@ -581,6 +599,7 @@ IST_DEV void tile_sample_stream(const LaunchArgs& A, const DevOp op, uint32_t bg
     const Tap ty = row_tap(rows, wave + 4 * j);
     const uint32_t* r0 = ring + 2 * slot * wl;
     const uint32_t* r1 = r0 + wl;
+    // (the row blend of tile_sample_lds, spelled out: see the note above that function)
     uint32_t o[NP];
     uint32_t p00[NP], p01[NP], p10[NP], p11[NP];
 #pragma unroll
@@ -619,6 +638,28 @@ IST_DEV void tile_sample_stream(const LaunchArgs& A, const DevOp op, uint32_t bg
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kAreaRows = 4;             // source rows in flight per lane in step 1
 
+// steps 1 and 2 of the streamed filters (AREA and CUBIC share them).  acc = one source pixel's weighted sums, (r, g) and (b, a):
+// px joins with weight w2 (both halves equal), premultiplied unless the draw is opaque - two packed FMAs
+// (Both callers reach it through a local lambda, as they reached their own copies of this body.  Called directly, with the same
+// text, the area kernels went from 2 to 15 spilled VGPRs and the cubic kernels from 124 to 192 VGPRs, 4 waves per SIMD to 2.)
+template <bool OPAQUE>
+IST_DEV void acc_px(f32x2 acc[2], uint32_t px, f32x2 w2) {
+  f32x2 lo = {static_cast<float>(ch(px, 0)), static_cast<float>(ch(px, 1))};
+  f32x2 hi = {static_cast<float>(ch(px, 2)), static_cast<float>(px >> 24)};
+  if (!OPAQUE) { const f32x2 a2 = {hi.y, hi.y}; lo = lo * a2; hi.x = hi.x * hi.y; }
+  acc[0] = __builtin_elementwise_fma(w2, lo, acc[0]);
+  acc[1] = __builtin_elementwise_fma(w2, hi, acc[1]);
+}
+// the sums of chunk c's SP source pixels -> one float4 per source pixel in the wave's LDS row
+template <int SP>
+IST_DEV void put_sums(float* row, int c, const f32x2 acc[SP][2]) {
+#pragma unroll
+  for (int q = 0; q < SP; ++q) {
+    const f32x4 t = {acc[q][0].x, acc[q][0].y, acc[q][1].x, acc[q][1].y};
+    *reinterpret_cast<f32x4*>(row + 4 * (SP * c + q)) = t;
+  }
+}
+
 template <int NP, bool OPAQUE>
 IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, int X0, int Y0, int X1, int Y1, uint32_t* lds) {
   const int lane = threadIdx.x & 63;
@@ -627,8 +668,8 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
   // x footprint of the tile (wave-uniform): the boxes of its first and last column bound it
   const double ca = op.kx * (static_cast<double>(X0) + 0.5) + op.ox, cb = op.kx * (static_cast<double>(X1 - 1) + 0.5) + op.ox;
   const double fl = fmin(ca, cb) - 0.5 * bw, fh = fmax(ca, cb) + 0.5 * bw;
-  const int fx0 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(fl), -2.0e9), 2.0e9)));
-  const int fx1 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(ceil(fh), -2.0e9), 2.0e9)) - 1);
+  const int fx0 = __builtin_amdgcn_readfirstlane(clamp_int(floor(fl)));
+  const int fx1 = __builtin_amdgcn_readfirstlane(clamp_int(ceil(fh)) - 1);
   const int wl = (fx1 - fx0 + 1 + 3) & ~3;                  // source pixels per LDS row
   const int chunks = wl >> 2;
   float* row = reinterpret_cast<float*>(lds) + static_cast<size_t>(wave) * (4 * wl);
@@ -641,7 +682,7 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
   for (int p = 0; p < NP; ++p) {
     const double sxc = op.kx * (static_cast<double>(min(Xl + 64 * p, X1 - 1)) + 0.5) + op.ox;
     const double xlo = sxc - 0.5 * bw, xhi = sxc + 0.5 * bw;
-    const int ix0 = static_cast<int>(fmin(fmax(floor(xlo), -2.0e9), 2.0e9)), ix1 = static_cast<int>(fmin(fmax(ceil(xhi), -2.0e9), 2.0e9)) - 1;
+    const int ix0 = clamp_int(floor(xlo)), ix1 = clamp_int(ceil(xhi)) - 1;
     tap[p] = ((ix0 - fx0) << 8) | min(ix1 - ix0 + 1, 255);
     wf[p] = static_cast<float>(fmin(static_cast<double>(ix0) + 1.0, xhi) - fmax(static_cast<double>(ix0), xlo));
     wb[p] = static_cast<float>(fmin(static_cast<double>(ix1) + 1.0, xhi) - fmax(static_cast<double>(ix1), xlo));
@@ -653,8 +694,8 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
     // the rows of this output row's box (wave-uniform)
     const double syc = op.ky * (static_cast<double>(Y) + 0.5) + op.oy;
     const double ylo = syc - 0.5 * bh, yhi = syc + 0.5 * bh;
-    const int iy0 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(ylo), -2.0e9), 2.0e9)));
-    const int iy1 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(ceil(yhi), -2.0e9), 2.0e9)) - 1);
+    const int iy0 = __builtin_amdgcn_readfirstlane(clamp_int(floor(ylo)));
+    const int iy1 = __builtin_amdgcn_readfirstlane(clamp_int(ceil(yhi)) - 1);
     // 1 + 2: column sums of the box's rows -> LDS
     for (int c0 = 0; c0 < chunks; c0 += 64) {
       const int c = c0 + lane;
@@ -664,13 +705,7 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
       f32x2 acc[4][2];                                      // per source pixel: (r, g), (b, a)
 #pragma unroll
       for (int q = 0; q < 4; ++q) { acc[q][0] = f32x2{0.f, 0.f}; acc[q][1] = f32x2{0.f, 0.f}; }
-      auto add_px = [&](int q, uint32_t px, f32x2 w2) {
-        f32x2 lo = {static_cast<float>(ch(px, 0)), static_cast<float>(ch(px, 1))};
-        f32x2 hi = {static_cast<float>(ch(px, 2)), static_cast<float>(px >> 24)};
-        if (!OPAQUE) { const f32x2 a2 = {hi.y, hi.y}; lo = lo * a2; hi.x = hi.x * hi.y; }
-        acc[q][0] = __builtin_elementwise_fma(w2, lo, acc[q][0]);
-        acc[q][1] = __builtin_elementwise_fma(w2, hi, acc[q][1]);
-      };
+      auto add_px = [&](int q, uint32_t px, f32x2 w2) { acc_px<OPAQUE>(acc[q], px, w2); };     // (through a lambda: see acc_px)
       auto weight_of = [&](int y) {                         // overlap of source row y with the box (wave-uniform)
         const float w = static_cast<float>(fmin(static_cast<double>(y) + 1.0, yhi) - fmax(static_cast<double>(y), ylo));
         const float u = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w)));
@@ -706,13 +741,7 @@ IST_DEV void tile_area_stream(const LaunchArgs& A, const DevOp op, uint32_t bg, 
           add_px(3, ld4(g + static_cast<size_t>(min(max(xx + 3, op.cx0), op.cx1)) * 4), w2);
         }
       }
-      if (mine) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 t = {acc[q][0].x, acc[q][0].y, acc[q][1].x, acc[q][1].y};
-          *reinterpret_cast<f32x4*>(row + 4 * (4 * c + q)) = t;
-        }
-      }
+      if (mine) put_sums<4>(row, c, acc);
     }
     __builtin_amdgcn_wave_barrier();
     // 3: the box of every canvas pixel along x, from LDS
@@ -780,8 +809,8 @@ IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg,
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   // x footprint of the tile (wave-uniform): the taps are monotonic in X, so the first and last column bound it
   const double fa = (op.kx * (static_cast<double>(X0) + 0.5) + op.ox) - 0.5, fb = (op.kx * (static_cast<double>(X1 - 1) + 0.5) + op.ox) - 0.5;
-  const int fx0 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(fmin(fa, fb)), -2.0e9), 2.0e9))) - 1;
-  const int fx1 = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(floor(fmax(fa, fb)), -2.0e9), 2.0e9))) + 2;
+  const int fx0 = __builtin_amdgcn_readfirstlane(clamp_int(floor(fmin(fa, fb)))) - 1;
+  const int fx1 = __builtin_amdgcn_readfirstlane(clamp_int(floor(fmax(fa, fb)))) + 2;
   const int wl = (fx1 - fx0 + 1 + 3) & ~3;                  // source pixels per LDS row
   if (16 * wl > A.lds_words) return;                        // uniform; cannot happen (|kx| <= 1 and 256-pixel tiles: the host sizes the row for 260)
   const int chunks = wl / SP;
@@ -796,7 +825,7 @@ IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg,
   for (int p = 0; p < NP; ++p) {
     const double f = (op.kx * (static_cast<double>(min(Xl + 64 * p, X1 - 1)) + 0.5) + op.ox) - 0.5;
     const double fl = floor(f);
-    tap[p] = static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9)) - 1 - fx0;
+    tap[p] = clamp_int(fl) - 1 - fx0;
     cubic_weights(f - fl, wx[p]);
     __builtin_amdgcn_sched_barrier(0);                      // (one pixel's fp64 temporaries at a time)
   }
@@ -807,7 +836,7 @@ IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg,
     // with them a wave of occupancy: slower, LAB_NOTES.md section 2)
     const double f = (op.ky * (static_cast<double>(Y) + 0.5) + op.oy) - 0.5;
     const double fl = floor(f);
-    const int iy = __builtin_amdgcn_readfirstlane(static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9))) - 1;
+    const int iy = __builtin_amdgcn_readfirstlane(clamp_int(fl)) - 1;
     float wyv[4];
     cubic_weights(f - fl, wyv);
     f32x2 wy[4];
@@ -828,13 +857,7 @@ IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg,
       f32x2 acc[SP][2];                                     // per source pixel: (r, g), (b, a)
 #pragma unroll
       for (int q = 0; q < SP; ++q) { acc[q][0] = f32x2{0.f, 0.f}; acc[q][1] = f32x2{0.f, 0.f}; }
-      auto add_px = [&](int q, uint32_t px, f32x2 w2) {
-        f32x2 lo = {static_cast<float>(ch(px, 0)), static_cast<float>(ch(px, 1))};
-        f32x2 hi = {static_cast<float>(ch(px, 2)), static_cast<float>(px >> 24)};
-        if (!OPAQUE) { const f32x2 a2 = {hi.y, hi.y}; lo = lo * a2; hi.x = hi.x * hi.y; }
-        acc[q][0] = __builtin_elementwise_fma(w2, lo, acc[q][0]);
-        acc[q][1] = __builtin_elementwise_fma(w2, hi, acc[q][1]);
-      };
+      auto add_px = [&](int q, uint32_t px, f32x2 w2) { acc_px<OPAQUE>(acc[q], px, w2); };     // (through a lambda: see acc_px)
       if (inside) {
         uint32_t v[4][SP];
 #pragma unroll
@@ -855,13 +878,7 @@ IST_DEV void tile_cubic_stream(const LaunchArgs& A, const DevOp op, uint32_t bg,
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if (mine) {
-#pragma unroll
-        for (int q = 0; q < SP; ++q) {
-          const f32x4 t = {acc[q][0].x, acc[q][0].y, acc[q][1].x, acc[q][1].y};
-          *reinterpret_cast<f32x4*>(row + 4 * (SP * c + q)) = t;
-        }
-      }
+      if (mine) put_sums<SP>(row, c, acc);
     }
     __builtin_amdgcn_wave_barrier();
     // 3: the four column taps of every canvas pixel, from LDS
@@ -920,15 +937,7 @@ IST_DEV bool tile_swap_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, int
       const int i = i0 + u * 256 + tid;
       if (i < total) {
         const int r = i / chunks, c = i - r * chunks;
-        const int col = fx0 + 4 * c;
-        const uint8_t* grow = src + static_cast<size_t>(fy0 + r) * sp;
-        if (col + 3 <= op.cx1) v[u] = ld16(grow + static_cast<size_t>(col) * 4);
-        else {
-          v[u].x = ld4(grow + static_cast<size_t>(min(col, op.cx1)) * 4);
-          v[u].y = ld4(grow + static_cast<size_t>(min(col + 1, op.cx1)) * 4);
-          v[u].z = ld4(grow + static_cast<size_t>(min(col + 2, op.cx1)) * 4);
-          v[u].w = ld4(grow + static_cast<size_t>(min(col + 3, op.cx1)) * 4);
-        }
+        v[u] = ld16_clamped(src + static_cast<size_t>(fy0 + r) * sp, fx0 + 4 * c, op.cx1);
       }
     }
 #pragma unroll
@@ -976,14 +985,9 @@ IST_DEV bool tile_swap_lds(const LaunchArgs& A, const DevOp op, uint32_t bg, int
     const uint32_t* b1 = a1 + pitch;
     // (p00, p01, p10, p11): p01 = next source column, p10 = next source row
     const uint32_t p00[2] = {a0[0], a1[0]}, p01[2] = {b0[0], b1[0]}, p10[2] = {a0[1], a1[1]}, p11[2] = {b0[1], b1[1]};
+    const float tx[2] = {tc0.t, tc1.t};
     uint32_t o[2];
-    if (opaque || ((p00[0] & p01[0] & p10[0] & p11[0] & p00[1] & p01[1] & p10[1] & p11[1]) >> 24) == 255u) {
-      const float tx[2] = {tc0.t, tc1.t};
-      bilerpN_opaque<2>(p00, p01, p10, p11, tx, tr.t, o);
-    } else {
-      o[0] = bilerp_over(p00[0], p01[0], p10[0], p11[0], tc0.t, tr.t, bg, false);
-      o[1] = bilerp_over(p00[1], p01[1], p10[1], p11[1], tc1.t, tr.t, bg, false);
-    }
+    blend_taps<2>(p00, p01, p10, p11, tx, tr.t, opaque, bg, o);
     st4(dcol + static_cast<size_t>(Y) * A.dst_pitch, o[0]);
     st4(dcol + static_cast<size_t>(Y + 4) * A.dst_pitch, o[1]);
   }
@@ -1009,15 +1013,15 @@ IST_DEV CubicAxis cubic_axis(double k, double o, int w) {
   if (a.box) {
     const double bw = fabs(k);
     a.lo = s - 0.5 * bw; a.hi = s + 0.5 * bw;
-    a.i0 = static_cast<int>(fmin(fmax(floor(a.lo), -2.0e9), 2.0e9));
-    a.n = static_cast<int>(fmin(fmax(ceil(a.hi), -2.0e9), 2.0e9)) - a.i0;
+    a.i0 = clamp_int(floor(a.lo));
+    a.n = clamp_int(ceil(a.hi)) - a.i0;
     a.inv = static_cast<float>(1.0 / bw);
     a.w0 = a.w1 = a.w2 = a.w3 = 0.f;
   } else {
     const double f = s - 0.5, fl = floor(f);
     float w4[4];
     cubic_weights(f - fl, w4);
-    a.i0 = static_cast<int>(fmin(fmax(fl, -2.0e9), 2.0e9)) - 1;
+    a.i0 = clamp_int(fl) - 1;
     a.n = 4; a.lo = a.hi = 0.0; a.inv = 1.f;
     a.w0 = w4[0]; a.w1 = w4[1]; a.w2 = w4[2]; a.w3 = w4[3];
   }
@@ -1027,6 +1031,21 @@ IST_DEV float cubic_axis_weight(const CubicAxis& a, int j) {
   if (!a.box) return j == 0 ? a.w0 : j == 1 ? a.w1 : j == 2 ? a.w2 : a.w3;
   const double i = static_cast<double>(a.i0) + static_cast<double>(j);
   return static_cast<float>(fmin(i + 1.0, a.hi) - fmax(i, a.lo)) * a.inv;
+}
+
+// THE composite of pixel_general (the parity contract with the oracle): a sample with premultiplied colour P[] and alpha Aa, both on
+// the 0..255 scale, covering the fraction cov of the pixel, source-over on the premultiplied destination d.  fp64, the same
+// operations in the same order as the oracle (built with -ffp-contract=off: P * cov + d * keep must not fuse).
+IST_DEV uint32_t cover_over(const double P[3], double Aa, double cov, uint32_t d) {
+  const double keep = 1.0 - cov * (Aa / 255.0);
+  uint32_t o = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double v = floor(P[c] * cov + static_cast<double>(ch(d, c)) * keep + 0.5);
+    o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * c);
+  }
+  const double va = floor(Aa * cov + static_cast<double>(d >> 24) * keep + 0.5);
+  return o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
 }
 
 // CUBIC: the instantiation knows IST_FILTER_CUBIC (only the forms launched for cubic jobs do: the others keep their code and registers)
@@ -1056,26 +1075,18 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
       const int iy = nearest_tap(op.ky, op.oy, wy, op.cy0, op.cy1);
       const uint32_t s = ld4(src + static_cast<size_t>(iy) * sp + 4 * static_cast<size_t>(ix));
       if (cov >= 1.0) { d = over_int(s, d); continue; }
-      // fractional edge: coverage-weighted source-over in fp64, the same operations in the same order as the oracle
+      // fractional edge: coverage-weighted source-over (cover_over)
       const uint32_t a = s >> 24;
-      const double keep = 1.0 - cov * (static_cast<double>(a) / 255.0);
-      uint32_t o = 0;
-#pragma unroll
-      for (int ch_ = 0; ch_ < 3; ++ch_) {
-        const double P = static_cast<double>(ch(s, ch_) * a) / 255.0;
-        const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
-        o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
-      }
-      const double va = floor(static_cast<double>(a) * cov + static_cast<double>(d >> 24) * keep + 0.5);
-      d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
+      const double P[3] = {static_cast<double>(ch(s, 0) * a) / 255.0, static_cast<double>(ch(s, 1) * a) / 255.0, static_cast<double>(ch(s, 2) * a) / 255.0};
+      d = cover_over(P, static_cast<double>(a), cov, d);
     } else if (CUBIC ? ((area && (fabs(op.kx) > 1.0 || fabs(op.ky) > 1.0)) || (cubic && fabs(op.kx) > 1.0 && fabs(op.ky) > 1.0)) : (area && (fabs(op.kx) > 1.0 || fabs(op.ky) > 1.0))) {
       // IST_FILTER_AREA on a minifying draw: a box of width max(1, |k|) per axis around the sample position, source pixels
       // weighted by their overlap (fp32 sums of premultiplied taps; the oracle does the same sums in fp64)
       const double sxc = op.kx * (static_cast<double>(wx) + 0.5) + op.ox, syc = op.ky * (static_cast<double>(wy) + 0.5) + op.oy;
       const double bw = fmax(fabs(op.kx), 1.0), bh = fmax(fabs(op.ky), 1.0);
       const double xlo = sxc - 0.5 * bw, xhi = sxc + 0.5 * bw, ylo = syc - 0.5 * bh, yhi = syc + 0.5 * bh;
-      const int ix0 = static_cast<int>(fmin(fmax(floor(xlo), -2.0e9), 2.0e9)), ix1 = static_cast<int>(fmin(fmax(ceil(xhi), -2.0e9), 2.0e9)) - 1;
-      const int iy0 = static_cast<int>(fmin(fmax(floor(ylo), -2.0e9), 2.0e9)), iy1 = static_cast<int>(fmin(fmax(ceil(yhi), -2.0e9), 2.0e9)) - 1;
+      const int ix0 = clamp_int(floor(xlo)), ix1 = clamp_int(ceil(xhi)) - 1;
+      const int iy0 = clamp_int(floor(ylo)), iy1 = clamp_int(ceil(yhi)) - 1;
       float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
       for (int yy = iy0; yy <= iy1; ++yy) {
         const float oyw = static_cast<float>(fmin(static_cast<double>(yy) + 1.0, yhi) - fmax(static_cast<double>(yy), ylo));
@@ -1093,18 +1104,8 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
         acc0 += oyw * r0; acc1 += oyw * r1; acc2 += oyw * r2; acc3 += oyw * r3;
       }
       const double norm = 1.0 / (bw * bh);
-      const double Aa = static_cast<double>(acc3) * norm;
-      const double keep = 1.0 - cov * (Aa / 255.0);
-      const float accs[3] = {acc0, acc1, acc2};
-      uint32_t o = 0;
-#pragma unroll
-      for (int ch_ = 0; ch_ < 3; ++ch_) {
-        const double P = static_cast<double>(accs[ch_]) * norm / 255.0;
-        const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
-        o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
-      }
-      const double va = floor(Aa * cov + static_cast<double>(d >> 24) * keep + 0.5);
-      d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
+      const double P[3] = {static_cast<double>(acc0) * norm / 255.0, static_cast<double>(acc1) * norm / 255.0, static_cast<double>(acc2) * norm / 255.0};
+      d = cover_over(P, static_cast<double>(acc3) * norm, cov, d);
     } else if (CUBIC && cubic) {
       // IST_FILTER_CUBIC with an axis that does not shrink: four Catmull-Rom taps there, the box on an axis that shrinks (a draw that
       // shrinks on both took the branch above: the same bytes as under IST_FILTER_AREA).  Sums of premultiplied taps, rows first, the
@@ -1128,17 +1129,8 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
       }
       // the negative lobes overshoot: alpha to [0, 255], each premultiplied colour to [0, alpha], before compositing
       const double Aa = fmin(fmax(acc3, 0.0), 255.0);
-      const double keep = 1.0 - cov * (Aa / 255.0);
-      const double accs[3] = {acc0, acc1, acc2};
-      uint32_t o = 0;
-#pragma unroll
-      for (int ch_ = 0; ch_ < 3; ++ch_) {
-        const double P = fmin(fmax(static_cast<double>(accs[ch_]) / 255.0, 0.0), Aa);
-        const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
-        o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
-      }
-      const double va = floor(Aa * cov + static_cast<double>(d >> 24) * keep + 0.5);
-      d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
+      const double P[3] = {fmin(fmax(acc0 / 255.0, 0.0), Aa), fmin(fmax(acc1 / 255.0, 0.0), Aa), fmin(fmax(acc2 / 255.0, 0.0), Aa)};
+      d = cover_over(P, Aa, cov, d);
     } else {
       const Tap tx = bilinear_tap(op.kx, op.ox, wx, op.cx0, op.cx1);
       const Tap ty = bilinear_tap(op.ky, op.oy, wy, op.cy0, op.cy1);
@@ -1150,18 +1142,14 @@ IST_DEV uint32_t pixel_general(const LaunchArgs& A, const DevCell c, int X, int 
       const float a00 = static_cast<float>(p00 >> 24), a01 = static_cast<float>(p01 >> 24);
       const float a10 = static_cast<float>(p10 >> 24), a11 = static_cast<float>(p11 >> 24);
       const double Aa = static_cast<double>(lerpf(lerpf(a00, a01, tx.t), lerpf(a10, a11, tx.t), ty.t));
-      const double keep = 1.0 - cov * (Aa / 255.0);
-      uint32_t o = 0;
+      double P[3];
 #pragma unroll
       for (int ch_ = 0; ch_ < 3; ++ch_) {
         const float top = lerpf(static_cast<float>(ch(p00, ch_)) * a00, static_cast<float>(ch(p01, ch_)) * a01, tx.t);
         const float bot = lerpf(static_cast<float>(ch(p10, ch_)) * a10, static_cast<float>(ch(p11, ch_)) * a11, tx.t);
-        const double P = static_cast<double>(lerpf(top, bot, ty.t)) / 255.0;
-        const double v = floor(P * cov + static_cast<double>(ch(d, ch_)) * keep + 0.5);
-        o |= static_cast<uint32_t>(fmin(fmax(v, 0.0), 255.0)) << (8 * ch_);
+        P[ch_] = static_cast<double>(lerpf(top, bot, ty.t)) / 255.0;
       }
-      const double va = floor(Aa * cov + static_cast<double>(d >> 24) * keep + 0.5);
-      d = o | (static_cast<uint32_t>(fmin(fmax(va, 0.0), 255.0)) << 24);
+      d = cover_over(P, Aa, cov, d);
     }
   }
   // readback is straight alpha (ImageData): un-premultiply
@@ -1270,14 +1258,18 @@ IST_DEV void run_tile(const LaunchArgs& A, int64_t tile, bool fresh) {
 
 // PATHS: which cell kinds this instantiation can render (a job with only fill/copy cells gets the lean one: fewer
 // VGPRs); PERSIST: one block per tile (false) or a fixed grid striding over the tiles (true)
+// The body of the three single-job kernels below: they differ in their attributes only (and their names are in the recorded profiles).
 template <int PATHS, int V, bool PERSIST>
-__global__ __launch_bounds__(256) void ist_stitch_kernel(const LaunchArgs A, const int64_t n_tiles) {
+IST_DEV void run_grid(const LaunchArgs& A, int64_t n_tiles) {
   if (PERSIST) {
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) run_tile<PATHS, V>(A, t, false);
   } else {
     run_tile<PATHS, V>(A, static_cast<int64_t>(blockIdx.x), true);
   }
 }
+
+template <int PATHS, int V, bool PERSIST>
+__global__ __launch_bounds__(256) void ist_stitch_kernel(const LaunchArgs A, const int64_t n_tiles) { run_grid<PATHS, V, PERSIST>(A, n_tiles); }
 
 // the instantiation that carries the streamed box filter: held to 5 waves per SIMD (it compiled to 103 VGPRs, one register
 // past that step)
@@ -1285,15 +1277,9 @@ __global__ __launch_bounds__(256) void ist_stitch_kernel(const LaunchArgs A, con
 #define IST_AREA_WAVES 5
 #endif
 template <int PATHS, int V, bool PERSIST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_area_kernel(const LaunchArgs A, const int64_t n_tiles) {
-  if (PERSIST) {
-    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) run_tile<PATHS, V>(A, t, false);
-  } else {
-    run_tile<PATHS, V>(A, static_cast<int64_t>(blockIdx.x), true);
-  }
-}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_area_kernel(const LaunchArgs A, const int64_t n_tiles) { run_grid<PATHS, V, PERSIST>(A, n_tiles); }
 
-// the instantiations of IST_FILTER_CUBIC jobs that resample (kernel kinds 5 and 6): kernels of their own, so that no other form
+// the instantiations of IST_FILTER_CUBIC jobs that resample (KIND_CUBIC and KIND_CUBIC_GENERAL): kernels of their own, so that no other form
 // pays registers for the cubic tile function or for the cubic rule of the per-pixel stack
 #ifndef IST_CUBIC_WAVES         // (compile-time experiment switch: -DIST_CUBIC_WAVES=4 rebuilds the variant LAB_NOTES.md quotes; 0 = the compiler's choice)
 #define IST_CUBIC_WAVES 0
@@ -1304,13 +1290,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WA
 #define IST_CUBIC_EU
 #endif
 template <int PATHS, int V, bool PERSIST>
-__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_kernel(const LaunchArgs A, const int64_t n_tiles) {
-  if (PERSIST) {
-    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) run_tile<PATHS, V>(A, t, false);
-  } else {
-    run_tile<PATHS, V>(A, static_cast<int64_t>(blockIdx.x), true);
-  }
-}
+__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_kernel(const LaunchArgs A, const int64_t n_tiles) { run_grid<PATHS, V, PERSIST>(A, n_tiles); }
 
 // ------------------------------------------------------------------------------------------------ batch
 // Many independent jobs in one launch (ist_jobs_launch): the tiles of all jobs are numbered job-major, workgroup t finds its job
@@ -1335,8 +1315,9 @@ IST_DEV int batch_job_of(const BatchArgs& B, int64_t tile) {
   return __builtin_amdgcn_readfirstlane(lo);
 }
 
+// the body of the three batch kernels below (the twins of the single-job kernels: the same attributes)
 template <int PATHS, int V>
-__global__ __launch_bounds__(256) void ist_stitch_batch_kernel(const BatchArgs B) {
+IST_DEV void run_batch(const BatchArgs& B) {
   const int64_t tile = static_cast<int64_t>(blockIdx.x);
   const int j = batch_job_of(B, tile);
   const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
@@ -1344,41 +1325,40 @@ __global__ __launch_bounds__(256) void ist_stitch_batch_kernel(const BatchArgs B
 }
 
 template <int PATHS, int V>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_batch_area_kernel(const BatchArgs B) {
-  const int64_t tile = static_cast<int64_t>(blockIdx.x);
-  const int j = batch_job_of(B, tile);
-  const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
-  run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
-}
+__global__ __launch_bounds__(256) void ist_stitch_batch_kernel(const BatchArgs B) { run_batch<PATHS, V>(B); }
 
 template <int PATHS, int V>
-__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_batch_kernel(const BatchArgs B) {
-  const int64_t tile = static_cast<int64_t>(blockIdx.x);
-  const int j = batch_job_of(B, tile);
-  const int64_t local = tile - ((ConstI64*)B.tile_begin)[j];
-  run_tile<PATHS, V>(*(const LaunchArgs*)((ConstLaunchArgs*)B.jobs + j), local, true);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IST_AREA_WAVES))) void ist_stitch_batch_area_kernel(const BatchArgs B) { run_batch<PATHS, V>(B); }
+
+template <int PATHS, int V>
+__global__ __launch_bounds__(256) IST_CUBIC_EU void ist_cubic_batch_kernel(const BatchArgs B) { run_batch<PATHS, V>(B); }
+
+// THE kind table: the paths of each KernelKind (ist_launch.h), given once.  Every kind is an instantiation of one template, by what
+// the job's cells need: the fewer paths, the fewer registers and the more workgroups per CU (fill/copy: 28 VGPRs; + axis-aligned
+// resampling; + quarter turns and the per-pixel stack).  The streamed box filter keeps up to 8 source rows per lane in flight: it
+// has its own kinds so that its register count does not lower the occupancy of the jobs that never use it; the cubic kinds likewise.
+constexpr int kind_paths(int kind) {
+  switch (kind) {
+    case KIND_COPY: return HAS_FILL | HAS_COPY;
+    case KIND_SAMPLE: return HAS_FILL | HAS_COPY | HAS_SAMPLE;
+    case KIND_AREA: return HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA;
+    case KIND_FULL: return HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA;
+    case KIND_CUBIC: return HAS_FILL | HAS_COPY | HAS_AREA | HAS_CUBIC;
+    case KIND_CUBIC_GENERAL: return HAS_FILL | HAS_COPY | HAS_AREA | HAS_CUBIC | HAS_GENERAL;
+    default: return HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL;      // KIND_GENERAL
+  }
+}
+// f(std::integral_constant<int, kind_paths(kind)>): the runtime kind as a compile-time PATHS.  A number that names no kind runs
+// as KIND_GENERAL (kind_paths' default), here and nowhere else.
+template <int K = 0, class F>
+static void with_kind_paths(int kind, const F& f) {
+  if constexpr (K < kKernelKinds) {
+    if (kind != K) { with_kind_paths<K + 1>(kind, f); return; }
+  }
+  f(std::integral_constant<int, kind_paths(K)>{});      // K == kKernelKinds: no kind matched
 }
 
-constexpr int kCubicPaths = HAS_FILL | HAS_COPY | HAS_AREA | HAS_CUBIC;       // kind 5; kind 6 = | HAS_GENERAL
-
-int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream) {
-  if (args.n_tiles <= 0) return IST_OK;
-  if (args.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>(args.n_tiles)), block(256);
-  // the same instantiations by kind as launch_stitch (shipped copy variant 0, one workgroup per tile)
-  if (kind == 0) hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY, 0>), grid, block, dyn_lds_bytes, s, args);
-  else if (kind == 1) hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE, 0>), grid, block, dyn_lds_bytes, s, args);
-  else if (kind == 3) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
-  else if (kind == 4) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA, 0>), grid, block, dyn_lds_bytes, s, args);
-  else if (kind == 5) hipLaunchKernelGGL((ist_cubic_batch_kernel<kCubicPaths, 0>), grid, block, dyn_lds_bytes, s, args);
-  else if (kind == 6) hipLaunchKernelGGL((ist_cubic_batch_kernel<kCubicPaths | HAS_GENERAL, 0>), grid, block, dyn_lds_bytes, s, args);
-  else hipLaunchKernelGGL((ist_stitch_batch_kernel<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL, 0>), grid, block, dyn_lds_bytes, s, args);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(IST_E_HIP, std::string("batch kernel launch failed: ") + hipGetErrorString(e));
-  return IST_OK;
-}
-
+// the wrapper by PATHS: the cubic kinds and the kinds with the box filter have kernels (attributes) of their own
 template <int PATHS, int V, bool PERSIST>
 static void launch_one(const LaunchArgs& args, int64_t n_tiles, hipStream_t stream, int persist_blocks, unsigned dyn_lds) {
   const unsigned grid = PERSIST ? static_cast<unsigned>(std::min<int64_t>(n_tiles, persist_blocks)) : static_cast<unsigned>(n_tiles);
@@ -1386,6 +1366,24 @@ static void launch_one(const LaunchArgs& args, int64_t n_tiles, hipStream_t stre
   if constexpr ((PATHS & HAS_CUBIC) != 0) hipLaunchKernelGGL((ist_cubic_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
   else if constexpr ((PATHS & HAS_AREA) != 0) hipLaunchKernelGGL((ist_stitch_area_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
   else hipLaunchKernelGGL((ist_stitch_kernel<PATHS, V, PERSIST>), dim3(grid), dim3(256), dyn, stream, args, n_tiles);
+}
+template <int PATHS>
+static void launch_batch_one(const BatchArgs& args, dim3 grid, unsigned dyn, hipStream_t stream) {
+  if constexpr ((PATHS & HAS_CUBIC) != 0) hipLaunchKernelGGL((ist_cubic_batch_kernel<PATHS, 0>), grid, dim3(256), dyn, stream, args);
+  else if constexpr ((PATHS & HAS_AREA) != 0) hipLaunchKernelGGL((ist_stitch_batch_area_kernel<PATHS, 0>), grid, dim3(256), dyn, stream, args);
+  else hipLaunchKernelGGL((ist_stitch_batch_kernel<PATHS, 0>), grid, dim3(256), dyn, stream, args);
+}
+
+int launch_stitch_batch(const BatchArgs& args, int kind, unsigned dyn_lds_bytes, void* stream) {
+  if (args.n_tiles <= 0) return IST_OK;
+  if (args.n_tiles > 0x7FFFFFFF) return fail(IST_E_UNSUPPORTED, "a batch of more than 2^31 - 1 tiles");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>(args.n_tiles));
+  // the same instantiations by kind as launch_stitch (shipped copy variant 0, one workgroup per tile)
+  with_kind_paths(kind, [&](auto paths) { launch_batch_one<decltype(paths)::value>(args, grid, dyn_lds_bytes, s); });
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(IST_E_HIP, std::string("batch kernel launch failed: ") + hipGetErrorString(e));
+  return IST_OK;
 }
 
 template <int PATHS>
@@ -1411,17 +1409,8 @@ int launch_stitch(const LaunchArgs& args, int64_t n_tiles, int kind, void* strea
   const int v = knob % 100;
   const bool persist = knob >= 100;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // three instantiations of one template, by what the job's cells need: the fewer paths, the fewer registers and the
-  // more workgroups per CU (fill/copy: 28 VGPRs; + axis-aligned resampling; + quarter turns and the per-pixel stack)
-  // (the streamed box filter keeps up to 8 source rows per lane in flight: it has its own instantiation so that its register
-  // count does not lower the occupancy of the jobs that never use it)
-  if (kind == 0 && !full) launch_variant<HAS_FILL | HAS_COPY>(v, persist, args, n_tiles, s, pb, dl);
-  else if (kind == 1 && !full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE>(v, persist, args, n_tiles, s, pb, dl);
-  else if (kind == 3 && !full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_AREA>(v, persist, args, n_tiles, s, pb, dl);
-  else if (kind == 5) launch_variant<kCubicPaths>(v, persist, args, n_tiles, s, pb, dl);
-  else if (kind == 6) launch_variant<kCubicPaths | HAS_GENERAL>(v, persist, args, n_tiles, s, pb, dl);
-  else if (kind == 4 || full) launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL | HAS_AREA>(v, persist, args, n_tiles, s, pb, dl);
-  else launch_variant<HAS_FILL | HAS_COPY | HAS_SAMPLE | HAS_SWAP | HAS_GENERAL>(v, persist, args, n_tiles, s, pb, dl);
+  if (full && kind != KIND_CUBIC && kind != KIND_CUBIC_GENERAL) kind = KIND_FULL;    // IST_FULL_KERNEL: every non-cubic job through the widest form
+  with_kind_paths(kind, [&](auto paths) { launch_variant<decltype(paths)::value>(v, persist, args, n_tiles, s, pb, dl); });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(IST_E_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
   return IST_OK;

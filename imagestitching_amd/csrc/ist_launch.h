@@ -29,10 +29,19 @@ struct LaunchArgs {
   size_t pitch[kMaxImages];
 };
 
-// kind: 0 = the job has only FILL / COPY cells, 1 = + axis-aligned resampling (SAMPLE, SAMPLE_LDS, SAMPLE_STREAM), 3 = + the
-// streamed box filter (AREA_STREAM), 2 = quarter turns / paint stacks (no box filter), 4 = everything: the instantiation
-// with just those paths is launched.  IST_FILTER_CUBIC jobs that resample: 5 = FILL / COPY / AREA_STREAM / CUBIC_STREAM, 6 = + the
-// per-pixel paint stack under the cubic rule (no such job holds a bilinear cell).  ist_batch.cpp groups a batch by these (kKinds).
+// The kernel form a job needs (Compiled::kernel_kind, set by ist_compile.cpp): the instantiation with just the paths of the job's
+// cells is launched - the fewer paths, the fewer registers.  THE list: ist_kernels.hip maps each kind to its paths once
+// (kind_paths), ist_batch.cpp groups a batch by kind.  The values are part of ist_debug_cells' output: they stay.
+enum KernelKind : int32_t {
+  KIND_COPY = 0,            // FILL / COPY cells only
+  KIND_SAMPLE = 1,          // + axis-aligned resampling (SAMPLE, SAMPLE_LDS, SAMPLE_STREAM)
+  KIND_GENERAL = 2,         // + quarter turns (SWAP_LDS) and per-pixel paint stacks (GENERAL), no box filter
+  KIND_AREA = 3,            // KIND_SAMPLE + the streamed box filter (AREA_STREAM)
+  KIND_FULL = 4,            // KIND_GENERAL + AREA_STREAM: every path but the cubic one
+  KIND_CUBIC = 5,           // IST_FILTER_CUBIC jobs that resample: FILL / COPY / AREA_STREAM / CUBIC_STREAM
+  KIND_CUBIC_GENERAL = 6    // + the per-pixel paint stack under the cubic rule (no such job holds a bilinear cell)
+};
+constexpr int kKernelKinds = 7;
 int launch_stitch(const LaunchArgs& args, int64_t n_tiles, int kind, void* stream);
 
 // Several jobs of one kind in ONE launch (ist_jobs_launch).  Three device tables, uploaded per launch:
