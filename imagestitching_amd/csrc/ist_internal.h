@@ -219,6 +219,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
                               const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, void* stream2 = nullptr);
 int ctx_png_level(const ist_ctx* ctx);
 int ctx_png_color(const ist_ctx* ctx);                      // IST_PNG_RGBA / IST_PNG_RGB (ist_ctx_set_png_color)
+int ctx_png_filter(const ist_ctx* ctx);                     // IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE (ist_ctx_set_png_filter)
 // IST_E_UNSUPPORTED for the one pair of settings no encoder serves: the stored form (level 0) in RGB.  Every *_png entry point
 // calls it before anything is enqueued, and so does every place that picks between the stored and the compressing encoder.
 int ctx_png_form_check(const ist_ctx* ctx);

@@ -21,6 +21,20 @@
 //   * each workgroup also returns the Adler-32 partial sums of its filtered bytes and the raw CRC-32 of its output
 //     bytes; the host combines them (O(chunks)), lays the chunks out behind one another (several IDAT chunks if the
 //     stream exceeds the IDAT limit), a second kernel copies them into place, and ~100 header/trailer bytes are patched.
+//
+// ADAPTIVE ROW FILTERS (ist_ctx_set_png_filter, IST_PNG_FILTER_ADAPTIVE; the default stays Paeth on every row).  For a canvas in a
+// colour form of bpp bytes per pixel (4 RGBA, 3 RGB: alpha is not read) row y gets the filter type f of {0 None, 1 Sub, 2 Up,
+// 3 Average, 4 Paeth} with the least
+//     cost_f(y) = sum over the row's bpp w residual bytes r of (r < 128 ? r : 256 - r)
+// (the minimum sum of absolute differences; the filter byte itself is not counted).  Residuals are those of the PNG specification
+// 9.2 - 9.4: left / up / upper left are the same channel of the neighbouring pixel, zero outside the image; Average is
+// (left + up) >> 1 on the unwrapped 0..255 values; Paeth breaks its ties as above.  Ties between filters go to the first of
+// 4, 1, 2, 3, 0: Paeth wins ties, so a canvas on which nothing beats Paeth gives the default form's stream bit for bit, and flat
+// rows stay type 4 (on row 0, where Sub is Paeth and None is Up, neither Sub nor None is ever chosen).  The choice is a function
+// of the row's pixels and of the row above alone - not of the chunk grid, not of the slabs - and is made by a pre-pass kernel (ist_png_row_filter_kernel) that writes one byte per row; the compressing
+// kernels' adaptive twins read that byte in step A, form the residual with that predictor and store the type as the row's filter
+// byte.  Everything behind the filter - grid, spans, tokens, code rule, stored against Huffman, pads, Adler-32, slabs, IDAT layout,
+// IHDR (filter method 0 allows a type per row) - is unchanged.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -88,6 +102,16 @@ __device__ __forceinline__ uint32_t paeth4(uint32_t cur, uint32_t a, uint32_t b,
   const uint32_t pe = paeth_pred2(a & m, b & m, c & m), po = paeth_pred2((a >> 8) & m, (b >> 8) & m, (c >> 8) & m);
   const uint32_t pred = pe | (po << 8);
   // cur - pred in every byte: borrow-free subtraction of the low seven bits, the top bits by xor
+  return ((cur | 0x80808080u) - (pred & 0x7F7F7F7Fu)) ^ ((cur ^ ~pred) & 0x80808080u);
+}
+// the residuals of one pixel under filter type ft (the adaptive kernels): None, Sub, Up, Average = (left + up) >> 1 per channel in
+// 16-bit lanes (the bit a shift carries out of the upper lane falls into the masked half of the lower one), Paeth as above
+__device__ __forceinline__ uint32_t filter4(uint32_t ft, uint32_t cur, uint32_t a, uint32_t b, uint32_t c) {
+  const uint32_t m = 0x00FF00FFu;
+  uint32_t pred;
+  if (ft == 4) pred = paeth_pred2(a & m, b & m, c & m) | (paeth_pred2((a >> 8) & m, (b >> 8) & m, (c >> 8) & m) << 8);
+  else if (ft == 3) pred = ((((a & m) + (b & m)) >> 1) & m) | ((((((a >> 8) & m) + ((b >> 8) & m)) >> 1) & m) << 8);
+  else pred = ft == 1 ? a : (ft == 2 ? b : 0u);
   return ((cur | 0x80808080u) - (pred & 0x7F7F7F7Fu)) ^ ((cur ^ ~pred) & 0x80808080u);
 }
 
@@ -224,9 +248,10 @@ __device__ __forceinline__ int walk_span(const uint32_t (&sp)[16], int n, const 
 
 // One workgroup compresses chunk `chunk` of the canvas P describes (the body of the compressing kernels below).  BPP: bytes of a
 // pixel in the filtered stream - 4 (RGBA, colour type 6) or 3 (RGB, colour type 2: the canvas is still read a dword per pixel, the
-// alpha byte of the residual is not stored).  Only step A knows it; from step B on a chunk is bytes.
-template <int BPP>
-__device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t chunk) {
+// alpha byte of the residual is not stored).  Only step A knows it; from step B on a chunk is bytes.  ADAPT: the filter type of canvas
+// row y is ftab[y] (written by the row-filter pre-pass) instead of 4; again only step A knows.
+template <int BPP, bool ADAPT = false>
+__device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t chunk, const uint8_t* ftab = nullptr) {
   // ONE buffer, two lives: the filtered chunk (padded layout) until every thread has taken its span into registers, then the
   // Huffman scratch and the output bit stream
   static_assert(PADDED >= SLOT, "the output buffer aliases the filtered chunk");
@@ -258,10 +283,14 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 0] = wall_clock64();
   // ---- A. load + Paeth filter into LDS
   const int npix = npr * nrows;
+  // (adaptive, a chunk of one row or a piece of one: its type is one scalar load for the workgroup)
+  uint32_t ft_row = 4u;
+  if constexpr (ADAPT) { if (nrows == 1) ft_row = ((ConstPtr<uint8_t>)ftab)[y0]; }
   // four pixels per thread and round, all sixteen loads issued before the first filter: the one-pixel-per-iteration form
   // had four loads in flight per thread and spent 15 us of a chunk's 96 waiting for them (IST_PNG_PHASES, measured)
   for (int q0 = tid; q0 < npix; q0 += 1024) {
     uint32_t cur[4], a[4], b[4], c[4]; int pos[4]; bool first[4], on[4];
+    [[maybe_unused]] uint32_t ft[4] = {4u, 4u, 4u, 4u};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int q = q0 + 256 * u;
@@ -279,13 +308,19 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
         }
         pos[u] = r * rowlen + hasf + BPP * xx;
         first[u] = hasf && xx == 0;
+        if constexpr (ADAPT) {
+          ft[u] = nrows == 1 ? ft_row : static_cast<uint32_t>(ftab[y]);
+          if (first[u]) filt[padpos(r * rowlen)] = static_cast<uint8_t>(ft[u]);
+        } else
         if (first[u]) filt[padpos(r * rowlen)] = 4;              // filter type of the row
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (!on[u]) continue;
-      const uint32_t fv = paeth4(cur[u], a[u], b[u], c[u]);
+      uint32_t fv;
+      if constexpr (ADAPT) fv = filter4(ft[u], cur[u], a[u], b[u], c[u]);
+      else fv = paeth4(cur[u], a[u], b[u], c[u]);
 #pragma unroll
       for (int k = 0; k < BPP; ++k) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
     }
@@ -576,6 +611,153 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void i
   deflate_chunk<3>(P, g - base);
 }
 
+// ---- adaptive row filters (IST_PNG_FILTER_ADAPTIVE): the pre-pass that chooses a type per row, and the compressing kernels' twins
+// that follow it.  The rule is stated at the top of this file.
+//
+// The pre-pass.  A lane takes four neighbouring pixels of row y and of row y - 1 as one 16-byte load each (+ the pixel left of them,
+// an overlapping dword load), forms the five residuals of two channels at a time in packed 16-bit lanes - like paeth_pred2 - and adds
+// |residual as a signed byte| into five packed sums (8 terms of at most 128 per 16-bit lane and round: no carry between the lanes),
+// which it unpacks into five 32-bit sums per round.  The sums are integers: wave and workgroup reduction give the same numbers
+// in any launch shape.  One lane takes the argmin in the tie order 4, 1, 2, 3, 0 and writes the byte with an ordinary store.
+// LDS: the 4 x 5 reduction words.
+//
+// Launch shape (rows_per_group): a wave covers 256 pixels per round, a workgroup 1024.  Rows of up to kRowFilterWaveW = 1024
+// pixels - previews, thumbnails, the 606-pixel plans - get a WAVE each, four rows per workgroup: such a row is at most four rounds
+// of one wave, and a workgroup per row would leave three waves of four idle from the second round on (all of them below 257 px).
+// Wider rows get the whole workgroup.
+constexpr int kRowFilterWaveW = 1024;
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t abs_res2(s16x2 d) {            // per 16-bit lane: |d mod 256 read as a signed byte| = min(r, 256 - r)
+  const s16x2 t = __builtin_bit_cast(s16x2, __builtin_bit_cast(u16x2, d) << 8) >> 8;
+  const s16x2 zero = {0, 0};
+  return as_u32(__builtin_elementwise_max(t, zero - t));
+}
+__device__ __forceinline__ void cost_pair(uint32_t x, uint32_t l, uint32_t u, uint32_t ul, uint32_t (&pk)[5]) {      // two channels, 16-bit lanes holding 0..255
+  const s16x2 sx = as_s16x2(x), sl = as_s16x2(l), su = as_s16x2(u);
+  pk[0] += abs_res2(sx);
+  pk[1] += abs_res2(sx - sl);
+  pk[2] += abs_res2(sx - su);
+  pk[3] += abs_res2(sx - ((sl + su) >> 1));
+  pk[4] += abs_res2(sx - as_s16x2(paeth_pred2(l, u, ul)));
+}
+
+struct RowFilterArgs {
+  const uint8_t* canvas; size_t pitch; int64_t w, h;      // one file (jobs == nullptr): row number = canvas row
+  const DeflJob* jobs;           // batch: per file (device memory), rows numbered file-major ...
+  const int64_t* row_begin;      // ... row_begin[f] is file f's first, row_begin[n_files] the total
+  int32_t n_files;
+  int32_t rows_per_group;        // 4: a wave per row; 1: the workgroup's four waves share one row
+  int64_t row0, n_rows;          // this launch: rows [row0, row0 + n_rows)
+  uint8_t* table;                // table[row] = the type
+};
+
+template <int BPP>
+__device__ __forceinline__ void row_filter_body(const RowFilterArgs& A) {
+  __shared__ uint32_t part[4][5];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool per_wave = A.rows_per_group == 4;
+  const int64_t g = A.row0 + (per_wave ? 4 * static_cast<int64_t>(blockIdx.x) + wave : static_cast<int64_t>(blockIdx.x));
+  const bool live = g < A.row0 + A.n_rows;             // (wave-uniform; with a row per workgroup the same for all four waves)
+  uint32_t acc[5] = {0u, 0u, 0u, 0u, 0u};
+  if (live) {
+    const uint8_t* canvas = A.canvas; size_t pitch = A.pitch; int64_t w = A.w, y = g;
+    if (A.jobs) {
+      const int f = batch_file_of(A.row_begin, A.n_files, g);
+      const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)A.jobs + f);
+      canvas = J.canvas; pitch = J.pitch; w = J.w; y = g - ((ConstPtr<int64_t>)A.row_begin)[f];
+    }
+    const uint8_t* row = canvas + static_cast<size_t>(y) * pitch;
+    const int64_t first = per_wave ? lane : tid, step = per_wave ? 64 : 256;
+    const uint32_t me = 0x00FF00FFu, mo = BPP == 4 ? 0x00FF00FFu : 0x000000FFu;      // (RGB: the alpha lane is zero everywhere - it costs nothing)
+    for (int64_t x = 4 * first; x < w; x += 4 * step) {
+      // c[0] / b[0]: the pixel left of the four (zero left of the image); b: the row above (zero above the image)
+      uint32_t c[5] = {0u, 0u, 0u, 0u, 0u}, b[5] = {0u, 0u, 0u, 0u, 0u};
+      const int npx = static_cast<int>(min(static_cast<int64_t>(4), w - x));
+      const uint8_t* p = row + 4 * static_cast<size_t>(x);
+      if (npx == 4) {
+        const u32x4 v = *reinterpret_cast<const u32x4_a4*>(p);
+        c[1] = v.x; c[2] = v.y; c[3] = v.z; c[4] = v.w;
+        if (y > 0) { const u32x4 t = *reinterpret_cast<const u32x4_a4*>(p - pitch); b[1] = t.x; b[2] = t.y; b[3] = t.z; b[4] = t.w; }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (k < npx) {
+            c[1 + k] = *reinterpret_cast<const uint32_t*>(p + 4 * k);
+            if (y > 0) b[1 + k] = *reinterpret_cast<const uint32_t*>(p - pitch + 4 * k);
+          }
+      }
+      if (x > 0) {
+        c[0] = *reinterpret_cast<const uint32_t*>(p - 4);
+        if (y > 0) b[0] = *reinterpret_cast<const uint32_t*>(p - pitch - 4);
+      }
+      uint32_t pk[5] = {0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < npx) {
+          cost_pair(c[k + 1] & me, c[k] & me, b[k + 1] & me, b[k] & me, pk);
+          cost_pair((c[k + 1] >> 8) & mo, (c[k] >> 8) & mo, (b[k + 1] >> 8) & mo, (b[k] >> 8) & mo, pk);
+        }
+#pragma unroll
+      for (int f = 0; f < 5; ++f) acc[f] += (pk[f] & 0xFFFFu) + (pk[f] >> 16);
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < 5; ++f) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[f] += __shfl_xor(acc[f], off);
+    if (lane == 0) part[wave][f] = acc[f];
+  }
+  __syncthreads();
+  if (live && lane == 0 && (per_wave || wave == 0)) {
+    uint32_t cost[5];
+#pragma unroll
+    for (int f = 0; f < 5; ++f) cost[f] = per_wave ? part[wave][f] : part[0][f] + part[1][f] + part[2][f] + part[3][f];
+    uint32_t best = 4u, least = cost[4];                // ties: the first of 4, 1, 2, 3, 0
+    if (cost[1] < least) { best = 1u; least = cost[1]; }
+    if (cost[2] < least) { best = 2u; least = cost[2]; }
+    if (cost[3] < least) { best = 3u; least = cost[3]; }
+    if (cost[0] < least) { best = 0u; }
+    A.table[g] = static_cast<uint8_t>(best);
+  }
+}
+
+__global__ __launch_bounds__(256) void ist_png_row_filter_kernel(const RowFilterArgs A) { row_filter_body<4>(A); }
+__global__ __launch_bounds__(256) void ist_png_row_filter_rgb_kernel(const RowFilterArgs A) { row_filter_body<3>(A); }
+
+// The compressing kernels' adaptive twins: the same body, step A following the table (a separate argument: DeflArgs / DeflBatchArgs
+// are what the kernels above see, unchanged).  amdgpu_waves_per_eu(5) for both colour forms: step A holds one more value per pixel
+// in flight (the type) and three more predictors' worth of code, and steps B - E are the body that already spills 16 VGPRs under the
+// 72-register cap of 7 waves in the RGBA kernel; at 5 waves (96 registers) nothing spills and there is no private segment, as for the
+// RGB kernel above and at the price measured there.  LDS is the body's 21544 bytes.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_adapt_kernel(const DeflArgs P, const uint8_t* ftab) {
+  deflate_chunk<4, true>(P, P.chunk0 + blockIdx.x, ftab);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_adapt_rgb_kernel(const DeflArgs P, const uint8_t* ftab) {
+  deflate_chunk<3, true>(P, P.chunk0 + blockIdx.x, ftab);
+}
+// batch: file f's rows are table entries [row_begin[f], row_begin[f + 1])
+template <int BPP>
+__device__ __forceinline__ void deflate_adapt_batch_body(const DeflBatchArgs& B, const int64_t* row_begin, const uint8_t* ftab) {
+  const int64_t g = blockIdx.x;
+  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
+  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
+  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
+  DeflArgs P;
+  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
+  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
+  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
+  P.tables = B.tables; P.xpow16 = B.xpow16;
+  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
+  P.chunk0 = 0; P.dbg = nullptr;
+  deflate_chunk<BPP, true>(P, g - base, ftab + ((ConstPtr<int64_t>)row_begin)[f]);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_adapt_batch_kernel(const DeflBatchArgs B, const int64_t* row_begin, const uint8_t* ftab) {
+  deflate_adapt_batch_body<4>(B, row_begin, ftab);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_adapt_rgb_batch_kernel(const DeflBatchArgs B, const int64_t* row_begin, const uint8_t* ftab) {
+  deflate_adapt_batch_body<3>(B, row_begin, ftab);
+}
+
 struct GatherArgs { const uint8_t* slots; uint8_t* out; const int64_t* dst; const uint32_t* len16; int64_t chunk0; };
 
 __device__ __forceinline__ void gather_chunk(const uint8_t* s, uint8_t* d, const int units) {
@@ -744,6 +926,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
                               const std::function<int(int64_t, void*)>& need_rows, int64_t slab_rows_hint, void* stream2_) {
   { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int color = ctx_png_color(ctx);
+  const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
   const ChunkGrid g = make_grid(w, h, color);
   if (g.n_chunks > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
   if (png_deflate_bound(w, h, color) > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
@@ -783,7 +966,11 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     const int64_t r = g.pieces_per_row > 0 ? (static_cast<int64_t>(c_end) + g.pieces_per_row - 1) / g.pieces_per_row : static_cast<int64_t>(c_end) * g.rows_per_chunk;
     return std::min<int64_t>(h, r);
   };
-  const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_slots = o_pow + up(4 * xpow.size()), total_scratch = o_slots + n * SLOT;
+  // (adaptive: the row types, ONE TABLE OF h BYTES PER STREAM PARITY.  Slabs alternate between two streams and a slab boundary can
+  // fall inside a row; with a table per parity a slab's pre-pass writes, and its compressing kernel reads, only bytes of its own
+  // stream - the cut row is evaluated by both slabs, each into its own table - so the streams need no event and no wait for it)
+  const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_ftab = o_pow + up(4 * xpow.size()),
+               o_slots = o_ftab + (adaptive ? up(2 * static_cast<size_t>(h)) : 0), total_scratch = o_slots + n * SLOT;
   // the context's grow-only scratch: a 439 MB canvas needs 443 MB of slots, and allocating + freeing that per call cost
   // more than the gather kernel (and a free synchronises the device)
   uint8_t* scratch = nullptr;
@@ -840,7 +1027,25 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     A.rows_per_chunk = g.rows_per_chunk; A.pieces_per_row = g.pieces_per_row; A.piece_px = g.piece_px;
     A.chunk0 = static_cast<int64_t>(c0);
     A.dbg = static_cast<unsigned long long*>(dbg.p);
-    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
+    if (adaptive) {
+      // the pre-pass of every row this slab's chunks touch, on the slab's own stream, into the table of that stream (the row above
+      // the first one is only read: like the Paeth filter's, it belongs to an earlier slab and has been asked for)
+      const int64_t y_lo = g.pieces_per_row > 0 ? static_cast<int64_t>(c0) / g.pieces_per_row : static_cast<int64_t>(c0) * g.rows_per_chunk;
+      const int64_t y_hi = rows_of(c0 + cn);
+      uint8_t* const ftab = scratch + o_ftab + (s & 1) * static_cast<size_t>(h);
+      RowFilterArgs F;
+      F.canvas = A.canvas; F.pitch = pitch; F.w = w; F.h = h;
+      F.jobs = nullptr; F.row_begin = nullptr; F.n_files = 0;
+      F.rows_per_group = w <= kRowFilterWaveW ? 4 : 1;
+      F.row0 = y_lo; F.n_rows = y_hi - y_lo; F.table = ftab;
+      const unsigned groups = static_cast<unsigned>((F.n_rows + F.rows_per_group - 1) / F.rows_per_group);
+      if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, st, F);
+      else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, st, F);
+      PNG_HIP(hipGetLastError());
+      if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
+      else hipLaunchKernelGGL(ist_png_deflate_adapt_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
+    }
+    else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     PNG_HIP(hipGetLastError());
     tl_mark("png:   compression launched, slab", static_cast<long>(s));
@@ -953,12 +1158,16 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   const size_t nf = files.size();
   { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int color = ctx_png_color(ctx);
+  const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::vector<ChunkGrid> grid(nf);
-  std::vector<int64_t> begin(nf + 1, 0);
+  std::vector<int64_t> begin(nf + 1, 0), row_begin(nf + 1, 0);      // (row_begin: the rows of every file, file-major - the adaptive form's table)
+  int64_t widest = 0;
   for (size_t k = 0; k < nf; ++k) {
     grid[k] = make_grid(files[k].w, files[k].h, color);
     begin[k + 1] = begin[k] + grid[k].n_chunks;
+    row_begin[k + 1] = row_begin[k] + files[k].h;
+    widest = std::max(widest, files[k].w);
   }
   if (begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
   const size_t n = static_cast<size_t>(begin[nf]);
@@ -967,9 +1176,11 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // device: tables | per-file jobs | chunk_begin | slots;  pinned host: per-chunk results [len16 | crc | ad_a | ad_b | ad_n] |
   // per-chunk destination addresses (read in place by the gather) | the jobs + chunk_begin image that goes up
+  // (adaptive: row_begin goes up with the jobs; behind it the table of row types, which only kernels write)
   const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_jobs = o_pow + up(4 * xpow.size()), o_begin = o_jobs + up(sizeof(DeflJob) * nf),
-               o_slots = o_begin + up(8 * (nf + 1)), total_scratch = o_slots + n * SLOT;
-  const size_t h_res = 0, h_dst = up(20 * n), h_jobs = h_dst + up(8 * n), h_total = h_jobs + (o_slots - o_jobs);
+               o_rows = o_begin + up(8 * (nf + 1)), o_ftab = o_rows + (adaptive ? up(8 * (nf + 1)) : 0),
+               o_slots = o_ftab + (adaptive ? up(static_cast<size_t>(row_begin[nf])) : 0), total_scratch = o_slots + n * SLOT;
+  const size_t h_res = 0, h_dst = up(20 * n), h_jobs = h_dst + up(8 * n), h_total = h_jobs + (o_ftab - o_jobs);
   uint8_t* scratch = nullptr;
   {
     void* p = nullptr;
@@ -989,9 +1200,10 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
     hj[k] = DeflJob{static_cast<const uint8_t*>(f.canvas), f.pitch, f.w, f.h, grid[k].rows_per_chunk, grid[k].pieces_per_row, grid[k].piece_px, 0};
   }
   std::memcpy(hb, begin.data(), 8 * (nf + 1));
+  if (adaptive) std::memcpy(pin.p + h_jobs + (o_rows - o_jobs), row_begin.data(), 8 * (nf + 1));
   PNG_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
   PNG_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_slots - o_jobs, hipMemcpyHostToDevice, stream));
+  PNG_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_ftab - o_jobs, hipMemcpyHostToDevice, stream));
   uint32_t* res = reinterpret_cast<uint32_t*>(pin.p + h_res);
   DeflBatchArgs B;
   B.jobs = reinterpret_cast<const DeflJob*>(scratch + o_jobs);
@@ -1000,7 +1212,25 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   B.slots = scratch + o_slots;
   B.len16 = res; B.crc = res + n; B.ad_a = res + 2 * n; B.ad_b = res + 3 * n; B.ad_n = res + 4 * n;
   B.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); B.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
-  if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
+  if (adaptive) {
+    // ONE pre-pass launch for the rows of all files (a wave per row unless some file is wider than a wave's share), then the one
+    // compressing launch
+    if (row_begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
+    const int64_t* d_rows = reinterpret_cast<const int64_t*>(scratch + o_rows);
+    uint8_t* const ftab = scratch + o_ftab;
+    RowFilterArgs F;
+    F.canvas = nullptr; F.pitch = 0; F.w = 0; F.h = 0;
+    F.jobs = B.jobs; F.row_begin = d_rows; F.n_files = B.n_files;
+    F.rows_per_group = widest <= kRowFilterWaveW ? 4 : 1;
+    F.row0 = 0; F.n_rows = row_begin[nf]; F.table = ftab;
+    const unsigned groups = static_cast<unsigned>((F.n_rows + F.rows_per_group - 1) / F.rows_per_group);
+    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, stream, F);
+    else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, stream, F);
+    PNG_HIP(hipGetLastError());
+    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
+    else hipLaunchKernelGGL(ist_png_deflate_adapt_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
+  }
+  else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
   else hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
   PNG_HIP(hipGetLastError());
   count_png_batch_launch();

@@ -23,7 +23,10 @@ using namespace ist;
 namespace ist {
 int ctx_png_level(const ist_ctx* ctx) { return ctx ? ctx->png_level : 0; }
 int ctx_png_color(const ist_ctx* ctx) { return ctx ? ctx->png_color : IST_PNG_RGBA; }
+int ctx_png_filter(const ist_ctx* ctx) { return ctx ? ctx->png_filter : IST_PNG_FILTER_PAETH; }
 int ctx_png_form_check(const ist_ctx* ctx) {
+  if (ctx && ctx->png_level == 0 && ctx->png_filter == IST_PNG_FILTER_ADAPTIVE)
+    return fail(IST_E_UNSUPPORTED, "adaptive PNG row filters need the compressing encoder (pngLevel 1): the stored form filters nothing");
   if (ctx && ctx->png_level == 0 && ctx->png_color == IST_PNG_RGB)
     return fail(IST_E_UNSUPPORTED, "RGB PNG export needs the compressing encoder (pngLevel 1): the stored form writes RGBA only");
   return IST_OK;
@@ -152,6 +155,13 @@ int ist_ctx_set_png_color(ist_ctx* ctx, int color) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (color != IST_PNG_RGBA && color != IST_PNG_RGB) return fail(IST_E_INVALID, "PNG colour must be IST_PNG_RGBA (0) or IST_PNG_RGB (1)");
   ctx->png_color = color;
+  return IST_OK;
+}
+
+int ist_ctx_set_png_filter(ist_ctx* ctx, int filter) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (filter != IST_PNG_FILTER_PAETH && filter != IST_PNG_FILTER_ADAPTIVE) return fail(IST_E_INVALID, "PNG filter must be IST_PNG_FILTER_PAETH (0) or IST_PNG_FILTER_ADAPTIVE (1)");
+  ctx->png_filter = filter;
   return IST_OK;
 }
 

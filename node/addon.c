@@ -825,6 +825,8 @@ static napi_value set_png(napi_env env, napi_callback_info info, const char* usa
 static napi_value js_set_png_level(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngLevel(level)", ist_ctx_set_png_level); }
 /* setPngColor(color): 0 RGBA (colour type 6), 1 RGB (colour type 2, alpha not read; level 1 only) - ist_ctx_set_png_color */
 static napi_value js_set_png_color(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngColor(color)", ist_ctx_set_png_color); }
+/* setPngFilter(filter): 0 Paeth on every row, 1 adaptive (a type per row, chosen on the GPU; level 1 only) - ist_ctx_set_png_filter */
+static napi_value js_set_png_filter(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngFilter(filter)", ist_ctx_set_png_filter); }
 
 /* ---- resident bitmaps ------------------------------------------------------------------------------------------------------ */
 /* the code of a failed ist_bitmap_upload (it returns NULL; the message tells which rule failed) */
@@ -1027,6 +1029,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"encodeJpeg", NULL, js_encode_jpeg, NULL, NULL, NULL, napi_default, NULL},
       {"setPngLevel", NULL, js_set_png_level, NULL, NULL, NULL, napi_default, NULL},
       {"setPngColor", NULL, js_set_png_color, NULL, NULL, NULL, napi_default, NULL},
+      {"setPngFilter", NULL, js_set_png_filter, NULL, NULL, NULL, napi_default, NULL},
       {"decodePng", NULL, js_decode_png, NULL, NULL, NULL, napi_default, NULL},
       {"decodeImage", NULL, js_decode_image, NULL, NULL, NULL, napi_default, NULL},
       {"deviceCount", NULL, js_device_count, NULL, NULL, NULL, napi_default, NULL},

@@ -44,7 +44,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'devices', 'split', 'preview'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'devices', 'split', 'preview'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -194,7 +194,7 @@ function stitchSync(images, direction, opts) {
   return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a, false, ...g);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
-const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'preview'];
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'pngFilter', 'preview'];
 // the native arguments of request k of a batch, opts given apart (the JPEG batch takes its own two out first)
 function batchRequest(r, k, o) {
   for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
@@ -221,22 +221,22 @@ function stitchBatch(requests) {
 }
 function stitchBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchBatchSync(a) : []; }
 /** stitchBatch with the reference's export: resolves one {width, height, png: Buffer, plan} per request - the PNG stitchPng gives
- *  for it, in the form setPngLevel / setPngColor chose or opts = {pngLevel, pngColor} chooses for the whole batch (a per-request
- *  pngLevel or pngColor is refused) - and null for a request without images. The canvases never leave the GPU; one compression
+ *  for it, in the form setPngLevel / setPngColor / setPngFilter chose or opts = {pngLevel, pngColor, pngFilter} chooses for the whole
+ *  batch (a per-request pngLevel, pngColor or pngFilter is refused) - and null for a request without images. The canvases never leave the GPU; one compression
  *  launch encodes every file of a sub-batch. */
 function stitchPngBatch(requests, opts) {
   let a;
-  try { a = batchArgs(requests); pngColorOf(opts); } catch (e) { return Promise.reject(e); }
+  try { a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a.length) return Promise.resolve([]);
   try { pngForm(opts); } catch (e) { return Promise.reject(e); }
   return native.stitchPngBatch(a);
 }
-function stitchPngBatchSync(requests, opts) { const a = batchArgs(requests); pngColorOf(opts); if (!a.length) return []; pngForm(opts); return native.stitchPngBatchSync(a); }
+function stitchPngBatchSync(requests, opts) { const a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); if (!a.length) return []; pngForm(opts); return native.stitchPngBatchSync(a); }
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
   let a, h, pv;
-  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); } catch (e) { return Promise.reject(e); }
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); pngFilterOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
   return runStitch(opts, h, a, true, pv.length ? [null, 0] : [], pv, () => pngForm(opts));      // (no devices, split 0 ahead of the preview box)
 }
@@ -306,7 +306,26 @@ function pngColorOf(opts) {
   if (typeof opts.pngColor !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_COLOR, opts.pngColor)) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
   return PNG_COLOR[opts.pngColor];
 }
-function pngForm(opts) { pngLevel(opts); const c = pngColorOf(opts); if (c !== null) native.setPngColor(c); }
+/** opts.pngFilter: 'paeth' = filter type 4 on every row (default), 'adaptive' = a type per row, chosen on the GPU by the least sum of
+ *  absolute residuals (include/imagestitch.h states the rule), pngLevel 1 only: 6-7 per cent fewer bytes on photographs, 1-4 on flat
+ *  content. A process-wide setting of the native context, like pngColor; an unknown value is a TypeError before any native call. */
+const PNG_FILTER = { paeth: 0, adaptive: 1 };      // IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE
+function pngFilterOf(opts) {
+  if (!opts || opts.pngFilter === undefined || opts.pngFilter === null) return null;
+  if (typeof opts.pngFilter !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_FILTER, opts.pngFilter)) throw new TypeError("pngFilter must be 'paeth' or 'adaptive'");
+  return PNG_FILTER[opts.pngFilter];
+}
+function pngForm(opts) {
+  const c = pngColorOf(opts), f = pngFilterOf(opts);          // (both checked before the first native call)
+  pngLevel(opts);
+  if (c !== null) native.setPngColor(c);
+  if (f !== null) native.setPngFilter(f);
+}
+function setPngFilter(filter) {
+  const f = pngFilterOf({ pngFilter: filter });
+  if (f === null) throw new TypeError("pngFilter must be 'paeth' or 'adaptive'");
+  native.setPngFilter(f);
+}
 function setPngColor(color) {
   const c = pngColorOf({ pngColor: color });
   if (c === null) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
@@ -326,6 +345,7 @@ async function stitchFiles(paths, direction, opts, outPath) {
   const a = args([], direction, opts);
   const pv = previewArgs(opts);
   pngColorOf(opts);
+  pngFilterOf(opts);
   if (!paths || !paths.length) return null;
   const files = paths.map((p) => fs.readFileSync(p));
   // one native call: Huffman / inflate on host threads, reconstruction + stitch + PNG on the GPU, buffers stay in HBM
@@ -341,5 +361,5 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, decodePng, decodeImage, plan,
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, decodePng, decodeImage, plan,
                    decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
