@@ -220,7 +220,8 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
 int ctx_png_level(const ist_ctx* ctx);
 int ctx_png_color(const ist_ctx* ctx);                      // IST_PNG_RGBA / IST_PNG_RGB (ist_ctx_set_png_color)
 int ctx_png_filter(const ist_ctx* ctx);                     // IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE (ist_ctx_set_png_filter)
-// IST_E_UNSUPPORTED for the one pair of settings no encoder serves: the stored form (level 0) in RGB.  Every *_png entry point
+int ctx_png_match(const ist_ctx* ctx);                      // IST_PNG_MATCH_RUN / IST_PNG_MATCH_WINDOW (ist_ctx_set_png_match)
+// IST_E_UNSUPPORTED for the settings no encoder serves: the stored form (level 0) in RGB, with adaptive row filters or with window matches.  Every *_png entry point
 // calls it before anything is enqueued, and so does every place that picks between the stored and the compressing encoder.
 int ctx_png_form_check(const ist_ctx* ctx);
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p);   // the context's grow-only PNG scratch (kept across calls)

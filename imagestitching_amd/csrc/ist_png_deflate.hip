@@ -35,6 +35,23 @@
 // kernels' adaptive twins read that byte in step A, form the residual with that predictor and store the type as the row's filter
 // byte.  Everything behind the filter - grid, spans, tokens, code rule, stored against Huffman, pads, Adler-32, slabs, IDAT layout,
 // IHDR (filter method 0 allows a type per row) - is unchanged.
+//
+// WINDOW MATCHES (ist_ctx_set_png_match, IST_PNG_MATCH_WINDOW; the default stays the run form above).  A chunk may also copy from its
+// own earlier spans - what rendered text needs, whose residual patterns return at a distance, not next to each other.  In a chunk of n
+// bytes b every position p with p + 4 <= n has a key, the little-endian word b[p..p+3], and H(p) = (key * 2654435761 mod 2^32) >> 20.
+// cand(p) = the greatest q with a key, H(q) == H(p) and q < 64 (p / 64): the latest position of that hash in an EARLIER span, or none;
+// a function of the chunk's bytes alone.  Every span is parsed on its own from its first byte; at p: run = the bytes from p on equal to
+// b[p] inside the span; m = the bytes for which b[cand(p) + i] == b[p + i], at most 63 and not past the span's end, 0 without a
+// candidate (the source may run into the destination span: an overlapping copy).  m >= 4 and m >= run: one match of m bytes at
+// distance p - cand(p); otherwise run >= 4: the run form's literal + match of run - 1 at distance 1; otherwise a literal.  Codes: the
+// literal/length code by the rule of step C; a second code over the 30 distance symbols by the same rule (one symbol in use: length
+// 1; none: symbol 0 with length 1); one of them incomplete after 16 rounds: no window form.  Block: the run form's with HDIST = the
+// highest distance symbol in use and its HDIST + 1 lengths behind the 286 in the same 4-bit code; a match is length code, extra bits,
+// distance code, extra bits.  Choice per chunk: stored or run form exactly as the default setting decides; the window form replaces
+// that only where its chunk WITH lead bytes and pads is smaller (the 5-byte pads are not monotone in the body), a tie keeps the
+// default's bytes - so no chunk and no file grows, SLOT and ist_png_bound stand, and a chunk that keeps the run or stored form is the
+// default setting's chunk bit for bit.  Filter, colour form, grid, checksums, len16, slots, gather and slabs are untouched.  The
+// kernels are window twins of their own (deflate_chunk_window below); tests/png_match_reference.py restates the rule on the CPU.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -362,6 +379,7 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   }
 
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 2] = wall_clock64();
+  // (build_code below states this same rule a second time, for the window twins; a change here is a change there)
   // ---- C. code lengths and codes: ONE WAVE, in registers.  Not Huffman's algorithm: Shannon lengths (the smallest l with
   // count * 2^l >= total, <= 15 for a 16 KiB chunk; their Kraft sum is <= 1) and then the slack handed back - symbols
   // are shortened by one bit, shortest codes first, as long as the Kraft sum allows, round after round until the code is
@@ -758,6 +776,518 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void i
   deflate_adapt_batch_body<3>(B, row_begin, ftab);
 }
 
+// ---- window matches (IST_PNG_MATCH_WINDOW): the compressing kernels' window twins.  The rule is stated at the top of this file.
+//
+// One body for both colour forms and both row-filter settings (bpp and the table of row types are runtime arguments: only step A reads
+// them, and this body is bound by LDS, not by registers), so two kernels: single and batch.  LDS of a workgroup, 75828 bytes (two
+// workgroups on a CU of 160 KiB):
+//   buf    17408  the filtered chunk, 4 pad bytes after every 64 - alive until the parse is done - then the output bit stream
+//   candt  33792  16-bit entry per position, 2 pad entries after every 64 (a span is 33 dwords: a thread walking its own span and a wave
+//                 walking one span are both conflict free): first H(p), then cand(p); 0xFFFF = no key / no candidate
+//   htab   16384  the 4096-entry hash table: the latest position of every hash (32-bit, so that an LDS max resolves a round's inserts)
+//   area    4096  run form: histogram, lengths, codes (+ its one distance code); later the CRC tables
+//   area2   4096  window form: the same three and the distance histogram, lengths, codes
+// Steps: A filter into buf.  B every thread takes its span into registers, writes H of its 64 positions; wave 0 then walks the spans in
+// order - round s: lane i looks position 64 s + i up, then inserts it; a wave's LDS operations complete in order, so all look-ups of a
+// round precede its inserts and follow those of the round before - while waves 1-3 already count the run form and their Adler sums.
+// B2 every thread parses its span against the table (bytes compared in buf) into three 64-bit masks - literals, match starts, which
+// matches are window matches; a match ends where the next token starts - and counts the window form.  C three waves build the three
+// codes side by side.  D both forms' bits, two scans, the choice: stored or run as before, window where its padded chunk is smaller.  E as before.
+constexpr int NDSYM = 30;                // distance symbols
+constexpr int CAND_PITCH = 66;           // 16-bit entries per span in the candidate table
+constexpr uint32_t NOCAND = 0xFFFFu;
+
+// deflate distance symbol of distance d (1 .. 16383: symbols 0 .. 27): symbol, extra-bit count, extra-bit value
+__device__ __forceinline__ void dist_code(int d, int* sym, int* eb, int* ev) {
+  if (d <= 4) { *sym = d - 1; *eb = 0; *ev = 0; return; }
+  const int t = d - 1, e = (31 - __builtin_clz(t)) - 1;
+  *sym = 2 * (e + 1) + ((t >> e) & 1); *eb = e; *ev = t & ((1 << e) - 1);
+}
+
+// eq bit i: byte i of the span equals byte i - 1 (as in span_masks)
+__device__ __forceinline__ unsigned long long span_eq(const uint32_t (&sp)[16], int n) {
+  unsigned long long eq = 0;
+#pragma unroll
+  for (int d = 0; d < 16; ++d) {
+    const uint32_t w = sp[d];
+    const uint32_t prev = d ? (sp[d ? d - 1 : 0] >> 24) : (~w & 0xFFu);
+    const uint32_t x = w ^ ((w << 8) | prev);
+    const uint32_t nz = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+    const uint32_t z = (nz ^ 0x80808080u) >> 7;
+    eq |= static_cast<unsigned long long>(((z * 0x00204081u) >> 21) & 15u) << (4 * d);
+  }
+  const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+  return eq & valid & ~1ull;
+}
+
+// the four bytes at position p .. p + 3 of the filtered chunk (padded layout; p + 3 < CH), little-endian
+__device__ __forceinline__ uint32_t load4(const uint32_t* buf, int p) {
+  const int a = p & ~3, sh = 8 * (p & 3);
+  const uint32_t lo = buf[padpos(a) >> 2], hi = buf[padpos(min(a + 4, CH - 4)) >> 2];      // (the last dword again where there is no next one: shifted out)
+  return static_cast<uint32_t>(((static_cast<unsigned long long>(hi) << 32) | lo) >> sh);
+}
+
+// The tokens of a span in either form: bit i of lit - byte i is a literal; of mstart - a match starts at byte i and runs to the next
+// token (or the span's end); of win - that match's distance is i - cand(i), otherwise 1.
+struct SpanTokens { unsigned long long lit, mstart, win; };
+
+// One pass of a thread over its tokens, in order.  PASS 0: histograms (dhist may be null: the run form's distances need none);
+// 1: count bits; 2: emit.  cand: this span's row of the candidate table (read at window matches only); base: the span's first position.
+template <int PASS>
+__device__ __forceinline__ int walk_tokens(const uint32_t (&sp)[16], int n, const SpanTokens& M, const uint16_t* cand, const int base, uint32_t* hist, uint32_t* dhist,
+                                           const uint32_t* clen, const uint32_t* dclen, const uint32_t* code, const uint32_t* dcode, BitWriter* bw) {
+  int bits = 0;
+  const unsigned long long tok = M.lit | M.mstart;
+#pragma unroll 1
+  for (int d = 0; d < 16; ++d) {
+    if (4 * d >= n) break;
+    const uint32_t lit4 = static_cast<uint32_t>(M.lit >> (4 * d)) & 15u, ms4 = static_cast<uint32_t>(M.mstart >> (4 * d)) & 15u;
+    if (!(lit4 | ms4)) continue;
+    const uint32_t w = span_word(sp, d);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = 4 * d + k;
+      if (lit4 & (1u << k)) {
+        const uint32_t b = (w >> (8 * k)) & 255u;
+        if (PASS == 0) atomicAdd(&hist[b], 1u);
+        else if (PASS == 1) bits += static_cast<int>(clen[b]);
+        else { const uint32_t p = code[b]; bw->put(p & 0xFFFFu, static_cast<int>(p >> 16)); }
+      } else if (ms4 & (1u << k)) {
+        const unsigned long long next = (tok >> i) >> 1;
+        const int mlen = next ? __ffsll(static_cast<long long>(next)) : n - i;
+        const int dist = ((M.win >> i) & 1ull) ? base + i - static_cast<int>(cand[i]) : 1;
+        int msym, meb, mev, dsym, deb, dev;
+        len_code(mlen, &msym, &meb, &mev);
+        dist_code(dist, &dsym, &deb, &dev);
+        if (PASS == 0) { atomicAdd(&hist[msym], 1u); if (dhist) atomicAdd(&dhist[dsym], 1u); }
+        else if (PASS == 1) bits += static_cast<int>(clen[msym]) + meb + static_cast<int>(dclen[dsym]) + deb;
+        else {
+          const uint32_t pm = code[msym], pd = dcode[dsym];
+          bw->put(pm & 0xFFFFu, static_cast<int>(pm >> 16));
+          if (meb) bw->put(static_cast<uint32_t>(mev), meb);
+          bw->put(pd & 0xFFFFu, static_cast<int>(pd >> 16));
+          if (deb) bw->put(static_cast<uint32_t>(dev), deb);
+        }
+      }
+    }
+  }
+  return bits;
+}
+
+// (A second statement of step C of deflate_chunk above, whose machine code is pinned and is therefore not touched: a change of the rule
+// is a change of both.)
+// The code rule of step C (Shannon lengths, then the slack handed back in up to 16 rounds; canonical codes) for ONE WAVE over nsym <= 320
+// symbols: lane j holds symbols j, 64 + j, ... 256 + j.  Writes clen[] and code[] (code | length << 16, bit-reversed) and returns whether
+// the code is complete.  single: the distance code's two special cases - one symbol in use gets length 1, none in use gives symbol 0
+// length 1 (what the run form's header says).
+__device__ __forceinline__ bool build_code(const uint32_t* hist, uint32_t* clen, uint32_t* code, const int nsym, const int lane, const bool single) {
+  uint32_t cnt[5]; int ln[5];
+  uint32_t tot = 0;
+  int used = 0;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) { const int sy = 64 * q + lane; cnt[q] = sy < nsym ? hist[sy] : 0u; tot += cnt[q]; used += __popcll(__ballot(cnt[q] != 0u)); }
+  if (single && used <= 1) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int sy = 64 * q + lane;
+      if (sy < nsym) { const bool it = used ? cnt[q] != 0u : sy == 0; clen[sy] = it ? 1u : 0u; code[sy] = it ? (1u << 16) : 0u; }
+    }
+    return true;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+  int kraft = 0, cls[16];
+#pragma unroll
+  for (int l = 0; l < 16; ++l) cls[l] = 0;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    ln[q] = 0;
+    if (cnt[q]) {
+      const uint32_t r = (tot + cnt[q] - 1) / cnt[q];
+      int l = r <= 1u ? 0 : 32 - __clz(static_cast<int>(r - 1u));
+      l = l < 1 ? 1 : (l > 15 ? 15 : l);
+      ln[q] = l;
+      kraft += 1 << (15 - l);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) kraft += __shfl_xor(kraft, off);
+#pragma unroll
+  for (int l = 1; l < 16; ++l) {
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) c += __popcll(__ballot(ln[q] == l));
+    cls[l] = c;
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  auto ranks_in = [&](int l, int (&rk)[5]) {
+    int acc = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const unsigned long long m = __ballot(ln[q] == l);
+      rk[q] = acc + __popcll(m & below);
+      acc += __popcll(m);
+    }
+  };
+  int slack = 32768 - kraft;
+  for (int round = 0; round < 16 && slack > 0; ++round) {
+#pragma unroll
+    for (int l = 2; l < 16; ++l) {
+      const int cost = 1 << (15 - l);
+      const int take = min(cls[l], slack / cost);
+      if (take > 0) {
+        int rk[5];
+        ranks_in(l, rk);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) if (ln[q] == l && rk[q] < take) ln[q] = l - 1;
+        cls[l] -= take; cls[l - 1] += take; slack -= take * cost;
+      }
+    }
+  }
+  if (slack != 0 || tot == 0) return false;
+  int first[16]; int cd = 0;
+  first[0] = 0;
+#pragma unroll
+  for (int l = 1; l < 16; ++l) { cd = (cd + cls[l - 1]) << 1; first[l] = cd; }
+  int cdq[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+  for (int l = 1; l < 16; ++l) {
+    if (cls[l] == 0) continue;
+    int rk[5];
+    ranks_in(l, rk);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) if (ln[q] == l) cdq[q] = first[l] + rk[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const int sy = 64 * q + lane;
+    if (sy < nsym) {
+      clen[sy] = static_cast<uint32_t>(ln[q]);
+      code[sy] = ln[q] ? (rev_bits(static_cast<uint32_t>(cdq[q]), ln[q]) | (static_cast<uint32_t>(ln[q]) << 16)) : 0u;
+    }
+  }
+  return true;
+}
+
+// One workgroup compresses chunk `chunk` with window matches.  bpp: 4 or 3; ftab: the row types of the adaptive filters, or null for
+// Paeth on every row.
+__device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const int64_t chunk, const uint8_t* ftab, const int bpp) {
+  static_assert(PADDED >= SLOT, "the output buffer aliases the filtered chunk");
+  __shared__ __attribute__((aligned(16))) uint32_t buf[PADDED / 4];
+  uint8_t* const filt = reinterpret_cast<uint8_t*>(buf);
+  uint32_t* const outw = buf;
+  __shared__ __attribute__((aligned(16))) uint32_t area[1024];       // (>= 3 * 288 + 2 * 32)
+  __shared__ __attribute__((aligned(16))) uint32_t area2[1024];      // (>= 3 * 288 + 3 * 32)
+  __shared__ int htab[4096];
+  __shared__ __attribute__((aligned(4))) uint16_t candt[256 * CAND_PITCH];
+  uint32_t* const hist = area; uint32_t* const clen = area + 288; uint32_t* const code = area + 576;
+  uint32_t* const rdclen = area + 864; uint32_t* const rdcode = area + 896;                       // the run form's one distance code
+  uint32_t* const hist2 = area2; uint32_t* const clen2 = area2 + 288; uint32_t* const code2 = area2 + 576;
+  uint32_t* const dhist = area2 + 864; uint32_t* const dclen = area2 + 896; uint32_t* const dcode = area2 + 928;
+  uint32_t (*const T)[256] = reinterpret_cast<uint32_t (*)[256]>(area);
+  __shared__ uint32_t wsum[8];
+  __shared__ int s_out_len, s_skip_run, s_skip_ll, s_skip_d, s_hdist;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool adapt = ftab != nullptr;
+
+  int64_t y0; int nrows, x0, npr;
+  if (P.rows_per_chunk > 0) {
+    y0 = chunk * P.rows_per_chunk; nrows = static_cast<int>(min(static_cast<int64_t>(P.rows_per_chunk), P.h - y0)); x0 = 0; npr = static_cast<int>(P.w);
+  } else {
+    y0 = chunk / P.pieces_per_row; nrows = 1;
+    const int piece = static_cast<int>(chunk - y0 * P.pieces_per_row);
+    x0 = piece * P.piece_px; npr = static_cast<int>(min(static_cast<int64_t>(P.piece_px), P.w - x0));
+  }
+  const int hasf = x0 == 0 ? 1 : 0;
+  const int rowlen = hasf + bpp * npr;
+  const int len = rowlen * nrows;                // <= CH by construction
+
+  for (int i = tid; i < 1024; i += 256) { area[i] = 0; area2[i] = 0; }
+  for (int i = tid; i < 4096; i += 256) htab[i] = -1;
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 0] = wall_clock64();
+  // ---- A. load + filter into LDS (as deflate_chunk's; the type of a row is 4 without a table)
+  const int npix = npr * nrows;
+  for (int q0 = tid; q0 < npix; q0 += 1024) {
+    uint32_t cur[4], a[4], b[4], c[4], ft[4]; int pos[4]; bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + 256 * u;
+      on[u] = q < npix;
+      cur[u] = a[u] = b[u] = c[u] = 0u; pos[u] = 0; ft[u] = 4u;
+      if (on[u]) {
+        const int r = nrows == 1 ? 0 : q / npr, xx = q - r * npr;
+        const int64_t y = y0 + r; const int x = x0 + xx;
+        const uint8_t* row = P.canvas + static_cast<size_t>(y) * P.pitch;
+        cur[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x));
+        if (x > 0) a[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x - 1));
+        if (y > 0) {
+          b[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x));
+          if (x > 0) c[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x - 1));
+        }
+        pos[u] = r * rowlen + hasf + bpp * xx;
+        if (adapt) ft[u] = static_cast<uint32_t>(ftab[y]);
+        if (hasf && xx == 0) filt[padpos(r * rowlen)] = static_cast<uint8_t>(ft[u]);      // filter type of the row
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (!on[u]) continue;
+      const uint32_t fv = filter4(ft[u], cur[u], a[u], b[u], c[u]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) if (k < bpp) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
+    }
+  }
+  __syncthreads();
+  // (behind the barrier: other waves zeroed these words above; they are first read in step D, several barriers on)
+  if (tid == 0) { rdclen[0] = 1u; rdcode[0] = 1u << 16; }
+
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 1] = wall_clock64();
+  // ---- B. spans into registers; H of every position; the candidate table (wave 0) beside the run form's histogram and the Adler partials
+  const int base = tid * SPAN;
+  const int n = max(0, min(SPAN, len - base));
+  uint32_t sp[16];
+  {
+    const uint32_t* mw = reinterpret_cast<const uint32_t*>(filt + tid * (SPAN + 4));
+#pragma unroll
+    for (int d = 0; d < 16; ++d) sp[d] = mw[d];
+  }
+  uint16_t* const cand = candt + tid * CAND_PITCH;
+  {
+    const uint32_t nextw = tid < 255 ? *reinterpret_cast<const uint32_t*>(filt + (tid + 1) * (SPAN + 4)) : 0u;
+    uint32_t* const cw = reinterpret_cast<uint32_t*>(cand);
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      uint32_t pair = 0;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int i = 2 * j + e, d = i >> 2, sh = 8 * (i & 3);
+        const uint32_t lo = sp[d], hi = d < 15 ? sp[d < 15 ? d + 1 : 15] : nextw;
+        const uint32_t key = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+        const uint32_t hv = base + i + 4 <= len ? (key * 2654435761u) >> 20 : NOCAND;
+        pair |= hv << (16 * e);
+      }
+      cw[j] = pair;
+    }
+  }
+  __syncthreads();                                   // every H is written (and every span is in registers)
+  if (wave == 0) {
+    const int nspans = (len + SPAN - 1) / SPAN;
+    uint32_t hn = candt[lane];
+    for (int s = 0; s < nspans; ++s) {
+      uint16_t* const e = candt + s * CAND_PITCH + lane;
+      const uint32_t h = hn;
+      if (s + 1 < nspans) hn = e[CAND_PITCH];          // (the next round's hash is on its way while this round's look-up returns)
+      if (h != NOCAND) {
+        const int c = htab[h];
+        *e = static_cast<uint16_t>(c < 0 ? NOCAND : static_cast<uint32_t>(c));
+        atomicMax(&htab[h], SPAN * s + lane);
+      }
+    }
+  }
+  const unsigned long long eq = span_eq(sp, n);
+  const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+  SpanTokens RT;                                      // the run form, as span_masks has it
+  {
+    const unsigned long long t = eq & (eq >> 1) & (eq >> 2);
+    const unsigned long long covered = (t | (t << 1) | (t << 2)) & valid;
+    RT.lit = valid & ~covered; RT.mstart = covered & ~(covered << 1); RT.win = 0ull;
+  }
+  walk_tokens<0>(sp, n, RT, cand, base, hist, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (tid == 0) { atomicAdd(&hist[256], 1u); atomicAdd(&hist2[256], 1u); }
+  uint32_t a1 = 0, a2 = 0;
+#pragma unroll
+  for (int d = 0; d < 16; ++d)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = 4 * d + k;
+      const uint32_t b = i < n ? (sp[d] >> (8 * k)) & 255u : 0u;
+      a1 += b; a2 += static_cast<uint32_t>(len - (base + i)) * b;
+    }
+  a2 %= 65521u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); }
+  if (lane == 0) { wsum[wave] = a1; wsum[4 + wave] = a2; }
+  __syncthreads();                                   // the candidate table is complete
+  if (tid == 0) {
+    P.ad_a[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    P.ad_b[chunk] = (wsum[4] + wsum[5] + wsum[6] + wsum[7]) % 65521u;
+    P.ad_n[chunk] = static_cast<uint32_t>(len);
+  }
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 2] = wall_clock64();
+  // ---- B2. the window parse of this span: greedy from its first byte
+  // First, for all 64 positions at once (independent loads: their latency overlaps), whether the candidate's four key bytes are the
+  // position's own - a hash collision, the usual case on photographs, ends here; a match of fewer than 4 bytes is no match, so only
+  // positions that pass (and have 4 bytes left in the span) are measured in the serial walk, 4 bytes a step.
+  unsigned long long ok4 = 0ull;
+  {
+    const uint32_t nextw = tid < 255 ? *reinterpret_cast<const uint32_t*>(filt + (tid + 1) * (SPAN + 4)) : 0u;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+      const int d = i >> 2, sh = 8 * (i & 3);
+      const uint32_t lo = sp[d], hi = d < 15 ? sp[d < 15 ? d + 1 : 15] : nextw;
+      const uint32_t key = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+      const uint32_t c = cand[i];                     // (no branch: position 0 stands in where there is no candidate, so every load can be issued at once)
+      const uint32_t src = load4(buf, c != NOCAND ? static_cast<int>(c) : 0);
+      ok4 |= static_cast<unsigned long long>(c != NOCAND && i + 4 <= n && src == key) << i;
+    }
+  }
+  SpanTokens WT{0ull, 0ull, 0ull};
+  for (int i = 0; i < n;) {
+    const int run = __ffsll(static_cast<long long>(~((eq >> i) >> 1)));      // bytes from i on that equal byte i
+    int m = 0;
+    if ((ok4 >> i) & 1ull) {
+      const int c = static_cast<int>(cand[i]), cap = min(63, n - i);
+      m = 4;
+      while (m + 4 <= cap) {
+        const uint32_t x = load4(buf, c + m) ^ load4(buf, base + i + m);
+        if (x) { m += (__ffs(static_cast<int>(x)) - 1) >> 3; break; }
+        m += 4;
+      }
+      if (m + 4 > cap) while (m < cap && filt[padpos(c + m)] == filt[padpos(base + i + m)]) ++m;
+    }
+    if (m >= 4 && m >= run) { WT.mstart |= 1ull << i; WT.win |= 1ull << i; i += m; }
+    else if (run >= 4) { WT.lit |= 1ull << i; WT.mstart |= 2ull << i; i += run; }
+    else { WT.lit |= 1ull << i; i += 1; }
+  }
+  walk_tokens<0>(sp, n, WT, cand, base, hist2, dhist, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const int lead = chunk == 0 ? 2 : 0;               // the zlib header travels with the first chunk
+  __syncthreads();                                   // both histograms are final; nobody reads buf as the filtered chunk any more
+
+  // ---- C. three codes, a wave each
+  if (wave == 0) { const bool ok = build_code(hist, clen, code, NSYM, lane, false); if (lane == 0) s_skip_run = ok ? 0 : 1; }
+  else if (wave == 1) { const bool ok = build_code(hist2, clen2, code2, NSYM, lane, false); if (lane == 0) s_skip_ll = ok ? 0 : 1; }
+  else if (wave == 2) {
+    const unsigned long long um = __ballot(lane < NDSYM && dhist[lane < NDSYM ? lane : 0] != 0u);
+    const bool ok = build_code(dhist, dclen, dcode, NDSYM, lane, true);
+    if (lane == 0) { s_skip_d = ok ? 0 : 1; s_hdist = um ? 63 - __clzll(static_cast<long long>(um)) : 0; }
+  }
+  __syncthreads();
+  const bool skip_run = s_skip_run != 0, skip_win = s_skip_ll != 0 || s_skip_d != 0;
+  const int hdist = s_hdist;
+
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 3] = wall_clock64();
+  // ---- D. bits per thread in both forms, two exclusive scans, the choice between stored, run and window form
+  const int rbits = skip_run ? 0 : walk_tokens<1>(sp, n, RT, cand, base, nullptr, nullptr, clen, rdclen, nullptr, nullptr, nullptr);
+  const int wbits = skip_win ? 0 : walk_tokens<1>(sp, n, WT, cand, base, nullptr, nullptr, clen2, dclen, nullptr, nullptr, nullptr);
+  int rincl = rbits, wincl = wbits;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(rincl, off), u = __shfl_up(wincl, off);
+    if (lane >= off) { rincl += t; wincl += u; }
+  }
+  if (lane == 63) { wsum[wave] = static_cast<uint32_t>(rincl); wsum[4 + wave] = static_cast<uint32_t>(wincl); }
+  __syncthreads();
+  int rwave = 0, wwave = 0;
+  for (int k = 0; k < wave; ++k) { rwave += static_cast<int>(wsum[k]); wwave += static_cast<int>(wsum[4 + k]); }
+  const int rtotal = static_cast<int>(wsum[0] + wsum[1] + wsum[2] + wsum[3]), wtotal = static_cast<int>(wsum[4] + wsum[5] + wsum[6] + wsum[7]);
+  const int rend = lead * 8 + HDR_BITS + rtotal + static_cast<int>(clen[256]);
+  const int wend = lead * 8 + HDR_BITS + 4 * hdist + wtotal + static_cast<int>(clen2[256]);
+  const int rbytes = (rend + 3 + 7) / 8 + 4, wbytes = (wend + 3 + 7) / 8 + 4;      // + the empty stored block that re-aligns to a byte
+  // 0 stored, 1 run, 2 window.  Stored against run as deflate_chunk decides it; the window form only where its chunk WITH its pads is
+  // smaller (the 5-byte pads to a multiple of 16 are not monotone in the body: k pads with 5 k = -x mod 16, k = 13 (-x mod 16) mod 16)
+  int form = 0, best = lead + 5 + len;
+  if (!skip_run && rbytes < best) { form = 1; best = rbytes; }
+  auto padded = [](int x) { return x + 5 * ((13 * ((16 - (x & 15)) & 15)) & 15); };
+  if (!skip_win && padded(wbytes) < padded(best)) { form = 2; best = wbytes; }
+  for (int i = tid; i < SLOT / 4; i += 256) outw[i] = 0;
+  __syncthreads();
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 4] = wall_clock64();
+  uint8_t* outb = reinterpret_cast<uint8_t*>(outw);
+  int body_end;                                       // bytes before the alignment pads
+  if (form != 0) {
+    const bool win = form == 2;
+    const uint32_t* const cl = win ? clen2 : clen; const uint32_t* const co = win ? code2 : code;
+    const uint32_t* const dl = win ? dclen : rdclen; const uint32_t* const dc = win ? dcode : rdcode;
+    const int hd = win ? hdist : 0, end_bit = win ? wend : rend;
+    const int my_start = lead * 8 + HDR_BITS + 4 * hd + (win ? wwave + wincl - wbits : rwave + rincl - rbits);
+    // header: BFINAL 0, BTYPE 2, HLIT 29, HDIST hd, HCLEN 15, the 19 code-length-code lengths, 286 + hd + 1 code lengths in 4 bits each
+    const int hb = lead * 8;
+    if (tid == 0) {
+      if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
+      or_bits(outw, hb, 4u | (29u << 3) | (static_cast<uint32_t>(hd) << 8) | (15u << 13), 17);
+    }
+    if (tid < 19) or_bits(outw, hb + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);
+    for (int s = tid; s < NSYM + hd + 1; s += 256) {
+      const uint32_t l = s < NSYM ? cl[s] : dl[s - NSYM];
+      or_bits(outw, hb + 17 + 57 + 4 * s, rev_bits(l, 4), 4);
+    }
+    BitWriter bw; bw.init(outw, my_start);
+    walk_tokens<2>(sp, n, win ? WT : RT, cand, base, nullptr, nullptr, nullptr, nullptr, co, dc, &bw);
+    bw.flush();
+    if (tid == 0) or_bits(outw, end_bit - static_cast<int>(cl[256]), co[256] & 0xFFFFu, static_cast<int>(cl[256]));
+    body_end = (end_bit + 3 + 7) / 8;                 // 3 zero bits: BFINAL 0, BTYPE 00; then to the byte boundary
+    __syncthreads();
+    if (tid == 0) { outb[body_end + 2] = 0xFF; outb[body_end + 3] = 0xFF; }      // LEN 0000, NLEN FFFF
+    body_end += 4;
+  } else {
+    if (tid == 0) {
+      if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
+      uint8_t* q = outb + lead;
+      q[0] = 0; q[1] = len & 0xFF; q[2] = (len >> 8) & 0xFF; q[3] = (~len) & 0xFF; q[4] = ((~len) >> 8) & 0xFF;
+    }
+#pragma unroll
+    for (int d = 0; d < 16; ++d)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * d + k < n) outb[lead + 5 + base + 4 * d + k] = static_cast<uint8_t>(sp[d] >> (8 * k));
+    body_end = lead + 5 + len;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int total = body_end;
+    while (total & 15) { outb[total + 3] = 0xFF; outb[total + 4] = 0xFF; total += 5; }   // empty stored blocks: 00 00 00 FF FF
+    s_out_len = total;
+    P.len16[chunk] = static_cast<uint32_t>(total >> 4);
+  }
+  __syncthreads();
+
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 5] = wall_clock64();
+  // ---- E. write the chunk to its slot; raw CRC of its bytes (as deflate_chunk's)
+  for (int i = tid; i < 1024; i += 256) area[i] = P.tables[i];
+  __syncthreads();
+  const int out_len = s_out_len;
+  uint8_t* slot = P.slots + static_cast<size_t>(chunk) * SLOT;
+  uint32_t crc = 0;
+  for (int u = tid; u < (out_len >> 4); u += 256) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(outw + 4 * u);
+    *reinterpret_cast<u32x4*>(slot + 16 * static_cast<size_t>(u)) = v;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t c = 0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      c ^= w[d];
+      c = T[3][c & 0xFF] ^ T[2][(c >> 8) & 0xFF] ^ T[1][(c >> 16) & 0xFF] ^ T[0][c >> 24];
+    }
+    crc ^= gf_mul(P.xpow16[(out_len >> 4) - 1 - u], c);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) crc ^= __shfl_xor(crc, off);
+  __syncthreads();
+  if (lane == 0) wsum[wave] = crc;
+  __syncthreads();
+  if (tid == 0) P.crc[chunk] = wsum[0] ^ wsum[1] ^ wsum[2] ^ wsum[3];
+  if (P.dbg && tid == 0) P.dbg[chunk * 8 + 6] = wall_clock64();
+}
+
+__global__ __launch_bounds__(256) void ist_png_deflate_window_kernel(const DeflArgs P, const uint8_t* ftab, const int bpp) {
+  deflate_chunk_window(P, P.chunk0 + blockIdx.x, ftab, bpp);
+}
+// batch: file f's rows are table entries [row_begin[f], row_begin[f + 1]) when there is a table
+__global__ __launch_bounds__(256) void ist_png_deflate_window_batch_kernel(const DeflBatchArgs B, const int64_t* row_begin, const uint8_t* ftab, const int bpp) {
+  const int64_t g = blockIdx.x;
+  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
+  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
+  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
+  DeflArgs P;
+  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
+  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
+  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
+  P.tables = B.tables; P.xpow16 = B.xpow16;
+  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
+  P.chunk0 = 0; P.dbg = nullptr;
+  deflate_chunk_window(P, g - base, ftab ? ftab + ((ConstPtr<int64_t>)row_begin)[f] : nullptr, bpp);
+}
+
 struct GatherArgs { const uint8_t* slots; uint8_t* out; const int64_t* dst; const uint32_t* len16; int64_t chunk0; };
 
 __device__ __forceinline__ void gather_chunk(const uint8_t* s, uint8_t* d, const int units) {
@@ -927,6 +1457,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int color = ctx_png_color(ctx);
   const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
+  const bool window = ctx_png_match(ctx) == IST_PNG_MATCH_WINDOW;
   const ChunkGrid g = make_grid(w, h, color);
   if (g.n_chunks > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
   if (png_deflate_bound(w, h, color) > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
@@ -1042,9 +1573,11 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
       if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, st, F);
       else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, st, F);
       PNG_HIP(hipGetLastError());
-      if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
+      if (window) hipLaunchKernelGGL(ist_png_deflate_window_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab), bpp_of(color));
+      else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
       else hipLaunchKernelGGL(ist_png_deflate_adapt_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
     }
+    else if (window) hipLaunchKernelGGL(ist_png_deflate_window_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(nullptr), bpp_of(color));
     else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
     PNG_HIP(hipGetLastError());
@@ -1159,6 +1692,7 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int color = ctx_png_color(ctx);
   const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
+  const bool window = ctx_png_match(ctx) == IST_PNG_MATCH_WINDOW;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::vector<ChunkGrid> grid(nf);
   std::vector<int64_t> begin(nf + 1, 0), row_begin(nf + 1, 0);      // (row_begin: the rows of every file, file-major - the adaptive form's table)
@@ -1227,9 +1761,11 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
     if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, stream, F);
     else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, stream, F);
     PNG_HIP(hipGetLastError());
-    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
+    if (window) hipLaunchKernelGGL(ist_png_deflate_window_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab), bpp_of(color));
+    else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
     else hipLaunchKernelGGL(ist_png_deflate_adapt_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
   }
+  else if (window) hipLaunchKernelGGL(ist_png_deflate_window_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, static_cast<const int64_t*>(nullptr), static_cast<const uint8_t*>(nullptr), bpp_of(color));
   else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
   else hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
   PNG_HIP(hipGetLastError());

@@ -24,7 +24,10 @@ namespace ist {
 int ctx_png_level(const ist_ctx* ctx) { return ctx ? ctx->png_level : 0; }
 int ctx_png_color(const ist_ctx* ctx) { return ctx ? ctx->png_color : IST_PNG_RGBA; }
 int ctx_png_filter(const ist_ctx* ctx) { return ctx ? ctx->png_filter : IST_PNG_FILTER_PAETH; }
+int ctx_png_match(const ist_ctx* ctx) { return ctx ? ctx->png_match : IST_PNG_MATCH_RUN; }
 int ctx_png_form_check(const ist_ctx* ctx) {
+  if (ctx && ctx->png_level == 0 && ctx->png_match == IST_PNG_MATCH_WINDOW)
+    return fail(IST_E_UNSUPPORTED, "PNG window matches need the compressing encoder (pngLevel 1): the stored form matches nothing");
   if (ctx && ctx->png_level == 0 && ctx->png_filter == IST_PNG_FILTER_ADAPTIVE)
     return fail(IST_E_UNSUPPORTED, "adaptive PNG row filters need the compressing encoder (pngLevel 1): the stored form filters nothing");
   if (ctx && ctx->png_level == 0 && ctx->png_color == IST_PNG_RGB)
@@ -162,6 +165,13 @@ int ist_ctx_set_png_filter(ist_ctx* ctx, int filter) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (filter != IST_PNG_FILTER_PAETH && filter != IST_PNG_FILTER_ADAPTIVE) return fail(IST_E_INVALID, "PNG filter must be IST_PNG_FILTER_PAETH (0) or IST_PNG_FILTER_ADAPTIVE (1)");
   ctx->png_filter = filter;
+  return IST_OK;
+}
+
+int ist_ctx_set_png_match(ist_ctx* ctx, int match) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (match != IST_PNG_MATCH_RUN && match != IST_PNG_MATCH_WINDOW) return fail(IST_E_INVALID, "PNG match must be IST_PNG_MATCH_RUN (0) or IST_PNG_MATCH_WINDOW (1)");
+  ctx->png_match = match;
   return IST_OK;
 }
 

@@ -64,6 +64,7 @@ DEFAULT_OPTS = {
     "edgeAA": None,         # anti-alias fractional rectangle edges by area coverage (IST_FILTER_EDGE_AA); None: on iff `platform` is given (edge_aa_of)
     "pngLevel": None,       # PNG export form of the *_png / stitch_files calls: 0 stored, 1 compressed on the GPU; None = DEFAULT_PNG_LEVEL
     "pngColor": None,       # PNG colour form of the same calls: 'rgba' (colour type 6) or 'rgb' (colour type 2: alpha is not read; level 1 only); None = 'rgba'
+    "pngMatch": None,       # PNG matches of the same calls: 'run' (runs of equal bytes inside a 64-byte span) or 'window' (also copies from earlier spans of the chunk, found on the GPU; level 1 only); None = 'run'
     "pngFilter": None,      # PNG row filters of the same calls: 'paeth' (type 4 on every row) or 'adaptive' (a type per row, chosen on the GPU; level 1 only); None = 'paeth'
     "devices": None,        # list of GPU indices (devices[0] = root): shard the stitch over them from this one process (ist_stitch_rgba8_multi)
     "preview": None,        # (box_w, box_h): stitch_png / stitch_files also return the canvas shrunk to fit that box (the redraw into the preview
@@ -78,6 +79,7 @@ _SPLITS = {"image": L.SPLIT_IMAGE, "band": L.SPLIT_BAND, "rows": L.SPLIT_ROWS, "
 DEFAULT_PNG_LEVEL = 1
 PNG_COLORS = {"rgba": 0, "rgb": 1}           # IST_PNG_RGBA / IST_PNG_RGB
 PNG_FILTERS = {"paeth": 0, "adaptive": 1}    # IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE
+PNG_MATCHES = {"run": 0, "window": 1}        # IST_PNG_MATCH_RUN / IST_PNG_MATCH_WINDOW
 
 
 def _png_color(color):
@@ -96,6 +98,15 @@ def _png_filter(row_filter):
     if not isinstance(row_filter, str) or row_filter not in PNG_FILTERS:
         raise ValueError("pngFilter must be 'paeth' or 'adaptive', not %r" % (row_filter,))
     return PNG_FILTERS[row_filter]
+
+
+def _png_match(match):
+    """IST_PNG_MATCH_* of a pngMatch / match= value (None: runs), checked before any library call"""
+    if match is None:
+        return PNG_MATCHES["run"]
+    if not isinstance(match, str) or match not in PNG_MATCHES:
+        raise TypeError("pngMatch must be 'run' or 'window', not %r" % (match,))
+    return PNG_MATCHES[match]
 
 
 def debug_png_grid(w, h, color="rgba"):
@@ -389,16 +400,17 @@ def _ctx(device=0):
     return c
 
 
-def _ctx_png(device, level, color=None, row_filter=None):
-    """The context with its PNG export form set (ist_ctx_set_png_level, ist_ctx_set_png_color, ist_ctx_set_png_filter - level, colour
-    and row filter together, so a call never inherits the colour or the filter of the one before it): a per-context setting, so
-    concurrent callers that want different forms on one device should serialise.  An unknown colour or filter raises ValueError before
-    the context is asked for."""
-    form, filt = _png_color(color), _png_filter(row_filter)
+def _ctx_png(device, level, color=None, row_filter=None, match=None):
+    """The context with its PNG export form set (ist_ctx_set_png_level, ist_ctx_set_png_color, ist_ctx_set_png_filter,
+    ist_ctx_set_png_match - level, colour, row filter and matches together, so a call never inherits the colour, the filter or the
+    matches of the one before it): a per-context setting, so concurrent callers that want different forms on one device should
+    serialise.  An unknown colour or filter raises ValueError, an unknown match TypeError, before the context is asked for."""
+    form, filt, mat = _png_color(color), _png_filter(row_filter), _png_match(match)
     c = _ctx(device)
     L.check(L.lib.ist_ctx_set_png_level(c, int(DEFAULT_PNG_LEVEL if level is None else level)))
     L.check(L.lib.ist_ctx_set_png_color(c, form))
     L.check(L.lib.ist_ctx_set_png_filter(c, filt))
+    L.check(L.lib.ist_ctx_set_png_match(c, mat))
     return c
 
 
@@ -467,7 +479,7 @@ def _stitch(images, direction, o, device, kind, jpeg=()):
         devs = (C.c_int * len(o["devices"]))(*[int(d) for d in o["devices"]])
         name, head, mid = name + "_multi", (devs, len(devs)), (_SPLITS[o["split"]],)
     else:
-        head, mid = (_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"]) if kind == "png" else _ctx(device),), jpeg
+        head, mid = (_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"]) if kind == "png" else _ctx(device),), jpeg
     # (rgba8, what the N-API addon binds: plan, render, and the export as ONE DMA into a pinned block of the library's pool; the numpy
     # array below is a view of that block - no host copy - and returns it to the pool when it is garbage collected)
     fn = getattr(L.lib, name + ("_preview" if pv is not None else ""))
@@ -496,7 +508,7 @@ def stitch(images, direction, opts=None, device=0):
     return _stitch(images, direction, o, device, "rgba8")
 
 
-_BATCH_REFUSED = ("devices", "split", "pngLevel", "pngColor", "pngFilter", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
+_BATCH_REFUSED = ("devices", "split", "pngLevel", "pngColor", "pngFilter", "pngMatch", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
 
 
 def _batch_requests(reqs, why):
@@ -553,19 +565,20 @@ def stitch_batch(requests, device=0):
     return _run_batch(L.lib.ist_stitch_rgba8_batch, _ctx(device), creqs)
 
 
-def stitch_png_batch(requests, device=0, level=None, color=None, row_filter=None):
+def stitch_png_batch(requests, device=0, level=None, color=None, row_filter=None, match=None):
     """Many independent stitch_png() calls in one go (ist_stitch_png_batch): stitch_batch with a PNG file in place of each
     canvas.  Every sub-batch is rendered by one launch per kernel form and encoded by ONE compression launch; only the files
     cross PCIe.  requests as for stitch_batch (no per-request pngLevel or pngColor: `level` chooses the form for the whole batch, 0
-    stored, 1 compressed, None = DEFAULT_PNG_LEVEL, `color` its colour form, 'rgba' or 'rgb' as opts['pngColor'], and `row_filter` its row filters, 'paeth' or 'adaptive' as opts['pngFilter']).  Returns a list of {'width', 'height', 'png': bytes}, with None for a request
+    stored, 1 compressed, None = DEFAULT_PNG_LEVEL, `color` its colour form, 'rgba' or 'rgb' as opts['pngColor'], `row_filter` its row filters, 'paeth' or 'adaptive' as opts['pngFilter'], and `match` its matches, 'run' or 'window' as opts['pngMatch']).  Returns a list of {'width', 'height', 'png': bytes}, with None for a request
     without images; each file's zlib stream is stitch_png(*requests[k])['png']'s, byte for byte."""
     reqs = list(requests)
     if not reqs:
         return []
     _png_color(color)
     _png_filter(row_filter)
-    creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=, color=, row_filter=")
-    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level, color, row_filter), creqs, key="png")
+    _png_match(match)
+    creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=, color=, row_filter=, match=")
+    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level, color, row_filter, match), creqs, key="png")
 
 
 def launch_jobs(jobs, srcs, outs, stream=None):
@@ -735,6 +748,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     o = _merge(opts)
     _png_color(o["pngColor"])
     _png_filter(o["pngFilter"])
+    _png_match(o["pngMatch"])
     n = len(paths)
     if n == 0:
         return None
@@ -744,7 +758,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     cplan, out, ln = L.Plan(), C.POINTER(C.c_uint8)(), C.c_int64(0)
     pv = _preview_arg(o)
     fn = L.lib.ist_stitch_paths_png if pv is None else L.lib.ist_stitch_paths_png_preview
-    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
+    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
                                  *([] if pv is None else [C.byref(pv)]))), cplan)
     if size is None:
         return None
@@ -758,17 +772,20 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     return res
 
 
-def encode_png(pixels, device=0, level=None, color=None, row_filter=None):
+def encode_png(pixels, device=0, level=None, color=None, row_filter=None, match=None):
     """Lossless PNG of an HxWx4 uint8 array, encoded on the GPU (export step, utils/canvas.js:205-242).
     level 0: stored deflate blocks; 1: Paeth + run-length + Huffman (ist_ctx_set_png_level).  color 'rgba' (default, colour type 6) or
     'rgb' (colour type 2: alpha is not read; level 1 only - ist_ctx_set_png_color).  row_filter 'paeth' (default: filter type 4 on
     every row) or 'adaptive' (a type per row, chosen on the GPU by the least sum of absolute residuals; level 1 only -
-    ist_ctx_set_png_filter; `filter` is the resampling filter, hence the name)."""
+    ist_ctx_set_png_filter; `filter` is the resampling filter, hence the name).  match 'run' (default: runs of equal bytes inside a
+    64-byte span) or 'window' (a chunk also copies from its earlier spans, found on the GPU; never a larger file, half the bytes
+    on rendered text (profiles/r17_png_match.json), a slower encoder; level 1 only - ist_ctx_set_png_match)."""
     _png_color(color)
     _png_filter(row_filter)
+    _png_match(match)
     a, ptr, pitch = _host_rows(_rgba(pixels))
     out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level, color, row_filter), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
+    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level, color, row_filter, match), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
     return _take_png(out, n)
 
 
@@ -779,14 +796,16 @@ def stitch_png(images, direction, opts=None, device=0):
     o = _merge(opts)
     _png_color(o["pngColor"])
     _png_filter(o["pngFilter"])
+    _png_match(o["pngMatch"])
     return _stitch(images, direction, o, device, "png")
 
 
-def encode_png_device(canvas, out=None, stream=None, device=None, level=None, color=None, row_filter=None):
+def encode_png_device(canvas, out=None, stream=None, device=None, level=None, color=None, row_filter=None, match=None):
     """PNG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor) into a CUDA uint8 tensor; returns (tensor, length).
-    level, color, row_filter: as encode_png."""
+    level, color, row_filter, match: as encode_png."""
     _png_color(color)
     _png_filter(row_filter)
+    _png_match(match)
     import torch
     _check_canvas(canvas, "encode_png_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
@@ -794,7 +813,7 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None, co
     st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
     n = C.c_int64(0)
     dev = canvas.device.index if device is None else device
-    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level, color, row_filter), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
+    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level, color, row_filter, match), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
                                         C.c_void_p(dst), cap, C.byref(n), C.c_void_p(st.cuda_stream)))
     return out[off:off + n.value], n.value
 
@@ -913,13 +932,14 @@ def stitch_jpeg_batch(requests, device=0):
     return _run_batch(L.lib.ist_stitch_jpeg_batch, _ctx(device), creqs, (qs, ss), "jpeg")
 
 
-def encode_png_batch_device(canvases, outs=None, stream=None, level=None, color=None, row_filter=None):
+def encode_png_batch_device(canvases, outs=None, stream=None, level=None, color=None, row_filter=None, match=None):
     """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
     launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns
-    [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas at the same level, color and row_filter."""
+    [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas at the same level, color, row_filter and match."""
     _png_color(color)
     _png_filter(row_filter)
-    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level, color, row_filter), "encode_png_batch_device", list(canvases),
+    _png_match(match)
+    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level, color, row_filter, match), "encode_png_batch_device", list(canvases),
                                 lambda k, w, h: L.lib.ist_png_bound(w, h), outs, stream)
 
 

@@ -324,6 +324,30 @@ IST_API int ist_ctx_set_png_color(ist_ctx* ctx, int color);
  * names pngLevel 1). */
 enum { IST_PNG_FILTER_PAETH = 0, IST_PNG_FILTER_ADAPTIVE = 1 };
 IST_API int ist_ctx_set_png_filter(ist_ctx* ctx, int filter);
+/* PNG matches for every *_png entry point of this context (single, batch, bitmaps, files, paths, *_png_preview, ist_render_png and
+ * ist_png_encode_*), in either colour form and with either row-filter setting.  IST_PNG_MATCH_RUN (default): a run of equal bytes
+ * inside a 64-byte span is a literal and one match at distance 1; every call does exactly what it did before this setting existed.
+ * IST_PNG_MATCH_WINDOW: a chunk may also copy from earlier spans of itself, by this rule.  In a chunk of n bytes b every position p
+ * with p + 4 <= n has a key, the little-endian 32-bit word b[p..p+3], and H(p) = ((key * 2654435761) mod 2^32) >> 20.  cand(p) is the
+ * greatest q with a key, H(q) == H(p) and q < 64 * (p / 64) - the most recent position of that hash in an earlier span - or none: a
+ * function of the chunk's bytes alone.  Every span is parsed on its own from its first byte.  At p: run = the bytes from p on equal
+ * to b[p], inside the span; m = the number of bytes for which b[cand(p) + i] == b[p + i], at most 63 and not past the span's end, 0
+ * without a candidate (the source may run into the destination span: deflate's overlapping copy).  m >= 4 and m >= run: one match of m
+ * bytes at distance p - cand(p); otherwise run >= 4: the literal and a match of run - 1 bytes at distance 1, as before; otherwise a
+ * literal.  The literal/length code follows the existing code rule; a second code over the 30 distance symbols follows the same rule
+ * (one distance symbol in use: length 1; none: symbol 0 with length 1); a chunk one of whose codes does not complete in the rule's 16
+ * rounds has no window form.  The block is the run form's with HDIST = the highest distance symbol in use, its HDIST + 1 lengths
+ * behind the 286 literal/length lengths in the same 4-bit code; a match is length code, length extra bits, distance code, distance
+ * extra bits.  Per chunk the default setting's choice between stored and run form is made first, unchanged; the window form replaces
+ * it only where its chunk, lead bytes and pads to 16 bytes included, is smaller (a tie keeps the default setting's bytes): no chunk
+ * and no file is larger than with IST_PNG_MATCH_RUN, and ist_png_bound is unchanged.  Filter, colour form, grid, spans, stored form,
+ * pads, the Adler-32, slabs, the IDAT layout and the IHDR are unchanged.  Rendered text comes out at half the bytes (49.9 per cent on a 4032 x 27216 canvas, profiles/r17_png_match.json), photographs
+ * keep the run form in nearly every chunk, and the encoder takes several times as long, which is why it is not the default.
+ * IST_E_NO_CONTEXT for a NULL context, IST_E_INVALID for any other value.  The stored form (level 0) matches nothing: on a context at
+ * level 0 with IST_PNG_MATCH_WINDOW every *_png call fails with IST_E_UNSUPPORTED before anything is enqueued (the message names
+ * pngLevel 1). */
+enum { IST_PNG_MATCH_RUN = 0, IST_PNG_MATCH_WINDOW = 1 };
+IST_API int ist_ctx_set_png_match(ist_ctx* ctx, int match);
 /* compile an op list for a canvas (replaces createOffscreenCanvas + the recorded draw calls; utils/canvas.js:131,
  * index.js:1391-1428, 1532-1551).  clear_rgba = canvas initial colour ({0,0,0,0} for a fresh canvas).
  * clip = NULL renders the whole canvas; otherwise only that region is written (getImageData(0,0,1,1), 1564). */

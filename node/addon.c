@@ -827,6 +827,8 @@ static napi_value js_set_png_level(napi_env env, napi_callback_info info) { retu
 static napi_value js_set_png_color(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngColor(color)", ist_ctx_set_png_color); }
 /* setPngFilter(filter): 0 Paeth on every row, 1 adaptive (a type per row, chosen on the GPU; level 1 only) - ist_ctx_set_png_filter */
 static napi_value js_set_png_filter(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngFilter(filter)", ist_ctx_set_png_filter); }
+/* setPngMatch(match): 0 runs inside a 64-byte span, 1 window (a chunk also copies from its earlier spans, found on the GPU; level 1 only) - ist_ctx_set_png_match */
+static napi_value js_set_png_match(napi_env env, napi_callback_info info) { return set_png(env, info, "setPngMatch(match)", ist_ctx_set_png_match); }
 
 /* ---- resident bitmaps ------------------------------------------------------------------------------------------------------ */
 /* the code of a failed ist_bitmap_upload (it returns NULL; the message tells which rule failed) */
@@ -1030,6 +1032,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"setPngLevel", NULL, js_set_png_level, NULL, NULL, NULL, napi_default, NULL},
       {"setPngColor", NULL, js_set_png_color, NULL, NULL, NULL, napi_default, NULL},
       {"setPngFilter", NULL, js_set_png_filter, NULL, NULL, NULL, napi_default, NULL},
+      {"setPngMatch", NULL, js_set_png_match, NULL, NULL, NULL, napi_default, NULL},
       {"decodePng", NULL, js_decode_png, NULL, NULL, NULL, napi_default, NULL},
       {"decodeImage", NULL, js_decode_image, NULL, NULL, NULL, napi_default, NULL},
       {"deviceCount", NULL, js_device_count, NULL, NULL, NULL, napi_default, NULL},

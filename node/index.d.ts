@@ -18,6 +18,7 @@ export interface StitchOptions {
   edgeAA?: boolean;                         // anti-alias fractional rectangle edges (ctx.scale(superSample), unrounded cursor); default: true iff `platform` is given
   onProgress?: (percent: number) => void;   // stitchProgress checkpoints (index.js:1193-1611)
   pngLevel?: 0 | 1;                         // PNG export form: 0 stored, 1 compressed on the GPU (process-wide once set)
+  pngMatch?: 'run' | 'window';              // PNG matches: 'run' runs inside a 64-byte span (default), 'window' a chunk also copies from its earlier spans, found on the GPU - never larger, half the bytes on rendered text, a slower encoder, pngLevel 1 only (process-wide once set)
   pngFilter?: 'paeth' | 'adaptive';         // PNG row filters: 'paeth' type 4 on every row (default), 'adaptive' a type per row chosen on the GPU - smaller files, pngLevel 1 only (process-wide once set)
   pngColor?: 'rgba' | 'rgb';                // PNG colour form: 'rgba' colour type 6 (default), 'rgb' colour type 2 - alpha is not read, pngLevel 1 only (process-wide once set; the Canvas shim always exports RGBA)
   devices?: number[];                       // GPUs to shard the stitch over from this process; devices[0] is the root (RCCL gather over xGMI)
@@ -33,14 +34,14 @@ export interface StitchResult { width: number; height: number; data: Buffer; pla
 export function stitch(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchResult | null>;
 export function stitchSync(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchResult | null;
 export function plan(images: StitchImage[], direction: Direction, opts?: StitchOptions): StitchPlan | null;
-// one request of a batch: a stitch on the batch's GPU (devices / split / pngLevel / pngColor / pngFilter / preview are refused with a TypeError)
-export interface StitchRequest { images: StitchImage[]; direction: Direction; opts?: Omit<StitchOptions, 'devices' | 'split' | 'pngLevel' | 'pngColor' | 'pngFilter' | 'preview' | 'onProgress'>; }
+// one request of a batch: a stitch on the batch's GPU (devices / split / pngLevel / pngColor / pngFilter / pngMatch / preview are refused with a TypeError)
+export interface StitchRequest { images: StitchImage[]; direction: Direction; opts?: Omit<StitchOptions, 'devices' | 'split' | 'pngLevel' | 'pngColor' | 'pngFilter' | 'pngMatch' | 'preview' | 'onProgress'>; }
 export function stitchBatch(requests: StitchRequest[]): Promise<(StitchResult | null)[]>;
 export function stitchBatchSync(requests: StitchRequest[]): (StitchResult | null)[];
 export interface Preview { width: number; height: number; data: Buffer; }     // RGBA8, straight alpha, dense rows
 export interface StitchPngResult { width: number; height: number; png: Buffer; plan: StitchPlan; preview?: Preview; }   // preview: only when opts.preview was given
 export function stitchPng(images: StitchImage[], direction: Direction, opts?: StitchOptions): Promise<StitchPngResult | null>;
-export interface PngFormOptions { pngLevel?: 0 | 1; pngColor?: 'rgba' | 'rgb'; pngFilter?: 'paeth' | 'adaptive'; }      // one PNG form for a whole call
+export interface PngFormOptions { pngLevel?: 0 | 1; pngColor?: 'rgba' | 'rgb'; pngFilter?: 'paeth' | 'adaptive'; pngMatch?: 'run' | 'window'; }      // one PNG form for a whole call
 export function stitchPngBatch(requests: StitchRequest[]): Promise<(StitchPngResult | null)[]>;
 export function stitchPngBatchSync(requests: StitchRequest[]): (StitchPngResult | null)[];
 export function stitchPngBatch(requests: StitchRequest[], opts: PngFormOptions): Promise<(StitchPngResult | null)[]>;      // one PNG form for the whole batch
@@ -49,7 +50,7 @@ export function encodePng(data: Uint8Array, width: number, height: number, opts?
 // the export with fileType 'jpg': a baseline JFIF file, pinned byte for byte by include/imagestitch.h (alpha is not read); preview and devices are refused
 export interface JpegOptions { quality?: number; subsampling?: '420' | '444' | 420 | 444; optimize?: boolean; }      // quality: an integer 1..100, default 90; subsampling default '420'; optimize default false: the file's own Huffman tables (smaller file, same pixels)
 export interface StitchJpegResult { width: number; height: number; jpeg: Buffer; plan: StitchPlan; }
-export function stitchJpeg(images: StitchImage[] | Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split' | 'preview' | 'pngLevel' | 'pngColor' | 'pngFilter'> & JpegOptions): Promise<StitchJpegResult | null>;
+export function stitchJpeg(images: StitchImage[] | Bitmap[], direction: Direction, opts?: Omit<StitchOptions, 'devices' | 'split' | 'preview' | 'pngLevel' | 'pngColor' | 'pngFilter' | 'pngMatch'> & JpegOptions): Promise<StitchJpegResult | null>;
 export function encodeJpeg(data: Uint8Array, width: number, height: number, opts?: JpegOptions): Buffer;
 // stitchPngBatch with a JPEG in place of each PNG: file k is the file stitchJpeg resolves for request k; null for a request without images
 export interface StitchJpegRequest { images: StitchImage[]; direction: Direction; opts?: StitchRequest['opts'] & JpegOptions; }
@@ -58,6 +59,7 @@ export function stitchJpegBatchSync(requests: StitchJpegRequest[]): (StitchJpegR
 export function setPngLevel(level: 0 | 1): void;
 export function setPngColor(color: 'rgba' | 'rgb'): void;
 export function setPngFilter(filter: 'paeth' | 'adaptive'): void;
+export function setPngMatch(match: 'run' | 'window'): void;
 export function decodePng(file: Uint8Array): { width: number; height: number; data: Buffer };
 export function stitchFiles(paths: string[], direction: Direction, opts?: StitchOptions, outPath?: string): Promise<StitchPngResult | null>;
 export function decodeImage(file: Uint8Array): { width: number; height: number; orientation: number; opaque: boolean; data: Buffer };

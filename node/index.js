@@ -44,7 +44,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'devices', 'split', 'preview'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'devices', 'split', 'preview'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -194,7 +194,7 @@ function stitchSync(images, direction, opts) {
   return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a, false, ...g);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
-const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'pngFilter', 'preview'];
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'preview'];
 // the native arguments of request k of a batch, opts given apart (the JPEG batch takes its own two out first)
 function batchRequest(r, k, o) {
   for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
@@ -221,22 +221,22 @@ function stitchBatch(requests) {
 }
 function stitchBatchSync(requests) { const a = batchArgs(requests); return a.length ? native.stitchBatchSync(a) : []; }
 /** stitchBatch with the reference's export: resolves one {width, height, png: Buffer, plan} per request - the PNG stitchPng gives
- *  for it, in the form setPngLevel / setPngColor / setPngFilter chose or opts = {pngLevel, pngColor, pngFilter} chooses for the whole
- *  batch (a per-request pngLevel, pngColor or pngFilter is refused) - and null for a request without images. The canvases never leave the GPU; one compression
+ *  for it, in the form setPngLevel / setPngColor / setPngFilter / setPngMatch chose or opts = {pngLevel, pngColor, pngFilter, pngMatch}
+ *  chooses for the whole batch (a per-request pngLevel, pngColor, pngFilter or pngMatch is refused) - and null for a request without images. The canvases never leave the GPU; one compression
  *  launch encodes every file of a sub-batch. */
 function stitchPngBatch(requests, opts) {
   let a;
-  try { a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); } catch (e) { return Promise.reject(e); }
+  try { a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); pngMatchOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a.length) return Promise.resolve([]);
   try { pngForm(opts); } catch (e) { return Promise.reject(e); }
   return native.stitchPngBatch(a);
 }
-function stitchPngBatchSync(requests, opts) { const a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); if (!a.length) return []; pngForm(opts); return native.stitchPngBatchSync(a); }
+function stitchPngBatchSync(requests, opts) { const a = batchArgs(requests); pngColorOf(opts); pngFilterOf(opts); pngMatchOf(opts); if (!a.length) return []; pngForm(opts); return native.stitchPngBatchSync(a); }
 /** stitch + the reference's export step: resolves {width, height, png: Buffer (a lossless PNG file), plan}. The canvas
  *  never leaves the GPU; only the PNG bytes cross PCIe (utils/canvas.js:205-242, index.js:1577-1579). */
 function stitchPng(images, direction, opts) {
   let a, h, pv;
-  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); pngFilterOf(opts); } catch (e) { return Promise.reject(e); }
+  try { h = bitmapHandles(images, opts); a = args(images, direction, opts); pv = previewArgs(opts); pngColorOf(opts); pngFilterOf(opts); pngMatchOf(opts); } catch (e) { return Promise.reject(e); }
   if (!a[0].length) return Promise.resolve(null);
   return runStitch(opts, h, a, true, pv.length ? [null, 0] : [], pv, () => pngForm(opts));      // (no devices, split 0 ahead of the preview box)
 }
@@ -315,11 +315,27 @@ function pngFilterOf(opts) {
   if (typeof opts.pngFilter !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_FILTER, opts.pngFilter)) throw new TypeError("pngFilter must be 'paeth' or 'adaptive'");
   return PNG_FILTER[opts.pngFilter];
 }
+/** opts.pngMatch: 'run' = runs of equal bytes inside a 64-byte span (default), 'window' = a chunk also copies from its earlier spans,
+ *  found on the GPU (include/imagestitch.h states the rule), pngLevel 1 only: never a larger file, half the bytes on rendered text
+ *  (profiles/r17_png_match.json), a slower encoder. A process-wide setting of the native context, like pngColor; an unknown value is a TypeError
+ *  before any native call. */
+const PNG_MATCH = { run: 0, window: 1 };      // IST_PNG_MATCH_RUN / IST_PNG_MATCH_WINDOW
+function pngMatchOf(opts) {
+  if (!opts || opts.pngMatch === undefined || opts.pngMatch === null) return null;
+  if (typeof opts.pngMatch !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_MATCH, opts.pngMatch)) throw new TypeError("pngMatch must be 'run' or 'window'");
+  return PNG_MATCH[opts.pngMatch];
+}
 function pngForm(opts) {
-  const c = pngColorOf(opts), f = pngFilterOf(opts);          // (both checked before the first native call)
+  const c = pngColorOf(opts), f = pngFilterOf(opts), m = pngMatchOf(opts);          // (all checked before the first native call)
   pngLevel(opts);
   if (c !== null) native.setPngColor(c);
   if (f !== null) native.setPngFilter(f);
+  if (m !== null) native.setPngMatch(m);
+}
+function setPngMatch(match) {
+  const m = pngMatchOf({ pngMatch: match });
+  if (m === null) throw new TypeError("pngMatch must be 'run' or 'window'");
+  native.setPngMatch(m);
 }
 function setPngFilter(filter) {
   const f = pngFilterOf({ pngFilter: filter });
@@ -346,6 +362,7 @@ async function stitchFiles(paths, direction, opts, outPath) {
   const pv = previewArgs(opts);
   pngColorOf(opts);
   pngFilterOf(opts);
+  pngMatchOf(opts);
   if (!paths || !paths.length) return null;
   const files = paths.map((p) => fs.readFileSync(p));
   // one native call: Huffman / inflate on host threads, reconstruction + stitch + PNG on the GPU, buffers stay in HBM
@@ -361,5 +378,5 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, decodePng, decodeImage, plan,
+module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
                    decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
