@@ -190,6 +190,12 @@ SYMBOLS = [
     ("ist_image_decode_rgba8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64]),
     ("ist_decode_files_device", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_int64), C.POINTER(ImageDesc)]),
+    ("ist_jpeg_scaled_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("ist_decode_scale_fit", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("ist_image_decode_rgba8_scaled", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_int64]),
+    ("ist_decode_files_device_scaled", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ImageDesc)]),
+    ("ist_debug_jpeg_scaled_launches", C.c_int64, []),
     ("ist_ctx_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("ist_ctx_last_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     ("ist_stitch_files_png", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_double,
@@ -211,6 +217,7 @@ SYMBOLS = [
                                  C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
     ("ist_bitmap_upload", C.c_void_p, [C.c_void_p, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t]),
     ("ist_bitmaps_decode", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_void_p)]),
+    ("ist_bitmaps_decode_scaled", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
     ("ist_bitmap_desc", C.c_int, [C.c_void_p, C.POINTER(ImageDesc)]),
     ("ist_bitmap_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64]),
     ("ist_bitmap_retain", None, [C.c_void_p]),

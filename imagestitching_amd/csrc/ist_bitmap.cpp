@@ -135,15 +135,21 @@ ist_bitmap* ist_bitmap_upload(ist_ctx* ctx, const ist_image_desc* desc, const ui
 }
 
 int ist_bitmaps_decode(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, ist_bitmap** out) {
+  return ist_bitmaps_decode_scaled(ctx, files, lens, n, nullptr, out);
+}
+
+int ist_bitmaps_decode_scaled(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, const int32_t* denom, ist_bitmap** out) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (n <= 0) return IST_NOTHING_TO_DO;
   if (!files || !lens || !out) return fail(IST_E_INVALID, "ist_bitmaps_decode: NULL argument");
   if (n > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one call");
   for (int i = 0; i < n; ++i) out[i] = nullptr;
+  const int drc = check_denoms("ist_bitmaps_decode_scaled", denom, n);
+  if (drc) return drc;
   std::vector<ist_bitmap*> made;
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
-  const int rc = decode_files_locked(ctx, files, lens, n, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
+  const int rc = decode_files_locked(ctx, files, lens, n, denom, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
     for (int i = 0; i < n; ++i) {
       ist_bitmap* b = bitmap_alloc(ctx->device, descs[static_cast<size_t>(i)]);
       if (!b) return g_last_code;

@@ -23,14 +23,16 @@ std::atomic<int64_t> g_gpu_entropy_files{0};
 std::atomic<int64_t> g_gpu_entropy_sync_launches{0};
 
 // ---- JPEG decode: entropy decoding on the host, reconstruction on the GPU (ist_jpeg.cpp / ist_jpeg_kernels.hip) ----------
-void jpeg_layout(const JpegImage& J, size_t* off, JpegDevLayout* L) {
+// denom > 1: a component's sample plane holds S x S bytes per block, S = its reduced IDCT size
+void jpeg_layout(const JpegImage& J, size_t* off, JpegDevLayout* L, int denom = 1) {
   std::memset(L, 0, sizeof(*L));
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
     const size_t nblk = static_cast<size_t>(C.blocks_x) * C.blocks_y;
+    const size_t S = denom > 1 ? static_cast<size_t>(jpeg_scaled_idct_size(8 / denom, C.h, C.v, J.hmax, J.vmax)) : 8;
     L->coef[c] = arena_take(off, nblk * 128);
     L->q[c] = arena_take(off, 128);
-    L->plane[c] = arena_take(off, nblk * 64);
+    L->plane[c] = arena_take(off, nblk * S * S);
   }
 }
 // the `ent` arena part of a host-decoded image (components in sparse form)
@@ -62,9 +64,9 @@ JpegDeviceJob jpeg_device_job(const JpegImage& J, uint8_t* d, const JpegDevLayou
 }
 
 int jpeg_enqueue(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLayout& L, uint8_t* d_out, size_t out_pitch, hipStream_t stream, bool coef_on_device = false,
-                 bool chroma_done = false) {
+                 bool chroma_done = false, int denom = 1) {
   JpegDeviceJob job = jpeg_device_job(J, d, L, d_out, out_pitch);
-  job.chroma_done = chroma_done;
+  job.chroma_done = chroma_done; job.denom = denom;
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
     const size_t nblk = static_cast<size_t>(C.blocks_x) * C.blocks_y;
@@ -84,7 +86,39 @@ int jpeg_enqueue(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLa
       IST_HIP(hipMemcpyAsync(d_coef, C.coef.data(), nblk * 128, hipMemcpyHostToDevice, stream));
     }
   }
-  return jpeg_launch_reconstruct(job, stream);
+  return denom > 1 ? jpeg_launch_reconstruct_scaled(job, stream) : jpeg_launch_reconstruct(job, stream);      // (1 / 1: the full-size launches and nothing else)
+}
+
+bool valid_denom(int d) { return d == 1 || d == 2 || d == 4 || d == 8; }
+
+// one JPEG file -> RGBA8 in host memory at 1 / denom
+int jpeg_decode_rgba8(const char* who, ist_ctx* ctx, const uint8_t* file, int64_t len, int denom, uint8_t* out, size_t out_pitch, int64_t out_rows) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  JpegImage J;
+  int rc = jpeg_parse_and_entropy_decode(file, len, &J, false);
+  if (rc) return rc;
+  int sw = J.width, sh = J.height;
+  jpeg_scaled_size(J.width, J.height, denom, &sw, &sh);
+  if (!out || out_pitch < static_cast<size_t>(sw) * 4 || out_rows < sh) return fail(IST_E_INVALID, std::string(who) + ": output buffer too small");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  // one device allocation: coefficients + tables + sample planes + RGBA
+  size_t off = 0;
+  JpegDevLayout L;
+  jpeg_layout(J, &off, &L, denom);
+  jpeg_layout_sparse(J, &off, &L);                      // (one arena holds both parts here)
+  const size_t row = static_cast<size_t>(sw) * 4;
+  const size_t o_out = arena_take(&off, row * sh);
+  uint8_t* d = nullptr;
+  rc = ctx->scratch_arena.grow(off);
+  if (rc) return rc;
+  d = static_cast<uint8_t*>(ctx->scratch_arena.p);
+  rc = jpeg_enqueue(J, d, d, L, d + o_out, row, ctx->stream, false, false, denom);
+  if (rc) return rc;
+  std::vector<RowsCopy> down{RowsCopy{d + o_out, nullptr, out, out_pitch, row, static_cast<size_t>(sh)}};
+  rc = stager_of(ctx).download(down, ctx->stream);
+  (void)hipStreamSynchronize(ctx->stream);              // nothing of this call may still read the arena when the next call reuses it
+  return rc;
 }
 
 bool is_jpeg(const uint8_t* f, int64_t n) { return f && n >= 2 && f[0] == 0xFF && f[1] == 0xD8; }
@@ -104,30 +138,7 @@ int ist_jpeg_info(const uint8_t* file, int64_t len, int32_t* width, int32_t* hei
 }
 
 int ist_jpeg_decode_rgba8(ist_ctx* ctx, const uint8_t* file, int64_t len, uint8_t* out, size_t out_pitch, int64_t out_rows) {
-  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  JpegImage J;
-  int rc = jpeg_parse_and_entropy_decode(file, len, &J, false);
-  if (rc) return rc;
-  if (!out || out_pitch < static_cast<size_t>(J.width) * 4 || out_rows < J.height) return fail(IST_E_INVALID, "ist_jpeg_decode_rgba8: output buffer too small");
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  DeviceGuard g(ctx->device);
-  // one device allocation: coefficients + tables + sample planes + RGBA
-  size_t off = 0;
-  JpegDevLayout L;
-  jpeg_layout(J, &off, &L);
-  jpeg_layout_sparse(J, &off, &L);                      // (one arena holds both parts here)
-  const size_t row = static_cast<size_t>(J.width) * 4;
-  const size_t o_out = arena_take(&off, row * J.height);
-  uint8_t* d = nullptr;
-  rc = ctx->scratch_arena.grow(off);
-  if (rc) return rc;
-  d = static_cast<uint8_t*>(ctx->scratch_arena.p);
-  rc = jpeg_enqueue(J, d, d, L, d + o_out, row, ctx->stream);
-  if (rc) return rc;
-  std::vector<RowsCopy> down{RowsCopy{d + o_out, nullptr, out, out_pitch, row, static_cast<size_t>(J.height)}};
-  rc = stager_of(ctx).download(down, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);              // nothing of this call may still read the arena when the next call reuses it
-  return rc;
+  return jpeg_decode_rgba8("ist_jpeg_decode_rgba8", ctx, file, len, 1, out, out_pitch, out_rows);
 }
 
 // format-agnostic front door: PNG (host decode) or JPEG (host entropy decode + GPU reconstruction)
@@ -147,6 +158,27 @@ int ist_image_decode_rgba8(ist_ctx* ctx, const uint8_t* file, int64_t len, uint8
   if (is_misc(file, len)) return ist_misc_decode_rgba8(file, len, out, out_pitch, out_rows);
   if (is_webp(file, len)) return webp_decode_rgba8(file, len, out, out_pitch, out_rows);
   return ist_png_decode_rgba8(file, len, out, out_pitch, out_rows);
+}
+
+int ist_image_decode_rgba8_scaled(ist_ctx* ctx, const uint8_t* file, int64_t len, int32_t denom, uint8_t* out, size_t out_pitch, int64_t out_rows) {
+  if (!valid_denom(denom)) return fail(IST_E_INVALID, "ist_image_decode_rgba8_scaled: the file's denominator " + std::to_string(denom) + " is not 1, 2, 4 or 8");
+  if (is_jpeg(file, len)) return jpeg_decode_rgba8("ist_image_decode_rgba8_scaled", ctx, file, len, denom, out, out_pitch, out_rows);
+  return ist_image_decode_rgba8(ctx, file, len, out, out_pitch, out_rows);      // other file types decode at 1 / 1
+}
+
+int ist_jpeg_scaled_size(int32_t w, int32_t h, int32_t denom, int32_t* sw, int32_t* sh) {
+  if (w < 1 || h < 1 || !valid_denom(denom) || !sw || !sh) return fail(IST_E_INVALID, "ist_jpeg_scaled_size: bad argument");
+  int a = 0, b = 0;
+  jpeg_scaled_size(w, h, denom, &a, &b);
+  *sw = a; *sh = b;
+  return IST_OK;
+}
+
+int ist_decode_scale_fit(int32_t w, int32_t h, int32_t min_w, int32_t min_h) {
+  if (w < 1 || h < 1 || min_w < 1 || min_h < 1) return fail(IST_E_INVALID, "ist_decode_scale_fit: bad argument");
+  for (int d = 8; d > 1; d /= 2)
+    if ((static_cast<int64_t>(w) + d - 1) / d >= min_w && (static_cast<int64_t>(h) + d - 1) / d >= min_h) return d;
+  return 1;
 }
 
 }  // extern "C"
@@ -201,8 +233,8 @@ static int ensure_image_lanes(ist_ctx* ctx, int n) {
   return IST_OK;
 }
 
-FileDecoder::FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph)
-    : ctx_(ctx), files_(files), lens_(lens), n_(n), ph_(ph), dec_(static_cast<size_t>(n)),
+FileDecoder::FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, const int32_t* denom)
+    : ctx_(ctx), files_(files), lens_(lens), n_(n), ph_(ph), denom_(denom), dec_(static_cast<size_t>(n)),
       on_gpu_(static_cast<size_t>(n), 0), taken_(static_cast<size_t>(n), 0), uploaded_(static_cast<size_t>(n), 0), started_(static_cast<size_t>(n), 0),
       chroma_done_(static_cast<size_t>(n), 0), jo_(static_cast<size_t>(n)) {}
 FileDecoder::~FileDecoder() {
@@ -241,10 +273,12 @@ std::vector<ist_image_desc> FileDecoder::descs(const int64_t* lens) const {
     ist_image_desc& d = descs[static_cast<size_t>(i)];
     std::memset(&d, 0, sizeof d);
     d.width = D.w; d.height = D.h; d.orientation = D.orient ? D.orient : 1; d.opaque = D.jpeg ? 1 : 0; d.file_size = lens[i];
+    if (denom_of(i) > 1) { int sw = 0, sh = 0; jpeg_scaled_size(D.w, D.h, denom_of(i), &sw, &sh); d.bmp_width = sw; d.bmp_height = sh; }
   }
   return descs;
 }
-void FileDecoder::layout(size_t* off) { for (int i = 0; i < n_; ++i) if (dec_[static_cast<size_t>(i)].jpeg) jpeg_layout(dec_[static_cast<size_t>(i)].J, off, &jo_[static_cast<size_t>(i)]); }
+void FileDecoder::layout(size_t* off) { for (int i = 0; i < n_; ++i) if (dec_[static_cast<size_t>(i)].jpeg) jpeg_layout(dec_[static_cast<size_t>(i)].J, off, &jo_[static_cast<size_t>(i)], denom_of(i)); }
+int FileDecoder::denom_of(int i) const { return denom_ && dec_[static_cast<size_t>(i)].jpeg ? denom_[i] : 1; }      // (other file types decode at 1 / 1)
 
 int FileDecoder::start(uint8_t* arena, uint8_t* const* img, const size_t* pitch) {
   arena_ = arena; img_ = img; pitch_ = pitch;
@@ -274,7 +308,7 @@ int FileDecoder::take(int i, hipStream_t consumer) {
   if (rc) return rc;
   Dec& D = dec_[k];
   taken_[k] = 1;
-  if (on_gpu_[k]) return jpeg_enqueue(D.J, arena_, nullptr, jo_[k], img_[i], pitch_[i], consumer, true, chroma_done_[k] != 0);
+  if (on_gpu_[k]) return jpeg_enqueue(D.J, arena_, nullptr, jo_[k], img_[i], pitch_[i], consumer, true, chroma_done_[k] != 0, denom_of(i));
   const size_t row = static_cast<size_t>(D.w) * 4;
   if (!D.jpeg) {                                  // PNG / BMP / GIF / WebP: decoded on the thread, uploaded here
     std::vector<RowsCopy> up;
@@ -299,7 +333,7 @@ int FileDecoder::take(int i, hipStream_t consumer) {
     rc = ctx_->scratch_ent.grow(need, need / 2);
     if (rc) return rc;
   }
-  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, img_[i], pitch_[i], consumer, false);
+  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, img_[i], pitch_[i], consumer, false, false, denom_of(i));
 }
 
 int FileDecoder::finish(hipStream_t consumer) {
@@ -355,7 +389,7 @@ int FileDecoder::chroma_all(hipStream_t consumer) {
   std::vector<JpegDeviceJob> chroma;
   for (int i = 0; i < n_; ++i) {
     const size_t k = static_cast<size_t>(i);
-    if (!on_gpu_[k] || dec_[k].J.ncomp != 3) continue;
+    if (!on_gpu_[k] || dec_[k].J.ncomp != 3 || denom_of(i) > 1) continue;      // (a reduced image makes its own planes, sized by its IDCTs)
     chroma.push_back(jpeg_device_job(dec_[k].J, arena_, jo_[k], nullptr, 0));
     chroma_done_[k] = 1;
   }
@@ -412,11 +446,17 @@ void FileDecoder::worker(int i) {
   uploaded_[k] = 1;
 }
 
-int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
+int check_denoms(const char* who, const int32_t* denom, int n) {
+  for (int i = 0; denom && i < n; ++i)
+    if (!valid_denom(denom[i])) return fail(IST_E_INVALID, std::string(who) + ": the denominator of image " + std::to_string(i) + " is " + std::to_string(denom[i]) + ", not 1, 2, 4 or 8");
+  return IST_OK;
+}
+
+int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, const int32_t* denom,
                         const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place) {
   DeviceGuard g(ctx->device);
   Phases ph(ctx);
-  FileDecoder fd(ctx, files, lens, n, &ph);
+  FileDecoder fd(ctx, files, lens, n, &ph, denom);
   int rc = fd.headers();
   if (rc) return rc;
   const std::vector<ist_image_desc> descs = fd.descs(lens);
@@ -499,25 +539,33 @@ int ist_ctx_last_timing(ist_ctx* ctx, double* ms, int n) {
 }
 
 // files -> decoded bitmaps in caller-owned device memory (the Image.src step, utils/canvas.js:27-121, ending in HBM)
-int ist_decode_files_device(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, void* const* dst,
-                            const size_t* dst_pitch, const int64_t* dst_rows, ist_image_desc* out_descs) {
+int ist_decode_files_device_scaled(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, const int32_t* denom, void* const* dst,
+                                   const size_t* dst_pitch, const int64_t* dst_rows, ist_image_desc* out_descs) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (n_images <= 0) return IST_NOTHING_TO_DO;
   if (!files || !lens || !dst || !dst_pitch || !dst_rows) return fail(IST_E_INVALID, "ist_decode_files_device: NULL argument");
   if (n_images > kMaxImages) return fail(IST_E_UNSUPPORTED, "more than 128 images in one call");
+  const int rc = check_denoms("ist_decode_files_device_scaled", denom, n_images);
+  if (rc) return rc;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  return decode_files_locked(ctx, files, lens, n_images, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
+  return decode_files_locked(ctx, files, lens, n_images, denom, [&](const std::vector<ist_image_desc>& descs, uint8_t** img, size_t* pitch) -> int {
     for (int i = 0; i < n_images; ++i) {
       const ist_image_desc& D = descs[static_cast<size_t>(i)];
+      const int bw = bitmap_w(D), bh = bitmap_h(D);      // (the scaled size of a reduced JPEG)
       // the file's own header is untrusted: the caller states what its buffer holds
-      if (!dst[i] || dst_pitch[i] < static_cast<size_t>(D.width) * 4 || (dst_pitch[i] & 3) || dst_rows[i] < D.height || (reinterpret_cast<uintptr_t>(dst[i]) & 3))
-        return fail(IST_E_INVALID, "ist_decode_files_device: the buffer of image " + std::to_string(i) + " is too small for " + std::to_string(D.width) + "x" + std::to_string(D.height));
+      if (!dst[i] || dst_pitch[i] < static_cast<size_t>(bw) * 4 || (dst_pitch[i] & 3) || dst_rows[i] < bh || (reinterpret_cast<uintptr_t>(dst[i]) & 3))
+        return fail(IST_E_INVALID, "ist_decode_files_device: the buffer of image " + std::to_string(i) + " is too small for " + std::to_string(bw) + "x" + std::to_string(bh));
       img[i] = static_cast<uint8_t*>(dst[i]);
       pitch[i] = dst_pitch[i];
       if (out_descs) out_descs[i] = D;
     }
     return IST_OK;
   });
+}
+
+int ist_decode_files_device(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, void* const* dst,
+                            const size_t* dst_pitch, const int64_t* dst_rows, ist_image_desc* out_descs) {
+  return ist_decode_files_device_scaled(ctx, files, lens, n_images, nullptr, dst, dst_pitch, dst_rows, out_descs);
 }
 
 }  // extern "C"

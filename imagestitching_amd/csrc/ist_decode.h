@@ -33,12 +33,15 @@ struct JpegDevLayout { size_t coef[3], q[3], plane[3], ent[3], start[3], cnt[3];
 // image the caller consumes, in any order -> finish().  The destructor joins whatever still runs.
 class FileDecoder {
  public:
-  FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph);
+  // denom (optional): the decode denominator of each file, 1, 2, 4 or 8 (checked by the caller: check_denoms); NULL = all 1.  It
+  // applies to JPEG files; every other type decodes at 1 / 1.
+  FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, const int32_t* denom = nullptr);
   ~FileDecoder();
   // 1. frame headers only (microseconds per file): sizes, sampling, EXIF orientation - what the planner and the arena need
   int headers();
   const Dec& dec(int i) const { return dec_[static_cast<size_t>(i)]; }
-  // what the planner needs of each file (orientation from the file, like getImageInfo -> index.js:734)
+  // what the planner needs of each file (orientation from the file, like getImageInfo -> index.js:734): width / height = the natural
+  // size; bmp_width / bmp_height = the scaled size of a JPEG decoded at 1 / 2, 1 / 4 or 1 / 8 (0, "as natural", for every other file)
   std::vector<ist_image_desc> descs(const int64_t* lens) const;
   // device bytes of the JPEG stages (coefficient planes, tables, sample planes), carved from *off of the caller's arena
   void layout(size_t* off);
@@ -53,13 +56,14 @@ class FileDecoder {
 
  private:
   hipStream_t stream_of(int i) const;
+  int denom_of(int i) const;
   void join_all();
   int first_error();
   int huffman_all(hipStream_t consumer);
   int chroma_all(hipStream_t consumer);
   void worker(int i);
 
-  ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_;
+  ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_; const int32_t* denom_;
   std::vector<Dec> dec_;
   bool running_ = false;                                       // the context's worker pool is on this call's files
   std::vector<char> on_gpu_, taken_, uploaded_, started_, chroma_done_;      // started_: the image's stream carries uploads of this call; chroma_done_: its chroma planes were made behind the Huffman batch
@@ -71,8 +75,9 @@ class FileDecoder {
 // files -> bitmaps in device memory: the decode of ist_decode_files_device and ist_bitmaps_decode.  Once every frame header is
 // read, place(descs, img, pitch) is told what each file holds (descs[i]: size, EXIF orientation, opaque, file_size) and fills
 // img[i] / pitch[i] with where bitmap i goes, or fails the call before anything is decoded.  Caller holds ctx->mu; returns with
-// ctx->stream idle.
-int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n,
+// ctx->stream idle.  denom: as FileDecoder's (NULL = all 1); img[i] / pitch[i] then hold bitmap_w x bitmap_h of descs[i].
+int check_denoms(const char* who, const int32_t* denom, int n);      // IST_E_INVALID, the message names the image: before anything is enqueued
+int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, const int32_t* denom,
                         const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place);
 
 }  // namespace ist

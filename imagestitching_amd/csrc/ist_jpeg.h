@@ -137,7 +137,23 @@ struct JpegDeviceJob {
   bool rgb = false;                    // components 0, 1, 2 are R, G, B: upsampled like chroma, not colour-converted
   uint8_t* out; size_t out_pitch;
   bool chroma_done = false;            // jpeg_launch_chroma_idct has already made d_plane[1], d_plane[2] on this stream
+  int denom = 1;                       // decode at 1 / denom of the natural size (1, 2, 4, 8): out is the scaled bitmap, d_plane[c] holds
+                                       // blocks_x * S_c bytes per row for ALL components (jpeg_launch_reconstruct_scaled)
 };
+// ---- reduced-size decode (ist_jpeg_scaled.hip; the contract is stated in include/imagestitch.h) ----
+// output size of a w x h image at 1 / denom: ceil(w * N / 8), N = 8 / denom
+inline void jpeg_scaled_size(int w, int h, int denom, int* sw, int* sh) {
+  const int64_t N = 8 / denom;
+  *sw = static_cast<int>((w * N + 7) / 8); *sh = static_cast<int>((h * N + 7) / 8);
+}
+// IDCT size S of a component sampled h x v (a lone component: 1 x 1) in a frame of hmax x vmax, N = 8 / denom
+inline int jpeg_scaled_idct_size(int N, int h, int v, int hmax, int vmax) {
+  int S = N;
+  while (S < 8 && (hmax * N) % (h * S * 2) == 0 && (vmax * N) % (v * S * 2) == 0) S *= 2;
+  return S;
+}
+// job.denom in {2, 4, 8}: reduced IDCTs of every component into d_plane[c], then planes -> RGBA8 (upsampling + colour conversion)
+int jpeg_launch_reconstruct_scaled(const JpegDeviceJob& job, void* stream);
 // chroma planes (one launch: components 1, 2 -> sample planes), then luma IDCT fused with upsampling + colour conversion
 int jpeg_launch_reconstruct(const JpegDeviceJob& job, void* stream);
 // the chroma planes of SEVERAL images in one launch (per 18 components): what the file pipeline runs once behind the Huffman

@@ -675,25 +675,71 @@ def image_info(data):
     return w.value, h.value, o.value
 
 
-def decode_image(data, device=0):
+_SCALES = (1, 2, 4, 8)
+
+
+def scaled_size(w, h, scale):
+    """(sw, sh) of a w x h JPEG decoded at 1 / scale, scale in {1, 2, 4, 8}: ceil(w / scale), ceil(h / scale) (ist_jpeg_scaled_size).
+    Pure CPU."""
+    sw, sh = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib.ist_jpeg_scaled_size(int(w), int(h), int(scale), C.byref(sw), C.byref(sh)))
+    return sw.value, sh.value
+
+
+def decode_scale_fit(w, h, min_w, min_h):
+    """The largest scale in {1, 2, 4, 8} at which a w x h file still decodes to at least min_w x min_h pixels, 1 if none does
+    (ist_decode_scale_fit).  Pure CPU."""
+    d = L.lib.ist_decode_scale_fit(int(w), int(h), int(min_w), int(min_h))
+    L.check(d if d < 0 else 0)
+    return d
+
+
+def _scales(scale, blobs, who):
+    """scale= of a decode call -> (one denominator per file, the C array or None for all 1).  JPEG files take the denominator, every
+    other type decodes at 1 / 1."""
+    n = len(blobs)
+    ds = [int(d) for d in _per_file(scale, n, who + ": scale")]
+    for i, d in enumerate(ds):
+        if d not in _SCALES:
+            raise L.StitchError(-1, "%s: the scale of image %d is %d, not 1, 2, 4 or 8" % (who, i, d))
+    return ds, (None if all(d == 1 for d in ds) else (C.c_int32 * max(1, n))(*ds))
+
+
+def _is_jpeg(buf):
+    return buf[:2] == b"\xff\xd8"
+
+
+def decode_image(data, device=0, scale=1):
     """PNG or JPEG file bytes -> HxWx4 uint8 RGBA.  JPEG: Huffman decoding on the host, IDCT / upsampling / colour
     conversion on the GPU.  The bitmap is returned as stored (EXIF orientation is applied by the stitch, like the
-    reference's drawWithOrientation)."""
+    reference's drawWithOrientation).  scale: 1, 2, 4 or 8 - a JPEG decodes at 1 / scale of its size (scaled_size), as
+    libjpeg-turbo's decode-to-scale does, byte for byte; other file types decode at 1 / 1."""
     buf = bytes(data)
+    (d,), _ = _scales(scale, [buf], "decode_image")
     w, h, _ = image_info(buf)
+    jpeg = _is_jpeg(buf)
+    if jpeg and d > 1:
+        w, h = scaled_size(w, h, d)
     out = np.empty((h, w, 4), np.uint8)
-    ctx = _ctx(device) if buf[:2] == b"\xff\xd8" else None          # only JPEG needs the GPU
-    L.check(L.lib.ist_image_decode_rgba8(ctx, buf, len(buf), out.ctypes.data, out.strides[0], out.shape[0]))
+    ctx = _ctx(device) if jpeg else None          # only JPEG needs the GPU
+    if d == 1:
+        L.check(L.lib.ist_image_decode_rgba8(ctx, buf, len(buf), out.ctypes.data, out.strides[0], out.shape[0]))
+    else:
+        L.check(L.lib.ist_image_decode_rgba8_scaled(ctx, buf, len(buf), d, out.ctypes.data, out.strides[0], out.shape[0]))
     return out
 
 
-def decode_files_device(blobs, device=0, out=None):
+def decode_files_device(blobs, device=0, out=None, scale=1):
     """File bytes -> bitmaps in HBM (ist_decode_files_device): returns ([HxWx4 uint8 CUDA tensors], [image dicts for
     plan/compile]).  Baseline JPEG: Huffman decoding + reconstruction on the GPU; only the file bytes cross PCIe.
-    out: optional list of preallocated tensors (one spare row behind each is the caller's business)."""
+    out: optional list of preallocated tensors (one spare row behind each is the caller's business).
+    scale: 1, 2, 4 or 8, one for all files or one per file: a JPEG decodes at 1 / scale (scaled_size); its dict then carries
+    'bmpWidth' / 'bmpHeight' = the tensor's size beside the natural 'width' / 'height', which is what plan and compile expect."""
     import torch
     n = len(blobs)
+    ds, cden = _scales(scale, blobs, "decode_files_device")
     sizes = [image_info(b) for b in blobs]
+    sizes = [scaled_size(w, h, d) + (o,) if d > 1 and _is_jpeg(b) else (w, h, o) for (w, h, o), d, b in zip(sizes, ds, blobs)]
     dev = torch.device("cuda", device)
     if out is None:
         out = [torch.empty((h + 1, w, 4), dtype=torch.uint8, device=dev)[:h] for (w, h, _) in sizes]
@@ -708,8 +754,14 @@ def decode_files_device(blobs, device=0, out=None):
     for i, t in enumerate(out):
         dst[i], pitch[i], rows[i] = t.data_ptr(), t.stride(0), t.shape[0]
     descs = (L.ImageDesc * n)()
-    L.check(L.lib.ist_decode_files_device(_ctx(device), files, lens, n, dst, pitch, rows, descs))
+    if cden is None:
+        L.check(L.lib.ist_decode_files_device(_ctx(device), files, lens, n, dst, pitch, rows, descs))
+    else:
+        L.check(L.lib.ist_decode_files_device_scaled(_ctx(device), files, lens, n, cden, dst, pitch, rows, descs))
     imgs = [{"width": d.width, "height": d.height, "orientation": d.orientation, "opaque": bool(d.opaque), "fileSize": d.file_size} for d in descs]
+    for im, d in zip(imgs, descs):
+        if d.bmp_width or d.bmp_height:
+            im["bmpWidth"], im["bmpHeight"] = int(d.bmp_width), int(d.bmp_height)
     return out, imgs
 
 
@@ -1087,26 +1139,61 @@ def _bitmap_descs(images):
     return arr
 
 
-def decode_bitmaps(files, device=0):
-    """Image files (bytes, or paths that are read here) -> [Bitmap], decoded straight into HBM by the decoder of stitch_files (baseline
-    JPEG: Huffman decoding + reconstruction on the GPU).  Each bitmap's desc is what stitch_files plans with: size, EXIF orientation,
-    opaque for JPEG, file_size = the file's length.  All or nothing: a file that does not decode raises StitchError('图片k解码异常: ...')
-    and no bitmap is kept."""
-    ctx = _ctx(device)
+def _read_files(files):
     blobs = []
     for f in files:
         if isinstance(f, (str, os.PathLike)):
             with open(f, "rb") as fh:
                 f = fh.read()
         blobs.append(bytes(f))
+    return blobs
+
+
+def decode_bitmaps(files, device=0, scale=1):
+    """Image files (bytes, or paths that are read here) -> [Bitmap], decoded straight into HBM by the decoder of stitch_files (baseline
+    JPEG: Huffman decoding + reconstruction on the GPU).  Each bitmap's desc is what stitch_files plans with: size, EXIF orientation,
+    opaque for JPEG, file_size = the file's length.  All or nothing: a file that does not decode raises StitchError('图片k解码异常: ...')
+    and no bitmap is kept.
+    scale: 1, 2, 4 or 8, one for all files or one per file: a JPEG is decoded at 1 / scale of its size (scaled_size; libjpeg-turbo's
+    decode-to-scale, byte for byte) and held at that size - width / height stay the natural size, shape is the stored one - so a
+    12 MP photo at scale 4 holds 3 MB instead of 48 MB and plans, stitches, previews and thumbnails like the full-size bitmap.  Other
+    file types decode at 1 / 1."""
+    ctx = _ctx(device)
+    blobs = _read_files(files)
     n = len(blobs)
     if n == 0:
         return []
+    _, cden = _scales(scale, blobs, "decode_bitmaps")
     cfiles = (C.c_char_p * n)(*blobs)
     lens = (C.c_int64 * n)(*[len(b) for b in blobs])
     out = (C.c_void_p * n)()
-    L.check(L.lib.ist_bitmaps_decode(ctx, cfiles, lens, n, out))
+    if cden is None:
+        L.check(L.lib.ist_bitmaps_decode(ctx, cfiles, lens, n, out))
+    else:
+        L.check(L.lib.ist_bitmaps_decode_scaled(ctx, cfiles, lens, n, cden, out))
     return [Bitmap(out[i], device) for i in range(n)]
+
+
+def thumbnails_from_files(files, cell, mode="fill", orient=True, device=0):
+    """Image files (bytes or paths) -> their thumbnails for a cell (width, height), as thumbnails() returns them, without ever holding
+    a full-size bitmap: every JPEG is decoded at the largest scale (decode_scale_fit) at which its stored pixels still cover its
+    thumbnail, so the grid of nine 12 MP photos (index.wxml:4-22) reads a sixty-fourth of their pixels.  The bitmaps are released
+    before the call returns."""
+    blobs = _read_files(files)
+    if not blobs:
+        return []
+    infos = [image_info(b) for b in blobs]
+    items = thumbnail_layout([(w, h, o or 1) for (w, h, o) in infos], cell, mode, orient)
+    scales = []
+    for (w, h, o), t in zip(infos, items):
+        tw, th = (t["height"], t["width"]) if orient and o >= 5 else (t["width"], t["height"])      # the thumbnail on the STORED axes
+        scales.append(decode_scale_fit(w, h, max(1, tw), max(1, th)))
+    bitmaps = decode_bitmaps(blobs, device, scale=scales)
+    try:
+        return thumbnails(bitmaps, cell, mode, orient)
+    finally:
+        for b in bitmaps:
+            b.close()
 
 
 def upload_bitmap(image, device=0):

@@ -489,6 +489,50 @@ enum { IST_PHASE_HOST_DECODE = 0, IST_PHASE_PLAN_ARENA = 1, IST_PHASE_ENTROPY_GP
 IST_API int ist_ctx_set_timing(ist_ctx* ctx, int on);
 IST_API int ist_ctx_last_timing(ist_ctx* ctx, double* ms, int n);
 
+/* ---- reduced-size JPEG decode: 1/2, 1/4, 1/8 (csrc/ist_jpeg_scaled.hip; the decoded bitmap that is smaller than the image, bmp.width
+ * against width, index.js:1522-1523) ----
+ * A JPEG file decodes at 1 / d of its natural size, d = 1, 2, 4 or 8, from the coefficients the full-size decode reads: the entropy
+ * stage is the same, the reconstruction is libjpeg-turbo's decode-to-scale (scale_num / scale_denom; Pillow's Image.draft), byte for
+ * byte.  The contract (restated in numpy in tests/jpeg_scaled_reference.py), with N = 8 / d:
+ *   - output size: sw = ceil(W N / 8), sh = ceil(H N / 8).
+ *   - IDCT size S of a component sampled (h, v) (a lone component counts as 1 x 1): start at S = N; while S < 8 and
+ *     (hmax N) mod (h S 2) == 0 and (vmax N) mod (v S 2) == 0, S doubles.  The component's true plane is cw = ceil(W h S / (hmax 8)) by
+ *     ch = ceil(H v S / (vmax 8)) samples and is upsampled by ux = hmax N / (h S), uy = vmax N / (v S).  For the layouts the decoder
+ *     takes: 4:2:0 chroma at 2 N without upsampling (at d = 2 luma is 4 x 4 and chroma the full 8 x 8), 4:2:2 keeps ux = 2, 4:4:0
+ *     keeps uy = 2; ux = uy = 2 never occurs for d > 1.
+ *   - upsampling: h2v1 and h1v2 are the triangle filters of the full-size decode with the same roundings ((3 near + far + 1) >> 2
+ *     towards the previous sample, + 2 towards the next, edges replicated); h2v1 replicates when the scaled plane is at most 2
+ *     samples wide; at d = 8 every upsampling is replication (libjpeg drops the filter when the smallest IDCT is 1 x 1).
+ *   - reduced IDCT of the dequantised coefficients c[v][u], 32-bit arithmetic, DESCALE(x, n) = (x + (1 << (n - 1))) >> n
+ *     (arithmetic shift), F(x) = round(8192 x):
+ *       4 x 4: pass 1 on columns 0, 1, 2, 3, 5, 6, 7 reading rows 0, 1, 2, 3, 5, 6, 7 (index 4 is unused), pass 2 on the four rows
+ *         over the same seven columns.  t0 = x0 << 14, t2 = x2 F(1.847759065) - x6 F(0.765366865), t10 = t0 + t2, t12 = t0 - t2,
+ *         o0 = -x7 F(0.211164243) + x5 F(1.451774981) - x3 F(2.172734803) + x1 F(1.061594337),
+ *         o2 = -x7 F(0.509795579) - x5 F(0.601344887) + x3 F(0.899976223) + x1 F(2.562915447);
+ *         outputs 0..3 = t10 + o2, t12 + o0, t12 - o0, t10 - o2, DESCALEd by 12 in pass 1 and by 19 in pass 2.
+ *       2 x 2: pass 1 on columns 0, 1, 3, 5, 7 reading rows 0, 1, 3, 5, 7, pass 2 on the two rows.  t10 = x0 << 15,
+ *         t0 = -x7 F(0.720959822) + x5 F(0.850430095) - x3 F(1.272758580) + x1 F(3.624509785);
+ *         outputs t10 + t0, t10 - t0, DESCALEd by 13 in pass 1 and by 20 in pass 2.
+ *       1 x 1: DESCALE(c[0][0], 3).       8 x 8: the full-size IDCT.
+ *     Every sample then gets + 128 and is clamped to 0..255.  Colour conversion, the RGB rule and alpha 255 are the full-size ones.
+ * The denominator applies to every JPEG the decoder takes (baseline on the GPU Huffman path, sequential and progressive files on the
+ * host entropy path); other file types decode at 1 / 1.  d = 1 runs the full-size launches and nothing else.  A denominator outside
+ * {1, 2, 4, 8} is IST_E_INVALID, the message names the file, before anything is enqueued.  Every other rule is the unscaled call's. */
+/* (sw, sh) of a w x h image at 1 / denom.  Pure CPU.  IST_E_INVALID: w or h < 1, a denominator outside {1, 2, 4, 8}, a NULL output */
+IST_API int ist_jpeg_scaled_size(int32_t w, int32_t h, int32_t denom, int32_t* sw, int32_t* sh);
+/* the largest d in {1, 2, 4, 8} with ceil(w / d) >= min_w and ceil(h / d) >= min_h, 1 if none qualifies: the denominator at which a
+ * w x h file still covers min_w x min_h stored pixels.  Pure CPU.  IST_E_INVALID (negative) for a non-positive argument. */
+IST_API int ist_decode_scale_fit(int32_t w, int32_t h, int32_t min_w, int32_t min_h);
+/* ist_image_decode_rgba8 at 1 / denom: out holds sw x sh pixels (capacity checks use the scaled size) */
+IST_API int ist_image_decode_rgba8_scaled(ist_ctx* ctx, const uint8_t* file, int64_t len, int32_t denom, uint8_t* out, size_t out_pitch,
+                                          int64_t out_rows);
+/* ist_decode_files_device with one denominator per file (denom == NULL: all 1, which IS ist_decode_files_device): dst[i] holds the
+ * scaled bitmap; out_descs[i].width / height = the natural size, bmp_width / bmp_height = the scaled size of a JPEG decoded at d > 1
+ * (0 = as natural for every other file, as ist_decode_files_device reports it). */
+IST_API int ist_decode_files_device_scaled(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, const int32_t* denom,
+                                           void* const* dst, const size_t* dst_pitch, const int64_t* dst_rows, ist_image_desc* out_descs);
+IST_API int64_t ist_debug_jpeg_scaled_launches(void);   /* reduced-IDCT launches made so far */
+
 /* ---- files in, file out: the whole onStitch (decode -> plan -> resample+blit -> PNG export; index.js:1441-1581) ---- */
 /* files[i] = the bytes of one image file of any type ist_image_info recognises.  Baseline JPEG: container parse + de-stuffing
  * on a host thread per image, Huffman decoding, reconstruction, stitch and PNG compression on the GPU; progressive JPEG /
@@ -562,6 +606,10 @@ IST_API ist_bitmap* ist_bitmap_upload(ist_ctx* ctx, const ist_image_desc* desc, 
  * plans it (size, EXIF orientation, opaque for JPEG, file_size = lens[i]).  All or nothing: when file k fails, nothing is returned
  * (out[] is left NULL) and the message is '图片k解码异常: ...'.  n <= 0: IST_NOTHING_TO_DO; more than 128: IST_E_UNSUPPORTED. */
 IST_API int ist_bitmaps_decode(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, ist_bitmap** out);
+/* the same with one decode denominator per file (1, 2, 4, 8; NULL: all 1 - "reduced-size JPEG decode" above): a JPEG decoded at 1 / d
+ * is an ordinary bitmap whose desc has bmp_width / bmp_height = the scaled size and width / height = the natural size, so plan,
+ * stitch, previews, thumbnails and exports take it as it is; it holds 4 sw sh bytes (+ the tail) instead of 4 w h. */
+IST_API int ist_bitmaps_decode_scaled(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, const int32_t* denom, ist_bitmap** out);
 IST_API int ist_bitmap_desc(const ist_bitmap* b, ist_image_desc* out);
 /* the pixels back into host memory (dst_rows rows of dst_pitch bytes must hold the bitmap) */
 IST_API int ist_bitmap_download(ist_bitmap* b, uint8_t* dst, size_t dst_pitch, int64_t dst_rows);

@@ -22,7 +22,8 @@
  *   encodeJpeg(data, width, height, quality, subsampling) -> Buffer;  stitch / stitchBitmaps(..., filter, {quality, subsampling})
  *       resolve {width,height,jpeg} (ist_stitch_jpeg / ist_stitch_bitmaps_jpeg: asPng given as an object is the JPEG export)
  *   deviceCount(), lastError(), abiVersion()
- *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[]) -> Promise<handle[]>;
+ *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[], scales?: number[]) -> Promise<handle[]>;
+ *     decodeScaleFit(width, height, minWidth, minHeight) -> 1 | 2 | 4 | 8;
  *   bitmapDesc(h) -> {width,height,orientation,bmpWidth,bmpHeight,opaque,fileSize};  bitmapDownload(h) -> Buffer;  bitmapRelease(h);
  *   stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng) -> Promise (as stitch);  stitchBitmapsSync(...same...);
  *   debugBitmapBytes().  A handle is an object that wraps ONE reference of a bitmap: bitmapRelease drops it (again: nothing), its
@@ -858,12 +859,13 @@ static napi_value js_upload_bitmap(napi_env env, napi_callback_info info) {
   return h;
 }
 
-/* decodeBitmaps(files: Buffer[]) -> Promise<handle[]> (ist_bitmaps_decode: all or nothing) */
-typedef struct { job h; files_t files; ist_bitmap** out; } decode_job;
+/* decodeBitmaps(files: Buffer[], scales?: number[]) -> Promise<handle[]> (ist_bitmaps_decode_scaled: all or nothing; scales = one
+ * decode denominator per file, 1 / 2 / 4 / 8, checked by the library; absent: all 1, which is ist_bitmaps_decode) */
+typedef struct { job h; files_t files; int32_t* denom; ist_bitmap** out; } decode_job;
 
 static int decode_run(ist_ctx* ctx, job* h) {
   decode_job* j = (decode_job*)h;
-  return j->files.n ? ist_bitmaps_decode(ctx, j->files.ptr, j->files.len, j->files.n, j->out) : IST_OK;
+  return j->files.n ? ist_bitmaps_decode_scaled(ctx, j->files.ptr, j->files.len, j->files.n, j->denom, j->out) : IST_OK;
 }
 static napi_value decode_result(napi_env env, job* h) {
   decode_job* j = (decode_job*)h;
@@ -880,17 +882,36 @@ static void decode_free(napi_env env, job* h) {
   decode_job* j = (decode_job*)h;
   for (int i = 0; i < j->files.n; i++) if (j->out[i]) ist_bitmap_release(j->out[i]);
   files_free(env, &j->files);
-  free(j->out); free(j);
+  free(j->denom); free(j->out); free(j);
 }
 static const job_kind DECODE = {decode_run, decode_result, decode_free};
 
 static napi_value js_decode_bitmaps(napi_env env, napi_callback_info info) {
-  napi_value argv[1]; files_t files;
-  if (!args_of(env, info, 1, 1, argv, "decodeBitmaps(files: Buffer[])") || !files_parse(env, argv[0], "decodeBitmaps(files: Buffer[])", &files)) return NULL;
+  static const char usage[] = "decodeBitmaps(files: Buffer[], scales?: number[])";
+  napi_value argv[2]; files_t files; int32_t* denom = NULL; uint32_t ns = 0;
+  if (!args_of(env, info, 1, 2, argv, usage) || !files_parse(env, argv[0], usage, &files)) return NULL;
+  if (!is_nullish(env, argv[1])) {
+    if (!array_len(env, argv[1], &ns) || ns != (uint32_t)files.n) { files_free(env, &files); return throw_type(env, "decodeBitmaps: scales must hold one number per file"); }
+    denom = (int32_t*)calloc(ns ? ns : 1, sizeof *denom);
+    for (uint32_t i = 0; i < ns; i++) {
+      napi_value v;
+      denom[i] = napi_get_element(env, argv[1], i, &v) == napi_ok && type_of(env, v) == napi_number ? int_of(env, v, 0) : 0;      /* (0: the library names the file) */
+    }
+  }
   decode_job* j = (decode_job*)calloc(1, sizeof *j);
-  j->h.kind = &DECODE; j->files = files;
+  j->h.kind = &DECODE; j->files = files; j->denom = denom;
   j->out = (ist_bitmap**)calloc(files.n ? files.n : 1, sizeof(ist_bitmap*));
   return job_queue(env, &j->h, "imagestitch.decodeBitmaps");
+}
+
+/* decodeScaleFit(width, height, minWidth, minHeight) -> 1 | 2 | 4 | 8 (ist_decode_scale_fit: pure CPU) */
+static napi_value js_decode_scale_fit(napi_env env, napi_callback_info info) {
+  napi_value argv[4], out;
+  if (!args_of(env, info, 4, 4, argv, "decodeScaleFit(width, height, minWidth, minHeight)")) return NULL;
+  const int d = ist_decode_scale_fit(int_of(env, argv[0], 0), int_of(env, argv[1], 0), int_of(env, argv[2], 0), int_of(env, argv[3], 0));
+  if (d < 0) return throw_ist(env, d);
+  napi_create_int32(env, d, &out);
+  return out;
 }
 
 static napi_value js_bitmap_desc(napi_env env, napi_callback_info info) {
@@ -1040,6 +1061,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_default, NULL},
       {"uploadBitmap", NULL, js_upload_bitmap, NULL, NULL, NULL, napi_default, NULL},
       {"decodeBitmaps", NULL, js_decode_bitmaps, NULL, NULL, NULL, napi_default, NULL},
+      {"decodeScaleFit", NULL, js_decode_scale_fit, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDownload", NULL, js_bitmap_download, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapPreview", NULL, js_bitmap_preview, NULL, NULL, NULL, napi_default, NULL},

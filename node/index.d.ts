@@ -73,7 +73,10 @@ export class Bitmap {
   preview(width: number, height: number): Preview;   // the stored pixels shrunk to fit the box, reduced in GPU memory (no EXIF turn, as download())
   release(): void;          // idempotent; any other use afterwards throws
 }
-export function decodeBitmaps(files: (Uint8Array | string)[]): Promise<Bitmap[]>;
+/** scale: 1, 2, 4 or 8 (one for all files or one per file): a JPEG is decoded at 1 / scale and kept at that size; other types at 1 / 1 */
+export function decodeBitmaps(files: (Uint8Array | string)[], opts?: { scale?: 1 | 2 | 4 | 8 | (1 | 2 | 4 | 8)[] }): Promise<Bitmap[]>;
+/** the largest scale at which a width x height file still decodes to at least minWidth x minHeight pixels (1 if none does) */
+export function decodeScaleFit(width: number, height: number, minWidth: number, minHeight: number): 1 | 2 | 4 | 8;
 export function uploadBitmap(image: StitchImage): Bitmap;
 // the grid of chosen images (index.wxml:4-22): every bitmap as a thumbnail for the cell - 'fill' (default) crops to the cell's aspect ratio
 // (aspectFill), 'fit' fits the whole image into it (aspectFit) - turned by its EXIF orientation unless orient is false, all of them

@@ -11,7 +11,7 @@
  *   encodeJpeg(data, width, height, {quality, subsampling, optimize}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   stitchJpegBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, jpeg, plan} | null)[]>  (one GPU, many JPEG files)
- *   decodeBitmaps(files) -> Promise<Bitmap[]>,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
+ *   decodeBitmaps(files, {scale?}) -> Promise<Bitmap[]>,  decodeScaleFit(w, h, minW, minH) -> 1 | 2 | 4 | 8,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
  *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
  *       that box (the redraw into the preview node, index.js:1597-1603), reduced in GPU memory beside the export;
@@ -144,15 +144,27 @@ function bitmapHandles(images, opts) {
 }
 /** Image files (Buffers, or paths read here as stitchFiles reads them) -> Bitmaps, decoded straight into GPU memory by the decoder
  *  of stitchFiles; each one's width / height / orientation / opaque / fileSize is what stitchFiles plans with.  All or nothing: a
- *  file that does not decode rejects with '图片k解码异常: ...' and no bitmap is kept. */
-async function decodeBitmaps(files) {
-  if (!Array.isArray(files)) throw new TypeError('decodeBitmaps(files: (Uint8Array | string)[])');
+ *  file that does not decode rejects with '图片k解码异常: ...' and no bitmap is kept.
+ *  opts.scale: 1, 2, 4 or 8, one for all files or one per file - a JPEG is decoded at 1 / scale of its size (libjpeg-turbo's
+ *  decode-to-scale, byte for byte) and kept at that size: width / height stay the natural size, bmpWidth / bmpHeight are the stored
+ *  one, and stitch, previews and thumbnails take the bitmap as it is.  Other file types decode at 1 / 1. */
+async function decodeBitmaps(files, opts) {
+  if (!Array.isArray(files)) throw new TypeError('decodeBitmaps(files: (Uint8Array | string)[], {scale?})');
+  const scale = opts === undefined || opts === null ? undefined : opts.scale;
+  let scales;
+  if (scale !== undefined && scale !== null) {
+    scales = Array.isArray(scale) ? scale : files.map(() => scale);
+    if (scales.length !== files.length || !scales.every((d) => typeof d === 'number')) throw new TypeError('decodeBitmaps: scale must be a number or one number per file');
+  }
   const fs = require('fs');
   const bufs = files.map((f) => (typeof f === 'string' ? fs.readFileSync(f) : f));
   if (!bufs.length) return [];
-  const handles = await native.decodeBitmaps(bufs);
+  const handles = await native.decodeBitmaps(bufs, scales);
   return handles.map((h) => new Bitmap(MADE_HERE, h));
 }
+/** The largest scale in {1, 2, 4, 8} at which a width x height file still decodes to at least minWidth x minHeight pixels (1 if none
+ *  does): what to pass as decodeBitmaps' scale for a file that is only ever shown that small.  Pure CPU. */
+function decodeScaleFit(width, height, minWidth, minHeight) { return native.decodeScaleFit(width, height, minWidth, minHeight); }
 /** One host image ({width, height, data, orientation?, fileSize?, opaque?}, as stitch takes it) -> a Bitmap with that desc. */
 function uploadBitmap(image) { return new Bitmap(MADE_HERE, native.uploadBitmap([image])); }
 /** The grid of chosen images (index.wxml:4-22): every Bitmap as a thumbnail for a width x height cell, all of them cropped or fitted,
@@ -379,4 +391,4 @@ function plan(images, direction, opts) {
 }
 
 module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
-                   decodeBitmaps, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+                   decodeBitmaps, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
