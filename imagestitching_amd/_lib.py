@@ -105,6 +105,14 @@ class ThumbItem(C.Structure):
                 ("src_h", C.c_int32), ("turn", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
+class OverlapOpts(C.Structure):
+    _fields_ = [("tolerance", C.c_int32), ("min_rows", C.c_int32), ("min_informative", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Overlap(C.Structure):
+    _fields_ = [("header", C.c_int32), ("footer", C.c_int32), ("overlap", C.c_int32), ("reserved", C.c_int32), ("cost", C.c_int64)]
+
+
 class JpegCoefInfo(C.Structure):
     _fields_ = [("ok", C.c_int32), ("launches", C.c_int32), ("ncomp", C.c_int32), ("reserved", C.c_int32),
                 ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3)]
@@ -272,6 +280,15 @@ SYMBOLS = [
     ("ist_debug_jpeg_batch_launches", C.c_int64, []),
     ("ist_jpeg_optimal_table", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int)]),
     ("ist_debug_jpeg_histogram_launches", C.c_int64, []),
+    ("ist_overlap_edge", C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.POINTER(C.c_int32)]),
+    ("ist_overlap_select", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.POINTER(OverlapOpts), C.POINTER(C.c_int32)]),
+    ("ist_overlap_rows", C.c_int, [C.POINTER(Overlap), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("ist_bitmaps_overlap", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(OverlapOpts), C.POINTER(Overlap)]),
+    ("ist_overlap_device", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(ImageDesc), C.c_int, C.POINTER(OverlapOpts),
+                                     C.POINTER(Overlap)]),
+    ("ist_debug_overlap_launches", C.c_int64, []),
+    ("ist_debug_overlap_signatures", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
+    ("ist_bitmap_rows", C.c_void_p, [C.c_void_p, C.c_int32, C.c_int32]),
 ]
 
 if not os.path.exists(LIB_PATH):

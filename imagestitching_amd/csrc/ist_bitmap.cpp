@@ -18,7 +18,9 @@ struct ist_bitmap {
   int device = 0;
   DevBuf block;                          // row 0 first; rows are 4 * bitmap_w(desc) bytes apart, kSourceTail readable bytes behind the last
   ist_image_desc desc{};
-  uint8_t* px() const { return static_cast<uint8_t*>(block.p); }
+  ist_bitmap* parent = nullptr;          // a row view (ist_bitmap_rows): no block of its own, one reference on the bitmap that has it
+  uint8_t* row0 = nullptr;               // ... and its first row inside that block
+  uint8_t* px() const { return parent ? row0 : static_cast<uint8_t*>(block.p); }
 };
 
 namespace {
@@ -195,7 +197,28 @@ void ist_bitmap_retain(ist_bitmap* b) {
 void ist_bitmap_release(ist_bitmap* b) {
   if (!b || b->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
   g_bitmap_bytes.fetch_sub(static_cast<int64_t>(b->block.bytes), std::memory_order_relaxed);
+  ist_bitmap* parent = b->parent;
   delete b;
+  ist_bitmap_release(parent);            // (a view's parent is never a view: one step)
+}
+
+ist_bitmap* ist_bitmap_rows(ist_bitmap* b, int32_t y0, int32_t rows) {
+  if (!b) { fail(IST_E_INVALID, "ist_bitmap_rows: NULL bitmap"); return nullptr; }
+  const ist_image_desc& d = b->desc;
+  if (d.orientation > 1) { fail(IST_E_UNSUPPORTED, "ist_bitmap_rows: the bitmap has EXIF orientation " + std::to_string(d.orientation) + " (rows of the stored pixels are not rows of the image)"); return nullptr; }
+  if (bitmap_w(d) != d.width || bitmap_h(d) != d.height) { fail(IST_E_UNSUPPORTED, "ist_bitmap_rows: the bitmap was decoded at a reduced scale"); return nullptr; }
+  if (y0 < 0 || rows < 1 || static_cast<int64_t>(y0) + rows > bitmap_h(d)) {
+    fail(IST_E_INVALID, "ist_bitmap_rows: rows [" + std::to_string(y0) + ", " + std::to_string(static_cast<int64_t>(y0) + rows) + ") are not inside the bitmap's " + std::to_string(bitmap_h(d)));
+    return nullptr;
+  }
+  ist_bitmap* v = new ist_bitmap;
+  v->device = b->device;
+  v->desc = d;
+  v->desc.height = rows; v->desc.bmp_height = d.bmp_height > 0 ? rows : 0; v->desc.file_size = 0;
+  v->parent = b->parent ? b->parent : b;     // a view of a view holds the bitmap that owns the block
+  v->row0 = b->px() + static_cast<size_t>(y0) * row_of(d);
+  ist_bitmap_retain(v->parent);
+  return v;
 }
 
 int ist_stitch_bitmaps_rgba8(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int direction, int mode, double gap, const ist_limits* limits,
@@ -237,6 +260,27 @@ int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int
   if (n <= 0) return IST_NOTHING_TO_DO;
   const int jpeg[2] = {quality, subsampling};
   return stitch_bitmaps(ctx, bitmaps, n, direction, mode, gap, limits, filter, false, out_plan, out_jpeg, out_len, nullptr, jpeg);
+}
+
+int ist_bitmaps_overlap(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, const ist_overlap_opts* opts, ist_overlap* out) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (n < 2) return fail(IST_E_INVALID, "ist_bitmaps_overlap: an overlap needs at least two bitmaps");
+  if (!bitmaps || !out) return fail(IST_E_INVALID, "ist_bitmaps_overlap: NULL argument");
+  if (opts && (opts->tolerance < 0 || opts->min_rows < 0 || opts->min_informative < 0)) return fail(IST_E_INVALID, "ist_bitmaps_overlap: negative option");
+  Held held;
+  int rc = take_bitmaps(ctx, bitmaps, n, &held);
+  if (rc) return rc;
+  std::vector<ist_image_desc> descs(static_cast<size_t>(n));
+  std::vector<const void*> src(static_cast<size_t>(n));
+  std::vector<size_t> pitch(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    rc = overlap_check_desc(bitmaps[i]->desc, i);
+    if (rc) return rc;
+    descs[static_cast<size_t>(i)] = bitmaps[i]->desc;
+    src[static_cast<size_t>(i)] = bitmaps[i]->px();
+    pitch[static_cast<size_t>(i)] = row_of(bitmaps[i]->desc);
+  }
+  return overlap_run(ctx, src.data(), pitch.data(), descs.data(), n, opts, out);
 }
 
 int ist_bitmap_preview(ist_ctx* ctx, ist_bitmap* b, int32_t pw, int32_t ph, uint8_t* dst, size_t dst_pitch) {

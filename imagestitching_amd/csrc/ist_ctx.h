@@ -81,6 +81,12 @@ struct ist_ctx {
   // the reduce behind the last render
   ist::DevBuf prev_out;
   ist::Event prev_ready;
+  // overlap search (ist_overlap_host.cpp): tables, signatures, edge sums, costs and flags of one call, and the pinned block its tables go up
+  // from and its results come down to; grow-only.  ovl_rows signature rows of the last call start ovl_sig_at bytes into scratch_ovl.
+  ist::DevBuf scratch_ovl;
+  ist::PinnedBuf ovl_host;
+  int64_t ovl_rows = 0;
+  size_t ovl_sig_at = 0;
   // The streams come LAST: members go in reverse order of declaration, so every stream is waited for and destroyed (Stream's
   // destructor) before the first block above is freed.  A stream added here is picked up by streams() below, which is all that
   // ist_ctx_sync and ist_ctx_destroy know about them.
@@ -188,6 +194,11 @@ int preview_enqueue(ist_ctx* ctx, const void* src, size_t src_pitch, int64_t w, 
                     int32_t pw, int32_t ph, hipStream_t stream);
 // what a call that has retained a bitmap reads of it (ist_bitmap.cpp): its device, row 0, the row pitch and the desc
 void bitmap_view(const ist_bitmap* b, int* device, const uint8_t** row0, size_t* pitch, ist_image_desc* desc);
+// ---- overlap search (ist_overlap_host.cpp) ----
+// the pairs of n >= 2 images in device memory on the context's device -> out[n - 1]; takes ctx->mu; the arguments have been checked
+int overlap_run(ist_ctx* ctx, const void* const* src, const size_t* pitch, const ist_image_desc* descs, int n, const ist_overlap_opts* opts,
+                ist_overlap* out);
+int overlap_check_desc(const ist_image_desc& d, int i);     // IST_E_UNSUPPORTED "image i: ..." for EXIF orientation > 1 or a reduced-scale decode
 // The preview of a canvas that an export is reading.  prepare() before the encoder; queue(reader) once every render of the canvas has
 // been ordered in front of `reader`: the reduce and its small copy to pinned memory run on ctx->prev_stream behind that point;
 // finish() after the encoder waits for that stream alone and hands the pixels over.  Whatever happens, nothing is in flight and

@@ -69,6 +69,8 @@ DEFAULT_OPTS = {
     "devices": None,        # list of GPU indices (devices[0] = root): shard the stitch over them from this one process (ist_stitch_rgba8_multi)
     "preview": None,        # (box_w, box_h): stitch_png / stitch_files also return the canvas shrunk to fit that box (the redraw into the preview
                             # node, index.js:1597-1603), as result['preview'], HxWx4 uint8.  Refused where no canvas stays in HBM behind an export.
+    "overlap": None,        # 'auto', or a dict of tolerance / min_rows / min_informative: a vertical strip of Bitmaps (scrolled screenshots) is stitched
+                            # without the bars and the overlaps its neighbours share (find_overlaps, crop_overlaps); the result also has 'overlaps'
     "split": "auto",        # with devices: "image" (image i -> devices[i mod n], BASELINE configs[3]), "band" (equal output rows per device, cut draw
                             # by draw), "rows" (device s owns a band of canvas rows across ALL draws: full-width bands for horizontal strips and
                             # centred rects too, index.js:1540-1553), "auto" = "image" when its parts are full-width (vertical min / max), else "rows"
@@ -132,14 +134,29 @@ def _limits(opts):
     return lim
 
 
-def _merge(opts):
+def _merge(opts, overlap=False):
     o = dict(DEFAULT_OPTS)
     if opts:
         unknown = set(opts) - set(o)
         if unknown:
             raise TypeError("unknown stitch option(s): %s" % sorted(unknown))
         o.update(opts)
+    if o["overlap"] is not None and not overlap:
+        raise TypeError(_OVERLAP_NEEDS)
     return o
+
+
+_OVERLAP_NEEDS = ("the 'overlap' option applies to stitch / stitch_png / stitch_jpeg of a vertical strip of Bitmaps "
+                  "(upload_bitmap / decode_bitmaps): the overlaps are searched where the pixels are resident")
+
+
+def _overlap_opts(value):
+    """the keyword arguments of find_overlaps for an 'overlap' option value ('auto' or a dict of them), checked before any library call"""
+    if value == "auto":
+        return {}
+    if not isinstance(value, dict) or set(value) - {"tolerance", "min_rows", "min_informative"}:
+        raise TypeError("overlap must be 'auto' or a dict of tolerance / min_rows / min_informative, not %r" % (value,))
+    return dict(value)
 
 
 def _no_preview(o, who, why):
@@ -467,6 +484,20 @@ def _stitch(images, direction, o, device, kind, jpeg=()):
     n = len(images)
     if n == 0:
         return None
+    if o["overlap"] is not None:
+        kw = _overlap_opts(o["overlap"])
+        if direction != "vertical" or not all(isinstance(im, Bitmap) for im in images) or o.get("devices") is not None:
+            raise TypeError(_OVERLAP_NEEDS)
+        records = find_overlaps(images, **kw) if n > 1 else []
+        views = _crop_views(images, records)
+        try:
+            res = _stitch(views, direction, dict(o, overlap=None), device, kind, jpeg)
+        finally:
+            for v in views:
+                v.close()
+        if res is not None:
+            res["overlaps"] = records
+        return res
     if _is_bitmap_request(images, o):
         name, srcs = "ist_stitch_bitmaps_" + kind, ((C.c_void_p * n)(*[None if b is None else b.handle() for b in images]),)
     else:
@@ -503,12 +534,12 @@ def stitch(images, direction, opts=None, device=0):
     or simply an HxWx4 uint8 array; or a list of Bitmaps (decode_bitmaps / upload_bitmap: nothing is uploaded).  A view with padded
     rows is read where it is (_host_rows).  Returns None when images is empty (the reference returns early).
     """
-    o = _merge(opts)
+    o = _merge(opts, overlap=True)
     _no_preview(o, "stitch", "the caller gets the pixels; stitch_png / stitch_files keep the canvas in HBM and can add its preview")
     return _stitch(images, direction, o, device, "rgba8")
 
 
-_BATCH_REFUSED = ("devices", "split", "pngLevel", "pngColor", "pngFilter", "pngMatch", "preview")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
+_BATCH_REFUSED = ("devices", "split", "pngLevel", "pngColor", "pngFilter", "pngMatch", "preview", "overlap")      # a batch runs on one GPU; stitch_png_batch picks ONE PNG form for all its files; batch previews are not built
 
 
 def _batch_requests(reqs, why):
@@ -845,7 +876,7 @@ def stitch_png(images, direction, opts=None, device=0):
     """stitch(images, direction, opts) with the reference's export: returns {'width','height','png': bytes}.  The
     canvas stays on the device; only the PNG crosses PCIe.  images are marshalled as stitch() marshals them (padded views are read
     where they are); they may be a list of Bitmaps."""
-    o = _merge(opts)
+    o = _merge(opts, overlap=True)
     _png_color(o["pngColor"])
     _png_filter(o["pngFilter"])
     _png_match(o["pngMatch"])
@@ -925,7 +956,7 @@ def stitch_jpeg(images, direction, opts=None, device=0):
     or a list of Bitmaps."""
     opts = dict(opts or {})
     jpeg = _jpeg_args(opts.pop("quality", 90), opts.pop("subsampling", "420"), opts.pop("optimize", False))
-    o = _merge(opts)
+    o = _merge(opts, overlap=True)
     _no_preview(o, "stitch_jpeg", "previews are built beside the PNG export")
     if o.get("devices") is not None:
         raise TypeError("stitch_jpeg: devices= does not apply (the JPEG export runs on one GPU)")
@@ -1104,6 +1135,15 @@ class Bitmap:
         L.check(L.lib.ist_bitmap_preview(_ctx(self.device), C.c_void_p(self.handle()), pw, ph, out.ctypes.data, out.strides[0]))
         return out
 
+    def rows(self, y0, n):
+        """rows [y0, y0 + n) of the stored pixels as a Bitmap of their own (ist_bitmap_rows): a view that shares this bitmap's block and
+        keeps it alive, copies nothing, and goes wherever a Bitmap goes.  Refused for EXIF orientation > 1 and reduced-scale decodes."""
+        h = L.lib.ist_bitmap_rows(C.c_void_p(self.handle()), int(y0), int(n))
+        if not h:
+            msg = L.last_error()
+            raise L.StitchError(-7 if "orientation" in msg or "reduced scale" in msg else -1, msg)
+        return Bitmap(h, self.device)
+
     def close(self):
         if self._h:
             L.lib.ist_bitmap_release(C.c_void_p(self._h))
@@ -1137,6 +1177,88 @@ def _bitmap_descs(images):
         if b is not None:
             arr[i] = b._desc
     return arr
+
+
+def _overlap_call_opts(tolerance, min_rows, min_informative):
+    return L.OverlapOpts(int(tolerance), int(min_rows), int(min_informative), 0)
+
+
+def _overlap_records(out, n):
+    return [{"header": int(out[i].header), "footer": int(out[i].footer), "overlap": int(out[i].overlap), "cost": int(out[i].cost)} for i in range(n)]
+
+
+def find_overlaps(bitmaps, tolerance=8, min_rows=16, min_informative=8):
+    """Per neighbouring pair of a vertical strip of Bitmaps (scrolled screenshots, top to bottom): {'header', 'footer', 'overlap', 'cost'} -
+    the rows of a bar both shots repeat at the top and at the bottom, the rows of the upper shot's body that the lower one shows again,
+    and the summed row difference at that overlap (ist_bitmaps_overlap; the rule is in include/imagestitch.h).  Found on the GPU from
+    the resident pixels: three launches per call.  The defaults are the contract's, not measured optima: tolerance 8 is two 8-bit
+    levels per pixel.  Periodic content is ambiguous by nature; content that changes inside the overlap may give overlap 0."""
+    bitmaps = list(bitmaps)
+    if not all(isinstance(b, Bitmap) for b in bitmaps):
+        raise TypeError("find_overlaps: expected Bitmaps (upload_bitmap / decode_bitmaps)")
+    n = len(bitmaps)
+    out = (L.Overlap * max(1, n - 1))()
+    opts = _overlap_call_opts(tolerance, min_rows, min_informative)
+    handles = (C.c_void_p * max(1, n))(*[b.handle() for b in bitmaps])
+    L.check(L.lib.ist_bitmaps_overlap(_ctx(bitmaps[0].device if n else 0), handles, n, C.byref(opts), out))
+    return _overlap_records(out, n - 1)
+
+
+def find_overlaps_device(tensors, tolerance=8, min_rows=16, min_informative=8):
+    """find_overlaps for HxWx4 uint8 CUDA tensors (any row pitch, dense pixels) on one device (ist_overlap_device).  The current
+    stream is synchronised first: the call reads the tensors on the library's stream and returns the records."""
+    import torch
+    tensors = list(tensors)
+    n = len(tensors)
+    if n:
+        _check_canvases(tensors, "find_overlaps_device: ")
+    descs = (L.ImageDesc * max(1, n))()
+    ptrs, pitches = (C.c_void_p * max(1, n))(), (C.c_size_t * max(1, n))()
+    for i, t in enumerate(tensors):
+        descs[i].width, descs[i].height, descs[i].orientation = int(t.shape[1]), int(t.shape[0]), 1
+        ptrs[i], pitches[i] = t.data_ptr(), t.stride(0)
+    out = (L.Overlap * max(1, n - 1))()
+    opts = _overlap_call_opts(tolerance, min_rows, min_informative)
+    dev = (tensors[0].device.index or 0) if n else 0
+    if n:
+        torch.cuda.current_stream(dev).synchronize()
+    L.check(L.lib.ist_overlap_device(_ctx(dev), ptrs, pitches, descs, n, C.byref(opts), out))
+    return _overlap_records(out, n - 1)
+
+
+def overlap_rows(pairs, heights):
+    """The crop rule (ist_overlap_rows; pure CPU): [(top, bot)] per image - image i keeps rows [top, bot) - for the records of
+    find_overlaps and the images' heights.  A pair with overlap 0 crops nothing; an image that would keep no row voids its pair."""
+    n = len(heights)
+    if len(pairs) != max(0, n - 1):
+        raise ValueError("overlap_rows: %d images need %d pairs, not %d" % (n, max(0, n - 1), len(pairs)))
+    cp = (L.Overlap * max(1, n - 1))()
+    for i, p in enumerate(pairs):
+        cp[i].header, cp[i].footer, cp[i].overlap, cp[i].cost = int(p["header"]), int(p["footer"]), int(p["overlap"]), int(p.get("cost", 0))
+    ch = (C.c_int32 * max(1, n))(*[int(h) for h in heights])
+    top, bot = (C.c_int32 * max(1, n))(), (C.c_int32 * max(1, n))()
+    L.check(L.lib.ist_overlap_rows(cp, ch, n, top, bot))
+    return [(int(top[i]), int(bot[i])) for i in range(n)]
+
+
+def _crop_views(bitmaps, records):
+    rows = overlap_rows(records, [b.shape[0] for b in bitmaps])
+    views = []
+    try:
+        for b, (t, e) in zip(bitmaps, rows):
+            views.append(b.rows(t, e - t))
+    except Exception:
+        for v in views:
+            v.close()
+        raise
+    return views
+
+
+def crop_overlaps(bitmaps, **opts):
+    """The strip without what its neighbours share: one row view per Bitmap (Bitmap.rows over overlap_rows of find_overlaps(bitmaps,
+    **opts)); nothing is copied, and the views stitch, preview and export like any Bitmap."""
+    bitmaps = list(bitmaps)
+    return _crop_views(bitmaps, find_overlaps(bitmaps, **opts) if len(bitmaps) > 1 else [])
 
 
 def _read_files(files):

@@ -874,6 +874,66 @@ IST_API int ist_stitch_jpeg_batch(ist_ctx* ctx, const ist_stitch_request* reqs, 
 /* rounds (one transform launch each) made by batch encodes in this process so far */
 IST_API int64_t ist_debug_jpeg_batch_launches(void);
 
+/* ---- overlap removal for scrolled screenshots --------------------------------------------------------------------------------
+ * A vertical strip of screenshots repeats a bar at the top and at the bottom of every shot, and the content of each shot overlaps
+ * the shot above it by an unknown number of rows.  Per neighbouring pair (A above, B below) the library finds the shared header H,
+ * the shared footer F and the overlap K, and ist_overlap_rows says which rows of every image to keep.  THE CONTRACT (restated in
+ * numpy by tests/overlap_reference.py; the GPU agrees with it exactly).  Bitmaps are RGBA8, alpha is not read, all arithmetic is
+ * integer, sums are 64-bit, and no result depends on the order of a sum.
+ *   Signature.  For an image of width w, row y and cell c in [0, 32):  S(y, c) = sum of R + 2 G + B over the pixels x with
+ *     e(c) <= x < e(c + 1), e(c) = floor(c w / 32).  A cell may be empty (w < 32).  S fits in uint32.
+ *     D(p, q) = sum over c of |S(p, c) - S(q, c)| for two rows;  T = tolerance * w.
+ *     (Cell sums, not hashes: independent per-pixel noise grows like the square root of a cell's pixels while T grows like w, and a
+ *     scroll indicator touches one cell.)
+ *   Pair.  Widths differ: {0, 0, 0, 0}.  Otherwise hm = min(hA, hB), L = floor(hm / 2).
+ *     Header H: m(y) = [D(A row y, B row y) <= T] for y < L; H = the greatest t in [1, L] with m(t - 1) true and
+ *       #{y < t : not m(y)} <= floor(t / 4), else 0.  (The quarter lets a changed clock inside the bar pass.)
+ *     Footer F: the same rule on rows counted from the bottom: row hA - 1 - y of A against row hB - 1 - y of B.
+ *     Bodies: A rows [H, hA - F), B rows [H, hB - F), bodyA and bodyB rows; kmax = min(bodyA, bodyB - 1): the lower image always keeps
+ *       a row of its own.
+ *     Informative rows: row r of B's body (0 <= r < bodyB - 1) is informative iff D(B row H + r, B row H + r + 1) > T;
+ *       inf(k) = #{informative r : r < min(k, bodyB - 1)}.
+ *     cost(k) = sum over r < k of D(A row hA - F - k + r, B row H + r).
+ *     Candidates: k in [min_rows, kmax] with cost(k) <= T k and inf(k) >= min_informative.
+ *     Choice: k1 beats k2 iff cost(k1) k2 < cost(k2) k1 (the least mean row cost, cross-multiplied); an exact tie goes to the SMALLER
+ *       k (when in doubt, keep pixels).  No candidate: K = 0.  H and F are reported even then.
+ *   The defaults (tolerance 8 = two 8-bit levels per pixel in the units of S, min_rows 16, min_informative 8) are contract defaults,
+ *   not measured optima.  Not handled: periodic content (a list of identical items is ambiguous by nature); content that changes
+ *   inside the overlap between two shots raises the cost and may give K = 0; horizontal strips; sub-row alignment. */
+typedef struct ist_overlap_opts { int32_t tolerance, min_rows, min_informative, reserved; } ist_overlap_opts;
+typedef struct ist_overlap { int32_t header, footer, overlap, reserved; int64_t cost; } ist_overlap;
+/* The three host rules, pure CPU.  IST_E_INVALID for a NULL pointer, a negative count or a negative option.
+ * edge: d[0 .. n) = D of the row pairs counted from the edge, *t = H (or F) as above with L = n. */
+IST_API int ist_overlap_edge(const int64_t* d, int n, int64_t T, int32_t* t);
+/* select: cost[0 .. kmax], inf[0 .. kmax] (inf[k] = inf(k) above), *k = K.  opts NULL: the defaults. */
+IST_API int ist_overlap_select(const int64_t* cost, const int32_t* inf, int kmax, int64_t T, const ist_overlap_opts* opts, int32_t* k);
+/* the crop rule: image i of n (pairs[0 .. n - 1), heights[0 .. n)) keeps rows [top[i], bot[i]).  top[0] = 0, bot[n - 1] = heights[n - 1];
+ * a pair with overlap > 0 gives top[i + 1] = header + overlap and bot[i] = heights[i] - footer (the shared header and the overlap leave
+ * the lower image, the shared footer the upper one); a pair with overlap 0 crops nothing.  Then for i = 1 .. n - 2 in order: an image
+ * left with less than one row voids pair i (bot[i] = heights[i], top[i + 1] = 0).  n < 1: IST_E_INVALID. */
+IST_API int ist_overlap_rows(const ist_overlap* pairs, const int32_t* heights, int n, int32_t* top, int32_t* bot);
+/* out[i] = the pair (bitmap i, bitmap i + 1), i < n - 1.  Three launches (signatures of all images; edge differences of all pairs;
+ * costs and informative flags of all pairs) on the context's stream, which is synchronised twice: the host runs the edge rule between
+ * the second and the third launch, and the selection after the third.  Scratch is the context's, grow-only: a repeated shape allocates
+ * nothing.  Refused before anything is enqueued: n < 2 or a NULL table IST_E_INVALID; a NULL entry IST_E_DECODE; a bitmap of another
+ * device than the context's IST_E_INVALID; a bitmap with EXIF orientation > 1, or decoded at a reduced scale, IST_E_UNSUPPORTED
+ * ("image k: ..."); more than 128 images IST_E_UNSUPPORTED. */
+IST_API int ist_bitmaps_overlap(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, const ist_overlap_opts* opts, ist_overlap* out);
+/* the same for images in caller-owned device memory (image k: bitmap_w x bitmap_h of descs[k] at src[k], rows pitch[k] bytes apart,
+ * 4-byte aligned).  The caller's writes to the images must have completed; the call returns with the results in host memory. */
+IST_API int ist_overlap_device(ist_ctx* ctx, const void* const* src, const size_t* pitch, const ist_image_desc* descs, int n,
+                               const ist_overlap_opts* opts, ist_overlap* out);
+/* kernel launches made by the two calls above in this process so far (3 per call) */
+IST_API int64_t ist_debug_overlap_launches(void);
+/* the signature table of the context's LAST overlap call: `rows` rows (the images' rows in image order) of 32 uint32 each into out */
+IST_API int ist_debug_overlap_signatures(ist_ctx* ctx, uint32_t* out, int64_t rows);
+/* A bitmap that is rows [y0, y0 + rows) of another: it shares the parent's block and holds a reference on the parent, copies nothing,
+ * and its row 0 is the parent's row y0.  Its desc is the parent's with `rows` as the height and file_size 0; ist_debug_bitmap_bytes
+ * does not count it; every call that takes a bitmap takes a view.  Either may be released first: the block goes with its last
+ * holder.  NULL on failure: IST_E_INVALID for a NULL bitmap or rows outside it, IST_E_UNSUPPORTED for a bitmap with EXIF orientation
+ * > 1 or decoded at a reduced scale. */
+IST_API ist_bitmap* ist_bitmap_rows(ist_bitmap* b, int32_t y0, int32_t rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,9 @@
  *     decodeScaleFit(width, height, minWidth, minHeight) -> 1 | 2 | 4 | 8;
  *   bitmapDesc(h) -> {width,height,orientation,bmpWidth,bmpHeight,opaque,fileSize};  bitmapDownload(h) -> Buffer;  bitmapRelease(h);
  *   stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng) -> Promise (as stitch);  stitchBitmapsSync(...same...);
- *   debugBitmapBytes().  A handle is an object that wraps ONE reference of a bitmap: bitmapRelease drops it (again: nothing), its
+ *   debugBitmapBytes();  bitmapRows(h, y0, rows) -> handle of a row view (ist_bitmap_rows);
+ *   findOverlaps(handles, tolerance, minRows, minInformative) -> Promise<[{header, footer, overlap, cost}]>, findOverlapsSync(...same...)
+ *   (ist_bitmaps_overlap), overlapRows(pairs, heights) -> [[top, bot]] (ist_overlap_rows).  A handle is an object that wraps ONE reference of a bitmap: bitmapRelease drops it (again: nothing), its
  *   finaliser drops it when the handle is collected unreleased; a stitch holds a reference of its own from the call to its completion.
  *
  * images[i] = {width, height, orientation?, fileSize?, opaque?, bmpWidth?, bmpHeight?, data?: Uint8Array|Buffer}
@@ -1014,6 +1016,92 @@ static napi_value js_thumbnails(napi_env env, napi_callback_info info) {
   return job_queue(env, &j->h, "imagestitch.thumbnails");
 }
 
+/* ---- overlap removal for scrolled screenshots ------------------------------------------------------------------------------ */
+/* findOverlaps(handles, tolerance, minRows, minInformative) -> Promise<[{header, footer, overlap, cost}]> (ist_bitmaps_overlap: one
+ * record per neighbouring pair of a vertical strip, top to bottom); findOverlapsSync(...same...) -> the array itself */
+typedef struct { job h; bitmaps_t bm; ist_overlap_opts opts; ist_overlap* out; } overlap_job;
+
+static int overlap_run(ist_ctx* ctx, job* h) {
+  overlap_job* j = (overlap_job*)h;
+  return ist_bitmaps_overlap(ctx, j->bm.b, j->bm.n, &j->opts, j->out);
+}
+static napi_value overlap_result(napi_env env, job* h) {
+  overlap_job* j = (overlap_job*)h;
+  napi_value arr;
+  if (napi_create_array_with_length(env, (size_t)(j->bm.n - 1), &arr) != napi_ok) return NULL;
+  for (int i = 0; i + 1 < j->bm.n; i++) {
+    napi_value o;
+    if (napi_create_object(env, &o) != napi_ok) return NULL;
+    set_num(env, o, "header", j->out[i].header); set_num(env, o, "footer", j->out[i].footer);
+    set_num(env, o, "overlap", j->out[i].overlap); set_num(env, o, "cost", (double)j->out[i].cost);
+    if (napi_set_element(env, arr, (uint32_t)i, o) != napi_ok) return NULL;
+  }
+  return arr;
+}
+static void overlap_free(napi_env env, job* h) {
+  overlap_job* j = (overlap_job*)h;
+  (void)env;
+  bitmaps_free(&j->bm);
+  free(j->out); free(j);
+}
+static const job_kind OVERLAP = {overlap_run, overlap_result, overlap_free};
+
+static job* overlap_parse(napi_env env, napi_callback_info info) {
+  static const char usage[] = "findOverlaps(bitmaps, tolerance, minRows, minInformative)";
+  napi_value argv[4]; bitmaps_t bm;
+  if (!args_of(env, info, 4, 4, argv, usage) || !bitmaps_parse(env, argv[0], usage, &bm)) return NULL;
+  overlap_job* j = (overlap_job*)calloc(1, sizeof *j);
+  j->h.kind = &OVERLAP; j->bm = bm;
+  j->opts.tolerance = int_of(env, argv[1], -1); j->opts.min_rows = int_of(env, argv[2], -1); j->opts.min_informative = int_of(env, argv[3], -1);      /* (-1: the library's 'negative option') */
+  j->out = (ist_overlap*)calloc(bm.n > 1 ? (size_t)bm.n - 1 : 1, sizeof(ist_overlap));
+  return &j->h;
+}
+static napi_value js_find_overlaps(napi_env env, napi_callback_info info) { return job_queue(env, overlap_parse(env, info), "imagestitch.findOverlaps"); }
+static napi_value js_find_overlaps_sync(napi_env env, napi_callback_info info) { return job_now(env, overlap_parse(env, info)); }
+
+/* overlapRows(pairs: [{header, footer, overlap}], heights: number[]) -> [[top, bot]] (ist_overlap_rows: the crop rule, pure CPU) */
+static napi_value js_overlap_rows(napi_env env, napi_callback_info info) {
+  static const char usage[] = "overlapRows(pairs, heights)";
+  napi_value argv[2], arr = NULL; uint32_t np = 0, n = 0;
+  if (!args_of(env, info, 2, 2, argv, usage)) return NULL;
+  if (!array_len(env, argv[0], &np) || !array_len(env, argv[1], &n) || np + 1 != (n ? n : 1)) return throw_type(env, "overlapRows(pairs, heights): n images need n - 1 pairs");
+  ist_overlap* pairs = (ist_overlap*)calloc(np ? np : 1, sizeof *pairs);
+  int32_t* rows = (int32_t*)calloc(3 * (size_t)(n ? n : 1), sizeof *rows);      /* heights, top, bot */
+  for (uint32_t i = 0; i < np; i++) {
+    napi_value e; int64_t v;
+    napi_get_element(env, argv[0], i, &e);
+    if (get_named_i64(env, e, "header", &v)) pairs[i].header = (int32_t)v;
+    if (get_named_i64(env, e, "footer", &v)) pairs[i].footer = (int32_t)v;
+    if (get_named_i64(env, e, "overlap", &v)) pairs[i].overlap = (int32_t)v;
+  }
+  for (uint32_t i = 0; i < n; i++) { napi_value e; napi_get_element(env, argv[1], i, &e); rows[i] = int_of(env, e, 0); }
+  const int rc = ist_overlap_rows(pairs, rows, (int)n, rows + n, rows + 2 * (size_t)n);
+  if (rc < 0) throw_ist(env, rc);
+  else if (napi_create_array_with_length(env, n, &arr) == napi_ok) {
+    for (uint32_t i = 0; i < n; i++) {
+      napi_value pr, t, b;
+      napi_create_array_with_length(env, 2, &pr);
+      napi_create_int32(env, rows[n + i], &t); napi_create_int32(env, rows[2 * (size_t)n + i], &b);
+      napi_set_element(env, pr, 0, t); napi_set_element(env, pr, 1, b);
+      napi_set_element(env, arr, i, pr);
+    }
+  }
+  free(pairs); free(rows);
+  return arr;
+}
+
+/* bitmapRows(handle, y0, rows) -> handle of a view: rows [y0, y0 + rows) of the bitmap where they are (ist_bitmap_rows) */
+static napi_value js_bitmap_rows(napi_env env, napi_callback_info info) {
+  napi_value argv[3]; ist_bitmap* b;
+  if (!args_of(env, info, 3, 3, argv, "bitmapRows(handle, y0, rows)") || !(b = bitmap_of(env, argv[0]))) return NULL;
+  if (type_of(env, argv[1]) != napi_number || type_of(env, argv[2]) != napi_number) return throw_type(env, "bitmapRows(handle, y0, rows): y0 and rows must be numbers");
+  ist_bitmap* v = ist_bitmap_rows(b, int_of(env, argv[1], -1), int_of(env, argv[2], 0));
+  if (!v) return throw_ist(env, strstr(ist_last_error(), "orientation") || strstr(ist_last_error(), "reduced scale") ? IST_E_UNSUPPORTED : IST_E_INVALID);
+  napi_value h = bitmap_wrap(env, v);
+  if (!h) napi_throw_error(env, NULL, "could not wrap the bitmap");
+  return h;
+}
+
 /* bitmapRelease(handle): drops the handle's reference (a released handle: nothing) */
 static napi_value js_bitmap_release(napi_env env, napi_callback_info info) {
   napi_value argv[1]; bitmap_ref* r;
@@ -1070,6 +1158,10 @@ static napi_value init(napi_env env, napi_value exports) {
       {"stitchBitmaps", NULL, js_stitch_bitmaps, NULL, NULL, NULL, napi_default, NULL},
       {"stitchBitmapsSync", NULL, js_stitch_bitmaps_sync, NULL, NULL, NULL, napi_default, NULL},
       {"debugBitmapBytes", NULL, js_debug_bitmap_bytes, NULL, NULL, NULL, napi_default, NULL},
+      {"findOverlaps", NULL, js_find_overlaps, NULL, NULL, NULL, napi_default, NULL},
+      {"findOverlapsSync", NULL, js_find_overlaps_sync, NULL, NULL, NULL, napi_default, NULL},
+      {"overlapRows", NULL, js_overlap_rows, NULL, NULL, NULL, napi_default, NULL},
+      {"bitmapRows", NULL, js_bitmap_rows, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

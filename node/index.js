@@ -44,7 +44,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'devices', 'split', 'preview'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'devices', 'split', 'preview', 'overlap'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -67,9 +67,11 @@ function limitsOf(opts) {
 // anti-aliases them); OFF for the lifted MI355X default (every output pixel owned by exactly one image).
 function edgeAA(o) { return (o.edgeAA === undefined || o.edgeAA === null) ? (o.platform !== undefined && o.platform !== null) : !!o.edgeAA; }
 
+const OVERLAP_NEEDS = 'option overlap applies to stitch / stitchSync / stitchPng / stitchJpeg of a vertical strip of Bitmaps (uploadBitmap / decodeBitmaps): the overlaps are searched where the pixels are resident';
 function args(images, direction, opts) {
   const o = opts || {};
   for (const k of Object.keys(o)) if (!KNOWN.includes(k)) throw new TypeError('unknown stitch option ' + k);
+  if (o.overlap !== undefined && o.overlap !== null) throw new TypeError(OVERLAP_NEEDS);      // (withOverlap takes the option out where it applies)
   if (!(direction in DIRECTION)) throw new TypeError("direction must be 'vertical' or 'horizontal'");
   const mode = o.mode || 'min';                      // `|| 'min'` (index.js:1257)
   if (!(mode in MODE)) throw new TypeError('unknown mode ' + mode);
@@ -132,6 +134,9 @@ class Bitmap {
   /** the stored pixels shrunk to fit a width x height box (index.js:1600-1602; EXIF orientation is not applied, as in download()):
    *  {width, height, data}, reduced in GPU memory - a thumbnail without the download */
   preview(width, height) { return native.bitmapPreview(this.handle, width, height); }
+  /** rows [y0, y0 + n) of the stored pixels as a Bitmap of their own: a view that shares this bitmap's memory and keeps it alive,
+   *  copies nothing, and goes wherever a Bitmap goes.  Refused (err.code '-7') for EXIF orientation > 1 and reduced-scale decodes. */
+  rows(y0, n) { return new Bitmap(MADE_HERE, native.bitmapRows(this.handle, y0, n)); }
   release() { native.bitmapRelease(this.handle); }
 }
 // a request made of Bitmaps -> their native handles (null entries stay null: the library rejects them as a missing image); null for a
@@ -180,6 +185,67 @@ function thumbnails(bitmaps, cell) {
   if (!bitmaps.length) return Promise.resolve([]);
   try { return native.thumbnails(bitmaps.map((x) => (x ? x.handle : null)), c.width, c.height, mode === 'fit' ? 1 : 0, c.orient !== false); } catch (e) { return Promise.reject(e); }      // (a released Bitmap throws on this thread)
 }
+// {tolerance, minRows, minInformative} of an overlap search (the contract's defaults, include/imagestitch.h), checked
+function overlapArgs(o) {
+  const v = Object.assign({ tolerance: 8, minRows: 16, minInformative: 8 }, o || {});
+  for (const k of Object.keys(v)) if (!['tolerance', 'minRows', 'minInformative'].includes(k)) throw new TypeError('unknown overlap option ' + k);
+  for (const k of Object.keys(v)) if (!Number.isInteger(v[k]) || v[k] < 0) throw new RangeError(k + ' must be a non-negative integer');
+  return [v.tolerance, v.minRows, v.minInformative];
+}
+function overlapHandles(bitmaps) {
+  if (!Array.isArray(bitmaps) || !bitmaps.every((x) => x instanceof Bitmap)) throw new TypeError('findOverlaps(bitmaps: Bitmap[], {tolerance?, minRows?, minInformative?}): ' + OVERLAP_NEEDS);
+  return bitmaps.map((x) => x.handle);
+}
+/** Per neighbouring pair of a vertical strip of Bitmaps (scrolled screenshots, top to bottom): {header, footer, overlap, cost} - the
+ *  rows of a bar both shots repeat at the top and at the bottom, the rows of the upper shot's body the lower one shows again, and
+ *  the summed row difference there.  Found on the GPU from the resident pixels (three launches); the rule and its limits are in
+ *  include/imagestitch.h.  The defaults are the contract's, not measured optima: tolerance 8 is two 8-bit levels per pixel. */
+function findOverlaps(bitmaps, opts) {
+  try { return native.findOverlaps(overlapHandles(bitmaps), ...overlapArgs(opts)); } catch (e) { return Promise.reject(e); }
+}
+function findOverlapsSync(bitmaps, opts) { return native.findOverlapsSync(overlapHandles(bitmaps), ...overlapArgs(opts)); }
+/** The crop rule (pure CPU): [[top, bot]] per image - image i keeps rows [top, bot) - for findOverlaps' records and the heights. */
+function overlapRows(pairs, heights) { return native.overlapRows(pairs, heights); }
+// opts.overlap ('auto' or {tolerance, minRows, minInformative}) around one stitch call: the overlaps are found, the call runs on row
+// views of the bitmaps with the option taken out, the views are released, and the result carries the records as `overlaps`
+function overlapOf(images, direction, opts) {
+  const v = opts ? opts.overlap : undefined;
+  if (v === undefined || v === null) return null;
+  if (v !== 'auto' && (typeof v !== 'object' || Array.isArray(v))) throw new TypeError("overlap must be 'auto' or {tolerance, minRows, minInformative}");
+  const o = overlapArgs(v === 'auto' ? null : v);
+  if (direction !== 'vertical' || !Array.isArray(images) || !images.length || !images.every((x) => x instanceof Bitmap) || (opts.devices !== undefined && opts.devices !== null)) throw new TypeError(OVERLAP_NEEDS);
+  const rest = Object.assign({}, opts);
+  delete rest.overlap;
+  return { o, rest };
+}
+function cropViews(images, records) {
+  const rows = native.overlapRows(records, images.map((b) => b.bmpHeight));
+  const views = [];
+  try { images.forEach((b, i) => views.push(b.rows(rows[i][0], rows[i][1] - rows[i][0]))); } catch (e) { views.forEach((x) => x.release()); throw e; }
+  return views;
+}
+function withOverlap(fn) {
+  return (images, direction, opts) => {
+    let w;
+    try { w = overlapOf(images, direction, opts); } catch (e) { return Promise.reject(e); }
+    if (!w) return fn(images, direction, opts);
+    const found = images.length > 1 ? native.findOverlaps(images.map((x) => x.handle), ...w.o) : Promise.resolve([]);
+    return found.then((records) => {
+      const views = cropViews(images, records);
+      const done = () => views.forEach((x) => x.release());
+      return fn(views, direction, w.rest).then((r) => { done(); if (r) r.overlaps = records; return r; }, (e) => { done(); throw e; });
+    });
+  };
+}
+function withOverlapSync(fn) {
+  return (images, direction, opts) => {
+    const w = overlapOf(images, direction, opts);
+    if (!w) return fn(images, direction, opts);
+    const records = images.length > 1 ? native.findOverlapsSync(images.map((x) => x.handle), ...w.o) : [];
+    const views = cropViews(images, records);
+    try { const r = fn(views, direction, w.rest); if (r) r.overlaps = records; return r; } finally { views.forEach((x) => x.release()); }
+  };
+}
 /** device bytes held by the live bitmaps of this process */
 function debugBitmapBytes() { return native.debugBitmapBytes(); }
 
@@ -206,7 +272,7 @@ function stitchSync(images, direction, opts) {
   return h ? native.stitchBitmapsSync(h, a[1], a[2], a[3], a[4], a[5], false) : native.stitchSync(...a, false, ...g);
 }
 // A batch runs on one GPU and returns pixels: the device-group and PNG options do not apply to its requests.
-const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'preview'];
+const BATCH_REFUSED = ['devices', 'split', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'preview', 'overlap'];
 // the native arguments of request k of a batch, opts given apart (the JPEG batch takes its own two out first)
 function batchRequest(r, k, o) {
   for (const key of BATCH_REFUSED) if (key in o) throw new TypeError('request ' + k + ': option ' + key + ' does not apply to a batch');
@@ -390,5 +456,5 @@ function plan(images, direction, opts) {
   return native.plan(a[0], a[1], a[2], a[3], a[4]);
 }
 
-module.exports = { stitch, stitchSync, stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng, stitchJpeg, stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
-                   decodeBitmaps, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+module.exports = { stitch: withOverlap(stitch), stitchSync: withOverlapSync(stitchSync), stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng: withOverlap(stitchPng), stitchJpeg: withOverlap(stitchJpeg), stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
+                   decodeBitmaps, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, findOverlaps, findOverlapsSync, overlapRows, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
