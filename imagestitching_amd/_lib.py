@@ -280,6 +280,7 @@ SYMBOLS = [
     ("ist_debug_jpeg_batch_launches", C.c_int64, []),
     ("ist_jpeg_optimal_table", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int)]),
     ("ist_debug_jpeg_histogram_launches", C.c_int64, []),
+    ("ist_debug_jpeg_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]),
     ("ist_overlap_edge", C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.POINTER(C.c_int32)]),
     ("ist_overlap_select", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.POINTER(OverlapOpts), C.POINTER(C.c_int32)]),
     ("ist_overlap_rows", C.c_int, [C.POINTER(Overlap), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

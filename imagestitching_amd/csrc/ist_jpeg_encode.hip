@@ -772,6 +772,20 @@ extern "C" {
 int64_t ist_debug_jpeg_encode_launches(void) { return g_launches.load(std::memory_order_relaxed); }
 int64_t ist_debug_jpeg_histogram_launches(void) { return g_hist_launches.load(std::memory_order_relaxed); }
 
+int ist_debug_jpeg_counts(ist_ctx* ctx, int64_t* out, int64_t n) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!out || n < 0 || n % kJpegCounters != 0) return fail(IST_E_INVALID, "ist_debug_jpeg_counts: NULL argument or a count that is no multiple of " + std::to_string(kJpegCounters));
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const int64_t held = static_cast<int64_t>(ctx->scratch_jpg_counts.bytes / 8);
+  if (n > held) return fail(IST_E_INVALID, "ist_debug_jpeg_counts: the block holds " + std::to_string(held) + " counters");
+  if (n == 0) return IST_OK;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
+  IST_HIP(hipStreamSynchronize(ctx->stream));
+  IST_HIP(hipMemcpy(out, ctx->scratch_jpg_counts.p, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost));
+  return IST_OK;
+}
+
 int ist_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]) {
   if (quality < 1 || quality > 100) return fail(IST_E_INVALID, "ist_jpeg_quant_tables: quality must be 1..100");
   if (!luma || !chroma) return fail(IST_E_INVALID, "ist_jpeg_quant_tables: NULL table");

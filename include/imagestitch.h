@@ -838,6 +838,11 @@ IST_API int ist_stitch_bitmaps_jpeg(ist_ctx* ctx, ist_bitmap* const* bitmaps, in
 IST_API int64_t ist_debug_jpeg_encode_launches(void);
 /* histogram launches (IST_JPEG_OPTIMIZE: one per slab of a single file, one per counted round of a batch) so far */
 IST_API int64_t ist_debug_jpeg_histogram_launches(void);
+/* the symbol counts that the context's last encode with IST_JPEG_OPTIMIZE made, as its histogram kernel left them: the first n
+ * counters of the block, 544 per optimised file of that call in file order; per file and table slot (luma, then chroma) 16 DC sizes,
+ * then 256 AC symbols.  Synchronises the context's stream and copies; launches nothing.  IST_E_NO_CONTEXT; IST_E_INVALID: a NULL out,
+ * n negative, no multiple of 544 or above what the block holds (it grows with the calls and is never cleared between them). */
+IST_API int ist_debug_jpeg_counts(ist_ctx* ctx, int64_t* out, int64_t n);
 
 /* ---- batched JPEG export: many canvases per launch --------------------------------------------------------------------------
  * The encoder's unit of work is the restart interval (one MCU row), and an interval of file A needs an interval of file B as little

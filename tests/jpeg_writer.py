@@ -261,6 +261,12 @@ def _scan_blocks(f, cs):
 def _symbols(f, cs, restart):
     """The scan as events in coding order: (table class 0 DC / 1 AC, component, symbol) for Huffman codes, component -1
     for raw magnitude bits (value, size); plus the restart interval each event belongs to."""
+    ev, _, iv, n_iv = _events(f, cs, restart)
+    return ev, iv, n_iv
+
+
+def _events(f, cs, restart):
+    """_symbols, and the block (its index in coding order) that each event belongs to"""
     comp, by, bx, mcu = _scan_blocks(f, cs)
     nb = len(comp)
     Z = np.zeros((nb, 64), np.int64)
@@ -316,11 +322,18 @@ def _symbols(f, cs, restart):
     order = np.argsort(key, kind="stable")
     ev = [np.concatenate(x)[order] for x in (cls, ecomp, sym, raw, nbits)]
     blk = key[order] // 1024
-    return ev, interval[blk], int(interval.max()) + 1 if nb else 0
+    return ev, blk, interval[blk], int(interval.max()) + 1 if nb else 0
 
 
 def _pack(codes, lens):
     """bit strings -> bytes, padded with 1 bits, 0xFF stuffed with 0x00."""
+    data = _pack_bits(codes, lens)
+    ff = np.nonzero(data == 0xFF)[0]
+    return np.insert(data, ff + 1, 0).tobytes()
+
+
+def _pack_bits(codes, lens):
+    """bit strings -> a uint8 array, padded with 1 bits, before any stuffing."""
     lens = np.asarray(lens, np.int64)
     codes = np.asarray(codes, np.int64)
     keep = lens > 0
@@ -332,14 +345,12 @@ def _pack(codes, lens):
         lens = np.append(lens, pad)
         total += pad
     if total == 0:
-        return b""
+        return np.zeros(0, np.uint8)
     starts = np.cumsum(lens) - lens
     rep = np.repeat(np.arange(len(lens)), lens)
     within = np.arange(total) - starts[rep]
     bits = (codes[rep] >> (lens[rep] - 1 - within)) & 1
-    data = np.packbits(bits.astype(np.uint8))
-    ff = np.nonzero(data == 0xFF)[0]
-    return np.insert(data, ff + 1, 0).tobytes()
+    return np.packbits(bits.astype(np.uint8))
 
 
 def _seg(marker, payload, fill):
@@ -361,7 +372,9 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
     tables: 'front' (every DQT / DHT before the frame) or 'scan' (each scan's tables just in front of it: quantisation
     tables appear right before a component's first scan, Huffman slots are redefined per scan when their content changes).
     trace: a list that receives, per scan, what was coded (tests/jpeg_sync_model.py works from it): the _symbols events, the
-    length in bits of every event (code or magnitude bits), the event index where each restart interval starts, and the slots.
+    length in bits of every event (code or magnitude bits), the event index where each restart interval starts, and the slots;
+    also every event's value ("codes": the Huffman code or the magnitude bits) and the block it belongs to ("block": the index in
+    the scan's coding order), from which tests/jpeg_encode_cases.py restates the encoder's batch loop.
     """
     n = len(f.comps)
     scans = scans or [list(range(n))]
@@ -383,7 +396,8 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
     def dht(tc, slot, bits, vals):
         return _seg(0xC4, bytes([tc * 16 + slot]) + bytes(bits) + bytes(vals), fill)
 
-    scan_ev = [_symbols(f, cs, restart) for cs in scans]
+    scan_all = [_events(f, cs, restart) for cs in scans]
+    scan_ev = [(ev, iv, n_iv) for ev, _, iv, n_iv in scan_all]
     slots = (dc_slots, ac_slots)
 
     def table_for(tc, slot, evs):
@@ -417,7 +431,7 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
         body += bytes([c["id"], c["h"] * 16 + c["v"], c["tq"]])
     out += _seg(0xC0 + sof, body, fill)
     latched = set()
-    for si, (cs, (ev, iv, n_iv)) in enumerate(zip(scans, scan_ev)):
+    for si, (cs, (ev, blk, iv, n_iv)) in enumerate(zip(scans, scan_all)):
         if noise and si > 0:
             out += _seg(0xFE, b"between scans %d" % si, fill)
             out += _seg(0xE9, bytes(rng.integers(0, 256, 20, dtype=np.uint8)), fill)
@@ -451,7 +465,7 @@ def write_jpeg(f, *, sof=0, marker="jfif", scans=None, huff="std", dc_slots=None
         bounds = np.searchsorted(iv, np.arange(n_iv + 1))
         if trace is not None:
             trace.append({"comps": list(cs), "cls": cls, "comp": comp, "sym": sym, "lens": lens.copy(), "bounds": bounds,
-                          "dc_slots": tuple(dc_slots), "ac_slots": tuple(ac_slots)})
+                          "dc_slots": tuple(dc_slots), "ac_slots": tuple(ac_slots), "codes": codes.copy(), "block": blk})
         for k in range(n_iv):
             if k:
                 out += b"\xff" * fill + bytes([0xFF, 0xD0 + (k - 1) % 8])

@@ -277,6 +277,21 @@ def test_every_entry_point_accepts_the_flag_as_far_as_the_checks_without_a_devic
     assert before == (L.lib.ist_debug_jpeg_encode_launches(), L.lib.ist_debug_jpeg_batch_launches(), L.lib.ist_debug_jpeg_histogram_launches())
 
 
+def test_debug_counts_refuses_bad_arguments_without_a_device():
+    """ist_debug_jpeg_counts: every argument is checked before the context is used (what the block holds needs a context: that refusal is
+    in tests/test_gpu_jpeg_encode_regimes.py)"""
+    fake = C.c_void_p(8)                                   # (never dereferenced)
+    out = (C.c_int64 * 1088)()
+    before = L.lib.ist_debug_jpeg_encode_launches(), L.lib.ist_debug_jpeg_histogram_launches()
+    assert L.lib.ist_debug_jpeg_counts(None, out, 544) == NO_CONTEXT
+    assert L.lib.ist_debug_jpeg_counts(fake, None, 544) == INVALID
+    for n in (-544, -1, 1, 16, 272, 543, 545, 1087):
+        assert L.lib.ist_debug_jpeg_counts(fake, out, n) == INVALID and "544" in L.last_error(), n
+    assert before == (L.lib.ist_debug_jpeg_encode_launches(), L.lib.ist_debug_jpeg_histogram_launches())
+    header = open(os.path.join(ROOT, "include", "imagestitch.h")).read()
+    assert "IST_API int ist_debug_jpeg_counts(ist_ctx* ctx, int64_t* out, int64_t n);" in header
+
+
 def test_python_wrappers_check_optimize():
     px = np.zeros((4, 4, 4), np.uint8)
     for bad in (1, 0, "yes", None, np.bool_(True), [True]):
