@@ -118,6 +118,13 @@ class JpegCoefInfo(C.Structure):
                 ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3)]
 
 
+class ColorTables(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("mq", (C.c_int32 * 3) * 3), ("dec", (C.c_uint16 * 256) * 3)]
+
+
+COLOR_PROFILE_IGNORE, COLOR_PROFILE_SRGB = 0, 1
+COLOR_NONE, COLOR_IDENTITY, COLOR_CONVERT, COLOR_UNSUPPORTED = 0, 1, 2, 3
+
 # every symbol include/imagestitch.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ist_abi_version", C.c_int, []),
@@ -290,6 +297,11 @@ SYMBOLS = [
     ("ist_debug_overlap_launches", C.c_int64, []),
     ("ist_debug_overlap_signatures", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
     ("ist_bitmap_rows", C.c_void_p, [C.c_void_p, C.c_int32, C.c_int32]),
+    ("ist_ctx_set_color_profile", C.c_int, [C.c_void_p, C.c_int]),
+    ("ist_image_color", C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int32)]),
+    ("ist_icc_tables", C.c_int, [C.c_char_p, C.c_int64, C.POINTER(ColorTables)]),
+    ("ist_color_convert_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.POINTER(ColorTables), C.c_void_p]),
+    ("ist_debug_color_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

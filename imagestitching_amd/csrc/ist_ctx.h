@@ -48,6 +48,7 @@ struct ist_ctx {
   int png_color = IST_PNG_RGBA;          // colour type 6, or IST_PNG_RGB: colour type 2, alpha not read (ist_ctx_set_png_color)
   int png_filter = IST_PNG_FILTER_PAETH; // type 4 on every row, or IST_PNG_FILTER_ADAPTIVE: a type per row, level 1 only (ist_ctx_set_png_filter)
   int png_match = IST_PNG_MATCH_RUN;     // runs inside a span, or IST_PNG_MATCH_WINDOW: also matches at a distance, level 1 only (ist_ctx_set_png_match)
+  int color_profile = IST_COLOR_PROFILE_IGNORE;   // or IST_COLOR_PROFILE_SRGB: ICC-tagged files are converted to sRGB behind their decode (ist_ctx_set_color_profile)
   std::unique_ptr<ist::Stager> stager;   // pinned staging ring, built on first use
   bool timing_on = false;                // ist_ctx_set_timing: the file pipeline records its phase times (adds a sync per phase)
   double last_ms[IST_PHASE_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};

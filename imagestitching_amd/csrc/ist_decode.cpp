@@ -115,6 +115,10 @@ int jpeg_decode_rgba8(const char* who, ist_ctx* ctx, const uint8_t* file, int64_
   d = static_cast<uint8_t*>(ctx->scratch_arena.p);
   rc = jpeg_enqueue(J, d, d, L, d + o_out, row, ctx->stream, false, false, denom);
   if (rc) return rc;
+  if (ctx->color_profile == IST_COLOR_PROFILE_SRGB) {
+    ist_color_tables t;
+    if (image_color_tables(file, len, &t) == IST_COLOR_CONVERT) { rc = launch_color_convert(d + o_out, row, sw, sh, t, ctx->stream); if (rc) return rc; }
+  }
   std::vector<RowsCopy> down{RowsCopy{d + o_out, nullptr, out, out_pitch, row, static_cast<size_t>(sh)}};
   rc = stager_of(ctx).download(down, ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);              // nothing of this call may still read the arena when the next call reuses it
@@ -306,8 +310,21 @@ int FileDecoder::take(int i, hipStream_t consumer) {
   if (rc) return rc;
   rc = chroma_all(consumer);
   if (rc) return rc;
-  Dec& D = dec_[k];
   taken_[k] = 1;
+  rc = place(i, consumer);
+  if (rc) return rc;
+  // the one place where bitmap i lands: a file tagged with a profile the contract takes is converted to sRGB behind it, in place
+  const Dec& D = dec_[k];
+  if (ctx_->color_profile != IST_COLOR_PROFILE_SRGB || D.color.kind != IST_COLOR_CONVERT) return IST_OK;
+  int bw = D.w, bh = D.h;
+  if (denom_of(i) > 1) jpeg_scaled_size(D.w, D.h, denom_of(i), &bw, &bh);
+  return launch_color_convert(img_[i], pitch_[i], bw, bh, D.color, consumer);
+}
+
+int FileDecoder::place(int i, hipStream_t consumer) {
+  const size_t k = static_cast<size_t>(i);
+  int rc = IST_OK;
+  Dec& D = dec_[k];
   if (on_gpu_[k]) return jpeg_enqueue(D.J, arena_, nullptr, jo_[k], img_[i], pitch_[i], consumer, true, chroma_done_[k] != 0, denom_of(i));
   const size_t row = static_cast<size_t>(D.w) * 4;
   if (!D.jpeg) {                                  // PNG / BMP / GIF / WebP: decoded on the thread, uploaded here
@@ -403,6 +420,7 @@ void FileDecoder::worker(int i) {
   DeviceGuard dg(ctx_->device);
   const uint8_t* f = files_[i]; const int64_t len = lens_[i];
   auto failed = [&](int rc) { D.rc = rc; D.err = g_last_error; };     // (thread-local message: carry it out)
+  if (ctx_->color_profile == IST_COLOR_PROFILE_SRGB) image_color_tables(f, len, &D.color);      // (a bad profile never fails a decode)
   if (!D.jpeg) {
     D.px.resize(static_cast<size_t>(D.w) * D.h * 4);
     const int rc = ist_image_decode_rgba8(nullptr, f, len, D.px.data(), static_cast<size_t>(D.w) * 4, D.h);
@@ -524,6 +542,23 @@ int ist_debug_jpeg_gpu_coefficients(ist_ctx* ctx, const uint8_t* file, int64_t l
     for (int c = 0; c < J.ncomp; ++c) IST_HIP(hipMemcpyAsync(planes[c], d + o_coef[c], nblk[c] * 128, hipMemcpyDeviceToHost, ctx->stream));
   IST_HIP(hipStreamSynchronize(ctx->stream));           // nothing of this call may still read the arena when the next call reuses it
   return IST_OK;
+}
+
+int ist_ctx_set_color_profile(ist_ctx* ctx, int profile) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (profile != IST_COLOR_PROFILE_IGNORE && profile != IST_COLOR_PROFILE_SRGB) return fail(IST_E_INVALID, "colour profile must be IST_COLOR_PROFILE_IGNORE (0) or IST_COLOR_PROFILE_SRGB (1)");
+  ctx->color_profile = profile;
+  return IST_OK;
+}
+
+int ist_color_convert_device(ist_ctx* ctx, void* ptr, size_t pitch, int64_t w, int64_t h, const ist_color_tables* tables, void* stream) {
+  if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
+  if (!ptr || !tables || w < 1 || h < 1) return fail(IST_E_INVALID, "ist_color_convert_device: bad argument");
+  if (pitch / 4 < static_cast<uint64_t>(w) || (pitch & 3) || (reinterpret_cast<uintptr_t>(ptr) & 3)) return fail(IST_E_INVALID, "ist_color_convert_device: a short or unaligned pitch, or an unaligned pointer");
+  if (tables->kind == IST_COLOR_IDENTITY) return IST_OK;
+  if (tables->kind != IST_COLOR_CONVERT) return fail(IST_E_INVALID, "ist_color_convert_device: the tables are neither IST_COLOR_CONVERT nor IST_COLOR_IDENTITY");
+  DeviceGuard g(ctx->device);
+  return launch_color_convert(static_cast<uint8_t*>(ptr), pitch, w, h, *tables, stream);
 }
 
 int ist_ctx_set_timing(ist_ctx* ctx, int on) {

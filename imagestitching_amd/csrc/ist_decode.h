@@ -9,11 +9,13 @@
 #include <vector>
 
 #include "ist_ctx.h"
+#include "ist_icc.h"
 
 namespace ist {
 
 // what is known of one file: after FileDecoder::headers() the size and orientation, after its worker the decoded form
-struct Dec { int rc = 0; std::string err; bool jpeg = false; JpegImage J; JpegGpuScan G; int w = 0, h = 0, orient = 0; std::vector<uint8_t> px; };
+struct Dec { int rc = 0; std::string err; bool jpeg = false; JpegImage J; JpegGpuScan G; int w = 0, h = 0, orient = 0; std::vector<uint8_t> px;
+             ist_color_tables color = {}; };      // color: the file's profile, read by its worker when the context converts to sRGB (kind NONE otherwise)
 
 // phase clock: stderr lines under IST_TIMING=1, numbers for ist_ctx_last_timing when the context asked for them.  Phases
 // end with a stream synchronisation only while one of the two is on.
@@ -62,6 +64,7 @@ class FileDecoder {
   int huffman_all(hipStream_t consumer);
   int chroma_all(hipStream_t consumer);
   void worker(int i);
+  int place(int i, hipStream_t consumer);      // take() without the colour conversion: bitmap i lands at img_[i] on `consumer`
 
   ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_; const int32_t* denom_;
   std::vector<Dec> dec_;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "ist_internal.h"
+#include "ist_icc.h"
 #include "ist_jpeg.h"
 
 #include <emmintrin.h>
@@ -564,6 +565,39 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
 int jpeg_parse_and_entropy_decode(const uint8_t* f, int64_t n, JpegImage* J, bool header_only, JpegGpuScan* gs) {
   try { return jpeg_parse_inner(f, n, J, header_only, gs); }
   catch (const std::bad_alloc&) { return fail(IST_E_NOMEM, "out of memory while decoding the JPEG"); }
+}
+
+// The ICC profile of a file (ist_icc.h): the APP2 "ICC_PROFILE\0" chunks in front of the first scan, joined in seq order.  A walk of
+// its own over the segments, beside the decode: whatever is wrong with the chunks means "no profile", never a failed decode.
+bool jpeg_icc_profile(const uint8_t* f, int64_t n, std::vector<uint8_t>* icc) {
+  icc->clear();
+  if (!f || n < 4 || f[0] != 0xFF || f[1] != 0xD8) return false;
+  struct Chunk { const uint8_t* p = nullptr; size_t n = 0; bool seen = false; };
+  Chunk chunk[256];
+  int count = 0, seen = 0;
+  int64_t pos = 2;
+  while (pos + 4 <= n) {
+    if (f[pos] != 0xFF) { ++pos; continue; }
+    const int m = f[pos + 1];
+    if (m == 0xFF) { ++pos; continue; }
+    if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { pos += 2; continue; }
+    if (m == 0xD9 || m == 0xDA) break;
+    const int64_t len = be16(f + pos + 2);
+    if (len < 2 || pos + 2 + len > n) return false;
+    const uint8_t* d = f + pos + 4; const int64_t dl = len - 2;
+    if (m == 0xE2 && dl >= 14 && std::memcmp(d, "ICC_PROFILE\0", 12) == 0) {
+      const int seq = d[12], cnt = d[13];
+      if (seq == 0 || seq > cnt || (count && cnt != count) || chunk[seq].seen) return false;
+      count = cnt;
+      chunk[seq].p = d + 14; chunk[seq].n = static_cast<size_t>(dl - 14); chunk[seq].seen = true;
+      ++seen;
+    }
+    pos += 2 + len;
+  }
+  if (count == 0 || seen != count) return false;
+  try { for (int s = 1; s <= count; ++s) icc->insert(icc->end(), chunk[s].p, chunk[s].p + chunk[s].n); }
+  catch (const std::bad_alloc&) { icc->clear(); return false; }
+  return true;
 }
 
 std::vector<int16_t> jpeg_dense_coefficients(const JpegComp& c) {

@@ -19,6 +19,7 @@
 #include <new>
 #include <vector>
 
+#include "ist_icc.h"
 #include "ist_internal.h"
 
 using namespace ist;
@@ -200,6 +201,51 @@ struct Inflater {
 };
 
 }  // namespace
+
+// The ICC profile of a file (ist_icc.h): iCCP (name, NUL, method 0, zlib stream) in front of the first IDAT, inflated with a cap of
+// kMaxIccBytes; without one, an sRGB chunk sets *srgb.  A walk of its own beside the decode (no CRC check: the decode makes it):
+// a damaged chunk or stream means "no profile", never a failed decode.
+bool ist::png_icc_profile(const uint8_t* f, int64_t n, std::vector<uint8_t>* icc, bool* srgb) {
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+  icc->clear(); *srgb = false;
+  if (!f || n < 8 || std::memcmp(f, sig, 8) != 0) return false;
+  bool have_iccp = false, ok = false;
+  for (int64_t pos = 8; pos + 12 <= n;) {
+    const uint32_t len = be32(f + pos);
+    const uint8_t* type = f + pos + 4; const uint8_t* data = f + pos + 8;
+    if (pos + 12 + int64_t(len) > n) break;
+    if (!std::memcmp(type, "IDAT", 4) || !std::memcmp(type, "IEND", 4)) break;
+    if (!std::memcmp(type, "sRGB", 4)) *srgb = true;
+    else if (!std::memcmp(type, "iCCP", 4) && !have_iccp) {
+      have_iccp = true;                                     // (it wins over sRGB even when it turns out to be damaged)
+      uint32_t k = 0;
+      while (k < len && k < 80 && data[k]) ++k;             // the name: 1-79 bytes, then NUL
+      if (k >= 1 && k < 80 && k + 2 <= len && data[k] == 0 && data[k + 1] == 0) {
+        z_stream z; std::memset(&z, 0, sizeof z);
+        if (inflateInit(&z) == Z_OK) {
+          z.next_in = const_cast<Bytef*>(data + k + 2); z.avail_in = len - (k + 2);
+          try {
+            std::vector<uint8_t> out(65536);
+            size_t have = 0;
+            for (;;) {
+              z.next_out = out.data() + have; z.avail_out = static_cast<uInt>(out.size() - have);
+              const int r = inflate(&z, Z_NO_FLUSH);
+              have = out.size() - z.avail_out;
+              if (r == Z_STREAM_END) { ok = true; break; }
+              if (r != Z_OK || have < out.size() || out.size() >= kMaxIccBytes) break;      // damaged, starved, or above the cap
+              out.resize(std::min(out.size() * 2, kMaxIccBytes));
+            }
+            if (ok) { out.resize(have); icc->swap(out); }
+          } catch (const std::bad_alloc&) { ok = false; }
+          inflateEnd(&z);
+        }
+      }
+    }
+    pos += 12 + int64_t(len);
+  }
+  if (have_iccp) *srgb = false;
+  return ok;
+}
 
 extern "C" {
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ist_internal.h"
+#include "ist_icc.h"
 #include "ist_webp.h"
 
 namespace ist {
@@ -485,6 +486,29 @@ int parse_riff(const uint8_t* f, int64_t n, Riff* R) {
 }  // namespace
 
 bool is_webp(const uint8_t* f, int64_t n) { return f && n >= 12 && !std::memcmp(f, "RIFF", 4) && !std::memcmp(f + 8, "WEBP", 4); }
+
+// The ICC profile of a file (ist_icc.h): the first top-level ICCP chunk behind a VP8X chunk.  A walk of its own beside the decode:
+// a damaged container means "no profile", never a failed decode.
+bool webp_icc_profile(const uint8_t* f, int64_t n, std::vector<uint8_t>* icc) {
+  icc->clear();
+  if (!is_webp(f, n) || n < 20) return false;
+  int64_t end = 8 + static_cast<int64_t>(le32(f + 4));
+  if (end > n) end = n;
+  bool vp8x = false;
+  for (int64_t pos = 12; pos + 8 <= end;) {
+    const uint8_t* tag = f + pos;
+    const int64_t len = le32(f + pos + 4);
+    if (pos + 8 + len > end) return false;
+    if (!std::memcmp(tag, "VP8X", 4)) vp8x = true;
+    else if (!std::memcmp(tag, "ICCP", 4)) {
+      if (!vp8x) return false;
+      try { icc->assign(f + pos + 8, f + pos + 8 + len); } catch (const std::bad_alloc&) { icc->clear(); return false; }
+      return true;
+    }
+    pos += 8 + len + (len & 1);
+  }
+  return false;
+}
 
 int webp_info(const uint8_t* f, int64_t n, int32_t* w, int32_t* h, int32_t* orientation) {
   Riff R;

@@ -69,6 +69,8 @@ DEFAULT_OPTS = {
     "devices": None,        # list of GPU indices (devices[0] = root): shard the stitch over them from this one process (ist_stitch_rgba8_multi)
     "preview": None,        # (box_w, box_h): stitch_png / stitch_files also return the canvas shrunk to fit that box (the redraw into the preview
                             # node, index.js:1597-1603), as result['preview'], HxWx4 uint8.  Refused where no canvas stays in HBM behind an export.
+    "colorProfile": None,   # stitch_files: 'ignore' (pixels as decoded) or 'srgb' (a file tagged with a matrix/TRC ICC profile - Display P3, Adobe RGB - is
+                            # converted to sRGB on the GPU behind its decode; include/imagestitch.h "colour profiles"); None = 'ignore'
     "overlap": None,        # 'auto', or a dict of tolerance / min_rows / min_informative: a vertical strip of Bitmaps (scrolled screenshots) is stitched
                             # without the bars and the overlaps its neighbours share (find_overlaps, crop_overlaps); the result also has 'overlaps'
     "split": "auto",        # with devices: "image" (image i -> devices[i mod n], BASELINE configs[3]), "band" (equal output rows per device, cut draw
@@ -134,7 +136,7 @@ def _limits(opts):
     return lim
 
 
-def _merge(opts, overlap=False):
+def _merge(opts, overlap=False, color=False):
     o = dict(DEFAULT_OPTS)
     if opts:
         unknown = set(opts) - set(o)
@@ -143,7 +145,24 @@ def _merge(opts, overlap=False):
         o.update(opts)
     if o["overlap"] is not None and not overlap:
         raise TypeError(_OVERLAP_NEEDS)
+    if o["colorProfile"] is not None and not color:
+        raise TypeError(_COLOR_NEEDS)
     return o
+
+
+_COLOR_NEEDS = ("the 'colorProfile' option applies to stitch_files: a profile comes with a file, so the conversion belongs to the decode "
+                "(decode_bitmaps / decode_files_device take profile=); raw pixels carry none")
+COLOR_PROFILES = {"ignore": L.COLOR_PROFILE_IGNORE, "srgb": L.COLOR_PROFILE_SRGB}
+COLOR_KINDS = ("none", "identity", "convert", "unsupported")      # IST_COLOR_*
+
+
+def _color_profile(profile):
+    """IST_COLOR_PROFILE_* of a colorProfile / profile= value (None: ignore), checked before any library call"""
+    if profile is None:
+        return COLOR_PROFILES["ignore"]
+    if not isinstance(profile, str) or profile not in COLOR_PROFILES:
+        raise ValueError("colorProfile must be 'ignore' or 'srgb', not %r" % (profile,))
+    return COLOR_PROFILES[profile]
 
 
 _OVERLAP_NEEDS = ("the 'overlap' option applies to stitch / stitch_png / stitch_jpeg of a vertical strip of Bitmaps "
@@ -414,6 +433,15 @@ def _ctx(device=0):
         if not c:
             raise L.StitchError(-5, L.last_error())
         _ctx_cache[device] = c
+    return c
+
+
+def _ctx_color(device, profile):
+    """The context with its colour setting set (ist_ctx_set_color_profile): per context like the PNG form, so every call that decodes
+    files sets it and never inherits the one before it.  An unknown value raises ValueError before the context is asked for."""
+    p = _color_profile(profile)
+    c = _ctx(device)
+    L.check(L.lib.ist_ctx_set_color_profile(c, p))
     return c
 
 
@@ -740,19 +768,23 @@ def _is_jpeg(buf):
     return buf[:2] == b"\xff\xd8"
 
 
-def decode_image(data, device=0, scale=1):
+def decode_image(data, device=0, scale=1, profile="ignore"):
     """PNG or JPEG file bytes -> HxWx4 uint8 RGBA.  JPEG: Huffman decoding on the host, IDCT / upsampling / colour
     conversion on the GPU.  The bitmap is returned as stored (EXIF orientation is applied by the stitch, like the
     reference's drawWithOrientation).  scale: 1, 2, 4 or 8 - a JPEG decodes at 1 / scale of its size (scaled_size), as
-    libjpeg-turbo's decode-to-scale does, byte for byte; other file types decode at 1 / 1."""
+    libjpeg-turbo's decode-to-scale does, byte for byte; other file types decode at 1 / 1.
+    profile: 'ignore' or 'srgb' - a JPEG tagged with an ICC profile the colour contract takes is converted to sRGB on the GPU.  PNG,
+    WebP, BMP and GIF files are decoded on the host here and never reach the device: they are NOT converted by this call
+    (decode_bitmaps and decode_files_device convert every file type)."""
     buf = bytes(data)
+    _color_profile(profile)
     (d,), _ = _scales(scale, [buf], "decode_image")
     w, h, _ = image_info(buf)
     jpeg = _is_jpeg(buf)
     if jpeg and d > 1:
         w, h = scaled_size(w, h, d)
     out = np.empty((h, w, 4), np.uint8)
-    ctx = _ctx(device) if jpeg else None          # only JPEG needs the GPU
+    ctx = _ctx_color(device, profile) if jpeg else None          # only JPEG needs the GPU
     if d == 1:
         L.check(L.lib.ist_image_decode_rgba8(ctx, buf, len(buf), out.ctypes.data, out.strides[0], out.shape[0]))
     else:
@@ -760,14 +792,16 @@ def decode_image(data, device=0, scale=1):
     return out
 
 
-def decode_files_device(blobs, device=0, out=None, scale=1):
+def decode_files_device(blobs, device=0, out=None, scale=1, profile="ignore"):
     """File bytes -> bitmaps in HBM (ist_decode_files_device): returns ([HxWx4 uint8 CUDA tensors], [image dicts for
     plan/compile]).  Baseline JPEG: Huffman decoding + reconstruction on the GPU; only the file bytes cross PCIe.
     out: optional list of preallocated tensors (one spare row behind each is the caller's business).
     scale: 1, 2, 4 or 8, one for all files or one per file: a JPEG decodes at 1 / scale (scaled_size); its dict then carries
-    'bmpWidth' / 'bmpHeight' = the tensor's size beside the natural 'width' / 'height', which is what plan and compile expect."""
+    'bmpWidth' / 'bmpHeight' = the tensor's size beside the natural 'width' / 'height', which is what plan and compile expect.
+    profile: 'ignore' or 'srgb' - a file tagged with an ICC profile the colour contract takes lands converted to sRGB."""
     import torch
     n = len(blobs)
+    _color_profile(profile)
     ds, cden = _scales(scale, blobs, "decode_files_device")
     sizes = [image_info(b) for b in blobs]
     sizes = [scaled_size(w, h, d) + (o,) if d > 1 and _is_jpeg(b) else (w, h, o) for (w, h, o), d, b in zip(sizes, ds, blobs)]
@@ -785,10 +819,11 @@ def decode_files_device(blobs, device=0, out=None, scale=1):
     for i, t in enumerate(out):
         dst[i], pitch[i], rows[i] = t.data_ptr(), t.stride(0), t.shape[0]
     descs = (L.ImageDesc * n)()
+    ctx = _ctx_color(device, profile)
     if cden is None:
-        L.check(L.lib.ist_decode_files_device(_ctx(device), files, lens, n, dst, pitch, rows, descs))
+        L.check(L.lib.ist_decode_files_device(ctx, files, lens, n, dst, pitch, rows, descs))
     else:
-        L.check(L.lib.ist_decode_files_device_scaled(_ctx(device), files, lens, n, cden, dst, pitch, rows, descs))
+        L.check(L.lib.ist_decode_files_device_scaled(ctx, files, lens, n, cden, dst, pitch, rows, descs))
     imgs = [{"width": d.width, "height": d.height, "orientation": d.orientation, "opaque": bool(d.opaque), "fileSize": d.file_size} for d in descs]
     for im, d in zip(imgs, descs):
         if d.bmp_width or d.bmp_height:
@@ -828,10 +863,11 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     reconstruction on the GPU) -> plan (EXIF orientation from the file, like getImageInfo, index.js:734) -> one fused
     stitch launch -> PNG export on the GPU.  Only file bytes go in and PNG bytes come out over PCIe.
     Returns {'width','height','png'} and writes out_path when given.  The mini-program's whole onStitch: index.js:1441-1581."""
-    o = _merge(opts)
+    o = _merge(opts, color=True)
     _png_color(o["pngColor"])
     _png_filter(o["pngFilter"])
     _png_match(o["pngMatch"])
+    _color_profile(o["colorProfile"])
     n = len(paths)
     if n == 0:
         return None
@@ -841,6 +877,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     cplan, out, ln = L.Plan(), C.POINTER(C.c_uint8)(), C.c_int64(0)
     pv = _preview_arg(o)
     fn = L.lib.ist_stitch_paths_png if pv is None else L.lib.ist_stitch_paths_png_preview
+    _ctx_color(device, o["colorProfile"])
     size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
                                  *([] if pv is None else [C.byref(pv)]))), cplan)
     if size is None:
@@ -1271,7 +1308,7 @@ def _read_files(files):
     return blobs
 
 
-def decode_bitmaps(files, device=0, scale=1):
+def decode_bitmaps(files, device=0, scale=1, profile="ignore"):
     """Image files (bytes, or paths that are read here) -> [Bitmap], decoded straight into HBM by the decoder of stitch_files (baseline
     JPEG: Huffman decoding + reconstruction on the GPU).  Each bitmap's desc is what stitch_files plans with: size, EXIF orientation,
     opaque for JPEG, file_size = the file's length.  All or nothing: a file that does not decode raises StitchError('图片k解码异常: ...')
@@ -1279,8 +1316,11 @@ def decode_bitmaps(files, device=0, scale=1):
     scale: 1, 2, 4 or 8, one for all files or one per file: a JPEG is decoded at 1 / scale of its size (scaled_size; libjpeg-turbo's
     decode-to-scale, byte for byte) and held at that size - width / height stay the natural size, shape is the stored one - so a
     12 MP photo at scale 4 holds 3 MB instead of 48 MB and plans, stitches, previews and thumbnails like the full-size bitmap.  Other
-    file types decode at 1 / 1."""
-    ctx = _ctx(device)
+    file types decode at 1 / 1.
+    profile: 'ignore' (the pixels as decoded) or 'srgb': a file tagged with an ICC profile the colour contract takes (matrix/TRC RGB:
+    Display P3, Adobe RGB, ...) is converted to sRGB in place by one launch behind its decode; untagged, sRGB-tagged and unsupported
+    files stay as decoded (image_color says which a file is)."""
+    ctx = _ctx_color(device, profile)
     blobs = _read_files(files)
     n = len(blobs)
     if n == 0:
@@ -1296,11 +1336,12 @@ def decode_bitmaps(files, device=0, scale=1):
     return [Bitmap(out[i], device) for i in range(n)]
 
 
-def thumbnails_from_files(files, cell, mode="fill", orient=True, device=0):
+def thumbnails_from_files(files, cell, mode="fill", orient=True, device=0, profile="ignore"):
     """Image files (bytes or paths) -> their thumbnails for a cell (width, height), as thumbnails() returns them, without ever holding
     a full-size bitmap: every JPEG is decoded at the largest scale (decode_scale_fit) at which its stored pixels still cover its
     thumbnail, so the grid of nine 12 MP photos (index.wxml:4-22) reads a sixty-fourth of their pixels.  The bitmaps are released
-    before the call returns."""
+    before the call returns.  profile: as decode_bitmaps."""
+    _color_profile(profile)
     blobs = _read_files(files)
     if not blobs:
         return []
@@ -1310,12 +1351,52 @@ def thumbnails_from_files(files, cell, mode="fill", orient=True, device=0):
     for (w, h, o), t in zip(infos, items):
         tw, th = (t["height"], t["width"]) if orient and o >= 5 else (t["width"], t["height"])      # the thumbnail on the STORED axes
         scales.append(decode_scale_fit(w, h, max(1, tw), max(1, th)))
-    bitmaps = decode_bitmaps(blobs, device, scale=scales)
+    bitmaps = decode_bitmaps(blobs, device, scale=scales, profile=profile)
     try:
         return thumbnails(bitmaps, cell, mode, orient)
     finally:
         for b in bitmaps:
             b.close()
+
+
+def image_color(data):
+    """The colour kind of an image file (ist_image_color): 'none' (untagged), 'identity' (tagged sRGB: nothing to do), 'convert' (a
+    profile that profile='srgb' converts) or 'unsupported' (a profile the contract does not take: LUT-only, GRAY, CMYK, damaged).
+    Pure CPU."""
+    buf = bytes(data)
+    kind = C.c_int32(0)
+    L.check(L.lib.ist_image_color(buf, len(buf), C.byref(kind)))
+    return COLOR_KINDS[kind.value]
+
+
+def _icc_tables(icc):
+    buf = bytes(icc)
+    t = L.ColorTables()
+    L.check(L.lib.ist_icc_tables(buf, len(buf), C.byref(t)))
+    return t
+
+
+def icc_tables(icc):
+    """The integer tables of an ICC profile (ist_icc_tables): {'kind', 'dec': 3x256 uint16, 'mq': 3x3 int32}; dec and mq are None
+    for 'unsupported'.  Pure CPU."""
+    t = _icc_tables(icc)
+    kind = COLOR_KINDS[t.kind]
+    if kind not in ("convert", "identity"):
+        return {"kind": kind, "dec": None, "mq": None}
+    return {"kind": kind, "dec": np.ctypeslib.as_array(t.dec).astype(np.uint16), "mq": np.ctypeslib.as_array(t.mq).astype(np.int32)}
+
+
+def convert_color_device(tensor, icc, stream=None):
+    """An HxWx4 uint8 CUDA tensor (any row stride that is a multiple of 4 bytes, pixels contiguous) through the tables of the ICC
+    profile `icc` to sRGB, in place (ist_color_convert_device), asynchronous on `stream` (None: the current torch stream).  Identity
+    tables change nothing; a profile the contract does not take raises StitchError(IST_E_INVALID).  Returns the tensor."""
+    import torch
+    t = tensor
+    _check_canvas(t, "convert_color_device: ")
+    tables = _icc_tables(icc)
+    s = torch.cuda.current_stream(t.device).cuda_stream if stream is None else int(stream)
+    L.check(L.lib.ist_color_convert_device(_ctx(t.device.index), t.data_ptr(), t.stride(0), t.shape[1], t.shape[0], C.byref(tables), s))
+    return tensor
 
 
 def upload_bitmap(image, device=0):

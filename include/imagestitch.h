@@ -939,6 +939,68 @@ IST_API int ist_debug_overlap_signatures(ist_ctx* ctx, uint32_t* out, int64_t ro
  * > 1 or decoded at a reduced scale. */
 IST_API ist_bitmap* ist_bitmap_rows(ist_bitmap* b, int32_t y0, int32_t rows);
 
+/* ---- colour profiles: ICC-tagged files converted to sRGB on decode -----------------------------------------------------------
+ * A file may carry an ICC profile that says what its RGB code values mean (Display P3 for phone photos, Adobe RGB for many exports);
+ * exports are untagged, so a viewer reads them as sRGB.  With IST_COLOR_PROFILE_SRGB on a context, every bitmap the file decoders of
+ * that context leave in device memory is converted to sRGB in place, by one launch behind its decode on the same stream.  The default
+ * is IST_COLOR_PROFILE_IGNORE: every call does exactly what it did before this setting existed.  Relative colorimetric, clipping, no
+ * black-point compensation.  Alpha is copied; straight-alpha colour values are converted whatever the alpha is.
+ * THE CONTRACT (restated in numpy by tests/icc_reference.py; the GPU agrees with it byte for byte).  All integer; '>>' is an
+ * arithmetic shift of a 64-bit value, '/' and '%' on non-negative integers.
+ *   Where the profile is read.  JPEG: the APP2 segments in front of the first scan that begin "ICC_PROFILE\0", seq (from 1), count,
+ *     joined in seq order; a missing chunk, a seq used twice, chunks that disagree on count, seq 0 or seq > count: no profile.  PNG: iCCP
+ *     (name, NUL, method 0, a zlib stream of at most 4 MiB inflated) in front of the first IDAT; else an sRGB chunk means IDENTITY; gAMA /
+ *     cHRM / cICP alone: no profile.  WebP: the ICCP chunk of a file with a VP8X chunk.  BMP, GIF: none.  A damaged profile never fails a
+ *     decode.
+ *   Which profiles are taken (everything else is IST_COLOR_UNSUPPORTED and the pixels stay as decoded).  The header's size field is
+ *     >= 132 and <= the bytes given, and bounds everything; 'acsp' at byte 36; data colour space 'RGB ', PCS 'XYZ '; the tag table lies
+ *     inside; the FIRST tag of each of rXYZ, gXYZ, bXYZ (type 'XYZ ', three s15Fixed16) and rTRC, gTRC, bTRC is used and lies inside with
+ *     its whole body.  A TRC is 'curv' (count 0: identity; count 1: a u8Fixed8 gamma > 0; count n >= 2: n u16 entries) or 'para' with
+ *     function type 0 .. 4 (parameters s15Fixed16, read as int / 65536.0; g > 0; a != 0 for types 1 and 2).  Matrix/TRC tags are used
+ *     even when A2B0 is present; wtpt and chad are not read (the colorants are PCS-relative).  A matrix entry outside int32:
+ *     UNSUPPORTED.
+ *   dec[c][v], c = r, g, b, v = 0 .. 255, uint16.  A function f: clamp(floor(65535 f(v / 255.0) + 0.5), 0, 65535), f in IEEE double,
+ *     powers by the C library's pow, B = max(a x + b, 0):
+ *       gamma and para 0: x^g        para 1: x >= -b / a ? B^g : 0        para 2: x >= -b / a ? B^g + c : c
+ *       para 3: x >= d ? B^g : c x   para 4: x >= d ? B^g + e : c x + f
+ *     curv count 0: 257 v.  A table t[0 .. n-1]: p = v (n - 1), i = p / 255, r = p % 255,
+ *       dec = (t[i] (255 - r) + t[min(i + 1, n - 1)] r + 127) / 255.
+ *   Mq (Q16) = (INV C + 2^23) >> 24; C = the colorants as s15.16 integers, rows X, Y, Z, columns r, g, b; INV = the inverse of the sRGB
+ *     colorants (D50) in Q24:  {{52584397, -27133356, -8233164}, {-16421465, 32147857, 561266}, {1207600, -3841813, 23584544}}
+ *     (the sRGB colorants {{28576, 25239, 9375}, {14581, 46983, 3972}, {912, 6361, 46787}} give 65536 I exactly).
+ *   Per pixel: lin_j = dec[j][v_j];  o_i = clamp((sum_j Mq[i][j] lin_j + 2^15) >> 16, 0, 65535);  the output code of channel i is the
+ *     number of c in 1 .. 255 with T[c] <= o_i, T[c] = ceil(65535 s((c - 0.5) / 255)), s(x) = x <= 0.04045 ? x / 12.92 :
+ *     ((x + 0.055) / 1.055)^2.4 - a fixed table, carried as a literal (csrc/ist_icc.h; tools/gen_icc_encode_table.py).
+ *   Kinds: NONE (no profile); IDENTITY (Mq == 65536 I and every code of every channel maps to itself: nothing is launched); CONVERT;
+ *     UNSUPPORTED. */
+enum { IST_COLOR_PROFILE_IGNORE = 0, IST_COLOR_PROFILE_SRGB = 1 };
+enum { IST_COLOR_NONE = 0, IST_COLOR_IDENTITY = 1, IST_COLOR_CONVERT = 2, IST_COLOR_UNSUPPORTED = 3 };
+typedef struct ist_color_tables {
+  int32_t kind;               /* IST_COLOR_* */
+  int32_t mq[3][3];           /* Q16; rows = output r, g, b */
+  uint16_t dec[3][256];
+} ist_color_tables;
+/* The setting of a context, read by ist_bitmaps_decode[_scaled], ist_decode_files_device[_scaled], ist_stitch_files_png /
+ * ist_stitch_paths_png (+ _preview; an image reconstructed straight into its box of the canvas is converted there) and by the JPEG
+ * branch of ist_image_decode_rgba8[_scaled] / ist_jpeg_decode_rgba8, whose pixels pass through device memory.  PNG, WebP, BMP and GIF
+ * files of ist_image_decode_rgba8 are decoded on the host into the caller's buffer and never reach the device: they are NOT converted
+ * there (decode them with ist_bitmaps_decode or ist_decode_files_device).  ist_bitmap_upload and raw host pixels are never converted.
+ * IST_E_NO_CONTEXT for a NULL context, IST_E_INVALID for any other value. */
+IST_API int ist_ctx_set_color_profile(ist_ctx* ctx, int profile);
+/* *kind = the IST_COLOR_* of a file (by signature: JPEG, PNG, WebP; anything else NONE).  Host only, no context.  IST_E_INVALID: a
+ * NULL argument or len <= 0. */
+IST_API int ist_image_color(const uint8_t* file, int64_t len, int32_t* kind);
+/* an ICC profile -> out->kind and, for CONVERT and IDENTITY, dec and mq (zeroed otherwise).  Host only.  Returns the kind;
+ * IST_E_INVALID for a NULL argument or len <= 0. */
+IST_API int ist_icc_tables(const uint8_t* icc, int64_t len, ist_color_tables* out);
+/* the conversion on caller-owned device memory: the w x h box of RGBA8 at ptr (4-byte aligned; rows pitch bytes apart, a multiple of 4
+ * that is >= 4 w), in place, asynchronous on `stream` (hipStream_t, NULL = default stream); no byte outside the box is written.  The
+ * tables travel by value with the launch.  IDENTITY tables launch nothing.  IST_E_NO_CONTEXT; IST_E_INVALID: NULL ptr or tables,
+ * w or h < 1, a short or unaligned pitch, an unaligned ptr, tables whose kind is neither CONVERT nor IDENTITY. */
+IST_API int ist_color_convert_device(ist_ctx* ctx, void* ptr, size_t pitch, int64_t w, int64_t h, const ist_color_tables* tables, void* stream);
+/* launches of the conversion kernel in this process so far */
+IST_API int64_t ist_debug_color_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@
  *   encodeJpeg(data, width, height, quality, subsampling) -> Buffer;  stitch / stitchBitmaps(..., filter, {quality, subsampling})
  *       resolve {width,height,jpeg} (ist_stitch_jpeg / ist_stitch_bitmaps_jpeg: asPng given as an object is the JPEG export)
  *   deviceCount(), lastError(), abiVersion()
- *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[], scales?: number[]) -> Promise<handle[]>;
+ *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[], scales?: number[], colorProfile?: number) -> Promise<handle[]>;
+ *   imageColor(file: Buffer) -> 0 .. 3 (IST_COLOR_*);
  *     decodeScaleFit(width, height, minWidth, minHeight) -> 1 | 2 | 4 | 8;
  *   bitmapDesc(h) -> {width,height,orientation,bmpWidth,bmpHeight,opaque,fileSize};  bitmapDownload(h) -> Buffer;  bitmapRelease(h);
  *   stitchBitmaps(handles, direction, mode, gap, limits, filter, asPng) -> Promise (as stitch);  stitchBitmapsSync(...same...);
@@ -92,6 +93,13 @@ static ist_ctx* ctx_or_throw(napi_env env) {
 
 /* ---- reading what the caller brings -------------------------------------------------------------------------------------- */
 /* the call's arguments, up to cap of them (those not given read as undefined); 0 with TypeError(usage) pending below `need` */
+/* The colour setting is the context's (ist_ctx_set_color_profile), and jobs run on pool threads: a call that decodes files holds this
+ * lock from setting its own value to the end of its library call, and leaves IST_COLOR_PROFILE_IGNORE behind - so no call ever sees
+ * another call's value, and every entry point without the option does what it always did. */
+static pthread_mutex_t g_color_mu = PTHREAD_MUTEX_INITIALIZER;
+static void color_begin(ist_ctx* ctx, int profile) { pthread_mutex_lock(&g_color_mu); if (ctx) ist_ctx_set_color_profile(ctx, profile); }
+static void color_end(ist_ctx* ctx) { if (ctx) ist_ctx_set_color_profile(ctx, IST_COLOR_PROFILE_IGNORE); pthread_mutex_unlock(&g_color_mu); }
+
 static int args_of(napi_env env, napi_callback_info info, size_t need, size_t cap, napi_value* argv, const char* usage) {
   size_t argc = cap;
   if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) == napi_ok && argc >= need) return 1;
@@ -497,6 +505,7 @@ typedef struct {
   strip_t s;
   out_kind out; int quality, subsampling; /* OUT_JPEG: {quality, subsampling} */
   int devices[64]; int ndev, split;       /* opts.devices / opts.split: ndev 0 = the process-wide single context */
+  int profile;                            /* SRC_FILES: IST_COLOR_PROFILE_* of opts.colorProfile */
   int want_preview; ist_preview pv;       /* OUT_PNG with {preview: {width, height}}: the canvas shrunk to fit that box, beside the file */
   ist_plan plan; uint8_t* block; int64_t file_len;    /* the canvas, or file_len bytes of its file */
 } stitch_job;
@@ -506,7 +515,12 @@ static int stitch_run(ist_ctx* ctx, job* h) {
   const strip_t* s = &j->s;
   const images_t* im = &j->im;
   ist_preview* pv = j->want_preview ? &j->pv : NULL;
-  if (j->src == SRC_FILES) return ist_stitch_files_png_preview(ctx, j->files.ptr, j->files.len, j->files.n, STRIP_ARGS(s), &j->plan, &j->block, &j->file_len, pv);
+  if (j->src == SRC_FILES) {
+    color_begin(ctx, j->profile);
+    const int rc = ist_stitch_files_png_preview(ctx, j->files.ptr, j->files.len, j->files.n, STRIP_ARGS(s), &j->plan, &j->block, &j->file_len, pv);
+    color_end(ctx);
+    return rc;
+  }
   if (j->src == SRC_BITMAPS)
     return j->out == OUT_JPEG ? ist_stitch_bitmaps_jpeg(ctx, j->bm.b, j->bm.n, STRIP_ARGS(s), j->quality, j->subsampling, &j->plan, &j->block, &j->file_len)
          : j->out == OUT_PNG  ? ist_stitch_bitmaps_png_preview(ctx, j->bm.b, j->bm.n, STRIP_ARGS(s), &j->plan, &j->block, &j->file_len, pv)
@@ -584,16 +598,18 @@ static job* stitch_bitmaps_parse(napi_env env, napi_callback_info info) {
 static napi_value js_stitch_bitmaps(napi_env env, napi_callback_info info) { return job_queue(env, stitch_bitmaps_parse(env, info), "imagestitch.stitchBitmaps"); }
 static napi_value js_stitch_bitmaps_sync(napi_env env, napi_callback_info info) { return job_now(env, stitch_bitmaps_parse(env, info)); }
 
-/* stitchFiles(files: Buffer[], direction, mode, gap, limits, filter, previewWidth, previewHeight) -> Promise<{width,height,png,plan}>
- * the device-resident pipeline (ist_stitch_files_png): only file bytes go in, only PNG bytes come out */
+/* stitchFiles(files: Buffer[], direction, mode, gap, limits, filter, previewWidth, previewHeight, colorProfile) -> Promise<{width,height,png,plan}>
+ * the device-resident pipeline (ist_stitch_files_png): only file bytes go in, only PNG bytes come out.  colorProfile: IST_COLOR_PROFILE_*
+ * (absent: ignore), set on the context for this call alone */
 static napi_value js_stitch_files(napi_env env, napi_callback_info info) {
-  napi_value argv[8];
-  if (!args_of(env, info, 6, 8, argv, "stitchFiles(files, direction, mode, gap, limits, filter, previewWidth, previewHeight)")) return NULL;
+  napi_value argv[9];
+  if (!args_of(env, info, 6, 9, argv, "stitchFiles(files, direction, mode, gap, limits, filter, previewWidth, previewHeight, colorProfile)")) return NULL;
   stitch_job* j = stitch_job_new(SRC_FILES);
   if (!files_parse(env, argv[0], "files must be an array of Buffers", &j->files)) { stitch_free(env, &j->h); return NULL; }
   strip_parse(env, argv + 1, &j->s);
   j->out = OUT_PNG;
   preview_parse(env, argv[6], argv[7], j);
+  j->profile = int_of(env, argv[8], IST_COLOR_PROFILE_IGNORE);
   return job_queue(env, &j->h, "imagestitch.stitchFiles");
 }
 
@@ -782,7 +798,9 @@ static napi_value js_decode_image(napi_env env, napi_callback_info info) {
   if (is_jpeg && !ctx) return NULL;
   void* out_data = NULL; napi_value buf;
   if (napi_create_buffer(env, (size_t)w * (size_t)h * 4, &out_data, &buf) != napi_ok) return throw_oom(env);
+  color_begin(ctx, IST_COLOR_PROFILE_IGNORE);            /* (never inside another call's setting) */
   rc = ist_image_decode_rgba8(ctx, p, (int64_t)len, (uint8_t*)out_data, (size_t)w * 4, (int64_t)h);
+  color_end(ctx);
   if (rc < 0) return throw_ist(env, rc);
   napi_value o = pixels_to_js(env, w, h, buf);
   set_num(env, o, "orientation", orient ? orient : 1);
@@ -861,13 +879,18 @@ static napi_value js_upload_bitmap(napi_env env, napi_callback_info info) {
   return h;
 }
 
-/* decodeBitmaps(files: Buffer[], scales?: number[]) -> Promise<handle[]> (ist_bitmaps_decode_scaled: all or nothing; scales = one
- * decode denominator per file, 1 / 2 / 4 / 8, checked by the library; absent: all 1, which is ist_bitmaps_decode) */
-typedef struct { job h; files_t files; int32_t* denom; ist_bitmap** out; } decode_job;
+/* decodeBitmaps(files: Buffer[], scales?: number[], colorProfile?: number) -> Promise<handle[]> (ist_bitmaps_decode_scaled: all or
+ * nothing; scales = one decode denominator per file, 1 / 2 / 4 / 8, checked by the library; absent: all 1, which is ist_bitmaps_decode;
+ * colorProfile = IST_COLOR_PROFILE_*, absent: ignore, set on the context for this call alone) */
+typedef struct { job h; files_t files; int32_t* denom; int profile; ist_bitmap** out; } decode_job;
 
 static int decode_run(ist_ctx* ctx, job* h) {
   decode_job* j = (decode_job*)h;
-  return j->files.n ? ist_bitmaps_decode_scaled(ctx, j->files.ptr, j->files.len, j->files.n, j->denom, j->out) : IST_OK;
+  if (!j->files.n) return IST_OK;
+  color_begin(ctx, j->profile);
+  const int rc = ist_bitmaps_decode_scaled(ctx, j->files.ptr, j->files.len, j->files.n, j->denom, j->out);
+  color_end(ctx);
+  return rc;
 }
 static napi_value decode_result(napi_env env, job* h) {
   decode_job* j = (decode_job*)h;
@@ -889,9 +912,9 @@ static void decode_free(napi_env env, job* h) {
 static const job_kind DECODE = {decode_run, decode_result, decode_free};
 
 static napi_value js_decode_bitmaps(napi_env env, napi_callback_info info) {
-  static const char usage[] = "decodeBitmaps(files: Buffer[], scales?: number[])";
-  napi_value argv[2]; files_t files; int32_t* denom = NULL; uint32_t ns = 0;
-  if (!args_of(env, info, 1, 2, argv, usage) || !files_parse(env, argv[0], usage, &files)) return NULL;
+  static const char usage[] = "decodeBitmaps(files: Buffer[], scales?: number[], colorProfile?: number)";
+  napi_value argv[3]; files_t files; int32_t* denom = NULL; uint32_t ns = 0;
+  if (!args_of(env, info, 1, 3, argv, usage) || !files_parse(env, argv[0], usage, &files)) return NULL;
   if (!is_nullish(env, argv[1])) {
     if (!array_len(env, argv[1], &ns) || ns != (uint32_t)files.n) { files_free(env, &files); return throw_type(env, "decodeBitmaps: scales must hold one number per file"); }
     denom = (int32_t*)calloc(ns ? ns : 1, sizeof *denom);
@@ -901,9 +924,19 @@ static napi_value js_decode_bitmaps(napi_env env, napi_callback_info info) {
     }
   }
   decode_job* j = (decode_job*)calloc(1, sizeof *j);
-  j->h.kind = &DECODE; j->files = files; j->denom = denom;
+  j->h.kind = &DECODE; j->files = files; j->denom = denom; j->profile = int_of(env, argv[2], IST_COLOR_PROFILE_IGNORE);
   j->out = (ist_bitmap**)calloc(files.n ? files.n : 1, sizeof(ist_bitmap*));
   return job_queue(env, &j->h, "imagestitch.decodeBitmaps");
+}
+
+/* imageColor(file: Buffer) -> 0 .. 3, the IST_COLOR_* kind of the file's ICC profile (ist_image_color: pure CPU) */
+static napi_value js_image_color(napi_env env, napi_callback_info info) {
+  napi_value argv[1], out; const uint8_t* p; size_t len; int32_t kind = 0;
+  if (!args_of(env, info, 1, 1, argv, "imageColor(buffer)")) return NULL;
+  if (!bytes_of(env, argv[0], &p, &len)) return throw_type(env, "imageColor expects a Buffer / Uint8Array");
+  const int rc = ist_image_color(p, (int64_t)len, &kind);
+  if (rc < 0) return throw_ist(env, rc);
+  return napi_create_int32(env, kind, &out) == napi_ok ? out : NULL;
 }
 
 /* decodeScaleFit(width, height, minWidth, minHeight) -> 1 | 2 | 4 | 8 (ist_decode_scale_fit: pure CPU) */
@@ -1149,6 +1182,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_default, NULL},
       {"uploadBitmap", NULL, js_upload_bitmap, NULL, NULL, NULL, napi_default, NULL},
       {"decodeBitmaps", NULL, js_decode_bitmaps, NULL, NULL, NULL, napi_default, NULL},
+      {"imageColor", NULL, js_image_color, NULL, NULL, NULL, napi_default, NULL},
       {"decodeScaleFit", NULL, js_decode_scale_fit, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDownload", NULL, js_bitmap_download, NULL, NULL, NULL, napi_default, NULL},

@@ -2,6 +2,7 @@
 /// <reference types="node" />
 export type Direction = 'vertical' | 'horizontal';
 export type StitchMode = 'min' | 'max' | 'original';
+export type ColorProfile = 'ignore' | 'srgb';
 export interface StitchImage {
   width: number;            // naturalWidth  (pages/index/index.js:724-739)
   height: number;           // naturalHeight
@@ -18,6 +19,7 @@ export interface StitchOptions {
   edgeAA?: boolean;                         // anti-alias fractional rectangle edges (ctx.scale(superSample), unrounded cursor); default: true iff `platform` is given
   onProgress?: (percent: number) => void;   // stitchProgress checkpoints (index.js:1193-1611)
   pngLevel?: 0 | 1;                         // PNG export form: 0 stored, 1 compressed on the GPU (process-wide once set)
+  colorProfile?: ColorProfile;              // stitchFiles only (decodeBitmaps takes its own): 'srgb' converts files tagged with a matrix/TRC ICC profile (Display P3, Adobe RGB) to sRGB on the GPU behind their decode; default 'ignore'
   pngMatch?: 'run' | 'window';              // PNG matches: 'run' runs inside a 64-byte span (default), 'window' a chunk also copies from its earlier spans, found on the GPU - never larger, half the bytes on rendered text, a slower encoder, pngLevel 1 only (process-wide once set)
   pngFilter?: 'paeth' | 'adaptive';         // PNG row filters: 'paeth' type 4 on every row (default), 'adaptive' a type per row chosen on the GPU - smaller files, pngLevel 1 only (process-wide once set)
   pngColor?: 'rgba' | 'rgb';                // PNG colour form: 'rgba' colour type 6 (default), 'rgb' colour type 2 - alpha is not read, pngLevel 1 only (process-wide once set; the Canvas shim always exports RGBA)
@@ -74,7 +76,9 @@ export class Bitmap {
   release(): void;          // idempotent; any other use afterwards throws
 }
 /** scale: 1, 2, 4 or 8 (one for all files or one per file): a JPEG is decoded at 1 / scale and kept at that size; other types at 1 / 1 */
-export function decodeBitmaps(files: (Uint8Array | string)[], opts?: { scale?: 1 | 2 | 4 | 8 | (1 | 2 | 4 | 8)[] }): Promise<Bitmap[]>;
+export function decodeBitmaps(files: (Uint8Array | string)[], opts?: { scale?: 1 | 2 | 4 | 8 | (1 | 2 | 4 | 8)[]; colorProfile?: ColorProfile }): Promise<Bitmap[]>;
+// the colour kind of a file's ICC profile: untagged, tagged sRGB, what colorProfile 'srgb' converts, or a profile the contract does not take
+export function imageColor(file: Uint8Array | string): 'none' | 'identity' | 'convert' | 'unsupported';
 /** the largest scale at which a width x height file still decodes to at least minWidth x minHeight pixels (1 if none does) */
 export function decodeScaleFit(width: number, height: number, minWidth: number, minHeight: number): 1 | 2 | 4 | 8;
 export function uploadBitmap(image: StitchImage): Bitmap;

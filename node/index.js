@@ -11,7 +11,7 @@
  *   encodeJpeg(data, width, height, {quality, subsampling, optimize}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   stitchJpegBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, jpeg, plan} | null)[]>  (one GPU, many JPEG files)
- *   decodeBitmaps(files, {scale?}) -> Promise<Bitmap[]>,  decodeScaleFit(w, h, minW, minH) -> 1 | 2 | 4 | 8,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
+ *   decodeBitmaps(files, {scale?, colorProfile?}) -> Promise<Bitmap[]>,  imageColor(file) -> 'none' | 'identity' | 'convert' | 'unsupported',  decodeScaleFit(w, h, minW, minH) -> 1 | 2 | 4 | 8,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
  *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
  *       that box (the redraw into the preview node, index.js:1597-1603), reduced in GPU memory beside the export;
@@ -44,7 +44,7 @@ const DIRECTION = { vertical: 0, horizontal: 1 };
 const MODE = { min: 0, max: 1, original: 2 };
 const FILTER = { nearest: 0, bilinear: 1, area: 2, cubic: 3 };
 const PLATFORM = { other: 0, devtools: 0, windows: 0, mac: 0, ios: 1, android: 2 };
-const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'devices', 'split', 'preview', 'overlap'];
+const KNOWN = ['mode', 'gap', 'filter', 'platform', 'maxSide', 'maxPixels', 'superSample', 'onProgress', 'edgeAA', 'pngLevel', 'pngColor', 'pngFilter', 'pngMatch', 'devices', 'split', 'preview', 'overlap', 'colorProfile'];
 const SPLIT = { image: 0, band: 1, rows: 2, auto: 3 };
 const FILTER_EDGE_AA = 0x100;    // IST_FILTER_EDGE_AA: anti-alias fractional rectangle edges by area coverage
 
@@ -68,9 +68,21 @@ function limitsOf(opts) {
 function edgeAA(o) { return (o.edgeAA === undefined || o.edgeAA === null) ? (o.platform !== undefined && o.platform !== null) : !!o.edgeAA; }
 
 const OVERLAP_NEEDS = 'option overlap applies to stitch / stitchSync / stitchPng / stitchJpeg of a vertical strip of Bitmaps (uploadBitmap / decodeBitmaps): the overlaps are searched where the pixels are resident';
-function args(images, direction, opts) {
+// opts.colorProfile / decodeBitmaps' colorProfile: 'ignore' = the pixels as decoded (default), 'srgb' = a file tagged with a matrix/TRC
+// ICC profile (Display P3, Adobe RGB) is converted to sRGB on the GPU behind its decode (include/imagestitch.h "colour profiles").
+// The value travels with its native call; an unknown one is a TypeError before any native call.
+const COLOR_PROFILE = { ignore: 0, srgb: 1 };      // IST_COLOR_PROFILE_IGNORE / IST_COLOR_PROFILE_SRGB
+const COLOR_KIND = ['none', 'identity', 'convert', 'unsupported'];      // IST_COLOR_*
+const COLOR_NEEDS = 'option colorProfile applies to stitchFiles and decodeBitmaps: a profile comes with a file, raw pixels carry none';
+function colorProfileOf(opts) {
+  if (!opts || opts.colorProfile === undefined || opts.colorProfile === null) return COLOR_PROFILE.ignore;
+  if (typeof opts.colorProfile !== 'string' || !Object.prototype.hasOwnProperty.call(COLOR_PROFILE, opts.colorProfile)) throw new TypeError("colorProfile must be 'ignore' or 'srgb'");
+  return COLOR_PROFILE[opts.colorProfile];
+}
+function args(images, direction, opts, files) {
   const o = opts || {};
   for (const k of Object.keys(o)) if (!KNOWN.includes(k)) throw new TypeError('unknown stitch option ' + k);
+  if (!files && o.colorProfile !== undefined && o.colorProfile !== null) throw new TypeError(COLOR_NEEDS);
   if (o.overlap !== undefined && o.overlap !== null) throw new TypeError(OVERLAP_NEEDS);      // (withOverlap takes the option out where it applies)
   if (!(direction in DIRECTION)) throw new TypeError("direction must be 'vertical' or 'horizontal'");
   const mode = o.mode || 'min';                      // `|| 'min'` (index.js:1257)
@@ -152,9 +164,12 @@ function bitmapHandles(images, opts) {
  *  file that does not decode rejects with '图片k解码异常: ...' and no bitmap is kept.
  *  opts.scale: 1, 2, 4 or 8, one for all files or one per file - a JPEG is decoded at 1 / scale of its size (libjpeg-turbo's
  *  decode-to-scale, byte for byte) and kept at that size: width / height stay the natural size, bmpWidth / bmpHeight are the stored
- *  one, and stitch, previews and thumbnails take the bitmap as it is.  Other file types decode at 1 / 1. */
+ *  one, and stitch, previews and thumbnails take the bitmap as it is.  Other file types decode at 1 / 1.
+ *  opts.colorProfile: 'ignore' (default) or 'srgb' - a file tagged with an ICC profile the colour contract takes lands converted to sRGB;
+ *  untagged, sRGB-tagged and unsupported files stay as decoded (imageColor says which a file is). */
 async function decodeBitmaps(files, opts) {
-  if (!Array.isArray(files)) throw new TypeError('decodeBitmaps(files: (Uint8Array | string)[], {scale?})');
+  if (!Array.isArray(files)) throw new TypeError('decodeBitmaps(files: (Uint8Array | string)[], {scale?, colorProfile?})');
+  const profile = colorProfileOf(opts);
   const scale = opts === undefined || opts === null ? undefined : opts.scale;
   let scales;
   if (scale !== undefined && scale !== null) {
@@ -164,9 +179,12 @@ async function decodeBitmaps(files, opts) {
   const fs = require('fs');
   const bufs = files.map((f) => (typeof f === 'string' ? fs.readFileSync(f) : f));
   if (!bufs.length) return [];
-  const handles = await native.decodeBitmaps(bufs, scales);
+  const handles = await native.decodeBitmaps(bufs, scales, profile);
   return handles.map((h) => new Bitmap(MADE_HERE, h));
 }
+/** The colour kind of an image file: 'none' (untagged), 'identity' (tagged sRGB), 'convert' (what colorProfile 'srgb' converts) or
+ *  'unsupported' (a profile the contract does not take: LUT-only, GRAY, CMYK, damaged).  Pure CPU. */
+function imageColor(file) { return COLOR_KIND[native.imageColor(typeof file === 'string' ? require('fs').readFileSync(file) : file)]; }
 /** The largest scale in {1, 2, 4, 8} at which a width x height file still decodes to at least minWidth x minHeight pixels (1 if none
  *  does): what to pass as decodeBitmaps' scale for a file that is only ever shown that small.  Pure CPU. */
 function decodeScaleFit(width, height, minWidth, minHeight) { return native.decodeScaleFit(width, height, minWidth, minHeight); }
@@ -436,15 +454,16 @@ function decodeImage(file) { return native.decodeImage(file); }
  *  outPath when given. A file that does not decode rejects with '图片N解码异常' like index.js:1512-1514. */
 async function stitchFiles(paths, direction, opts, outPath) {
   const fs = require('fs');
-  const a = args([], direction, opts);
+  const a = args([], direction, opts, true);
   const pv = previewArgs(opts);
   pngColorOf(opts);
   pngFilterOf(opts);
   pngMatchOf(opts);
+  const profile = colorProfileOf(opts);
   if (!paths || !paths.length) return null;
   const files = paths.map((p) => fs.readFileSync(p));
   // one native call: Huffman / inflate on host threads, reconstruction + stitch + PNG on the GPU, buffers stay in HBM
-  const res = await withProgress(opts, () => { pngForm(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5], ...pv); });
+  const res = await withProgress(opts, () => { pngForm(opts); return native.stitchFiles(files, a[1], a[2], a[3], a[4], a[5], pv[0], pv[1], profile); });
   if (res && outPath) fs.writeFileSync(outPath, res.png);
   return res;
 }
@@ -457,4 +476,4 @@ function plan(images, direction, opts) {
 }
 
 module.exports = { stitch: withOverlap(stitch), stitchSync: withOverlapSync(stitchSync), stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng: withOverlap(stitchPng), stitchJpeg: withOverlap(stitchJpeg), stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
-                   decodeBitmaps, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, findOverlaps, findOverlapsSync, overlapRows, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+                   decodeBitmaps, imageColor, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, findOverlaps, findOverlapsSync, overlapRows, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "imagestitch.h"
+#include "ist_icc.h"
 #include "ist_jpeg.h"
 #include "ist_webp.h"
 
@@ -21,6 +22,7 @@ static uint32_t rnd() { s_rng ^= s_rng << 13; s_rng ^= s_rng >> 7; s_rng ^= s_rn
 static void one(const std::vector<uint8_t>& f, long* ok, long* bad) {
   const uint8_t* p = f.data(); const int64_t n = int64_t(f.size());
   int32_t w = 0, h = 0, o = 0; int rc;
+  { ist_color_tables t; const int kind = ist::image_color_tables(p, n, &t); if (kind < IST_COLOR_NONE || kind > IST_COLOR_UNSUPPORTED || t.kind != kind) abort(); }   // the profile walk + parse: any file, never an error
   if (n >= 2 && p[0] == 0xFF && p[1] == 0xD8) {
     ist::JpegImage J;
     rc = ist::jpeg_parse_and_entropy_decode(p, n, &J, true);

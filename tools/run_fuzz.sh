@@ -4,6 +4,7 @@
 #   tools/run_fuzz.sh compile ITERS               random + hostile op lists through the op-list compiler, invariants checked
 #   tools/run_fuzz.sh jpegbatch ITERS [SEED]      random batches through the rounds, header blob and piece records of the batched JPEG export
 #   tools/run_fuzz.sh jpegoptimize ITERS [SEED]   random + adversarial symbol counts through the optimal-table builder and the DHT / header writer
+#   tools/run_fuzz.sh icc ITERS [SEED]            random + adversarial ICC profiles, bare and inside JPEG / PNG / WebP containers, through the colour-profile parser
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); C=$ROOT/imagestitching_amd/csrc
 OUT=${IST_FUZZ_BIN:-/tmp/ist_fuzz}
@@ -18,10 +19,13 @@ elif [ "$1" = jpegbatch ]; then
 elif [ "$1" = jpegoptimize ]; then
   shift
   g++ $FLAGS "$HERE/check_jpeg_optimize_host.cpp" "$C/ist_jpeg_enc_host.cpp" -o "$OUT"
+elif [ "$1" = icc ]; then
+  shift
+  g++ $FLAGS "$HERE/check_icc_host.cpp" "$C/ist_icc.cpp" "$C/ist_png_decode.cpp" "$C/ist_image_misc.cpp" "$C/ist_jpeg.cpp" "$C/ist_webp.cpp" "$C/ist_webp_vp8.cpp" "$C/ist_plan.cpp" -lz -o "$OUT"
 else
   # (IST_FUZZ_REUSE=1: keep a binary that is already there - the tests build the harness once per session)
   if [ -z "$IST_FUZZ_REUSE" ] || [ ! -x "$OUT" ]; then
-    g++ $FLAGS "$HERE/fuzz_decoders.cpp" "$C/ist_png_decode.cpp" "$C/ist_image_misc.cpp" "$C/ist_jpeg.cpp" "$C/ist_webp.cpp" "$C/ist_webp_vp8.cpp" "$C/ist_plan.cpp" -lz -o "$OUT"
+    g++ $FLAGS "$HERE/fuzz_decoders.cpp" "$C/ist_icc.cpp" "$C/ist_png_decode.cpp" "$C/ist_image_misc.cpp" "$C/ist_jpeg.cpp" "$C/ist_webp.cpp" "$C/ist_webp_vp8.cpp" "$C/ist_plan.cpp" -lz -o "$OUT"
   fi
 fi
 "$OUT" "$@"
