@@ -205,6 +205,7 @@ struct Pipeline {
   int64_t* out_len;                       // PNG or JPEG files out (NULL: canvases)
   const int* quality = nullptr;           // JPEG files out: per request (NULL: PNG)
   const int* subsampling = nullptr;
+  PngForm png;                            // PNG files out: the form of the call
   std::vector<JobPtr> jobs[2];            // the jobs whose tables live in half 0 / 1
   bool used[2] = {false, false};
   int next = 0;
@@ -326,9 +327,7 @@ struct Pipeline {
       const int rc = png_batch_check(files[q], idx[q]);
       if (rc) { const std::string why = g_last_error; return fail(rc, "request " + std::to_string(idx[q]) + ": " + why); }
     }
-    int rc = ctx_png_form_check(ctx);
-    if (rc) return rc;
-    rc = ctx->png_level > 0 ? png_encode_batch_deflate(ctx, files, ctx->stream, true) : png_encode_batch_stored(ctx, files, ctx->stream, true);
+    const int rc = png.compressed() ? png_encode_batch_deflate(ctx, png, files, ctx->stream, true) : png_encode_batch_stored(ctx, png, files, ctx->stream, true);
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) {
       const size_t len = static_cast<size_t>(files[q].len);
@@ -371,9 +370,9 @@ struct Pipeline {
   }
 };
 
-// ist_stitch_rgba8_batch (out_len NULL), ist_stitch_png_batch and (quality, subsampling given) ist_stitch_jpeg_batch
+// ist_stitch_rgba8_batch (out_len NULL), ist_stitch_png_batch (png: its form) and (quality, subsampling given) ist_stitch_jpeg_batch
 int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_pixels, int64_t* out_len,
-                 const int* quality = nullptr, const int* subsampling = nullptr) {
+                 const int* quality = nullptr, const int* subsampling = nullptr, const PngForm& png = {}) {
   const size_t n = static_cast<size_t>(n_reqs);
   for (size_t k = 0; k < n; ++k) { out_pixels[k] = nullptr; std::memset(&out_plans[k], 0, sizeof(ist_plan)); if (out_len) out_len[k] = 0; }
   auto release = [&]() {
@@ -405,9 +404,9 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
     } else if (out_len) {                                 // + its file, and at level 1 its chunk slots (~1.01 x the canvas)
       const int64_t cw = out_plans[k].canvas_w, ch = out_plans[k].canvas_h;
       bytes[k] += static_cast<size_t>(ist_png_bound(cw, ch));
-      // (the RGBA chunk count whatever the context's colour form: the RGB form never has more chunks, and a budget that does not depend
-      // on the form cuts the same sub-batches for both)
-      if (ctx->png_level > 0) bytes[k] += static_cast<size_t>(png_deflate_chunks(cw, ch) * png_deflate_slot_bytes());
+      // (the RGBA chunk count whatever the call's colour form: the RGBA count is the documented upper bound for both - the RGB form never
+      // has more chunks - and a budget that does not depend on the colour cuts the same sub-batches for both)
+      if (png.compressed()) bytes[k] += static_cast<size_t>(png_deflate_chunks(cw, ch) * png_deflate_slot_bytes());
     }
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
@@ -417,7 +416,7 @@ int stitch_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_p
   if (rc) { release(); return rc; }
   // sub-batches: consecutive requests while their device bytes fit the budget, and at most kMaxBatchJobs of them
   Pipeline pipe(ctx, reqs, ops, n_ops, out_plans, out_pixels, out_len);
-  pipe.quality = quality; pipe.subsampling = subsampling;
+  pipe.quality = quality; pipe.subsampling = subsampling; pipe.png = png;
   std::vector<int> idx;
   size_t held = 0;
   const size_t budget = sub_batch_bytes();
@@ -446,8 +445,9 @@ int ist_stitch_rgba8_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_r
 int ist_stitch_png_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, ist_plan* out_plans, uint8_t** out_png, int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (n_reqs < 0 || (n_reqs > 0 && (!reqs || !out_plans || !out_png || !out_len))) return fail(IST_E_INVALID, "ist_stitch_png_batch: NULL argument");
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
-  return stitch_batch(ctx, reqs, n_reqs, out_plans, out_png, out_len);
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  { const int rc = form.check(); if (rc) return rc; }
+  return stitch_batch(ctx, reqs, n_reqs, out_plans, out_png, out_len, nullptr, nullptr, form);
 }
 
 int ist_stitch_jpeg_batch(ist_ctx* ctx, const ist_stitch_request* reqs, int n_reqs, const int* quality, const int* subsampling,

@@ -85,7 +85,8 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   PlanGuard pg{out_plan};
   const int64_t cw = out_plan->canvas_w, ch = out_plan->canvas_h;
   if (jpeg) { rc = jpeg_check_export("ist_stitch_bitmaps_jpeg", cw, ch, jpeg[0], jpeg[1]); if (rc) return rc; }
-  if (want_png) { rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  if (want_png) { rc = form.check(); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
@@ -98,7 +99,7 @@ int stitch_bitmaps(ist_ctx* ctx, ist_bitmap* const* bitmaps, int n, int directio
   if (rc) return rc;
   IST_HIP(hipStreamSynchronize(ctx->stream));      // the canvas is complete; the job's tables may go back to the pool
   if (jpeg) rc = jpeg_to_host(ctx, ctx->scratch_dst.p, row, cw, ch, jpeg[0], jpeg[1], out, out_len);
-  else if (want_png) rc = png_to_host(ctx, ctx->scratch_dst.p, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
+  else if (want_png) rc = png_to_host(ctx, form, ctx->scratch_dst.p, row, cw, ch, nullptr, out, out_len, nullptr, 0, preview);
   else rc = read_back_pooled(ctx->scratch_dst.p, row * static_cast<size_t>(ch), ctx->stream, out);    // the export as ONE DMA (index.js:1577-1579)
   pg.keep = rc == IST_OK;
   return rc;

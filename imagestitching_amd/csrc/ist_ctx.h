@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -44,13 +45,8 @@ struct ist_ctx {
   std::vector<ist::DevBuf> table_pool;
   std::mutex table_mu;
   std::mutex mu;                         // one host-path stitch in flight per context (index.js:772 isStitching)
-  int png_level = 1;                     // 1: Paeth + run-length + Huffman; 0: stored deflate blocks (ist_ctx_set_png_level)
-  int png_color = IST_PNG_RGBA;          // colour type 6, or IST_PNG_RGB: colour type 2, alpha not read (ist_ctx_set_png_color)
-  int png_filter = IST_PNG_FILTER_PAETH; // type 4 on every row, or IST_PNG_FILTER_ADAPTIVE: a type per row, level 1 only (ist_ctx_set_png_filter)
-  int png_match = IST_PNG_MATCH_RUN;     // runs inside a span, or IST_PNG_MATCH_WINDOW: also matches at a distance, level 1 only (ist_ctx_set_png_match)
-  int color_profile = IST_COLOR_PROFILE_IGNORE;   // or IST_COLOR_PROFILE_SRGB: ICC-tagged files are converted to sRGB behind their decode (ist_ctx_set_color_profile)
+  std::atomic<uint32_t> settings{ist::kDefaultSettings};   // every ist_ctx_set_* setting, packed (ist_settings.h); a call reads it ONCE: settings_of below
   std::unique_ptr<ist::Stager> stager;   // pinned staging ring, built on first use
-  bool timing_on = false;                // ist_ctx_set_timing: the file pipeline records its phase times (adds a sync per phase)
   double last_ms[IST_PHASE_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
   // An event that is recorded on CALLERS' streams behind the last reader of a block of the context: no wait for the context's own
   // streams covers it, so it is waited for itself before it goes - and it is declared BEHIND the blocks it guards, so that it goes first.
@@ -107,6 +103,7 @@ struct ist_ctx {
 };
 
 namespace ist {
+inline Settings settings_of(const ist_ctx* ctx) { return ctx ? settings_unpack(ctx->settings.load(std::memory_order_relaxed)) : Settings{}; }
 // where a compiled job's five tables sit in the job's device block
 struct DevTables {
   DevOp* ops = nullptr;
@@ -173,7 +170,8 @@ int ensure_render(ist_ctx* ctx);          // the context's render stream
 int read_back_pooled(const void* dev, size_t bytes, hipStream_t stream, uint8_t** out);   // device bytes -> a pooled pinned block
 // the PNG file of a canvas in device memory -> a pooled pinned block (need_rows / slab_rows_hint: as png_encode_device_deflate)
 // preview (optional): + the preview of the canvas, one reduce queued behind the last render (PreviewTail below)
-int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
+// form: the call's snapshot, checked by the entry point (PngForm::check)
+int png_to_host(ist_ctx* ctx, const PngForm& form, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
                 const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, ist_preview* preview = nullptr);
 
 // ---- JPEG export (ist_jpeg_encode.hip) ----

@@ -100,6 +100,7 @@ int jpeg_decode_rgba8(const char* who, ist_ctx* ctx, const uint8_t* file, int64_
   int sw = J.width, sh = J.height;
   jpeg_scaled_size(J.width, J.height, denom, &sw, &sh);
   if (!out || out_pitch < static_cast<size_t>(sw) * 4 || out_rows < sh) return fail(IST_E_INVALID, std::string(who) + ": output buffer too small");
+  const bool to_srgb = settings_of(ctx).color_profile == IST_COLOR_PROFILE_SRGB;      // the call's setting: read once
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   // one device allocation: coefficients + tables + sample planes + RGBA
@@ -115,7 +116,7 @@ int jpeg_decode_rgba8(const char* who, ist_ctx* ctx, const uint8_t* file, int64_
   d = static_cast<uint8_t*>(ctx->scratch_arena.p);
   rc = jpeg_enqueue(J, d, d, L, d + o_out, row, ctx->stream, false, false, denom);
   if (rc) return rc;
-  if (ctx->color_profile == IST_COLOR_PROFILE_SRGB) {
+  if (to_srgb) {
     ist_color_tables t;
     if (image_color_tables(file, len, &t) == IST_COLOR_CONVERT) { rc = launch_color_convert(d + o_out, row, sw, sh, t, ctx->stream); if (rc) return rc; }
   }
@@ -200,10 +201,10 @@ int ist_decode_scale_fit(int32_t w, int32_t h, int32_t min_w, int32_t min_h) {
 // asks for the image.  With phase timing on, the same steps run with a stream sync between them.
 namespace ist {
 
-Phases::Phases(ist_ctx* c) : ctx(c) {
+Phases::Phases(ist_ctx* c, bool timing) : ctx(c), record(timing) {
   static const bool env = std::getenv("IST_TIMING") != nullptr;
-  print = env; on = env || c->timing_on;
-  if (c->timing_on) for (double& v : c->last_ms) v = 0.0;
+  print = env; on = env || record;
+  if (record) for (double& v : c->last_ms) v = 0.0;
   t_prev = std::chrono::steady_clock::now();
 }
 void Phases::lap(int phase, const char* what, hipStream_t st) {
@@ -212,7 +213,7 @@ void Phases::lap(int phase, const char* what, hipStream_t st) {
   const auto t = std::chrono::steady_clock::now();
   const double ms = std::chrono::duration<double, std::milli>(t - t_prev).count();
   if (print) std::fprintf(stderr, "[ist timing] %-28s %8.2f ms\n", what, ms);
-  if (ctx->timing_on && phase >= 0 && phase < IST_PHASE_COUNT) ctx->last_ms[phase] += ms;
+  if (record && phase >= 0 && phase < IST_PHASE_COUNT) ctx->last_ms[phase] += ms;
   t_prev = t;
 }
 
@@ -237,8 +238,8 @@ static int ensure_image_lanes(ist_ctx* ctx, int n) {
   return IST_OK;
 }
 
-FileDecoder::FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, const int32_t* denom)
-    : ctx_(ctx), files_(files), lens_(lens), n_(n), ph_(ph), denom_(denom), dec_(static_cast<size_t>(n)),
+FileDecoder::FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, int color_profile, const int32_t* denom)
+    : ctx_(ctx), files_(files), lens_(lens), n_(n), ph_(ph), to_srgb_(color_profile == IST_COLOR_PROFILE_SRGB), denom_(denom), dec_(static_cast<size_t>(n)),
       on_gpu_(static_cast<size_t>(n), 0), taken_(static_cast<size_t>(n), 0), uploaded_(static_cast<size_t>(n), 0), started_(static_cast<size_t>(n), 0),
       chroma_done_(static_cast<size_t>(n), 0), jo_(static_cast<size_t>(n)) {}
 FileDecoder::~FileDecoder() {
@@ -315,7 +316,7 @@ int FileDecoder::take(int i, hipStream_t consumer) {
   if (rc) return rc;
   // the one place where bitmap i lands: a file tagged with a profile the contract takes is converted to sRGB behind it, in place
   const Dec& D = dec_[k];
-  if (ctx_->color_profile != IST_COLOR_PROFILE_SRGB || D.color.kind != IST_COLOR_CONVERT) return IST_OK;
+  if (!to_srgb_ || D.color.kind != IST_COLOR_CONVERT) return IST_OK;
   int bw = D.w, bh = D.h;
   if (denom_of(i) > 1) jpeg_scaled_size(D.w, D.h, denom_of(i), &bw, &bh);
   return launch_color_convert(img_[i], pitch_[i], bw, bh, D.color, consumer);
@@ -420,7 +421,7 @@ void FileDecoder::worker(int i) {
   DeviceGuard dg(ctx_->device);
   const uint8_t* f = files_[i]; const int64_t len = lens_[i];
   auto failed = [&](int rc) { D.rc = rc; D.err = g_last_error; };     // (thread-local message: carry it out)
-  if (ctx_->color_profile == IST_COLOR_PROFILE_SRGB) image_color_tables(f, len, &D.color);      // (a bad profile never fails a decode)
+  if (to_srgb_) image_color_tables(f, len, &D.color);      // (a bad profile never fails a decode)
   if (!D.jpeg) {
     D.px.resize(static_cast<size_t>(D.w) * D.h * 4);
     const int rc = ist_image_decode_rgba8(nullptr, f, len, D.px.data(), static_cast<size_t>(D.w) * 4, D.h);
@@ -473,8 +474,9 @@ int check_denoms(const char* who, const int32_t* denom, int n) {
 int decode_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, const int32_t* denom,
                         const std::function<int(const std::vector<ist_image_desc>&, uint8_t**, size_t*)>& place) {
   DeviceGuard g(ctx->device);
-  Phases ph(ctx);
-  FileDecoder fd(ctx, files, lens, n, &ph, denom);
+  const Settings set = settings_of(ctx);      // what this call reads of the context's settings: read once
+  Phases ph(ctx, set.timing);
+  FileDecoder fd(ctx, files, lens, n, &ph, set.color_profile, denom);
   int rc = fd.headers();
   if (rc) return rc;
   const std::vector<ist_image_desc> descs = fd.descs(lens);
@@ -546,9 +548,7 @@ int ist_debug_jpeg_gpu_coefficients(ist_ctx* ctx, const uint8_t* file, int64_t l
 
 int ist_ctx_set_color_profile(ist_ctx* ctx, int profile) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (profile != IST_COLOR_PROFILE_IGNORE && profile != IST_COLOR_PROFILE_SRGB) return fail(IST_E_INVALID, "colour profile must be IST_COLOR_PROFILE_IGNORE (0) or IST_COLOR_PROFILE_SRGB (1)");
-  ctx->color_profile = profile;
-  return IST_OK;
+  return settings_set(&ctx->settings, kColorProfile, profile);
 }
 
 int ist_color_convert_device(ist_ctx* ctx, void* ptr, size_t pitch, int64_t w, int64_t h, const ist_color_tables* tables, void* stream) {
@@ -563,8 +563,7 @@ int ist_color_convert_device(ist_ctx* ctx, void* ptr, size_t pitch, int64_t w, i
 
 int ist_ctx_set_timing(ist_ctx* ctx, int on) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  ctx->timing_on = on != 0;
-  return IST_OK;
+  return settings_set(&ctx->settings, kTiming, on != 0);
 }
 
 int ist_ctx_last_timing(ist_ctx* ctx, double* ms, int n) {

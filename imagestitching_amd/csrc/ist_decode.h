@@ -15,14 +15,14 @@ namespace ist {
 
 // what is known of one file: after FileDecoder::headers() the size and orientation, after its worker the decoded form
 struct Dec { int rc = 0; std::string err; bool jpeg = false; JpegImage J; JpegGpuScan G; int w = 0, h = 0, orient = 0; std::vector<uint8_t> px;
-             ist_color_tables color = {}; };      // color: the file's profile, read by its worker when the context converts to sRGB (kind NONE otherwise)
+             ist_color_tables color = {}; };      // color: the file's profile, read by its worker when the call converts to sRGB (kind NONE otherwise)
 
 // phase clock: stderr lines under IST_TIMING=1, numbers for ist_ctx_last_timing when the context asked for them.  Phases
-// end with a stream synchronisation only while one of the two is on.
+// end with a stream synchronisation only while one of the two is on.  record: the call's timing setting (its snapshot, ist_settings.h).
 struct Phases {
-  ist_ctx* ctx; bool print, on;
+  ist_ctx* ctx; bool record, print, on;
   std::chrono::steady_clock::time_point t_prev;
-  explicit Phases(ist_ctx* c);
+  Phases(ist_ctx* c, bool timing);
   void lap(int phase, const char* what, hipStream_t st);
 };
 
@@ -36,8 +36,8 @@ struct JpegDevLayout { size_t coef[3], q[3], plane[3], ent[3], start[3], cnt[3];
 class FileDecoder {
  public:
   // denom (optional): the decode denominator of each file, 1, 2, 4 or 8 (checked by the caller: check_denoms); NULL = all 1.  It
-  // applies to JPEG files; every other type decodes at 1 / 1.
-  FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, const int32_t* denom = nullptr);
+  // applies to JPEG files; every other type decodes at 1 / 1.  color_profile: the call's setting (its snapshot), for every image alike.
+  FileDecoder(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, Phases* ph, int color_profile, const int32_t* denom = nullptr);
   ~FileDecoder();
   // 1. frame headers only (microseconds per file): sizes, sampling, EXIF orientation - what the planner and the arena need
   int headers();
@@ -66,7 +66,7 @@ class FileDecoder {
   void worker(int i);
   int place(int i, hipStream_t consumer);      // take() without the colour conversion: bitmap i lands at img_[i] on `consumer`
 
-  ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_; const int32_t* denom_;
+  ist_ctx* ctx_; const uint8_t* const* files_; const int64_t* lens_; int n_; Phases* ph_; const bool to_srgb_; const int32_t* denom_;
   std::vector<Dec> dec_;
   bool running_ = false;                                       // the context's worker pool is on this call's files
   std::vector<char> on_gpu_, taken_, uploaded_, started_, chroma_done_;      // started_: the image's stream carries uploads of this call; chroma_done_: its chroma planes were made behind the Huffman batch

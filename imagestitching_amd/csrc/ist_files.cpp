@@ -55,18 +55,18 @@ int compile_banded(ist_ctx* ctx, int64_t cw, int64_t ch, const uint8_t clear[4],
   return IST_OK;
 }
 
-// (the caller holds ctx->mu and has checked the arguments)
-int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
+// (the caller holds ctx->mu and has checked the arguments; set: its snapshot of the context's settings, the PNG form checked)
+int stitch_files_png_locked(ist_ctx* ctx, const Settings& set, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
                             double gap, const ist_limits* limits, int filter, ist_plan* out_plan, uint8_t** out_png, int64_t* out_len,
                             ist_preview* preview) {
   const int n = n_images;
   DeviceGuard g(ctx->device);
-  Phases ph(ctx);
+  Phases ph(ctx, set.timing);
   // (IST_TUNING=1 IST_TIMELINE=1: host-side marks of one call on stderr, microseconds from its start)
   const bool tl_outer = tl_active();                      // (ist_stitch_paths_png started the call's clock: its file reads are part of the call)
   if (!tl_outer) tl_begin();
   struct TlEnd { bool mine; ~TlEnd() { if (mine) tl_end("ist_stitch_files_png"); } } tl_end_guard{!tl_outer};
-  FileDecoder fd(ctx, files, lens, n, &ph);
+  FileDecoder fd(ctx, files, lens, n, &ph, set.color_profile);
   int rc = fd.headers();
   if (rc) return rc;
   tl_mark("headers parsed");
@@ -208,7 +208,7 @@ int stitch_files_png_locked(ist_ctx* ctx, const uint8_t* const* files, const int
   int64_t hint_rows = 0;
   for (const ist_part& p : bj.parts) hint_rows = std::max<int64_t>(hint_rows, p.Y1 - p.Y0);
   tl_mark("encoder entered");
-  rc = png_to_host(ctx, d + o_canvas, canvas_pitch, out_plan->canvas_w, out_plan->canvas_h, d + o_png, &host, &len, need_rows, hint_rows, preview);
+  rc = png_to_host(ctx, set.png, d + o_canvas, canvas_pitch, out_plan->canvas_w, out_plan->canvas_h, d + o_png, &host, &len, need_rows, hint_rows, preview);
   tl_mark("encoder returned (file in host memory)");
   if (rc == IST_OK) rc = fd.finish(render);               // (images whose draw is clipped away entirely)
   (void)hipStreamSynchronize(render);                     // nothing of this call runs on when the arena is handed to the next
@@ -312,9 +312,10 @@ int ist_stitch_files_png_preview(ist_ctx* ctx, const uint8_t* const* files, cons
   const int rcp = preview_check(preview);
   if (rcp) return rcp;
   if (rc) return rc;
-  { const int rcf = ctx_png_form_check(ctx); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
+  const Settings set = settings_of(ctx);      // what this call reads of the context's settings: read once
+  { const int rcf = set.png.check(); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
-  return stitch_files_png_locked(ctx, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
+  return stitch_files_png_locked(ctx, set, files, lens, n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
 }
 
 int ist_stitch_files_png(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n_images, int direction, int mode,
@@ -331,7 +332,8 @@ int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths, int n_i
   const int rcp = preview_check(preview);
   if (rcp) return rcp;
   if (rc) return rc;
-  { const int rcf = ctx_png_form_check(ctx); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
+  const Settings set = settings_of(ctx);      // what this call reads of the context's settings: read once
+  { const int rcf = set.png.check(); if (rcf) return rcf; }      // (level 0 in RGB: refused before anything is read or enqueued)
   tl_begin();
   struct TlEnd { ~TlEnd() { tl_end("ist_stitch_paths_png"); } } tl_end_guard;
   std::lock_guard<std::mutex> lock(ctx->mu);
@@ -341,7 +343,7 @@ int ist_stitch_paths_png_preview(ist_ctx* ctx, const char* const* paths, int n_i
   std::vector<int64_t> lens;
   rc = read_paths(ctx, paths, n_images, &ptr, &lens);
   if (rc) return rc;
-  return stitch_files_png_locked(ctx, ptr.data(), lens.data(), n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
+  return stitch_files_png_locked(ctx, set, ptr.data(), lens.data(), n_images, direction, mode, gap, limits, filter, out_plan, out_png, out_len, preview);
 }
 
 int ist_stitch_paths_png(ist_ctx* ctx, const char* const* paths, int n_images, int direction, int mode, double gap, const ist_limits* limits,

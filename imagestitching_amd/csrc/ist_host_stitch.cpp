@@ -188,7 +188,7 @@ int stitch_banded_duplex(ist_ctx* ctx, const ist_plan* plan, const ist_op* ops, 
   return finish(IST_OK);
 }
 
-int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
+int render_png_banded(ist_ctx* ctx, const PngForm& form, int64_t canvas_w, int64_t canvas_h, const uint8_t clear_rgba[4], const ist_op* ops, int n_ops,
                       const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
                       uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
   RowBands rb;
@@ -222,7 +222,7 @@ int render_png_banded(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const ui
   };
   int64_t hint = 0;
   for (int b = 0; b < rb.nb; ++b) hint = std::max<int64_t>(hint, rb.y1(b) - rb.y0(b));
-  rc = png_to_host(ctx, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint, preview);
+  rc = png_to_host(ctx, form, rb.canvas, rb.row, canvas_w, canvas_h, nullptr, out_png, out_len, need_rows, hint, preview);
   (void)hipStreamSynchronize(R); (void)stager_of(ctx).sync(); (void)hipStreamSynchronize(ctx->stream);
   if (rc == IST_OK) g_duplex_stitches.fetch_add(1, std::memory_order_relaxed);
   return rc;
@@ -233,14 +233,15 @@ int render_png(ist_ctx* ctx, int64_t canvas_w, int64_t canvas_h, const uint8_t c
                const ist_image_desc* images, const uint8_t* const* src, const size_t* src_pitch, int n_images, int filter,
                uint8_t** out_png, int64_t* out_len, ist_preview* preview) {
   *out_png = nullptr; *out_len = 0;
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  { const int rc = form.check(); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
-  int rc = render_png_banded(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len, preview);
+  int rc = render_png_banded(ctx, form, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, out_png, out_len, preview);
   if (rc != 1) return rc;                      // (1: not applicable, nothing queued)
   rc = render_to_scratch(ctx, canvas_w, canvas_h, clear_rgba, ops, n_ops, images, src, src_pitch, n_images, filter, nullptr, nullptr, nullptr);
   if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst.p, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len, nullptr, 0, preview);
+  return png_to_host(ctx, form, ctx->scratch_dst.p, static_cast<size_t>(canvas_w) * 4, canvas_w, canvas_h, nullptr, out_png, out_len, nullptr, 0, preview);
 }
 
 }  // namespace
@@ -365,7 +366,8 @@ int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int6
                          int64_t* out_len) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
   if (!pixels || !out_png || !out_len || w < 1 || h < 1 || pitch < static_cast<size_t>(w) * 4) return fail(IST_E_INVALID, "ist_png_encode_rgba8: bad argument");
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  { const int rc = form.check(); if (rc) return rc; }
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   const size_t row = static_cast<size_t>(w) * 4;
@@ -374,7 +376,7 @@ int ist_png_encode_rgba8(ist_ctx* ctx, const uint8_t* pixels, size_t pitch, int6
   std::vector<RowsCopy> up{RowsCopy{ctx->scratch_dst.p, pixels, nullptr, pitch, row, static_cast<size_t>(h)}};
   rc = stager_of(ctx).upload(up, ctx->stream);
   if (rc) return rc;
-  return png_to_host(ctx, ctx->scratch_dst.p, row, w, h, nullptr, out_png, out_len);
+  return png_to_host(ctx, form, ctx->scratch_dst.p, row, w, h, nullptr, out_png, out_len);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/imagestitch.h"
+#include "ist_settings.h"
 
 namespace ist {
 
@@ -206,7 +207,8 @@ struct PlanGuard { ist_plan* p; bool keep = false; ~PlanGuard() { if (!keep) ist
 // around a failure the caller tolerates: the thread's g_last_error / g_last_code are what they were before, once it goes out of scope
 struct KeepLastError { std::string msg = g_last_error; int code = g_last_code; ~KeepLastError() { g_last_error = msg; g_last_code = code; } };
 
-// PNG export, compressing form (ist_png_deflate.hip); ist_png_encode_device picks it when the context's level is > 0
+// PNG export, compressing form (ist_png_deflate.hip); ist_png_encode_device picks it when the call's form is compressed.  `form` is the
+// entry point's snapshot of the context's settings, checked there (ist_settings.h): the encoders neither read the context's nor check again.
 int64_t png_deflate_bound(int64_t w, int64_t h, int color = IST_PNG_RGBA);   // (the RGBA bound holds for both colour forms)
 // host_out (pinned, out_cap bytes) + aux stream, both optional: the file also lands in host memory, slab by slab, while
 // later slabs are still being compressed
@@ -214,16 +216,11 @@ int64_t png_deflate_bound(int64_t w, int64_t h, int color = IST_PNG_RGBA);   // 
 // `stream2`) - a producer that renders the canvas band by band submits the missing bands there / orders s behind them.
 // slab_rows_hint (optional): canvas rows a slab should cover (the producer's band height), so that slab boundaries fall on
 // band boundaries.  stream2 (optional, with host_out): slabs alternate between the two streams.
-int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap,
+int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap,
                               int64_t* out_len, void* stream, uint8_t* host_out, void* aux,
                               const std::function<int(int64_t, void*)>& need_rows = nullptr, int64_t slab_rows_hint = 0, void* stream2 = nullptr);
-int ctx_png_level(const ist_ctx* ctx);
-int ctx_png_color(const ist_ctx* ctx);                      // IST_PNG_RGBA / IST_PNG_RGB (ist_ctx_set_png_color)
-int ctx_png_filter(const ist_ctx* ctx);                     // IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE (ist_ctx_set_png_filter)
-int ctx_png_match(const ist_ctx* ctx);                      // IST_PNG_MATCH_RUN / IST_PNG_MATCH_WINDOW (ist_ctx_set_png_match)
-// IST_E_UNSUPPORTED for the settings no encoder serves: the stored form (level 0) in RGB, with adaptive row filters or with window matches.  Every *_png entry point
-// calls it before anything is enqueued, and so does every place that picks between the stored and the compressing encoder.
-int ctx_png_form_check(const ist_ctx* ctx);
+// the stored form (ist_png.hip): what ist_png_encode_device does at level 0, behind its argument checks
+int png_encode_device_stored(const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap, int64_t* out_len, void* stream);
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p);   // the context's grow-only PNG scratch (kept across calls)
 
 // ---- batch PNG export (ist_png_encode_batch_device, ist_stitch_png_batch) ----
@@ -234,8 +231,8 @@ struct PngBatchFile { const void* canvas; size_t pitch; int64_t w, h; uint8_t* o
 // ist_png_encode_device writes for canvas k at the same level.  Returns with `stream` idle (the checksums are combined on the
 // host).  host_patches: the patches are left in files[k].patches for a caller that writes them into its host copy of the file;
 // otherwise they are copied to the device.  The arguments are checked by the caller (png_batch_check).
-int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
-int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
+int png_encode_batch_deflate(ist_ctx* ctx, const PngForm& form, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
+int png_encode_batch_stored(ist_ctx* ctx, const PngForm& form, std::vector<PngBatchFile>& files, void* stream, bool host_patches);
 int png_batch_check(const PngBatchFile& f, int k);          // the rules of ist_png_encode_device for file k (message names it)
 int64_t png_deflate_chunks(int64_t w, int64_t h, int color = IST_PNG_RGBA);   // chunks (= slots of SLOT bytes) of the compressing form
 void png_deflate_grid(int64_t w, int64_t h, int color, int64_t out[4]);       // n_chunks, rows_per_chunk, pieces_per_row, piece_px

@@ -26,7 +26,7 @@
 
 #include "ist_crc.h"
 #include "ist_host.h"
-#include "ist_internal.h"
+#include "ist_ctx.h"
 
 namespace ist {
 
@@ -344,7 +344,7 @@ void stored_patches(const Layout& L, const unsigned long long* s1, const unsigne
 
 // The stored form of a batch: every row segment of every file in ONE ist_png_rows_batch_kernel launch; the partials come back in
 // one copy each and every file is finished on the host (stored_patches, as for one file).
-int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
+int png_encode_batch_stored(ist_ctx* ctx, const PngForm&, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
   const size_t nf = files.size();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const std::vector<uint32_t>& xpow = stored_tables().xpow;
@@ -379,7 +379,6 @@ int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void
   struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(std::max(o_pow, total - o_s1)))};
   if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
   struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
-#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
   RowsJob* hj = reinterpret_cast<RowsJob*>(pin.p + o_jobs);
   for (size_t k = 0; k < nf; ++k) {
     const PngBatchFile& f = files[k];
@@ -393,10 +392,10 @@ int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void
     J.row_bytes = lay[k].row_bytes; J.h = static_cast<int32_t>(f.h); J.nb = lay[k].nb; J.segs = segs[k]; J.pad_ = 0;
   }
   std::memcpy(pin.p + o_begin, wg.data(), 8 * (nf + 1));
-  PNG_HIP(hipMemcpyAsync(d, pin.p, o_pow, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(d + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(d + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemsetAsync(d + o_s1, 0, total - o_s1, stream));
+  IST_HIP(hipMemcpyAsync(d, pin.p, o_pow, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(d + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(d + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemsetAsync(d + o_s1, 0, total - o_s1, stream));
   RowsBatchArgs B;
   B.jobs = reinterpret_cast<const RowsJob*>(d + o_jobs);
   B.wg_begin = reinterpret_cast<const int64_t*>(d + o_begin);
@@ -404,11 +403,11 @@ int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void
   B.xpow4 = reinterpret_cast<const uint32_t*>(d + o_pow);
   B.tables = reinterpret_cast<const uint32_t*>(d + o_T);
   hipLaunchKernelGGL(ist_png_rows_batch_kernel, dim3(static_cast<unsigned>(wg[nf])), dim3(256), 0, stream, B);
-  PNG_HIP(hipGetLastError());
+  IST_HIP(hipGetLastError());
   count_png_batch_launch();
   // the partials into the same pinned block (its upload has been consumed by the time the kernel runs: same stream)
-  PNG_HIP(hipMemcpyAsync(pin.p, d + o_s1, total - o_s1, hipMemcpyDeviceToHost, stream));
-  PNG_HIP(hipStreamSynchronize(stream));
+  IST_HIP(hipMemcpyAsync(pin.p, d + o_s1, total - o_s1, hipMemcpyDeviceToHost, stream));
+  IST_HIP(hipStreamSynchronize(stream));
   const unsigned long long* s1 = reinterpret_cast<const unsigned long long*>(pin.p);
   const unsigned long long* s2 = reinterpret_cast<const unsigned long long*>(pin.p + (o_s2 - o_s1));
   const uint32_t* crc = reinterpret_cast<const uint32_t*>(pin.p + (o_crc - o_s1));
@@ -418,11 +417,67 @@ int png_encode_batch_stored(ist_ctx* ctx, std::vector<PngBatchFile>& files, void
     stored_patches(lay[k], s1 + row_at[k], s2 + row_at[k], crc + acc_at[k], &f.patches);
     f.len = lay[k].total;
     if (!host_patches)
-      for (const PngPatch& pt : f.patches) PNG_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
+      for (const PngPatch& pt : f.patches) IST_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
   }
-  PNG_HIP(hipStreamSynchronize(stream));
+  IST_HIP(hipStreamSynchronize(stream));
   drain.armed = false;
-#undef PNG_HIP
+  return IST_OK;
+}
+
+// The stored form of one file: every row segment in ONE ist_png_rows_kernel launch, finished on the host (stored_patches).
+int png_encode_device_stored(const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap, int64_t* out_len, void* stream_) {
+  if (w > (1ll << 29) || h > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for PNG");      // (png_to_host comes here without ist_png_encode_device's checks)
+  Layout L;
+  make_layout(w, h, &L);
+  if (L.total > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+
+  const CrcTables& T = stored_tables().T;
+  const std::vector<uint32_t>& xpow = stored_tables().xpow;
+  // device scratch: row table, xpow, tables, partial sums
+  const size_t n_acc = static_cast<size_t>(h) * L.nb;
+  const size_t bytes_tab = sizeof(int64_t) * static_cast<size_t>(h), bytes_pow = 4 * xpow.size(), bytes_T = sizeof(T);
+  const size_t bytes_s = 8 * static_cast<size_t>(h), bytes_crc = 4 * n_acc;
+  auto up16 = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  const size_t o_tab = 0, o_pow = o_tab + up16(bytes_tab), o_T = o_pow + up16(bytes_pow), o_s1 = o_T + up16(bytes_T),
+               o_s2 = o_s1 + up16(bytes_s), o_crc = o_s2 + up16(bytes_s), scratch_bytes = o_crc + up16(bytes_crc);
+  DevBuf block;                                                     // (a free waits for the device: the early returns below are safe)
+  if (block.grow(scratch_bytes)) return fail(IST_E_NOMEM, "PNG scratch allocation failed");
+  uint8_t* const scratch = static_cast<uint8_t*>(block.p);
+  IST_HIP(hipMemcpyAsync(scratch + o_tab, L.row_tab.data(), bytes_tab, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), bytes_pow, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_T, &T, bytes_T, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemsetAsync(scratch + o_s1, 0, scratch_bytes - o_s1, stream));
+  PngArgs A;
+  A.canvas = static_cast<const uint8_t*>(canvas); A.pitch = pitch; A.out = static_cast<uint8_t*>(out);
+  A.row_tab = reinterpret_cast<const int64_t*>(scratch + o_tab);
+  A.xpow4 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
+  A.tables = reinterpret_cast<const uint32_t*>(scratch + o_T);
+  A.s1 = reinterpret_cast<unsigned long long*>(scratch + o_s1);
+  A.s2 = reinterpret_cast<unsigned long long*>(scratch + o_s2);
+  A.crc = reinterpret_cast<uint32_t*>(scratch + o_crc);
+  A.row_bytes = L.row_bytes; A.h = static_cast<int32_t>(h); A.nb = L.nb;
+  const unsigned gx = static_cast<unsigned>((L.row_bytes + 4096 * kChunks - 1) / (4096 * kChunks));
+  if (static_cast<int64_t>(gx) * h > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
+  A.segs = gx;
+  hipLaunchKernelGGL(ist_png_rows_kernel, dim3(static_cast<unsigned>(gx * static_cast<unsigned>(h))), dim3(256), 0, stream, A);
+  IST_HIP(hipGetLastError());
+  // ---- combine the partials on the host
+  std::vector<unsigned long long> s1(static_cast<size_t>(h)), s2(static_cast<size_t>(h));
+  std::vector<uint32_t> crc(n_acc);
+  IST_HIP(hipMemcpyAsync(s1.data(), scratch + o_s1, bytes_s, hipMemcpyDeviceToHost, stream));
+  IST_HIP(hipMemcpyAsync(s2.data(), scratch + o_s2, bytes_s, hipMemcpyDeviceToHost, stream));
+  IST_HIP(hipMemcpyAsync(crc.data(), scratch + o_crc, bytes_crc, hipMemcpyDeviceToHost, stream));
+  IST_HIP(hipStreamSynchronize(stream));
+
+  std::vector<PngPatch> patches;
+  stored_patches(L, s1.data(), s2.data(), crc.data(), &patches);
+  for (const PngPatch& pt : patches)
+    IST_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
+  IST_HIP(hipStreamSynchronize(stream));
+  *out_len = L.total;
   return IST_OK;
 }
 
@@ -446,62 +501,10 @@ int ist_png_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_
     return fail(IST_E_INVALID, "ist_png_encode_device: bad argument");
   if (w > (1ll << 29) || h > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for PNG");
   if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(IST_E_INVALID, "PNG output buffer must be 16-byte aligned");
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
-  if (ctx_png_level(ctx) > 0) return png_encode_device_deflate(ctx, canvas, pitch, w, h, out, out_cap, out_len, stream_, nullptr, nullptr);
-  Layout L;
-  make_layout(w, h, &L);
-  if (L.total > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-
-  const CrcTables& T = stored_tables().T;
-  const std::vector<uint32_t>& xpow = stored_tables().xpow;
-  // device scratch: row table, xpow, tables, partial sums
-  const size_t n_acc = static_cast<size_t>(h) * L.nb;
-  const size_t bytes_tab = sizeof(int64_t) * static_cast<size_t>(h), bytes_pow = 4 * xpow.size(), bytes_T = sizeof(T);
-  const size_t bytes_s = 8 * static_cast<size_t>(h), bytes_crc = 4 * n_acc;
-  auto up16 = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t o_tab = 0, o_pow = o_tab + up16(bytes_tab), o_T = o_pow + up16(bytes_pow), o_s1 = o_T + up16(bytes_T),
-               o_s2 = o_s1 + up16(bytes_s), o_crc = o_s2 + up16(bytes_s), scratch_bytes = o_crc + up16(bytes_crc);
-  DevBuf block;                                                     // (a free waits for the device: the early returns below are safe)
-  if (block.grow(scratch_bytes)) return fail(IST_E_NOMEM, "PNG scratch allocation failed");
-  uint8_t* const scratch = static_cast<uint8_t*>(block.p);
-#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
-  PNG_HIP(hipMemcpyAsync(scratch + o_tab, L.row_tab.data(), bytes_tab, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), bytes_pow, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_T, &T, bytes_T, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemsetAsync(scratch + o_s1, 0, scratch_bytes - o_s1, stream));
-  PngArgs A;
-  A.canvas = static_cast<const uint8_t*>(canvas); A.pitch = pitch; A.out = static_cast<uint8_t*>(out);
-  A.row_tab = reinterpret_cast<const int64_t*>(scratch + o_tab);
-  A.xpow4 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
-  A.tables = reinterpret_cast<const uint32_t*>(scratch + o_T);
-  A.s1 = reinterpret_cast<unsigned long long*>(scratch + o_s1);
-  A.s2 = reinterpret_cast<unsigned long long*>(scratch + o_s2);
-  A.crc = reinterpret_cast<uint32_t*>(scratch + o_crc);
-  A.row_bytes = L.row_bytes; A.h = static_cast<int32_t>(h); A.nb = L.nb;
-  const unsigned gx = static_cast<unsigned>((L.row_bytes + 4096 * kChunks - 1) / (4096 * kChunks));
-  if (static_cast<int64_t>(gx) * h > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
-  A.segs = gx;
-  hipLaunchKernelGGL(ist_png_rows_kernel, dim3(static_cast<unsigned>(gx * static_cast<unsigned>(h))), dim3(256), 0, stream, A);
-  PNG_HIP(hipGetLastError());
-  // ---- combine the partials on the host
-  std::vector<unsigned long long> s1(static_cast<size_t>(h)), s2(static_cast<size_t>(h));
-  std::vector<uint32_t> crc(n_acc);
-  PNG_HIP(hipMemcpyAsync(s1.data(), scratch + o_s1, bytes_s, hipMemcpyDeviceToHost, stream));
-  PNG_HIP(hipMemcpyAsync(s2.data(), scratch + o_s2, bytes_s, hipMemcpyDeviceToHost, stream));
-  PNG_HIP(hipMemcpyAsync(crc.data(), scratch + o_crc, bytes_crc, hipMemcpyDeviceToHost, stream));
-  PNG_HIP(hipStreamSynchronize(stream));
-
-  std::vector<PngPatch> patches;
-  stored_patches(L, s1.data(), s2.data(), crc.data(), &patches);
-  for (const PngPatch& pt : patches)
-    PNG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipStreamSynchronize(stream));
-#undef PNG_HIP
-  *out_len = L.total;
-  return IST_OK;
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  { const int rc = form.check(); if (rc) return rc; }
+  if (form.compressed()) return png_encode_device_deflate(ctx, form, canvas, pitch, w, h, out, out_cap, out_len, stream_, nullptr, nullptr);
+  return png_encode_device_stored(canvas, pitch, w, h, out, out_cap, out_len, stream_);
 }
 
 }  // extern "C"

@@ -53,10 +53,11 @@ int ist_png_encode_batch_device(ist_ctx* ctx, const void* const* canvases, const
     const int rc = png_batch_check(f, k);
     if (rc) return rc;
   }
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
+  const PngForm form = settings_of(ctx).png;      // the call's form: read once
+  { const int rc = form.check(); if (rc) return rc; }      // (level 0 in RGB: refused before anything is enqueued)
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(IST_E_NO_DEVICE, "hipSetDevice failed");
-  const int rc = ctx_png_level(ctx) > 0 ? png_encode_batch_deflate(ctx, files, stream, false) : png_encode_batch_stored(ctx, files, stream, false);
+  const int rc = form.compressed() ? png_encode_batch_deflate(ctx, form, files, stream, false) : png_encode_batch_stored(ctx, form, files, stream, false);
   if (rc) return rc;
   for (int k = 0; k < n; ++k) out_len[k] = files[static_cast<size_t>(k)].len;
   return IST_OK;

@@ -64,7 +64,7 @@
 
 #include "ist_crc.h"
 #include "ist_host.h"
-#include "ist_internal.h"
+#include "ist_ctx.h"
 
 namespace ist {
 
@@ -1321,12 +1321,9 @@ void put32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = (v >> 16) & 0xFF; p[
 
 struct ChunkGrid { int64_t n_chunks; int rows_per_chunk, pieces_per_row, piece_px; };
 
-// bytes of a pixel in the filtered stream of a colour form (IST_PNG_RGBA / IST_PNG_RGB)
-int bpp_of(int color) { return color == IST_PNG_RGB ? 3 : 4; }
-
 ChunkGrid make_grid(int64_t w, int64_t h, int color) {
   ChunkGrid g{0, 0, 0, 0};
-  const int bpp = bpp_of(color);
+  const int bpp = color == IST_PNG_RGB ? 3 : 4;      // bytes of a pixel in the filtered stream of a colour form (IST_PNG_RGBA / IST_PNG_RGB)
   const int64_t R = bpp * w + 1;
   if (R <= CH) { g.rows_per_chunk = static_cast<int>(CH / R); g.n_chunks = (h + g.rows_per_chunk - 1) / g.rows_per_chunk; }
   else { g.piece_px = (CH - 1) / bpp; g.pieces_per_row = static_cast<int>((w + g.piece_px - 1) / g.piece_px); g.n_chunks = h * g.pieces_per_row; }
@@ -1438,6 +1435,29 @@ struct FileLayout {
   }
 };
 
+// ---- the two places that pick a kernel for a form
+// the adaptive form's pre-pass over F.n_rows rows (one file: rows of `widest` pixels; a batch: the rows of all files, the widest that wide)
+void launch_row_filter(const PngForm& form, RowFilterArgs F, int64_t widest, hipStream_t st) {
+  F.rows_per_group = widest <= kRowFilterWaveW ? 4 : 1;
+  const dim3 groups(static_cast<unsigned>((F.n_rows + F.rows_per_group - 1) / F.rows_per_group));
+  hipLaunchKernelGGL((form.bpp() == 3 ? ist_png_row_filter_rgb_kernel : ist_png_row_filter_kernel), groups, dim3(256), 0, st, F);
+}
+// the compressing kernel of `form`, a workgroup per chunk.  ftab: the pre-pass's row types (NULL unless adaptive); rows: the batch's row_begin (likewise)
+void launch_deflate(const PngForm& form, size_t n_chunks, hipStream_t st, const DeflArgs& A, const uint8_t* ftab) {
+  const dim3 grid(static_cast<unsigned>(n_chunks)), wg(256);
+  const bool rgb = form.bpp() == 3;
+  if (form.window()) hipLaunchKernelGGL(ist_png_deflate_window_kernel, grid, wg, 0, st, A, ftab, form.bpp());
+  else if (form.adaptive()) hipLaunchKernelGGL((rgb ? ist_png_deflate_adapt_rgb_kernel : ist_png_deflate_adapt_kernel), grid, wg, 0, st, A, ftab);
+  else hipLaunchKernelGGL((rgb ? ist_png_deflate_rgb_kernel : ist_png_deflate_kernel), grid, wg, 0, st, A);
+}
+void launch_deflate(const PngForm& form, size_t n_chunks, hipStream_t st, const DeflBatchArgs& B, const int64_t* rows, const uint8_t* ftab) {
+  const dim3 grid(static_cast<unsigned>(n_chunks)), wg(256);
+  const bool rgb = form.bpp() == 3;
+  if (form.window()) hipLaunchKernelGGL(ist_png_deflate_window_batch_kernel, grid, wg, 0, st, B, rows, ftab, form.bpp());
+  else if (form.adaptive()) hipLaunchKernelGGL((rgb ? ist_png_deflate_adapt_rgb_batch_kernel : ist_png_deflate_adapt_batch_kernel), grid, wg, 0, st, B, rows, ftab);
+  else hipLaunchKernelGGL((rgb ? ist_png_deflate_rgb_batch_kernel : ist_png_deflate_batch_kernel), grid, wg, 0, st, B);
+}
+
 }  // namespace
 
 // upper bound of the compressed form: every chunk stored.  (The RGB form never has more chunks than the RGBA one: the RGBA bound
@@ -1451,13 +1471,11 @@ int64_t png_deflate_bound(int64_t w, int64_t h, int color) {
 // host_out (optional, pinned, out_cap bytes) + aux: the file is ALSO delivered to host memory, slab by slab, on the aux
 // stream while later slabs are still being compressed on `stream` — the PNG's trip over PCIe (2.6 ms for the 146 MB of a
 // 439 MB photo canvas) then hides behind the encoder (3.3 ms) instead of following it.  Each slab is its own IDAT chunk.
-int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap,
+int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* canvas, size_t pitch, int64_t w, int64_t h, void* out, int64_t out_cap,
                               int64_t* out_len, void* stream_, uint8_t* host_out, void* aux_,
                               const std::function<int(int64_t, void*)>& need_rows, int64_t slab_rows_hint, void* stream2_) {
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
-  const int color = ctx_png_color(ctx);
-  const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
-  const bool window = ctx_png_match(ctx) == IST_PNG_MATCH_WINDOW;
+  const int color = form.color;
+  const bool adaptive = form.adaptive();
   const ChunkGrid g = make_grid(w, h, color);
   if (g.n_chunks > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "image too large for one PNG launch");
   if (png_deflate_bound(w, h, color) > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
@@ -1511,10 +1529,9 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     if (rc) return rc;
     scratch = static_cast<uint8_t*>(p);
   }
-#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
-  PNG_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  if (stream2 != stream) PNG_HIP(hipStreamSynchronize(stream));      // (both are blocking staged copies of static data: the tables are in place for either stream)
+  IST_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
+  if (stream2 != stream) IST_HIP(hipStreamSynchronize(stream));      // (both are blocking staged copies of static data: the tables are in place for either stream)
   // ---- every slab's compression goes out now, each followed by the copy of its per-chunk results and an event
   // (pinned: a device-to-host copy into pageable memory would block this thread until the slab is compressed, and the
   // slabs' launches would no longer run ahead of the host)
@@ -1558,32 +1575,25 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     A.rows_per_chunk = g.rows_per_chunk; A.pieces_per_row = g.pieces_per_row; A.piece_px = g.piece_px;
     A.chunk0 = static_cast<int64_t>(c0);
     A.dbg = static_cast<unsigned long long*>(dbg.p);
+    uint8_t* ftab = nullptr;
     if (adaptive) {
       // the pre-pass of every row this slab's chunks touch, on the slab's own stream, into the table of that stream (the row above
       // the first one is only read: like the Paeth filter's, it belongs to an earlier slab and has been asked for)
       const int64_t y_lo = g.pieces_per_row > 0 ? static_cast<int64_t>(c0) / g.pieces_per_row : static_cast<int64_t>(c0) * g.rows_per_chunk;
       const int64_t y_hi = rows_of(c0 + cn);
-      uint8_t* const ftab = scratch + o_ftab + (s & 1) * static_cast<size_t>(h);
+      ftab = scratch + o_ftab + (s & 1) * static_cast<size_t>(h);
       RowFilterArgs F;
       F.canvas = A.canvas; F.pitch = pitch; F.w = w; F.h = h;
       F.jobs = nullptr; F.row_begin = nullptr; F.n_files = 0;
-      F.rows_per_group = w <= kRowFilterWaveW ? 4 : 1;
       F.row0 = y_lo; F.n_rows = y_hi - y_lo; F.table = ftab;
-      const unsigned groups = static_cast<unsigned>((F.n_rows + F.rows_per_group - 1) / F.rows_per_group);
-      if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, st, F);
-      else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, st, F);
-      PNG_HIP(hipGetLastError());
-      if (window) hipLaunchKernelGGL(ist_png_deflate_window_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab), bpp_of(color));
-      else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
-      else hipLaunchKernelGGL(ist_png_deflate_adapt_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(ftab));
+      launch_row_filter(form, F, w, st);
+      IST_HIP(hipGetLastError());
     }
-    else if (window) hipLaunchKernelGGL(ist_png_deflate_window_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A, static_cast<const uint8_t*>(nullptr), bpp_of(color));
-    else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(ist_png_deflate_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, st, A);
-    PNG_HIP(hipGetLastError());
+    launch_deflate(form, cn, st, A, ftab);
+    IST_HIP(hipGetLastError());
     tl_mark("png:   compression launched, slab", static_cast<long>(s));
     { const int rc = evs[s].ensure(); if (rc) return rc; }
-    PNG_HIP(hipEventRecord(evs[s], st));
+    IST_HIP(hipEventRecord(evs[s], st));
     return IST_OK;
   };
   // one slab ahead: slab s+1 is compressing while the host lays out slab s and the aux stream carries it away
@@ -1598,7 +1608,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
   for (size_t s = 0; s < n_slabs; ++s) {
     const size_t c0 = slab_at[s], cn = slab_at[s + 1] - c0;
     if (s + 1 < n_slabs) { const int rc = compress(s + 1); if (rc) return rc; tl_mark("png: submitted the compression of slab", static_cast<long>(s + 1)); }
-    PNG_HIP(hipEventSynchronize(evs[s]));
+    IST_HIP(hipEventSynchronize(evs[s]));
     tl_mark("png: compressed (event passed), slab", static_cast<long>(s));
     if (fail_at >= 0 && static_cast<size_t>(fail_at) == s) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length (forced: IST_PNG_FAIL_AT)");
     const uint8_t* r = res.p + 20 * per_slab * s;
@@ -1623,17 +1633,17 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     hipStream_t gs = host_out ? ((s & 1) ? stream2 : stream) : aux;
     GatherArgs G{scratch + o_slots, static_cast<uint8_t*>(out), dst, reinterpret_cast<const uint32_t*>(res.p + 20 * per_slab * s) - c0, static_cast<int64_t>(c0)};
     hipLaunchKernelGGL(ist_png_gather_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, gs, G);
-    PNG_HIP(hipGetLastError());
+    IST_HIP(hipGetLastError());
     tl_mark("png:   gather launched, slab", static_cast<long>(s));
     if (host_out) {
       { const int rc = gathered[s].ensure(); if (rc) return rc; }
-      PNG_HIP(hipEventRecord(gathered[s], gs));
-      PNG_HIP(hipStreamWaitEvent(aux, gathered[s], 0));
+      IST_HIP(hipEventRecord(gathered[s], gs));
+      IST_HIP(hipStreamWaitEvent(aux, gathered[s], 0));
       tl_mark("png:   event created + recorded + aux ordered behind it, slab", static_cast<long>(s));
     }
     if (!host_out)                                     // (with a host sink the headers are written there, below)
       for (const PngPatch& pt : patches)
-        PNG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, aux));
+        IST_HIP(hipMemcpyAsync(static_cast<uint8_t*>(out) + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, aux));
     if (host_out) {
       // 256-byte aligned ends.  The bytes past `pos` in the last 256 are the next slab's: its own copy, ordered behind
       // this one, delivers them
@@ -1643,23 +1653,23 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
       if (!skip_d2h && copy_grid > 0) {
         hipLaunchKernelGGL(ist_png_to_host_kernel, dim3(static_cast<unsigned>(copy_grid)), dim3(256), 0, aux, reinterpret_cast<const u32x4*>(static_cast<const uint8_t*>(out) + c_lo),
                            reinterpret_cast<u32x4*>(host_out + c_lo), (c_hi - c_lo) / 16);
-        PNG_HIP(hipGetLastError());
+        IST_HIP(hipGetLastError());
       } else if (!skip_d2h) {
         // (round 4, tools/exp_slow_call.py + the marks around this call: one call in 600 - 3000 loses 6.5 - 7.3 ms INSIDE this
         // hipMemcpyAsync - the runtime's submission of one slab's device-to-host copy, slab 4, 8 or 9, on four different boxes; the
         // only stall of the call that is neither a wait of ours nor host scheduling.  Bounding the copies queued on the aux stream to
         // four - waiting for copy s-4's event before submitting copy s - did not remove it (1 and 3 such calls in 2 x 3000, against 2
         // and 1 unbounded) and cost 0.15 - 0.2 ms of the median call: dropped.)
-        PNG_HIP(hipMemcpyAsync(host_out + c_lo, static_cast<const uint8_t*>(out) + c_lo, static_cast<size_t>(c_hi - c_lo), hipMemcpyDeviceToHost, aux));
+        IST_HIP(hipMemcpyAsync(host_out + c_lo, static_cast<const uint8_t*>(out) + c_lo, static_cast<size_t>(c_hi - c_lo), hipMemcpyDeviceToHost, aux));
       }
       tl_mark("png: laid out, gather + copy submitted, slab", static_cast<long>(s));
     }
   }
   tl_mark("png: every slab submitted; waiting for the copies (aux stream)");
-  PNG_HIP(hipStreamSynchronize(aux));
+  IST_HIP(hipStreamSynchronize(aux));
   tl_mark("png: aux stream idle (the file is in host memory)");
-  if (aux != stream) PNG_HIP(hipStreamSynchronize(stream));
-  if (stream2 != stream) PNG_HIP(hipStreamSynchronize(stream2));
+  if (aux != stream) IST_HIP(hipStreamSynchronize(stream));
+  if (stream2 != stream) IST_HIP(hipStreamSynchronize(stream2));
   tl_mark("png: encoder streams idle");
   drain.armed = false;                                 // the streams are idle
   if (dbg.p) {
@@ -1670,7 +1680,6 @@ int png_encode_device_deflate(ist_ctx* ctx, const void* canvas, size_t pitch, in
     static const char* names[6] = {"A load+filter", "B histogram+adler", "C code build", "D bit counts+scan", "body emit", "E slot write+crc"};
     for (int k = 0; k < 6; ++k) std::fprintf(stderr, "[png phases] %-18s %8.2f us per chunk (100 MHz clock)\n", names[k], sum[k] / static_cast<double>(n) / 100.0);
   }
-#undef PNG_HIP
   if (host_out)                                        // signature, chunk headers, lengths, CRCs, trailer: ~30 bytes per slab
     for (const std::vector<PngPatch>& v : slab_patches)
       for (const PngPatch& pt : v) std::memcpy(host_out + pt.at, pt.b, static_cast<size_t>(pt.n));
@@ -1687,12 +1696,10 @@ int64_t png_deflate_slot_bytes() { return SLOT; }
 
 // The compressing form of a batch: every chunk of every file in ONE ist_png_deflate_batch_kernel launch, the host layout of
 // each file (FileLayout, as for one file), then every chunk of every file in ONE ist_png_gather_batch_kernel launch.
-int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
+int png_encode_batch_deflate(ist_ctx* ctx, const PngForm& form, std::vector<PngBatchFile>& files, void* stream_, bool host_patches) {
   const size_t nf = files.size();
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
-  const int color = ctx_png_color(ctx);
-  const bool adaptive = ctx_png_filter(ctx) == IST_PNG_FILTER_ADAPTIVE;
-  const bool window = ctx_png_match(ctx) == IST_PNG_MATCH_WINDOW;
+  const int color = form.color;
+  const bool adaptive = form.adaptive();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   std::vector<ChunkGrid> grid(nf);
   std::vector<int64_t> begin(nf + 1, 0), row_begin(nf + 1, 0);      // (row_begin: the rows of every file, file-major - the adaptive form's table)
@@ -1726,7 +1733,6 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
   // every way out below waits for the stream first: the kernels write `pin` and read it in place (declared after it: runs first)
   struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
-#define PNG_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) return fail(IST_E_HIP, std::string(#e) + ": " + hipGetErrorString(e_)); } while (0)
   DeflJob* hj = reinterpret_cast<DeflJob*>(pin.p + h_jobs);
   int64_t* hb = reinterpret_cast<int64_t*>(pin.p + h_jobs + (o_begin - o_jobs));
   for (size_t k = 0; k < nf; ++k) {
@@ -1735,9 +1741,9 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   }
   std::memcpy(hb, begin.data(), 8 * (nf + 1));
   if (adaptive) std::memcpy(pin.p + h_jobs + (o_rows - o_jobs), row_begin.data(), 8 * (nf + 1));
-  PNG_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_ftab - o_jobs, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_ftab - o_jobs, hipMemcpyHostToDevice, stream));
   uint32_t* res = reinterpret_cast<uint32_t*>(pin.p + h_res);
   DeflBatchArgs B;
   B.jobs = reinterpret_cast<const DeflJob*>(scratch + o_jobs);
@@ -1746,31 +1752,25 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   B.slots = scratch + o_slots;
   B.len16 = res; B.crc = res + n; B.ad_a = res + 2 * n; B.ad_b = res + 3 * n; B.ad_n = res + 4 * n;
   B.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); B.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
+  const int64_t* d_rows = nullptr;
+  uint8_t* ftab = nullptr;
   if (adaptive) {
     // ONE pre-pass launch for the rows of all files (a wave per row unless some file is wider than a wave's share), then the one
     // compressing launch
     if (row_begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
-    const int64_t* d_rows = reinterpret_cast<const int64_t*>(scratch + o_rows);
-    uint8_t* const ftab = scratch + o_ftab;
+    d_rows = reinterpret_cast<const int64_t*>(scratch + o_rows);
+    ftab = scratch + o_ftab;
     RowFilterArgs F;
     F.canvas = nullptr; F.pitch = 0; F.w = 0; F.h = 0;
     F.jobs = B.jobs; F.row_begin = d_rows; F.n_files = B.n_files;
-    F.rows_per_group = widest <= kRowFilterWaveW ? 4 : 1;
     F.row0 = 0; F.n_rows = row_begin[nf]; F.table = ftab;
-    const unsigned groups = static_cast<unsigned>((F.n_rows + F.rows_per_group - 1) / F.rows_per_group);
-    if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_row_filter_rgb_kernel, dim3(groups), dim3(256), 0, stream, F);
-    else hipLaunchKernelGGL(ist_png_row_filter_kernel, dim3(groups), dim3(256), 0, stream, F);
-    PNG_HIP(hipGetLastError());
-    if (window) hipLaunchKernelGGL(ist_png_deflate_window_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab), bpp_of(color));
-    else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_adapt_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
-    else hipLaunchKernelGGL(ist_png_deflate_adapt_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, d_rows, static_cast<const uint8_t*>(ftab));
+    launch_row_filter(form, F, widest, stream);
+    IST_HIP(hipGetLastError());
   }
-  else if (window) hipLaunchKernelGGL(ist_png_deflate_window_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B, static_cast<const int64_t*>(nullptr), static_cast<const uint8_t*>(nullptr), bpp_of(color));
-  else if (color == IST_PNG_RGB) hipLaunchKernelGGL(ist_png_deflate_rgb_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
-  else hipLaunchKernelGGL(ist_png_deflate_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, B);
-  PNG_HIP(hipGetLastError());
+  launch_deflate(form, n, stream, B, d_rows, ftab);
+  IST_HIP(hipGetLastError());
   count_png_batch_launch();
-  PNG_HIP(hipStreamSynchronize(stream));
+  IST_HIP(hipStreamSynchronize(stream));
   // ---- host: each file laid out as one slab
   int64_t* dst = reinterpret_cast<int64_t*>(pin.p + h_dst);
   for (size_t k = 0; k < nf; ++k) {
@@ -1787,13 +1787,12 @@ int png_encode_batch_deflate(ist_ctx* ctx, std::vector<PngBatchFile>& files, voi
   }
   GatherBatchArgs G{scratch + o_slots, reinterpret_cast<const uint64_t*>(dst), res};
   hipLaunchKernelGGL(ist_png_gather_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, G);
-  PNG_HIP(hipGetLastError());
+  IST_HIP(hipGetLastError());
   if (!host_patches)
     for (const PngBatchFile& f : files)
-      for (const PngPatch& pt : f.patches) PNG_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
-  PNG_HIP(hipStreamSynchronize(stream));
+      for (const PngPatch& pt : f.patches) IST_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
+  IST_HIP(hipStreamSynchronize(stream));
   drain.armed = false;
-#undef PNG_HIP
   return IST_OK;
 }
 

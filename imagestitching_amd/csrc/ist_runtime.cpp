@@ -21,19 +21,6 @@
 using namespace ist;
 
 namespace ist {
-int ctx_png_level(const ist_ctx* ctx) { return ctx ? ctx->png_level : 0; }
-int ctx_png_color(const ist_ctx* ctx) { return ctx ? ctx->png_color : IST_PNG_RGBA; }
-int ctx_png_filter(const ist_ctx* ctx) { return ctx ? ctx->png_filter : IST_PNG_FILTER_PAETH; }
-int ctx_png_match(const ist_ctx* ctx) { return ctx ? ctx->png_match : IST_PNG_MATCH_RUN; }
-int ctx_png_form_check(const ist_ctx* ctx) {
-  if (ctx && ctx->png_level == 0 && ctx->png_match == IST_PNG_MATCH_WINDOW)
-    return fail(IST_E_UNSUPPORTED, "PNG window matches need the compressing encoder (pngLevel 1): the stored form matches nothing");
-  if (ctx && ctx->png_level == 0 && ctx->png_filter == IST_PNG_FILTER_ADAPTIVE)
-    return fail(IST_E_UNSUPPORTED, "adaptive PNG row filters need the compressing encoder (pngLevel 1): the stored form filters nothing");
-  if (ctx && ctx->png_level == 0 && ctx->png_color == IST_PNG_RGB)
-    return fail(IST_E_UNSUPPORTED, "RGB PNG export needs the compressing encoder (pngLevel 1): the stored form writes RGBA only");
-  return IST_OK;
-}
 int ctx_png_scratch(ist_ctx* ctx, size_t need, void** p) { const int rc = ctx->scratch_png.grow(need); *p = ctx->scratch_png.p; return rc; }
 
 static std::atomic<int64_t> g_dev_allocs{0};
@@ -69,7 +56,7 @@ int ensure_render(ist_ctx* ctx) { return ctx->render.ensure(Stream::kHighest); }
 // at least ist_png_bound bytes (nullptr: the context's own).  The compressing encoder hands the file over slab by slab
 // while it is still compressing (png_encode_device_deflate); the stored form is encoded whole and copied once.
 // Caller holds ctx->mu.  Synchronises ctx->stream.
-int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
+int png_to_host(ist_ctx* ctx, const PngForm& form, const void* canvas, size_t pitch, int64_t w, int64_t h, void* dfile, uint8_t** out_png, int64_t* out_len,
                 const std::function<int(int64_t, void*)>& need_rows_in, int64_t slab_rows_hint, ist_preview* preview) {
   // With a preview: the encoder's request for the canvas's LAST rows is the point behind which every render has been ordered in
   // front of the stream that asked.  The reduce is queued there, on a stream of its own - beside the last slab's compression, not in
@@ -86,7 +73,6 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
     };
   }
   const std::function<int(int64_t, void*)>& need_rows = preview ? with_preview : need_rows_in;
-  { const int rc = ctx_png_form_check(ctx); if (rc) return rc; }
   const int64_t cap = ist_png_bound(w, h);
   if (!dfile) {
     const int rc = ctx->scratch_file.grow(static_cast<size_t>(cap));
@@ -94,12 +80,12 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
     dfile = ctx->scratch_file.p;
   }
   int64_t len = 0;
-  if (ctx->png_level > 0) {
+  if (form.compressed()) {
     { const int rc = ensure_aux(ctx); if (rc) return rc; }
     uint8_t* host = static_cast<uint8_t*>(pool_take(static_cast<size_t>(cap)));
     if (!host) return fail(IST_E_NOMEM, "out of pinned host memory for the result");
     { KeepLastError tolerated; (void)ctx->png2.ensure(); }   // (without it the slabs share one stream)
-    const int rc = png_encode_device_deflate(ctx, canvas, pitch, w, h, dfile, cap, &len, ctx->stream, host, ctx->aux, need_rows, slab_rows_hint, ctx->png2);
+    const int rc = png_encode_device_deflate(ctx, form, canvas, pitch, w, h, dfile, cap, &len, ctx->stream, host, ctx->aux, need_rows, slab_rows_hint, ctx->png2);
     if (rc) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamSynchronize(ctx->stream); if (ctx->png2) (void)hipStreamSynchronize(ctx->png2); pool_give(host); return rc; }
     if (preview) { const int rc2 = tail.finish(); if (rc2) { pool_give(host); return rc2; } }
     *out_png = host; *out_len = len;
@@ -107,7 +93,7 @@ int png_to_host(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64
   }
   int rc = need_rows ? need_rows(h, ctx->stream) : IST_OK;   // (the stored form reads the whole canvas in one pass)
   if (rc) return rc;
-  rc = ist_png_encode_device(ctx, canvas, pitch, w, h, dfile, cap, &len, ctx->stream);
+  rc = png_encode_device_stored(canvas, pitch, w, h, dfile, cap, &len, ctx->stream);
   if (rc) return rc;
   uint8_t* host = nullptr;
   rc = read_back_pooled(dfile, static_cast<size_t>(len), ctx->stream, &host);
@@ -149,30 +135,22 @@ ist_ctx* ist_ctx_create(int device) {
 
 int ist_ctx_set_png_level(ist_ctx* ctx, int level) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (level < 0 || level > 1) return fail(IST_E_INVALID, "PNG level must be 0 (stored) or 1 (compressed)");
-  ctx->png_level = level;
-  return IST_OK;
+  return settings_set(&ctx->settings, kPngLevel, level);
 }
 
 int ist_ctx_set_png_color(ist_ctx* ctx, int color) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (color != IST_PNG_RGBA && color != IST_PNG_RGB) return fail(IST_E_INVALID, "PNG colour must be IST_PNG_RGBA (0) or IST_PNG_RGB (1)");
-  ctx->png_color = color;
-  return IST_OK;
+  return settings_set(&ctx->settings, kPngColor, color);
 }
 
 int ist_ctx_set_png_filter(ist_ctx* ctx, int filter) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (filter != IST_PNG_FILTER_PAETH && filter != IST_PNG_FILTER_ADAPTIVE) return fail(IST_E_INVALID, "PNG filter must be IST_PNG_FILTER_PAETH (0) or IST_PNG_FILTER_ADAPTIVE (1)");
-  ctx->png_filter = filter;
-  return IST_OK;
+  return settings_set(&ctx->settings, kPngFilter, filter);
 }
 
 int ist_ctx_set_png_match(ist_ctx* ctx, int match) {
   if (!ctx) return fail(IST_E_NO_CONTEXT, "无法获取绘图上下文");
-  if (match != IST_PNG_MATCH_RUN && match != IST_PNG_MATCH_WINDOW) return fail(IST_E_INVALID, "PNG match must be IST_PNG_MATCH_RUN (0) or IST_PNG_MATCH_WINDOW (1)");
-  ctx->png_match = match;
-  return IST_OK;
+  return settings_set(&ctx->settings, kPngMatch, match);
 }
 
 int ist_debug_png_grid(int64_t w, int64_t h, int color, int64_t out[4]) {

@@ -113,6 +113,17 @@ def _png_match(match):
     return PNG_MATCHES[match]
 
 
+def _png_form(level=None, color=None, row_filter=None, match=None):
+    """(level, IST_PNG_*, IST_PNG_FILTER_*, IST_PNG_MATCH_*) of a call's PNG options, checked - colour, filter, match, level: in that
+    order - before any library call.  level None: DEFAULT_PNG_LEVEL."""
+    form = _png_color(color), _png_filter(row_filter), _png_match(match)
+    return (int(DEFAULT_PNG_LEVEL if level is None else level),) + form
+
+
+def _opts_png_form(o):
+    return _png_form(o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"])
+
+
 def debug_png_grid(w, h, color="rgba"):
     """(n_chunks, rows_per_chunk (0: pieces of a row), pieces_per_row, piece_px) of the compressing encoder's chunk grid for a w x h
     canvas in a colour form (ist_debug_png_grid).  Pure CPU."""
@@ -445,15 +456,15 @@ def _ctx_color(device, profile):
     return c
 
 
-def _ctx_png(device, level, color=None, row_filter=None, match=None):
+def _ctx_png(device, form=None):
     """The context with its PNG export form set (ist_ctx_set_png_level, ist_ctx_set_png_color, ist_ctx_set_png_filter,
     ist_ctx_set_png_match - level, colour, row filter and matches together, so a call never inherits the colour, the filter or the
     matches of the one before it): a per-context setting, so concurrent callers that want different forms on one device should
-    serialise.  An unknown colour or filter raises ValueError, an unknown match TypeError, before the context is asked for."""
-    form, filt, mat = _png_color(color), _png_filter(row_filter), _png_match(match)
+    serialise.  form: what _png_form returned (a bare level stands for _png_form(level): that level in the default form)."""
+    level, color, filt, mat = form if isinstance(form, tuple) else _png_form(form)
     c = _ctx(device)
-    L.check(L.lib.ist_ctx_set_png_level(c, int(DEFAULT_PNG_LEVEL if level is None else level)))
-    L.check(L.lib.ist_ctx_set_png_color(c, form))
+    L.check(L.lib.ist_ctx_set_png_level(c, level))
+    L.check(L.lib.ist_ctx_set_png_color(c, color))
     L.check(L.lib.ist_ctx_set_png_filter(c, filt))
     L.check(L.lib.ist_ctx_set_png_match(c, mat))
     return c
@@ -538,7 +549,7 @@ def _stitch(images, direction, o, device, kind, jpeg=()):
         devs = (C.c_int * len(o["devices"]))(*[int(d) for d in o["devices"]])
         name, head, mid = name + "_multi", (devs, len(devs)), (_SPLITS[o["split"]],)
     else:
-        head, mid = (_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"]) if kind == "png" else _ctx(device),), jpeg
+        head, mid = (_ctx_png(device, _opts_png_form(o)) if kind == "png" else _ctx(device),), jpeg
     # (rgba8, what the N-API addon binds: plan, render, and the export as ONE DMA into a pinned block of the library's pool; the numpy
     # array below is a view of that block - no host copy - and returns it to the pool when it is garbage collected)
     fn = getattr(L.lib, name + ("_preview" if pv is not None else ""))
@@ -633,11 +644,9 @@ def stitch_png_batch(requests, device=0, level=None, color=None, row_filter=None
     reqs = list(requests)
     if not reqs:
         return []
-    _png_color(color)
-    _png_filter(row_filter)
-    _png_match(match)
+    form = _png_form(level, color, row_filter, match)
     creqs, keep = _batch_requests(reqs, "one GPU, one PNG form for the whole batch: level=, color=, row_filter=, match=")
-    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, level, color, row_filter, match), creqs, key="png")
+    return _run_batch(L.lib.ist_stitch_png_batch, _ctx_png(device, form), creqs, key="png")
 
 
 def launch_jobs(jobs, srcs, outs, stream=None):
@@ -864,9 +873,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     stitch launch -> PNG export on the GPU.  Only file bytes go in and PNG bytes come out over PCIe.
     Returns {'width','height','png'} and writes out_path when given.  The mini-program's whole onStitch: index.js:1441-1581."""
     o = _merge(opts, color=True)
-    _png_color(o["pngColor"])
-    _png_filter(o["pngFilter"])
-    _png_match(o["pngMatch"])
+    form = _opts_png_form(o)
     _color_profile(o["colorProfile"])
     n = len(paths)
     if n == 0:
@@ -878,7 +885,7 @@ def stitch_files(paths, direction, opts=None, out_path=None, device=0, copy=True
     pv = _preview_arg(o)
     fn = L.lib.ist_stitch_paths_png if pv is None else L.lib.ist_stitch_paths_png_preview
     _ctx_color(device, o["colorProfile"])
-    size = _plan_size(L.check(fn(_ctx_png(device, o["pngLevel"], o["pngColor"], o["pngFilter"], o["pngMatch"]), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
+    size = _plan_size(L.check(fn(_ctx_png(device, form), cpaths, n, *_plan_args(direction, o), C.byref(cplan), C.byref(out), C.byref(ln),
                                  *([] if pv is None else [C.byref(pv)]))), cplan)
     if size is None:
         return None
@@ -900,12 +907,10 @@ def encode_png(pixels, device=0, level=None, color=None, row_filter=None, match=
     ist_ctx_set_png_filter; `filter` is the resampling filter, hence the name).  match 'run' (default: runs of equal bytes inside a
     64-byte span) or 'window' (a chunk also copies from its earlier spans, found on the GPU; never a larger file, half the bytes
     on rendered text (profiles/r17_png_match.json), a slower encoder; level 1 only - ist_ctx_set_png_match)."""
-    _png_color(color)
-    _png_filter(row_filter)
-    _png_match(match)
+    form = _png_form(level, color, row_filter, match)
     a, ptr, pitch = _host_rows(_rgba(pixels))
     out, n = C.POINTER(C.c_uint8)(), C.c_int64(0)
-    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, level, color, row_filter, match), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
+    L.check(L.lib.ist_png_encode_rgba8(_ctx_png(device, form), ptr, pitch, a.shape[1], a.shape[0], C.byref(out), C.byref(n)))
     return _take_png(out, n)
 
 
@@ -914,18 +919,14 @@ def stitch_png(images, direction, opts=None, device=0):
     canvas stays on the device; only the PNG crosses PCIe.  images are marshalled as stitch() marshals them (padded views are read
     where they are); they may be a list of Bitmaps."""
     o = _merge(opts, overlap=True)
-    _png_color(o["pngColor"])
-    _png_filter(o["pngFilter"])
-    _png_match(o["pngMatch"])
+    _opts_png_form(o)
     return _stitch(images, direction, o, device, "png")
 
 
 def encode_png_device(canvas, out=None, stream=None, device=None, level=None, color=None, row_filter=None, match=None):
     """PNG of a canvas that is resident in HBM (HxWx4 uint8 CUDA tensor) into a CUDA uint8 tensor; returns (tensor, length).
     level, color, row_filter, match: as encode_png."""
-    _png_color(color)
-    _png_filter(row_filter)
-    _png_match(match)
+    form = _png_form(level, color, row_filter, match)
     import torch
     _check_canvas(canvas, "encode_png_device: ")
     h, w = int(canvas.shape[0]), int(canvas.shape[1])
@@ -933,7 +934,7 @@ def encode_png_device(canvas, out=None, stream=None, device=None, level=None, co
     st = stream if stream is not None else torch.cuda.current_stream(canvas.device)
     n = C.c_int64(0)
     dev = canvas.device.index if device is None else device
-    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, level, color, row_filter, match), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
+    L.check(L.lib.ist_png_encode_device(_ctx_png(dev or 0, form), C.c_void_p(canvas.data_ptr()), canvas.stride(0), w, h,
                                         C.c_void_p(dst), cap, C.byref(n), C.c_void_p(st.cuda_stream)))
     return out[off:off + n.value], n.value
 
@@ -1056,10 +1057,8 @@ def encode_png_batch_device(canvases, outs=None, stream=None, level=None, color=
     """PNG files of many canvases resident in HBM (HxWx4 uint8 CUDA tensors of one device, any row pitch) in ONE compression
     launch (ist_png_encode_batch_device).  outs: optional CUDA uint8 tensors of at least ist_png_bound + 16 bytes each.  Returns
     [(tensor, length)], each file byte for byte what encode_png_device gives for that canvas at the same level, color, row_filter and match."""
-    _png_color(color)
-    _png_filter(row_filter)
-    _png_match(match)
-    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, level, color, row_filter, match), "encode_png_batch_device", list(canvases),
+    form = _png_form(level, color, row_filter, match)
+    return _encode_batch_device(L.lib.ist_png_encode_batch_device, lambda d: _ctx_png(d, form), "encode_png_batch_device", list(canvases),
                                 lambda k, w, h: L.lib.ist_png_bound(w, h), outs, stream)
 
 

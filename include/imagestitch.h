@@ -299,7 +299,8 @@ IST_API int ist_ctx_set_png_level(ist_ctx* ctx, int level);
  * is an upper bound for both forms.
  * IST_E_NO_CONTEXT for a NULL context, IST_E_INVALID for any other value.  The stored form (level 0) writes RGBA only: on a
  * context at level 0 with IST_PNG_RGB every *_png call fails with IST_E_UNSUPPORTED before anything is enqueued (the message
- * names pngLevel 1). */
+ * names pngLevel 1).  The setting is sampled once, when a call starts: a setter that
+ * runs while a call is in flight changes the next call, never part of this one. */
 enum { IST_PNG_RGBA = 0, IST_PNG_RGB = 1 };
 IST_API int ist_ctx_set_png_color(ist_ctx* ctx, int color);
 /* PNG row filters for every *_png entry point of this context (single, batch, bitmaps, files, paths, *_png_preview, ist_render_png
@@ -321,7 +322,8 @@ IST_API int ist_ctx_set_png_color(ist_ctx* ctx, int color);
  * lose a fraction of a per cent on a screenshot, which is why it is not the default.
  * IST_E_NO_CONTEXT for a NULL context, IST_E_INVALID for any other value.  The stored form (level 0) filters nothing: on a context
  * at level 0 with IST_PNG_FILTER_ADAPTIVE every *_png call fails with IST_E_UNSUPPORTED before anything is enqueued (the message
- * names pngLevel 1). */
+ * names pngLevel 1).  The setting is sampled once, when a call starts: a setter that
+ * runs while a call is in flight changes the next call, never part of this one. */
 enum { IST_PNG_FILTER_PAETH = 0, IST_PNG_FILTER_ADAPTIVE = 1 };
 IST_API int ist_ctx_set_png_filter(ist_ctx* ctx, int filter);
 /* PNG matches for every *_png entry point of this context (single, batch, bitmaps, files, paths, *_png_preview, ist_render_png and
@@ -345,7 +347,8 @@ IST_API int ist_ctx_set_png_filter(ist_ctx* ctx, int filter);
  * keep the run form in nearly every chunk, and the encoder takes several times as long, which is why it is not the default.
  * IST_E_NO_CONTEXT for a NULL context, IST_E_INVALID for any other value.  The stored form (level 0) matches nothing: on a context at
  * level 0 with IST_PNG_MATCH_WINDOW every *_png call fails with IST_E_UNSUPPORTED before anything is enqueued (the message names
- * pngLevel 1). */
+ * pngLevel 1).  The setting is sampled once, when a call starts: a setter that
+ * runs while a call is in flight changes the next call, never part of this one. */
 enum { IST_PNG_MATCH_RUN = 0, IST_PNG_MATCH_WINDOW = 1 };
 IST_API int ist_ctx_set_png_match(ist_ctx* ctx, int match);
 /* compile an op list for a canvas (replaces createOffscreenCanvas + the recorded draw calls; utils/canvas.js:131,

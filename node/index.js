@@ -393,34 +393,40 @@ function encodeJpeg(data, width, height, opts) { const j = jpegArgs(opts); retur
  *  (photographs about half, screenshots a few per cent). A process-wide setting of the native context. */
 function pngLevel(opts) { if (opts && opts.pngLevel !== undefined && opts.pngLevel !== null) native.setPngLevel(opts.pngLevel | 0); }
 function setPngLevel(level) { native.setPngLevel(level | 0); }
+/** The native value of opts[key], one of the names of `table` (null: not given); anything else is a TypeError before any native call. */
+function pngOption(opts, key, table, message) {
+  const v = opts ? opts[key] : undefined;
+  if (v === undefined || v === null) return null;
+  if (typeof v !== 'string' || !Object.prototype.hasOwnProperty.call(table, v)) throw new TypeError(message);
+  return table[v];
+}
+/** setPngColor / setPngFilter / setPngMatch: the option's check, then its native setter (a missing value is refused too). */
+function pngSetter(of, key, message, apply) {
+  return (value) => {
+    const v = of({ [key]: value });
+    if (v === null) throw new TypeError(message);
+    native[apply](v);
+  };
+}
 /** opts.pngColor: 'rgba' = colour type 6 (default), 'rgb' = colour type 2 - alpha is not read (every stitched canvas is opaque; a
  *  caller with a translucent one composites it first), pngLevel 1 only: 12-17 per cent fewer bytes on photographs. A process-wide
  *  setting of the native context, like pngLevel; an unknown value is a TypeError before any native call. */
 const PNG_COLOR = { rgba: 0, rgb: 1 };             // IST_PNG_RGBA / IST_PNG_RGB
-function pngColorOf(opts) {
-  if (!opts || opts.pngColor === undefined || opts.pngColor === null) return null;
-  if (typeof opts.pngColor !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_COLOR, opts.pngColor)) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
-  return PNG_COLOR[opts.pngColor];
-}
+const PNG_COLOR_ERR = "pngColor must be 'rgba' or 'rgb'";
+function pngColorOf(opts) { return pngOption(opts, 'pngColor', PNG_COLOR, PNG_COLOR_ERR); }
 /** opts.pngFilter: 'paeth' = filter type 4 on every row (default), 'adaptive' = a type per row, chosen on the GPU by the least sum of
  *  absolute residuals (include/imagestitch.h states the rule), pngLevel 1 only: 6-7 per cent fewer bytes on photographs, 1-4 on flat
  *  content. A process-wide setting of the native context, like pngColor; an unknown value is a TypeError before any native call. */
 const PNG_FILTER = { paeth: 0, adaptive: 1 };      // IST_PNG_FILTER_PAETH / IST_PNG_FILTER_ADAPTIVE
-function pngFilterOf(opts) {
-  if (!opts || opts.pngFilter === undefined || opts.pngFilter === null) return null;
-  if (typeof opts.pngFilter !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_FILTER, opts.pngFilter)) throw new TypeError("pngFilter must be 'paeth' or 'adaptive'");
-  return PNG_FILTER[opts.pngFilter];
-}
+const PNG_FILTER_ERR = "pngFilter must be 'paeth' or 'adaptive'";
+function pngFilterOf(opts) { return pngOption(opts, 'pngFilter', PNG_FILTER, PNG_FILTER_ERR); }
 /** opts.pngMatch: 'run' = runs of equal bytes inside a 64-byte span (default), 'window' = a chunk also copies from its earlier spans,
  *  found on the GPU (include/imagestitch.h states the rule), pngLevel 1 only: never a larger file, half the bytes on rendered text
  *  (profiles/r17_png_match.json), a slower encoder. A process-wide setting of the native context, like pngColor; an unknown value is a TypeError
  *  before any native call. */
 const PNG_MATCH = { run: 0, window: 1 };      // IST_PNG_MATCH_RUN / IST_PNG_MATCH_WINDOW
-function pngMatchOf(opts) {
-  if (!opts || opts.pngMatch === undefined || opts.pngMatch === null) return null;
-  if (typeof opts.pngMatch !== 'string' || !Object.prototype.hasOwnProperty.call(PNG_MATCH, opts.pngMatch)) throw new TypeError("pngMatch must be 'run' or 'window'");
-  return PNG_MATCH[opts.pngMatch];
-}
+const PNG_MATCH_ERR = "pngMatch must be 'run' or 'window'";
+function pngMatchOf(opts) { return pngOption(opts, 'pngMatch', PNG_MATCH, PNG_MATCH_ERR); }
 function pngForm(opts) {
   const c = pngColorOf(opts), f = pngFilterOf(opts), m = pngMatchOf(opts);          // (all checked before the first native call)
   pngLevel(opts);
@@ -428,21 +434,9 @@ function pngForm(opts) {
   if (f !== null) native.setPngFilter(f);
   if (m !== null) native.setPngMatch(m);
 }
-function setPngMatch(match) {
-  const m = pngMatchOf({ pngMatch: match });
-  if (m === null) throw new TypeError("pngMatch must be 'run' or 'window'");
-  native.setPngMatch(m);
-}
-function setPngFilter(filter) {
-  const f = pngFilterOf({ pngFilter: filter });
-  if (f === null) throw new TypeError("pngFilter must be 'paeth' or 'adaptive'");
-  native.setPngFilter(f);
-}
-function setPngColor(color) {
-  const c = pngColorOf({ pngColor: color });
-  if (c === null) throw new TypeError("pngColor must be 'rgba' or 'rgb'");
-  native.setPngColor(c);
-}
+const setPngMatch = pngSetter(pngMatchOf, 'pngMatch', PNG_MATCH_ERR, 'setPngMatch');
+const setPngFilter = pngSetter(pngFilterOf, 'pngFilter', PNG_FILTER_ERR, 'setPngFilter');
+const setPngColor = pngSetter(pngColorOf, 'pngColor', PNG_COLOR_ERR, 'setPngColor');
 /** PNG file bytes -> {width, height, data} (RGBA8, straight alpha). Host decode: the Image.src step for 'png' inputs
  *  (utils/canvas.js:27-121; SUPPORTED_IMAGE_TYPES, index.js:4). JPEG / WebP / HEIC are not built: err.code '-7'. */
 function decodePng(file) { return native.decodePng(file); }

@@ -5,6 +5,7 @@
 #   tools/run_fuzz.sh jpegbatch ITERS [SEED]      random batches through the rounds, header blob and piece records of the batched JPEG export
 #   tools/run_fuzz.sh jpegoptimize ITERS [SEED]   random + adversarial symbol counts through the optimal-table builder and the DHT / header writer
 #   tools/run_fuzz.sh icc ITERS [SEED]            random + adversarial ICC profiles, bare and inside JPEG / PNG / WebP containers, through the colour-profile parser
+#   tools/run_fuzz.sh settings [ITERS]            ThreadSanitizer (its own flags, not the ASan set): setter and reader threads on the context's settings word
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); C=$ROOT/imagestitching_amd/csrc
 OUT=${IST_FUZZ_BIN:-/tmp/ist_fuzz}
@@ -22,6 +23,9 @@ elif [ "$1" = jpegoptimize ]; then
 elif [ "$1" = icc ]; then
   shift
   g++ $FLAGS "$HERE/check_icc_host.cpp" "$C/ist_icc.cpp" "$C/ist_png_decode.cpp" "$C/ist_image_misc.cpp" "$C/ist_jpeg.cpp" "$C/ist_webp.cpp" "$C/ist_webp_vp8.cpp" "$C/ist_plan.cpp" -lz -o "$OUT"
+elif [ "$1" = settings ]; then
+  shift
+  g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -I"$C" "$HERE/check_settings_host.cpp" -o "$OUT"
 else
   # (IST_FUZZ_REUSE=1: keep a binary that is already there - the tests build the harness once per session)
   if [ -z "$IST_FUZZ_REUSE" ] || [ ! -x "$OUT" ]; then
