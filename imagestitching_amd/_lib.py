@@ -118,6 +118,15 @@ class JpegCoefInfo(C.Structure):
                 ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3)]
 
 
+class JpegJoinInfo(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("image", C.c_int32), ("subsampling", C.c_int32), ("reserved", C.c_int32),
+                ("width", C.c_int64), ("height", C.c_int64)]
+
+
+# IST_JOIN_*: the reason codes of ist_jpeg_join_check, by value
+JOIN_REASONS = ("ok", "not_jpeg", "layout", "mixed", "tables", "size", "align", "orient", "limit", "range")
+
+
 class ColorTables(C.Structure):
     _fields_ = [("kind", C.c_int32), ("mq", (C.c_int32 * 3) * 3), ("dec", (C.c_uint16 * 256) * 3)]
 
@@ -302,6 +311,10 @@ SYMBOLS = [
     ("ist_icc_tables", C.c_int, [C.c_char_p, C.c_int64, C.POINTER(ColorTables)]),
     ("ist_color_convert_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.POINTER(ColorTables), C.c_void_p]),
     ("ist_debug_color_launches", C.c_int64, []),
+    ("ist_jpeg_join_check", C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(JpegJoinInfo)]),
+    ("ist_jpeg_join_files", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(JpegJoinInfo),
+                                      C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int64)]),
+    ("ist_debug_jpeg_join_launches", C.c_int64, []),
 ]
 
 if not os.path.exists(LIB_PATH):

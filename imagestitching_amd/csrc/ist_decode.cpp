@@ -63,10 +63,8 @@ JpegDeviceJob jpeg_device_job(const JpegImage& J, uint8_t* d, const JpegDevLayou
   return job;
 }
 
-int jpeg_enqueue(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLayout& L, uint8_t* d_out, size_t out_pitch, hipStream_t stream, bool coef_on_device = false,
-                 bool chroma_done = false, int denom = 1) {
-  JpegDeviceJob job = jpeg_device_job(J, d, L, d_out, out_pitch);
-  job.chroma_done = chroma_done; job.denom = denom;
+// the coefficients of an image into its dense device planes at L.coef (coef_on_device: the GPU entropy decoder already filled them)
+int jpeg_upload_coefficients(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLayout& L, hipStream_t stream, bool coef_on_device) {
   for (int c = 0; c < J.ncomp; ++c) {
     const JpegComp& C = J.comp[c];
     const size_t nblk = static_cast<size_t>(C.blocks_x) * C.blocks_y;
@@ -86,6 +84,15 @@ int jpeg_enqueue(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLa
       IST_HIP(hipMemcpyAsync(d_coef, C.coef.data(), nblk * 128, hipMemcpyHostToDevice, stream));
     }
   }
+  return IST_OK;
+}
+
+int jpeg_enqueue(const JpegImage& J, uint8_t* d, uint8_t* d_ent, const JpegDevLayout& L, uint8_t* d_out, size_t out_pitch, hipStream_t stream, bool coef_on_device = false,
+                 bool chroma_done = false, int denom = 1) {
+  JpegDeviceJob job = jpeg_device_job(J, d, L, d_out, out_pitch);
+  job.chroma_done = chroma_done; job.denom = denom;
+  const int rc = jpeg_upload_coefficients(J, d, d_ent, L, stream, coef_on_device);
+  if (rc) return rc;
   return denom > 1 ? jpeg_launch_reconstruct_scaled(job, stream) : jpeg_launch_reconstruct(job, stream);      // (1 / 1: the full-size launches and nothing else)
 }
 
@@ -299,6 +306,7 @@ int FileDecoder::start(uint8_t* arena, uint8_t* const* img, const size_t* pitch)
   ph_->lap(IST_PHASE_HOST_DECODE, "decode on host threads (+ scan uploads)", nullptr);
   rc2 = huffman_all(ctx_->stream); if (rc2) return rc2;
   ph_->lap(IST_PHASE_ENTROPY_GPU, "entropy decode (GPU)", ctx_->stream);
+  if (coef_only_) return IST_OK;                  // (no bitmap is made: coefficients() does the rest)
   for (int i = 0; i < n_; ++i) { rc2 = take(i, ctx_->stream); if (rc2) return rc2; }
   ph_->lap(IST_PHASE_RECONSTRUCT, "H2D + JPEG reconstruct (GPU)", ctx_->stream);
   return IST_OK;
@@ -334,8 +342,19 @@ int FileDecoder::place(int i, hipStream_t consumer) {
     else up.push_back(RowsCopy{img_[i], D.px.data(), nullptr, row, row, static_cast<size_t>(D.h)});
     return stager_of(ctx_).upload(up, consumer);
   }
-  // a JPEG whose coefficients are on the host (progressive, non-interleaved scans, thousands of restart intervals, or a file that
-  // failed the GPU decoder's validation and is decoded again by the host decoder)
+  JpegDevLayout L;
+  rc = host_coefficients(i, consumer, &L);
+  if (rc) return rc;
+  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, img_[i], pitch_[i], consumer, false, false, denom_of(i));
+}
+
+// A JPEG whose coefficients are on the host (progressive, non-interleaved scans, thousands of restart intervals, or a file that
+// failed the GPU decoder's validation and is decoded again by the host decoder here): *L = its layout with the sparse part in the
+// context's entry block, which is grown for it
+int FileDecoder::host_coefficients(int i, hipStream_t consumer, JpegDevLayout* out) {
+  const size_t k = static_cast<size_t>(i);
+  int rc = IST_OK;
+  Dec& D = dec_[k];
   if (D.G.eligible) {
     D.G.eligible = false;
     JpegImage host;
@@ -351,7 +370,44 @@ int FileDecoder::place(int i, hipStream_t consumer) {
     rc = ctx_->scratch_ent.grow(need, need / 2);
     if (rc) return rc;
   }
-  return jpeg_enqueue(D.J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, img_[i], pitch_[i], consumer, false, false, denom_of(i));
+  *out = L;
+  return IST_OK;
+}
+
+void FileDecoder::layout_coefficients(size_t* off) {
+  coef_only_ = true;
+  for (int i = 0; i < n_; ++i) {
+    const Dec& D = dec_[static_cast<size_t>(i)];
+    if (!D.jpeg) continue;
+    JpegDevLayout& L = jo_[static_cast<size_t>(i)];
+    std::memset(&L, 0, sizeof L);
+    for (int c = 0; c < D.J.ncomp; ++c) L.coef[c] = arena_take(off, static_cast<size_t>(D.J.comp[c].blocks_x) * D.J.comp[c].blocks_y * 128);
+  }
+}
+
+int FileDecoder::coefficients(hipStream_t consumer, std::vector<JpegCoefPlanes>* out) {
+  int rc = huffman_all(consumer);
+  if (rc) return rc;
+  out->assign(static_cast<size_t>(n_), JpegCoefPlanes{});
+  for (int i = 0; i < n_; ++i) {
+    const size_t k = static_cast<size_t>(i);
+    if (!dec_[k].jpeg) return fail(IST_E_INVALID, "image " + std::to_string(i) + " is not a JPEG: it has no coefficients");
+    if (!on_gpu_[k] && !taken_[k]) {
+      JpegDevLayout L;
+      rc = host_coefficients(i, consumer, &L);
+      if (rc) return rc;
+      rc = jpeg_upload_coefficients(dec_[k].J, arena_, static_cast<uint8_t*>(ctx_->scratch_ent.p), L, consumer, false);
+      if (rc) return rc;
+    }
+    taken_[k] = 1;
+    const JpegImage& J = dec_[k].J;
+    JpegCoefPlanes& P = (*out)[k];
+    for (int c = 0; c < J.ncomp; ++c) {
+      P.coef[c] = reinterpret_cast<const int16_t*>(arena_ + jo_[k].coef[c]);
+      P.blocks_x[c] = J.comp[c].blocks_x; P.blocks_y[c] = J.comp[c].blocks_y;
+    }
+  }
+  return IST_OK;
 }
 
 int FileDecoder::finish(hipStream_t consumer) {

@@ -55,8 +55,18 @@ class FileDecoder {
   int take(int i, hipStream_t consumer);
   int finish(hipStream_t consumer);       // take() for every image not taken yet
   int gpu_decoded() const;                // images the GPU entropy decoder took
+  // Stopping at the coefficients (the lossless join): layout_coefficients() in place of layout() carves the dense coefficient planes
+  // and nothing else (no table, no sample plane); start() then takes NULL img / pitch; coefficients() in place of take() / finish()
+  // does what the first take() does (waits for the host side, runs the Huffman batch on `consumer`) and then, per file, what place()
+  // does up to the planes: nothing for a file the GPU decoder took, the sparse entries uploaded and scattered into the zeroed plane
+  // for a host-decoded sequential file, the dense upload for a progressive one.  No reconstruction launch, no bitmap.  Every file
+  // must be a JPEG.  out[i]: the planes of file i, complete on `consumer`.
+  void layout_coefficients(size_t* off);
+  int coefficients(hipStream_t consumer, std::vector<JpegCoefPlanes>* out);
 
  private:
+  int host_coefficients(int i, hipStream_t consumer, JpegDevLayout* out);
+  bool coef_only_ = false;
   hipStream_t stream_of(int i) const;
   int denom_of(int i) const;
   void join_all();

@@ -158,7 +158,10 @@ int exif_orientation(const uint8_t* d, size_t n) {
 
 constexpr uint32_t kMaxGpuIntervals = 2048;
 
-static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool header_only, JpegGpuScan* gs) {
+// tables_only: the segments are walked and the scan headers read as a decode would (the colour space and the components'
+// quantisation tables are latched where a decode latches them), up to the scan header that fixes the last component's table; no
+// entropy-coded byte is decoded: what a lossless join needs to know of a file before it spends anything on it
+static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool header_only, JpegGpuScan* gs, bool tables_only = false) {
   if (!f || n < 4 || f[0] != 0xFF || f[1] != 0xD8) return fail(IST_E_DECODE, "not a JPEG file");
   Huff dc[4], ac[4];
   uint16_t qt[4][64]; bool have_q[4] = {false, false, false, false};
@@ -274,6 +277,20 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
       const bool dc_scan = Ss == 0, need_ac = !progressive || !dc_scan, need_dc = dc_scan && Ah == 0;
       for (int s = 0; s < ns; ++s) {
         if ((need_dc && !dc[td[s]].present) || (need_ac && !ac[ta[s]].present)) return fail(IST_E_DECODE, "JPEG scan uses an undefined Huffman table");
+      }
+      if (tables_only) {
+        for (int s = 0; s < ns; ++s)
+          if (!latch(ci[s])) return fail(IST_E_DECODE, "JPEG component uses an undefined quantisation table");
+        J->scans++;
+        bool all = true;
+        for (int c = 0; c < J->ncomp; ++c) all = all && latched[c];
+        if (all) return IST_OK;                    // every table is fixed: nothing behind this scan header changes the answer (a photo's 3 MB of scan are not walked)
+        --J->scans;
+        const uint8_t* q = d + dl;                 // behind the entropy-coded segment: the next marker that is neither stuffing nor RSTn
+        while (q + 1 < f + n && !(q[0] == 0xFF && q[1] != 0x00 && q[1] != 0xFF && !(q[1] >= 0xD0 && q[1] <= 0xD7))) ++q;
+        pos = q - f;
+        J->scans++;
+        continue;
       }
       // the GPU entropy decoder takes baseline files whose single scan interleaves all components (restart intervals or not)
       int mcu_blocks = 0;
@@ -565,6 +582,11 @@ static int jpeg_parse_inner(const uint8_t* f, int64_t n, JpegImage* J, bool head
 int jpeg_parse_and_entropy_decode(const uint8_t* f, int64_t n, JpegImage* J, bool header_only, JpegGpuScan* gs) {
   try { return jpeg_parse_inner(f, n, J, header_only, gs); }
   catch (const std::bad_alloc&) { return fail(IST_E_NOMEM, "out of memory while decoding the JPEG"); }
+}
+
+int jpeg_parse_tables(const uint8_t* f, int64_t n, JpegImage* J) {
+  try { return jpeg_parse_inner(f, n, J, false, nullptr, true); }
+  catch (const std::bad_alloc&) { return fail(IST_E_NOMEM, "out of memory while reading the JPEG"); }
 }
 
 // The ICC profile of a file (ist_icc.h): the APP2 "ICC_PROFILE\0" chunks in front of the first scan, joined in seq order.  A walk of

@@ -120,11 +120,20 @@ struct JpegGpuScan {
   JpegGpuTables tables;
 };
 
+// one file's quantised coefficients on the device: per component blocks_y x blocks_x x 64 int16, natural order, DC integrated
+struct JpegCoefPlanes { const int16_t* coef[3] = {nullptr, nullptr, nullptr}; int32_t blocks_x[3] = {0, 0, 0}, blocks_y[3] = {0, 0, 0}; };
+
 // container parsing + Huffman decoding (host).  header_only stops after the frame header (size, sampling, orientation
 // if the EXIF segment precedes it).  Returns IST_OK or an error code with the thread-local message set.
 int jpeg_parse_and_entropy_decode(const uint8_t* file, int64_t len, JpegImage* out, bool header_only, JpegGpuScan* gpu_scan = nullptr);
 // With gpu_scan: when the file qualifies (gpu_scan->eligible) the scan is NOT decoded on the host; the components then
 // carry neither dense nor sparse coefficients and jpeg_gpu_entropy_decode fills the device planes.
+
+// The same walk over the same segments without decoding a scan, up to the scan header that fixes the last component's quantisation
+// table: size, sampling, colour space, orientation (of an EXIF segment in front of that scan), and every component's table as a decode
+// would latch it (the one in force when the component's first scan starts).  The errors of the container and of the scan headers up
+// to there are the decode's; damage behind it is not seen.
+int jpeg_parse_tables(const uint8_t* file, int64_t len, JpegImage* out);
 
 // GPU stages (ist_jpeg_kernels.hip): coefficient planes (device) -> RGBA8 (device).  d_coef[c] / q_host[c] per component,
 // planes = scratch for the reconstructed sample planes.  Asynchronous on `stream`.

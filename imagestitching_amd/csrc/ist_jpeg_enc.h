@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "../../include/imagestitch.h"
@@ -63,6 +64,10 @@ struct JpegHuffSpec { uint8_t bits[4][16]; uint8_t vals[4][256]; int n[4]; };
 int jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[256]);
 // an optimised file's tables from its counts (kJpegCounters of them): the codes into T->dc / T->ac (0: no code), the specs into H
 void jpeg_enc_tables_optimal(int quality, const int64_t* counts, JpegTables* T, JpegHuffSpec* H);
+// ... the codes alone: T keeps its quantisation tables (whatever they came from)
+void jpeg_enc_codes_optimal(const int64_t* counts, JpegTables* T, JpegHuffSpec* H);
+// the Annex K codes beside quantisation tables that are given as data (natural order): what a lossless join writes back
+void jpeg_enc_tables_of(const uint8_t luma[64], const uint8_t chroma[64], JpegTables* T);
 // SOI, APP0, DQT x 2, DHT x 4 (H, or Annex K when NULL), DRI, SOF0, SOS
 std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart, const JpegHuffSpec* H = nullptr);
 
@@ -109,6 +114,22 @@ struct JpegOptFile { int hist = -1; bool built = false; JpegTables T; std::vecto
 // quantisers (what the transform reads) and a header of the most bytes.
 void jpeg_round_pack(const JpegRound& R, const JpegBatchFile* files, const ist_jpeg_piece* pieces, uint8_t* host, const uint8_t* dev,
                      uint8_t* scratch, const JpegOptFile* opt = nullptr);
+
+// ---- one file, slab by slab (ist_jpeg_encode.hip) ----
+// The single-file encoder's loop with "fill the slab's scratch" left to the caller: fill(r0, rows, coef, tab, stream) enqueues on
+// `stream` whatever leaves MCU rows [r0, r0 + rows) of the w x h file in `coef` (blocks in coding order, 64 int16 each in zig-zag
+// order); tab: the file's tables on the device.  A canvas fills it with the transform kernel, a join with its own.  With
+// IST_JPEG_OPTIMIZE and more than one slab every slab is filled twice.  synced (optional) is called behind every synchronisation of
+// `stream` that follows a fill; what it returns other than IST_OK ends the call.
+struct JpegSlabSource {
+  std::function<int(int64_t r0, int64_t rows, int16_t* coef, const JpegTables* tab, void* stream)> fill;
+  std::function<int()> synced;
+};
+// T: the file's quantisation tables with the Annex K codes (jpeg_enc_tables / jpeg_enc_tables_of).  `out`: device, 16-byte aligned,
+// cap >= ist_jpeg_bound.  Synchronises `stream`.
+int jpeg_encode_slabs(ist_ctx* ctx, int64_t w, int64_t h, int subsampling, const JpegTables& T, void* out, int64_t cap, int64_t* out_len,
+                      void* stream, const JpegSlabSource& src);
+int64_t jpeg_slab_rows(const JpegGeometry& g);   // MCU rows per slab: what kJpegEncBudget holds, or IST_TUNING=1 IST_JPEG_ENC_ROWS=<rows>
 
 int64_t jpeg_batch_budget();                     // kJpegEncBudget, or IST_TUNING=1 IST_JPEG_ENC_BUDGET=<bytes> (read once)
 int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k);      // the rules of ist_jpeg_encode_device for file k (message: "<what> k: ...")

@@ -121,6 +121,10 @@ int jpeg_optimal_table(const int64_t freq[256], uint8_t bits[16], uint8_t vals[2
 
 void jpeg_enc_tables_optimal(int quality, const int64_t* counts, JpegTables* T, JpegHuffSpec* H) {
   jpeg_enc_tables(quality, T);
+  jpeg_enc_codes_optimal(counts, T, H);
+}
+
+void jpeg_enc_codes_optimal(const int64_t* counts, JpegTables* T, JpegHuffSpec* H) {
   std::memset(T->dc, 0, sizeof T->dc); std::memset(T->ac, 0, sizeof T->ac);
   std::memset(H, 0, sizeof *H);
   for (int tc = 0; tc < 2; ++tc)
@@ -145,6 +149,11 @@ void jpeg_enc_tables(int quality, JpegTables* T) {
   for (int s = 0; s < 2; ++s) { huff_codes(kDcBits[s], kDcVals, T->dc[s]); huff_codes(kAcBits[s], kAcVals[s], T->ac[s]); }
   jpeg_quant_tables(quality, T->q[0], T->q[1]);
   for (int k = 0; k < 64; ++k) T->zz_of[kZigzag[k]] = static_cast<uint8_t>(k);
+}
+
+void jpeg_enc_tables_of(const uint8_t luma[64], const uint8_t chroma[64], JpegTables* T) {
+  jpeg_enc_tables(50, T);
+  std::memcpy(T->q[0], luma, 64); std::memcpy(T->q[1], chroma, 64);
 }
 
 std::vector<uint8_t> jpeg_enc_header(int64_t w, int64_t h, int subsampling, const JpegTables& T, int64_t restart, const JpegHuffSpec* H) {

@@ -486,6 +486,8 @@ int check_args(const char* who, const void* canvas, size_t pitch, int64_t w, int
 
 }  // namespace
 
+int64_t jpeg_slab_rows(const JpegGeometry& g) { return slab_rows_of(g); }
+
 int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k) {
   const std::string who = std::string(what) + " " + std::to_string(k);
   const int rc = check_args(who.c_str(), f.canvas, f.pitch, f.w, f.h, f.quality, f.subsampling);
@@ -497,16 +499,39 @@ int jpeg_batch_check(const JpegBatchFile& f, const char* what, int k) {
 }
 
 // The file of a canvas in device memory into `out` (device, out_cap bytes).  The arguments have been checked.  Synchronises `stream`.
-// IST_JPEG_OPTIMIZE: every slab is transformed and counted first (no host wait between slabs: stream order protects the scratch), one
-// synchronisation brings the counts down, the tables and the header go up, and the slab loop runs with the wide entropy kernel.  A
-// file of one slab keeps its coefficients; a file of N > 1 slabs is transformed twice.
+// The loop is jpeg_encode_slabs; what fills a slab here is the transform kernel.
 int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w, int64_t h, int quality, int subsampling, void* out,
                        int64_t out_cap, int64_t* out_len, hipStream_t stream) {
   const Geometry g = geometry(w, h, subsampling);
-  const bool optimize = jpeg_ss_optimize(subsampling);
-  const int64_t slab_rows = slab_rows_of(g);
   JpegTables T;
   jpeg_enc_tables(quality, &T);
+  XformArgs X;
+  X.canvas = static_cast<const uint8_t*>(canvas); X.pitch = pitch; X.w = static_cast<int32_t>(w); X.h = static_cast<int32_t>(h);
+  X.tab = nullptr; X.coef = nullptr;
+  X.mcus_x = static_cast<int32_t>(g.mcus_x); X.mcu_row0 = 0; X.is420 = jpeg_ss_420(subsampling);
+  const unsigned gx = static_cast<unsigned>(X.is420 ? g.mcus_x : (g.mcus_x + 3) / 4);
+  JpegSlabSource src;
+  src.fill = [&](int64_t r0, int64_t rows, int16_t* coef, const JpegTables* tab, void* st) -> int {
+    X.mcu_row0 = static_cast<int32_t>(r0); X.coef = coef; X.tab = tab;
+    hipLaunchKernelGGL(ist_jpeg_transform_kernel, dim3(gx, static_cast<unsigned>(rows)), dim3(256), 0, static_cast<hipStream_t>(st), X);
+    IST_HIP(hipGetLastError());
+    g_launches.fetch_add(1, std::memory_order_relaxed);
+    return IST_OK;
+  };
+  return jpeg_encode_slabs(ctx, w, h, subsampling, T, out, out_cap, out_len, stream, src);
+}
+
+// One file, slab by slab; src.fill leaves a slab's coefficients in the scratch (ist_jpeg_enc.h).
+// IST_JPEG_OPTIMIZE: every slab is filled and counted first (no host wait between slabs: stream order protects the scratch), one
+// synchronisation brings the counts down, the tables and the header go up, and the slab loop runs with the wide entropy kernel.  A
+// file of one slab keeps its coefficients; a file of N > 1 slabs is filled twice.
+int jpeg_encode_slabs(ist_ctx* ctx, int64_t w, int64_t h, int subsampling, const JpegTables& T0, void* out, int64_t out_cap, int64_t* out_len,
+                      void* stream_, const JpegSlabSource& src) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const Geometry g = geometry(w, h, subsampling);
+  const bool optimize = jpeg_ss_optimize(subsampling);
+  const int64_t slab_rows = slab_rows_of(g);
+  JpegTables T = T0;
   std::vector<uint8_t> head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x);      // (optimised: no header is longer than this one)
   if (static_cast<int64_t>(head.size()) + 2 > out_cap) return fail(IST_E_INVALID, "JPEG output buffer too small (see ist_jpeg_bound)");
 
@@ -527,18 +552,9 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
   // (every way out below leaves the stream idle: kernels in flight write `res` and read the tables)
   struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
   IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  XformArgs X;
-  X.canvas = static_cast<const uint8_t*>(canvas); X.pitch = pitch; X.w = static_cast<int32_t>(w); X.h = static_cast<int32_t>(h);
-  X.tab = reinterpret_cast<const JpegTables*>(scratch); X.coef = reinterpret_cast<int16_t*>(scratch + o_coef);
-  X.mcus_x = static_cast<int32_t>(g.mcus_x); X.mcu_row0 = 0; X.is420 = jpeg_ss_420(subsampling);
-  const unsigned gx = static_cast<unsigned>(X.is420 ? g.mcus_x : (g.mcus_x + 3) / 4);
-  auto transform = [&](int64_t r0, int64_t rows) -> int {
-    X.mcu_row0 = static_cast<int32_t>(r0);
-    hipLaunchKernelGGL(ist_jpeg_transform_kernel, dim3(gx, static_cast<unsigned>(rows)), dim3(256), 0, stream, X);
-    IST_HIP(hipGetLastError());
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    return IST_OK;
-  };
+  struct { const JpegTables* tab; int16_t* coef; } X{reinterpret_cast<const JpegTables*>(scratch), reinterpret_cast<int16_t*>(scratch + o_coef)};
+  auto transform = [&](int64_t r0, int64_t rows) -> int { return src.fill(r0, rows, X.coef, X.tab, stream); };
+  auto synced = [&]() -> int { return src.synced ? src.synced() : IST_OK; };
   bool kept = false;                                 // the (only) slab's coefficients are in the scratch already
   if (optimize) {
     int64_t* const counters = static_cast<int64_t*>(ctx->scratch_jpg_counts.p);
@@ -555,8 +571,10 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
     }
     IST_HIP(hipMemcpyAsync(res.p + o_counts, counters, kCountBytes, hipMemcpyDeviceToHost, stream));
     IST_HIP(hipStreamSynchronize(stream));
+    rc = synced();
+    if (rc) return rc;
     JpegHuffSpec spec;
-    jpeg_enc_tables_optimal(quality, reinterpret_cast<const int64_t*>(res.p + o_counts), &T, &spec);
+    jpeg_enc_codes_optimal(reinterpret_cast<const int64_t*>(res.p + o_counts), &T, &spec);
     head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x, &spec);
     IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
     kept = g.mcus_y <= slab_rows;
@@ -573,6 +591,8 @@ int jpeg_encode_device(ist_ctx* ctx, const void* canvas, size_t pitch, int64_t w
     else hipLaunchKernelGGL(ist_jpeg_entropy_kernel, dim3(static_cast<unsigned>(rows)), dim3(kBatch), 0, stream, E);
     IST_HIP(hipGetLastError());
     IST_HIP(hipStreamSynchronize(stream));
+    rc = synced();
+    if (rc) return rc;
     for (int64_t k = 0; k < rows; ++k) {
       if (r0 + k > 0) pos += 2;                      // RSTn
       // (length 0 is also what the wide kernel reports for a symbol that the file's tables have no code for)

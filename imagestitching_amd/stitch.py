@@ -1335,6 +1335,53 @@ def decode_bitmaps(files, device=0, scale=1, profile="ignore"):
     return [Bitmap(out[i], device) for i in range(n)]
 
 
+def _join_args(files, direction, who):
+    if direction not in _DIRECTIONS:
+        raise ValueError("%s: direction must be 'vertical' or 'horizontal'" % who)
+    blobs = _read_files(files)
+    n = len(blobs)
+    if n == 0:
+        raise ValueError("%s: no files" % who)
+    return blobs, (C.c_char_p * n)(*blobs), (C.c_int64 * n)(*[len(b) for b in blobs]), n
+
+
+def _join_record(info):
+    return {"ok": info.reason == 0, "reason": L.JOIN_REASONS[info.reason], "image": int(info.image), "width": int(info.width),
+            "height": int(info.height), "subsampling": {0: "444", 1: "420"}.get(info.subsampling)}
+
+
+def jpeg_join_check(files, direction):
+    """Can these JPEG files (bytes, or paths that are read here) be joined losslessly (ist_jpeg_join_check: headers only, no GPU)?
+    Returns {'ok', 'reason', 'image', 'width', 'height', 'subsampling'}: reason is 'ok' or the lower-case name of the first refusal
+    ('not_jpeg', 'layout', 'mixed', 'tables', 'size', 'align', 'orient', 'limit'), image the first image it applies to (-1: none),
+    width / height the joined file's size when ok (else 0), subsampling '444' / '420' of image 0 once known (else None).  The
+    library's message of a refusal is last_error()."""
+    _, cfiles, lens, n = _join_args(files, direction, "jpeg_join_check")
+    info = L.JpegJoinInfo()
+    rc = L.lib.ist_jpeg_join_check(cfiles, lens, n, _DIRECTIONS[direction], C.byref(info))
+    if rc < 0 and rc != -7:      # (IST_E_UNSUPPORTED is the refusal the record describes)
+        L.check(rc)
+    return _join_record(info)
+
+
+def join_jpeg(files, direction, optimize=False, device=0):
+    """JPEG files (bytes or paths, as decode_bitmaps takes them) -> ONE JPEG file (bytes) that carries exactly the sources' quantised
+    coefficients and quantisation tables (ist_jpeg_join_files): what jpegtran does for one file, done for a strip.  No pixel is made:
+    the files are entropy-decoded to their coefficient planes on the GPU, one kernel moves the blocks into the export's scratch, and
+    the export's entropy coder writes the file - no generation loss, no quality to choose.  The sources must share a width
+    (vertical) or height (horizontal), a sampling layout (4:4:4 or 4:2:0) and their quantisation tables; every image but the last
+    must be a whole number of MCUs along the join (jpeg_join_check says whether a set qualifies, and why not).  optimize=True: the
+    file's own Huffman tables (IST_JPEG_OPTIMIZE).  An ineligible set raises StitchError (IST_E_UNSUPPORTED) whose message names the
+    image and the reason; nothing falls back to the pixel route - the caller asks jpeg_join_check and decides."""
+    if not isinstance(optimize, bool):
+        raise TypeError("optimize: expected a bool")
+    _, cfiles, lens, n = _join_args(files, direction, "join_jpeg")
+    out, m = C.POINTER(C.c_uint8)(), C.c_int64(0)
+    L.check(L.lib.ist_jpeg_join_files(_ctx(device), cfiles, lens, n, _DIRECTIONS[direction], JPEG_OPTIMIZE if optimize else 0, None,
+                                      C.byref(out), C.byref(m)))
+    return _take_png(out, m)
+
+
 def thumbnails_from_files(files, cell, mode="fill", orient=True, device=0, profile="ignore"):
     """Image files (bytes or paths) -> their thumbnails for a cell (width, height), as thumbnails() returns them, without ever holding
     a full-size bitmap: every JPEG is decoded at the largest scale (decode_scale_fit) at which its stored pixels still cover its

@@ -882,6 +882,73 @@ IST_API int ist_stitch_jpeg_batch(ist_ctx* ctx, const ist_stitch_request* reqs, 
 /* rounds (one transform launch each) made by batch encodes in this process so far */
 IST_API int64_t ist_debug_jpeg_batch_launches(void);
 
+/* ---- lossless JPEG joins: a strip of compatible JPEG files becomes one JPEG in the coefficient domain -------------------------
+ * What jpegtran does for one file, done for a strip: the sources' QUANTISED coefficients (the decoder's dense planes, see
+ * ist_debug_jpeg_gpu_coefficients) are moved, block by block, into the export's coefficient scratch and entropy-coded by the export's
+ * kernels.  No pixel is ever made: no IDCT, no colour conversion, no stitch, no FDCT, no second quantisation, no generation loss, and
+ * no quality to choose.
+ *
+ * THE RULE.  A join of n files (1 <= n <= 128) in `direction` IST_VERTICAL or IST_HORIZONTAL:
+ *   - layout and tables: the result has image 0's sampling layout (4:4:4 or 4:2:0) and image 0's quantisation tables.  The header is
+ *     the export's (SOI, APP0, DQT x 2, DHT x 4, DRI, SOF0, SOS) with DQT 0 = the SOURCES' luma table and DQT 1 = the sources' chroma
+ *     table, not the tables of a quality;
+ *   - geometry: vertical W = w_0, H = sum h_i, and component c's block rows are the sources' block rows of that component, one image
+ *     after the other; horizontal H = h_0, W = sum w_i, and each block row is the sources' block rows of the same index side by
+ *     side.  (W, H) is the canvas ist_plan_compute gives for these images with IST_MODE_MIN, gap 0, unlimited caps (super-sample 1);
+ *   - everything else is the export's contract unchanged: one restart interval per MCU row, DC predictors zero at each interval, the
+ *     Annex K tables (or, with IST_JPEG_OPTIMIZE, the file's optimal tables by the rule above), padding bits, stuffing, RSTn order, EOI.
+ *   So the file equals, byte for byte, the export's file of a frame whose coefficient arrays are the sources' arrays concatenated
+ *   along the block-row axis (vertical) or the block-column axis (horizontal).
+ *
+ * ELIGIBILITY is decided from the headers alone, by the decoder's own parser (the segments are walked and the scan headers read as a
+ * decode reads them, up to the scan header that fixes the last component's table; no entropy-coded byte is decoded).  Images are looked at in order and, per image, the reasons in the order of this
+ * list; the first failing image and its reason are reported:
+ *   IST_JOIN_NOT_JPEG  not a JPEG, or one the decoder refuses (its message is kept);
+ *   IST_JOIN_LAYOUT    not three components in the YCbCr colour space (the decoder's libjpeg rule: JFIF, Adobe transform, component
+ *                      ids), or a sampling layout other than 4:4:4 / 4:2:0, the two the export writes;
+ *   IST_JOIN_MIXED     the layout differs from image 0's;
+ *   IST_JOIN_TABLES    a component's quantisation table (the one in force when its first scan starts, as the decoder latches it)
+ *                      differs from image 0's; in image 0, Cb's differs from Cr's, or an entry is 0 or above 255 (a DQT the export's
+ *                      8-bit segment cannot carry; a component no scan names has an all-zero table);
+ *   IST_JOIN_SIZE      widths differ (vertical) or heights differ (horizontal);
+ *   IST_JOIN_ALIGN     an image other than the last has a height (vertical) or width (horizontal) that is not a multiple of the MCU
+ *                      size (8 for 4:4:4, 16 for 4:2:0).  The last image may be partial on both axes, and every image may be partial
+ *                      across the join axis;
+ *   IST_JOIN_ORIENT    EXIF orientation above 1 (lossless turns are out of scope);
+ *   IST_JOIN_LIMIT     the joined side (sum of heights, vertical; of widths, horizontal) exceeds 65535 at this image; also n > 128
+ *                      (image = 128, decided before any file is read);
+ *   IST_JOIN_RANGE     found on the device only, by ist_jpeg_join_files: a DC outside [-1024, 1023] or an AC outside [-1023, 1023].
+ *                      The entropy kernel would clamp such a value silently and the join would not be lossless; inside these bounds
+ *                      every coded DC difference is within +-2047.  Every 8-bit baseline file of a real encoder is inside them.  The
+ *                      call fails and no file is returned (image = -1: the kernel does not say which).
+ * The context's colour-profile setting is not read: no pixel exists, and the export writes no profile anyway.  EXIF and ICC segments
+ * of the sources are not carried. */
+enum { IST_JOIN_OK = 0, IST_JOIN_NOT_JPEG = 1, IST_JOIN_LAYOUT = 2, IST_JOIN_MIXED = 3, IST_JOIN_TABLES = 4, IST_JOIN_SIZE = 5,
+       IST_JOIN_ALIGN = 6, IST_JOIN_ORIENT = 7, IST_JOIN_LIMIT = 8, IST_JOIN_RANGE = 9 };
+typedef struct ist_jpeg_join_info {
+  int32_t reason, image;      /* IST_JOIN_*; the first failing image (-1: none) */
+  int32_t subsampling;        /* IST_JPEG_444 / IST_JPEG_420 of image 0 once it is known to have one of them, else -1 */
+  int32_t reserved;
+  int64_t width, height;      /* of the joined file when reason is IST_JOIN_OK, else 0 */
+} ist_jpeg_join_info;
+/* Pure CPU, no context: headers only.  Returns 0 and reason = IST_JOIN_OK, or IST_E_UNSUPPORTED with reason / image filled and a
+ * message that names the image and the reason ("image k: ...").  IST_E_INVALID for NULL arrays, n <= 0 or an unknown direction (a
+ * NULL or empty entry of `files` is IST_JOIN_NOT_JPEG of that image).  out may be NULL. */
+IST_API int ist_jpeg_join_check(const uint8_t* const* files, const int64_t* lens, int n, int direction, ist_jpeg_join_info* out);
+/* files -> one JPEG (a pooled pinned block of the file's length, release with ist_free).  flags: 0 or IST_JPEG_OPTIMIZE.  The files are
+ * entropy-decoded as ist_decode_files_device decodes them (the GPU Huffman decoder where it takes the file, the host decoders
+ * otherwise) but stop at the coefficient planes; one join launch per slab of MCU rows fills the encoder's scratch in place of its
+ * transform, and the export's entropy (histogram, gather) launches run unchanged.  With IST_JPEG_OPTIMIZE and more than one slab the
+ * fill runs twice, as the transform does.  Errors, in this order: IST_E_NO_CONTEXT; IST_E_INVALID: unknown flags, then NULL arrays /
+ * n <= 0 / an unknown direction ("bad argument"), then a NULL output; then what ist_jpeg_join_check refuses (out_info, optional, is
+ * filled as by that call); a file whose scan does not decode: IST_E_DECODE '图片N解码异常: ...'; IST_JOIN_RANGE (IST_E_UNSUPPORTED).
+ * On any failure *out_jpeg is NULL and nothing is held. */
+IST_API int ist_jpeg_join_files(ist_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int direction, int flags,
+                                ist_jpeg_join_info* out_info, uint8_t** out_jpeg, int64_t* out_len);
+/* join launches (one per slab of MCU rows; two with IST_JPEG_OPTIMIZE and more than one slab) made in this process so far.  A join
+ * makes no transform, reconstruction or stitch launch: ist_debug_jpeg_encode_launches does not move across it. */
+IST_API int64_t ist_debug_jpeg_join_launches(void);
+
 /* ---- overlap removal for scrolled screenshots --------------------------------------------------------------------------------
  * A vertical strip of screenshots repeats a bar at the top and at the bottom of every shot, and the content of each shot overlaps
  * the shot above it by an unknown number of rows.  Per neighbouring pair (A above, B below) the library finds the shared header H,

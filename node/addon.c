@@ -21,6 +21,8 @@
  *   encodePng(data, width, height) -> Buffer;  stitch(..., filter, true) resolves {width,height,png}
  *   encodeJpeg(data, width, height, quality, subsampling) -> Buffer;  stitch / stitchBitmaps(..., filter, {quality, subsampling})
  *       resolve {width,height,jpeg} (ist_stitch_jpeg / ist_stitch_bitmaps_jpeg: asPng given as an object is the JPEG export)
+ *   joinJpegCheck(files: Buffer[], direction) -> {ok, reason, image, width, height, subsampling} (ist_jpeg_join_check: pure CPU);
+ *   joinJpeg(files: Buffer[], direction, flags?) -> Promise<Buffer> (ist_jpeg_join_files: the lossless join; flags 0 or IST_JPEG_OPTIMIZE)
  *   deviceCount(), lastError(), abiVersion()
  *   resident bitmaps (ist_bitmap_*): uploadBitmap([image]) -> handle;  decodeBitmaps(files: Buffer[], scales?: number[], colorProfile?: number) -> Promise<handle[]>;
  *   imageColor(file: Buffer) -> 0 .. 3 (IST_COLOR_*);
@@ -929,6 +931,63 @@ static napi_value js_decode_bitmaps(napi_env env, napi_callback_info info) {
   return job_queue(env, &j->h, "imagestitch.decodeBitmaps");
 }
 
+/* ---- lossless JPEG joins (ist_jpeg_join_check, ist_jpeg_join_files) -------------------------------------------------------- */
+/* {ok, reason, image, width, height, subsampling}: reason / subsampling as the library's codes (index.js names them) */
+static napi_value join_info_to_js(napi_env env, const ist_jpeg_join_info* info) {
+  napi_value o;
+  if (napi_create_object(env, &o) != napi_ok) return NULL;
+  set_bool(env, o, "ok", info->reason == IST_JOIN_OK);
+  set_num(env, o, "reason", info->reason);
+  set_num(env, o, "image", info->image);
+  set_num(env, o, "width", (double)info->width);
+  set_num(env, o, "height", (double)info->height);
+  set_num(env, o, "subsampling", info->subsampling);
+  return o;
+}
+
+/* joinJpegCheck(files: Buffer[], direction: number) -> the record (ist_jpeg_join_check: pure CPU, headers only; a refusal is a
+ * record, not an Error) */
+static napi_value js_join_jpeg_check(napi_env env, napi_callback_info info) {
+  static const char usage[] = "joinJpegCheck(files: Buffer[], direction: number)";
+  napi_value argv[2]; files_t files; ist_jpeg_join_info rec;
+  if (!args_of(env, info, 2, 2, argv, usage) || !files_parse(env, argv[0], usage, &files)) return NULL;
+  const int rc = ist_jpeg_join_check(files.ptr, files.len, files.n, int_of(env, argv[1], -1), &rec);
+  files_free(env, &files);
+  if (rc < 0 && rc != IST_E_UNSUPPORTED) return throw_ist(env, rc);
+  return join_info_to_js(env, &rec);
+}
+
+/* joinJpeg(files: Buffer[], direction: number, flags: number) -> Promise<Buffer> (ist_jpeg_join_files; flags 0 or IST_JPEG_OPTIMIZE) */
+typedef struct { job h; files_t files; int direction, flags; uint8_t* file; int64_t len; } join_job;
+
+static int join_run(ist_ctx* ctx, job* h) {
+  join_job* j = (join_job*)h;
+  return ist_jpeg_join_files(ctx, j->files.ptr, j->files.len, j->files.n, j->direction, j->flags, NULL, &j->file, &j->len);
+}
+static napi_value join_result(napi_env env, job* h) {
+  join_job* j = (join_job*)h;
+  napi_value buf = block_to_buffer(env, j->file, (size_t)j->len);
+  j->file = NULL;                                         /* the Buffer owns the block now (or it was freed) */
+  return buf;
+}
+static void join_free(napi_env env, job* h) {
+  join_job* j = (join_job*)h;
+  if (j->file) ist_free(j->file);
+  files_free(env, &j->files);
+  free(j);
+}
+static const job_kind JOIN = {join_run, join_result, join_free};
+
+static napi_value js_join_jpeg(napi_env env, napi_callback_info info) {
+  static const char usage[] = "joinJpeg(files: Buffer[], direction: number, flags?: number)";
+  napi_value argv[3]; files_t files;
+  if (!args_of(env, info, 2, 3, argv, usage) || !files_parse(env, argv[0], usage, &files)) return NULL;
+  join_job* j = (join_job*)calloc(1, sizeof *j);
+  if (!j) { files_free(env, &files); return throw_oom(env); }
+  j->h.kind = &JOIN; j->files = files; j->direction = int_of(env, argv[1], -1); j->flags = int_of(env, argv[2], 0);
+  return job_queue(env, &j->h, "imagestitch.joinJpeg");
+}
+
 /* imageColor(file: Buffer) -> 0 .. 3, the IST_COLOR_* kind of the file's ICC profile (ist_image_color: pure CPU) */
 static napi_value js_image_color(napi_env env, napi_callback_info info) {
   napi_value argv[1], out; const uint8_t* p; size_t len; int32_t kind = 0;
@@ -1182,6 +1241,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_default, NULL},
       {"uploadBitmap", NULL, js_upload_bitmap, NULL, NULL, NULL, napi_default, NULL},
       {"decodeBitmaps", NULL, js_decode_bitmaps, NULL, NULL, NULL, napi_default, NULL},
+      {"joinJpegCheck", NULL, js_join_jpeg_check, NULL, NULL, NULL, napi_default, NULL},
+      {"joinJpeg", NULL, js_join_jpeg, NULL, NULL, NULL, napi_default, NULL},
       {"imageColor", NULL, js_image_color, NULL, NULL, NULL, napi_default, NULL},
       {"decodeScaleFit", NULL, js_decode_scale_fit, NULL, NULL, NULL, napi_default, NULL},
       {"bitmapDesc", NULL, js_bitmap_desc, NULL, NULL, NULL, napi_default, NULL},

@@ -78,6 +78,10 @@ export class Bitmap {
 /** scale: 1, 2, 4 or 8 (one for all files or one per file): a JPEG is decoded at 1 / scale and kept at that size; other types at 1 / 1 */
 export function decodeBitmaps(files: (Uint8Array | string)[], opts?: { scale?: 1 | 2 | 4 | 8 | (1 | 2 | 4 | 8)[]; colorProfile?: ColorProfile }): Promise<Bitmap[]>;
 // the colour kind of a file's ICC profile: untagged, tagged sRGB, what colorProfile 'srgb' converts, or a profile the contract does not take
+export type JoinReason = 'ok' | 'not_jpeg' | 'layout' | 'mixed' | 'tables' | 'size' | 'align' | 'orient' | 'limit' | 'range';
+export interface JoinCheck { ok: boolean; reason: JoinReason; image: number; width: number; height: number; subsampling: '444' | '420' | null; }      // image: the first failing image, -1 when ok; width / height: the joined file's, 0 when refused
+export function joinJpegCheck(files: (Uint8Array | string)[], direction: Direction): JoinCheck;      // headers only, pure CPU
+export function joinJpeg(files: (Uint8Array | string)[], direction: Direction, opts?: { optimize?: boolean }): Promise<Buffer>;      // lossless: the sources' coefficients and tables in one file; rejects for an ineligible set
 export function imageColor(file: Uint8Array | string): 'none' | 'identity' | 'convert' | 'unsupported';
 /** the largest scale at which a width x height file still decodes to at least minWidth x minHeight pixels (1 if none does) */
 export function decodeScaleFit(width: number, height: number, minWidth: number, minHeight: number): 1 | 2 | 4 | 8;

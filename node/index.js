@@ -11,6 +11,7 @@
  *   encodeJpeg(data, width, height, {quality, subsampling, optimize}) -> Buffer
  *   stitchPngBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, png, plan} | null)[]>   (one GPU, many PNG files)
  *   stitchJpegBatch([{images, direction, opts?}, ...]) -> Promise<({width, height, jpeg, plan} | null)[]>  (one GPU, many JPEG files)
+ *   joinJpegCheck(files, direction) -> {ok, reason, image, width, height, subsampling},  joinJpeg(files, direction, {optimize}) -> Promise<Buffer>   (lossless: compatible JPEG files joined in the coefficient domain)
  *   decodeBitmaps(files, {scale?, colorProfile?}) -> Promise<Bitmap[]>,  imageColor(file) -> 'none' | 'identity' | 'convert' | 'unsupported',  decodeScaleFit(w, h, minW, minH) -> 1 | 2 | 4 | 8,  uploadBitmap(image) -> Bitmap   (images kept in GPU memory: stitch, stitchSync,
  *       stitchPng and plan take Bitmap[] in place of images, and a restitch decodes and uploads nothing)
  *   stitchPng / stitchFiles with opts.preview = {width, height} also resolve preview: {width, height, data}: the canvas shrunk to fit
@@ -181,6 +182,37 @@ async function decodeBitmaps(files, opts) {
   if (!bufs.length) return [];
   const handles = await native.decodeBitmaps(bufs, scales, profile);
   return handles.map((h) => new Bitmap(MADE_HERE, h));
+}
+// the IST_JOIN_* reason codes of joinJpegCheck, by value
+const JOIN_REASON = ['ok', 'not_jpeg', 'layout', 'mixed', 'tables', 'size', 'align', 'orient', 'limit', 'range'];
+function joinArgs(files, direction, usage) {
+  if (!Array.isArray(files) || !files.length) throw new TypeError(usage);
+  if (!(direction in DIRECTION)) throw new TypeError("direction must be 'vertical' or 'horizontal'");
+  const fs = require('fs');
+  return [files.map((f) => (typeof f === 'string' ? fs.readFileSync(f) : f)), DIRECTION[direction]];
+}
+/** Can these JPEG files (Buffers, or paths read here) be joined losslessly?  Headers only, pure CPU.  Returns {ok, reason, image,
+ *  width, height, subsampling}: reason 'ok' or the first refusal ('not_jpeg', 'layout', 'mixed', 'tables', 'size', 'align', 'orient',
+ *  'limit'), image the first image it applies to (-1: none), width / height the joined file's size when ok (else 0), subsampling
+ *  '444' / '420' of image 0 once known (else null). */
+function joinJpegCheck(files, direction) {
+  const [bufs, dir] = joinArgs(files, direction, "joinJpegCheck(files: (Uint8Array | string)[], direction)");
+  const r = native.joinJpegCheck(bufs, dir);
+  return { ok: r.ok, reason: JOIN_REASON[r.reason], image: r.image, width: r.width, height: r.height, subsampling: r.subsampling === 0 ? '444' : r.subsampling === 1 ? '420' : null };
+}
+/** JPEG files -> ONE JPEG file (a Buffer) that carries exactly the sources' quantised coefficients and quantisation tables: what
+ *  jpegtran does for one file, done for a strip, on the GPU.  No pixel is made, nothing is lost, no quality is chosen.  The sources
+ *  share a width (vertical) or height (horizontal), a sampling layout (4:4:4 / 4:2:0) and their quantisation tables (joinJpegCheck
+ *  says whether a set qualifies).  opts.optimize (a boolean, default false): the file's own Huffman tables.  An ineligible set
+ *  rejects with the library's Error (IST_E_UNSUPPORTED, the message names the image and the reason); nothing falls back to pixels. */
+function joinJpeg(files, direction, opts) {
+  let a, optimize;
+  try {
+    a = joinArgs(files, direction, "joinJpeg(files: (Uint8Array | string)[], direction, {optimize?})");
+    optimize = (opts && opts.optimize !== undefined && opts.optimize !== null) ? opts.optimize : false;
+    if (typeof optimize !== 'boolean') throw new TypeError('optimize must be a boolean');
+  } catch (e) { return Promise.reject(e); }
+  return native.joinJpeg(a[0], a[1], optimize ? 0x100 : 0);
 }
 /** The colour kind of an image file: 'none' (untagged), 'identity' (tagged sRGB), 'convert' (what colorProfile 'srgb' converts) or
  *  'unsupported' (a profile the contract does not take: LUT-only, GRAY, CMYK, damaged).  Pure CPU. */
@@ -470,4 +502,4 @@ function plan(images, direction, opts) {
 }
 
 module.exports = { stitch: withOverlap(stitch), stitchSync: withOverlapSync(stitchSync), stitchBatch, stitchBatchSync, stitchPngBatch, stitchPngBatchSync, stitchJpegBatch, stitchJpegBatchSync, stitchPng: withOverlap(stitchPng), stitchJpeg: withOverlap(stitchJpeg), stitchFiles, encodePng, encodeJpeg, setPngLevel, setPngColor, setPngFilter, setPngMatch, decodePng, decodeImage, plan,
-                   decodeBitmaps, imageColor, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, findOverlaps, findOverlapsSync, overlapRows, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };
+                   decodeBitmaps, joinJpegCheck, joinJpeg, imageColor, decodeScaleFit, uploadBitmap, thumbnails, debugBitmapBytes, findOverlaps, findOverlapsSync, overlapRows, Bitmap, native, DIRECTION, MODE, FILTER, PLATFORM, SPLIT };

@@ -4,6 +4,7 @@
 #   tools/run_fuzz.sh compile ITERS               random + hostile op lists through the op-list compiler, invariants checked
 #   tools/run_fuzz.sh jpegbatch ITERS [SEED]      random batches through the rounds, header blob and piece records of the batched JPEG export
 #   tools/run_fuzz.sh jpegoptimize ITERS [SEED]   random + adversarial symbol counts through the optimal-table builder and the DHT / header writer
+#   tools/run_fuzz.sh jpegjoin ITERS [SEED]       random + hostile sets of files through the lossless join's eligibility rule, its table and the slab walk of the kernel's block mapping
 #   tools/run_fuzz.sh icc ITERS [SEED]            random + adversarial ICC profiles, bare and inside JPEG / PNG / WebP containers, through the colour-profile parser
 #   tools/run_fuzz.sh settings [ITERS]            ThreadSanitizer (its own flags, not the ASan set): setter and reader threads on the context's settings word
 set -e
@@ -20,6 +21,9 @@ elif [ "$1" = jpegbatch ]; then
 elif [ "$1" = jpegoptimize ]; then
   shift
   g++ $FLAGS "$HERE/check_jpeg_optimize_host.cpp" "$C/ist_jpeg_enc_host.cpp" -o "$OUT"
+elif [ "$1" = jpegjoin ]; then
+  shift
+  g++ $FLAGS "$HERE/check_jpeg_join_host.cpp" "$C/ist_jpeg_join_host.cpp" "$C/ist_jpeg_enc_host.cpp" "$C/ist_jpeg.cpp" "$C/ist_plan.cpp" -o "$OUT"
 elif [ "$1" = icc ]; then
   shift
   g++ $FLAGS "$HERE/check_icc_host.cpp" "$C/ist_icc.cpp" "$C/ist_png_decode.cpp" "$C/ist_image_misc.cpp" "$C/ist_jpeg.cpp" "$C/ist_webp.cpp" "$C/ist_webp_vp8.cpp" "$C/ist_plan.cpp" -lz -o "$OUT"
