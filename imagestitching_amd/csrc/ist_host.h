@@ -37,6 +37,39 @@ void* pool_take_batch(size_t bytes);
 bool pool_give(void* p);                // true when p came from pool_take (the block is kept for reuse or released)
 void pool_trim();                       // release every cached block
 
+// One block of the pool for the length of a scope: pool_take in take(), pool_give in the destructor.  Move-only and, like the owners
+// of ist_device.h, for automatic storage only (the note at the top of that file applies).
+struct PoolBlock {
+  void* p = nullptr;
+  PoolBlock() = default;
+  PoolBlock(PoolBlock&& o) noexcept : p(o.p) { o.p = nullptr; }
+  PoolBlock& operator=(PoolBlock&& o) noexcept { std::swap(p, o.p); return *this; }
+  ~PoolBlock() { if (p) pool_give(p); }
+  bool take(size_t bytes) { if (p) pool_give(p); p = pool_take(bytes); return p != nullptr; }
+  template <typename T = uint8_t> T* at(size_t byte_offset = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + byte_offset); }
+};
+
+// Leaves up to three streams idle on every way out of a scope that has not disarm()ed it.  Destruction runs against declaration, so
+// declare it AFTER the blocks that the work in flight reads and writes: it then waits before they go back to the pool.  A wait that
+// fails leaves no error behind for the next launch check.  Move-only, automatic storage only.
+struct StreamDrain {
+  hipStream_t s[3];
+  bool armed = true;
+  StreamDrain(hipStream_t a, hipStream_t b, hipStream_t c) : s{a, b, c} {}
+  StreamDrain(hipStream_t a, hipStream_t b) : StreamDrain(a, b, a) {}
+  explicit StreamDrain(hipStream_t a) : StreamDrain(a, a, a) {}
+  StreamDrain(StreamDrain&& o) noexcept : s{o.s[0], o.s[1], o.s[2]}, armed(o.armed) { o.armed = false; }
+  StreamDrain& operator=(StreamDrain&&) = delete;
+  void disarm() { armed = false; }
+  ~StreamDrain() {
+    if (!armed) return;
+    for (int k = 0; k < 3; ++k) {
+      if ((k > 0 && s[k] == s[0]) || (k > 1 && s[k] == s[1])) continue;      // each distinct stream once
+      if (hipStreamSynchronize(s[k]) != hipSuccess) (void)hipGetLastError();
+    }
+  }
+};
+
 // ---- staged copies between caller memory and device memory -------------------------------------------------------
 class Stager {
  public:

@@ -545,12 +545,12 @@ int jpeg_encode_slabs(ist_ctx* ctx, int64_t w, int64_t h, int subsampling, const
   // per interval of a slab: its length (written by the kernel) and its place in the file (read by the gather), in pinned memory;
   // behind them the counts of an optimised file
   const size_t o_counts = static_cast<size_t>(slab_rows) * 16;
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(o_counts + (optimize ? kCountBytes : 0)))};
-  if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
-  int64_t* const dst = reinterpret_cast<int64_t*>(res.p);
-  uint32_t* const len = reinterpret_cast<uint32_t*>(res.p + 8 * static_cast<size_t>(slab_rows));
+  PoolBlock res;
+  if (!res.take(o_counts + (optimize ? kCountBytes : 0))) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
+  int64_t* const dst = res.at<int64_t>();
+  uint32_t* const len = res.at<uint32_t>(8 * static_cast<size_t>(slab_rows));
   // (every way out below leaves the stream idle: kernels in flight write `res` and read the tables)
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
+  StreamDrain drain(stream);
   IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
   struct { const JpegTables* tab; int16_t* coef; } X{reinterpret_cast<const JpegTables*>(scratch), reinterpret_cast<int16_t*>(scratch + o_coef)};
   auto transform = [&](int64_t r0, int64_t rows) -> int { return src.fill(r0, rows, X.coef, X.tab, stream); };
@@ -569,12 +569,12 @@ int jpeg_encode_slabs(ist_ctx* ctx, int64_t w, int64_t h, int subsampling, const
       IST_HIP(hipGetLastError());
       g_hist_launches.fetch_add(1, std::memory_order_relaxed);
     }
-    IST_HIP(hipMemcpyAsync(res.p + o_counts, counters, kCountBytes, hipMemcpyDeviceToHost, stream));
+    IST_HIP(hipMemcpyAsync(res.at(o_counts), counters, kCountBytes, hipMemcpyDeviceToHost, stream));
     IST_HIP(hipStreamSynchronize(stream));
     rc = synced();
     if (rc) return rc;
     JpegHuffSpec spec;
-    jpeg_enc_codes_optimal(reinterpret_cast<const int64_t*>(res.p + o_counts), &T, &spec);
+    jpeg_enc_codes_optimal(res.at<const int64_t>(o_counts), &T, &spec);
     head = jpeg_enc_header(w, h, subsampling, T, g.mcus_x, &spec);
     IST_HIP(hipMemcpyAsync(scratch, &T, sizeof T, hipMemcpyHostToDevice, stream));
     kept = g.mcus_y <= slab_rows;
@@ -659,13 +659,13 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
   // per interval of a round: its length (written by the kernel) and its place in its file (read by the gather), in pinned memory;
   // behind them the counts of the optimised files
   const size_t o_counts = static_cast<size_t>(max_ivs) * 16;
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(o_counts + count_bytes))};
-  if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
-  int64_t* const dst = reinterpret_cast<int64_t*>(res.p);
-  uint32_t* const len = reinterpret_cast<uint32_t*>(res.p + 8 * static_cast<size_t>(max_ivs));
+  PoolBlock res;
+  if (!res.take(o_counts + count_bytes)) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG encoder");
+  int64_t* const dst = res.at<int64_t>();
+  uint32_t* const len = res.at<uint32_t>(8 * static_cast<size_t>(max_ivs));
   std::vector<int64_t> pos(static_cast<size_t>(n), kJpegHeaderBytes);      // (an optimised file's: its own header's length, below)
   // Every way out leaves the stream idle (kernels in flight read the slot and write `res`).
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{stream};
+  StreamDrain drain(stream);
   // one round's table block up, its transform and, for its optimised pieces, their histogram
   auto transform = [&](const JpegRound& R, ist_ctx::BatchSlot* slot, bool count, unsigned parts) -> int {
     uint8_t* const d = static_cast<uint8_t*>(slot->dev.p);
@@ -685,14 +685,14 @@ int jpeg_encode_batch(ist_ctx* ctx, std::vector<JpegBatchFile>& files, void* str
   };
   // the counts down (one synchronisation), then every optimised file's tables and header
   auto build_tables = [&]() -> int {
-    IST_HIP(hipMemcpyAsync(res.p + o_counts, counters, count_bytes, hipMemcpyDeviceToHost, stream));
+    IST_HIP(hipMemcpyAsync(res.at(o_counts), counters, count_bytes, hipMemcpyDeviceToHost, stream));
     IST_HIP(hipStreamSynchronize(stream));
     for (int k = 0; k < n; ++k) {
       JpegOptFile& o = opt[static_cast<size_t>(k)];
       if (o.hist < 0) continue;
       const JpegBatchFile& f = files[static_cast<size_t>(k)];
       JpegHuffSpec spec;
-      jpeg_enc_tables_optimal(f.quality, reinterpret_cast<const int64_t*>(res.p + o_counts) + static_cast<size_t>(o.hist) * kJpegCounters, &o.T, &spec);
+      jpeg_enc_tables_optimal(f.quality, res.at<const int64_t>(o_counts) + static_cast<size_t>(o.hist) * kJpegCounters, &o.T, &spec);
       o.head = jpeg_enc_header(f.w, f.h, f.subsampling, o.T, geometry(f.w, f.h, f.subsampling).mcus_x, &spec);
       o.built = true;
       pos[static_cast<size_t>(k)] = static_cast<int64_t>(o.head.size());

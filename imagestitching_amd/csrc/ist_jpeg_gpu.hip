@@ -805,13 +805,13 @@ int jpeg_gpu_entropy_decode(const std::vector<JpegGpuItem>& items, std::vector<u
   uint8_t* const d = static_cast<uint8_t*>(block.p);
   // pinned block: [small inputs | results: flag, half totals, error words]
   const size_t res_bytes = 256 + 16 * static_cast<size_t>(n_half) + 4 * n_unit;
-  struct Pin { uint8_t* p; ~Pin() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(small_bytes + res_bytes))};
-  if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the Huffman decoder");
+  PoolBlock pin;
+  if (!pin.take(small_bytes + res_bytes)) return fail(IST_E_NOMEM, "out of pinned host memory for the Huffman decoder");
   // (every return below leaves the stream idle before `pin` goes back to the pool: the copies into it are waited for)
-  struct Idle { hipStream_t s; ~Idle() { (void)hipStreamSynchronize(s); } } idle{stream};
-  uint8_t* hs = pin.p;                                 // host image of the small-input region
-  volatile uint32_t* h_flag = reinterpret_cast<volatile uint32_t*>(pin.p + small_bytes);
-  uint32_t* h_half = reinterpret_cast<uint32_t*>(pin.p + small_bytes + 256);
+  StreamDrain idle(stream);
+  uint8_t* hs = pin.at();                                // host image of the small-input region
+  volatile uint32_t* h_flag = pin.at<volatile uint32_t>(small_bytes);
+  uint32_t* h_half = pin.at<uint32_t>(small_bytes + 256);
   uint32_t* h_err = h_half + 4 * static_cast<size_t>(n_half);
   std::memset(hs, 0, small_bytes);
   uint16_t* half_img = reinterpret_cast<uint16_t*>(hs + (o_sub - o_small));   // unit of every group of 128 subsequences

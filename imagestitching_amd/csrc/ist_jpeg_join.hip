@@ -109,7 +109,7 @@ int join_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* 
   Phases ph(ctx, false);                          // (the phases are those of a decode to bitmaps: nothing is recorded for a join)
   FileDecoder fd(ctx, files, lens, n, &ph, IST_COLOR_PROFILE_IGNORE);
   // (declared behind the decoder: the stream is idle before the decoder lets go of the host coefficients that uploads may still read)
-  struct Drain { hipStream_t s; ~Drain() { if (hipStreamSynchronize(s) != hipSuccess) (void)hipGetLastError(); } } drain{ctx->stream};
+  StreamDrain drain(ctx->stream);
   int rc = fd.headers();
   if (rc) return rc;
   for (int i = 0; i < n; ++i)                     // what the arena is sized from must be what the plan was made from
@@ -123,9 +123,9 @@ int join_files_locked(ist_ctx* ctx, const uint8_t* const* files, const int64_t* 
   rc = ctx->scratch_file.grow(static_cast<size_t>(cap));
   if (rc) return rc;
   uint8_t* const arena = static_cast<uint8_t*>(ctx->scratch_dec.p);
-  struct Pinned { void* p; ~Pinned() { if (p) pool_give(p); } } flag_block{pool_take(256)};
-  if (!flag_block.p) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG join");
-  volatile uint32_t* const flag = static_cast<volatile uint32_t*>(flag_block.p);
+  PoolBlock flag_block;
+  if (!flag_block.take(256)) return fail(IST_E_NOMEM, "out of pinned host memory for the JPEG join");
+  volatile uint32_t* const flag = flag_block.at<volatile uint32_t>();
   *flag = 0;
   rc = fd.start(arena, nullptr, nullptr);
   if (rc) return rc;

@@ -376,13 +376,13 @@ int png_encode_batch_stored(ist_ctx* ctx, const PngForm&, std::vector<PngBatchFi
     if (rc) return rc;
     d = static_cast<uint8_t*>(p);
   }
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(std::max(o_pow, total - o_s1)))};
-  if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
-  struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
-  RowsJob* hj = reinterpret_cast<RowsJob*>(pin.p + o_jobs);
+  PoolBlock pin;
+  if (!pin.take(std::max(o_pow, total - o_s1))) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  StreamDrain drain(stream);                          // (declared after the block: every way out waits before it goes back)
+  RowsJob* hj = pin.at<RowsJob>(o_jobs);
   for (size_t k = 0; k < nf; ++k) {
     const PngBatchFile& f = files[k];
-    std::memcpy(pin.p + o_tab + 8 * row_at[k], lay[k].row_tab.data(), 8 * static_cast<size_t>(f.h));
+    std::memcpy(pin.at(o_tab + 8 * row_at[k]), lay[k].row_tab.data(), 8 * static_cast<size_t>(f.h));
     RowsJob& J = hj[k];
     J.canvas = static_cast<const uint8_t*>(f.canvas); J.pitch = f.pitch; J.out = f.out;
     J.row_tab = reinterpret_cast<const int64_t*>(d + o_tab) + row_at[k];
@@ -391,7 +391,7 @@ int png_encode_batch_stored(ist_ctx* ctx, const PngForm&, std::vector<PngBatchFi
     J.crc = reinterpret_cast<uint32_t*>(d + o_crc) + acc_at[k];
     J.row_bytes = lay[k].row_bytes; J.h = static_cast<int32_t>(f.h); J.nb = lay[k].nb; J.segs = segs[k]; J.pad_ = 0;
   }
-  std::memcpy(pin.p + o_begin, wg.data(), 8 * (nf + 1));
+  std::memcpy(pin.at(o_begin), wg.data(), 8 * (nf + 1));
   IST_HIP(hipMemcpyAsync(d, pin.p, o_pow, hipMemcpyHostToDevice, stream));
   IST_HIP(hipMemcpyAsync(d + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
   IST_HIP(hipMemcpyAsync(d + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
@@ -408,9 +408,9 @@ int png_encode_batch_stored(ist_ctx* ctx, const PngForm&, std::vector<PngBatchFi
   // the partials into the same pinned block (its upload has been consumed by the time the kernel runs: same stream)
   IST_HIP(hipMemcpyAsync(pin.p, d + o_s1, total - o_s1, hipMemcpyDeviceToHost, stream));
   IST_HIP(hipStreamSynchronize(stream));
-  const unsigned long long* s1 = reinterpret_cast<const unsigned long long*>(pin.p);
-  const unsigned long long* s2 = reinterpret_cast<const unsigned long long*>(pin.p + (o_s2 - o_s1));
-  const uint32_t* crc = reinterpret_cast<const uint32_t*>(pin.p + (o_crc - o_s1));
+  const unsigned long long* s1 = pin.at<const unsigned long long>();
+  const unsigned long long* s2 = pin.at<const unsigned long long>(o_s2 - o_s1);
+  const uint32_t* crc = pin.at<const uint32_t>(o_crc - o_s1);
   for (size_t k = 0; k < nf; ++k) {
     PngBatchFile& f = files[k];
     f.patches.clear();
@@ -420,7 +420,7 @@ int png_encode_batch_stored(ist_ctx* ctx, const PngForm&, std::vector<PngBatchFi
       for (const PngPatch& pt : f.patches) IST_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
   }
   IST_HIP(hipStreamSynchronize(stream));
-  drain.armed = false;
+  drain.disarm();
   return IST_OK;
 }
 

@@ -94,6 +94,16 @@ struct DeflArgs {
   int64_t chunk0;                // first chunk of this launch (the canvas is encoded in slabs of chunks)
   unsigned long long* dbg;       // IST_PNG_PHASES (tuning): 8 clock samples per chunk
 };
+// the batch kernels' arguments: the chunks of many canvases in ONE launch (png_encode_batch_deflate), see "batch twins" below
+struct DeflJob { const uint8_t* canvas; size_t pitch; int64_t w, h; int32_t rows_per_chunk, pieces_per_row, piece_px, pad_; };
+struct DeflBatchArgs {
+  const DeflJob* jobs;           // per file (device memory)
+  const int64_t* chunk_begin;    // n_files + 1 (device memory)
+  int32_t n_files;
+  uint8_t* slots;
+  uint32_t* len16; uint32_t* crc; uint32_t* ad_a; uint32_t* ad_b; uint32_t* ad_n;
+  const uint32_t* tables; const uint32_t* xpow16;
+};
 
 __device__ __forceinline__ int padpos(int p) { return p + ((p >> 6) << 2); }
 
@@ -179,7 +189,9 @@ __device__ __forceinline__ uint32_t span_word(const uint32_t (&sp)[16], int d) {
 // passes; this one ~6).  eq bit i: byte i equals byte i-1.  A run of R >= 4 equal bytes is its first byte as a literal + ONE
 // match of R - 1 bytes at distance 1, shorter runs are literals: `covered` = the bytes inside matches = every eq position that
 // belongs to three consecutive eq bits; a match starts where a covered stretch starts and is as long as the stretch.
-struct SpanMasks { unsigned long long lit, mstart, covered; };
+// (eq is returned too: the window parse measures its runs on it.  Splitting the function into eq and the run masks adds an instruction
+// to each of deflate_chunk's kernels.)
+struct SpanMasks { unsigned long long lit, mstart, covered, eq; };
 __device__ __forceinline__ SpanMasks span_masks(const uint32_t (&sp)[16], int n) {
   unsigned long long eq = 0;
 #pragma unroll
@@ -199,6 +211,7 @@ __device__ __forceinline__ SpanMasks span_masks(const uint32_t (&sp)[16], int n)
   m.covered = (t | (t << 1) | (t << 2)) & valid;
   m.lit = valid & ~m.covered;
   m.mstart = m.covered & ~(m.covered << 1);
+  m.eq = eq;
   return m;
 }
 
@@ -263,10 +276,277 @@ __device__ __forceinline__ int walk_span(const uint32_t (&sp)[16], int n, const 
   return bits;
 }
 
+// ---- The steps of a chunk as functions: deflate_chunk_window below is made of them, deflate_chunk of those that leave the machine
+// code of its eight kernels as it was (span load, span masks, block header, pads, Adler report, step E; the batch kernels' unpack) -
+// the other steps it states inline, each with a note.  Whether a step can be shared there is decided by compiling, not by reading:
+// a function is simplified on its own before it is inlined, and with the constants of ALL its callers (block_header is a template
+// for that reason: the window body's call would otherwise change what the run form's call compiles to).  The LDS arrays belong to
+// the two bodies and come in as pointers.
+
+// which pixels: rows [y0, y0 + nrows) x columns [x0, x0 + npr); the filter byte belongs to the piece with x0 == 0.  bpp: bytes of a
+// pixel in the filtered stream; rowlen and len = rowlen * nrows (<= CH by construction) are counted in those
+struct ChunkRect { int64_t y0; int nrows, x0, npr, hasf, rowlen, len; };
+__device__ __forceinline__ ChunkRect chunk_rect(const DeflArgs& P, const int64_t chunk, const int bpp) {
+  ChunkRect R;
+  if (P.rows_per_chunk > 0) {
+    R.y0 = chunk * P.rows_per_chunk; R.nrows = static_cast<int>(min(static_cast<int64_t>(P.rows_per_chunk), P.h - R.y0)); R.x0 = 0; R.npr = static_cast<int>(P.w);
+  } else {
+    R.y0 = chunk / P.pieces_per_row; R.nrows = 1;
+    const int piece = static_cast<int>(chunk - R.y0 * P.pieces_per_row);
+    R.x0 = piece * P.piece_px; R.npr = static_cast<int>(min(static_cast<int64_t>(P.piece_px), P.w - R.x0));
+  }
+  R.hasf = R.x0 == 0 ? 1 : 0;
+  R.rowlen = R.hasf + bpp * R.npr;
+  R.len = R.rowlen * R.nrows;
+  return R;
+}
+
+// A. load + filter into the padded LDS image.  bpp: 4 (RGBA, colour type 6) or 3 (RGB, colour type 2: the canvas is still read a
+// dword per pixel, the alpha byte of the residual is not stored).  ftab: the filter type of canvas row y is ftab[y] (written by the
+// row-filter pre-pass); null: 4 on every row.  Four pixels per thread and round, all sixteen loads issued before the first filter.
+__device__ __forceinline__ void filter_chunk(const DeflArgs& P, const ChunkRect& R, const uint8_t* ftab, const int bpp, uint8_t* filt) {
+  const int npix = R.npr * R.nrows;
+  for (int q0 = threadIdx.x; q0 < npix; q0 += 1024) {
+    uint32_t cur[4], a[4], b[4], c[4], ft[4]; int pos[4]; bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + 256 * u;
+      on[u] = q < npix;
+      cur[u] = a[u] = b[u] = c[u] = 0u; pos[u] = 0; ft[u] = 4u;
+      if (on[u]) {
+        const int r = R.nrows == 1 ? 0 : q / R.npr, xx = q - r * R.npr;      // (one row per chunk - every image wider than 2047 px - needs no division)
+        const int64_t y = R.y0 + r; const int x = R.x0 + xx;
+        const uint8_t* row = P.canvas + static_cast<size_t>(y) * P.pitch;
+        cur[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x));
+        if (x > 0) a[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x - 1));
+        if (y > 0) {
+          b[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x));
+          if (x > 0) c[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x - 1));
+        }
+        pos[u] = r * R.rowlen + R.hasf + bpp * xx;
+        if (ftab) ft[u] = static_cast<uint32_t>(ftab[y]);
+        if (R.hasf && xx == 0) filt[padpos(r * R.rowlen)] = static_cast<uint8_t>(ft[u]);      // filter type of the row
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (!on[u]) continue;
+      const uint32_t fv = filter4(ft[u], cur[u], a[u], b[u], c[u]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) if (k < bpp) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
+    }
+  }
+}
+
+// a thread's span out of the padded LDS image into registers
+__device__ __forceinline__ void load_span(const uint8_t* filt, const int tid, uint32_t (&sp)[16]) {
+  const u32x4* mine = reinterpret_cast<const u32x4*>(filt + tid * (SPAN + 4));      // (68-byte pitch: 4-byte aligned)
+  const uint32_t* mw = reinterpret_cast<const uint32_t*>(mine);
+#pragma unroll
+  for (int d = 0; d < 16; ++d) sp[d] = mw[d];
+}
+
+// Adler-32 partials of the chunk's filtered bytes: the sum of the bytes and their sum weighted with the distance from the chunk's end,
+// mod 65521, per wave into wsum[0..3] and wsum[4..7]; behind a barrier thread 0 reports their totals and the byte count
+__device__ __forceinline__ void adler_partials(const uint32_t (&sp)[16], const int n, const int base, const int len, uint32_t* wsum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t a1 = 0, a2 = 0;
+#pragma unroll
+  for (int d = 0; d < 16; ++d)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = 4 * d + k;
+      const uint32_t b = i < n ? (sp[d] >> (8 * k)) & 255u : 0u;
+      a1 += b; a2 += static_cast<uint32_t>(len - (base + i)) * b;
+    }
+  a2 %= 65521u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); }
+  if (lane == 0) { wsum[wave] = a1; wsum[4 + wave] = a2; }
+}
+__device__ __forceinline__ void adler_report(const DeflArgs& P, const int64_t chunk, const uint32_t* wsum, const int len) {
+  P.ad_a[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  P.ad_b[chunk] = (wsum[4] + wsum[5] + wsum[6] + wsum[7]) % 65521u;
+  P.ad_n[chunk] = static_cast<uint32_t>(len);
+}
+
+// C. The code rule (Shannon lengths, then the slack handed back in up to 16 rounds; canonical codes) for ONE WAVE over nsym <= 320
+// symbols: lane j holds symbols j, 64 + j, ... 256 + j.  Writes clen[] and code[] (code | length << 16, bit-reversed) and returns whether
+// the code is complete.  single: the distance code's two special cases - one symbol in use gets length 1, none in use gives symbol 0
+// length 1 (what the run form's header says).
+__device__ __forceinline__ bool build_code(const uint32_t* hist, uint32_t* clen, uint32_t* code, const int nsym, const int lane, const bool single) {
+  uint32_t cnt[5]; int ln[5];
+  uint32_t tot = 0;
+  int used = 0;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) { const int sy = 64 * q + lane; cnt[q] = sy < nsym ? hist[sy] : 0u; tot += cnt[q]; used += __popcll(__ballot(cnt[q] != 0u)); }
+  if (single && used <= 1) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int sy = 64 * q + lane;
+      if (sy < nsym) { const bool it = used ? cnt[q] != 0u : sy == 0; clen[sy] = it ? 1u : 0u; code[sy] = it ? (1u << 16) : 0u; }
+    }
+    return true;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+  int kraft = 0, cls[16];
+#pragma unroll
+  for (int l = 0; l < 16; ++l) cls[l] = 0;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    ln[q] = 0;
+    if (cnt[q]) {
+      const uint32_t r = (tot + cnt[q] - 1) / cnt[q];
+      int l = r <= 1u ? 0 : 32 - __clz(static_cast<int>(r - 1u));
+      l = l < 1 ? 1 : (l > 15 ? 15 : l);
+      ln[q] = l;
+      kraft += 1 << (15 - l);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) kraft += __shfl_xor(kraft, off);
+#pragma unroll
+  for (int l = 1; l < 16; ++l) {
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) c += __popcll(__ballot(ln[q] == l));
+    cls[l] = c;
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  auto ranks_in = [&](int l, int (&rk)[5]) {
+    int acc = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const unsigned long long m = __ballot(ln[q] == l);
+      rk[q] = acc + __popcll(m & below);
+      acc += __popcll(m);
+    }
+  };
+  int slack = 32768 - kraft;
+  for (int round = 0; round < 16 && slack > 0; ++round) {
+#pragma unroll
+    for (int l = 2; l < 16; ++l) {
+      const int cost = 1 << (15 - l);
+      const int take = min(cls[l], slack / cost);
+      if (take > 0) {
+        int rk[5];
+        ranks_in(l, rk);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) if (ln[q] == l && rk[q] < take) ln[q] = l - 1;
+        cls[l] -= take; cls[l - 1] += take; slack -= take * cost;
+      }
+    }
+  }
+  if (slack != 0 || tot == 0) return false;
+  int first[16]; int cd = 0;
+  first[0] = 0;
+#pragma unroll
+  for (int l = 1; l < 16; ++l) { cd = (cd + cls[l - 1]) << 1; first[l] = cd; }
+  int cdq[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+  for (int l = 1; l < 16; ++l) {
+    if (cls[l] == 0) continue;
+    int rk[5];
+    ranks_in(l, rk);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) if (ln[q] == l) cdq[q] = first[l] + rk[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const int sy = 64 * q + lane;
+    if (sy < nsym) {
+      clen[sy] = static_cast<uint32_t>(ln[q]);
+      code[sy] = ln[q] ? (rev_bits(static_cast<uint32_t>(cdq[q]), ln[q]) | (static_cast<uint32_t>(ln[q]) << 16)) : 0u;
+    }
+  }
+  return true;
+}
+
+// header of a dynamic block at bit 8 lead: BFINAL 0, BTYPE 2, HLIT 29, HDIST hdist, HCLEN 15, the 19 code-length-code lengths, then
+// the 286 + hdist + 1 code lengths.  Code-length alphabet: symbols 0..15 all 4 bits long (a complete code: canonical code of symbol
+// s = s), 16-18 unused.  dclen: the distance code's lengths; null (hdist 0) for the run form's one distance code of 1 bit.
+template <bool DIST>
+__device__ __forceinline__ void block_header(uint32_t* outw, const int lead, const int hdist, const uint32_t* clen, const uint32_t* dclen, const int tid) {
+  uint8_t* outb = reinterpret_cast<uint8_t*>(outw);
+  const int hb = lead * 8;
+  if (tid == 0) {
+    if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
+    or_bits(outw, hb, 4u | (29u << 3) | (static_cast<uint32_t>(hdist) << 8) | (15u << 13), 17);
+  }
+  if (tid < 19) or_bits(outw, hb + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);       // order 16,17,18,0,8,7,...: first three are unused
+  for (int s = tid; s < NSYM + hdist + 1; s += 256) {
+    const uint32_t l = s < NSYM ? clen[s] : (dclen ? dclen[s - NSYM] : 1u);
+    or_bits(outw, hb + 17 + 57 + 4 * s, rev_bits(l, 4), 4);
+  }
+}
+
+// the end of a dynamic block whose tokens end at bit end_bit - clen[256]: the end-of-block symbol, then the empty stored block that
+// re-aligns to a byte.  Returns the bytes before the alignment pads.
+__device__ __forceinline__ int block_end(uint32_t* outw, const int end_bit, const uint32_t* clen, const uint32_t* code, const int tid) {
+  uint8_t* outb = reinterpret_cast<uint8_t*>(outw);
+  if (tid == 0) or_bits(outw, end_bit - static_cast<int>(clen[256]), code[256] & 0xFFFFu, static_cast<int>(clen[256]));
+  int body_end = (end_bit + 3 + 7) / 8;               // 3 zero bits: BFINAL 0, BTYPE 00; then to the byte boundary
+  __syncthreads();
+  if (tid == 0) { outb[body_end + 2] = 0xFF; outb[body_end + 3] = 0xFF; }      // LEN 0000, NLEN FFFF
+  return body_end + 4;
+}
+
+// the stored form of a chunk: every thread writes its span behind the 5-byte block header.  Returns the bytes before the alignment pads.
+__device__ __forceinline__ int stored_form(uint8_t* outb, const int lead, const int len, const uint32_t (&sp)[16], const int n, const int base, const int tid) {
+  if (tid == 0) {
+    if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
+    uint8_t* q = outb + lead;
+    q[0] = 0; q[1] = len & 0xFF; q[2] = (len >> 8) & 0xFF; q[3] = (~len) & 0xFF; q[4] = ((~len) >> 8) & 0xFF;
+  }
+#pragma unroll
+  for (int d = 0; d < 16; ++d)
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (4 * d + k < n) outb[lead + 5 + base + 4 * d + k] = static_cast<uint8_t>(sp[d] >> (8 * k));
+  return lead + 5 + len;
+}
+
+// (thread 0) pads the chunk to a multiple of 16 bytes with empty stored blocks - 00 00 00 FF FF - and reports its length
+__device__ __forceinline__ void pad_chunk(const DeflArgs& P, const int64_t chunk, uint8_t* outb, const int body_end, int* out_len) {
+  int total = body_end;
+  while (total & 15) { outb[total + 3] = 0xFF; outb[total + 4] = 0xFF; total += 5; }
+  *out_len = total;
+  P.len16[chunk] = static_cast<uint32_t>(total >> 4);
+}
+
+// E. write the chunk to its slot; raw CRC of its bytes (each 16-byte unit shifted to the end of the chunk).  area: 1024 words that are
+// dead by now and take the CRC tables
+__device__ __forceinline__ void write_slot(const DeflArgs& P, const int64_t chunk, const uint32_t* outw, const int* s_out_len, uint32_t* area, uint32_t* wsum) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t (*const T)[256] = reinterpret_cast<uint32_t (*)[256]>(area);
+  for (int i = tid; i < 1024; i += 256) area[i] = P.tables[i];
+  __syncthreads();
+  const int out_len = *s_out_len;
+  uint8_t* slot = P.slots + static_cast<size_t>(chunk) * SLOT;
+  uint32_t crc = 0;
+  for (int u = tid; u < (out_len >> 4); u += 256) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(outw + 4 * u);
+    *reinterpret_cast<u32x4*>(slot + 16 * static_cast<size_t>(u)) = v;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t c = 0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      c ^= w[d];
+      c = T[3][c & 0xFF] ^ T[2][(c >> 8) & 0xFF] ^ T[1][(c >> 16) & 0xFF] ^ T[0][c >> 24];
+    }
+    crc ^= gf_mul(P.xpow16[(out_len >> 4) - 1 - u], c);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) crc ^= __shfl_xor(crc, off);
+  __syncthreads();
+  if (lane == 0) wsum[wave] = crc;
+  __syncthreads();
+  if (tid == 0) P.crc[chunk] = wsum[0] ^ wsum[1] ^ wsum[2] ^ wsum[3];
+}
+
 // One workgroup compresses chunk `chunk` of the canvas P describes (the body of the compressing kernels below).  BPP: bytes of a
-// pixel in the filtered stream - 4 (RGBA, colour type 6) or 3 (RGB, colour type 2: the canvas is still read a dword per pixel, the
-// alpha byte of the residual is not stored).  Only step A knows it; from step B on a chunk is bytes.  ADAPT: the filter type of canvas
-// row y is ftab[y] (written by the row-filter pre-pass) instead of 4; again only step A knows.
+// pixel in the filtered stream - 4 or 3; ADAPT: the row types come from ftab.  Only step A knows either; from step B on a chunk is bytes.
 template <int BPP, bool ADAPT = false>
 __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t chunk, const uint8_t* ftab = nullptr) {
   // ONE buffer, two lives: the filtered chunk (padded layout) until every thread has taken its span into registers, then the
@@ -278,12 +558,11 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   // one LDS area, two lives: histogram / code lengths / codes while the block is built, then the CRC tables
   __shared__ __attribute__((aligned(16))) uint32_t area[1024];      // (>= 3 * 288)
   uint32_t* const hist = area; uint32_t* const clen = area + 288; uint32_t* const code = area + 576;
-  uint32_t (*const T)[256] = reinterpret_cast<uint32_t (*)[256]>(area);
   __shared__ uint32_t wsum[8];
   __shared__ int s_out_len, s_skip;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-  // ---- which pixels: rows [y0, y0 + nrows) x columns [x0, x0 + npr); the filter byte belongs to the piece with x0 == 0
+  // ---- which pixels.  (chunk_rect states this for the window body.  Sharing it here changes the pinned code objects: in each of five
+  // forms the two adaptive batch kernels come out with other scalar registers, at 6214 and 6190 instructions as before.)
   int64_t y0; int nrows, x0, npr;
   if (P.rows_per_chunk > 0) {
     y0 = chunk * P.rows_per_chunk; nrows = static_cast<int>(min(static_cast<int64_t>(P.rows_per_chunk), P.h - y0)); x0 = 0; npr = static_cast<int>(P.w);
@@ -298,7 +577,8 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
 
   for (int i = tid; i < 288; i += 256) { hist[i] = 0; clen[i] = 0; code[i] = 0; }
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 0] = wall_clock64();
-  // ---- A. load + Paeth filter into LDS
+  // ---- A. load + filter into LDS.  (filter_chunk states this for the window body.  Sharing it here changes the pinned code objects,
+  // as a template on BPP and ADAPT too: ist_png_deflate_kernel 6147 -> 6129 instructions, the adaptive kernel 6285 -> 6303.)
   const int npix = npr * nrows;
   // (adaptive, a chunk of one row or a piece of one: its type is one scalar load for the workgroup)
   uint32_t ft_row = 4u;
@@ -349,15 +629,12 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   const int base = tid * SPAN;
   const int n = max(0, min(SPAN, len - base));
   uint32_t sp[16];
-  {
-    const u32x4* mine = reinterpret_cast<const u32x4*>(filt + tid * (SPAN + 4));      // (68-byte pitch: 4-byte aligned)
-    const uint32_t* mw = reinterpret_cast<const uint32_t*>(mine);
-#pragma unroll
-    for (int d = 0; d < 16; ++d) sp[d] = mw[d];
-  }
+  load_span(filt, tid, sp);
   __syncthreads();                                   // every span is in registers: the buffer is free
   walk_span<0>(sp, n, span_masks(sp, n), hist, nullptr, nullptr, nullptr);
   if (tid == 0) atomicAdd(&hist[256], 1u);
+  // (adler_partials states these sums for the window body.  Sharing it here changes the pinned code objects: ist_png_deflate_kernel
+  // 6147 -> 6139 instructions.)
   uint32_t a1 = 0, a2 = 0;
 #pragma unroll
   for (int d = 0; d < 16; ++d)
@@ -372,14 +649,11 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   for (int off = 32; off > 0; off >>= 1) { a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); }
   if (lane == 0) { wsum[wave] = a1; wsum[4 + wave] = a2; }
   __syncthreads();
-  if (tid == 0) {
-    P.ad_a[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    P.ad_b[chunk] = (wsum[4] + wsum[5] + wsum[6] + wsum[7]) % 65521u;
-    P.ad_n[chunk] = static_cast<uint32_t>(len);
-  }
+  if (tid == 0) adler_report(P, chunk, wsum, len);
 
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 2] = wall_clock64();
-  // (build_code below states this same rule a second time, for the window twins; a change here is a change there)
+  // (build_code states this rule for the window body.  Sharing it here changes the pinned code objects: ist_png_deflate_kernel
+  // 6147 -> 6123 instructions and its private segment 68 -> 72 bytes; as a template or moved verbatim 6128 and 6126.)
   // ---- C. code lengths and codes: ONE WAVE, in registers.  Not Huffman's algorithm: Shannon lengths (the smallest l with
   // count * 2^l >= total, <= 15 for a 16 KiB chunk; their Kraft sum is <= 1) and then the slack handed back - symbols
   // are shortened by one bit, shortest codes first, as long as the Kraft sum allows, round after round until the code is
@@ -502,27 +776,20 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
   uint8_t* outb = reinterpret_cast<uint8_t*>(outw);
   int body_end;                                       // bytes before the alignment pads
   if (!stored) {
-    // header: BFINAL 0, BTYPE 2, HLIT 29, HDIST 0, HCLEN 15, the 19 code-length-code lengths, 286 + 1 code lengths.
-    // Code-length alphabet: symbols 0..15 all 4 bits long (a complete code: canonical code of symbol s = s), 16-18 unused.
-    const int hb = lead * 8;
-    if (tid == 0) {
-      if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
-      or_bits(outw, hb, 4u | (29u << 3) | (0u << 8) | (15u << 13), 17);
-    }
-    if (tid < 19) or_bits(outw, hb + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);       // order 16,17,18,0,8,7,...: first three are unused
-    for (int s = tid; s < NSYM + 1; s += 256) {
-      const uint32_t l = s < NSYM ? clen[s] : 1u;                                // the one distance code: 1 bit
-      or_bits(outw, hb + 17 + 57 + 4 * s, rev_bits(l, 4), 4);
-    }
+    block_header<false>(outw, lead, 0, clen, nullptr, tid);
     BitWriter bw; bw.init(outw, my_start);
     walk_span<2>(sp, n, masks, nullptr, clen, code, &bw);
     bw.flush();
+    // (block_end states these five lines for the window body.  Sharing it here changes the pinned code objects: ist_png_deflate_kernel
+    // 6147 -> 6172 instructions, returning the length or through a reference alike.)
     if (tid == 0) or_bits(outw, end_bit - static_cast<int>(clen[256]), code[256] & 0xFFFFu, static_cast<int>(clen[256]));
     body_end = (end_bit + 3 + 7) / 8;                 // 3 zero bits: BFINAL 0, BTYPE 00; then to the byte boundary
     __syncthreads();
     if (tid == 0) { outb[body_end + 2] = 0xFF; outb[body_end + 3] = 0xFF; }      // LEN 0000, NLEN FFFF
     body_end += 4;
   } else {
+    // (stored_form states this for the window body.  Sharing it here changes the pinned code objects: ist_png_deflate_kernel
+    // 6147 -> 6139 instructions, whole or split into its header and its span copy.)
     if (tid == 0) {
       if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
       uint8_t* q = outb + lead;
@@ -536,39 +803,12 @@ __device__ __forceinline__ void deflate_chunk(const DeflArgs& P, const int64_t c
     body_end = lead + 5 + len;
   }
   __syncthreads();
-  if (tid == 0) {
-    int total = body_end;
-    while (total & 15) { outb[total + 3] = 0xFF; outb[total + 4] = 0xFF; total += 5; }   // empty stored blocks: 00 00 00 FF FF
-    s_out_len = total;
-    P.len16[chunk] = static_cast<uint32_t>(total >> 4);
-  }
+  if (tid == 0) pad_chunk(P, chunk, outb, body_end, &s_out_len);
   __syncthreads();
 
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 5] = wall_clock64();
-  // ---- E. write the chunk to its slot; raw CRC of its bytes (each 16-byte unit shifted to the end of the chunk)
-  for (int i = tid; i < 1024; i += 256) area[i] = P.tables[i];          // the code tables are dead: the area now holds the CRC tables
-  __syncthreads();
-  const int out_len = s_out_len;
-  uint8_t* slot = P.slots + static_cast<size_t>(chunk) * SLOT;
-  uint32_t crc = 0;
-  for (int u = tid; u < (out_len >> 4); u += 256) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(outw + 4 * u);
-    *reinterpret_cast<u32x4*>(slot + 16 * static_cast<size_t>(u)) = v;
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t c = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      c ^= w[d];
-      c = T[3][c & 0xFF] ^ T[2][(c >> 8) & 0xFF] ^ T[1][(c >> 16) & 0xFF] ^ T[0][c >> 24];
-    }
-    crc ^= gf_mul(P.xpow16[(out_len >> 4) - 1 - u], c);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) crc ^= __shfl_xor(crc, off);
-  __syncthreads();
-  if (lane == 0) wsum[wave] = crc;
-  __syncthreads();
-  if (tid == 0) P.crc[chunk] = wsum[0] ^ wsum[1] ^ wsum[2] ^ wsum[3];
+  // ---- E. write the chunk to its slot; raw CRC of its bytes
+  write_slot(P, chunk, outw, &s_out_len, area, wsum);
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 6] = wall_clock64();
 }
 
@@ -587,17 +827,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void i
 // ---- batch twins: the chunks of many canvases in ONE launch (png_encode_batch_deflate).  Chunks are numbered file-major;
 // chunk_begin[f] is file f's first, chunk_begin[n_files] the total.  A file's per-chunk results and slots are the arrays'
 // entries [chunk_begin[f], chunk_begin[f + 1]), so the body above runs unchanged on the file's own chunk numbers.
-struct DeflJob { const uint8_t* canvas; size_t pitch; int64_t w, h; int32_t rows_per_chunk, pieces_per_row, piece_px, pad_; };
-struct DeflBatchArgs {
-  const DeflJob* jobs;           // per file (device memory)
-  const int64_t* chunk_begin;    // n_files + 1 (device memory)
-  int32_t n_files;
-  uint8_t* slots;
-  uint32_t* len16; uint32_t* crc; uint32_t* ad_a; uint32_t* ad_b; uint32_t* ad_n;
-  const uint32_t* tables; const uint32_t* xpow16;
-};
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_batch_kernel(const DeflBatchArgs B) {
+// workgroup blockIdx.x of a batch launch: its file *f, its chunk number *chunk in that file, and the arguments the file's own launch
+// would have had (the file's slice of the slots and of the per-chunk results)
+__device__ __forceinline__ DeflArgs batch_chunk(const DeflBatchArgs& B, int64_t* chunk, int* file) {
   const int64_t g = blockIdx.x;
   const int f = batch_file_of(B.chunk_begin, B.n_files, g);
   const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
@@ -609,24 +842,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void i
   P.tables = B.tables; P.xpow16 = B.xpow16;
   P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
   P.chunk0 = 0; P.dbg = nullptr;
-  deflate_chunk<4>(P, g - base);
+  *chunk = g - base; *file = f;
+  return P;
 }
 
-// the RGB form of the batch.  (Its own copy of the twelve lines above: shared through a function they compile to other code, and the
-// 4-byte kernel is to stay the code object it was.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void ist_png_deflate_batch_kernel(const DeflBatchArgs B) {
+  int64_t chunk; int f;
+  const DeflArgs P = batch_chunk(B, &chunk, &f);
+  deflate_chunk<4>(P, chunk);
+}
+
+// the RGB form of the batch
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_rgb_batch_kernel(const DeflBatchArgs B) {
-  const int64_t g = blockIdx.x;
-  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
-  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
-  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
-  DeflArgs P;
-  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
-  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
-  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
-  P.tables = B.tables; P.xpow16 = B.xpow16;
-  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
-  P.chunk0 = 0; P.dbg = nullptr;
-  deflate_chunk<3>(P, g - base);
+  int64_t chunk; int f;
+  const DeflArgs P = batch_chunk(B, &chunk, &f);
+  deflate_chunk<3>(P, chunk);
 }
 
 // ---- adaptive row filters (IST_PNG_FILTER_ADAPTIVE): the pre-pass that chooses a type per row, and the compressing kernels' twins
@@ -756,18 +986,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void i
 // batch: file f's rows are table entries [row_begin[f], row_begin[f + 1])
 template <int BPP>
 __device__ __forceinline__ void deflate_adapt_batch_body(const DeflBatchArgs& B, const int64_t* row_begin, const uint8_t* ftab) {
-  const int64_t g = blockIdx.x;
-  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
-  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
-  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
-  DeflArgs P;
-  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
-  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
-  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
-  P.tables = B.tables; P.xpow16 = B.xpow16;
-  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
-  P.chunk0 = 0; P.dbg = nullptr;
-  deflate_chunk<BPP, true>(P, g - base, ftab + ((ConstPtr<int64_t>)row_begin)[f]);
+  int64_t chunk; int f;
+  const DeflArgs P = batch_chunk(B, &chunk, &f);
+  deflate_chunk<BPP, true>(P, chunk, ftab + ((ConstPtr<int64_t>)row_begin)[f]);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ist_png_deflate_adapt_batch_kernel(const DeflBatchArgs B, const int64_t* row_begin, const uint8_t* ftab) {
   deflate_adapt_batch_body<4>(B, row_begin, ftab);
@@ -802,22 +1023,6 @@ __device__ __forceinline__ void dist_code(int d, int* sym, int* eb, int* ev) {
   if (d <= 4) { *sym = d - 1; *eb = 0; *ev = 0; return; }
   const int t = d - 1, e = (31 - __builtin_clz(t)) - 1;
   *sym = 2 * (e + 1) + ((t >> e) & 1); *eb = e; *ev = t & ((1 << e) - 1);
-}
-
-// eq bit i: byte i of the span equals byte i - 1 (as in span_masks)
-__device__ __forceinline__ unsigned long long span_eq(const uint32_t (&sp)[16], int n) {
-  unsigned long long eq = 0;
-#pragma unroll
-  for (int d = 0; d < 16; ++d) {
-    const uint32_t w = sp[d];
-    const uint32_t prev = d ? (sp[d ? d - 1 : 0] >> 24) : (~w & 0xFFu);
-    const uint32_t x = w ^ ((w << 8) | prev);
-    const uint32_t nz = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-    const uint32_t z = (nz ^ 0x80808080u) >> 7;
-    eq |= static_cast<unsigned long long>(((z * 0x00204081u) >> 21) & 15u) << (4 * d);
-  }
-  const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-  return eq & valid & ~1ull;
 }
 
 // the four bytes at position p .. p + 3 of the filtered chunk (padded layout; p + 3 < CH), little-endian
@@ -874,101 +1079,6 @@ __device__ __forceinline__ int walk_tokens(const uint32_t (&sp)[16], int n, cons
   return bits;
 }
 
-// (A second statement of step C of deflate_chunk above, whose machine code is pinned and is therefore not touched: a change of the rule
-// is a change of both.)
-// The code rule of step C (Shannon lengths, then the slack handed back in up to 16 rounds; canonical codes) for ONE WAVE over nsym <= 320
-// symbols: lane j holds symbols j, 64 + j, ... 256 + j.  Writes clen[] and code[] (code | length << 16, bit-reversed) and returns whether
-// the code is complete.  single: the distance code's two special cases - one symbol in use gets length 1, none in use gives symbol 0
-// length 1 (what the run form's header says).
-__device__ __forceinline__ bool build_code(const uint32_t* hist, uint32_t* clen, uint32_t* code, const int nsym, const int lane, const bool single) {
-  uint32_t cnt[5]; int ln[5];
-  uint32_t tot = 0;
-  int used = 0;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) { const int sy = 64 * q + lane; cnt[q] = sy < nsym ? hist[sy] : 0u; tot += cnt[q]; used += __popcll(__ballot(cnt[q] != 0u)); }
-  if (single && used <= 1) {
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const int sy = 64 * q + lane;
-      if (sy < nsym) { const bool it = used ? cnt[q] != 0u : sy == 0; clen[sy] = it ? 1u : 0u; code[sy] = it ? (1u << 16) : 0u; }
-    }
-    return true;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
-  int kraft = 0, cls[16];
-#pragma unroll
-  for (int l = 0; l < 16; ++l) cls[l] = 0;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    ln[q] = 0;
-    if (cnt[q]) {
-      const uint32_t r = (tot + cnt[q] - 1) / cnt[q];
-      int l = r <= 1u ? 0 : 32 - __clz(static_cast<int>(r - 1u));
-      l = l < 1 ? 1 : (l > 15 ? 15 : l);
-      ln[q] = l;
-      kraft += 1 << (15 - l);
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) kraft += __shfl_xor(kraft, off);
-#pragma unroll
-  for (int l = 1; l < 16; ++l) {
-    int c = 0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) c += __popcll(__ballot(ln[q] == l));
-    cls[l] = c;
-  }
-  const unsigned long long below = (1ull << lane) - 1ull;
-  auto ranks_in = [&](int l, int (&rk)[5]) {
-    int acc = 0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const unsigned long long m = __ballot(ln[q] == l);
-      rk[q] = acc + __popcll(m & below);
-      acc += __popcll(m);
-    }
-  };
-  int slack = 32768 - kraft;
-  for (int round = 0; round < 16 && slack > 0; ++round) {
-#pragma unroll
-    for (int l = 2; l < 16; ++l) {
-      const int cost = 1 << (15 - l);
-      const int take = min(cls[l], slack / cost);
-      if (take > 0) {
-        int rk[5];
-        ranks_in(l, rk);
-#pragma unroll
-        for (int q = 0; q < 5; ++q) if (ln[q] == l && rk[q] < take) ln[q] = l - 1;
-        cls[l] -= take; cls[l - 1] += take; slack -= take * cost;
-      }
-    }
-  }
-  if (slack != 0 || tot == 0) return false;
-  int first[16]; int cd = 0;
-  first[0] = 0;
-#pragma unroll
-  for (int l = 1; l < 16; ++l) { cd = (cd + cls[l - 1]) << 1; first[l] = cd; }
-  int cdq[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-  for (int l = 1; l < 16; ++l) {
-    if (cls[l] == 0) continue;
-    int rk[5];
-    ranks_in(l, rk);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) if (ln[q] == l) cdq[q] = first[l] + rk[q];
-  }
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const int sy = 64 * q + lane;
-    if (sy < nsym) {
-      clen[sy] = static_cast<uint32_t>(ln[q]);
-      code[sy] = ln[q] ? (rev_bits(static_cast<uint32_t>(cdq[q]), ln[q]) | (static_cast<uint32_t>(ln[q]) << 16)) : 0u;
-    }
-  }
-  return true;
-}
-
 // One workgroup compresses chunk `chunk` with window matches.  bpp: 4 or 3; ftab: the row types of the adaptive filters, or null for
 // Paeth on every row.
 __device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const int64_t chunk, const uint8_t* ftab, const int bpp) {
@@ -984,59 +1094,17 @@ __device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const in
   uint32_t* const rdclen = area + 864; uint32_t* const rdcode = area + 896;                       // the run form's one distance code
   uint32_t* const hist2 = area2; uint32_t* const clen2 = area2 + 288; uint32_t* const code2 = area2 + 576;
   uint32_t* const dhist = area2 + 864; uint32_t* const dclen = area2 + 896; uint32_t* const dcode = area2 + 928;
-  uint32_t (*const T)[256] = reinterpret_cast<uint32_t (*)[256]>(area);
   __shared__ uint32_t wsum[8];
   __shared__ int s_out_len, s_skip_run, s_skip_ll, s_skip_d, s_hdist;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool adapt = ftab != nullptr;
-
-  int64_t y0; int nrows, x0, npr;
-  if (P.rows_per_chunk > 0) {
-    y0 = chunk * P.rows_per_chunk; nrows = static_cast<int>(min(static_cast<int64_t>(P.rows_per_chunk), P.h - y0)); x0 = 0; npr = static_cast<int>(P.w);
-  } else {
-    y0 = chunk / P.pieces_per_row; nrows = 1;
-    const int piece = static_cast<int>(chunk - y0 * P.pieces_per_row);
-    x0 = piece * P.piece_px; npr = static_cast<int>(min(static_cast<int64_t>(P.piece_px), P.w - x0));
-  }
-  const int hasf = x0 == 0 ? 1 : 0;
-  const int rowlen = hasf + bpp * npr;
-  const int len = rowlen * nrows;                // <= CH by construction
+  const ChunkRect R = chunk_rect(P, chunk, bpp);
+  const int len = R.len;
 
   for (int i = tid; i < 1024; i += 256) { area[i] = 0; area2[i] = 0; }
   for (int i = tid; i < 4096; i += 256) htab[i] = -1;
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 0] = wall_clock64();
-  // ---- A. load + filter into LDS (as deflate_chunk's; the type of a row is 4 without a table)
-  const int npix = npr * nrows;
-  for (int q0 = tid; q0 < npix; q0 += 1024) {
-    uint32_t cur[4], a[4], b[4], c[4], ft[4]; int pos[4]; bool on[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int q = q0 + 256 * u;
-      on[u] = q < npix;
-      cur[u] = a[u] = b[u] = c[u] = 0u; pos[u] = 0; ft[u] = 4u;
-      if (on[u]) {
-        const int r = nrows == 1 ? 0 : q / npr, xx = q - r * npr;
-        const int64_t y = y0 + r; const int x = x0 + xx;
-        const uint8_t* row = P.canvas + static_cast<size_t>(y) * P.pitch;
-        cur[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x));
-        if (x > 0) a[u] = *reinterpret_cast<const uint32_t*>(row + 4 * static_cast<size_t>(x - 1));
-        if (y > 0) {
-          b[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x));
-          if (x > 0) c[u] = *reinterpret_cast<const uint32_t*>(row - P.pitch + 4 * static_cast<size_t>(x - 1));
-        }
-        pos[u] = r * rowlen + hasf + bpp * xx;
-        if (adapt) ft[u] = static_cast<uint32_t>(ftab[y]);
-        if (hasf && xx == 0) filt[padpos(r * rowlen)] = static_cast<uint8_t>(ft[u]);      // filter type of the row
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (!on[u]) continue;
-      const uint32_t fv = filter4(ft[u], cur[u], a[u], b[u], c[u]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) if (k < bpp) filt[padpos(pos[u] + k)] = static_cast<uint8_t>(fv >> (8 * k));
-    }
-  }
+  // ---- A. load + filter into LDS (the type of a row is 4 without a table)
+  filter_chunk(P, R, ftab, bpp, filt);
   __syncthreads();
   // (behind the barrier: other waves zeroed these words above; they are first read in step D, several barriers on)
   if (tid == 0) { rdclen[0] = 1u; rdcode[0] = 1u << 16; }
@@ -1046,11 +1114,7 @@ __device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const in
   const int base = tid * SPAN;
   const int n = max(0, min(SPAN, len - base));
   uint32_t sp[16];
-  {
-    const uint32_t* mw = reinterpret_cast<const uint32_t*>(filt + tid * (SPAN + 4));
-#pragma unroll
-    for (int d = 0; d < 16; ++d) sp[d] = mw[d];
-  }
+  load_span(filt, tid, sp);
   uint16_t* const cand = candt + tid * CAND_PITCH;
   {
     const uint32_t nextw = tid < 255 ? *reinterpret_cast<const uint32_t*>(filt + (tid + 1) * (SPAN + 4)) : 0u;
@@ -1084,35 +1148,14 @@ __device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const in
       }
     }
   }
-  const unsigned long long eq = span_eq(sp, n);
-  const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-  SpanTokens RT;                                      // the run form, as span_masks has it
-  {
-    const unsigned long long t = eq & (eq >> 1) & (eq >> 2);
-    const unsigned long long covered = (t | (t << 1) | (t << 2)) & valid;
-    RT.lit = valid & ~covered; RT.mstart = covered & ~(covered << 1); RT.win = 0ull;
-  }
+  const SpanMasks RM = span_masks(sp, n);
+  const unsigned long long eq = RM.eq;
+  const SpanTokens RT{RM.lit, RM.mstart, 0ull};      // the run form
   walk_tokens<0>(sp, n, RT, cand, base, hist, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (tid == 0) { atomicAdd(&hist[256], 1u); atomicAdd(&hist2[256], 1u); }
-  uint32_t a1 = 0, a2 = 0;
-#pragma unroll
-  for (int d = 0; d < 16; ++d)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int i = 4 * d + k;
-      const uint32_t b = i < n ? (sp[d] >> (8 * k)) & 255u : 0u;
-      a1 += b; a2 += static_cast<uint32_t>(len - (base + i)) * b;
-    }
-  a2 %= 65521u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); }
-  if (lane == 0) { wsum[wave] = a1; wsum[4 + wave] = a2; }
+  adler_partials(sp, n, base, len, wsum);
   __syncthreads();                                   // the candidate table is complete
-  if (tid == 0) {
-    P.ad_a[chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    P.ad_b[chunk] = (wsum[4] + wsum[5] + wsum[6] + wsum[7]) % 65521u;
-    P.ad_n[chunk] = static_cast<uint32_t>(len);
-  }
+  if (tid == 0) adler_report(P, chunk, wsum, len);
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 2] = wall_clock64();
   // ---- B2. the window parse of this span: greedy from its first byte
   // First, for all 64 positions at once (independent loads: their latency overlaps), whether the candidate's four key bytes are the
@@ -1200,72 +1243,19 @@ __device__ __forceinline__ void deflate_chunk_window(const DeflArgs& P, const in
     const uint32_t* const dl = win ? dclen : rdclen; const uint32_t* const dc = win ? dcode : rdcode;
     const int hd = win ? hdist : 0, end_bit = win ? wend : rend;
     const int my_start = lead * 8 + HDR_BITS + 4 * hd + (win ? wwave + wincl - wbits : rwave + rincl - rbits);
-    // header: BFINAL 0, BTYPE 2, HLIT 29, HDIST hd, HCLEN 15, the 19 code-length-code lengths, 286 + hd + 1 code lengths in 4 bits each
-    const int hb = lead * 8;
-    if (tid == 0) {
-      if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
-      or_bits(outw, hb, 4u | (29u << 3) | (static_cast<uint32_t>(hd) << 8) | (15u << 13), 17);
-    }
-    if (tid < 19) or_bits(outw, hb + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);
-    for (int s = tid; s < NSYM + hd + 1; s += 256) {
-      const uint32_t l = s < NSYM ? cl[s] : dl[s - NSYM];
-      or_bits(outw, hb + 17 + 57 + 4 * s, rev_bits(l, 4), 4);
-    }
+    block_header<true>(outw, lead, hd, cl, dl, tid);
     BitWriter bw; bw.init(outw, my_start);
     walk_tokens<2>(sp, n, win ? WT : RT, cand, base, nullptr, nullptr, nullptr, nullptr, co, dc, &bw);
     bw.flush();
-    if (tid == 0) or_bits(outw, end_bit - static_cast<int>(cl[256]), co[256] & 0xFFFFu, static_cast<int>(cl[256]));
-    body_end = (end_bit + 3 + 7) / 8;                 // 3 zero bits: BFINAL 0, BTYPE 00; then to the byte boundary
-    __syncthreads();
-    if (tid == 0) { outb[body_end + 2] = 0xFF; outb[body_end + 3] = 0xFF; }      // LEN 0000, NLEN FFFF
-    body_end += 4;
-  } else {
-    if (tid == 0) {
-      if (lead) { outb[0] = 0x78; outb[1] = 0x01; }
-      uint8_t* q = outb + lead;
-      q[0] = 0; q[1] = len & 0xFF; q[2] = (len >> 8) & 0xFF; q[3] = (~len) & 0xFF; q[4] = ((~len) >> 8) & 0xFF;
-    }
-#pragma unroll
-    for (int d = 0; d < 16; ++d)
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (4 * d + k < n) outb[lead + 5 + base + 4 * d + k] = static_cast<uint8_t>(sp[d] >> (8 * k));
-    body_end = lead + 5 + len;
-  }
+    body_end = block_end(outw, end_bit, cl, co, tid);
+  } else body_end = stored_form(outb, lead, len, sp, n, base, tid);
   __syncthreads();
-  if (tid == 0) {
-    int total = body_end;
-    while (total & 15) { outb[total + 3] = 0xFF; outb[total + 4] = 0xFF; total += 5; }   // empty stored blocks: 00 00 00 FF FF
-    s_out_len = total;
-    P.len16[chunk] = static_cast<uint32_t>(total >> 4);
-  }
+  if (tid == 0) pad_chunk(P, chunk, outb, body_end, &s_out_len);
   __syncthreads();
 
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 5] = wall_clock64();
-  // ---- E. write the chunk to its slot; raw CRC of its bytes (as deflate_chunk's)
-  for (int i = tid; i < 1024; i += 256) area[i] = P.tables[i];
-  __syncthreads();
-  const int out_len = s_out_len;
-  uint8_t* slot = P.slots + static_cast<size_t>(chunk) * SLOT;
-  uint32_t crc = 0;
-  for (int u = tid; u < (out_len >> 4); u += 256) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(outw + 4 * u);
-    *reinterpret_cast<u32x4*>(slot + 16 * static_cast<size_t>(u)) = v;
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t c = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      c ^= w[d];
-      c = T[3][c & 0xFF] ^ T[2][(c >> 8) & 0xFF] ^ T[1][(c >> 16) & 0xFF] ^ T[0][c >> 24];
-    }
-    crc ^= gf_mul(P.xpow16[(out_len >> 4) - 1 - u], c);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) crc ^= __shfl_xor(crc, off);
-  __syncthreads();
-  if (lane == 0) wsum[wave] = crc;
-  __syncthreads();
-  if (tid == 0) P.crc[chunk] = wsum[0] ^ wsum[1] ^ wsum[2] ^ wsum[3];
+  // ---- E. write the chunk to its slot; raw CRC of its bytes
+  write_slot(P, chunk, outw, &s_out_len, area, wsum);
   if (P.dbg && tid == 0) P.dbg[chunk * 8 + 6] = wall_clock64();
 }
 
@@ -1274,18 +1264,9 @@ __global__ __launch_bounds__(256) void ist_png_deflate_window_kernel(const DeflA
 }
 // batch: file f's rows are table entries [row_begin[f], row_begin[f + 1]) when there is a table
 __global__ __launch_bounds__(256) void ist_png_deflate_window_batch_kernel(const DeflBatchArgs B, const int64_t* row_begin, const uint8_t* ftab, const int bpp) {
-  const int64_t g = blockIdx.x;
-  const int f = batch_file_of(B.chunk_begin, B.n_files, g);
-  const int64_t base = ((ConstPtr<int64_t>)B.chunk_begin)[f];
-  const DeflJob J = *(const DeflJob*)((ConstPtr<DeflJob>)B.jobs + f);
-  DeflArgs P;
-  P.canvas = J.canvas; P.pitch = J.pitch; P.w = J.w; P.h = J.h;
-  P.slots = B.slots + static_cast<size_t>(base) * SLOT;
-  P.len16 = B.len16 + base; P.crc = B.crc + base; P.ad_a = B.ad_a + base; P.ad_b = B.ad_b + base; P.ad_n = B.ad_n + base;
-  P.tables = B.tables; P.xpow16 = B.xpow16;
-  P.rows_per_chunk = J.rows_per_chunk; P.pieces_per_row = J.pieces_per_row; P.piece_px = J.piece_px;
-  P.chunk0 = 0; P.dbg = nullptr;
-  deflate_chunk_window(P, g - base, ftab ? ftab + ((ConstPtr<int64_t>)row_begin)[f] : nullptr, bpp);
+  int64_t chunk; int f;
+  const DeflArgs P = batch_chunk(B, &chunk, &f);
+  deflate_chunk_window(P, chunk, ftab ? ftab + ((ConstPtr<int64_t>)row_begin)[f] : nullptr, bpp);
 }
 
 struct GatherArgs { const uint8_t* slots; uint8_t* out; const int64_t* dst; const uint32_t* len16; int64_t chunk0; };
@@ -1352,6 +1333,23 @@ const DeflTables& defl_tables() {
   return D;
 }
 
+// the tables into the scratch, where the kernels read them (blocking staged copies of static data)
+int upload_tables(uint8_t* d_tables, uint8_t* d_xpow, hipStream_t stream) {
+  const DeflTables& D = defl_tables();
+  IST_HIP(hipMemcpyAsync(d_tables, &D.T, sizeof D.T, hipMemcpyHostToDevice, stream));
+  IST_HIP(hipMemcpyAsync(d_xpow, D.xpow.data(), 4 * D.xpow.size(), hipMemcpyHostToDevice, stream));
+  return IST_OK;
+}
+
+// The five per-chunk result arrays as the kernels write them into ONE block, [len16 | crc | ad_a | ad_b | ad_n] with `stride` entries
+// each, so that a run of chunks' results are one contiguous piece of pinned memory.  Indexed with the chunk number; `first` is the
+// chunk whose results are the arrays' entry 0 (a slab's first chunk; 0 in a batch).
+struct ChunkResults { uint32_t *len16, *crc, *ad_a, *ad_b, *ad_n; };
+ChunkResults chunk_results(void* base, size_t stride, size_t first) {
+  uint32_t* const r = static_cast<uint32_t*>(base) - first;
+  return ChunkResults{r, r + stride, r + 2 * stride, r + 3 * stride, r + 4 * stride};
+}
+
 // The host side of ONE file, called slab by slab (the whole file is one slab in a batch): Adler-32 of the filtered stream from
 // the chunks' partials, each chunk's place in the file (a new IDAT chunk per slab, and wherever the IDAT limit is reached), the
 // CRC of every IDAT, and the ~100 bytes no kernel writes - signature, IHDR, chunk headers, trailer - as patches.
@@ -1396,21 +1394,20 @@ struct FileLayout {
     lp.at = idat_len_at; put32(lp.b, static_cast<uint32_t>(idat_data)); lp.n = 4; patches->push_back(lp);
     pos += 4;
   }
-  // chunks [0, cn) of the slab with the kernel's per-chunk results; dst[k] = base + the chunk's offset in the file.  last: the
-  // file ends with this slab (trailer, IEND)
-  int slab(const uint32_t* len16, const uint32_t* crc, const uint32_t* ada, const uint32_t* adb, const uint32_t* adn, size_t cn,
-           int64_t* dst, int64_t base, bool last, std::vector<PngPatch>* out) {
+  // chunks [c0, c0 + cn) - a slab - with the kernel's per-chunk results; dst[k] = base + the offset of chunk c0 + k in the file.
+  // last: the file ends with this slab (trailer, IEND)
+  int slab(const ChunkResults& R, size_t c0, size_t cn, int64_t* dst, int64_t base, bool last, std::vector<PngPatch>* out) {
     const uint64_t M = 65521;
     patches = out;
     open_idat();                                       // a slab starts its own IDAT
     for (size_t k = 0; k < cn; ++k) {
-      b = (b + (adn[k] % M) * a + adb[k]) % M;
-      a = (a + ada[k]) % M;
-      const int64_t bytes = static_cast<int64_t>(len16[k]) * 16;
+      b = (b + (R.ad_n[c0 + k] % M) * a + R.ad_b[c0 + k]) % M;
+      a = (a + R.ad_a[c0 + k]) % M;
+      const int64_t bytes = static_cast<int64_t>(R.len16[c0 + k]) * 16;
       if (bytes <= 0 || bytes > SLOT) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length");
       if (idat_data > 0 && idat_data + bytes + 9 > limit) { close_idat(); open_idat(); }
       dst[k] = base + pos;
-      reg = gf_mul(xpow[static_cast<size_t>(len16[k])], reg) ^ crc[k];
+      reg = gf_mul(xpow[static_cast<size_t>(R.len16[c0 + k])], reg) ^ R.crc[c0 + k];
       pos += bytes; idat_data += bytes;
     }
     if (last) {
@@ -1485,8 +1482,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
   // so every slab paid its own tail - the last, partly filled round of workgroups - with the rest of the chip idle; on two
   // streams slab s+1 fills in as slab s drains (a slab is ~3 rounds of workgroups: measured 0.59 ms per 3024-chunk slab alone)
   hipStream_t stream2 = (host_out && stream2_) ? static_cast<hipStream_t>(stream2_) : stream;
-  const CrcTables& T = defl_tables().T;
-  const std::vector<uint32_t>& xpow = defl_tables().xpow;
+  const DeflTables& tables = defl_tables();
   const size_t n = static_cast<size_t>(g.n_chunks);
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // per-chunk results, five arrays interleaved per SLAB so that a slab's results are one contiguous copy:
@@ -1518,7 +1514,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
   // (adaptive: the row types, ONE TABLE OF h BYTES PER STREAM PARITY.  Slabs alternate between two streams and a slab boundary can
   // fall inside a row; with a table per parity a slab's pre-pass writes, and its compressing kernel reads, only bytes of its own
   // stream - the cut row is evaluated by both slabs, each into its own table - so the streams need no event and no wait for it)
-  const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_ftab = o_pow + up(4 * xpow.size()),
+  const size_t o_T = 0, o_pow = o_T + up(sizeof tables.T), o_ftab = o_pow + up(4 * tables.xpow.size()),
                o_slots = o_ftab + (adaptive ? up(2 * static_cast<size_t>(h)) : 0), total_scratch = o_slots + n * SLOT;
   // the context's grow-only scratch: a 439 MB canvas needs 443 MB of slots, and allocating + freeing that per call cost
   // more than the gather kernel (and a free synchronises the device)
@@ -1529,28 +1525,24 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
     if (rc) return rc;
     scratch = static_cast<uint8_t*>(p);
   }
-  IST_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  IST_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  if (stream2 != stream) IST_HIP(hipStreamSynchronize(stream));      // (both are blocking staged copies of static data: the tables are in place for either stream)
+  { const int rc = upload_tables(scratch + o_T, scratch + o_pow, stream); if (rc) return rc; }
+  if (stream2 != stream) IST_HIP(hipStreamSynchronize(stream));      // (the tables are in place for either stream)
   // ---- every slab's compression goes out now, each followed by the copy of its per-chunk results and an event
   // (pinned: a device-to-host copy into pageable memory would block this thread until the slab is compressed, and the
   // slabs' launches would no longer run ahead of the host)
   std::vector<Event> evs(n_slabs), gathered(n_slabs);   // (a slab that was never launched has an empty one)
 
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } res{static_cast<uint8_t*>(pool_take(20 * per_slab * n_slabs))};
-  if (!res.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  PoolBlock res;
+  if (!res.take(20 * per_slab * n_slabs)) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
   // file offset of every chunk: pinned host memory the gather kernel reads in place (a pageable source would cost one small
   // staged copy per slab on the aux stream; those, and the header patches, were ~0.5 ms of stream time per slab)
-  struct PinnedDst { int64_t* p; ~PinnedDst() { if (p) pool_give(p); } } dstp{static_cast<int64_t*>(pool_take(8 * n))};
-  if (!dstp.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  PoolBlock dstp;
+  if (!dstp.take(8 * n)) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
   DevBuf dbg;
   // EVERY way out of this function below - the errors too - first waits for both streams: the kernels in flight write their
   // per-chunk results into `res` and read `dstp` in place, and a block given back to the pool while slab s+1 is still
   // compressing could be handed to another thread's call.  (Declared after the two blocks: destroyed before them.)
-  struct Drain {
-    hipStream_t a, b, c; bool armed = true;
-    ~Drain() { if (armed) { (void)hipStreamSynchronize(a); if (b != a) (void)hipStreamSynchronize(b); if (c != a && c != b) (void)hipStreamSynchronize(c); } }
-  } drain{stream, aux, stream2};
+  StreamDrain drain(stream, aux, stream2);
   static const bool phases = tuning_mode() && std::getenv("IST_PNG_PHASES") != nullptr;      // (IST_TUNING=1 processes only)
   if (phases) { KeepLastError tolerated; (void)dbg.grow(64 * n); }
   // test knob (IST_TUNING=1 IST_PNG_FAIL_AT=<slab>): fail the layout of that slab the way a damaged result would, so that the
@@ -1564,13 +1556,11 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
     // the kernel writes its per-chunk results straight into the pinned host block (visible to the host behind the event).
     // As small device-to-host COPIES on this stream they shared the copy engine's queue with the slabs' big copies on the
     // aux stream: each big copy then took 0.9 ms instead of 0.4 and the PNG phase 6.8 ms instead of 3.4 (measured)
-    uint8_t* r = res.p + 20 * per_slab * s;
+    const ChunkResults R = chunk_results(res.at(20 * per_slab * s), per_slab, c0);      // (the kernel indexes the arrays with the global chunk number)
     DeflArgs A;
     A.canvas = static_cast<const uint8_t*>(canvas); A.pitch = pitch; A.w = w; A.h = h;
     A.slots = scratch + o_slots;
-    // (the kernel indexes the arrays with the global chunk number)
-    A.len16 = reinterpret_cast<uint32_t*>(r) - c0; A.crc = reinterpret_cast<uint32_t*>(r + 4 * per_slab) - c0;
-    A.ad_a = reinterpret_cast<uint32_t*>(r + 8 * per_slab) - c0; A.ad_b = reinterpret_cast<uint32_t*>(r + 12 * per_slab) - c0; A.ad_n = reinterpret_cast<uint32_t*>(r + 16 * per_slab) - c0;
+    A.len16 = R.len16; A.crc = R.crc; A.ad_a = R.ad_a; A.ad_b = R.ad_b; A.ad_n = R.ad_n;
     A.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); A.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
     A.rows_per_chunk = g.rows_per_chunk; A.pieces_per_row = g.pieces_per_row; A.piece_px = g.piece_px;
     A.chunk0 = static_cast<int64_t>(c0);
@@ -1602,7 +1592,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
   // ---- host, slab by slab: Adler-32 of the filtered stream, the layout of the chunks in the file, the CRC of every
   // IDAT; then the slab's gather (and its trip to the host) on the aux stream
   FileLayout lay;
-  int64_t* const dst = dstp.p;
+  int64_t* const dst = dstp.at<int64_t>();
   std::vector<std::vector<PngPatch>> slab_patches(n_slabs);     // (all of them live until the final synchronisation)
   lay.header(w, h, color, &slab_patches[0]);
   for (size_t s = 0; s < n_slabs; ++s) {
@@ -1611,14 +1601,9 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
     IST_HIP(hipEventSynchronize(evs[s]));
     tl_mark("png: compressed (event passed), slab", static_cast<long>(s));
     if (fail_at >= 0 && static_cast<size_t>(fail_at) == s) return fail(IST_E_HIP, "PNG deflate kernel returned an impossible chunk length (forced: IST_PNG_FAIL_AT)");
-    const uint8_t* r = res.p + 20 * per_slab * s;
+    const ChunkResults R = chunk_results(res.at(20 * per_slab * s), per_slab, c0);
     const int64_t slab_begin = s == 0 ? 0 : lay.pos;   // file bytes [slab_begin, pos) are final once this slab is laid out
-    {
-      const int rc = lay.slab(reinterpret_cast<const uint32_t*>(r), reinterpret_cast<const uint32_t*>(r + 4 * per_slab),
-                              reinterpret_cast<const uint32_t*>(r + 8 * per_slab), reinterpret_cast<const uint32_t*>(r + 12 * per_slab),
-                              reinterpret_cast<const uint32_t*>(r + 16 * per_slab), cn, dst + c0, 0, s + 1 == n_slabs, &slab_patches[s]);
-      if (rc) return rc;
-    }
+    { const int rc = lay.slab(R, c0, cn, dst + c0, 0, s + 1 == n_slabs, &slab_patches[s]); if (rc) return rc; }
     const int64_t pos = lay.pos;
     const std::vector<PngPatch>& patches = slab_patches[s];
     if (pos > out_cap) return fail(IST_E_INVALID, "PNG output buffer too small (see ist_png_bound)");
@@ -1631,7 +1616,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
     // went from 3.66 to 4.23 ms.)
     tl_mark("png:   host layout done, slab", static_cast<long>(s));
     hipStream_t gs = host_out ? ((s & 1) ? stream2 : stream) : aux;
-    GatherArgs G{scratch + o_slots, static_cast<uint8_t*>(out), dst, reinterpret_cast<const uint32_t*>(res.p + 20 * per_slab * s) - c0, static_cast<int64_t>(c0)};
+    GatherArgs G{scratch + o_slots, static_cast<uint8_t*>(out), dst, R.len16, static_cast<int64_t>(c0)};
     hipLaunchKernelGGL(ist_png_gather_kernel, dim3(static_cast<unsigned>(cn)), dim3(256), 0, gs, G);
     IST_HIP(hipGetLastError());
     tl_mark("png:   gather launched, slab", static_cast<long>(s));
@@ -1671,7 +1656,7 @@ int png_encode_device_deflate(ist_ctx* ctx, const PngForm& form, const void* can
   if (aux != stream) IST_HIP(hipStreamSynchronize(stream));
   if (stream2 != stream) IST_HIP(hipStreamSynchronize(stream2));
   tl_mark("png: encoder streams idle");
-  drain.armed = false;                                 // the streams are idle
+  drain.disarm();                                      // the streams are idle
   if (dbg.p) {
     std::vector<unsigned long long> hdbg(8 * n);
     (void)hipMemcpy(hdbg.data(), dbg.p, 64 * n, hipMemcpyDeviceToHost);
@@ -1712,13 +1697,12 @@ int png_encode_batch_deflate(ist_ctx* ctx, const PngForm& form, std::vector<PngB
   }
   if (begin[nf] > 2147483647ll) return fail(IST_E_OUTPUT_SIZE, "batch too large for one PNG launch");
   const size_t n = static_cast<size_t>(begin[nf]);
-  const CrcTables& T = defl_tables().T;
-  const std::vector<uint32_t>& xpow = defl_tables().xpow;
+  const DeflTables& tables = defl_tables();
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   // device: tables | per-file jobs | chunk_begin | slots;  pinned host: per-chunk results [len16 | crc | ad_a | ad_b | ad_n] |
   // per-chunk destination addresses (read in place by the gather) | the jobs + chunk_begin image that goes up
   // (adaptive: row_begin goes up with the jobs; behind it the table of row types, which only kernels write)
-  const size_t o_T = 0, o_pow = o_T + up(sizeof T), o_jobs = o_pow + up(4 * xpow.size()), o_begin = o_jobs + up(sizeof(DeflJob) * nf),
+  const size_t o_T = 0, o_pow = o_T + up(sizeof tables.T), o_jobs = o_pow + up(4 * tables.xpow.size()), o_begin = o_jobs + up(sizeof(DeflJob) * nf),
                o_rows = o_begin + up(8 * (nf + 1)), o_ftab = o_rows + (adaptive ? up(8 * (nf + 1)) : 0),
                o_slots = o_ftab + (adaptive ? up(static_cast<size_t>(row_begin[nf])) : 0), total_scratch = o_slots + n * SLOT;
   const size_t h_res = 0, h_dst = up(20 * n), h_jobs = h_dst + up(8 * n), h_total = h_jobs + (o_ftab - o_jobs);
@@ -1729,28 +1713,27 @@ int png_encode_batch_deflate(ist_ctx* ctx, const PngForm& form, std::vector<PngB
     if (rc) return rc;
     scratch = static_cast<uint8_t*>(p);
   }
-  struct Pinned { uint8_t* p; ~Pinned() { if (p) pool_give(p); } } pin{static_cast<uint8_t*>(pool_take(h_total))};
-  if (!pin.p) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
+  PoolBlock pin;
+  if (!pin.take(h_total)) return fail(IST_E_NOMEM, "out of pinned host memory for the PNG encoder");
   // every way out below waits for the stream first: the kernels write `pin` and read it in place (declared after it: runs first)
-  struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{stream};
-  DeflJob* hj = reinterpret_cast<DeflJob*>(pin.p + h_jobs);
-  int64_t* hb = reinterpret_cast<int64_t*>(pin.p + h_jobs + (o_begin - o_jobs));
+  StreamDrain drain(stream);
+  DeflJob* hj = pin.at<DeflJob>(h_jobs);
+  int64_t* hb = pin.at<int64_t>(h_jobs + (o_begin - o_jobs));
   for (size_t k = 0; k < nf; ++k) {
     const PngBatchFile& f = files[k];
     hj[k] = DeflJob{static_cast<const uint8_t*>(f.canvas), f.pitch, f.w, f.h, grid[k].rows_per_chunk, grid[k].pieces_per_row, grid[k].piece_px, 0};
   }
   std::memcpy(hb, begin.data(), 8 * (nf + 1));
-  if (adaptive) std::memcpy(pin.p + h_jobs + (o_rows - o_jobs), row_begin.data(), 8 * (nf + 1));
-  IST_HIP(hipMemcpyAsync(scratch + o_T, &T, sizeof T, hipMemcpyHostToDevice, stream));
-  IST_HIP(hipMemcpyAsync(scratch + o_pow, xpow.data(), 4 * xpow.size(), hipMemcpyHostToDevice, stream));
-  IST_HIP(hipMemcpyAsync(scratch + o_jobs, pin.p + h_jobs, o_ftab - o_jobs, hipMemcpyHostToDevice, stream));
-  uint32_t* res = reinterpret_cast<uint32_t*>(pin.p + h_res);
+  if (adaptive) std::memcpy(pin.at(h_jobs + (o_rows - o_jobs)), row_begin.data(), 8 * (nf + 1));
+  { const int rc = upload_tables(scratch + o_T, scratch + o_pow, stream); if (rc) return rc; }
+  IST_HIP(hipMemcpyAsync(scratch + o_jobs, pin.at(h_jobs), o_ftab - o_jobs, hipMemcpyHostToDevice, stream));
+  const ChunkResults R = chunk_results(pin.at(h_res), n, 0);
   DeflBatchArgs B;
   B.jobs = reinterpret_cast<const DeflJob*>(scratch + o_jobs);
   B.chunk_begin = reinterpret_cast<const int64_t*>(scratch + o_begin);
   B.n_files = static_cast<int32_t>(nf);
   B.slots = scratch + o_slots;
-  B.len16 = res; B.crc = res + n; B.ad_a = res + 2 * n; B.ad_b = res + 3 * n; B.ad_n = res + 4 * n;
+  B.len16 = R.len16; B.crc = R.crc; B.ad_a = R.ad_a; B.ad_b = R.ad_b; B.ad_n = R.ad_n;
   B.tables = reinterpret_cast<const uint32_t*>(scratch + o_T); B.xpow16 = reinterpret_cast<const uint32_t*>(scratch + o_pow);
   const int64_t* d_rows = nullptr;
   uint8_t* ftab = nullptr;
@@ -1772,27 +1755,26 @@ int png_encode_batch_deflate(ist_ctx* ctx, const PngForm& form, std::vector<PngB
   count_png_batch_launch();
   IST_HIP(hipStreamSynchronize(stream));
   // ---- host: each file laid out as one slab
-  int64_t* dst = reinterpret_cast<int64_t*>(pin.p + h_dst);
+  int64_t* dst = pin.at<int64_t>(h_dst);
   for (size_t k = 0; k < nf; ++k) {
     PngBatchFile& f = files[k];
     const size_t c0 = static_cast<size_t>(begin[k]), cn = static_cast<size_t>(begin[k + 1] - begin[k]);
     FileLayout lay;
     f.patches.clear();
     lay.header(f.w, f.h, color, &f.patches);
-    const int rc = lay.slab(res + c0, res + n + c0, res + 2 * n + c0, res + 3 * n + c0, res + 4 * n + c0, cn, dst + c0,
-                            static_cast<int64_t>(reinterpret_cast<uintptr_t>(f.out)), true, &f.patches);
+    const int rc = lay.slab(R, c0, cn, dst + c0, static_cast<int64_t>(reinterpret_cast<uintptr_t>(f.out)), true, &f.patches);
     if (rc) { const std::string why = g_last_error; return fail(rc, "file " + std::to_string(k) + ": " + why); }
     if (lay.pos > f.cap) return fail(IST_E_INVALID, "file " + std::to_string(k) + ": PNG output buffer too small (see ist_png_bound)");
     f.len = lay.pos;
   }
-  GatherBatchArgs G{scratch + o_slots, reinterpret_cast<const uint64_t*>(dst), res};
+  GatherBatchArgs G{scratch + o_slots, reinterpret_cast<const uint64_t*>(dst), R.len16};
   hipLaunchKernelGGL(ist_png_gather_batch_kernel, dim3(static_cast<unsigned>(n)), dim3(256), 0, stream, G);
   IST_HIP(hipGetLastError());
   if (!host_patches)
     for (const PngBatchFile& f : files)
       for (const PngPatch& pt : f.patches) IST_HIP(hipMemcpyAsync(f.out + pt.at, pt.b, static_cast<size_t>(pt.n), hipMemcpyHostToDevice, stream));
   IST_HIP(hipStreamSynchronize(stream));
-  drain.armed = false;
+  drain.disarm();
   return IST_OK;
 }
 
